@@ -12,8 +12,14 @@ all-reduce per step, inside the timed region:
   weak   (default)            every rank traces --rays (1e8) rays: N x 1e8 in total
   strong (--total-rays R)     R rays in total, R/N per rank (config C3: R = 1e9)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what
+the headline figure does not need (N = 1): a fresh point cloud traced with its build inside
+the timer, the CPU baseline with the parity sample against the oracle, and the other
+BASELINE workloads as `secondary`.  `--dump-outputs DIR` writes what the last timed step
+handed its caller (the flux and the TraceInfo counters) as DIR/<name>.npy.
 
 `--gpus N` with N > 1 and no RANK in the environment starts the N ranks itself
 (torch.distributed.run as a child process, before anything touches the GPU).
@@ -321,6 +327,34 @@ def secondary_failures(sec):
     return bad
 
 
+DUMP_MAX_ELEMS = 2 << 20   # flux elements dumped: at most 16 MB of float64 flux + 16 MB of sample index
+
+
+def step_outputs(tr, shard, info, counters, world):
+    """What the last timed step handed its caller, as float arrays: N = 1 the float flux in the host's TracingData and
+    the TraceInfo counters; N > 1 the all-reduced int64 accumulators as float64 flux and the all-reduced counters."""
+    if world == 1:
+        flux = np.asarray(tr.getLocalData().getVectorData("flux"), dtype=np.float32)
+        cnt = [int(getattr(info, k)) for k in COUNTER_NAMES]
+    else:
+        from viennaray_amd import distributed as vd
+        flux = vd.accumulators_to_flux(shard.acc)
+        cnt = [counters[k] for k in COUNTER_NAMES]
+    out = {"trace_info": np.asarray(cnt, dtype=np.float64)}
+    if flux.size > DUMP_MAX_ELEMS:   # a fixed, seeded sample of the primitives (the same for every run of one --grid)
+        idx = np.sort(np.random.default_rng(12345).choice(flux.size, DUMP_MAX_ELEMS, replace=False))
+        out["flux_sample_index"] = idx.astype(np.float64)
+        flux = flux[idx]
+    out["flux"] = flux
+    return out
+
+
+def dump_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def emit(out):
     """Print THE json line; return the exit code: 0, or 3 when a parity check of the line failed (headline sample or any
     secondary) — after the line, so the record stays intact."""
@@ -350,6 +384,10 @@ def main():
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the non-headline workloads")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
+    ap.add_argument("--full", action="store_true",
+                    help="also the fresh-cloud build timing, the CPU baseline + parity sample and the other BASELINE workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's flux and counters as DIR/<name>.npy")
     ap.add_argument("--stub-shard", action="store_true",
                     help="CPU rehearsal of the multi-rank path (tests): a deterministic stand-in shard, gloo")
     ap.add_argument("--stub-secondary-error", action="store_true",
@@ -358,6 +396,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if "RANK" not in os.environ and args.gpus > 1:
         # the driver's command shape `python bench.py --gpus N ...`: start the ranks ourselves,
         # as children, before this process initialises the GPU
@@ -444,6 +484,8 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(tr, shard, info, cnts, world))
 
     # per-rank spread of the step (outside the timed region): a measured N > 1 curve must be attributable
     per_rank = vd.rank_report([rank, np.mean(trace_ms) if trace_ms else 0.0, np.mean(gen_ms) if gen_ms else 0.0,
@@ -505,7 +547,7 @@ def main():
                 "per_rank": [dict(zip(cols, [int(r[0])] + [round(v, 4) for v in r[1:6]] + [int(r[6])])) for r in per_rank],
                 "note": "allreduce_ms: HIP events round the two collectives of a step (int64 flux + counters) on this rank; "
                         "a rank that finishes its shard early waits inside the collective for the slowest one"}
-        if world == 1:
+        if world == 1 and args.full:
             from oracle import pyoracle as po  # the checker / CPU baseline only (never the product path)
             threads = min(po.max_threads(), host_cpu_share())
             # ---- a fresh point cloud in a live context: setGeometry + BVH/neighbourhood build + trace
@@ -754,6 +796,9 @@ def stub_main(args, rank, world, total_rays):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     exit_code = 0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"flux": vd.accumulators_to_flux(acc),
+                                         "trace_info": np.asarray([counters[k] for k in COUNTER_NAMES], dtype=np.float64)})
     if rank == 0:
         out = ({"metric": "stub", "value": total_rays * args.steps / elapsed / 1e6, "unit": "Mrays/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -767,7 +812,7 @@ def stub_main(args, rank, world, total_rays):
                                         "trace_ms_max": round(max(r[1] for r in per_rank), 4),
                                         "per_rank": [dict(rank=int(r[0]), trace_ms=round(r[1], 4), allreduce_ms=round(r[4], 4),
                                                           step_wall_ms=round(r[5], 4), rays=int(r[6])) for r in per_rank]}})
-        if args.stub_secondary_error:
+        if args.stub_secondary_error and args.full:
             out["secondary"] = [dict(name="stub_ok", counter_diff={"geometryHits": 0}, flux_l2_rel_err=0.0),
                                 dict(name="stub_broken", error="injected failure")]
         exit_code = emit(out)

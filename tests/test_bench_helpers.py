@@ -93,3 +93,31 @@ def test_a_failing_secondary_shows_in_the_exit_code():
     bad = b.secondary_failures([ok, dict(name="C5p", error="boom"), dict(name="C2", counter_diff={"geometryHits": 1}, flux_l2_rel_err=0.0),
                                 dict(name="C1", counter_diff={"geometryHits": 0}, flux_l2_rel_err=2e-4)])
     assert len(bad) == 3 and bad[0].startswith("C5p") and "counters differ" in bad[1] and "flux" in bad[2]
+
+
+def test_step_outputs_sample_a_large_flux_the_same_way_every_time():
+    """--dump-outputs stays under 64 MB: a flux larger than DUMP_MAX_ELEMS is dumped as a fixed, seeded sample with its
+    primitive indices; a smaller one whole, as the caller received it."""
+    import numpy as np
+    b = _bench()
+
+    class Info:
+        pass
+    info = Info()
+    for i, k in enumerate(b.COUNTER_NAMES):
+        setattr(info, k, 10 + i)
+
+    class FakeTracer:
+        def __init__(self, n): self.flux = np.arange(n, dtype=np.float32)
+        def getLocalData(self): return self
+        def getVectorData(self, key): return self.flux
+
+    small = b.step_outputs(FakeTracer(1000), None, info, None, 1)
+    assert sorted(small) == ["flux", "trace_info"] and small["flux"].dtype == np.float32
+    assert np.array_equal(small["flux"], np.arange(1000)) and small["trace_info"].tolist() == list(range(10, 16))
+    n = b.DUMP_MAX_ELEMS + 12345
+    big = [b.step_outputs(FakeTracer(n), None, info, None, 1) for _ in range(2)]
+    assert big[0]["flux"].size == b.DUMP_MAX_ELEMS and big[0]["flux_sample_index"].dtype == np.float64
+    assert np.array_equal(big[0]["flux"], big[0]["flux_sample_index"].astype(np.float32))
+    assert all(np.array_equal(big[0][k], big[1][k]) for k in big[0])
+    assert sum(a.nbytes for a in big[0].values()) <= 64 << 20

@@ -75,10 +75,29 @@ def test_a_failing_secondary_fails_the_run_after_the_json_line():
     JSON line printed and intact (round-3 verdict: a broken BASELINE config used to leave a green record)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--stub-shard",
-                        "--grid", "20", "--rays", "1000", "--stub-secondary-error"], env=env, capture_output=True, text=True, timeout=300)
+                        "--grid", "20", "--rays", "1000", "--stub-secondary-error", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 3, (p.returncode, p.stderr[-500:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["parity_failed"] == ["stub_broken: injected failure"]
     assert "parity check failed" in p.stderr
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_dump_outputs_writes_the_last_steps_arrays(gpus, tmp_path):
+    """`--dump-outputs DIR`: the last timed step's flux and counters as float .npy files, the same for two runs with the
+    same arguments (rehearsed with the stand-in shard)."""
+    args = ["--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--stub-shard", "--grid", "50", "--rays", "10007"]
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = _run(args + ["--dump-outputs", str(d)])
+        assert out["steps"] == 2
+        runs.append({f.stem: np.load(d / f.name) for f in sorted(d.iterdir())})
+    assert sorted(runs[0]) == ["flux", "trace_info"]
+    for name, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64)
+        assert np.array_equal(a, runs[1][name])
+    assert runs[0]["flux"].shape == (2500,) and runs[0]["flux"].sum() == 10007 * gpus
+    assert runs[0]["trace_info"][0] == 10007 * gpus    # totalRaysTraced

@@ -460,7 +460,7 @@ def test_gpu_shard_driver_matches_plain_apply():
                                                 ("disk2D", "trenchGrid2D.dat", 500, 119500),
                                                 ("triangle3D", "trenchMesh.dat", 20, 256000),
                                                 ("triangle2D", "lineMesh.dat", 400, 102400)])
-def test_ported_reference_example_runs(name, data, rpp, rays):
+def test_ported_reference_example_runs(name, data, rpp, rays, tmp_path):
     """The reference's four example programs, ported to the C++ façade (same API, other include
     path), run on the fixture copies of the reference's data files."""
     import os
@@ -469,9 +469,8 @@ def test_ported_reference_example_runs(name, data, rpp, rays):
     exe = os.path.join(root, "examples", name, name)
     if not os.path.exists(exe):
         subprocess.check_call(["make", "-C", os.path.join(root, "examples")])
-    cwd = os.path.join(root, "gpurun_out") if os.path.isdir(os.path.join(root, "gpurun_out")) else "/tmp"
     out = subprocess.run([exe, os.path.join(root, "tests", "golden", "data", data), str(rpp)],
-                         capture_output=True, text=True, cwd=cwd, timeout=300)
+                         capture_output=True, text=True, cwd=tmp_path, timeout=300)   # (the examples write their .vtk / .vtp there)
     assert out.returncode == 0, out.stdout + out.stderr
     assert f"rays {rays}" in out.stdout, out.stdout
     mean = float(out.stdout.split("mean normalised flux")[1].split()[0])
