@@ -992,6 +992,14 @@ public:
       check(vr_register_particle_model(ctx_, name.c_str(), source.c_str(), numData, needsFull ? VR_MODEL_NEEDS_FULL : 0, &kind));
     return kind;
   }
+  /// ... a model with per-ray state: numState = VrUserModel::kStateWords (1 .. 4; init / surface_reflection / collide
+  /// hooks, vr_register_particle_model_ex; implies needsFull).  SourceRandom only.
+  int registerParticleModel(const std::string &name, const std::string &source, int numData, int numState) {
+    int32_t kind = -1;
+    if (ctx_)
+      check(vr_register_particle_model_ex(ctx_, name.c_str(), source.c_str(), numData, numState, 0, &kind));
+    return kind;
+  }
   /// NOT in the reference's CPU Trace (its gpu::Trace keeps a particle list, gpu/raygTrace.hpp:163-248): several
   /// particles traced in ONE apply() — the same seed for all, one generator pass per source distribution;
   /// getLocalData() holds particle 0's data labels, then particle 1's, ...; getRayTraceInfo() their summed counters.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times one apply() of a named fixture geometry on the GPU.
-usage: tools/case_bench.py <trench3d|trench2d|mesh|plane100|ripple<n>[a<amp>]> <sticking> <raysPerPoint> [repeat]
+usage: tools/case_bench.py <trench3d|trench2d|mesh|plane<n>|ripple<n>[a<amp>]> <sticking> <raysPerPoint> [repeat]
        tools/case_bench.py <C4|C5p|C5r> [repeat]      (SURVEY.md 8d configs, 1e8 rays)"""
 import sys, os, time
 import numpy as np
@@ -50,18 +50,43 @@ elif case.startswith("ripple"):   # ripple<n>[a<amp>]: an n x n rippled sheet of
     p = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
     t = vr.TraceDisk(3); t.setGeometry(p, nrm.astype(np.float32), 1.0)
     t.setBoundaryConditions([vr.BoundaryCondition.PERIODIC_BOUNDARY] * 3)
-elif case == "plane100":
-    p, n = vr.io.plane_grid(100, 1.0)
+elif case.startswith("plane") and case[5:].isdigit():   # plane<n>: an n x n plane of disks (plane1000: 10^6 disks)
+    p, n = vr.io.plane_grid(int(case[5:]), 1.0)
     t = vr.TraceDisk(3); t.setGeometry(p, n, 1.0); t.setBoundaryConditions([vr.BoundaryCondition.PERIODIC_BOUNDARY] * 3)
 else:
     gd, p, n = trench3d()
     t = vr.TraceDisk(3); t.setGeometry(p, n, gd); t.setBoundaryConditions([vr.BoundaryCondition.PERIODIC_BOUNDARY] * 3)
-# VR_CASE_PARTICLE=coned|cosine2: the same workload through the extended kernel (device particle registry)
+# VR_CASE_PARTICLE=coned|cosine2|state1|nostate: the same workload through the extended kernel (device particle registry)
 _pk = os.environ.get("VR_CASE_PARTICLE", "")
 if _pk == "coned":
     particle = vr.ConedCosineParticle(sticking, 1.0, 0.8, "flux")
 elif _pk == "cosine2":
     particle = vr.DiffuseCosineParticle(sticking, "flux", "cosine")
+elif _pk in ("state1", "nostate"):
+    # the cost of per-ray state: a stateful wrapper of ModelDiffuse (one state word, init without draws) against the same
+    # model registered without state — both in the P_EXT_FULL kernels of a run-time module
+    if _pk == "nostate":
+        src, ns = "struct VrUserModel : ModelDiffuse { static constexpr bool kNeedsFull = true; };", 0
+    else:
+        src, ns = """struct VrUserModel : ModelDiffuse {
+  static constexpr bool kNeedsFull = true;
+  static constexpr int kStateWords = 1;
+  __device__ static void init(const ModelCtx &, RayState &s, Rng &, unsigned &) { s.v[0] = 0.f; }
+  template <int D>
+  __device__ static Reflection surface_reflection(const ModelCtx &m, RayState &, float w, const V3 &rayDir, const V3 &n,
+                                                  unsigned primID, int, float base, Rng &rng, unsigned &t2) {
+    Reflection r{base, rayDir};
+    if (w - w * base > 0.f)
+      r.dir = ModelDiffuse::reflect<D>(m, rayDir, n, rng, t2);
+    return r;
+  }
+  template <class Credit>
+  __device__ static void collide(const ModelCtx &m, const RayState &, float w, const V3 &d, const V3 &n, unsigned primID,
+                                 int, Credit &&credit) {
+    ModelDiffuse::collide(m, w, d, n, primID, credit);
+  }
+};""", 1
+    particle = vr.UserModelParticle(t.registerParticleModel(src, numData=1, needsFull=True, name=_pk, numState=ns), sticking, ["flux"])
 t.setParticleType(particle if particle is not None else vr.DiffuseParticle(sticking, "flux"))
 if fixed:
     t.setNumberOfRaysFixed(fixed)

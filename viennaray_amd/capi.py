@@ -60,6 +60,7 @@ SIGNATURES = {
     "vr_set_particle": (C.c_int, [_vp, C.POINTER(ParticlePOD)]),
     "vr_set_particles": (C.c_int, [_vp, C.POINTER(ParticlePOD), C.c_uint32]),
     "vr_register_particle_model": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, _i32p]),
+    "vr_register_particle_model_ex": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, _i32p]),
     "vr_set_global_data": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
     "vr_set_global_scalars": (C.c_int, [_vp, _fp, C.c_uint32]),
     "vr_get_particle_trace_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(TraceInfoPOD)]),
@@ -106,6 +107,7 @@ SIGNATURES = {
     "vr_debug_intersect": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, _i32p, _u32p, _fp]),
     "vr_debug_process_hit": (C.c_int, [_vp, _fp, _fp, _fp, _u32p, C.c_uint32, _fp, _fp, _i32p]),
     "vr_debug_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp]),
+    "vr_debug_model_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp, _u32p]),
     "vr_debug_rng_outputs": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
     "vr_debug_issue_rate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_double)]),
     "vr_debug_bvh_stats": (C.c_int, [_vp, _u32p]),

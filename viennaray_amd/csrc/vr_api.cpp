@@ -86,7 +86,9 @@ struct UserModel {
   hipModule_t module = nullptr;
   int numData = 1;
   bool needsFull = false;
+  int numState = 0;                     // kStateWords of a stateful model (0: stateless)
   std::map<int, hipFunction_t> kernels; // key: D * 100 + geo * 10 + mode
+  hipFunction_t gen[2] = {nullptr, nullptr}; // a stateful model's generator (gen_state_kernel), 2-D / 3-D
 };
 
 // the prepared launch of one particle of a multi-particle apply()
@@ -97,6 +99,7 @@ struct ParticleLaunch {
   bool absorb = false;
   uint32_t numData = 1, dataBase = 0;
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
+  hipFunction_t userGen = nullptr;    // ... and a stateful model's generator (nullptr: the library's)
   float *primSticking = nullptr; // owned (hipMalloc): this particle's per-primitive sticking, leaf order
   bool relief = false;           // a second launch (looseMode) traces the loose bins
   int looseMode = 0;
@@ -136,6 +139,9 @@ struct vr_context {
   float particleParams[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int userModel = -1;             // index into userModels when the active particle is a run-time model
   hipFunction_t userKernel = nullptr; // ... and the kernel vr_apply_prepare picked from its module
+  hipFunction_t userGen = nullptr;    // ... and the generator of a stateful model (nullptr: the library's generators)
+  DevBuf<float> dRayState;            // a stateful model's per-ray state of one batch (the frame's VR_F_STATE_*), float4 per ray
+  DevBuf<int32_t> dPrimMaterial;      // material id per original primitive for a stateful model (VR_F_MAT_*)
   std::vector<UserModel> userModels;
   bool particleDirty = true;      // the sticking map needs recomputing
   std::vector<ParticleSpec> specs;      // vr_set_particles: > 1 entries = a multi-particle apply
@@ -580,17 +586,27 @@ static std::string compiler_identity(const std::string &hipcc) {
 // one of the built-in models — and the library compiles the extended trace kernels around it for gfx950 (hipcc --genco,
 // cached by content) and loads them.  The returned kind goes into vr_particle::kind like a built-in one.
 int vr_register_particle_model(vr_context *c, const char *name, const char *source, int numData, int flags, int32_t *kindOut) {
+  return vr_register_particle_model_ex(c, name, source, numData, 0, flags, kindOut);
+}
+
+// ... with per-ray state: numState = VrUserModel::kStateWords (0 .. 4; > 0: a stateful model, vr_particles.hpp — it runs in
+// the P_EXT_FULL kernels, so VR_MODEL_NEEDS_FULL is implied, and its module holds a generator of its own)
+int vr_register_particle_model_ex(vr_context *c, const char *name, const char *source, int numData, int numState, int flags,
+                                  int32_t *kindOut) {
   if (!c || !source || !kindOut || numData < 1 || numData > VR_MAX_LABELS)
     return fail(c, VR_E_INVALID, "vr_register_particle_model: bad argument (1 .. 4 data labels)");
+  if (numState < 0 || numState > VR_MAX_STATE_WORDS)
+    return fail(c, VR_E_INVALID, "vr_register_particle_model_ex: numState (the model's kStateWords) must be 0 .. 4");
   VR_HIP(c, hipSetDevice(c->device));
   const std::string csrc = csrc_dir();
-  const bool full = (flags & VR_MODEL_NEEDS_FULL) != 0;
+  const bool full = (flags & VR_MODEL_NEEDS_FULL) != 0 || numState > 0;
   const std::string hipcc = std::getenv("VR_HIPCC") ? std::getenv("VR_HIPCC") : "/opt/rocm/bin/hipcc";
   const std::string ccFlags = " --genco --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -Wno-unused-function";
   uint64_t h = 1469598103934665603ull;
   h = fnv1a(h, source, std::strlen(source));
   h = fnv1a(h, &numData, sizeof(numData));
   h = fnv1a(h, &full, sizeof(full));
+  h = fnv1a(h, &numState, sizeof(numState));
   std::string cksums;
   for (const char *fn : {"vr_trace.hip", "vr_device.hpp", "vr_particles.hpp", "vr_types.hpp", "vr_libm.hpp", "vr_kernels.hpp"}) {
     std::string text;
@@ -644,7 +660,7 @@ int vr_register_particle_model(vr_context *c, const char *name, const char *sour
     {
       std::ofstream f(mine + ".hip");
       f << "// generated by vr_register_particle_model\n#define VR_USER_MODULE 1\n#define VR_USER_NUM_DATA " << numData
-        << "\n#define VR_USER_MODEL_FILE \"" << mine << "_model.hpp\"\n#include <cstddef>\n#include \"" << csrc << "/vr_trace.hip\"\n"
+        << "\n#define VR_USER_NUM_STATE " << numState << "\n#define VR_USER_MODEL_FILE \"" << mine << "_model.hpp\"\n#include <cstddef>\n#include \"" << csrc << "/vr_trace.hip\"\n"
         << "static_assert(vr::VrUserModel::kNeedsFull == " << (full ? "true" : "false")
         << ", \"kNeedsFull differs from the VR_MODEL_NEEDS_FULL flag given at registration\");\n"
         // the launch parameters and the LDS frame as THIS library lays them out
@@ -689,7 +705,17 @@ int vr_register_particle_model(vr_context *c, const char *name, const char *sour
   um.name = name ? name : "";
   um.numData = numData;
   um.needsFull = full;
+  um.numState = numState;
   VR_HIP(c, hipModuleLoad(&um.module, hsaco.c_str()));
+  if (numState > 0)
+    for (int D = 2; D <= 3; ++D) {
+      char sym[128];
+      std::snprintf(sym, sizeof(sym), "_ZN2vr16gen_state_kernelILi%dENS_11VrUserModelEEEvNS_11TraceParamsE", D);
+      if (hipModuleGetFunction(&um.gen[D - 2], um.module, sym) != hipSuccess || !um.gen[D - 2]) {
+        (void)hipModuleUnload(um.module);
+        return fail(c, VR_E_STATE, (std::string("vr_register_particle_model: kernel missing from the code object: ") + sym).c_str());
+      }
+    }
   const int P = full ? (int)P_EXT_FULL : (int)P_EXT;
   for (int D = 2; D <= 3; ++D)
     for (int geo = 0; geo <= 1; ++geo)
@@ -1356,7 +1382,11 @@ static int prepare_one(vr_context *c) {
       return fail(c, VR_E_INVALID, "this particle model was registered without VR_MODEL_NEEDS_FULL: its code object has no "
                                    "kernel with WDIST crediting / mean-free-path scattering");
     extFull = um.needsFull;
+    if (um.numState > 0 && (!c->gridPoints.empty() || !c->hostOrg.empty()))
+      return fail(c, VR_E_INVALID, "a stateful particle model (numState > 0) runs its init on the device before the source "
+                                   "sample: SourceRandom only (plain or with a primary direction), not SourceGrid or a host source");
   }
+  const bool stateful = c->userModel >= 0 && c->userModels[c->userModel].numState > 0;
   c->kernelParticle = extended ? (extFull ? (int)P_EXT_FULL : (int)P_EXT) : c->particleKind;
   // a scene of a few hundred primitives goes into LDS as a whole (MODE 4: the general kernel — also for
   // absorbing particles — of whatever particle): pair nodes, records, neighbourhood, accumulators (one plane
@@ -1553,10 +1583,13 @@ static int prepare_one(vr_context *c) {
     c->slotStride = slots;
     // 32-byte records for every particle (vr_types.hpp); a non-absorbing particle under a source whose origin plane or
     // draw count varies (tilted, grid, host rays) adds 16 bytes per ray in a side array
-    c->recExtra = !c->absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || !c->hostOrg.empty());
+    // (a stateful model's init draws before the source sample: its draw count varies too)
+    c->recExtra = !c->absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || !c->hostOrg.empty() || stateful);
     const size_t recFloats = 8;
     if (c->recExtra)
       VR_HIP(c, c->dRecExtra.ensure_grow((size_t)cap * 4));
+    if (stateful) // (the state of every ray of a batch, float4 per ray; room for vr_reserve_rays' largest batch)
+      VR_HIP(c, c->dRayState.ensure_grow((size_t)std::max<uint64_t>(cap, std::min<uint64_t>(c->reserveRays, 1ull << 27)) * 4));
     size_t slotsWant = slots, binsWant = cntWords;
     if (c->reserveRays > span) { // vr_reserve_rays: room for the largest apply() announced
       TraceParams q = p;
@@ -1612,8 +1645,12 @@ static int prepare_one(vr_context *c) {
     }
     int blocks = 1;
     c->userKernel = nullptr;
+    c->userGen = nullptr;
     if (c->userModel >= 0) { // the kernel of the model's own code object
       const UserModel &um = c->userModels[c->userModel];
+      if (stateful && (c->absorb || (c->traceMode != 0 && c->traceMode != 4)))
+        return fail(c, VR_E_STATE, "stateful particle model: only the general kernels (MODE 0 / 4) carry the state");
+      c->userGen = stateful ? um.gen[D == 3 ? 1 : 0] : nullptr;
       auto it = um.kernels.find(D * 100 + c->geo.geo * 10 + c->traceMode);
       if (it == um.kernels.end())
         return fail(c, VR_E_STATE, "run-time particle model: no kernel for this geometry / mode in its code object");
@@ -1656,8 +1693,8 @@ static int prepare_one(vr_context *c) {
     size_t waves = 0;
     if (!c->absorb)
       waves = (size_t)std::max(c->grid, c->looseGrid) * (VR_BLOCK / 64);
-    if (c->usePrimaryDirection || !c->hostOrg.empty())
-      waves = std::max(waves, (size_t)c->numCUs * 8u * (VR_BLOCK / 64)); // launch_gen's grid bound
+    if (c->usePrimaryDirection || !c->hostOrg.empty() || stateful)
+      waves = std::max(waves, (size_t)c->numCUs * 8u * (VR_BLOCK / 64)); // launch_gen's grid bound (gen_state_kernel's too)
     if (waves > c->scratchWaves) {
       VR_HIP(c, c->dScratch.ensure(waves * 312u * 64u));
       c->scratchWaves = waves;
@@ -1733,6 +1770,17 @@ static int prepare_one(vr_context *c) {
   p.workCounter = c->dWorkQ.p;
   p.numQueues = VR_QUEUES;
   p.recExtra = c->recExtra ? c->dRecExtra.p : nullptr;
+  // a stateful model: its state buffer and the material ids of its hooks (the caller's id of the original primitive) go
+  // into the launch frame (VR_F_STATE_*, VR_F_MAT_*).  (Both are sized by what every particle of an apply shares — rays
+  // per batch, primitives — so a later particle's prepare does not move them.)
+  const int32_t *dMaterial = nullptr;
+  if (stateful && !c->geo.materialIds.empty()) {
+    std::vector<int32_t> ids(N, 0);
+    std::copy(c->geo.materialIds.begin(), c->geo.materialIds.begin() + std::min<size_t>(N, c->geo.materialIds.size()), ids.begin());
+    VR_HIP(c, c->dPrimMaterial.ensure(N));
+    VR_HIP(c, hipMemcpy(c->dPrimMaterial.p, ids.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    dMaterial = c->dPrimMaterial.p;
+  }
   p.spillRec = nullptr;
   p.spillCount = nullptr;
   if (c->reliefScene && c->looseMode == 7) {
@@ -1843,6 +1891,13 @@ static int prepare_one(vr_context *c) {
     f[21] = p.nbDist;
     for (int k = 22; k < VR_WALL_TABLE - 96; ++k)
       f[k] = 0.f;
+    if (stateful) { // VR_F_STATE_* / VR_F_MAT_*
+      const uint64_t sa = (uint64_t)(uintptr_t)c->dRayState.p, ma = (uint64_t)(uintptr_t)dMaterial;
+      f[VR_F_STATE_LO - 96] = bits((int32_t)(uint32_t)(sa & 0xFFFFFFFFull));
+      f[VR_F_STATE_HI - 96] = bits((int32_t)(uint32_t)(sa >> 32));
+      f[VR_F_MAT_LO - 96] = bits((int32_t)(uint32_t)(ma & 0xFFFFFFFFull));
+      f[VR_F_MAT_HI - 96] = bits((int32_t)(uint32_t)(ma >> 32));
+    }
     if (c->reliefScene) { // the relief field's fine tiles (VR_F_RF_*: relief_clip, vr_device.hpp)
       const ReliefParams &q = c->rf;
       f[32] = q.lo1;
@@ -1957,6 +2012,7 @@ struct LaunchDesc {
   int traceMode, kernelParticle;
   bool absorb;
   hipFunction_t userKernel; // a run-time model's kernel, or nullptr
+  hipFunction_t userGen;    // a stateful model's generator, or nullptr
   bool relief = false;      // flat with relief: a second launch (looseMode, looseGrid) traces the loose bins
   int looseMode = 0;
   unsigned looseGrid = 0;
@@ -2027,7 +2083,14 @@ static int run_batch(vr_context *c, const std::vector<LaunchDesc> &group, uint64
   if (rc != VR_OK)
     return rc;
   VR_HIP(c, hipEventRecord(g0, c->stream));
-  VR_HIP(c, launch_gen(pg, c->geo.D, keepRng, (unsigned)c->numCUs * 8u, c->stream));
+  if (group[0].userGen) { // a stateful model: its module's generator (init, then the source sample)
+    TraceParams pk = pg;
+    void *args[] = {&pk};
+    const unsigned grid = std::min<unsigned>((count + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
+    VR_HIP(c, hipModuleLaunchKernel(group[0].userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
+  } else {
+    VR_HIP(c, launch_gen(pg, c->geo.D, keepRng, (unsigned)c->numCUs * 8u, c->stream));
+  }
   VR_HIP(c, hipEventRecord(g1, c->stream));
   ++genNo;
   for (const LaunchDesc &L : group) {
@@ -2095,14 +2158,15 @@ int vr_apply_launch(vr_context *c) {
   // same record format (with / without the RNG cursors)
   std::vector<std::vector<LaunchDesc>> groups;
   if (nPart == 1) {
-    groups.push_back({LaunchDesc{&c->params, c->grid, c->traceMode, c->kernelParticle, c->absorb, c->userKernel, c->reliefScene,
-                                 c->looseMode, c->looseGrid}});
+    groups.push_back({LaunchDesc{&c->params, c->grid, c->traceMode, c->kernelParticle, c->absorb, c->userKernel, c->userGen,
+                                 c->reliefScene, c->looseMode, c->looseGrid}});
   } else {
     for (const ParticleLaunch &L : c->launches) {
-      const LaunchDesc d{&L.params, L.grid, L.traceMode, L.kernelParticle, L.absorb, L.userKernel, L.relief, L.looseMode, L.looseGrid};
+      const LaunchDesc d{&L.params, L.grid, L.traceMode, L.kernelParticle, L.absorb, L.userKernel, L.userGen, L.relief, L.looseMode,
+                         L.looseGrid};
       bool placed = false;
-      for (auto &g : groups)
-        if (g[0].absorb == d.absorb && g[0].params->ee == d.params->ee && g[0].params->eeGrid == d.params->eeGrid &&
+      for (auto &g : groups) // (a stateful model's generator runs its own init: a generator pass of its own)
+        if (!g[0].userGen && !d.userGen && g[0].absorb == d.absorb && g[0].params->ee == d.params->ee && g[0].params->eeGrid == d.params->eeGrid &&
             g[0].relief == d.relief) { // (relief: the generator's bins are laid out differently)
           g.push_back(d);
           placed = true;
@@ -2328,6 +2392,7 @@ int vr_apply_prepare(vr_context *c) {
     L.numData = c->numData;
     L.dataBase = base;
     L.userKernel = c->userKernel;
+    L.userGen = c->userGen;
     L.relief = c->reliefScene;
     L.looseMode = c->looseMode;
     L.looseGrid = c->looseGrid;
@@ -2851,6 +2916,53 @@ int vr_debug_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint3
     dir[3 * i] = r[3];
     dir[3 * i + 1] = r[4];
     dir[3 * i + 2] = r[5];
+  }
+  dI.release();
+  return VR_OK;
+}
+
+// vr_debug_source_sample for the active STATEFUL model: its generator (init, then the source sample) for the global ray
+// indices idx[]; the first origin, direction and the engine outputs consumed before the trace (init + source)
+int vr_debug_model_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
+                                 uint32_t *draws) {
+  if (!c || !idx || !org || !dir || !draws)
+    return VR_E_INVALID;
+  if (!c->prepared) {
+    int r = vr_apply_prepare(c);
+    if (r != VR_OK)
+      return r;
+  }
+  if (c->specs.size() > 1 || !c->userGen)
+    return fail(c, VR_E_STATE, "vr_debug_model_source_sample: the active particle is not (the only) stateful model");
+  if (n > c->batchCap)
+    return fail(c, VR_E_INVALID, "vr_debug_model_source_sample: more rays than one batch holds");
+  TraceParams p = c->params;
+  p.seed = seed;
+  p.batchCount = n;
+  p.binCount = nullptr; // no binning: record i goes to slot i
+  DevBuf<unsigned long long> dI;
+  VR_HIP(c, dI.ensure(std::max<uint32_t>(n, 1)));
+  VR_HIP(c, hipMemcpy(dI.p, idx, (size_t)n * 8, hipMemcpyHostToDevice));
+  p.idxList = dI.p;
+  if (n) {
+    void *args[] = {&p};
+    const unsigned grid = std::min<unsigned>((n + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
+    VR_HIP(c, hipModuleLaunchKernel(c->userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
+  }
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  std::vector<float> A((size_t)n * 8), E((size_t)n * 4);
+  VR_HIP(c, hipMemcpy(A.data(), c->dSlotRec.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+  VR_HIP(c, hipMemcpy(E.data(), c->dRecExtra.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+  // the compact record {org[firstDir], org[secondDir], dir.x, dir.y} {dir.z, ...} + the side array {org[rayDir], k, ...}
+  const int rd = p.rayDir, fd = p.firstDir;
+  for (uint32_t i = 0; i < n; ++i) {
+    const float *a = &A[8 * (size_t)i], *e = &E[4 * (size_t)i];
+    for (int k = 0; k < 3; ++k)
+      org[3 * i + k] = k == rd ? e[0] : (k == fd ? a[0] : a[1]);
+    dir[3 * i] = a[2];
+    dir[3 * i + 1] = a[3];
+    dir[3 * i + 2] = a[4];
+    std::memcpy(&draws[i], &e[1], 4);
   }
   dI.release();
   return VR_OK;

@@ -383,7 +383,15 @@ enum { VR_F_SRC_PLANE = 96, VR_F_RAYDIR = 97, VR_F_FIRSTDIR = 98, VR_F_SECONDDIR
        VR_F_HF_NX = 124, VR_F_HF_NY = 125, VR_F_HF_PTR_LO = 126, VR_F_HF_PTR_HI = 127,
        // the relief field's fine tiles (ReliefParams; NX = 0: none): relief_clip below
        VR_F_RF_LO1 = 128, VR_F_RF_LO2 = 129, VR_F_RF_INVT = 130, VR_F_RF_TILE = 131, VR_F_RF_NX = 132, VR_F_RF_NY = 133,
-       VR_F_RF_PTR_LO = 134, VR_F_RF_PTR_HI = 135 };
+       VR_F_RF_PTR_LO = 134, VR_F_RF_PTR_HI = 135,
+       // a stateful particle model (vr_particles.hpp; read only by the kernels of a module compiled around one): the
+       // per-ray state of the batch (float4 per ray, indexed like TraceParams::recExtra) and the material id per ORIGINAL
+       // primitive (0: none set).  (Here, not in TraceParams: the library's own kernels stay exactly as they are.)
+       VR_F_STATE_LO = 136, VR_F_STATE_HI = 137, VR_F_MAT_LO = 138, VR_F_MAT_HI = 139 };
+// a device address kept as two words of the frame (lo, hi)
+__device__ __forceinline__ unsigned long long frame_addr(const float *f, int lo) {
+  return ((unsigned long long)__float_as_uint(f[lo + 1]) << 32) | __float_as_uint(f[lo]);
+}
 
 __device__ __forceinline__ void hit_walls(const TraceParams &p, const float *__restrict__ wallS, const V3 &o,
                                           const V3 &d, float tnear, HitRec &h) {

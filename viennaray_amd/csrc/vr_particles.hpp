@@ -21,6 +21,17 @@
 //   collide  : surfaceCollision (rayParticle.hpp:60-68): what one hit adds to the particle's data labels; called
 //              for the closest disk and for every overlapping neighbour with that disk's own normal and id
 //              (rayTraceKernel.hpp:284-300); credit(label, value) adds to this primitive's entry of a label
+//
+// Stateful models (kStateWords = 1 .. 4; run-time registered models only, vr_register_particle_model_ex): the reference's
+// particle keeps state of its own per ray (an ion's energy: members of the per-thread clone, rayParticle.hpp:21-81; its GPU
+// path keeps it in PerRayData, gpu/raygPerRayData.hpp:25-27).  Such a model carries a RayState of kStateWords floats
+// from the ray's birth to its end and replaces sticking / reflect / collide by
+//   init               : initNew (rayTraceKernel.hpp:131-133): once per ray, BEFORE the source sample, from the ray's engine
+//   surface_reflection : sticking AND the new direction in one call (rayTraceKernel.hpp:310), may update the state and
+//                        draw from the engine; called after the hit's collide credits, also when it returns sticking >= 1
+//   collide            : as above, with the state (read only) and the material id of the primitive; no engine draws
+// materialId is the caller's id of the ORIGINAL primitive (vr_set_material_ids; 0 when none was set).  A stateful model
+// runs in the P_EXT_FULL instantiation (kNeedsFull), on SourceRandom only (plain or with a primary direction).
 #pragma once
 #include "vr_device.hpp"
 
@@ -125,6 +136,17 @@ struct ModelCtx {
   GlobalData global;
 };
 
+// per-ray state of a stateful model: only the first kStateWords words are carried
+struct RayState {
+  float v[4];
+};
+// surfaceReflection's result (rayParticle.hpp:44-50): the sticking and the direction after the hit
+struct Reflection {
+  float sticking;
+  V3 dir;
+};
+constexpr int VR_MAX_STATE_WORDS = 4;
+
 __device__ __forceinline__ ModelCtx model_ctx(const TraceParams &p) {
   ModelCtx m;
   m.params = p.particleParams;
@@ -143,6 +165,7 @@ __device__ __forceinline__ ModelCtx model_ctx(const TraceParams &p) {
 struct ModelDiffuse {
   static constexpr int kNumData = 1;
   static constexpr bool kNeedsFull = false;
+  static constexpr int kStateWords = 0; // (> 0: a stateful model, see the top of this file)
   __device__ static float sticking(const ModelCtx &, unsigned, float base) { return base; }
   template <int D>
   __device__ static V3 reflect(const ModelCtx &, const V3 &, const V3 &n, Rng &rng, unsigned &t2) {
@@ -213,8 +236,26 @@ template <class M0, class... M> struct ModelAt<0, ModelList<M0, M...>> {
   using type = M0;
 };
 
+template <int... W> constexpr int vr_max_state_words() {
+  const int w[] = {0, W...};
+  int r = 0;
+  for (int x : w)
+    r = x > r ? x : r;
+  return r;
+}
+template <class List> struct RegistryState;
+template <class... M> struct RegistryState<ModelList<M...>> {
+  static_assert(((M::kStateWords >= 0 && M::kStateWords <= VR_MAX_STATE_WORDS) && ...), "a model has 0 .. 4 state words");
+  static_assert(((M::kStateWords == 0 || M::kNeedsFull) && ...), "a stateful model (kStateWords > 0) needs kNeedsFull = true");
+  static constexpr int words = vr_max_state_words<M::kStateWords...>();
+};
+
 struct Particles {
   static constexpr int count = Registry::size;
+
+  // the largest kStateWords of the registry: 0 in the library itself (its instantiations carry no state), the run-time
+  // model's in a module compiled around a stateful one
+  static constexpr int stateWords = RegistryState<Registry>::words;
 
   // run f(Model{}) for the model of `kind`; FULL: the instantiation that carries the models with kNeedsFull
   // (the host never sends such a kind to the lean one)
@@ -249,20 +290,68 @@ struct Particles {
   template <bool FULL>
   __device__ __forceinline__ static float sticking(int kind, const ModelCtx &m, unsigned primID, float base) {
     float s = base;
-    with<FULL>(kind, [&](auto model) { s = decltype(model)::sticking(m, primID, base); });
+    with<FULL>(kind, [&](auto model) {
+      if constexpr (decltype(model)::kStateWords == 0) // (a stateful model: surface_reflection below)
+        s = decltype(model)::sticking(m, primID, base);
+    });
     return s;
   }
   template <int D, bool FULL>
   __device__ __forceinline__ static V3 reflect(int kind, const ModelCtx &m, const V3 &rayDir, const V3 &n, Rng &rng,
                                                unsigned &t2) {
     V3 r = rayDir;
-    with<FULL>(kind, [&](auto model) { r = decltype(model)::template reflect<D>(m, rayDir, n, rng, t2); });
+    with<FULL>(kind, [&](auto model) {
+      if constexpr (decltype(model)::kStateWords == 0)
+        r = decltype(model)::template reflect<D>(m, rayDir, n, rng, t2);
+    });
     return r;
   }
   template <bool FULL, class Credit>
   __device__ __forceinline__ static void collide(int kind, const ModelCtx &m, float w, const V3 &rayDir, const V3 &n,
                                                  unsigned primID, Credit &&credit) {
-    with<FULL>(kind, [&](auto model) { decltype(model)::collide(m, w, rayDir, n, primID, credit); });
+    with<FULL>(kind, [&](auto model) {
+      if constexpr (decltype(model)::kStateWords == 0)
+        decltype(model)::collide(m, w, rayDir, n, primID, credit);
+    });
+  }
+
+  // ---- the hooks of the kernels compiled around a stateful model (stateWords > 0); a stateless model of the same
+  //      registry keeps its own semantics through them ----
+  template <bool FULL>
+  __device__ __forceinline__ static void init(int kind, const ModelCtx &m, RayState &s, Rng &rng, unsigned &t2) {
+    with<FULL>(kind, [&](auto model) {
+      using M = decltype(model);
+      if constexpr (M::kStateWords > 0)
+        M::init(m, s, rng, t2);
+    });
+  }
+  template <int D, bool FULL>
+  __device__ __forceinline__ static Reflection surface_reflection(int kind, const ModelCtx &m, RayState &s, float w,
+                                                                  const V3 &rayDir, const V3 &n, unsigned primID,
+                                                                  int materialId, float base, Rng &rng, unsigned &t2) {
+    Reflection r{base, rayDir};
+    with<FULL>(kind, [&](auto model) {
+      using M = decltype(model);
+      if constexpr (M::kStateWords > 0) {
+        r = M::template surface_reflection<D>(m, s, w, rayDir, n, primID, materialId, base, rng, t2);
+      } else { // (no draws for a ray that dies here, as in the stateless kernels)
+        r.sticking = M::sticking(m, primID, base);
+        if (w - w * r.sticking > 0.f)
+          r.dir = M::template reflect<D>(m, rayDir, n, rng, t2);
+      }
+    });
+    return r;
+  }
+  template <bool FULL, class Credit>
+  __device__ __forceinline__ static void collide(int kind, const ModelCtx &m, const RayState &s, float w, const V3 &rayDir,
+                                                 const V3 &n, unsigned primID, int materialId, Credit &&credit) {
+    with<FULL>(kind, [&](auto model) {
+      using M = decltype(model);
+      if constexpr (M::kStateWords > 0)
+        M::collide(m, s, w, rayDir, n, primID, materialId, credit);
+      else
+        M::collide(m, w, rayDir, n, primID, credit);
+    });
   }
 };
 

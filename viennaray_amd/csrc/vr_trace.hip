@@ -33,7 +33,8 @@ namespace vr {
 // fixed-point weight: 2^40 per unit (order-independent integer accumulation)
 __device__ __forceinline__ u64 weight_fx(float w) { return (u64)((double)w * 1099511627776.0 + 0.5); }
 
-#ifndef VR_USER_MODULE // (a run-time compiled particle module holds trace kernels only, see the end of the file)
+// (a run-time compiled particle module holds the trace kernels and — for a stateful model — its own generator, built from
+//  the source sampling and the record store below; see the end of the file)
 // ---------------------------------------------------------------------------
 // source sampling (raySourceRandom.hpp:25-116)
 // ---------------------------------------------------------------------------
@@ -209,6 +210,7 @@ __device__ __forceinline__ unsigned gen_store(const TraceParams &p, unsigned i, 
   return slot;
 }
 
+#ifndef VR_USER_MODULE
 // Fixed number of source draws (no tilted primary direction): the NS engine outputs
 // the source sample needs are produced straight into registers by one 156+NS-step pass
 // of the seeding recurrence, which also leaves the streaming cursors for the trace kernel.
@@ -482,6 +484,12 @@ __device__ __forceinline__ void process_boundary_hit(const TraceParams &p, const
   }
 }
 
+// material id of ORIGINAL primitive `origId` for a stateful model's hooks (the frame's VR_F_MAT_*; none set: 0)
+__device__ __forceinline__ int material_of(const float *wallS, unsigned origId) {
+  const int *ids = reinterpret_cast<const int *>(frame_addr(wallS, VR_F_MAT_LO));
+  return ids ? ids[origId] : 0;
+}
+
 // "Segments that rise clear" (trace_kernel): does the height field over the source plane (HeightFieldParams, the launch
 // frame's VR_F_HF_*) say that a ray starting at `org` cannot meet the geometry?  It is above its tile's height — the highest
 // point of anything in the tile or its eight neighbours — from tnear on, and rises above the whole scene before it has
@@ -588,6 +596,8 @@ trace_kernel(const TraceParams p) {
   // decided at run time from TraceParams (vr_particles.hpp)
   constexpr bool EXT = PARTICLE >= P_EXT;           // (P_EXT, P_EXT_FULL)
   constexpr bool EXT_FULL = PARTICLE == P_EXT_FULL; // ... with the coned-cosine model, WDIST crediting and the mean free path
+  // per-ray state words of a stateful model (vr_particles.hpp): only a module compiled around one has them (0 in the library)
+  constexpr int SW = EXT_FULL ? Particles::stateWords : 0;
   // packet-query rounds credit disks wave-uniformly from the candidate list (pq_credit) instead of
   // walking the neighbour CSR per lane
   constexpr bool PQ_CREDIT = GEO == 0 && !EXT_FULL && (MODE == 1 || MODE == 3);
@@ -694,6 +704,7 @@ trace_kernel(const TraceParams p) {
   V3 org = mk(0, 0, 0), rayDirection = mk(0, 0, 1), dir2 = mk(0, 0, 1);
   V3 &dir = D == 3 ? rayDirection : dir2;
   float rayWeight = 0.f;
+  [[maybe_unused]] RayState rayState; // (SW > 0: the model's state, in registers from the ray's pick-up to its end)
   // The two per-ray counters are touched once per segment: in the general kernels they live in LDS, not in two of
   // the 80 VGPRs (left to the register allocator they went to scratch, and a scratch reload waits on the
   // vector-memory counter: for every load and atomic the wave has in flight).
@@ -907,6 +918,13 @@ trace_kernel(const TraceParams p) {
         if (!ABSORB && p.hostWeights) {     // (a host-callback source with weights of its own never runs an absorbing kernel)
           rayWeight = p.hostWeights[p.batchFirst + __float_as_uint(b.y)];
           initWeightBits = __float_as_uint(rayWeight);
+        }
+        if constexpr (SW > 0) { // what the model's init left (gen_state_kernel), indexed like the records' side array
+          const float4 sv = reinterpret_cast<const float4 *>(frame_addr(wallS, VR_F_STATE_LO))[__float_as_uint(b.y)];
+          rayState.v[0] = sv.x;
+          rayState.v[1] = sv.y;
+          rayState.v[2] = sv.z;
+          rayState.v[3] = sv.w;
         }
         numReflections = 0;
         boundaryHits = 0;
@@ -1178,13 +1196,24 @@ trace_kernel(const TraceParams p) {
               // (a coarse scene under sorted rays: a good share of the wave credits ONE disk — merged per distinct
               //  weight like the built-in particles' credits, or the 64 lanes queue up on one address in L2)
               auto creditTo = [&](unsigned q, float w, const V3 &nq, unsigned origId) {
-                Particles::collide<EXT_FULL>(kind, mctx, w, rayDirection, nq, origId, [&](int label, float v) {
-                  unsigned long long *plane = fluxAcc + (size_t)label * (SMALL ? p.numPrims : p.planeStride);
-                  if (aggregate && !SMALL) // (LDS accumulators take 64 adds on one address in their stride)
-                    credit_aggregated(plane, true, q, weight_fx(v));
-                  else
-                    atomicAdd(&plane[q], weight_fx(v));
-                });
+                if constexpr (SW > 0) { // (a stateful model: the ray's state and the primitive's material id too)
+                  Particles::collide<EXT_FULL>(kind, mctx, rayState, w, rayDirection, nq, origId, material_of(wallS, origId),
+                                               [&](int label, float v) {
+                                                 unsigned long long *plane = fluxAcc + (size_t)label * (SMALL ? p.numPrims : p.planeStride);
+                                                 if (aggregate && !SMALL)
+                                                   credit_aggregated(plane, true, q, weight_fx(v));
+                                                 else
+                                                   atomicAdd(&plane[q], weight_fx(v));
+                                               });
+                } else {
+                  Particles::collide<EXT_FULL>(kind, mctx, w, rayDirection, nq, origId, [&](int label, float v) {
+                    unsigned long long *plane = fluxAcc + (size_t)label * (SMALL ? p.numPrims : p.planeStride);
+                    if (aggregate && !SMALL) // (LDS accumulators take 64 adds on one address in their stride)
+                      credit_aggregated(plane, true, q, weight_fx(v));
+                    else
+                      atomicAdd(&plane[q], weight_fx(v));
+                  });
+                }
               };
               if (GEO == 0) {
                 const unsigned nb = nbOff[h.pos], ne = nbOff[h.pos + 1];
@@ -1236,8 +1265,18 @@ trace_kernel(const TraceParams p) {
               asm volatile("" : "+s"(sticking)); // (a value in a register, not a second address to choose from)
               if (p.primSticking)
                 sticking = primSticking[h.pos];
-              if (EXT) // (a registry model may make it depend on the primitive and the caller's global data)
+              [[maybe_unused]] V3 stateDir;
+              if constexpr (SW > 0) {
+                // a stateful model: ONE surfaceReflection call gives the sticking and the new direction and may update
+                // the state (rayTraceKernel.hpp:310) — also for a ray it kills: draws after its end are not observable
+                const Reflection r = Particles::surface_reflection<D, EXT_FULL>(
+                    p.particleKind, model_ctx(p), rayState, rayWeight, rayDirection, geomNormal, h.prim,
+                    material_of(wallS, h.prim), sticking, rng, cnt[K_TIER2 * VR_BLOCK]);
+                sticking = r.sticking;
+                stateDir = r.dir;
+              } else if (EXT) { // (a registry model may make it depend on the primitive and the caller's global data)
                 sticking = Particles::sticking<EXT_FULL>(p.particleKind, model_ctx(p), h.prim, sticking);
+              }
               const float wAfter = rayWeight - rayWeight * sticking;
               if (wAfter <= 0.f) {
                 active = false; // as above: the pending draws die with the ray
@@ -1245,7 +1284,9 @@ trace_kernel(const TraceParams p) {
                 // surfaceReflection, rayParticle.hpp:137-146 / 178-187
                 SUB_START
                 V3 newDir;
-                if (PARTICLE == 0)
+                if constexpr (SW > 0)
+                  newDir = stateDir;
+                else if (PARTICLE == 0)
                   newDir = reflection_diffuse<D>(geomNormal, rng, cnt[K_TIER2 * VR_BLOCK]);
                 else if (PARTICLE == 1)
                   newDir = reflect_specular(rayDirection, geomNormal);
@@ -1856,6 +1897,12 @@ hipError_t launch_gather_flux(const unsigned long long *acc, unsigned stride, un
 // ---------------------------------------------------------------------------
 static_assert(VrUserModel::kNumData >= 1 && VrUserModel::kNumData <= VR_MAX_LABELS, "a model has 1 .. VR_MAX_LABELS data labels");
 static_assert(VrUserModel::kNumData == VR_USER_NUM_DATA, "kNumData differs from the count given at registration");
+#ifndef VR_USER_NUM_STATE
+#define VR_USER_NUM_STATE 0
+#endif
+static_assert(VrUserModel::kStateWords >= 0 && VrUserModel::kStateWords <= VR_MAX_STATE_WORDS, "a model has 0 .. 4 state words (kStateWords)");
+static_assert(VrUserModel::kStateWords == VR_USER_NUM_STATE, "kStateWords differs from the numState given at registration");
+static_assert(VrUserModel::kStateWords == 0 || VrUserModel::kNeedsFull, "a stateful model (kStateWords > 0) needs kNeedsFull = true");
 constexpr int VR_USER_P = VrUserModel::kNeedsFull ? P_EXT_FULL : P_EXT;
 #define VR_INST(DD, GG, MM) template __global__ void trace_kernel<DD, GG, VR_USER_P, MM>(const TraceParams);
 VR_INST(2, 0, 0) VR_INST(2, 0, 4) VR_INST(2, 1, 0) VR_INST(2, 1, 4)
@@ -1863,6 +1910,36 @@ VR_INST(3, 0, 0) VR_INST(3, 0, 4) VR_INST(3, 1, 0) VR_INST(3, 1, 4)
 #undef VR_INST
 template __global__ void trace_kernel<2, 0, P_EXT, VrUserModel::kNeedsFull ? 0 : 3>(const TraceParams);
 template __global__ void trace_kernel<3, 0, P_EXT, VrUserModel::kNeedsFull ? 0 : 3>(const TraceParams);
+
+// The generator of a STATEFUL model (SourceRandom, plain or with a primary direction): the model's init (initNew,
+// rayTraceKernel.hpp:131-133) draws first, then the source sample from the same engine (the streaming generator of
+// gen_basis_kernel: the draw count varies), then the record with the true draw count — always with the side array
+// (TraceParams::recExtra) — and the ray's state at the same index (TraceParams::rayState).
+template <int D, class M = VrUserModel> __global__ __launch_bounds__(VR_BLOCK) void gen_state_kernel(const TraceParams p) {
+  if constexpr (M::kStateWords > 0) {
+    const unsigned tid = threadIdx.x;
+    const unsigned gwave = (blockIdx.x * VR_BLOCK + tid) >> 6; // physical wave of this (bounded) grid
+    u64 *scratchLane = p.rngScratch + (size_t)gwave * (312u * 64u) + (tid & 63u);
+    const ModelCtx mctx = model_ctx(p);
+    for (unsigned i = blockIdx.x * VR_BLOCK + tid; i < p.batchCount; i += gridDim.x * VR_BLOCK) {
+      const unsigned long long idx = p.idxList ? p.idxList[i] : p.batchFirst + i;
+      Rng rng;
+      rng_init(rng, tea3((unsigned)idx, p.seed), scratchLane);
+      unsigned t2 = 0;
+      RayState s;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        s.v[k] = 0.f;
+      M::init(mctx, s, rng, t2);
+      V3 o, d;
+      source_sample<D>(p, [&]() { return rng_next(rng, t2); }, o, d);
+      gen_store<D, true>(p, i, o, d, rng.k, rng.lo, rng.hi); // (k >= 156: the trace kernel rebuilds tier 2 from the seed)
+      reinterpret_cast<float4 *>(frame_addr(p.wallTable, VR_F_STATE_LO))[i] = make_float4(s.v[0], s.v[1], s.v[2], s.v[3]);
+    }
+  }
+}
+template __global__ void gen_state_kernel<2>(const TraceParams);
+template __global__ void gen_state_kernel<3>(const TraceParams);
 #endif // VR_USER_MODULE
 
 } // namespace vr

@@ -320,11 +320,17 @@ class Trace:
         self._particles = particles
         del keep
 
-    def registerParticleModel(self, source, numData=1, needsFull=False, name="user"):
-        """vr_register_particle_model: HIP source of `struct VrUserModel` -> the kind id of a UserModelParticle"""
+    def registerParticleModel(self, source, numData=1, needsFull=False, name="user", numState=0):
+        """vr_register_particle_model: HIP source of `struct VrUserModel` -> the kind id of a UserModelParticle.
+        numState = the model's kStateWords (1 .. 4: a stateful model with init / surface_reflection / collide hooks,
+        vr_register_particle_model_ex; it implies needsFull)"""
         k = C.c_int32(0)
-        self._check(self._L.vr_register_particle_model(self._h, name.encode(), source.encode(), int(numData),
-                                                       1 if needsFull else 0, C.byref(k)))
+        if numState:
+            self._check(self._L.vr_register_particle_model_ex(self._h, name.encode(), source.encode(), int(numData),
+                                                              int(numState), 1 if needsFull else 0, C.byref(k)))
+        else:
+            self._check(self._L.vr_register_particle_model(self._h, name.encode(), source.encode(), int(numData),
+                                                           1 if needsFull else 0, C.byref(k)))
         return int(k.value)
 
     def setGlobalData(self, data):
@@ -566,6 +572,18 @@ class Trace:
                                                  p.ctypes.data_as(C.POINTER(C.c_uint32)), n, _fptr(oo), _fptr(do),
                                                  r.ctypes.data_as(C.POINTER(C.c_int32))))
         return oo, do, r.astype(bool)
+
+    def debugModelSourceSample(self, idx, seed):
+        """the active stateful model's generator (init, then the source sample): first origin, direction and the engine
+        outputs consumed before the trace, per global ray index"""
+        i = np.ascontiguousarray(idx, dtype=np.uint64)
+        o = np.empty((i.size, 3), dtype=np.float32)
+        d = np.empty((i.size, 3), dtype=np.float32)
+        k = np.empty(i.size, dtype=np.uint32)
+        self._check(self._L.vr_debug_model_source_sample(self._h, i.ctypes.data_as(C.POINTER(C.c_uint64)), i.size,
+                                                         int(seed), _fptr(o), _fptr(d),
+                                                         k.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return o, d, k
 
     def debugSourceSample(self, idx, seed):
         i = np.ascontiguousarray(idx, dtype=np.uint64)
