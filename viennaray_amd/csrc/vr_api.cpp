@@ -14,6 +14,7 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <optional>
 #include <random>
 #include <sstream>
 #include <string>
@@ -66,9 +67,157 @@ template <class T> struct DevBuf {
   DevBuf() = default;
   DevBuf(const DevBuf &) = delete;
   DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      std::swap(p, o.p);
+      std::swap(cap, o.cap);
+    }
+    return *this;
+  }
   ~DevBuf() { release(); } // (vr_destroy selects the device before the context goes away)
 };
 } // namespace
+
+// Every tuning and experiment switch of the library, read from the environment in ONE place (read_knobs): an apply
+// reads them once, at vr_apply_prepare, into vr_context::knobs.  Unless its line says RESULTS, a switch only moves work
+// around: the flux and the TraceInfo counters stay bit-exact (tests/test_gpu_parity.py).  (VR_CSRC_DIR / VR_HIPCC /
+// VR_CACHE_DIR are configuration of vr_register_particle_model, read there.)
+struct Knobs {
+  // scene build
+  std::optional<uint32_t> accReplicas; // VR_ACC_REPLICAS: flux accumulator replicas, >= 1, rounded down to a power of two (unset: by scene size)
+  bool hostBuild = false;              // VR_HOST_BUILD (non-zero): LBVH, neighbourhood and disk areas on the host (validation path)
+  std::optional<uint32_t> leafMax;     // VR_LEAF_MAX [1, 15]: primitives per BVH leaf (unset: VR_LEAF_MAX disks, 3 triangles)
+  bool noChildOrder = false;           // VR_NO_CHILD_ORDER (non-zero): BVH children not ordered source side first
+  float mortonAniso = VR_MORTON_ANISO; // VR_MORTON_ANISO >= 1: largest aspect ratio of the Morton grid's cells
+  bool nbTwoPass = false;              // VR_NB_TWO_PASS (set): the neighbourhood query in two passes (count, fill)
+  // kernel choice
+  bool smallScene = true;              // VR_SMALL_SCENE (0: off): small scenes resident in LDS (MODE 4)
+  bool noRelief = false;               // VR_NO_RELIEF (set): no relief packets (MODE 5 / 6) on flat scenes with relief
+  float reliefMaxThick = 8.f;          // VR_RELIEF_MAX_THICK: thickest scene (grid cells along the source axis) for relief packets
+  float reliefTravel = 1.5f;           // VR_RELIEF_TRAVEL >= 0.05: a ray is loose when thickness x tan(theta) exceeds this (grid cells)
+  float reliefTile = 1.f;              // VR_RELIEF_TILE >= 0.25: fine relief tile side in grid cells
+  std::optional<int> reliefCoarseK;    // VR_RELIEF_COARSE_K >= 1: fine tiles per coarse tile side (unset: by field size)
+  float reliefShare = 0.3f;            // VR_RELIEF_SHARE: largest predicted share of loose rays for relief packets
+  float reliefSteps = 6.f;             // VR_RELIEF_STEPS >= 1: a ray crossing more tiles through the scene box is loose
+  int reliefLookups = 1;               // VR_RELIEF_LOOKUPS [0, 2]: coarse look-ups of the generator's hit prediction
+  bool noSpill = false;                // VR_NO_SPILL (set): the tight general relief kernel keeps its continuing rays
+  std::optional<bool> generalFlat;     // VR_GENERAL_FLAT (set): packet-query crediting in the general kernel on (non-zero) / off
+  std::optional<bool> absorbCarry;     // VR_ABSORB_CARRY (set): absorbing kernel with (non-zero) / without straggler carry-over
+  std::optional<int> traceBlocks;      // VR_TRACE_BLOCKS >= 1: blocks per CU of the trace launch (unset: by occupancy and rays)
+  std::optional<int> looseBlocks;      // VR_LOOSE_BLOCKS >= 1: ... of a relief scene's loose launch
+  // ray stream
+  std::optional<uint64_t> batchRays;   // VR_BATCH_RAYS >= 256: rays per batch (unset: 2^27)
+  uint32_t binCap = VR_BIN_CAP;        // VR_BIN_CAP >= 8: record slots per sort bin
+  uint32_t raysPerBin = 40;            // VR_RAYS_PER_BIN >= 1: rays per sort bin the grid is sized for
+  std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
+  std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
+  // kernel parameters (TraceParams)
+  uint32_t pqFrontier = 12;            // VR_PQ_FRONTIER [1, 24]: packet query gives up beyond this frontier
+  uint32_t pqCand = 24;                // VR_PQ_CAND [1, 24]: ... or beyond this many candidates
+  float pqMargin = 1.5f;               // VR_PQ_MARGIN >= 0: packet query's frontier-cache margin (units of 2 r / 1.7 cells)
+  std::optional<float> keyCoord;       // VR_KEY_COORD: sort plane of the ray stream (unset: host_sort_plane)
+  uint32_t packetBudget = 128;         // VR_PACKET_BUDGET >= 0: node visits of a packet traversal
+  std::optional<uint32_t> walkPark;    // VR_WALK_PARK [1, 100]: % of parked lanes that tests the leaves (unset: 25 disks, 10 triangles)
+  uint32_t walkExit = 16;              // VR_WALK_EXIT [1, 64]: a round's walk ends below this many walking lanes
+  uint32_t packetRatio = 3;            // VR_PACKET_RATIO >= 1: packet traversal gives up beyond ratio x mean path
+  uint32_t debugFlags = 0;             // VR_DEBUG_FLAGS: kernel experiment bits; many of them change RESULTS
+  bool noHeightField = false;          // VR_NO_HEIGHT_FIELD (set): no height field over the source plane
+  float hfTile = 4.f;                  // VR_HF_TILE >= 0.25: height-field tile side in grid cells
+  // diagnostics
+  bool printLaunches = false;          // VR_PRINT_LAUNCHES (set): trace-launch times and spilled rays on stderr
+  bool hostSmooth = false;             // VR_HOST_SMOOTH (set): vr_smooth_flux on the host
+  bool debugWalk = true;               // VR_DEBUG_WALK (0: the escape-link walk): vr_debug_intersect's walk
+#ifdef VR_DIAG
+  bool skipTight = false;              // VR_SKIP_TIGHT (set): a relief scene's loose launch alone; INCOMPLETE results
+  bool skipLoose = false;              // VR_SKIP_LOOSE (set): ... its tight launch alone; INCOMPLETE results
+#endif
+};
+
+static Knobs read_knobs() {
+  Knobs k;
+  if (const char *e = std::getenv("VR_ACC_REPLICAS"))
+    k.accReplicas = (uint32_t)std::max(1, std::atoi(e));
+  if (const char *e = std::getenv("VR_HOST_BUILD"))
+    k.hostBuild = std::atoi(e) != 0;
+  if (const char *e = std::getenv("VR_LEAF_MAX"))
+    k.leafMax = (uint32_t)std::min(15, std::max(1, std::atoi(e)));
+  if (const char *e = std::getenv("VR_NO_CHILD_ORDER"))
+    k.noChildOrder = std::atoi(e) != 0;
+  if (const char *e = std::getenv("VR_MORTON_ANISO"))
+    k.mortonAniso = std::max(1.f, (float)std::atof(e));
+  k.nbTwoPass = std::getenv("VR_NB_TWO_PASS") != nullptr;
+  if (const char *e = std::getenv("VR_SMALL_SCENE"))
+    k.smallScene = std::atoi(e) != 0;
+  k.noRelief = std::getenv("VR_NO_RELIEF") != nullptr;
+  if (const char *e = std::getenv("VR_RELIEF_MAX_THICK"))
+    k.reliefMaxThick = (float)std::atof(e);
+  if (const char *e = std::getenv("VR_RELIEF_TRAVEL"))
+    k.reliefTravel = std::max(0.05f, (float)std::atof(e));
+  if (const char *e = std::getenv("VR_RELIEF_TILE"))
+    k.reliefTile = std::max(0.25f, (float)std::atof(e));
+  if (const char *e = std::getenv("VR_RELIEF_COARSE_K"))
+    k.reliefCoarseK = std::max(1, std::atoi(e));
+  if (const char *e = std::getenv("VR_RELIEF_SHARE"))
+    k.reliefShare = (float)std::atof(e);
+  if (const char *e = std::getenv("VR_RELIEF_STEPS"))
+    k.reliefSteps = std::max(1.f, (float)std::atof(e));
+  if (const char *e = std::getenv("VR_RELIEF_LOOKUPS"))
+    k.reliefLookups = std::min(2, std::max(0, std::atoi(e)));
+  k.noSpill = std::getenv("VR_NO_SPILL") != nullptr;
+  if (const char *e = std::getenv("VR_GENERAL_FLAT"))
+    k.generalFlat = std::atoi(e) != 0;
+  if (const char *e = std::getenv("VR_ABSORB_CARRY"))
+    k.absorbCarry = std::atoi(e) != 0;
+  if (const char *e = std::getenv("VR_TRACE_BLOCKS"))
+    k.traceBlocks = std::max(1, std::atoi(e));
+  if (const char *e = std::getenv("VR_LOOSE_BLOCKS"))
+    k.looseBlocks = std::max(1, std::atoi(e));
+  if (const char *e = std::getenv("VR_BATCH_RAYS"))
+    k.batchRays = (uint64_t)std::max<long long>(256, std::atoll(e));
+  if (const char *e = std::getenv("VR_BIN_CAP"))
+    k.binCap = (uint32_t)std::max(8, std::atoi(e));
+  if (const char *e = std::getenv("VR_RAYS_PER_BIN"))
+    k.raysPerBin = (uint32_t)std::max(1, std::atoi(e));
+  if (const char *e = std::getenv("VR_SPAN_BINS"))
+    k.spanBins = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
+  if (const char *e = std::getenv("VR_QUEUES"))
+    k.numQueues = std::atoi(e) >= (int)VR_QUEUES ? VR_QUEUES : 1u;
+  if (const char *e = std::getenv("VR_PQ_FRONTIER"))
+    k.pqFrontier = (uint32_t)std::min(24, std::max(1, std::atoi(e))); // (<= 24: the cached frontier shares the lists with its box)
+  if (const char *e = std::getenv("VR_PQ_CAND"))
+    k.pqCand = (uint32_t)std::min(24, std::max(1, std::atoi(e))); // (2 * pqMaxCand + 1 records fit VR_PQ_CANDS)
+  if (const char *e = std::getenv("VR_PQ_MARGIN"))
+    k.pqMargin = std::max(0.f, (float)std::atof(e));
+  if (const char *e = std::getenv("VR_KEY_COORD"))
+    k.keyCoord = (float)std::atof(e);
+  if (const char *e = std::getenv("VR_PACKET_BUDGET"))
+    k.packetBudget = (uint32_t)std::max(0, std::atoi(e));
+  if (const char *e = std::getenv("VR_WALK_PARK"))
+    k.walkPark = (uint32_t)std::min(100, std::max(1, std::atoi(e)));
+  if (const char *e = std::getenv("VR_WALK_EXIT"))
+    k.walkExit = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
+  if (const char *e = std::getenv("VR_PACKET_RATIO"))
+    k.packetRatio = (uint32_t)std::max(1, std::atoi(e));
+  if (const char *e = std::getenv("VR_DEBUG_FLAGS"))
+    k.debugFlags = (uint32_t)std::atoi(e);
+  k.noHeightField = std::getenv("VR_NO_HEIGHT_FIELD") != nullptr;
+  if (const char *e = std::getenv("VR_HF_TILE"))
+    k.hfTile = std::max(0.25f, (float)std::atof(e));
+  k.printLaunches = std::getenv("VR_PRINT_LAUNCHES") != nullptr;
+  k.hostSmooth = std::getenv("VR_HOST_SMOOTH") != nullptr;
+  if (const char *e = std::getenv("VR_DEBUG_WALK"))
+    k.debugWalk = std::atoi(e) != 0;
+#ifdef VR_DIAG
+  k.skipTight = std::getenv("VR_SKIP_TIGHT") != nullptr;
+  k.skipLoose = std::getenv("VR_SKIP_LOOSE") != nullptr;
+#endif
+  return k;
+}
 
 // one entry of vr_set_particles (a deep copy of the caller's vr_particle)
 struct ParticleSpec {
@@ -91,17 +240,21 @@ struct UserModel {
   hipFunction_t gen[2] = {nullptr, nullptr}; // a stateful model's generator (gen_state_kernel), 2-D / 3-D
 };
 
-// the prepared launch of one particle of a multi-particle apply()
+// The prepared launch of one particle of an apply() (vr_context::launches: one per particle of vr_set_particles).
+// params holds everything but the buffers all particles share — ray stream, scratch, counters, accumulators — whose
+// addresses launch_params adds when the launch runs.
 struct ParticleLaunch {
   TraceParams params{};
+  uint32_t slot = 0;     // index of the particle: its counter block, wall-table / frame slot
+  uint32_t dataBase = 0; // its first accumulator plane
   unsigned grid = 0;
   int traceMode = 0, kernelParticle = 0;
   bool absorb = false;
-  uint32_t numData = 1, dataBase = 0;
+  bool recExtra = false; // the records' side array (TraceParams::recExtra)
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
   hipFunction_t userGen = nullptr;    // ... and a stateful model's generator (nullptr: the library's)
-  float *primSticking = nullptr; // owned (hipMalloc): this particle's per-primitive sticking, leaf order
-  bool relief = false;           // a second launch (looseMode) traces the loose bins
+  DevBuf<float> primSticking;         // this particle's per-primitive sticking, leaf order (params.primSticking, or unused)
+  bool relief = false; // flat with relief: a second launch (looseMode, looseGrid) traces the loose bins
   int looseMode = 0;
   unsigned looseGrid = 0;
   vr_trace_info info{};
@@ -133,19 +286,16 @@ struct vr_context {
   bool useWdist = false;
   uint32_t numData = 1;           // data labels of the (active) particle
   uint32_t totalData = 1;         // ... of all particles of the apply: accumulator planes, TracingData vectors
-  uint32_t dataBase = 0;          // first plane of the active particle
-  uint32_t counterSlot = 0;       // ... and its block of 80 counter words
   uint32_t accPlanes = 0;         // planes the accumulator buffers currently hold
   float particleParams[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int userModel = -1;             // index into userModels when the active particle is a run-time model
-  hipFunction_t userKernel = nullptr; // ... and the kernel vr_apply_prepare picked from its module
-  hipFunction_t userGen = nullptr;    // ... and the generator of a stateful model (nullptr: the library's generators)
   DevBuf<float> dRayState;            // a stateful model's per-ray state of one batch (the frame's VR_F_STATE_*), float4 per ray
   DevBuf<int32_t> dPrimMaterial;      // material id per original primitive for a stateful model (VR_F_MAT_*)
   std::vector<UserModel> userModels;
   bool particleDirty = true;      // the sticking map needs recomputing
   std::vector<ParticleSpec> specs;      // vr_set_particles: > 1 entries = a multi-particle apply
-  std::vector<ParticleLaunch> launches; // prepared by vr_apply_prepare when specs.size() > 1
+  std::vector<ParticleLaunch> launches; // prepared by vr_apply_prepare: one per particle (at least one)
+  Knobs knobs;                          // the tuning switches, read by vr_apply_prepare
   // Trace::setGlobalData: vectors (padded to one stride) and scalars, resident in HBM
   std::vector<std::vector<float>> globalVecs;
   std::vector<float> globalScalars;
@@ -184,14 +334,12 @@ struct vr_context {
   float sourceArea = 0.f;
   uint64_t numRaysLast = 0;
   bool prepared = false, launched = false, haveResult = false;
-  TraceParams params{};
-  unsigned grid = 0;
 
   vr_trace_info info{};
   double buildSeconds = 0.0;
 
   // device buffers
-  DevBuf<float> dNodes, dPrims, dPrimSticking;
+  DevBuf<float> dNodes, dPrims;
   DevBuf<float> dAreas, dFluxTmp;     // exposed area per primitive (caller's order); normalisation scratch
   DevBuf<uint32_t> dNormMax;          // flux_max_kernel's reduction word
   bool areasValid = false;
@@ -218,8 +366,6 @@ struct vr_context {
   float qbase[3] = {0, 0, 0}, qscale[3] = {0, 0, 0}; // frame of the 16-byte nodes
   float keyCoord = 0.f;          // sort plane of the ray stream on the tracing axis (host_sort_plane)
   float keyShare = 1.f;          // share of the surface shown to the source that lies in that plane
-  int traceMode = 0;             // trace_kernel MODE of the prepared launch
-  int kernelParticle = 0;        // PARTICLE template id of the prepared launch (P_EXT: extended kernel)
   SetupParams lastSetup{};       // buffers of the resident device build (vr_debug_bvh_check)
   bool haveSetup = false;
   int builtOrderAxis = -1;       // child order of the resident BVH (source side first)
@@ -238,7 +384,6 @@ struct vr_context {
   uint32_t batchCap = 0;      // rays per batch the buffers hold
   uint32_t numBins = 0;
   uint64_t rayFirstLaunch = 0, rayEndLaunch = 0;
-  bool absorb = true;
   float wallsHost[96] = {0};        // the eight wall triangles (made with the bounding box)
   std::vector<float> frameHostAll;  // wall table + scalar frame of every particle of the apply (staging of their uploads)
   // relief field over the source plane (ReliefParams): scenes that are flat with relief
@@ -250,25 +395,24 @@ struct vr_context {
   float rfLooseShare = 1.f;
   DevBuf<float> dSpillRec;     // the general relief kernel's spill queue (TraceParams::spillRec), 16 floats per ray of a batch
   DevBuf<uint32_t> dSpillCount;
-  bool reliefScene = false;    // the prepared launch: MODE 5 / 6 over the tight bins + looseMode over the loose ones
-  int looseMode = 0;
-  unsigned looseGrid = 0;
   DevBuf<uint32_t> dHfRaw;    // height field over the source plane (HeightFieldParams): built for particles that reflect
   DevBuf<float> dHf;
   HeightFieldParams hf{};
   uint32_t hfBuild = 0xFFFFFFFFu; // the bvhBuilds count and source frame it was made for
   int hfAxes[4] = {-1, -1, -1, -1};
-  bool recExtra = false;      // non-absorbing particle under a tilted / grid / host source: the records' side array
-  DevBuf<float> dRecExtra;
+  DevBuf<float> dRecExtra;    // the records' side array (ParticleLaunch::recExtra)
   std::vector<hipEvent_t> evK; // trace-kernel event pairs, one per batch
   std::vector<hipEvent_t> evG; // generator event pairs, one per batch
   double traceKernelSeconds = 0.0;
-  bool havePrimSticking = false;
   uint32_t worldSize = 1;     // ranks whose accumulators will be summed (vr_set_world_size): head-room of the overflow check
   unsigned long long *boundFlux = nullptr; // caller-owned accumulator buffer
   uint32_t boundFluxN = 0;
   unsigned long long *fluxOut() { return boundFlux ? boundFlux : dFluxOrig.p; }
 };
+
+// The launch the readers of "the" prepared launch see (vr_get_trace_mode, the vr_debug_* entry points, the spill print
+// of VR_PRINT_LAUNCHES): the LAST one prepared — after a multi-particle prepare, the last particle's.
+static const ParticleLaunch &current_launch(const vr_context *c) { return c->launches.back(); }
 
 #define VR_HIP(ctx, call)                                                                                              \
   do {                                                                                                                 \
@@ -284,9 +428,6 @@ static int fail(vr_context *c, int code, const char *msg) {
     c->err = msg;
   return code;
 }
-
-static void size_bins(int D, uint64_t count, uint32_t perBin, TraceParams &p, uint32_t &numBins);
-static void size_loose(int D, TraceParams &p);
 
 extern "C" {
 
@@ -325,15 +466,11 @@ void vr_destroy(vr_context *c) {
   (void)hipSetDevice(c->device);
   if (c->stream)
     (void)hipStreamSynchronize(c->stream);
-  for (auto &L : c->launches)
-    if (L.primSticking)
-      (void)hipFree(L.primSticking);
   for (auto &um : c->userModels)
     if (um.module)
       (void)hipModuleUnload(um.module);
   c->dNodes.release();
   c->dPrims.release();
-  c->dPrimSticking.release();
   c->dNbOff.release();
   c->dNbTmp.release();
   c->dNbIds.release();
@@ -494,8 +631,6 @@ int vr_set_particles(vr_context *c, const vr_particle *list, uint32_t n) {
   c->specs = std::move(specs);
   activate_particle(c, c->specs[0]);
   c->totalData = total;
-  c->dataBase = 0;
-  c->counterSlot = 0;
   // a caller's accumulator buffer (vr_bind_flux_accumulators) stays bound while it still has the right size: numPrims x
   // data labels of ALL particles; it is dropped only when the number of planes changed
   if (c->boundFlux && c->boundFluxN != c->geo.numPrims * total) {
@@ -956,6 +1091,7 @@ static int quantize_scene(vr_context *c, const float *preNodes, const float *roo
 }
 
 static int build_scene(vr_context *c) {
+  const Knobs &K = c->knobs;
   HostGeometry &g = c->geo;
   const uint32_t N = g.numPrims;
   const bool disk = g.geo == 0;
@@ -965,8 +1101,8 @@ static int build_scene(vr_context *c) {
   VR_HIP(c, c->dOrder.ensure(N));
   {
     uint32_t R = 1;
-    if (const char *e = std::getenv("VR_ACC_REPLICAS"))
-      R = (uint32_t)std::max(1, std::atoi(e));
+    if (K.accReplicas)
+      R = *K.accReplicas;
     else
       while (R < 64u && (size_t)N * (2u * R) <= (1u << 21))
         R *= 2u;
@@ -978,15 +1114,14 @@ static int build_scene(vr_context *c) {
   }
   VR_HIP(c, c->dCounters.ensure(80));
   VR_HIP(c, c->dNbOff.ensure((size_t)N + 1));
-  const char *hb = std::getenv("VR_HOST_BUILD");
-  if (hb && std::atoi(hb)) {
+  if (K.hostBuild) {
     // host builder (validation path): LBVH + CSR on the CPU, uploaded
     if (disk)
       host_neighbors(g.D, g.points3.data(), N, 2 * g.diskRadius, g.minC, g.nbOff, g.nbIds);
     else
       g.nbOff.assign((size_t)N + 1, 0u), g.nbIds.clear();
     c->hostNeighborsValid = true;
-    host_build_bvh(g, c->bvh);
+    host_build_bvh(g, c->bvh, K.mortonAniso);
     c->hostOrderValid = true;
     std::vector<float> prims;
     host_pack_prims(g, c->bvh, prims);
@@ -1025,21 +1160,14 @@ static int build_scene(vr_context *c) {
   SetupParams s{};
   // (triangles: a leaf of up to 3 — their test is 64 bytes and ~60 instructions per primitive; measured 4 -> 3:
   //  trenchMesh 0.1 29.6 -> 28.4 ms, C4 21.4 -> 20.6; disks: 2 .. 4 within 2 %, 6 and 8 slower)
-  s.leafMax = g.geo == 1 ? 3u : (uint32_t)VR_LEAF_MAX;
-  if (const char *e = std::getenv("VR_LEAF_MAX"))
-    s.leafMax = (uint32_t)std::min(15, std::max(1, std::atoi(e)));
-  s.orderAxis = c->ts[0];                   // rays travel along this axis ...
-  s.orderSign = c->ts[3] ? 1.f : -1.f;      // ... from its max (min) side: that child first
-  if (const char *e = std::getenv("VR_NO_CHILD_ORDER"))
-    if (std::atoi(e))
-      s.orderSign = 0.f;
+  s.leafMax = K.leafMax.value_or(g.geo == 1 ? 3u : (uint32_t)VR_LEAF_MAX);
+  s.orderAxis = c->ts[0];                                  // rays travel along this axis ...
+  s.orderSign = K.noChildOrder ? 0.f : c->ts[3] ? 1.f : -1.f; // ... from its max (min) side: that child first
   s.n = N;
   s.geo = g.geo;
   s.D = g.D;
   s.nbDist = 2 * g.diskRadius;
-  s.mortonAniso = VR_MORTON_ANISO;
-  if (const char *e = std::getenv("VR_MORTON_ANISO"))
-    s.mortonAniso = std::max(1.f, (float)std::atof(e));
+  s.mortonAniso = K.mortonAniso;
   VR_HIP(c, c->dNormal3.ensure((size_t)N * 3));
   VR_HIP(c, hipMemcpyAsync(c->dNormal3.p, g.normal3.data(), (size_t)N * 12, hipMemcpyHostToDevice, c->stream));
   if (disk) {
@@ -1132,7 +1260,7 @@ static int build_scene(vr_context *c) {
     VR_HIP(c, c->dNbIds.ensure(total));
     c->nbTotal = total;
     s.nbIds = c->dNbIds.p;
-    VR_HIP(c, launch_setup_neighbors(s, (overflow || std::getenv("VR_NB_TWO_PASS")) ? 1 : 3, c->stream));
+    VR_HIP(c, launch_setup_neighbors(s, (overflow || K.nbTwoPass) ? 1 : 3, c->stream));
   } else {
     c->nbTotal = 0;
     VR_HIP(c, hipMemsetAsync(c->dNbOff.p, 0, ((size_t)N + 1) * 4, c->stream));
@@ -1200,12 +1328,86 @@ static uint64_t rays_of_apply(const vr_context *c) {
   return c->numRaysFixed == 0 ? srcPoints * c->numRaysPerPoint : c->numRaysFixed;
 }
 
-// everything one particle's launch needs (scene build and areas only when they changed)
-static int prepare_one(vr_context *c) {
-  VR_HIP(c, hipSetDevice(c->device));
+// ---- apply() set-up: prepare_one and its stages ------------------------------------------------------------------
+
+// what the stages of one prepare_one hand on to each other
+struct PrepareState {
+  bool stateful = false;    // a stateful run-time model (its generator, per-ray state and material ids)
+  bool flatScene = false;   // the surface shown to the source lies in one plane and the scene box is thin along its axis
+  bool smallScene = false;  // the whole scene goes into LDS (MODE 4)
+  bool heightField = false; // the height field over the source plane is built (the frame's VR_F_HF_*)
+  const int32_t *dMaterial = nullptr; // a stateful model's material ids (the frame's VR_F_MAT_*)
+};
+
+// the largest coordinate of the BVH's root box (at least 1e-3): the scale of the float rounding the pads cover
+static float scene_scale(const vr_context *c) {
+  float scale = 1e-3f;
+  for (int k = 0; k < 3; ++k)
+    scale = std::max(scale, std::max(std::fabs(c->sceneLo[k]), std::fabs(c->sceneHi[k])));
+  return scale;
+}
+
+// sort-bin grid for a batch of `count` rays: far-plane cells holding ~perBin rays each
+static void size_bins(int D, uint64_t count, uint32_t perBin, TraceParams &p, uint32_t &numBins) {
+  const uint64_t target = std::max<uint64_t>(count / std::max<uint32_t>(perBin, 1u), 1);
+  if (D == 2) {
+    p.binT1 = (int)std::min<uint64_t>(target, 1u << 22);
+    p.binT2 = 1;
+    p.binTiles = 1;
+    numBins = (uint32_t)p.binT1;
+  } else {
+    p.binT1 = p.binT2 = (int)std::min<double>(4096.0, std::max(1.0, std::ceil(std::sqrt((double)target))));
+    p.binTiles = (p.binT1 + 7) / 8;
+    numBins = (uint32_t)p.binTiles * (uint32_t)p.binTiles * 64u;
+  }
+}
+
+// The LOOSE bins of a scene with relief (TraceParams, round 4): a grid a third as fine per axis as the tight one p.binT*
+// describes — they hold the grazing rays, about a tenth of all — whose cursors and record slots (+ an overflow region of
+// p.ovCap slots) lie behind the tight bins' in the same two buffers.
+static void size_loose(int D, TraceParams &p) {
+  p.looseT1 = std::max(1, p.binT1 / 3);
+  if (D == 2) {
+    p.looseT2 = 1;
+    p.looseTiles = 1;
+    p.looseNumBins = (uint32_t)p.looseT1;
+  } else {
+    p.looseT2 = std::max(1, p.binT2 / 3);
+    p.looseTiles = (p.looseT1 + 7) / 8;
+    p.looseNumBins = (uint32_t)p.looseTiles * (uint32_t)((p.looseT2 + 7) / 8) * 64u;
+  }
+  p.looseCntBase = (p.numBins + 1u + 3u) & ~3u;
+  p.looseSlotBase = p.numBins * p.binCap + p.ovCap;
+}
+
+// The ray-stream buffers for batches of `cap` rays: the sort-bin grid (into p.binT*), the record slots (bins + overflow
+// region) and the bin-cursor words; with relief, the loose bins and their overflow region behind the tight ones.
+struct StreamExtent {
+  uint32_t numBins = 0;
+  size_t slots = 0, cntWords = 0;
+  size_t looseSlots = 0; // (relief) record slots of the loose bins + their overflow region
+};
+static StreamExtent stream_extent(int D, uint32_t cap, uint32_t perBin, bool relief, TraceParams &p) {
+  StreamExtent e;
+  size_bins(D, cap, perBin, p, e.numBins);
+  e.slots = (size_t)e.numBins * p.binCap + cap;
+  e.cntWords = (size_t)e.numBins + 1;
+  if (relief) {
+    TraceParams q = p;
+    q.numBins = e.numBins;
+    q.ovCap = cap;
+    size_loose(D, q);
+    e.looseSlots = (size_t)q.looseNumBins * p.binCap + cap;
+    e.slots = (size_t)q.looseSlotBase + e.looseSlots;
+    e.cntWords = (size_t)q.looseCntBase + q.looseNumBins + 1;
+  }
+  return e;
+}
+
+// checkSettings (rayTraceDisk.hpp:196-217): the reference logs and carries on; with nothing to trace we stop and report
+// through the error flag.
+static int check_settings(vr_context *c) {
   c->info = vr_trace_info{};
-  // checkSettings (rayTraceDisk.hpp:196-217): the reference logs and carries
-  // on; with nothing to trace we stop and report through the error flag.
   if (!c->haveParticle) {
     c->info.error = 1;
     return fail(c, VR_E_INVALID, "No particle was specified in rayTrace. Aborting.");
@@ -1214,165 +1416,142 @@ static int prepare_one(vr_context *c) {
     c->info.error = 1;
     return fail(c, VR_E_INVALID, "No geometry was passed to rayTrace. Aborting.");
   }
-  const int D = c->geo.D;
   const int dir = effective_direction(c);
-  if (D == 2 && (dir == VR_POS_Z || dir == VR_NEG_Z)) {
+  if (c->geo.D == 2 && (dir == VR_POS_Z || dir == VR_NEG_Z)) {
     c->info.error = 1;
     return fail(c, VR_E_INVALID, "Invalid source direction in 2D geometry. Aborting.");
   }
   if (c->geo.geo == 0 && c->geo.diskRadius > c->geo.gridDelta)
     c->info.warning = 1;
+  return VR_OK;
+}
 
-  const auto t0 = std::chrono::steady_clock::now();
-  TraceParams &p = c->params;
-  const bool redoConfig = c->configDirty || c->geometryDirty;
-  if (redoConfig) {
-    // bounding box, trace settings, boundary (rayTraceDisk.hpp:21-27)
-    for (int k = 0; k < 3; ++k) {
-      c->bbLo[k] = c->geo.minC[k];
-      c->bbHi[k] = c->geo.maxC[k];
-    }
-    host_adjust_bbox(c->bbLo, c->bbHi, D, dir, c->geo.geo == 0 ? c->geo.diskRadius : c->geo.gridDelta);
-    c->ts = host_trace_settings(dir);
-    {
-      Tri walls[8];
-      host_build_walls(c->bbLo, c->bbHi, c->ts[1], c->ts[2], walls);
-      float *tbl = c->wallsHost; // (uploaded with the launch's scalar frame: end of this function)
-      for (int i = 0; i < 8; ++i) {
-        std::memcpy(tbl + 12 * i, walls[i].v0, 12);
-        std::memcpy(tbl + 12 * i + 3, walls[i].e1, 12);
-        std::memcpy(tbl + 12 * i + 6, walls[i].e2, 12);
-        std::memcpy(tbl + 12 * i + 9, walls[i].Ng, 12);
-      }
-    }
-    // rayBoundary.hpp:23-25: conditions are picked by AXIS
-    c->boundaryConds[0] = c->bcs[c->ts[1]];
-    c->boundaryConds[1] = (D == 2 && c->ts[2] >= 2) ? 0 : c->bcs[c->ts[2]];
-    // SourceRandom::getSourceArea (raySourceRandom.hpp:40-47)
-    const int f = c->ts[1], s = c->ts[2];
-    c->sourceArea = D == 2 ? (c->bbHi[f] - c->bbLo[f]) : (c->bbHi[f] - c->bbLo[f]) * (c->bbHi[s] - c->bbLo[s]);
-    c->keyCoord = host_sort_plane(c->geo, c->ts[0], c->ts[3] ? c->geo.minC[c->ts[0]] : c->geo.maxC[c->ts[0]],
-                                 &c->keyShare);
+// bounding box, trace settings, walls, boundary conditions (rayTraceDisk.hpp:21-27), source area and the sort plane
+static void setup_source_frame(vr_context *c) {
+  const int D = c->geo.D;
+  for (int k = 0; k < 3; ++k) {
+    c->bbLo[k] = c->geo.minC[k];
+    c->bbHi[k] = c->geo.maxC[k];
   }
+  host_adjust_bbox(c->bbLo, c->bbHi, D, effective_direction(c), c->geo.geo == 0 ? c->geo.diskRadius : c->geo.gridDelta);
+  c->ts = host_trace_settings(effective_direction(c));
+  {
+    Tri walls[8];
+    host_build_walls(c->bbLo, c->bbHi, c->ts[1], c->ts[2], walls);
+    float *tbl = c->wallsHost; // (uploaded with the launch's scalar frame: write_launch_frame)
+    for (int i = 0; i < 8; ++i) {
+      std::memcpy(tbl + 12 * i, walls[i].v0, 12);
+      std::memcpy(tbl + 12 * i + 3, walls[i].e1, 12);
+      std::memcpy(tbl + 12 * i + 6, walls[i].e2, 12);
+      std::memcpy(tbl + 12 * i + 9, walls[i].Ng, 12);
+    }
+  }
+  // rayBoundary.hpp:23-25: conditions are picked by AXIS
+  c->boundaryConds[0] = c->bcs[c->ts[1]];
+  c->boundaryConds[1] = (D == 2 && c->ts[2] >= 2) ? 0 : c->bcs[c->ts[2]];
+  // SourceRandom::getSourceArea (raySourceRandom.hpp:40-47)
+  const int f = c->ts[1], s = c->ts[2];
+  c->sourceArea = D == 2 ? (c->bbHi[f] - c->bbLo[f]) : (c->bbHi[f] - c->bbLo[f]) * (c->bbHi[s] - c->bbLo[s]);
+  c->keyCoord = host_sort_plane(c->geo, c->ts[0], c->ts[3] ? c->geo.minC[c->ts[0]] : c->geo.maxC[c->ts[0]], &c->keyShare);
+}
 
+// exposed area of every primitive, resident on the device for normalizeFlux
+// (computeDiskAreas, rayGeometryDisk.hpp:266-354: one thread per disk; triangle areas come
+// with the mesh, rayGeometryTriangle.hpp:145-176)
+static int compute_areas(vr_context *c) {
   const uint32_t N = c->geo.numPrims;
-  // the BVH's child order follows the source side: a new source direction rebuilds it
-  if (c->builtOrderAxis != c->ts[0] || c->builtOrderSign != (c->ts[3] ? 1.f : -1.f))
-    c->geometryDirty = true;
-  if (c->geometryDirty) {
-    int r = build_scene(c);
-    if (r != VR_OK)
-      return r;
-    c->geometryDirty = false;
-    ++c->bvhBuilds;
-    c->builtOrderAxis = c->ts[0];
-    c->builtOrderSign = c->ts[3] ? 1.f : -1.f;
-  }
-  // exposed area of every primitive, resident on the device for normalizeFlux
-  // (computeDiskAreas, rayGeometryDisk.hpp:266-354: one thread per disk; triangle areas come
-  // with the mesh, rayGeometryTriangle.hpp:145-176)
-  if (redoConfig || !c->areasValid) {
-    VR_HIP(c, c->dAreas.ensure(N));
-    c->diskAreasHostValid = false;
-    if (c->geo.geo == 0) {
-      AreaParams ap{};
-      ap.D = D;
-      ap.firstDir = c->ts[1];
-      ap.secondDir = c->ts[2];
-      // rayGeometryDisk.hpp:281-284 indexes the 2-entry BC array by AXIS; axis 2 is out of
-      // range there, entry 1 is used for it
-      ap.bcFirst = c->boundaryConds[c->ts[1] > 1 ? 1 : c->ts[1]];
-      ap.bcSecond = c->boundaryConds[c->ts[2] > 1 ? 1 : c->ts[2]];
-      for (int k = 0; k < 3; ++k) {
-        ap.minC[k] = c->geo.minC[k];
-        ap.maxC[k] = c->geo.maxC[k];
-      }
-      const char *hb = std::getenv("VR_HOST_BUILD");
-      if (hb && std::atoi(hb)) {
-        host_disk_areas(c->geo, ap, c->diskAreas);
-        VR_HIP(c, hipMemcpy(c->dAreas.p, c->diskAreas.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-        c->diskAreasHostValid = true;
-      } else {
-        VR_HIP(c, launch_disk_areas(c->dDisk4.p, c->dNormal3.p, N, ap, c->dAreas.p, c->stream));
-      }
+  VR_HIP(c, c->dAreas.ensure(N));
+  c->diskAreasHostValid = false;
+  if (c->geo.geo == 0) {
+    AreaParams ap{};
+    ap.D = c->geo.D;
+    ap.firstDir = c->ts[1];
+    ap.secondDir = c->ts[2];
+    // rayGeometryDisk.hpp:281-284 indexes the 2-entry BC array by AXIS; axis 2 is out of
+    // range there, entry 1 is used for it
+    ap.bcFirst = c->boundaryConds[c->ts[1] > 1 ? 1 : c->ts[1]];
+    ap.bcSecond = c->boundaryConds[c->ts[2] > 1 ? 1 : c->ts[2]];
+    for (int k = 0; k < 3; ++k) {
+      ap.minC[k] = c->geo.minC[k];
+      ap.maxC[k] = c->geo.maxC[k];
+    }
+    if (c->knobs.hostBuild) {
+      host_disk_areas(c->geo, ap, c->diskAreas);
+      VR_HIP(c, hipMemcpy(c->dAreas.p, c->diskAreas.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+      c->diskAreasHostValid = true;
     } else {
-      VR_HIP(c, hipMemcpyAsync(c->dAreas.p, c->geo.triAreas.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-      VR_HIP(c, hipStreamSynchronize(c->stream));
+      VR_HIP(c, launch_disk_areas(c->dDisk4.p, c->dNormal3.p, N, ap, c->dAreas.p, c->stream));
     }
-    c->areasValid = true;
+  } else {
+    VR_HIP(c, hipMemcpyAsync(c->dAreas.p, c->geo.triAreas.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
   }
-  // per-primitive sticking from the material map (gpu::Particle-style, rayParticle.hpp:208-218)
-  const bool redoSticking = redoConfig || c->particleDirty;
-  if (redoSticking)
-    c->havePrimSticking = false;
-  if (redoSticking && !c->matStickIds.empty()) {
-    int ro = ensure_host_order(c);
-    if (ro != VR_OK)
-      return ro;
-    std::vector<float> ps(N);
-    for (uint32_t q = 0; q < N; ++q) {
-      const uint32_t o = c->bvh.order[q];
-      const int mat = o < c->geo.materialIds.size() ? c->geo.materialIds[o] : 0;
-      float s = c->sticking;
-      for (size_t m = 0; m < c->matStickIds.size(); ++m)
-        if (c->matStickIds[m] == mat)
-          s = c->matStickVals[m];
-      ps[q] = s;
-    }
-    VR_HIP(c, c->dPrimSticking.ensure(N));
-    VR_HIP(c, hipMemcpy(c->dPrimSticking.p, ps.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    c->havePrimSticking = true;
-  }
-  const float *dStick = c->havePrimSticking ? c->dPrimSticking.p : nullptr;
-  c->configDirty = false;
-  c->particleDirty = false;
-  // Trace::setGlobalData: every vector padded to one stride, one upload
-  if (c->globalDirty) {
-    uint32_t stride = 0;
-    for (const auto &v : c->globalVecs)
-      stride = std::max<uint32_t>(stride, (uint32_t)v.size());
-    c->globalStride = stride;
-    if (stride && !c->globalVecs.empty()) {
-      std::vector<float> flat((size_t)stride * c->globalVecs.size(), 0.f);
-      for (size_t v = 0; v < c->globalVecs.size(); ++v)
-        std::copy(c->globalVecs[v].begin(), c->globalVecs[v].end(), flat.begin() + v * stride);
-      VR_HIP(c, c->dGlobalVec.ensure(flat.size()));
-      VR_HIP(c, hipMemcpy(c->dGlobalVec.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (!c->globalScalars.empty()) {
-      VR_HIP(c, c->dGlobalScalars.ensure(c->globalScalars.size()));
-      VR_HIP(c, hipMemcpy(c->dGlobalScalars.p, c->globalScalars.data(), c->globalScalars.size() * 4, hipMemcpyHostToDevice));
-    }
-    c->globalDirty = false;
-  }
+  c->areasValid = true;
+  return VR_OK;
+}
 
-  const uint64_t numRays = rays_of_apply(c);
-  c->numRaysLast = numRays;
-  uint64_t first = 0, last = numRays;
-  if (c->rayCount) {
-    first = std::min(c->rayFirst, numRays);
-    last = std::min(numRays, first + c->rayCount);
+// per-primitive sticking from the material map (gpu::Particle-style, rayParticle.hpp:208-218), the particle's own buffer
+static int prepare_sticking(vr_context *c, ParticleLaunch &L) {
+  L.params.primSticking = nullptr;
+  if (c->matStickIds.empty())
+    return VR_OK;
+  int ro = ensure_host_order(c);
+  if (ro != VR_OK)
+    return ro;
+  const uint32_t N = c->geo.numPrims;
+  std::vector<float> ps(N);
+  for (uint32_t q = 0; q < N; ++q) {
+    const uint32_t o = c->bvh.order[q];
+    const int mat = o < c->geo.materialIds.size() ? c->geo.materialIds[o] : 0;
+    float s = c->sticking;
+    for (size_t m = 0; m < c->matStickIds.size(); ++m)
+      if (c->matStickIds[m] == mat)
+        s = c->matStickVals[m];
+    ps[q] = s;
   }
-  c->rayFirstLaunch = first;
-  c->rayEndLaunch = last;
-  uint32_t seed = c->runNumber + c->rngSeed; // rayTraceKernel.hpp:100
-  if (c->haveSharedSeed) { // (vr_apply_sharded with random seeds: the one seed every rank agreed on)
-    seed = c->sharedSeed;
-  } else if (c->useRandomSeed) {
-    std::random_device rd;
-    seed = (uint32_t)rd();
+  VR_HIP(c, L.primSticking.ensure(N));
+  VR_HIP(c, hipMemcpy(L.primSticking.p, ps.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+  L.params.primSticking = L.primSticking.p;
+  return VR_OK;
+}
+
+// Trace::setGlobalData: every vector padded to one stride, one upload
+static int upload_global_data(vr_context *c) {
+  uint32_t stride = 0;
+  for (const auto &v : c->globalVecs)
+    stride = std::max<uint32_t>(stride, (uint32_t)v.size());
+  c->globalStride = stride;
+  if (stride && !c->globalVecs.empty()) {
+    std::vector<float> flat((size_t)stride * c->globalVecs.size(), 0.f);
+    for (size_t v = 0; v < c->globalVecs.size(); ++v)
+      std::copy(c->globalVecs[v].begin(), c->globalVecs[v].end(), flat.begin() + v * stride);
+    VR_HIP(c, c->dGlobalVec.ensure(flat.size()));
+    VR_HIP(c, hipMemcpy(c->dGlobalVec.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
   }
+  if (!c->globalScalars.empty()) {
+    VR_HIP(c, c->dGlobalScalars.ensure(c->globalScalars.size()));
+    VR_HIP(c, hipMemcpy(c->dGlobalScalars.p, c->globalScalars.data(), c->globalScalars.size() * 4, hipMemcpyHostToDevice));
+  }
+  c->globalDirty = false;
+  return VR_OK;
+}
+
+// the particle's kernel variant (absorbing, built-in, extended, stateful), the small-scene layout and whether the scene
+// is flat
+static int choose_particle_kernel(vr_context *c, ParticleLaunch &L, PrepareState &S) {
+  TraceParams &p = L.params;
+  const uint32_t N = c->geo.numPrims;
   // ABSORB: every hit takes the whole weight -> nothing after the first
   // surface hit is observable
-  c->absorb = c->sticking >= 1.f;
+  L.absorb = c->sticking >= 1.f;
   for (float v : c->matStickVals)
-    c->absorb = c->absorb && v >= 1.f;
+    L.absorb = L.absorb && v >= 1.f;
   // the extended kernel (vr_particles.hpp) serves everything beyond the two built-in particles
   const bool extended = c->particleKind >= VR_PARTICLE_CONED_COSINE || c->useWdist || c->meanFreePath > 0.f;
   if (extended)
-    c->absorb = false;
+    L.absorb = false;
   if (!c->hostOrg.empty() && !c->hostWeights.empty())
-    c->absorb = false; // (the absorbing kernels credit unit weights)
+    L.absorb = false; // (the absorbing kernels credit unit weights)
   // (the rare, register-hungry options — coned-cosine model, WDIST crediting, mean free path — have an instantiation
   //  of their own: multi-label and per-material particles should not pay for them)
   bool extFull = Particles::needsFull(c->particleKind) || c->useWdist || c->meanFreePath > 0.f;
@@ -1386,12 +1565,11 @@ static int prepare_one(vr_context *c) {
       return fail(c, VR_E_INVALID, "a stateful particle model (numState > 0) runs its init on the device before the source "
                                    "sample: SourceRandom only (plain or with a primary direction), not SourceGrid or a host source");
   }
-  const bool stateful = c->userModel >= 0 && c->userModels[c->userModel].numState > 0;
-  c->kernelParticle = extended ? (extFull ? (int)P_EXT_FULL : (int)P_EXT) : c->particleKind;
+  S.stateful = c->userModel >= 0 && c->userModels[c->userModel].numState > 0;
+  L.kernelParticle = extended ? (extFull ? (int)P_EXT_FULL : (int)P_EXT) : c->particleKind;
   // a scene of a few hundred primitives goes into LDS as a whole (MODE 4: the general kernel — also for
   // absorbing particles — of whatever particle): pair nodes, records, neighbourhood, accumulators (one plane
   // per data label), per-material sticking
-  bool smallScene = false;
   {
     const uint32_t recB = c->geo.geo == 0 ? 32u : 64u;
     uint32_t off[6], o = 0, nbTotal = 0;
@@ -1406,114 +1584,101 @@ static int prepare_one(vr_context *c) {
     put(2, ((size_t)N + 1) * 4);
     put(3, (size_t)nbTotal * 4);
     put(4, (size_t)N * 8 * c->numData);
-    put(5, c->havePrimSticking ? (size_t)N * 4 : 0);
-    smallScene = o <= VR_SMALL_LDS && c->numNodes > 0;
-    if (const char *e = std::getenv("VR_SMALL_SCENE"))
-      smallScene = smallScene && std::atoi(e) != 0;
+    put(5, p.primSticking ? (size_t)N * 4 : 0);
+    S.smallScene = o <= VR_SMALL_LDS && c->numNodes > 0 && c->knobs.smallScene;
     for (int k = 0; k < 6; ++k)
       p.smallOff[k] = off[k];
     p.smallNb = nbTotal;
     p.smallBytes = (o + 255u) & ~255u;
-    if (smallScene)
-      c->absorb = false; // (ray records with the RNG cursors: the general kernel reads them)
+    if (S.smallScene)
+      L.absorb = false; // (ray records with the RNG cursors: the general kernel reads them)
   }
-  // ---- flat WITH RELIEF?  (DESIGN.md 5.2 "relief packets")  The flat-scene kernels owe their speed to the packet
-  // query, and the query clips its rays to the SCENE box: half a grid cell of relief lets the grazing rays of a wave
-  // stretch its box over hundreds of cells.  Where the scene is thin along the source axis and the relief field says that
-  // few rays would be grazing ones (ReliefParams::stats), the rays are sorted by their predicted first hit, the grazing ones are filed apart
-  // (bin_of_relief, vr_trace.hip) and the query clips to the LOCAL relief (relief_clip, vr_device.hpp): MODE 5 / 6.
-  const bool flatScene = c->keyShare >= 0.95f && (c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]]) <= 0.25f * c->geo.gridDelta;
-  c->reliefScene = false;
-  {
-    float maxThick = 8.f, travel = 1.5f;
-    if (const char *e = std::getenv("VR_RELIEF_MAX_THICK"))
-      maxThick = (float)std::atof(e);
-    if (const char *e = std::getenv("VR_RELIEF_TRAVEL"))
-      travel = std::max(0.05f, (float)std::atof(e));
-    const float thickScene = c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]];
-    const bool plainSource = !c->usePrimaryDirection && c->gridPoints.empty() && c->hostOrg.empty();
-    const bool kernelOk = c->absorb || (c->geo.geo == 0 && c->kernelParticle <= (int)P_EXT);
-    bool want = !flatScene && !smallScene && plainSource && kernelOk && c->userModel < 0 && c->geo.gridDelta > 0.f &&
-                thickScene <= maxThick * c->geo.gridDelta && !std::getenv("VR_NO_RELIEF");
-    if (want) {
-      const bool stale = c->rfBuild != c->bvhBuilds || c->rfAxes[0] != c->ts[0] || c->rfAxes[1] != c->ts[1] ||
-                         c->rfAxes[2] != c->ts[2] || c->rfAxes[3] != c->ts[3] || c->rf.travel != travel * c->geo.gridDelta;
-      if (stale) {
-        ReliefParams &q = c->rf;
-        q.prims = c->dPrims.p;
-        q.n = N;
-        q.geo = c->geo.geo;
-        q.ax = c->ts[0];
-        q.a1 = c->ts[1];
-        q.a2 = c->ts[2];
-        const float ext1 = c->sceneHi[q.a1] - c->sceneLo[q.a1], ext2 = D == 3 ? c->sceneHi[q.a2] - c->sceneLo[q.a2] : 0.f;
-        float cells = 1.f; // fine tile side in grid cells
-        if (const char *e = std::getenv("VR_RELIEF_TILE"))
-          cells = std::max(0.25f, (float)std::atof(e));
-        float tile = std::max(cells * c->geo.gridDelta, std::max(ext1, ext2) / 1024.f);
-        q.tile = tile;
-        q.invTile = 1.f / tile;
-        q.lo1 = c->sceneLo[q.a1];
-        q.lo2 = D == 3 ? c->sceneLo[q.a2] : 0.f;
-        q.nx = std::max(1, std::min(1024, (int)std::ceil(ext1 / tile)));
-        q.ny = D == 3 ? std::max(1, std::min(1024, (int)std::ceil(ext2 / tile))) : 1;
-        q.k = std::max(2, (std::max(q.nx, q.ny) + 255) / 256);
-        if (const char *e = std::getenv("VR_RELIEF_COARSE_K"))
-          q.k = std::max(1, std::atoi(e));
-        q.cnx = (q.nx + q.k - 1) / q.k;
-        q.cny = (q.ny + q.k - 1) / q.k;
-        float scale = 1e-3f;
-        for (int k = 0; k < 3; ++k)
-          scale = std::max(scale, std::max(std::fabs(c->sceneLo[k]), std::fabs(c->sceneHi[k])));
-        q.pad = 1e-5f * scale;
-        q.travel = travel * c->geo.gridDelta;
-        q.emptyMid = c->keyCoord;
-        VR_HIP(c, c->dRfRawLo.ensure((size_t)q.nx * q.ny));
-        VR_HIP(c, c->dRfRawHi.ensure((size_t)q.nx * q.ny));
-        VR_HIP(c, c->dRfFine.ensure((size_t)q.nx * q.ny * 2));
-        VR_HIP(c, c->dRfCoarse.ensure((size_t)q.cnx * q.cny * 2));
-        VR_HIP(c, c->dRfStats.ensure(2));
-        q.rawLo = c->dRfRawLo.p;
-        q.rawHi = c->dRfRawHi.p;
-        q.fine = c->dRfFine.p;
-        q.coarse = c->dRfCoarse.p;
-        q.stats = c->dRfStats.p;
-        VR_HIP(c, launch_relief_field(q, c->stream));
-        uint32_t st[2] = {0, 0};
-        VR_HIP(c, hipMemcpyAsync(st, q.stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-        VR_HIP(c, hipStreamSynchronize(c->stream));
-        c->rfLooseShare = st[0] ? (float)st[1] / 4096.f / (float)st[0] : 1.f;
-        c->rfBuild = c->bvhBuilds;
-        for (int k = 0; k < 4; ++k)
-          c->rfAxes[k] = c->ts[k];
-      }
-      // (the share of a cosine source's rays that the generator would file as loose, from the coarse tiles' thickness:
-      //  where most rays are loose the structured-scene kernels do the work anyway, without the second launch)
-      float share = 0.3f;
-      if (const char *e = std::getenv("VR_RELIEF_SHARE"))
-        share = (float)std::atof(e);
-      c->reliefScene = c->rfLooseShare <= share;
+  S.flatScene = c->keyShare >= 0.95f && (c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]]) <= 0.25f * c->geo.gridDelta;
+  return VR_OK;
+}
+
+// ---- flat WITH RELIEF?  (DESIGN.md 5.2 "relief packets")  The flat-scene kernels owe their speed to the packet
+// query, and the query clips its rays to the SCENE box: half a grid cell of relief lets the grazing rays of a wave
+// stretch its box over hundreds of cells.  Where the scene is thin along the source axis and the relief field says that
+// few rays would be grazing ones (ReliefParams::stats), the rays are sorted by their predicted first hit, the grazing ones are filed apart
+// (bin_of_relief, vr_trace.hip) and the query clips to the LOCAL relief (relief_clip, vr_device.hpp): MODE 5 / 6.
+static int build_relief_field(vr_context *c, ParticleLaunch &L, const PrepareState &S) {
+  const Knobs &K = c->knobs;
+  TraceParams &p = L.params;
+  const int D = c->geo.D;
+  const float travel = K.reliefTravel;
+  L.relief = false;
+  const float thickScene = c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]];
+  const bool plainSource = !c->usePrimaryDirection && c->gridPoints.empty() && c->hostOrg.empty();
+  const bool kernelOk = L.absorb || (c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT);
+  const bool want = !S.flatScene && !S.smallScene && plainSource && kernelOk && c->userModel < 0 && c->geo.gridDelta > 0.f &&
+                    thickScene <= K.reliefMaxThick * c->geo.gridDelta && !K.noRelief;
+  if (want) {
+    const bool stale = c->rfBuild != c->bvhBuilds || c->rfAxes[0] != c->ts[0] || c->rfAxes[1] != c->ts[1] ||
+                       c->rfAxes[2] != c->ts[2] || c->rfAxes[3] != c->ts[3] || c->rf.travel != travel * c->geo.gridDelta;
+    if (stale) {
+      ReliefParams &q = c->rf;
+      q.prims = c->dPrims.p;
+      q.n = c->geo.numPrims;
+      q.geo = c->geo.geo;
+      q.ax = c->ts[0];
+      q.a1 = c->ts[1];
+      q.a2 = c->ts[2];
+      const float ext1 = c->sceneHi[q.a1] - c->sceneLo[q.a1], ext2 = D == 3 ? c->sceneHi[q.a2] - c->sceneLo[q.a2] : 0.f;
+      const float tile = std::max(K.reliefTile * c->geo.gridDelta, std::max(ext1, ext2) / 1024.f); // (fine tile)
+      q.tile = tile;
+      q.invTile = 1.f / tile;
+      q.lo1 = c->sceneLo[q.a1];
+      q.lo2 = D == 3 ? c->sceneLo[q.a2] : 0.f;
+      q.nx = std::max(1, std::min(1024, (int)std::ceil(ext1 / tile)));
+      q.ny = D == 3 ? std::max(1, std::min(1024, (int)std::ceil(ext2 / tile))) : 1;
+      q.k = K.reliefCoarseK.value_or(std::max(2, (std::max(q.nx, q.ny) + 255) / 256));
+      q.cnx = (q.nx + q.k - 1) / q.k;
+      q.cny = (q.ny + q.k - 1) / q.k;
+      q.pad = 1e-5f * scene_scale(c);
+      q.travel = travel * c->geo.gridDelta;
+      q.emptyMid = c->keyCoord;
+      VR_HIP(c, c->dRfRawLo.ensure((size_t)q.nx * q.ny));
+      VR_HIP(c, c->dRfRawHi.ensure((size_t)q.nx * q.ny));
+      VR_HIP(c, c->dRfFine.ensure((size_t)q.nx * q.ny * 2));
+      VR_HIP(c, c->dRfCoarse.ensure((size_t)q.cnx * q.cny * 2));
+      VR_HIP(c, c->dRfStats.ensure(2));
+      q.rawLo = c->dRfRawLo.p;
+      q.rawHi = c->dRfRawHi.p;
+      q.fine = c->dRfFine.p;
+      q.coarse = c->dRfCoarse.p;
+      q.stats = c->dRfStats.p;
+      VR_HIP(c, launch_relief_field(q, c->stream));
+      uint32_t st[2] = {0, 0};
+      VR_HIP(c, hipMemcpyAsync(st, q.stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+      VR_HIP(c, hipStreamSynchronize(c->stream));
+      c->rfLooseShare = st[0] ? (float)st[1] / 4096.f / (float)st[0] : 1.f;
+      c->rfBuild = c->bvhBuilds;
+      for (int k = 0; k < 4; ++k)
+        c->rfAxes[k] = c->ts[k];
     }
-    p.reliefCoarse = c->reliefScene ? c->rf.coarse : nullptr;
-    p.rcLo1 = c->rf.lo1;
-    p.rcLo2 = c->rf.lo2;
-    p.rcInvT = c->reliefScene ? c->rf.invTile / (float)c->rf.k : 0.f;
-    p.rcNx = c->rf.cnx;
-    p.rcNy = c->rf.cny;
-    p.reliefTravel = travel * c->geo.gridDelta;
-    {
-      // the tile walk of relief_clip starts where the ray enters the SCENE box: a ray that would cross more than `steps`
-      // tiles on its way through it is filed as loose too
-      float steps = 6.f;
-      if (const char *e = std::getenv("VR_RELIEF_STEPS"))
-        steps = std::max(1.f, (float)std::atof(e));
-      p.reliefTanMax = thickScene > 0.f ? steps * c->rf.tile / thickScene : 3.0e38f;
-    }
-    p.reliefLookups = 1; // (2: tight launch -0.1 ms, generator +0.4 ms per 1e8 rays — a random 8-byte gather per ray is a 128-byte line from L2)
-    if (const char *e = std::getenv("VR_RELIEF_LOOKUPS"))
-      p.reliefLookups = std::min(2, std::max(0, std::atoi(e)));
+    // (the share of a cosine source's rays that the generator would file as loose, from the coarse tiles' thickness:
+    //  where most rays are loose the structured-scene kernels do the work anyway, without the second launch)
+    L.relief = c->rfLooseShare <= K.reliefShare;
   }
-  // accumulators: one plane per data label, each replicated accReplicas times
+  p.reliefCoarse = L.relief ? c->rf.coarse : nullptr;
+  p.rcLo1 = c->rf.lo1;
+  p.rcLo2 = c->rf.lo2;
+  p.rcInvT = L.relief ? c->rf.invTile / (float)c->rf.k : 0.f;
+  p.rcNx = c->rf.cnx;
+  p.rcNy = c->rf.cny;
+  p.reliefTravel = travel * c->geo.gridDelta;
+  // the tile walk of relief_clip starts where the ray enters the SCENE box: a ray that would cross more than `steps`
+  // tiles on its way through it is filed as loose too
+  p.reliefTanMax = thickScene > 0.f ? K.reliefSteps * c->rf.tile / thickScene : 3.0e38f;
+  // (2 look-ups: tight launch -0.1 ms, generator +0.4 ms per 1e8 rays — a random 8-byte gather per ray is a 128-byte line from L2)
+  p.reliefLookups = K.reliefLookups;
+  return VR_OK;
+}
+
+// accumulators: one plane per data label of all particles, each replicated accReplicas times
+static int ensure_accumulators(vr_context *c) {
+  const uint32_t N = c->geo.numPrims;
   if (c->accPlanes != c->totalData) {
     VR_HIP(c, c->dFluxAcc.ensure((size_t)c->accStride * c->accReplicas * c->totalData));
     VR_HIP(c, c->dFluxOrig.ensure((size_t)N * c->totalData));
@@ -1521,167 +1686,153 @@ static int prepare_one(vr_context *c) {
   }
   if (c->boundFlux && c->boundFluxN != N * c->totalData)
     return fail(c, VR_E_STATE, "bound accumulator buffer does not hold numPrims x numData int64");
-  // source data
-  if (c->sourceDirty) {
-    if (!c->gridPoints.empty()) {
-      VR_HIP(c, c->dGrid.ensure(c->gridPoints.size()));
-      VR_HIP(c, hipMemcpy(c->dGrid.p, c->gridPoints.data(), c->gridPoints.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (!c->hostOrg.empty()) {
-      VR_HIP(c, c->dHostOrg.ensure(c->hostOrg.size()));
-      VR_HIP(c, c->dHostDir.ensure(c->hostDir.size()));
-      VR_HIP(c, hipMemcpy(c->dHostOrg.p, c->hostOrg.data(), c->hostOrg.size() * 4, hipMemcpyHostToDevice));
-      VR_HIP(c, hipMemcpy(c->dHostDir.p, c->hostDir.data(), c->hostDir.size() * 4, hipMemcpyHostToDevice));
-      if (!c->hostDraws.empty()) {
-        VR_HIP(c, c->dHostDraws.ensure(c->hostDraws.size()));
-        VR_HIP(c, hipMemcpy(c->dHostDraws.p, c->hostDraws.data(), c->hostDraws.size() * 4, hipMemcpyHostToDevice));
-      }
-      if (!c->hostWeights.empty()) {
-        VR_HIP(c, c->dHostWeights.ensure(c->hostWeights.size()));
-        VR_HIP(c, hipMemcpy(c->dHostWeights.p, c->hostWeights.data(), c->hostWeights.size() * 4, hipMemcpyHostToDevice));
-      }
-    }
-    c->sourceDirty = false;
-  }
+  return VR_OK;
+}
 
-  // ---- ray stream: one batch of up to 2^27 rays; larger launches run several batches ----------
+// sources other than SourceRandom: SourceGrid origins, host rays (+ draw counts, weights)
+static int upload_source_data(vr_context *c) {
+  if (!c->gridPoints.empty()) {
+    VR_HIP(c, c->dGrid.ensure(c->gridPoints.size()));
+    VR_HIP(c, hipMemcpy(c->dGrid.p, c->gridPoints.data(), c->gridPoints.size() * 4, hipMemcpyHostToDevice));
+  }
+  if (!c->hostOrg.empty()) {
+    VR_HIP(c, c->dHostOrg.ensure(c->hostOrg.size()));
+    VR_HIP(c, c->dHostDir.ensure(c->hostDir.size()));
+    VR_HIP(c, hipMemcpy(c->dHostOrg.p, c->hostOrg.data(), c->hostOrg.size() * 4, hipMemcpyHostToDevice));
+    VR_HIP(c, hipMemcpy(c->dHostDir.p, c->hostDir.data(), c->hostDir.size() * 4, hipMemcpyHostToDevice));
+    if (!c->hostDraws.empty()) {
+      VR_HIP(c, c->dHostDraws.ensure(c->hostDraws.size()));
+      VR_HIP(c, hipMemcpy(c->dHostDraws.p, c->hostDraws.data(), c->hostDraws.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (!c->hostWeights.empty()) {
+      VR_HIP(c, c->dHostWeights.ensure(c->hostWeights.size()));
+      VR_HIP(c, hipMemcpy(c->dHostWeights.p, c->hostWeights.data(), c->hostWeights.size() * 4, hipMemcpyHostToDevice));
+    }
+  }
+  c->sourceDirty = false;
+  return VR_OK;
+}
+
+// ---- ray stream: the apply's ray range, in batches of up to 2^27 rays; larger launches run several batches ----------
+static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState &S) {
+  const Knobs &K = c->knobs;
+  TraceParams &p = L.params;
+  const int D = c->geo.D;
+  const uint64_t numRays = rays_of_apply(c);
+  c->numRaysLast = numRays;
+  uint64_t first = 0, last = numRays;
+  if (c->rayCount) {
+    first = std::min(c->rayFirst, numRays);
+    last = std::min(numRays, first + c->rayCount);
+  }
+  c->rayFirstLaunch = first;
+  c->rayEndLaunch = last;
   const uint64_t span = last - first;
-  uint32_t cap = (uint32_t)std::min<uint64_t>(span, 1ull << 27);
-  if (const char *e = std::getenv("VR_BATCH_RAYS"))
-    cap = (uint32_t)std::min<uint64_t>(span, std::max<long long>(256, std::atoll(e)));
-  cap = std::max<uint32_t>(cap, 1u);
-  c->batchCap = cap;
+  c->batchCap = std::max<uint32_t>((uint32_t)std::min<uint64_t>(span, K.batchRays.value_or(1ull << 27)), 1u);
   // (Overlapping the generator of batch b+1 on a second stream with the tracer of batch b was measured slower in every
   //  round — 13.4 against 11.3 ms per C2 step in round 3: both kernels want the same issue slots and smaller batches
   //  sort less coherently — and is gone from the code.)
   // sort bins: far-plane cells holding ~40 rays each, VR_BIN_CAP slots (measured: 64 / 32 -> 128 / 40: generator
   // 5.0 -> 4.75 ms, C2 +2.5 %)
-  {
-    uint32_t binCap = VR_BIN_CAP, perBin = 40;
-    if (const char *e = std::getenv("VR_BIN_CAP"))
-      binCap = (uint32_t)std::max(8, std::atoi(e));
-    if (const char *e = std::getenv("VR_RAYS_PER_BIN"))
-      perBin = (uint32_t)std::max(1, std::atoi(e));
-    p.binCap = binCap;
-    c->raysPerBin = perBin;
-    uint32_t nb;
-    size_bins(D, cap, perBin, p, nb);
-    c->numBins = nb;
-    size_t slots = (size_t)nb * binCap + cap; // bins + overflow region
-    size_t cntWords = (size_t)nb + 1;
-    if (c->reliefScene) { // the loose bins with an overflow region of their own, behind the tight ones (size_loose)
-      TraceParams q = p;
-      q.numBins = nb;
-      q.ovCap = cap;
-      size_loose(D, q);
-      slots = (size_t)q.looseSlotBase + (size_t)q.looseNumBins * binCap + cap;
-      cntWords = (size_t)q.looseCntBase + q.looseNumBins + 1;
-      // (the loose launch numbers its slots from looseSlotBase on, and bit 31 of such a number marks a spill-queue record)
-      if (slots >= (1ull << 32) || (size_t)q.looseNumBins * binCap + cap >= (1ull << 31))
-        return fail(c, VR_E_STATE, "ray stream too large for 32-bit record slots (relief bins)");
-    }
-    c->slotStride = slots;
-    // 32-byte records for every particle (vr_types.hpp); a non-absorbing particle under a source whose origin plane or
-    // draw count varies (tilted, grid, host rays) adds 16 bytes per ray in a side array
-    // (a stateful model's init draws before the source sample: its draw count varies too)
-    c->recExtra = !c->absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || !c->hostOrg.empty() || stateful);
-    const size_t recFloats = 8;
-    if (c->recExtra)
-      VR_HIP(c, c->dRecExtra.ensure_grow((size_t)cap * 4));
-    if (stateful) // (the state of every ray of a batch, float4 per ray; room for vr_reserve_rays' largest batch)
-      VR_HIP(c, c->dRayState.ensure_grow((size_t)std::max<uint64_t>(cap, std::min<uint64_t>(c->reserveRays, 1ull << 27)) * 4));
-    size_t slotsWant = slots, binsWant = cntWords;
-    if (c->reserveRays > span) { // vr_reserve_rays: room for the largest apply() announced
-      TraceParams q = p;
-      uint32_t nbR = 0;
-      const uint32_t capR = (uint32_t)std::min<uint64_t>(c->reserveRays, 1ull << 27);
-      size_bins(D, capR, perBin, q, nbR);
-      size_t sR = (size_t)nbR * binCap + capR, bR = (size_t)nbR + 1;
-      if (c->reliefScene) {
-        q.numBins = nbR;
-        q.ovCap = capR;
-        size_loose(D, q);
-        sR = (size_t)q.looseSlotBase + (size_t)q.looseNumBins * binCap + capR;
-        bR = (size_t)q.looseCntBase + q.looseNumBins + 1;
-      }
-      slotsWant = std::max(slotsWant, sR);
-      binsWant = std::max(binsWant, bR);
-    }
-    VR_HIP(c, c->dSlotRec.ensure_grow(slotsWant * recFloats));
-    VR_HIP(c, c->dBinCount.ensure_grow(binsWant));
+  p.binCap = K.binCap;
+  c->raysPerBin = K.raysPerBin;
+  const StreamExtent e = stream_extent(D, c->batchCap, K.raysPerBin, L.relief, p);
+  c->numBins = e.numBins;
+  // (the loose launch numbers its slots from looseSlotBase on, and bit 31 of such a number marks a spill-queue record)
+  if (L.relief && (e.slots >= (1ull << 32) || e.looseSlots >= (1ull << 31)))
+    return fail(c, VR_E_STATE, "ray stream too large for 32-bit record slots (relief bins)");
+  c->slotStride = e.slots;
+  // 32-byte records for every particle (vr_types.hpp); a non-absorbing particle under a source whose origin plane or
+  // draw count varies (tilted, grid, host rays) adds 16 bytes per ray in a side array
+  // (a stateful model's init draws before the source sample: its draw count varies too)
+  L.recExtra = !L.absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || !c->hostOrg.empty() || S.stateful);
+  if (L.recExtra)
+    VR_HIP(c, c->dRecExtra.ensure_grow((size_t)c->batchCap * 4));
+  if (S.stateful) // (the state of every ray of a batch, float4 per ray; room for vr_reserve_rays' largest batch)
+    VR_HIP(c, c->dRayState.ensure_grow((size_t)std::max<uint64_t>(c->batchCap, std::min<uint64_t>(c->reserveRays, 1ull << 27)) * 4));
+  size_t slotsWant = e.slots, binsWant = e.cntWords;
+  if (c->reserveRays > span) { // vr_reserve_rays: room for the largest apply() announced
+    TraceParams q = p;
+    const StreamExtent r = stream_extent(D, (uint32_t)std::min<uint64_t>(c->reserveRays, 1ull << 27), K.raysPerBin, L.relief, q);
+    slotsWant = std::max(slotsWant, r.slots);
+    binsWant = std::max(binsWant, r.cntWords);
   }
+  VR_HIP(c, c->dSlotRec.ensure_grow(slotsWant * 8));
+  VR_HIP(c, c->dBinCount.ensure_grow(binsWant));
+  return VR_OK;
+}
 
-  // launch geometry of the persistent kernels
-  {
-    // absorbing particles: a (nearly) flat surface is served by packets alone; a structured one
-    // ends most rounds in per-lane walks and wants the straggler carry-over (MODE 2)
-    // general particles on a flat surface of disks: the general kernel with the packet query's crediting (MODE 3)
-    // (the lean extended kernel P_EXT — data labels, per-material sticking, global data — has the packet query's
-    //  crediting too; P_EXT_FULL, the instantiation with the rare options, stays on MODE 0)
-    // "flat": 95 % of the surface shown to the source lies in one plane AND the scene box is thin along the source
-    // axis — the packet query clips its rays to that box, and a box half a grid cell thick already lets the few
-    // grazing rays of a wave stretch its query over dozens of primitives (a 10^6-disk plane with ONE 50 x 50 bump of
-    // 0.3 cells: the absorbing kernel 6.4 -> 8.3 ms, the general one 11 -> 18; the kernels for structured scenes are
-    // then 2 - 6 % ahead of the flat ones.  DESIGN.md section 10: a flat layer + relief decomposition would close this)
-    c->traceMode = !c->absorb ? ((flatScene && c->geo.geo == 0 && c->kernelParticle <= (int)P_EXT) ? 3 : 0)
-                              : (flatScene ? 1 : 2);
-    c->looseMode = c->traceMode;
-    if (c->reliefScene) { // flat with relief: the flat-scene kernels on the tight bins, the structured-scene ones on the loose
-      c->traceMode = c->absorb ? 5 : 6;
-      if (!c->absorb && !std::getenv("VR_NO_SPILL"))
-        c->looseMode = 7; // ... which also resume the rays the tight general kernel spills (TraceParams::spillRec)
-    }
-    if (const char *e = std::getenv("VR_GENERAL_FLAT"))
-      if (!c->absorb && c->geo.geo == 0 && c->kernelParticle <= (int)P_EXT)
-        c->traceMode = std::atoi(e) ? 3 : 0;
-    if (const char *e = std::getenv("VR_ABSORB_CARRY"))
-      if (c->absorb)
-        c->traceMode = std::atoi(e) ? 2 : 1;
-    if (smallScene)
-      c->traceMode = 4;
-    if (c->traceMode != 5 && c->traceMode != 6) { // (an environment switch above took the mode back)
-      c->reliefScene = false;
-      p.reliefCoarse = nullptr;
-    }
-    int blocks = 1;
-    c->userKernel = nullptr;
-    c->userGen = nullptr;
-    if (c->userModel >= 0) { // the kernel of the model's own code object
-      const UserModel &um = c->userModels[c->userModel];
-      if (stateful && (c->absorb || (c->traceMode != 0 && c->traceMode != 4)))
-        return fail(c, VR_E_STATE, "stateful particle model: only the general kernels (MODE 0 / 4) carry the state");
-      c->userGen = stateful ? um.gen[D == 3 ? 1 : 0] : nullptr;
-      auto it = um.kernels.find(D * 100 + c->geo.geo * 10 + c->traceMode);
-      if (it == um.kernels.end())
-        return fail(c, VR_E_STATE, "run-time particle model: no kernel for this geometry / mode in its code object");
-      c->userKernel = it->second;
-      int nb = 0;
-      if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, c->userKernel, VR_BLOCK, c->traceMode == 4 ? p.smallBytes : 0) != hipSuccess)
-        nb = 2;
-      blocks = std::max(1, nb);
-    } else {
-      blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, c->kernelParticle, c->traceMode, p.smallBytes));
-    }
-    // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
-    // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of
-    // them — about sqrt(rays / 10^5).  10^6 rays: 0.69 -> 0.49 ms (absorbing 0.47 -> 0.31)
-    if (c->traceMode != 4)
-      blocks = std::min(blocks, std::max(1, (int)std::lround(std::sqrt((double)cap / 1e5))));
-    if (const char *e = std::getenv("VR_TRACE_BLOCKS"))
-      blocks = std::max(1, std::atoi(e));
-    c->grid = (unsigned)c->numCUs * (unsigned)blocks;
-    c->looseGrid = 0;
-    if (c->reliefScene) { // (the loose bins hold about a tenth of the rays)
-      int lb = std::max(1, trace_blocks_per_cu(D, c->geo.geo, c->kernelParticle, c->looseMode, 0));
-      lb = std::min(lb, std::max(1, (int)std::lround(std::sqrt((double)cap / 1e6))));
-      if (const char *e = std::getenv("VR_LOOSE_BLOCKS"))
-        lb = std::max(1, std::atoi(e));
-      c->looseGrid = (unsigned)c->numCUs * (unsigned)lb;
-    }
+// launch geometry of the persistent kernels: trace mode, the loose launch of a relief scene, blocks per CU
+static int choose_trace_mode(vr_context *c, ParticleLaunch &L, const PrepareState &S) {
+  const Knobs &K = c->knobs;
+  const int D = c->geo.D;
+  // absorbing particles: a (nearly) flat surface is served by packets alone; a structured one
+  // ends most rounds in per-lane walks and wants the straggler carry-over (MODE 2)
+  // general particles on a flat surface of disks: the general kernel with the packet query's crediting (MODE 3)
+  // (the lean extended kernel P_EXT — data labels, per-material sticking, global data — has the packet query's
+  //  crediting too; P_EXT_FULL, the instantiation with the rare options, stays on MODE 0)
+  // "flat": 95 % of the surface shown to the source lies in one plane AND the scene box is thin along the source
+  // axis — the packet query clips its rays to that box, and a box half a grid cell thick already lets the few
+  // grazing rays of a wave stretch its query over dozens of primitives (a 10^6-disk plane with ONE 50 x 50 bump of
+  // 0.3 cells: the absorbing kernel 6.4 -> 8.3 ms, the general one 11 -> 18; the kernels for structured scenes are
+  // then 2 - 6 % ahead of the flat ones.  DESIGN.md section 10: a flat layer + relief decomposition would close this)
+  const bool generalFlatOk = !L.absorb && c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT;
+  L.traceMode = !L.absorb ? ((S.flatScene && generalFlatOk) ? 3 : 0) : (S.flatScene ? 1 : 2);
+  L.looseMode = L.traceMode;
+  if (L.relief) { // flat with relief: the flat-scene kernels on the tight bins, the structured-scene ones on the loose
+    L.traceMode = L.absorb ? 5 : 6;
+    if (!L.absorb && !K.noSpill)
+      L.looseMode = 7; // ... which also resume the rays the tight general kernel spills (TraceParams::spillRec)
   }
+  if (K.generalFlat.has_value() && generalFlatOk)
+    L.traceMode = *K.generalFlat ? 3 : 0;
+  if (K.absorbCarry.has_value() && L.absorb)
+    L.traceMode = *K.absorbCarry ? 2 : 1;
+  if (S.smallScene)
+    L.traceMode = 4;
+  if (L.traceMode != 5 && L.traceMode != 6) { // (a switch above took the mode back)
+    L.relief = false;
+    L.params.reliefCoarse = nullptr;
+  }
+  int blocks = 1;
+  L.userKernel = nullptr;
+  L.userGen = nullptr;
+  if (c->userModel >= 0) { // the kernel of the model's own code object
+    const UserModel &um = c->userModels[c->userModel];
+    if (S.stateful && (L.absorb || (L.traceMode != 0 && L.traceMode != 4)))
+      return fail(c, VR_E_STATE, "stateful particle model: only the general kernels (MODE 0 / 4) carry the state");
+    L.userGen = S.stateful ? um.gen[D == 3 ? 1 : 0] : nullptr;
+    auto it = um.kernels.find(D * 100 + c->geo.geo * 10 + L.traceMode);
+    if (it == um.kernels.end())
+      return fail(c, VR_E_STATE, "run-time particle model: no kernel for this geometry / mode in its code object");
+    L.userKernel = it->second;
+    int nb = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, L.userKernel, VR_BLOCK, L.traceMode == 4 ? L.params.smallBytes : 0) != hipSuccess)
+      nb = 2;
+    blocks = std::max(1, nb);
+  } else {
+    blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.traceMode, L.params.smallBytes));
+  }
+  // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
+  // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of
+  // them — about sqrt(rays / 10^5).  10^6 rays: 0.69 -> 0.49 ms (absorbing 0.47 -> 0.31)
+  if (L.traceMode != 4)
+    blocks = std::min(blocks, std::max(1, (int)std::lround(std::sqrt((double)c->batchCap / 1e5))));
+  L.grid = (unsigned)c->numCUs * (unsigned)K.traceBlocks.value_or(blocks);
+  L.looseGrid = 0;
+  if (L.relief) { // (the loose bins hold about a tenth of the rays)
+    int lb = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.looseMode, 0));
+    lb = std::min(lb, std::max(1, (int)std::lround(std::sqrt((double)c->batchCap / 1e6))));
+    L.looseGrid = (unsigned)c->numCUs * (unsigned)K.looseBlocks.value_or(lb);
+  }
+  return VR_OK;
+}
+
+// the launch's scratch: walk stacks, RNG slabs, the spill queue (buffers every particle of the apply shares)
+static int size_scratch(vr_context *c, const ParticleLaunch &L, const PrepareState &S) {
   // deep part of the per-lane walk's stack (entries beyond the LDS-resident ones), one slab per resident wave
   {
-    const size_t waves = (size_t)std::max<unsigned>(c->grid, (unsigned)c->numCUs * 8u) * (VR_BLOCK / 64);
+    const size_t waves = (size_t)std::max<unsigned>(L.grid, (unsigned)c->numCUs * 8u) * (VR_BLOCK / 64);
     if (waves > c->walkStackWaves) {
       VR_HIP(c, c->dWalkStack.ensure(waves * (size_t)VR_STACK_GLOBAL * 64u));
       c->walkStackWaves = waves;
@@ -1691,20 +1842,38 @@ static int prepare_one(vr_context *c) {
   // 156 numbers per ray touches them — the general trace kernel and the tilted-source generator
   {
     size_t waves = 0;
-    if (!c->absorb)
-      waves = (size_t)std::max(c->grid, c->looseGrid) * (VR_BLOCK / 64);
-    if (c->usePrimaryDirection || !c->hostOrg.empty() || stateful)
+    if (!L.absorb)
+      waves = (size_t)std::max(L.grid, L.looseGrid) * (VR_BLOCK / 64);
+    if (c->usePrimaryDirection || !c->hostOrg.empty() || S.stateful)
       waves = std::max(waves, (size_t)c->numCUs * 8u * (VR_BLOCK / 64)); // launch_gen's grid bound (gen_state_kernel's too)
     if (waves > c->scratchWaves) {
       VR_HIP(c, c->dScratch.ensure(waves * 312u * 64u));
       c->scratchWaves = waves;
     }
   }
+  if (L.relief && L.looseMode == 7) { // the spill queue of the tight general relief kernel
+    // (a record per ray of a batch + the unused end of every wave's last 64-record block)
+    VR_HIP(c, c->dSpillRec.ensure_grow(((size_t)c->batchCap + (size_t)L.grid * (VR_BLOCK / 64) * 64u) * 16));
+    VR_HIP(c, c->dSpillCount.ensure(1));
+  }
+  return VR_OK;
+}
 
+// the launch's TraceParams (the shared buffers' addresses: launch_params, at launch time)
+static int fill_trace_params(vr_context *c, ParticleLaunch &L, PrepareState &S) {
+  const Knobs &K = c->knobs;
+  TraceParams &p = L.params;
+  const uint32_t N = c->geo.numPrims;
+  uint32_t seed = c->runNumber + c->rngSeed; // rayTraceKernel.hpp:100
+  if (c->haveSharedSeed) { // (vr_apply_sharded with random seeds: the one seed every rank agreed on)
+    seed = c->sharedSeed;
+  } else if (c->useRandomSeed) {
+    std::random_device rd;
+    seed = (uint32_t)rd();
+  }
   p.nodes = c->dNodes.p;
   p.qnodes = c->dQNodes.p;
   p.pnodes = c->dPNodes.p;
-  p.walkStack = c->dWalkStack.p;
   p.numNodes = c->numNodes;
   for (int k = 0; k < 3; ++k) {
     p.qbase[k] = c->qbase[k];
@@ -1715,36 +1884,26 @@ static int prepare_one(vr_context *c) {
   p.wideTopFirst = c->wideRoot[0];
   p.wideTopCount = c->wideRoot[1];
   p.widePrimBase = c->wideRoot[2];
-  p.pqMaxFrontier = 12;
-  if (const char *e = std::getenv("VR_PQ_FRONTIER"))
-    p.pqMaxFrontier = (uint32_t)std::min(24, std::max(1, std::atoi(e))); // (<= 24: the cached frontier shares the lists with its box)
-  p.pqMaxCand = 24;
-  if (const char *e = std::getenv("VR_PQ_CAND"))
-    p.pqMaxCand = (uint32_t)std::min(24, std::max(1, std::atoi(e))); // (2 * pqMaxCand + 1 records fit VR_PQ_CANDS)
-  {
-    float scale = 1e-3f;
-    for (int k = 0; k < 3; ++k) {
-      p.sceneLo[k] = c->sceneLo[k];
-      p.sceneHi[k] = c->sceneHi[k];
-      scale = std::max(scale, std::max(std::fabs(c->sceneLo[k]), std::fabs(c->sceneHi[k])));
-    }
-    p.nbDist = 2 * c->geo.diskRadius;
-    p.geoD = D;
-    p.pqPad = 1e-5f * scale; // >> the rounding of the clip (1e-7 relative); the boxes carry their own 4e-6 pad
+  p.pqMaxFrontier = K.pqFrontier;
+  p.pqMaxCand = K.pqCand;
+  for (int k = 0; k < 3; ++k) {
+    p.sceneLo[k] = c->sceneLo[k];
+    p.sceneHi[k] = c->sceneHi[k];
   }
+  p.nbDist = 2 * c->geo.diskRadius;
+  p.geoD = c->geo.D;
+  p.pqPad = 1e-5f * scene_scale(c); // >> the rounding of the clip (1e-7 relative); the boxes carry their own 4e-6 pad
   p.nbOff = c->dNbOff.p;
   p.nbIds = c->dNbIds.p;
-  p.primSticking = dStick;
   { // wall table + scalar frame: one slot per particle of the apply (each kernel stages its own launch's frame in LDS)
-    const size_t nSlots = std::max<size_t>(1, c->specs.size());
+    const size_t nSlots = c->launches.size();
     if (c->dWalls.cap < nSlots * VR_WALL_TABLE)
       VR_HIP(c, c->dWalls.ensure(nSlots * VR_WALL_TABLE));
     if (c->frameHostAll.size() < nSlots * VR_WALL_TABLE)
       c->frameHostAll.assign(nSlots * VR_WALL_TABLE, 0.f);
   }
-  p.wallTable = c->dWalls.p + (size_t)c->counterSlot * VR_WALL_TABLE;
+  p.wallTable = c->dWalls.p + (size_t)L.slot * VR_WALL_TABLE;
   p.planeStride = c->accStride * c->accReplicas;
-  p.fluxAcc = c->dFluxAcc.p + (size_t)c->dataBase * p.planeStride; // (this particle's planes)
   p.accStride = c->accStride;
   p.numData = c->numData;
   p.particleKind = c->particleKind;
@@ -1764,45 +1923,25 @@ static int prepare_one(vr_context *c) {
   p.hostDraws = c->hostDraws.empty() ? nullptr : c->dHostDraws.p;
   p.hostWeights = (c->hostOrg.empty() || c->hostWeights.empty()) ? nullptr : c->dHostWeights.p;
   p.accMask = c->accReplicas - 1u;
-  VR_HIP(c, c->dCounters.ensure(80 * std::max<size_t>(1, c->specs.size())));
-  p.counters = c->dCounters.p + 80 * (size_t)c->counterSlot;
+  VR_HIP(c, c->dCounters.ensure(80 * c->launches.size()));
   VR_HIP(c, c->dWorkQ.ensure(VR_QUEUES * VR_QUEUE_STRIDE));
-  p.workCounter = c->dWorkQ.p;
   p.numQueues = VR_QUEUES;
-  p.recExtra = c->recExtra ? c->dRecExtra.p : nullptr;
   // a stateful model: its state buffer and the material ids of its hooks (the caller's id of the original primitive) go
   // into the launch frame (VR_F_STATE_*, VR_F_MAT_*).  (Both are sized by what every particle of an apply shares — rays
   // per batch, primitives — so a later particle's prepare does not move them.)
-  const int32_t *dMaterial = nullptr;
-  if (stateful && !c->geo.materialIds.empty()) {
+  S.dMaterial = nullptr;
+  if (S.stateful && !c->geo.materialIds.empty()) {
     std::vector<int32_t> ids(N, 0);
     std::copy(c->geo.materialIds.begin(), c->geo.materialIds.begin() + std::min<size_t>(N, c->geo.materialIds.size()), ids.begin());
     VR_HIP(c, c->dPrimMaterial.ensure(N));
     VR_HIP(c, hipMemcpy(c->dPrimMaterial.p, ids.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    dMaterial = c->dPrimMaterial.p;
+    S.dMaterial = c->dPrimMaterial.p;
   }
-  p.spillRec = nullptr;
-  p.spillCount = nullptr;
-  if (c->reliefScene && c->looseMode == 7) {
-    // (a record per ray of a batch + the unused end of every wave's last 64-record block)
-    VR_HIP(c, c->dSpillRec.ensure_grow(((size_t)c->batchCap + (size_t)c->grid * (VR_BLOCK / 64) * 64u) * 16));
-    VR_HIP(c, c->dSpillCount.ensure(1));
-    p.spillRec = c->dSpillRec.p;
-    p.spillCount = c->dSpillCount.p;
-  }
-  {
-    // the packet query's search margin (frontier reuse over neighbouring rounds, flat-scene kernels): in units of the
-    // neighbourhood distance 2 r (disks) / 1.7 grid cells (triangles); pqMaxFrontier <= 24 entries fit the cached lists
-    float mg = 1.5f;
-    if (const char *e = std::getenv("VR_PQ_MARGIN"))
-      mg = std::max(0.f, (float)std::atof(e));
-    p.pqMargin = mg * (c->geo.geo == 0 ? 2.f * c->geo.diskRadius : 1.7f * c->geo.gridDelta);
-  }
-  p.rngScratch = c->dScratch.p;
-  p.slotRec = c->dSlotRec.p;
-  p.binCount = c->dBinCount.p;
+  // the packet query's search margin (frontier reuse over neighbouring rounds, flat-scene kernels): in units of the
+  // neighbourhood distance 2 r (disks) / 1.7 grid cells (triangles); pqMaxFrontier <= 24 entries fit the cached lists
+  p.pqMargin = K.pqMargin * (c->geo.geo == 0 ? 2.f * c->geo.diskRadius : 1.7f * c->geo.gridDelta);
   p.idxList = nullptr;
-  p.batchFirst = first;
+  p.batchFirst = c->rayFirstLaunch;
   p.batchCount = 0;
   p.ovCap = c->batchCap;
   p.numBins = c->numBins;
@@ -1839,130 +1978,169 @@ static int prepare_one(vr_context *c) {
     p.wallLoR = lr - margin;
     p.wallHiR = hr + margin;
   }
-  p.keyCoord = c->keyCoord;
-  if (const char *e = std::getenv("VR_KEY_COORD"))
-    p.keyCoord = (float)std::atof(e);
+  p.keyCoord = K.keyCoord.value_or(c->keyCoord);
   p.invExt1 = (p.hi1 > p.lo1) ? 1.f / (p.hi1 - p.lo1) : 0.f;
   p.invExt2 = (p.hi2 > p.lo2) ? 1.f / (p.hi2 - p.lo2) : 0.f;
-  p.packetBudget = 128;
-  if (const char *e = std::getenv("VR_PACKET_BUDGET"))
-    p.packetBudget = (uint32_t)std::max(0, std::atoi(e));
+  p.packetBudget = K.packetBudget;
   // (share of parked lanes at which the pending leaves are tested: sweep 10 / 18 / 25 / 35 / 50 — disks flat between
   //  18 and 35; triangles, whose leaf test is the longer one, 10: trenchMesh 0.1 28.3 -> 27.5 ms, C4 20.6 -> 20.2)
-  p.walkPark = c->geo.geo == 1 ? 10 : 25;
-  if (const char *e = std::getenv("VR_WALK_PARK"))
-    p.walkPark = (uint32_t)std::min(100, std::max(1, std::atoi(e)));
-  p.walkExit = 16; // (sweep 12 .. 36: 12 - 20 within 1 %, 36 slower by 4 - 7 %)
-  if (const char *e = std::getenv("VR_WALK_EXIT"))
-    p.walkExit = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
-  p.packetRatio = 3;
-  if (const char *e = std::getenv("VR_PACKET_RATIO"))
-    p.packetRatio = (uint32_t)std::max(1, std::atoi(e));
-  p.debugFlags = 0;
-  if (const char *e = std::getenv("VR_DEBUG_FLAGS"))
-    p.debugFlags = (uint32_t)std::atoi(e);
-  { // the launch's scalar frame, staged in LDS by the trace kernels (VR_F_*, vr_device.hpp)
-    float *const slotHost = c->frameHostAll.data() + (size_t)c->counterSlot * VR_WALL_TABLE;
-    std::memcpy(slotHost, c->wallsHost, sizeof(c->wallsHost));
-    float *f = slotHost + 96;
-    auto bits = [](int32_t v) {
-      float r;
-      std::memcpy(&r, &v, 4);
-      return r;
-    };
-    f[0] = p.srcCoord;
-    f[1] = bits(p.rayDir);
-    f[2] = bits(p.firstDir);
-    f[3] = bits(p.secondDir);
-    f[4] = f[5] = 0.f; // (the records' side-array address: written by the kernel from its own argument)
-    f[6] = p.lo1;
-    f[7] = p.hi1;
-    f[8] = p.lo2;
-    f[9] = p.hi2;
-    f[10] = p.wallLoR;
-    f[11] = p.wallHiR;
-    for (int k = 0; k < 3; ++k) {
-      f[12 + k] = p.sceneLo[k];
-      f[15 + k] = p.sceneHi[k];
-    }
-    f[18] = p.pqPad;
-    f[19] = bits(p.bc0);
-    f[20] = bits(p.bc1);
-    f[21] = p.nbDist;
-    for (int k = 22; k < VR_WALL_TABLE - 96; ++k)
-      f[k] = 0.f;
-    if (stateful) { // VR_F_STATE_* / VR_F_MAT_*
-      const uint64_t sa = (uint64_t)(uintptr_t)c->dRayState.p, ma = (uint64_t)(uintptr_t)dMaterial;
-      f[VR_F_STATE_LO - 96] = bits((int32_t)(uint32_t)(sa & 0xFFFFFFFFull));
-      f[VR_F_STATE_HI - 96] = bits((int32_t)(uint32_t)(sa >> 32));
-      f[VR_F_MAT_LO - 96] = bits((int32_t)(uint32_t)(ma & 0xFFFFFFFFull));
-      f[VR_F_MAT_HI - 96] = bits((int32_t)(uint32_t)(ma >> 32));
-    }
-    if (c->reliefScene) { // the relief field's fine tiles (VR_F_RF_*: relief_clip, vr_device.hpp)
-      const ReliefParams &q = c->rf;
-      f[32] = q.lo1;
-      f[33] = q.lo2;
-      f[34] = q.invTile;
-      f[35] = q.tile;
-      f[36] = bits(q.nx);
-      f[37] = bits(q.ny);
-      const uint64_t addr = (uint64_t)(uintptr_t)q.fine;
-      f[38] = bits((int32_t)(uint32_t)(addr & 0xFFFFFFFFull));
-      f[39] = bits((int32_t)(uint32_t)(addr >> 32));
-    }
-    // height field over the source plane: for particles that go on after a hit ("segments that rise clear", vr_trace.hip)
-    if (!c->absorb && c->geo.numPrims && !std::getenv("VR_NO_HEIGHT_FIELD")) {
-      const bool stale = c->hfBuild != c->bvhBuilds || c->hfAxes[0] != c->ts[0] || c->hfAxes[1] != c->ts[1] ||
-                         c->hfAxes[2] != c->ts[2] || c->hfAxes[3] != c->ts[3];
-      if (stale) {
-        HeightFieldParams &q = c->hf;
-        q.prims = c->dPrims.p;
-        q.n = c->geo.numPrims;
-        q.geo = c->geo.geo;
-        q.ax = c->ts[0];
-        q.a1 = c->ts[1];
-        q.a2 = c->ts[2];
-        q.sign = c->ts[3] ? 1.f : -1.f; // (ts[3]: the source plane lies at the max side)
-        const float ext1 = c->sceneHi[q.a1] - c->sceneLo[q.a1], ext2 = D == 3 ? c->sceneHi[q.a2] - c->sceneLo[q.a2] : 0.f;
-        float cells = 4.f; // (tile side in grid cells; sweep 2 / 3 / 4 / 6 / 8: see DESIGN.md 7)
-        if (const char *e = std::getenv("VR_HF_TILE"))
-          cells = std::max(0.25f, (float)std::atof(e));
-        float tile = std::max(cells * c->geo.gridDelta, std::max(ext1, ext2) / 256.f);
-        if (!(tile > 0.f))
-          tile = 1.f;
-        q.lo1 = c->sceneLo[q.a1];
-        q.lo2 = D == 3 ? c->sceneLo[q.a2] : 0.f;
-        q.invTile = 1.f / tile;
-        q.nx = std::max(1, std::min(256, (int)std::ceil(ext1 / tile)));
-        q.ny = D == 3 ? std::max(1, std::min(256, (int)std::ceil(ext2 / tile))) : 1;
-        float scale = 1e-3f;
-        for (int k = 0; k < 3; ++k)
-          scale = std::max(scale, std::max(std::fabs(c->sceneLo[k]), std::fabs(c->sceneHi[k])));
-        q.pad = 8e-7f * scale; // (a dozen ulp of the largest coordinate: see DESIGN.md 5.2)
-        VR_HIP(c, c->dHfRaw.ensure((size_t)q.nx * q.ny));
-        VR_HIP(c, c->dHf.ensure((size_t)q.nx * q.ny));
-        q.raw = c->dHfRaw.p;
-        q.field = c->dHf.p;
-        VR_HIP(c, launch_height_field(q, c->stream));
-        c->hfBuild = c->bvhBuilds;
-        for (int k = 0; k < 4; ++k)
-          c->hfAxes[k] = c->ts[k];
-      }
-      const HeightFieldParams &q = c->hf;
-      f[22] = q.lo1;
-      f[23] = q.lo2;
-      f[24] = q.invTile;
-      f[25] = 1.f / q.invTile;
-      f[26] = (q.sign > 0.f ? c->sceneHi[q.ax] : -c->sceneLo[q.ax]); // above this nothing is left (the BVH's root box)
-      f[27] = q.sign;
-      f[28] = bits(q.nx);
-      f[29] = bits(q.ny);
-      const uint64_t addr = (uint64_t)(uintptr_t)q.field;
-      f[30] = bits((int32_t)(uint32_t)(addr & 0xFFFFFFFFull));
-      f[31] = bits((int32_t)(uint32_t)(addr >> 32));
-    }
-    VR_HIP(c, hipMemcpyAsync(c->dWalls.p + (size_t)c->counterSlot * VR_WALL_TABLE, slotHost, VR_WALL_TABLE * 4, hipMemcpyHostToDevice, c->stream));
+  p.walkPark = K.walkPark.value_or(c->geo.geo == 1 ? 10u : 25u);
+  p.walkExit = K.walkExit; // (sweep 12 .. 36: 12 - 20 within 1 %, 36 slower by 4 - 7 %)
+  p.packetRatio = K.packetRatio;
+  p.debugFlags = K.debugFlags;
+  return VR_OK;
+}
+
+// height field over the source plane: for particles that go on after a hit ("segments that rise clear", vr_trace.hip)
+static int build_height_field(vr_context *c, const ParticleLaunch &L, PrepareState &S) {
+  S.heightField = !L.absorb && c->geo.numPrims && !c->knobs.noHeightField;
+  if (!S.heightField)
+    return VR_OK;
+  const bool stale = c->hfBuild != c->bvhBuilds || c->hfAxes[0] != c->ts[0] || c->hfAxes[1] != c->ts[1] ||
+                     c->hfAxes[2] != c->ts[2] || c->hfAxes[3] != c->ts[3];
+  if (!stale)
+    return VR_OK;
+  const int D = c->geo.D;
+  HeightFieldParams &q = c->hf;
+  q.prims = c->dPrims.p;
+  q.n = c->geo.numPrims;
+  q.geo = c->geo.geo;
+  q.ax = c->ts[0];
+  q.a1 = c->ts[1];
+  q.a2 = c->ts[2];
+  q.sign = c->ts[3] ? 1.f : -1.f; // (ts[3]: the source plane lies at the max side)
+  const float ext1 = c->sceneHi[q.a1] - c->sceneLo[q.a1], ext2 = D == 3 ? c->sceneHi[q.a2] - c->sceneLo[q.a2] : 0.f;
+  // (tile side in grid cells; sweep 2 / 3 / 4 / 6 / 8: see DESIGN.md 7)
+  float tile = std::max(c->knobs.hfTile * c->geo.gridDelta, std::max(ext1, ext2) / 256.f);
+  if (!(tile > 0.f))
+    tile = 1.f;
+  q.lo1 = c->sceneLo[q.a1];
+  q.lo2 = D == 3 ? c->sceneLo[q.a2] : 0.f;
+  q.invTile = 1.f / tile;
+  q.nx = std::max(1, std::min(256, (int)std::ceil(ext1 / tile)));
+  q.ny = D == 3 ? std::max(1, std::min(256, (int)std::ceil(ext2 / tile))) : 1;
+  q.pad = 8e-7f * scene_scale(c); // (a dozen ulp of the largest coordinate: see DESIGN.md 5.2)
+  VR_HIP(c, c->dHfRaw.ensure((size_t)q.nx * q.ny));
+  VR_HIP(c, c->dHf.ensure((size_t)q.nx * q.ny));
+  q.raw = c->dHfRaw.p;
+  q.field = c->dHf.p;
+  VR_HIP(c, launch_height_field(q, c->stream));
+  c->hfBuild = c->bvhBuilds;
+  for (int k = 0; k < 4; ++k)
+    c->hfAxes[k] = c->ts[k];
+  return VR_OK;
+}
+
+// the launch's wall table and scalar frame (VR_F_*, vr_device.hpp), staged in LDS by the trace kernels
+static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const PrepareState &S) {
+  const TraceParams &p = L.params;
+  float *const f = c->frameHostAll.data() + (size_t)L.slot * VR_WALL_TABLE;
+  std::memcpy(f, c->wallsHost, sizeof(c->wallsHost));
+  std::fill(f + 96, f + VR_WALL_TABLE, 0.f); // (VR_F_EXTRA_*, the records' side-array address: the kernel writes it)
+  auto bits = [](int32_t v) {
+    float r;
+    std::memcpy(&r, &v, 4);
+    return r;
+  };
+  auto addr = [&](int lo, const void *ptr) { // a device address as two words
+    const uint64_t a = (uint64_t)(uintptr_t)ptr;
+    f[lo] = bits((int32_t)(uint32_t)(a & 0xFFFFFFFFull));
+    f[lo + 1] = bits((int32_t)(uint32_t)(a >> 32));
+  };
+  f[VR_F_SRC_PLANE] = p.srcCoord;
+  f[VR_F_RAYDIR] = bits(p.rayDir);
+  f[VR_F_FIRSTDIR] = bits(p.firstDir);
+  f[VR_F_SECONDDIR] = bits(p.secondDir);
+  f[VR_F_LO1] = p.lo1;
+  f[VR_F_LO1 + 1] = p.hi1;
+  f[VR_F_LO1 + 2] = p.lo2;
+  f[VR_F_LO1 + 3] = p.hi2;
+  f[VR_F_WALL_LO_R] = p.wallLoR;
+  f[VR_F_WALL_HI_R] = p.wallHiR;
+  for (int k = 0; k < 3; ++k) {
+    f[VR_F_SCENE_LO + k] = p.sceneLo[k];
+    f[VR_F_SCENE_HI + k] = p.sceneHi[k];
   }
+  f[VR_F_PQ_PAD] = p.pqPad;
+  f[VR_F_BC0] = bits(p.bc0);
+  f[VR_F_BC1] = bits(p.bc1);
+  f[VR_F_NB_DIST] = p.nbDist;
+  if (S.heightField) { // (build_height_field)
+    const HeightFieldParams &q = c->hf;
+    f[VR_F_HF_LO1] = q.lo1;
+    f[VR_F_HF_LO2] = q.lo2;
+    f[VR_F_HF_INVT] = q.invTile;
+    f[VR_F_HF_TILE] = 1.f / q.invTile;
+    f[VR_F_HF_TOP] = (q.sign > 0.f ? c->sceneHi[q.ax] : -c->sceneLo[q.ax]); // above this nothing is left (the BVH's root box)
+    f[VR_F_HF_SIGN] = q.sign;
+    f[VR_F_HF_NX] = bits(q.nx);
+    f[VR_F_HF_NY] = bits(q.ny);
+    addr(VR_F_HF_PTR_LO, q.field);
+  }
+  if (L.relief) { // the relief field's fine tiles (relief_clip, vr_device.hpp)
+    const ReliefParams &q = c->rf;
+    f[VR_F_RF_LO1] = q.lo1;
+    f[VR_F_RF_LO2] = q.lo2;
+    f[VR_F_RF_INVT] = q.invTile;
+    f[VR_F_RF_TILE] = q.tile;
+    f[VR_F_RF_NX] = bits(q.nx);
+    f[VR_F_RF_NY] = bits(q.ny);
+    addr(VR_F_RF_PTR_LO, q.fine);
+  }
+  if (S.stateful) {
+    addr(VR_F_STATE_LO, c->dRayState.p);
+    addr(VR_F_MAT_LO, S.dMaterial);
+  }
+  VR_HIP(c, hipMemcpyAsync(c->dWalls.p + (size_t)L.slot * VR_WALL_TABLE, f, VR_WALL_TABLE * 4, hipMemcpyHostToDevice, c->stream));
+  return VR_OK;
+}
+
+#define VR_TRY(call)                                                                                                   \
+  do {                                                                                                                 \
+    const int r__ = (call);                                                                                            \
+    if (r__ != VR_OK)                                                                                                  \
+      return r__;                                                                                                      \
+  } while (0)
+
+// everything one particle's launch needs (scene build and areas only when they changed), into L.  Every device call
+// goes to c->stream in this order.
+static int prepare_one(vr_context *c, ParticleLaunch &L) {
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_TRY(check_settings(c));
+  const auto t0 = std::chrono::steady_clock::now();
+  const bool redoConfig = c->configDirty || c->geometryDirty;
+  if (redoConfig)
+    setup_source_frame(c);
+  // the BVH's child order follows the source side: a new source direction rebuilds it
+  if (c->builtOrderAxis != c->ts[0] || c->builtOrderSign != (c->ts[3] ? 1.f : -1.f))
+    c->geometryDirty = true;
+  if (c->geometryDirty) {
+    VR_TRY(build_scene(c));
+    c->geometryDirty = false;
+    ++c->bvhBuilds;
+    c->builtOrderAxis = c->ts[0];
+    c->builtOrderSign = c->ts[3] ? 1.f : -1.f;
+  }
+  if (redoConfig || !c->areasValid)
+    VR_TRY(compute_areas(c));
+  if (redoConfig || c->particleDirty)
+    VR_TRY(prepare_sticking(c, L));
+  c->configDirty = false;
+  c->particleDirty = false;
+  if (c->globalDirty)
+    VR_TRY(upload_global_data(c));
+  PrepareState S;
+  VR_TRY(choose_particle_kernel(c, L, S));
+  VR_TRY(build_relief_field(c, L, S));
+  VR_TRY(ensure_accumulators(c));
+  if (c->sourceDirty)
+    VR_TRY(upload_source_data(c));
+  VR_TRY(size_ray_stream(c, L, S));
+  VR_TRY(choose_trace_mode(c, L, S)); // (after the ray stream: blocks follow the batch size; the buffers keep the relief layout)
+  VR_TRY(size_scratch(c, L, S));
+  VR_TRY(fill_trace_params(c, L, S));
+  VR_TRY(build_height_field(c, L, S));
+  VR_TRY(write_launch_frame(c, L, S));
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (redoConfig)
     c->buildSeconds = secs; // a cheap re-prepare (new seed / ray range only) keeps the last build time
@@ -1971,52 +2149,6 @@ static int prepare_one(vr_context *c) {
   c->haveResult = false;
   return VR_OK;
 }
-
-// sort-bin grid for a batch of `count` rays: far-plane cells holding ~perBin rays each
-static void size_bins(int D, uint64_t count, uint32_t perBin, TraceParams &p, uint32_t &numBins) {
-  const uint64_t target = std::max<uint64_t>(count / std::max<uint32_t>(perBin, 1u), 1);
-  if (D == 2) {
-    p.binT1 = (int)std::min<uint64_t>(target, 1u << 22);
-    p.binT2 = 1;
-    p.binTiles = 1;
-    numBins = (uint32_t)p.binT1;
-  } else {
-    p.binT1 = p.binT2 = (int)std::min<double>(4096.0, std::max(1.0, std::ceil(std::sqrt((double)target))));
-    p.binTiles = (p.binT1 + 7) / 8;
-    numBins = (uint32_t)p.binTiles * (uint32_t)p.binTiles * 64u;
-  }
-}
-
-// The LOOSE bins of a scene with relief (TraceParams, round 4): a grid a third as fine per axis as the tight one p.binT*
-// describes — they hold the grazing rays, about a tenth of all — whose cursors and record slots (+ an overflow region of
-// p.ovCap slots) lie behind the tight bins' in the same two buffers.
-static void size_loose(int D, TraceParams &p) {
-  p.looseT1 = std::max(1, p.binT1 / 3);
-  if (D == 2) {
-    p.looseT2 = 1;
-    p.looseTiles = 1;
-    p.looseNumBins = (uint32_t)p.looseT1;
-  } else {
-    p.looseT2 = std::max(1, p.binT2 / 3);
-    p.looseTiles = (p.looseT1 + 7) / 8;
-    p.looseNumBins = (uint32_t)p.looseTiles * (uint32_t)((p.looseT2 + 7) / 8) * 64u;
-  }
-  p.looseCntBase = (p.numBins + 1u + 3u) & ~3u;
-  p.looseSlotBase = p.numBins * p.binCap + p.ovCap;
-}
-
-// what one trace launch of a batch needs beyond the prepared parameters
-struct LaunchDesc {
-  const TraceParams *params;
-  unsigned grid;
-  int traceMode, kernelParticle;
-  bool absorb;
-  hipFunction_t userKernel; // a run-time model's kernel, or nullptr
-  hipFunction_t userGen;    // a stateful model's generator, or nullptr
-  bool relief = false;      // flat with relief: a second launch (looseMode, looseGrid) traces the loose bins
-  int looseMode = 0;
-  unsigned looseGrid = 0;
-};
 
 static hipEvent_t &event_at(std::vector<hipEvent_t> &v, size_t i, vr_context *c, int &rc) {
   while (v.size() <= i) {
@@ -2031,9 +2163,28 @@ static hipEvent_t &event_at(std::vector<hipEvent_t> &v, size_t i, vr_context *c,
   return v[i];
 }
 
+// A prepared launch's parameters with the addresses of the buffers every particle of the apply shares (ray stream,
+// scratch, work queues, counter blocks, accumulator planes) as they are now: a later particle's prepare may have grown one.
+static TraceParams launch_params(const vr_context *c, const ParticleLaunch &L) {
+  TraceParams p = L.params;
+  p.slotRec = c->dSlotRec.p;
+  p.binCount = c->dBinCount.p;
+  p.walkStack = c->dWalkStack.p;
+  p.rngScratch = c->dScratch.p;
+  p.workCounter = c->dWorkQ.p;
+  p.recExtra = L.recExtra ? c->dRecExtra.p : nullptr;
+  const bool spill = L.relief && L.looseMode == 7;
+  p.spillRec = spill ? c->dSpillRec.p : nullptr;
+  p.spillCount = spill ? c->dSpillCount.p : nullptr;
+  p.counters = c->dCounters.p + 80 * (size_t)L.slot;
+  p.fluxAcc = c->dFluxAcc.p + (size_t)L.dataBase * p.planeStride; // (this particle's planes)
+  return p;
+}
+
 // the batch's own fields of a particle's launch parameters: sort bins, spans per queue grab, queues
-static TraceParams batch_params(vr_context *c, const LaunchDesc &L, uint64_t first, uint32_t count) {
-  TraceParams p = *L.params;
+static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t first, uint32_t count) {
+  const Knobs &K = c->knobs;
+  TraceParams p = launch_params(c, L);
   p.batchFirst = first;
   p.batchCount = count;
   uint32_t nbBatch = c->numBins;
@@ -2054,11 +2205,10 @@ static TraceParams batch_params(vr_context *c, const LaunchDesc &L, uint64_t fir
     //  plane is one of these, 4.9 % of the rounds at 32 bins, 2 % at 64 — which costs the absorbing kernel nothing
     //  measurable but the general flat-scene kernels 3 % (their failed round also loses its follow-up segments))
     uint64_t spanBins = L.traceMode == 0 ? 16 : ((L.traceMode == 3 || L.traceMode == 6) ? 64 : 32);
-    if (const char *e = std::getenv("VR_SPAN_BINS"))
-      spanBins = (uint64_t)std::min(64, std::max(1, std::atoi(e)));
+    if (K.spanBins)
+      spanBins = *K.spanBins;
     p.chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spanBins, nbBatch / std::max<uint64_t>(waves * 2, 1)));
   }
-  p.workCounter = c->dWorkQ.p;
   // One queue per XCD pays where neighbouring rounds share primitive records that do not fit an XCD's 4 MiB L2 and the
   // work per bin is even: flat scenes of more than ~10^5 primitives (measured, VR_QUEUES=1 / 8 on one box: C2 sticking
   // 0.1 15.62 -> 15.16 ms, C2 1.0 6.67 -> 6.62, plane 100^2 +-0; L2 hit rate of the C2 launch 74 -> 84 %, fabric reads
@@ -2066,35 +2216,42 @@ static TraceParams batch_params(vr_context *c, const LaunchDesc &L, uint64_t fir
   // not an eighth of the work: trench3D +3 %, C5 +6 %: one queue.
   const bool flat = L.traceMode == 3; // (the absorbing kernels have the single queue compiled in)
   p.numQueues = (flat && c->geo.numPrims > (1u << 17) && nbBatch >= 64u * VR_QUEUES * p.chunk) ? VR_QUEUES : 1u;
-  if (const char *e = std::getenv("VR_QUEUES"))
-    p.numQueues = std::atoi(e) >= (int)VR_QUEUES ? VR_QUEUES : 1u;
+  if (K.numQueues)
+    p.numQueues = *K.numQueues;
   return p;
 }
 
 // One batch of the ray stream: ONE generator pass straight into the sort bins, then the trace kernel of every
 // particle of `group` over the same records (particles of a group share source distribution and record format).
-static int run_batch(vr_context *c, const std::vector<LaunchDesc> &group, uint64_t first, uint32_t count, size_t &genNo,
-                     size_t &traceNo) {
+static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &group, uint64_t first, uint32_t count,
+                     size_t &genNo, size_t &traceNo) {
   int rc = VR_OK;
-  const bool keepRng = !group[0].absorb; // records carry the RNG cursors
-  const TraceParams pg = batch_params(c, group[0], first, count);
+  const ParticleLaunch &G = *group[0];
+  const bool keepRng = !G.absorb; // records carry the RNG cursors
+  const TraceParams pg = batch_params(c, G, first, count);
   VR_HIP(c, hipMemsetAsync(pg.binCount, 0, (pg.reliefCoarse ? (size_t)pg.looseCntBase + pg.looseNumBins + 1 : (size_t)pg.numBins + 1) * 4, c->stream));
   hipEvent_t g0 = event_at(c->evG, 2 * genNo, c, rc), g1 = event_at(c->evG, 2 * genNo + 1, c, rc);
   if (rc != VR_OK)
     return rc;
   VR_HIP(c, hipEventRecord(g0, c->stream));
-  if (group[0].userGen) { // a stateful model: its module's generator (init, then the source sample)
+  if (G.userGen) { // a stateful model: its module's generator (init, then the source sample)
     TraceParams pk = pg;
     void *args[] = {&pk};
     const unsigned grid = std::min<unsigned>((count + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
-    VR_HIP(c, hipModuleLaunchKernel(group[0].userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
+    VR_HIP(c, hipModuleLaunchKernel(G.userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
   } else {
     VR_HIP(c, launch_gen(pg, c->geo.D, keepRng, (unsigned)c->numCUs * 8u, c->stream));
   }
   VR_HIP(c, hipEventRecord(g1, c->stream));
   ++genNo;
-  for (const LaunchDesc &L : group) {
-    const TraceParams p = &L == &group[0] ? pg : batch_params(c, L, first, count);
+  for (const ParticleLaunch *Lp : group) {
+    const ParticleLaunch &L = *Lp;
+    bool tight = true, loose = L.relief;
+#ifdef VR_DIAG // (diagnostics: one of a relief scene's two launches alone — the result is incomplete)
+    tight = !(L.relief && c->knobs.skipTight);
+    loose = loose && !c->knobs.skipLoose;
+#endif
+    const TraceParams p = Lp == &G ? pg : batch_params(c, L, first, count);
     VR_HIP(c, hipMemsetAsync(p.workCounter, 0, VR_QUEUES * VR_QUEUE_STRIDE * 8, c->stream));
     if (p.spillCount)
       VR_HIP(c, hipMemsetAsync(p.spillCount, 0, 4, c->stream));
@@ -2104,18 +2261,17 @@ static int run_batch(vr_context *c, const std::vector<LaunchDesc> &group, uint64
     VR_HIP(c, hipEventRecord(k0, c->stream));
     // a small batch does not need the whole persistent grid: one wave per 64 rays is plenty
     const unsigned gridBatch = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(L.grid, ((uint64_t)count + 255) / 256));
-    if (L.relief && std::getenv("VR_SKIP_TIGHT")) { // (diagnostics: the loose launch alone — the result is incomplete)
-    } else if (L.userKernel) {
+    if (tight && L.userKernel) {
       TraceParams pk = p;
       void *args[] = {&pk};
       VR_HIP(c, hipModuleLaunchKernel(L.userKernel, gridBatch, 1, 1, VR_BLOCK, 1, 1, L.traceMode == 4 ? p.smallBytes : 0, c->stream,
                                       args, nullptr));
-    } else {
+    } else if (tight) {
       VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.traceMode, gridBatch, c->stream));
     }
     VR_HIP(c, hipEventRecord(k1, c->stream));
     ++traceNo;
-    if (L.relief && !std::getenv("VR_SKIP_LOOSE")) { // (VR_SKIP_LOOSE: diagnostics, the tight launch alone — the result is incomplete)
+    if (loose) {
       // the loose bins (the grazing rays, filed apart by the generator): the kernel for structured scenes over the second
       // set of bins — the same buffers from their loose parts on, a single queue
       TraceParams q = p;
@@ -2149,32 +2305,24 @@ int vr_apply_launch(vr_context *c) {
     return fail(c, VR_E_STATE, "vr_apply_launch: call vr_apply_prepare first");
   VR_HIP(c, hipSetDevice(c->device));
   const uint32_t N = c->geo.numPrims;
-  const size_t nPart = std::max<size_t>(1, c->specs.size());
   VR_HIP(c, hipMemsetAsync(c->dFluxAcc.p, 0, (size_t)c->accStride * c->accReplicas * c->totalData * 8, c->stream));
-  VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 80 * nPart * 8, c->stream));
+  VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 80 * c->launches.size() * 8, c->stream));
   VR_HIP(c, hipEventRecord(c->ev0, c->stream));
   // groups of particles that can share a generator pass: the same source distribution (cosine power: the rays of
   // index idx are then identical, gpu/raygTrace.hpp launches every particle with the apply's one seed) and the
   // same record format (with / without the RNG cursors)
-  std::vector<std::vector<LaunchDesc>> groups;
-  if (nPart == 1) {
-    groups.push_back({LaunchDesc{&c->params, c->grid, c->traceMode, c->kernelParticle, c->absorb, c->userKernel, c->userGen,
-                                 c->reliefScene, c->looseMode, c->looseGrid}});
-  } else {
-    for (const ParticleLaunch &L : c->launches) {
-      const LaunchDesc d{&L.params, L.grid, L.traceMode, L.kernelParticle, L.absorb, L.userKernel, L.userGen, L.relief, L.looseMode,
-                         L.looseGrid};
-      bool placed = false;
-      for (auto &g : groups) // (a stateful model's generator runs its own init: a generator pass of its own)
-        if (!g[0].userGen && !d.userGen && g[0].absorb == d.absorb && g[0].params->ee == d.params->ee && g[0].params->eeGrid == d.params->eeGrid &&
-            g[0].relief == d.relief) { // (relief: the generator's bins are laid out differently)
-          g.push_back(d);
-          placed = true;
-          break;
-        }
-      if (!placed)
-        groups.push_back({d});
-    }
+  std::vector<std::vector<const ParticleLaunch *>> groups;
+  for (const ParticleLaunch &L : c->launches) {
+    bool placed = false;
+    for (auto &g : groups) // (a stateful model's generator runs its own init: a generator pass of its own)
+      if (!g[0]->userGen && !L.userGen && g[0]->absorb == L.absorb && g[0]->params.ee == L.params.ee &&
+          g[0]->params.eeGrid == L.params.eeGrid && g[0]->relief == L.relief) { // (relief: the generator's bins are laid out differently)
+        g.push_back(&L);
+        placed = true;
+        break;
+      }
+    if (!placed)
+      groups.push_back({&L});
   }
   c->numGenLaunches = c->numTraceLaunches = 0;
   for (const auto &g : groups)
@@ -2215,10 +2363,9 @@ int vr_apply_finish(vr_context *c) {
     return fail(c, VR_E_STATE, "vr_apply_finish: nothing launched");
   VR_HIP(c, hipSetDevice(c->device));
   VR_HIP(c, hipStreamSynchronize(c->stream));
-  const size_t nPart = std::max<size_t>(1, c->specs.size());
+  const size_t nPart = c->launches.size();
   std::vector<unsigned long long> all(80 * nPart); // per particle: [0..7] TraceInfo counters, [60] the walk's stack-overflow flag
   VR_HIP(c, hipMemcpy(all.data(), c->dCounters.p, all.size() * 8, hipMemcpyDeviceToHost));
-  const unsigned long long *cnt = all.data();
 #ifdef VR_DIAG
   { // lane-occupancy diagnostics of a -DVR_DIAG build (see vr_trace.hip)
     unsigned long long dg[32];
@@ -2283,47 +2430,33 @@ int vr_apply_finish(vr_context *c) {
 #endif
   float ms = 0.f;
   VR_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  // per particle, and their sums in the context's TraceInfo
+  unsigned long long sum[80] = {};
+  for (size_t q = 0; q < nPart; ++q) {
+    vr_trace_info &pi = c->launches[q].info;
+    pi = vr_trace_info{};
+    pi.numRays = c->numRaysLast;
+    info_from_counters(pi, all.data() + 80 * q);
+    for (size_t w = 0; w < 80; ++w)
+      sum[w] += all[80 * q + w];
+  }
   vr_trace_info &i = c->info;
   i.numRays = c->numRaysLast;
-  if (nPart == 1) {
-    info_from_counters(i, cnt);
-  } else {
-    // per particle, and their sums in the context's TraceInfo
-    vr_trace_info sum{};
-    for (size_t q = 0; q < nPart; ++q) {
-      vr_trace_info &pi = c->launches[q].info;
-      pi = vr_trace_info{};
-      pi.numRays = c->numRaysLast;
-      info_from_counters(pi, all.data() + 80 * q);
-      sum.totalRaysTraced += pi.totalRaysTraced;
-      sum.nonGeometryHits += pi.nonGeometryHits;
-      sum.geometryHits += pi.geometryHits;
-      sum.particleHits += pi.particleHits;
-      sum.boundaryHits += pi.boundaryHits;
-      sum.reflections += pi.reflections;
-      sum.raysTerminated += pi.raysTerminated;
-      sum.rngFullStates += pi.rngFullStates;
-    }
-    const uint64_t nr = i.numRays;
-    const int32_t w = i.warning, e = i.error;
-    i = sum;
-    i.numRays = nr;
-    i.warning = w;
-    i.error = e;
-  }
+  info_from_counters(i, sum);
   i.timeTrace = ms * 1e-3;
   double kms = 0.0;
   for (size_t b = 0; b < c->numTraceLaunches; ++b) {
     float m = 0.f;
     VR_HIP(c, hipEventElapsedTime(&m, c->evK[2 * b], c->evK[2 * b + 1]));
     kms += m;
-    if (std::getenv("VR_PRINT_LAUNCHES")) // (diagnostics: a scene with relief runs two trace launches per batch)
+    if (c->knobs.printLaunches) // (diagnostics: a scene with relief runs two trace launches per batch)
       std::fprintf(stderr, "[vr] trace launch %zu: %.3f ms\n", b, m);
   }
   i.timeTraceKernel = kms * 1e-3;
-  if (std::getenv("VR_PRINT_LAUNCHES") && c->params.spillCount) { // (diagnostics: rays the tight general relief kernel handed over)
+  const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
+  if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)
     uint32_t sp = 0;
-    if (hipMemcpy(&sp, c->params.spillCount, 4, hipMemcpyDeviceToHost) == hipSuccess)
+    if (hipMemcpy(&sp, spillCount, 4, hipMemcpyDeviceToHost) == hipSuccess)
       std::fprintf(stderr, "[vr] spilled rays (last batch): %u\n", sp);
   }
   double gms = 0.0;
@@ -2350,80 +2483,42 @@ int vr_apply_finish(vr_context *c) {
   return VR_OK;
 }
 
-// Trace::apply() set-up.  One particle: prepare_one.  Several (vr_set_particles): every particle is prepared in
-// turn — its kernel variant, launch geometry, per-material sticking, accumulator planes and counter block — with
-// ONE seed for the whole apply (gpu/raygTrace.hpp:163-248).
+// Trace::apply() set-up: every particle (vr_set_particles) is prepared in turn — its kernel variant, launch geometry,
+// per-material sticking, accumulator planes and counter block — with ONE seed for the whole apply
+// (gpu/raygTrace.hpp:163-248).  The knobs are read here, once per apply.
 int vr_apply_prepare(vr_context *c) {
   if (!c)
     return VR_E_INVALID;
-  if (c->specs.size() <= 1) {
-    c->dataBase = 0;
-    c->counterSlot = 0;
-    return prepare_one(c);
-  }
-  if (c->useRandomSeed && !c->haveSharedSeed) { // one draw for all particles of this apply
+  c->knobs = read_knobs();
+  const size_t nPart = std::max<size_t>(1, c->specs.size());
+  const bool multi = nPart > 1; // (one particle: vr_set_particles made it the active one already)
+  if (multi && c->useRandomSeed && !c->haveSharedSeed) { // one draw for all particles of this apply
     std::random_device rd;
     c->sharedSeed = (uint32_t)rd();
     c->haveSharedSeed = true;
     c->keepSharedSeed = false;
   }
-  for (auto &L : c->launches)
-    if (L.primSticking) {
-      (void)hipFree(L.primSticking);
-      L.primSticking = nullptr;
-    }
-  c->launches.assign(c->specs.size(), ParticleLaunch{});
+  if (c->launches.size() != nPart) {
+    c->launches.clear();
+    c->launches.resize(nPart);
+  }
   uint32_t base = 0;
-  for (size_t q = 0; q < c->specs.size(); ++q) {
-    activate_particle(c, c->specs[q]);
-    c->dataBase = base;
-    c->counterSlot = (uint32_t)q;
-    const int r = prepare_one(c);
-    if (r != VR_OK) {
-      activate_particle(c, c->specs[0]);
-      return r;
-    }
+  for (size_t q = 0; q < nPart; ++q) {
+    if (multi)
+      activate_particle(c, c->specs[q]);
     ParticleLaunch &L = c->launches[q];
-    L.params = c->params;
-    L.grid = c->grid;
-    L.traceMode = c->traceMode;
-    L.kernelParticle = c->kernelParticle;
-    L.absorb = c->absorb;
-    L.numData = c->numData;
+    L.slot = (uint32_t)q;
     L.dataBase = base;
-    L.userKernel = c->userKernel;
-    L.userGen = c->userGen;
-    L.relief = c->reliefScene;
-    L.looseMode = c->looseMode;
-    L.looseGrid = c->looseGrid;
-    if (c->havePrimSticking) { // this particle's sticking map: the next prepare would overwrite the shared buffer
-      L.primSticking = c->dPrimSticking.p;
-      L.params.primSticking = L.primSticking;
-      c->dPrimSticking.p = nullptr;
-      c->dPrimSticking.cap = 0;
-      c->havePrimSticking = false;
+    const int r = prepare_one(c, L);
+    if (r != VR_OK) {
+      if (multi)
+        activate_particle(c, c->specs[0]);
+      return r;
     }
     base += c->numData;
   }
-  // the shared buffers were (re-)sized by each prepare in turn and only ever grow — a later particle may have moved
-  // one (records with RNG cursors after records without, a larger grid's walk stacks): everybody gets the final addresses
-  for (size_t q = 0; q < c->launches.size(); ++q) {
-    TraceParams &lp = c->launches[q].params;
-    lp.slotRec = c->dSlotRec.p;
-    lp.binCount = c->dBinCount.p;
-    lp.walkStack = c->dWalkStack.p;
-    lp.rngScratch = c->dScratch.p;
-    lp.workCounter = c->dWorkQ.p;
-    lp.recExtra = lp.recExtra ? c->dRecExtra.p : nullptr;
-    lp.spillRec = lp.spillRec ? c->dSpillRec.p : nullptr;
-    lp.spillCount = lp.spillCount ? c->dSpillCount.p : nullptr;
-    lp.counters = c->dCounters.p + 80 * q;
-    lp.fluxAcc = c->dFluxAcc.p + (size_t)c->launches[q].dataBase * lp.planeStride;
-  }
-  activate_particle(c, c->specs[0]);
-  c->dataBase = 0;
-  c->counterSlot = 0;
-  c->prepared = true;
+  if (multi)
+    activate_particle(c, c->specs[0]); // (between applies the first particle is the active one)
   return VR_OK;
 }
 
@@ -2602,7 +2697,7 @@ int vr_get_particle_trace_info(const vr_context *c, uint32_t q, vr_trace_info *o
 int vr_get_trace_mode(const vr_context *c, int32_t *mode) {
   if (!c || !mode)
     return VR_E_INVALID;
-  *mode = c->traceMode;
+  *mode = c->launches.empty() ? 0 : current_launch(c).traceMode;
   return VR_OK;
 }
 
@@ -2708,7 +2803,7 @@ int vr_smooth_flux(vr_context *c, float *flux, uint32_t n, int numNeighbors) {
   // device path: the geometry's own neighbourhood (numNeighbors == 1, what every reference example asks for) is
   // resident with the device-built scene; a wider one (k > 1) is a range query of radius k * 2 r over the resident BVH,
   // fused with the averaging.  No download of any neighbourhood.
-  if (c->haveSetup && !c->geometryDirty && !std::getenv("VR_HOST_SMOOTH")) {
+  if (c->haveSetup && !c->geometryDirty && !read_knobs().hostSmooth) {
     VR_HIP(c, hipSetDevice(c->device));
     DevBuf<float> dIn, dOut;
     DevBuf<uint32_t> dOv;
@@ -2825,14 +2920,13 @@ int vr_debug_intersect(vr_context *c, const float *org, const float *dir, const 
   VR_HIP(c, hipMemcpy(dD.p, dir, (size_t)n * 12, hipMemcpyHostToDevice));
   VR_HIP(c, hipMemcpy(dT.p, tnear, (size_t)n * 4, hipMemcpyHostToDevice));
   // the ordered (pair-node, stack) walk of the trace kernels; VR_DEBUG_WALK=0: the escape-link walk it replaced
-  int ordered = 1;
-  if (const char *e = std::getenv("VR_DEBUG_WALK"))
-    ordered = std::atoi(e) != 0;
+  const int ordered = read_knobs().debugWalk ? 1 : 0;
+  const TraceParams p = launch_params(c, current_launch(c));
   // (64-thread blocks running concurrently must not share a slab: at most walkStackWaves blocks per launch)
   const uint32_t chunk = (uint32_t)std::max<size_t>(c->walkStackWaves, 1) * 64u;
   for (uint32_t f0 = 0; f0 < n; f0 += chunk) {
     const uint32_t m = std::min(chunk, n - f0);
-    VR_HIP(c, launch_debug_intersect(c->params, c->geo.geo, dO.p + 3 * (size_t)f0, dD.p + 3 * (size_t)f0, dT.p + f0, m,
+    VR_HIP(c, launch_debug_intersect(p, c->geo.geo, dO.p + 3 * (size_t)f0, dD.p + 3 * (size_t)f0, dT.p + f0, m,
                                      dG.p + f0, dP.p + f0, dt.p + f0, ordered, (unsigned)std::max<size_t>(c->walkStackWaves, 1), c->stream));
   }
   VR_HIP(c, hipStreamSynchronize(c->stream));
@@ -2876,7 +2970,7 @@ int vr_debug_process_hit(vr_context *c, const float *org, const float *dir, cons
   VR_HIP(c, hipMemcpy(dD.p, dir, (size_t)n * 12, hipMemcpyHostToDevice));
   VR_HIP(c, hipMemcpy(dT.p, tfar, (size_t)n * 4, hipMemcpyHostToDevice));
   VR_HIP(c, hipMemcpy(dP.p, primID, (size_t)n * 4, hipMemcpyHostToDevice));
-  VR_HIP(c, launch_debug_process_hit(c->params, c->geo.D, dO.p, dD.p, dT.p, dP.p, n, dOo.p, dDo.p, dR.p, c->stream));
+  VR_HIP(c, launch_debug_process_hit(launch_params(c, current_launch(c)), c->geo.D, dO.p, dD.p, dT.p, dP.p, n, dOo.p, dDo.p, dR.p, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   VR_HIP(c, hipMemcpy(outOrg, dOo.p, (size_t)n * 12, hipMemcpyDeviceToHost));
   VR_HIP(c, hipMemcpy(outDir, dDo.p, (size_t)n * 12, hipMemcpyDeviceToHost));
@@ -2894,7 +2988,7 @@ int vr_debug_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint3
   }
   if (n > c->slotStride)
     return fail(c, VR_E_INVALID, "vr_debug_source_sample: more rays than one batch holds");
-  TraceParams p = c->params;
+  TraceParams p = launch_params(c, current_launch(c));
   p.seed = seed;
   p.batchCount = n;
   p.binCount = nullptr; // no binning: record i goes to slot i
@@ -2932,11 +3026,12 @@ int vr_debug_model_source_sample(vr_context *c, const uint64_t *idx, uint32_t n,
     if (r != VR_OK)
       return r;
   }
-  if (c->specs.size() > 1 || !c->userGen)
+  const ParticleLaunch &L = current_launch(c);
+  if (c->specs.size() > 1 || !L.userGen)
     return fail(c, VR_E_STATE, "vr_debug_model_source_sample: the active particle is not (the only) stateful model");
   if (n > c->batchCap)
     return fail(c, VR_E_INVALID, "vr_debug_model_source_sample: more rays than one batch holds");
-  TraceParams p = c->params;
+  TraceParams p = launch_params(c, L);
   p.seed = seed;
   p.batchCount = n;
   p.binCount = nullptr; // no binning: record i goes to slot i
@@ -2947,7 +3042,7 @@ int vr_debug_model_source_sample(vr_context *c, const uint64_t *idx, uint32_t n,
   if (n) {
     void *args[] = {&p};
     const unsigned grid = std::min<unsigned>((n + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
-    VR_HIP(c, hipModuleLaunchKernel(c->userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
+    VR_HIP(c, hipModuleLaunchKernel(L.userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
   }
   VR_HIP(c, hipStreamSynchronize(c->stream));
   std::vector<float> A((size_t)n * 8), E((size_t)n * 4);

@@ -63,8 +63,9 @@ void host_orthonormal_basis(const float *v, float *basis9);
 // rayGeometryDisk.hpp:266-354 (+ rayDiskBoundingBoxIntersector.hpp)
 void host_disk_areas(const HostGeometry &g, const AreaParams &p, std::vector<float> &areas);
 
-// LBVH over primitive boxes; fills bvh.nodes / bvh.order
-void host_build_bvh(const HostGeometry &g, Bvh &bvh);
+// LBVH over primitive boxes; fills bvh.nodes / bvh.order.  mortonAniso (>= 1): the Morton grid's cells have the scene
+// box's proportions, but at most mortonAniso : 1 (VR_MORTON_ANISO by default)
+void host_build_bvh(const HostGeometry &g, Bvh &bvh, float mortonAniso);
 // leaf-ordered primitive records (vr_types.hpp)
 void host_pack_prims(const HostGeometry &g, const Bvh &bvh, std::vector<float> &prims);
 
