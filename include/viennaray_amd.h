@@ -173,6 +173,15 @@ int vr_set_host_ray_weights(vr_context *ctx, const float *weights, uint64_t n);
 /* Source::getSourceArea() (raySource.hpp:17) for normalizeFlux(SOURCE) (rayTraceDisk.hpp:127,
  * rayTraceTriangle.hpp:113); area <= 0: SourceRandom's (raySourceRandom.hpp:40-47, the bbox source face)       */
 int vr_set_source_area(vr_context *ctx, float area);
+/* setSurfaceSource / clearSurfaceSource (gpu/raygTrace.hpp:267-297; sample: gpu/raygSource.hpp:13-26, 65-81, 105-118):
+ * the rays start ON the n given points — numRaysFixed if set, else numRaysPerPoint, rays per point (:134-149), global ray
+ * idx at point idx / raysPerPoint — from positions3[3 j] + unit normal * sourceOffset, along a power-1 cosine
+ * distribution about normals3[3 j] (any non-zero length), with start weight weights[j] (finite, >= 0), sampled on the
+ * device.  normalizeFlux(SOURCE) uses sourceArea (> 0) while it is set (gpu/raygTraceDisk.hpp:90-91,
+ * gpu/raygTraceTriangle.hpp:45-46).  The tables are copied to the device by this call.  Replaces a source grid and host
+ * rays, and is replaced by them; n == 0 = clearSurfaceSource().  An invalid argument leaves the previous source set.   */
+int vr_set_surface_source(vr_context *ctx, const float *positions3, const float *normals3, const float *weights, uint32_t n,
+                          float sourceArea, float sourceOffset);
 int vr_set_number_of_rays_per_point(vr_context *ctx, uint64_t n);
 int vr_set_number_of_rays_fixed(vr_context *ctx, uint64_t n);
 int vr_set_max_reflections(vr_context *ctx, uint32_t n);
@@ -289,6 +298,10 @@ int vr_debug_source_sample(vr_context *ctx, const uint64_t *idx, uint32_t n,
  * the engine outputs consumed before the trace (init + source sample) of global ray indices idx[]         */
 int vr_debug_model_source_sample(vr_context *ctx, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
                                  uint32_t *draws);
+/* ... of the surface source (vr_set_surface_source; gpu/raygSource.hpp:65-81), by the device function its generator
+ * runs: origin, direction, start weight and the engine outputs consumed (2) of global ray indices idx[]    */
+int vr_debug_surface_source_sample(vr_context *ctx, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
+                                   float *weight, uint32_t *draws);
 /* first `count` raw mt19937_64 outputs of the per-ray engine of ray idx      */
 int vr_debug_rng_outputs(vr_context *ctx, uint64_t idx, uint32_t seed,
                          uint32_t count, uint64_t *out);

@@ -1104,6 +1104,34 @@ public:
     if (ctx_)
       check(vr_set_source_area(ctx_, 0.f));
   }
+  /// gpu/raygTrace.hpp:267-297: the rays of the next applies start ON the given points (numRaysFixed if set, else
+  /// numRaysPerPoint, rays per point), leave along a cosine distribution about each point's normal from position +
+  /// unit normal * sourceOffset and carry the point's weight; sampled on the device.  normalizeFlux(SOURCE) then uses
+  /// sourceArea.  Takes the place of any other source; an empty set of points is clearSurfaceSource().
+  void setSurfaceSource(const std::vector<Vec3D<NumericType>> &positions, const std::vector<Vec3D<NumericType>> &normals,
+                        const std::vector<NumericType> &weights, NumericType sourceArea, NumericType sourceOffset) {
+    if (!ctx_)
+      return;
+    if (positions.size() != normals.size() || positions.size() != weights.size() || positions.size() > 0xFFFFFFFFull) {
+      setterError_ = true;
+      RTInfo_.error = true;
+      std::cerr << "viennaray_amd: setSurfaceSource: one normal and one weight per position.\n";
+      return;
+    }
+    const auto pos = flatten3(positions), nrm = flatten3(normals);
+    const std::vector<float> w(weights.begin(), weights.end());
+    const int rc = vr_set_surface_source(ctx_, pos.data(), nrm.data(), w.data(), (uint32_t)positions.size(),
+                                         (float)sourceArea, (float)sourceOffset);
+    check(rc);
+    if (rc == VR_OK && !positions.empty()) { // (a refused source leaves the previous one in place)
+      pSource_.reset();
+      sourceOnDevice_ = false;
+    }
+  }
+  void clearSurfaceSource() {
+    if (ctx_)
+      check(vr_set_surface_source(ctx_, nullptr, nullptr, nullptr, 0, 0.f, 0.f));
+  }
   void enableProgressBar() {}
   void disableProgressBar() {}
 

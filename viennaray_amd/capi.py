@@ -69,6 +69,7 @@ SIGNATURES = {
     "vr_set_host_rays": (C.c_int, [_vp, _fp, _fp, _u32p, C.c_uint64]),
     "vr_set_host_ray_weights": (C.c_int, [_vp, _fp, C.c_uint64]),
     "vr_set_source_area": (C.c_int, [_vp, C.c_float]),
+    "vr_set_surface_source": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, C.c_float, C.c_float]),
     "vr_reserve_rays": (C.c_int, [_vp, C.c_uint64]),
     "vr_set_number_of_rays_per_point": (C.c_int, [_vp, C.c_uint64]),
     "vr_set_number_of_rays_fixed": (C.c_int, [_vp, C.c_uint64]),
@@ -108,6 +109,7 @@ SIGNATURES = {
     "vr_debug_process_hit": (C.c_int, [_vp, _fp, _fp, _fp, _u32p, C.c_uint32, _fp, _fp, _i32p]),
     "vr_debug_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp]),
     "vr_debug_model_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp, _u32p]),
+    "vr_debug_surface_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp, _fp, _u32p]),
     "vr_debug_rng_outputs": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
     "vr_debug_issue_rate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_double)]),
     "vr_debug_bvh_stats": (C.c_int, [_vp, _u32p]),

@@ -308,6 +308,11 @@ struct vr_context {
   std::vector<uint32_t> hostDraws;
   std::vector<float> hostWeights;  // Source::getInitialRayWeight(idx) of the host rays (empty: 1)
   float sourceAreaOverride = 0.f;  // Source::getSourceArea() of a user source (<= 0: SourceRandom's, the bbox face)
+  // surface source (vr_set_surface_source): the tables live on the device, uploaded when they are set
+  uint32_t surfCount = 0;          // source points (0: no surface source)
+  float surfArea = 0.f, surfOffset = 0.f;
+  DevBuf<float> dSurfPos, dSurfNrm, dSurfWeights;
+  DevBuf<float> dSurfRayWeights;   // start weight of every ray of one batch (TraceParams::hostWeights of a surface source)
   uint64_t reserveRays = 0;        // vr_reserve_rays: the ray-stream buffers hold at least this many rays
   bool sourceDirty = false;
   DevBuf<float> dGrid, dHostOrg, dHostDir, dHostWeights;
@@ -914,6 +919,7 @@ int vr_set_source_grid(vr_context *c, const float *points3, uint32_t n) {
   c->hostDir.clear();
   c->hostDraws.clear();
   c->hostWeights.clear();
+  c->surfCount = 0;
   c->sourceDirty = true;
   c->prepared = false;
   return VR_OK;
@@ -931,7 +937,58 @@ int vr_set_host_rays(vr_context *c, const float *org3, const float *dir3, const 
     c->hostDraws.clear();
   c->hostWeights.clear();
   c->gridPoints.clear();
+  c->surfCount = 0;
   c->sourceDirty = true;
+  c->prepared = false;
+  return VR_OK;
+}
+// Surface source (gpu/raygTrace.hpp:267-297 setSurfaceSource / clearSurfaceSource): the next applies start their rays ON
+// the n points — numRaysFixed if set, else numRaysPerPoint, rays each (:134-149) — from positions3[3 j] + unit normal *
+// sourceOffset along a cosine distribution about normals3[3 j] (any non-zero length), with start weight weights[j];
+// normalizeFlux(SOURCE) then uses sourceArea (gpu/raygTraceDisk.hpp:90-91).  n == 0: back to SourceRandom.
+int vr_set_surface_source(vr_context *c, const float *positions3, const float *normals3, const float *weights, uint32_t n,
+                          float sourceArea, float sourceOffset) {
+  if (!c)
+    return VR_E_INVALID;
+  if (n == 0) {
+    if (c->surfCount) {
+      c->surfCount = 0;
+      c->prepared = false;
+    }
+    return VR_OK;
+  }
+  if (!positions3 || !normals3 || !weights)
+    return fail(c, VR_E_INVALID, "vr_set_surface_source: positions, normals and weights must not be NULL when n > 0");
+  if (!(sourceArea > 0.f) || !std::isfinite(sourceArea))
+    return fail(c, VR_E_INVALID, "vr_set_surface_source: sourceArea must be positive and finite");
+  if (!(sourceOffset >= 0.f) || !std::isfinite(sourceOffset))
+    return fail(c, VR_E_INVALID, "vr_set_surface_source: sourceOffset must be finite and >= 0");
+  for (size_t j = 0; j < n; ++j) {
+    const float *q = positions3 + 3 * j, *m = normals3 + 3 * j;
+    if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]))
+      return fail(c, VR_E_INVALID, ("vr_set_surface_source: position " + std::to_string(j) + " is not finite").c_str());
+    const float len = std::sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]); // (as the generator's vnormalize)
+    if (!(len > 0.f) || !std::isfinite(len))
+      return fail(c, VR_E_INVALID, ("vr_set_surface_source: normal " + std::to_string(j) + " has zero or non-finite length").c_str());
+    if (!(weights[j] >= 0.f) || !std::isfinite(weights[j]))
+      return fail(c, VR_E_INVALID, ("vr_set_surface_source: weight " + std::to_string(j) + " is negative or not finite").c_str());
+  }
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_HIP(c, hipStreamSynchronize(c->stream)); // (a launched apply may still read the previous tables)
+  VR_HIP(c, c->dSurfPos.ensure((size_t)n * 3));
+  VR_HIP(c, c->dSurfNrm.ensure((size_t)n * 3));
+  VR_HIP(c, c->dSurfWeights.ensure(n));
+  VR_HIP(c, hipMemcpy(c->dSurfPos.p, positions3, (size_t)n * 12, hipMemcpyHostToDevice));
+  VR_HIP(c, hipMemcpy(c->dSurfNrm.p, normals3, (size_t)n * 12, hipMemcpyHostToDevice));
+  VR_HIP(c, hipMemcpy(c->dSurfWeights.p, weights, (size_t)n * 4, hipMemcpyHostToDevice));
+  c->surfCount = n;
+  c->surfArea = sourceArea;
+  c->surfOffset = sourceOffset;
+  c->gridPoints.clear();
+  c->hostOrg.clear();
+  c->hostDir.clear();
+  c->hostDraws.clear();
+  c->hostWeights.clear();
   c->prepared = false;
   return VR_OK;
 }
@@ -1321,7 +1378,20 @@ static int effective_direction(const vr_context *c) {
 
 // rayTraceKernel.hpp:57-61: numRaysFixed, or source.getNumPoints() * numRaysPerPoint
 // (SourceRandom: the geometry's points; SourceGrid: the grid's; host rays: exactly those given)
+// Source::getSourceArea(): a surface source's own (gpu/raygTraceDisk.hpp:90-91), a user source's override, else
+// SourceRandom's — the source face of the bounding box
+static float effective_source_area(const vr_context *c) {
+  if (c->surfCount)
+    return c->surfArea;
+  return c->sourceAreaOverride > 0.f ? c->sourceAreaOverride : c->sourceArea;
+}
+
+// rays per point of a surface source (gpu/raygTrace.hpp:134-149: the fixed count, if set, is the launch's x extent)
+static uint64_t surface_rays_per_point(const vr_context *c) { return c->numRaysFixed ? c->numRaysFixed : c->numRaysPerPoint; }
+
 static uint64_t rays_of_apply(const vr_context *c) {
+  if (c->surfCount)
+    return (uint64_t)c->surfCount * surface_rays_per_point(c);
   if (!c->hostOrg.empty())
     return c->hostOrg.size() / 3;
   const uint64_t srcPoints = !c->gridPoints.empty() ? c->gridPoints.size() / 3 : c->geo.numPrims;
@@ -1423,6 +1493,11 @@ static int check_settings(vr_context *c) {
   }
   if (c->geo.geo == 0 && c->geo.diskRadius > c->geo.gridDelta)
     c->info.warning = 1;
+  // (a surface source divides the ray index by the rays per point in 32 bits: the index is tea3's 32-bit input anyway)
+  if (c->surfCount && rays_of_apply(c) > 0xFFFFFFFFull) {
+    c->info.error = 1;
+    return fail(c, VR_E_INVALID, "surface source: points x rays per point exceeds the 32-bit ray index of one apply");
+  }
   return VR_OK;
 }
 
@@ -1550,7 +1625,7 @@ static int choose_particle_kernel(vr_context *c, ParticleLaunch &L, PrepareState
   const bool extended = c->particleKind >= VR_PARTICLE_CONED_COSINE || c->useWdist || c->meanFreePath > 0.f;
   if (extended)
     L.absorb = false;
-  if (!c->hostOrg.empty() && !c->hostWeights.empty())
+  if ((!c->hostOrg.empty() && !c->hostWeights.empty()) || c->surfCount)
     L.absorb = false; // (the absorbing kernels credit unit weights)
   // (the rare, register-hungry options — coned-cosine model, WDIST crediting, mean free path — have an instantiation
   //  of their own: multi-label and per-material particles should not pay for them)
@@ -1561,9 +1636,10 @@ static int choose_particle_kernel(vr_context *c, ParticleLaunch &L, PrepareState
       return fail(c, VR_E_INVALID, "this particle model was registered without VR_MODEL_NEEDS_FULL: its code object has no "
                                    "kernel with WDIST crediting / mean-free-path scattering");
     extFull = um.needsFull;
-    if (um.numState > 0 && (!c->gridPoints.empty() || !c->hostOrg.empty()))
+    if (um.numState > 0 && (!c->gridPoints.empty() || !c->hostOrg.empty() || c->surfCount))
       return fail(c, VR_E_INVALID, "a stateful particle model (numState > 0) runs its init on the device before the source "
-                                   "sample: SourceRandom only (plain or with a primary direction), not SourceGrid or a host source");
+                                   "sample: SourceRandom only (plain or with a primary direction), not SourceGrid, a host "
+                                   "source or a surface source");
   }
   S.stateful = c->userModel >= 0 && c->userModels[c->userModel].numState > 0;
   L.kernelParticle = extended ? (extFull ? (int)P_EXT_FULL : (int)P_EXT) : c->particleKind;
@@ -1609,7 +1685,7 @@ static int build_relief_field(vr_context *c, ParticleLaunch &L, const PrepareSta
   const float travel = K.reliefTravel;
   L.relief = false;
   const float thickScene = c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]];
-  const bool plainSource = !c->usePrimaryDirection && c->gridPoints.empty() && c->hostOrg.empty();
+  const bool plainSource = !c->usePrimaryDirection && c->gridPoints.empty() && c->hostOrg.empty() && !c->surfCount;
   const bool kernelOk = L.absorb || (c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT);
   const bool want = !S.flatScene && !S.smallScene && plainSource && kernelOk && c->userModel < 0 && c->geo.gridDelta > 0.f &&
                     thickScene <= K.reliefMaxThick * c->geo.gridDelta && !K.noRelief;
@@ -1745,9 +1821,11 @@ static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState 
   // 32-byte records for every particle (vr_types.hpp); a non-absorbing particle under a source whose origin plane or
   // draw count varies (tilted, grid, host rays) adds 16 bytes per ray in a side array
   // (a stateful model's init draws before the source sample: its draw count varies too)
-  L.recExtra = !L.absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || !c->hostOrg.empty() || S.stateful);
+  L.recExtra = !L.absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || !c->hostOrg.empty() || c->surfCount || S.stateful);
   if (L.recExtra)
     VR_HIP(c, c->dRecExtra.ensure_grow((size_t)c->batchCap * 4));
+  if (c->surfCount)
+    VR_HIP(c, c->dSurfRayWeights.ensure_grow(c->batchCap));
   if (S.stateful) // (the state of every ray of a batch, float4 per ray; room for vr_reserve_rays' largest batch)
     VR_HIP(c, c->dRayState.ensure_grow((size_t)std::max<uint64_t>(c->batchCap, std::min<uint64_t>(c->reserveRays, 1ull << 27)) * 4));
   size_t slotsWant = e.slots, binsWant = e.cntWords;
@@ -1922,6 +2000,16 @@ static int fill_trace_params(vr_context *c, ParticleLaunch &L, PrepareState &S) 
   p.hostDir = c->hostOrg.empty() ? nullptr : c->dHostDir.p;
   p.hostDraws = c->hostDraws.empty() ? nullptr : c->dHostDraws.p;
   p.hostWeights = (c->hostOrg.empty() || c->hostWeights.empty()) ? nullptr : c->dHostWeights.p;
+  p.surfPos = p.surfNrm = p.surfWeights = nullptr;
+  p.surfRays = 0;
+  p.surfOffset = 0.f;
+  if (c->surfCount) { // (hostWeights: the batch's start weights, written by the generator — batch_params)
+    p.surfPos = c->dSurfPos.p;
+    p.surfNrm = c->dSurfNrm.p;
+    p.surfWeights = c->dSurfWeights.p;
+    p.surfRays = (uint32_t)surface_rays_per_point(c);
+    p.surfOffset = c->surfOffset;
+  }
   p.accMask = c->accReplicas - 1u;
   VR_HIP(c, c->dCounters.ensure(80 * c->launches.size()));
   VR_HIP(c, c->dWorkQ.ensure(VR_QUEUES * VR_QUEUE_STRIDE));
@@ -2191,6 +2279,13 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   size_bins(c->geo.D, count, c->raysPerBin, p, nbBatch); // (<= the grid the buffers were sized for)
   nbBatch = std::min(nbBatch, c->numBins);
   p.numBins = nbBatch;
+  // a surface source has no sort bins: its records lie in index order in the overflow region (gen_surface_kernel),
+  // which the trace kernel reads as virtual bins of binCap rays
+  const bool unbinned = p.surfPos != nullptr;
+  if (p.surfPos) // the batch's start weights, addressed by GLOBAL ray index like a host source's (gen_surface_kernel writes them)
+    p.hostWeights = c->dSurfRayWeights.p - first;
+  if (unbinned)
+    p.numBins = 0;
   if (L.relief)
     size_loose(c->geo.D, p); // (p.ovCap = the batch capacity: the tight bins' overflow region keeps its full size)
   else
@@ -2207,7 +2302,8 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
     uint64_t spanBins = L.traceMode == 0 ? 16 : ((L.traceMode == 3 || L.traceMode == 6) ? 64 : 32);
     if (K.spanBins)
       spanBins = *K.spanBins;
-    p.chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spanBins, nbBatch / std::max<uint64_t>(waves * 2, 1)));
+    const uint64_t binsToDeal = unbinned ? ((uint64_t)count + p.binCap - 1) / p.binCap : nbBatch;
+    p.chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spanBins, binsToDeal / std::max<uint64_t>(waves * 2, 1)));
   }
   // One queue per XCD pays where neighbouring rounds share primitive records that do not fit an XCD's 4 MiB L2 and the
   // work per bin is even: flat scenes of more than ~10^5 primitives (measured, VR_QUEUES=1 / 8 on one box: C2 sticking
@@ -2215,7 +2311,7 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   // 9.0 -> 5.2 GB).  A structured scene is L2 resident anyway and its bins differ in cost — an eighth of the trench is
   // not an eighth of the work: trench3D +3 %, C5 +6 %: one queue.
   const bool flat = L.traceMode == 3; // (the absorbing kernels have the single queue compiled in)
-  p.numQueues = (flat && c->geo.numPrims > (1u << 17) && nbBatch >= 64u * VR_QUEUES * p.chunk) ? VR_QUEUES : 1u;
+  p.numQueues = (flat && c->geo.numPrims > (1u << 17) && p.numBins >= 64u * VR_QUEUES * p.chunk) ? VR_QUEUES : 1u;
   if (K.numQueues)
     p.numQueues = *K.numQueues;
   return p;
@@ -2749,7 +2845,7 @@ static int normalize_on_device(vr_context *c, uint32_t n, int normType) {
   if (normType == VR_NORM_SOURCE) {
     if (c->numRaysLast == 0)
       return fail(c, VR_E_STATE, "No source was specified in rayTrace for the normalization.");
-    normFactor = (c->sourceAreaOverride > 0.f ? c->sourceAreaOverride : c->sourceArea) / c->numRaysLast;
+    normFactor = effective_source_area(c) / c->numRaysLast;
   } else if (normType != VR_NORM_MAX) {
     return VR_OK; // `default: break;` in the reference
   }
@@ -2883,7 +2979,7 @@ int vr_get_bounding_box(vr_context *c, float *out6) {
   return VR_OK;
 }
 float vr_get_source_area(vr_context *c) {
-  return c ? (c->sourceAreaOverride > 0.f ? c->sourceAreaOverride : c->sourceArea) : 0.f;
+  return c ? effective_source_area(c) : 0.f;
 }
 float vr_get_disk_radius(const vr_context *c) { return c ? c->geo.diskRadius : 0.f; }
 int vr_get_neighbor_counts(vr_context *c, uint32_t *out, uint32_t n) {
@@ -2988,6 +3084,10 @@ int vr_debug_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint3
   }
   if (n > c->slotStride)
     return fail(c, VR_E_INVALID, "vr_debug_source_sample: more rays than one batch holds");
+  if (c->surfCount) // (the surface generator looks its point up by the index)
+    for (uint32_t i = 0; i < n; ++i)
+      if (idx[i] >= rays_of_apply(c))
+        return fail(c, VR_E_INVALID, "vr_debug_source_sample: ray index beyond the surface source's ray count");
   TraceParams p = launch_params(c, current_launch(c));
   p.seed = seed;
   p.batchCount = n;
@@ -3012,6 +3112,47 @@ int vr_debug_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint3
     dir[3 * i + 2] = r[5];
   }
   dI.release();
+  return VR_OK;
+}
+
+// The surface source's sample (vr_trace.hip: surface_sample, the device function of its generator) for the global ray
+// indices idx[]: origin, direction, start weight and the engine outputs consumed (2)
+int vr_debug_surface_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
+                                   float *weight, uint32_t *draws) {
+  if (!c || !idx || !org || !dir || !weight || !draws)
+    return VR_E_INVALID;
+  if (!c->surfCount)
+    return fail(c, VR_E_STATE, "vr_debug_surface_source_sample: no surface source is set");
+  if (!c->prepared) {
+    int r = vr_apply_prepare(c);
+    if (r != VR_OK)
+      return r;
+  }
+  const uint64_t total = rays_of_apply(c);
+  for (uint32_t i = 0; i < n; ++i)
+    if (idx[i] >= total)
+      return fail(c, VR_E_INVALID, "vr_debug_surface_source_sample: ray index beyond the apply's ray count");
+  if (n == 0)
+    return VR_OK;
+  TraceParams p = launch_params(c, current_launch(c));
+  p.seed = seed;
+  p.batchCount = n;
+  DevBuf<unsigned long long> dI;
+  DevBuf<float> dO, dD, dW;
+  DevBuf<uint32_t> dK;
+  VR_HIP(c, dI.ensure(n));
+  VR_HIP(c, dO.ensure((size_t)n * 3));
+  VR_HIP(c, dD.ensure((size_t)n * 3));
+  VR_HIP(c, dW.ensure(n));
+  VR_HIP(c, dK.ensure(n));
+  VR_HIP(c, hipMemcpy(dI.p, idx, (size_t)n * 8, hipMemcpyHostToDevice));
+  p.idxList = dI.p;
+  VR_HIP(c, launch_debug_surface_sample(p, (unsigned)c->numCUs * 8u, dO.p, dD.p, dW.p, dK.p, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  VR_HIP(c, hipMemcpy(org, dO.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+  VR_HIP(c, hipMemcpy(dir, dD.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+  VR_HIP(c, hipMemcpy(weight, dW.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  VR_HIP(c, hipMemcpy(draws, dK.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return VR_OK;
 }
 

@@ -8,6 +8,9 @@
 namespace vr {
 
 hipError_t launch_gen(const TraceParams &p, int D, bool keepRng, unsigned maxBlocks, hipStream_t s);
+// surface_sample (the surface source's generator) for the p.batchCount ray indices p.idxList[]
+hipError_t launch_debug_surface_sample(const TraceParams &p, unsigned maxBlocks, float *org, float *dir, float *weight,
+                                       unsigned *draws, hipStream_t s);
 hipError_t launch_scan(unsigned *data, unsigned n, unsigned *tmp, hipStream_t s);
 hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid,
                         hipStream_t s);

@@ -181,6 +181,23 @@ template <int D> __device__ __forceinline__ unsigned bin_of_relief(const TracePa
 // ---------------------------------------------------------------------------
 // gen_kernel: ray index -> ray record
 // ---------------------------------------------------------------------------
+// the record of batch ray i in `slot`: both forms of vr_types.hpp
+template <bool KEEP>
+__device__ __forceinline__ void gen_write(const TraceParams &p, unsigned slot, unsigned i, const V3 &o, const V3 &d, unsigned k,
+                                          u64 lo, u64 hi) {
+  float4 *rec = reinterpret_cast<float4 *>(p.slotRec) + (size_t)2 * slot;
+  if (KEEP) {
+    // the compact record (vr_types.hpp) + what the plain generator's rays do not need: origin[rayDir], k, s[k]
+    rec[0] = make_float4(getc(o, p.firstDir), getc(o, p.secondDir), d.x, d.y);
+    rec[1] = make_float4(d.z, __uint_as_float(i), __uint_as_float((unsigned)(hi & 0xFFFFFFFFull)), __uint_as_float((unsigned)(hi >> 32)));
+    reinterpret_cast<float4 *>(const_cast<float *>(p.recExtra))[i] =
+        make_float4(getc(o, p.rayDir), __uint_as_float(k), __uint_as_float((unsigned)(lo & 0xFFFFFFFFull)), __uint_as_float((unsigned)(lo >> 32)));
+  } else {
+    rec[0] = make_float4(o.x, o.y, o.z, d.x);
+    rec[1] = make_float4(d.y, d.z, __uint_as_float(i), __uint_as_float(k));
+  }
+}
+
 // Writes the ray record straight into its sort bin (no separate sort pass): the bin's
 // cursor hands out one of p.binCap slots; a ray whose bin is full goes to the
 // overflow region, which is traced after the bins.  Returns the record slot.
@@ -196,17 +213,7 @@ __device__ __forceinline__ unsigned gen_store(const TraceParams &p, unsigned i, 
     else
       slot = p.numBins * p.binCap + atomicAdd(&p.binCount[p.numBins], 1u); // < ovCap by construction
   }
-  float4 *rec = reinterpret_cast<float4 *>(p.slotRec) + (size_t)2 * slot;
-  if (KEEP) {
-    // the compact record (vr_types.hpp) + what the plain generator's rays do not need: origin[rayDir], k, s[k]
-    rec[0] = make_float4(getc(o, p.firstDir), getc(o, p.secondDir), d.x, d.y);
-    rec[1] = make_float4(d.z, __uint_as_float(i), __uint_as_float((unsigned)(hi & 0xFFFFFFFFull)), __uint_as_float((unsigned)(hi >> 32)));
-    reinterpret_cast<float4 *>(const_cast<float *>(p.recExtra))[i] =
-        make_float4(getc(o, p.rayDir), __uint_as_float(k), __uint_as_float((unsigned)(lo & 0xFFFFFFFFull)), __uint_as_float((unsigned)(lo >> 32)));
-  } else {
-    rec[0] = make_float4(o.x, o.y, o.z, d.x);
-    rec[1] = make_float4(d.y, d.z, __uint_as_float(i), __uint_as_float(k));
-  }
+  gen_write<KEEP>(p, slot, i, o, d, k, lo, hi);
   return slot;
 }
 
@@ -340,6 +347,83 @@ template <int D, bool KEEP> __global__ __launch_bounds__(VR_BLOCK) void gen_host
       rng.k = k; // (k >= 156: the trace kernel rebuilds the full state from the seed and skips k outputs)
     }
     gen_store<D, KEEP>(p, i, o, d, rng.k, rng.lo, rng.hi);
+  }
+}
+
+// Surface source (gpu/raygSource.hpp:65-81, 105-118; gpu/raygTrace.hpp:267-297): global ray idx leaves source point
+// j = idx / surfRays from position + unit normal * offset, along a power-1 cosine distribution about the normal (Frisvad
+// basis) whatever the particle's source power, with the point's weight.  Two engine outputs, r1 then r2, as in
+// gen_grid_kernel.  Consecutive indices share their point: where the whole wave does, the point's seven table words
+// come through the scalar cache (one s_load each) instead of 64 identical vector loads.
+__device__ __forceinline__ void surface_sample(const TraceParams &p, unsigned idx, V3 &o, V3 &d, float &weight, u64 &lo, u64 &hi) {
+  u64 out[2];
+  mt_first_outputs<2>(tea3(idx, p.seed), out, lo, hi);
+  const float r1 = canon_f32(out[0]), r2 = canon_f32(out[1]);
+  const unsigned j = idx / p.surfRays;
+  const unsigned j0 = __builtin_amdgcn_readfirstlane(j);
+  V3 pos, n;
+  if (!ballot64(j != j0)) {
+    typedef const float __attribute__((address_space(4))) *ConstF32;
+    const ConstF32 sp = (ConstF32)p.surfPos + 3 * (size_t)j0, sn = (ConstF32)p.surfNrm + 3 * (size_t)j0;
+    pos = mk(sp[0], sp[1], sp[2]);
+    n = mk(sn[0], sn[1], sn[2]);
+    weight = ((ConstF32)p.surfWeights)[j0];
+  } else {
+    const float *sp = p.surfPos + 3 * (size_t)j, *sn = p.surfNrm + 3 * (size_t)j;
+    pos = mk(sp[0], sp[1], sp[2]);
+    n = mk(sn[0], sn[1], sn[2]);
+    weight = p.surfWeights[j];
+  }
+  vnormalize(n);
+  o = mk(pos.x + n.x * p.surfOffset, pos.y + n.y * p.surfOffset, pos.z + n.z * p.surfOffset);
+  const float cosT = sqrtf(r2), sinT = sqrtf(fmaxf(0.f, 1.f - cosT * cosT));
+  float sinP, cosP;
+  glibc_sincosf((float)(3.14159265358979323846 * 2.f * (double)r1), sinP, cosP);
+  const float s = copysignf(1.f, n.z), a = -1.f / (s + n.z), b = n.x * n.y * a;
+  const V3 t = mk(1.f + s * n.x * n.x * a, s * b, -s * n.x), b2 = mk(b, s + n.y * n.y * a, -n.y);
+  const float ct = cosP * sinT, st = sinP * sinT;
+  d = mk((n.x * cosT + t.x * ct) + b2.x * st, (n.y * cosT + t.y * ct) + b2.y * st, (n.z * cosT + t.z * ct) + b2.z * st);
+  vnormalize(d);
+}
+
+// No sort bins (bin_of's far-plane crossing supposes an origin on the source plane): the records stay in index order — a
+// wave of 64 consecutive rays shares its origin wherever a point has 64 rays or more — as one overflow region behind
+// numBins == 0 bins, which the trace kernel reads in chunks of binCap.  (Bins keyed on the origin's cell were measured
+// slower in both kernels: DESIGN.md 5.1.)
+template <int D, bool KEEP> __global__ __launch_bounds__(VR_BLOCK) void gen_surface_kernel(const TraceParams p) {
+  if (p.binCount && blockIdx.x == 0 && threadIdx.x == 0)
+    p.binCount[p.numBins] = p.batchCount;
+  for (unsigned i = blockIdx.x * VR_BLOCK + threadIdx.x; i < p.batchCount; i += gridDim.x * VR_BLOCK) {
+    const unsigned long long idx = p.idxList ? p.idxList[i] : p.batchFirst + i;
+    V3 o, d;
+    float w;
+    u64 lo, hi;
+    surface_sample(p, (unsigned)idx, o, d, w, lo, hi);
+    gen_write<KEEP>(p, p.binCount ? p.numBins * p.binCap + i : i, i, o, d, 2u, lo, hi);
+    // the start weight goes where the trace kernel reads a host ray's: hostWeights[global ray index] (4 bytes per ray
+    // of the batch; indexing the per-point table there instead would put a division into every general trace kernel,
+    // whose register allocation does not take it: 18 -> 48 spilled VGPRs in the 3-D disk kernel)
+    if (p.hostWeights)
+      const_cast<float *>(p.hostWeights)[p.batchFirst + i] = w;
+  }
+}
+
+// vr_debug_surface_source_sample: what the generator's sample gives for the ray indices p.idxList[]
+__global__ __launch_bounds__(VR_BLOCK) void debug_surface_kernel(const TraceParams p, float *org, float *dir, float *weight,
+                                                                 unsigned *draws) {
+  for (unsigned i = blockIdx.x * VR_BLOCK + threadIdx.x; i < p.batchCount; i += gridDim.x * VR_BLOCK) {
+    V3 o, d;
+    float w;
+    u64 lo, hi;
+    surface_sample(p, (unsigned)p.idxList[i], o, d, w, lo, hi);
+    org[3 * (size_t)i] = o.x;
+    org[3 * (size_t)i + 1] = o.y;
+    org[3 * (size_t)i + 2] = o.z;
+    dir[3 * (size_t)i] = d.x;
+    dir[3 * (size_t)i + 1] = d.y;
+    dir[3 * (size_t)i + 2] = d.z;
+    weight[i] = w;
+    draws[i] = 2u;
   }
 }
 
@@ -1629,8 +1713,8 @@ hipError_t launch_gen(const TraceParams &p, int D, bool keepRng, unsigned maxBlo
     return hipSuccess;
   if (grid > maxBlocks)
     grid = maxBlocks; // grid-stride; bounds the tier-2 slabs to grid waves
-  // source: SourceRandom (0: axis-aligned, 1: tilted primary direction), SourceGrid (2), host rays (3)
-  const int src = p.hostOrg ? 3 : (p.gridPoints ? 2 : (p.useBasis ? 1 : 0));
+  // source: SourceRandom (0: axis-aligned, 1: tilted primary direction), SourceGrid (2), host rays (3), surface source (4)
+  const int src = p.surfPos ? 4 : (p.hostOrg ? 3 : (p.gridPoints ? 2 : (p.useBasis ? 1 : 0)));
   const int key = src * 4 + (D == 2 ? 0 : 2) + (keepRng ? 1 : 0);
   if (src == 0 && p.reliefCoarse && p.binCount) { // the plain generator on a scene with relief: predicted-hit key, loose bins
     if (D == 2 && !keepRng)
@@ -1647,7 +1731,8 @@ hipError_t launch_gen(const TraceParams &p, int D, bool keepRng, unsigned maxBlo
   case K: hipLaunchKernelGGL((gen_kernel<DD, KEEP, false>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;               \
   case 4 + K: hipLaunchKernelGGL((gen_basis_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;            \
   case 8 + K: hipLaunchKernelGGL((gen_grid_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;             \
-  case 12 + K: hipLaunchKernelGGL((gen_host_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;
+  case 12 + K: hipLaunchKernelGGL((gen_host_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;            \
+  case 16 + K: hipLaunchKernelGGL((gen_surface_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;
   switch (key) {
     VR_GEN(0, 2, false)
     VR_GEN(1, 2, true)
@@ -1655,6 +1740,16 @@ hipError_t launch_gen(const TraceParams &p, int D, bool keepRng, unsigned maxBlo
     VR_GEN(3, 3, true)
   }
 #undef VR_GEN
+  return hipGetLastError();
+}
+
+hipError_t launch_debug_surface_sample(const TraceParams &p, unsigned maxBlocks, float *org, float *dir, float *weight,
+                                       unsigned *draws, hipStream_t s) {
+  unsigned grid = (p.batchCount + VR_BLOCK - 1) / VR_BLOCK;
+  if (grid > maxBlocks)
+    grid = maxBlocks;
+  if (grid)
+    hipLaunchKernelGGL(debug_surface_kernel, dim3(grid), dim3(VR_BLOCK), 0, s, p, org, dir, weight, draws);
   return hipGetLastError();
 }
 

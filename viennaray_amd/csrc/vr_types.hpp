@@ -175,6 +175,13 @@ struct TraceParams {
                                    // than relief_clip should walk (a plane with one bump: thin tiles everywhere, a thick scene box)
   float pqMargin;                  // flat-scene kernels: a packet query searches the 64-ary tree with its box enlarged by this
                                    // much, and the frontier it finds serves the following rounds whose boxes lie inside (0: off)
+  // ---- surface source (appended; gpu/raygSource.hpp:65-81, gpu/raygTrace.hpp:267-297): ray idx leaves source point
+  //      idx / surfRays along a cosine distribution about that point's normal (vr_trace.hip: surface_sample).  Its start
+  //      weight is the POINT's: the generator writes it to hostWeights[global ray index], a buffer of one batch then.
+  const float *surfPos, *surfNrm;  // [points] x 3: positions, normals (any non-zero length); nullptr: no surface source
+  const float *surfWeights;        // [points]
+  uint32_t surfRays;               // rays per source point
+  float surfOffset;                // origin = position + unit normal * surfOffset
 };
 
 // Relief field over the source plane (vr_setup.hip: relief_field_kernel): per fine tile the [lo, hi] range — along the

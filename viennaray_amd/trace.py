@@ -388,12 +388,28 @@ class Trace:
         if sourceArea is not None or hasattr(self._L, "vr_set_source_area"):
             self._check(self._L.vr_set_source_area(self._h, float(sourceArea) if sourceArea is not None else 0.0))
 
+    def setSurfaceSource(self, positions, normals, weights, sourceArea, sourceOffset):
+        """gpu/raygTrace.hpp:267-286: the rays start on the given points (numRaysFixed if set, else numRaysPerPoint,
+        rays per point), leave along a cosine distribution about each point's normal from position + unit normal *
+        sourceOffset and carry the point's weight; sampled on the device.  normalizeFlux(SOURCE) uses sourceArea."""
+        q = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        m = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if m.shape != q.shape or w.size != q.shape[0]:
+            raise VrError("setSurfaceSource: one normal and one weight per position")
+        self._check(self._L.vr_set_surface_source(self._h, _fptr(q), _fptr(m), _fptr(w), q.shape[0],
+                                                  float(sourceArea), float(sourceOffset)))
+
+    def clearSurfaceSource(self):
+        """gpu/raygTrace.hpp:288-297"""
+        self._check(self._L.vr_set_surface_source(self._h, None, None, None, 0, 0.0, 0.0))
+
     def reserveRays(self, n):
         """Size the HBM ray stream for applies of up to n rays (apply() per time step with a growing count)."""
         self._check(self._L.vr_reserve_rays(self._h, int(n)))
 
     def resetSource(self):
-        """rayTrace.hpp:58-61"""
+        """rayTrace.hpp:58-61 (also drops a surface source)"""
         self._check(self._L.vr_set_source_grid(self._h, None, 0))
         self._check(self._L.vr_set_source_area(self._h, 0.0))
 
@@ -584,6 +600,19 @@ class Trace:
                                                          int(seed), _fptr(o), _fptr(d),
                                                          k.ctypes.data_as(C.POINTER(C.c_uint32))))
         return o, d, k
+
+    def debugSurfaceSourceSample(self, idx, seed):
+        """the surface source's sample of global ray indices idx for kernel seed `seed`, by the generator's own device
+        function: origin, direction, start weight, engine outputs consumed"""
+        i = np.ascontiguousarray(idx, dtype=np.uint64)
+        o = np.empty((i.size, 3), dtype=np.float32)
+        d = np.empty((i.size, 3), dtype=np.float32)
+        w = np.empty(i.size, dtype=np.float32)
+        k = np.empty(i.size, dtype=np.uint32)
+        self._check(self._L.vr_debug_surface_source_sample(self._h, i.ctypes.data_as(C.POINTER(C.c_uint64)), i.size,
+                                                           int(seed), _fptr(o), _fptr(d), _fptr(w),
+                                                           k.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return o, d, w, k
 
     def debugSourceSample(self, idx, seed):
         i = np.ascontiguousarray(idx, dtype=np.uint64)
