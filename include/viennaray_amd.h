@@ -268,6 +268,32 @@ int vr_get_neighbor_counts(vr_context *ctx, uint32_t *out, uint32_t n);
  * replaces the device contents (e.g. after an all-reduce done elsewhere).    */
 #define VR_FLUX_FRAC_BITS 40
 int vr_flux_accumulators(vr_context *ctx, void **devPtr, uint32_t *n);
+/* ---- the data log (DataLog / AbstractParticle::logData, rayTraceKernel.hpp:131-133, 345) ----------------------
+ * A stateful run-time model (vr_register_particle_model_ex) with `static constexpr int kLogRows = R` (1 .. 16) and
+ *     template <class Log> __device__ static void log_data(const ModelCtx &, const RayState &s, Log &&log);
+ * logs once per ray, right after init and before the source sample: log(row, bin, value) is
+ * dataLog.data[row][bin] += value.  The hook draws nothing from the engine and cannot change the state.  The sums are
+ * int64 fixed point (value * 2^VR_LOG_FRAC_BITS): exact for counts, 6e-8 resolution, independent of grid, batch
+ * split and rank count.  A call with row / bin outside the shape, or a value that is negative, not finite or above
+ * 2^15, is dropped and counted.  An entry holds 2^39 (5.5e11) units per apply(), divided by the rank count rounded up
+ * to a power of two; beyond that the apply FAILS (VR_E_STATE, TraceInfo.error = 1, "data log overflow").
+ *
+ * vr_set_data_log_shape: the entries per row (at most 16 rows, 65536 entries in all); rows == 0 clears the shape and
+ * nothing is logged.  With a shape set, vr_apply_prepare refuses an apply none of whose particle models has a hook, and
+ * a shape with fewer rows than a hook's kLogRows.  Every apply starts from a zeroed log; in a particle list every model
+ * with a hook adds to the one log.  vr_apply_sharded all-reduces the log with the flux.
+ * vr_get_data_log: the last apply's sums as float(double(sum) * 2^-VR_LOG_FRAC_BITS), rows concatenated (n = all
+ * entries); vr_get_data_log_i64: the sums themselves; vr_get_data_log_dropped: the dropped calls.
+ * vr_data_log_accumulators: DEVICE memory of n int64 sums for callers that own the collective, valid from
+ * vr_apply_prepare until the shape changes; words [n] and [n + 1] behind them are the dropped counter and the overflow
+ * flag, so an all-reduce of n + 2 words carries both.                                                          */
+#define VR_LOG_FRAC_BITS 24
+int vr_set_data_log_shape(vr_context *ctx, const uint32_t *rowSizes, uint32_t rows);
+int vr_get_model_log_rows(const vr_context *ctx, int32_t kind, int32_t *rows); /* kLogRows of a particle kind (0: no hook) */
+int vr_get_data_log(vr_context *ctx, float *out, uint32_t n);
+int vr_get_data_log_i64(vr_context *ctx, int64_t *out, uint32_t n);
+int vr_get_data_log_dropped(vr_context *ctx, uint64_t *out);
+int vr_data_log_accumulators(vr_context *ctx, void **devPtr, uint32_t *n);
 /* Let the caller own the accumulator buffer instead (e.g. a torch int64 tensor
  * handed to torch.distributed/RCCL): DEVICE pointer to n int64; NULL restores
  * the library-owned buffer.  Must stay valid until replaced.  The binding survives

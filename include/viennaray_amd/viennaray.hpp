@@ -389,8 +389,10 @@ public:
 };
 
 // ---- particles --------------------------------------------------------------------
-// rayUtil.hpp:49-63.  The built-in particles log nothing; the type is here so programs that
-// pass a DataLog around keep compiling.
+// rayUtil.hpp:49-63.  The built-in particles log nothing.  A stateful run-time model with a log_data hook
+// (viennaray_amd/csrc/vr_particles.hpp) fills the log on the device: Trace::apply() takes the shape from `data` as the
+// caller sized it and ADDS the apply's sums to it (the reference merges its per-thread logs into the Trace's and never
+// clears them, rayTraceKernel.hpp:75-82, 345).
 template <class NumericType> struct DataLog {
   std::vector<std::vector<NumericType>> data;
   // element-wise sum of two logs (the shorter extent of each row counts)
@@ -922,6 +924,7 @@ public:
     if (pSource_ && !sourceOnDevice_ && !uploadHostSource())
       return;
     uploadGlobalData();
+    const bool logging = setDataLogShape();
     const int rc = world_ > 1 ? vr_apply_sharded(ctx_, rank_, world_, reduce_, reduceUser_) : vr_apply(ctx_);
     vr_trace_info i{};
     vr_get_trace_info(ctx_, &i);
@@ -949,6 +952,8 @@ public:
       std::cerr << vr_last_error(ctx_) << "\n";
       return;
     }
+    if (logging)
+      mergeDataLog();
     // rayTraceDisk.hpp:40-47: one vector per data label of the particle (of every particle of a list, in order)
     auto labels = pParticle_->getLocalDataLabels();
     for (const auto &extra : moreParticles_) {
@@ -980,6 +985,7 @@ public:
     moreParticles_.clear();
     vr_particle pod{};
     particleOnDevice_ = pParticle_->deviceModel(pod);
+    particleKinds_.assign(1, pod.kind);
     if (ctx_ && particleOnDevice_)
       check(vr_set_particle(ctx_, &pod));
   }
@@ -1017,6 +1023,9 @@ public:
       else
         moreParticles_.push_back(std::move(copy));
     }
+    particleKinds_.clear();
+    for (const vr_particle &pod : pods)
+      particleKinds_.push_back(pod.kind);
     if (ctx_ && particleOnDevice_)
       check(vr_set_particles(ctx_, pods.data(), (uint32_t)pods.size()));
   }
@@ -1153,6 +1162,34 @@ public:
   [[nodiscard]] vr_context *getContext() { return ctx_; }
 
 protected:
+  // The data log of this apply: the shape of dataLog_.data as the caller sized it, if a particle's device model has a
+  // log_data hook; otherwise (an empty log, or particles that log nothing, like the reference's built-in ones) no shape:
+  // nothing is logged and nothing is paid.
+  bool setDataLogShape() {
+    bool hook = false;
+    for (int32_t kind : particleKinds_) {
+      int32_t rows = 0;
+      hook = hook || (vr_get_model_log_rows(ctx_, kind, &rows) == VR_OK && rows > 0);
+    }
+    std::vector<uint32_t> sizes;
+    if (hook)
+      for (const auto &row : dataLog_.data)
+        sizes.push_back((uint32_t)row.size());
+    check(vr_set_data_log_shape(ctx_, sizes.data(), (uint32_t)sizes.size()));
+    return !sizes.empty();
+  }
+  void mergeDataLog() {
+    std::size_t n = 0;
+    for (const auto &row : dataLog_.data)
+      n += row.size();
+    std::vector<float> flat(n);
+    if (vr_get_data_log(ctx_, flat.data(), (uint32_t)n) != VR_OK)
+      return;
+    std::size_t o = 0;
+    for (auto &row : dataLog_.data)
+      for (auto &v : row)
+        v += (NumericType)flat[o++];
+  }
   void check(int rc) {
     if (rc != VR_OK) {
       setterError_ = true;
@@ -1263,6 +1300,7 @@ protected:
   TracingData<NumericType> localData_;
   TracingData<NumericType> *pGlobalData_ = nullptr;
   DataLog<NumericType> dataLog_;
+  std::vector<int32_t> particleKinds_; // the device kinds of pParticle_ and moreParticles_
   std::shared_ptr<Source<NumericType>> pSource_;
   TraceInfo RTInfo_;
   bool particleOnDevice_ = false, sourceOnDevice_ = false, setterError_ = false;

@@ -56,7 +56,7 @@ elif case.startswith("plane") and case[5:].isdigit():   # plane<n>: an n x n pla
 else:
     gd, p, n = trench3d()
     t = vr.TraceDisk(3); t.setGeometry(p, n, gd); t.setBoundaryConditions([vr.BoundaryCondition.PERIODIC_BOUNDARY] * 3)
-# VR_CASE_PARTICLE=coned|cosine2|state1|nostate: the same workload through the extended kernel (device particle registry)
+# VR_CASE_PARTICLE=coned|cosine2|state1|nostate|ion|ionlog: the same workload through the extended kernel (device particle registry)
 _pk = os.environ.get("VR_CASE_PARTICLE", "")
 if _pk == "coned":
     particle = vr.ConedCosineParticle(sticking, 1.0, 0.8, "flux")
@@ -87,6 +87,37 @@ elif _pk in ("state1", "nostate"):
   }
 };""", 1
     particle = vr.UserModelParticle(t.registerParticleModel(src, numData=1, needsFull=True, name=_pk, numState=ns), sticking, ["flux"])
+elif _pk in ("ion", "ionlog"):
+    # the cost of the data log (DESIGN.md 8c): an ion whose init samples an energy E in [0, 2) — `ionlog` histograms it with a
+    # log_data hook into a log of 2 rows x 64 bins (counts, energies), `ion` is the same model without the hook.
+    # VR_LOG_PLAIN_ATOMICS=1 takes the log's direct global atomics instead of the per-block LDS copy.
+    hook = """  static constexpr int kLogRows = 2;
+  template <class Log> __device__ static void log_data(const ModelCtx &, const RayState &s, Log &&log) {
+    log(0, (int)(s.v[0] * 32.f), 1.f);
+    log(1, (int)(s.v[0] * 32.f), s.v[0]);
+  }
+""" if _pk == "ionlog" else ""
+    src = """struct VrUserModel : ModelDiffuse {
+  static constexpr bool kNeedsFull = true;
+  static constexpr int kStateWords = 1;
+""" + hook + """  __device__ static void init(const ModelCtx &, RayState &s, Rng &rng, unsigned &t2) { s.v[0] = 2.f * canon_f32(rng_next(rng, t2)); }
+  template <int D>
+  __device__ static Reflection surface_reflection(const ModelCtx &, RayState &, float w, const V3 &rayDir, const V3 &n,
+                                                  unsigned, int, float base, Rng &rng, unsigned &t2) {
+    Reflection r{base, rayDir};
+    if (w - w * base > 0.f)
+      r.dir = reflection_diffuse<D>(n, rng, t2);
+    return r;
+  }
+  template <class Credit>
+  __device__ static void collide(const ModelCtx &, const RayState &, float w, const V3 &, const V3 &, unsigned, int,
+                                 Credit &&credit) {
+    credit(0, w);
+  }
+};"""
+    particle = vr.UserModelParticle(t.registerParticleModel(src, numData=1, name=_pk, numState=1), sticking, ["flux"])
+    if _pk == "ionlog":
+        t.setDataLogShape([64, 64])
 t.setParticleType(particle if particle is not None else vr.DiffuseParticle(sticking, "flux"))
 if fixed:
     t.setNumberOfRaysFixed(fixed)
@@ -102,5 +133,7 @@ for i in range(rep):
     print(json.dumps(dict(vr_case=case, sticking=sticking, rays=int(info.numRays), segments=int(info.totalRaysTraced),
                           device_ms=info.timeTrace * 1e3, trace_kernel_ms=info.timeTraceKernel * 1e3,
                           gen_kernel_ms=info.timeGenKernel * 1e3, mode=t.traceMode())))
+    if _pk == "ionlog":
+        print(f"data log: row 0 sums to {t.getDataLog()[0].sum(dtype=np.float64):.0f}, dropped {t.getDataLogDropped()}")
     print(f"{case} sticking {sticking}: rays {info.numRays} segments {info.totalRaysTraced} device {info.timeTrace*1e3:.2f} ms "
           f"trace_kernel {info.timeTraceKernel*1e3:.2f} ms -> {info.numRays/info.timeTrace/1e6:.0f} Mrays/s")

@@ -103,6 +103,12 @@ SIGNATURES = {
     "vr_get_neighbor_counts": (C.c_int, [_vp, _u32p, C.c_uint32]),
     "vr_flux_accumulators": (C.c_int, [_vp, C.POINTER(_vp), _u32p]),
     "vr_bind_flux_accumulators": (C.c_int, [_vp, _vp, C.c_uint32]),
+    "vr_set_data_log_shape": (C.c_int, [_vp, _u32p, C.c_uint32]),
+    "vr_get_model_log_rows": (C.c_int, [_vp, C.c_int32, _i32p]),
+    "vr_get_data_log": (C.c_int, [_vp, _fp, C.c_uint32]),
+    "vr_get_data_log_i64": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_uint32]),
+    "vr_get_data_log_dropped": (C.c_int, [_vp, _u64p]),
+    "vr_data_log_accumulators": (C.c_int, [_vp, C.POINTER(_vp), _u32p]),
     "vr_add_trace_info": (C.c_int, [_vp, C.POINTER(TraceInfoPOD)]),
     "vr_stream": (_vp, [_vp]),
     "vr_debug_intersect": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, _i32p, _u32p, _fp]),

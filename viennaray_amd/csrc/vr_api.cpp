@@ -83,6 +83,8 @@ template <class T> struct DevBuf {
 };
 } // namespace
 
+static_assert(VR_LOG_SCALE == (double)(1ull << VR_LOG_FRAC_BITS), "the kernels' log scale is 2^VR_LOG_FRAC_BITS");
+
 // Every tuning and experiment switch of the library, read from the environment in ONE place (read_knobs): an apply
 // reads them once, at vr_apply_prepare, into vr_context::knobs.  Unless its line says RESULTS, a switch only moves work
 // around: the flux and the TraceInfo counters stay bit-exact (tests/test_gpu_parity.py).  (VR_CSRC_DIR / VR_HIPCC /
@@ -132,6 +134,7 @@ struct Knobs {
   bool printLaunches = false;          // VR_PRINT_LAUNCHES (set): trace-launch times and spilled rays on stderr
   bool hostSmooth = false;             // VR_HOST_SMOOTH (set): vr_smooth_flux on the host
   bool debugWalk = true;               // VR_DEBUG_WALK (0: the escape-link walk): vr_debug_intersect's walk
+  bool logPlainAtomics = false;        // VR_LOG_PLAIN_ATOMICS (set): the data log without its per-block LDS copy (A/B of DESIGN.md 8c)
 #ifdef VR_DIAG
   bool skipTight = false;              // VR_SKIP_TIGHT (set): a relief scene's loose launch alone; INCOMPLETE results
   bool skipLoose = false;              // VR_SKIP_LOOSE (set): ... its tight launch alone; INCOMPLETE results
@@ -212,6 +215,7 @@ static Knobs read_knobs() {
   k.hostSmooth = std::getenv("VR_HOST_SMOOTH") != nullptr;
   if (const char *e = std::getenv("VR_DEBUG_WALK"))
     k.debugWalk = std::atoi(e) != 0;
+  k.logPlainAtomics = std::getenv("VR_LOG_PLAIN_ATOMICS") != nullptr;
 #ifdef VR_DIAG
   k.skipTight = std::getenv("VR_SKIP_TIGHT") != nullptr;
   k.skipLoose = std::getenv("VR_SKIP_LOOSE") != nullptr;
@@ -236,6 +240,7 @@ struct UserModel {
   int numData = 1;
   bool needsFull = false;
   int numState = 0;                     // kStateWords of a stateful model (0: stateless)
+  int logRows = 0;                      // kLogRows: rows of the data log its log_data hook writes (0: no hook)
   std::map<int, hipFunction_t> kernels; // key: D * 100 + geo * 10 + mode
   hipFunction_t gen[2] = {nullptr, nullptr}; // a stateful model's generator (gen_state_kernel), 2-D / 3-D
 };
@@ -291,6 +296,15 @@ struct vr_context {
   int userModel = -1;             // index into userModels when the active particle is a run-time model
   DevBuf<float> dRayState;            // a stateful model's per-ray state of one batch (the frame's VR_F_STATE_*), float4 per ray
   DevBuf<int32_t> dPrimMaterial;      // material id per original primitive for a stateful model (VR_F_MAT_*)
+  // the data log (vr_set_data_log_shape): int64 sums of the log_data hooks, rows concatenated, the control words behind
+  // them (VR_LOG_*, vr_device.hpp); zeroed at every launch, summed over the batches and particles of an apply on the device
+  std::vector<uint32_t> logRowSizes;
+  uint32_t logTotal = 0;              // entries of all rows
+  bool logActive = false;             // the prepared apply fills the log (a shape is set)
+  DevBuf<unsigned long long> dDataLog;
+  std::vector<unsigned long long> logCtlHost; // staging of the control words' upload
+  std::vector<unsigned long long> logHost;    // the last apply's sums + [dropped] (vr_get_data_log*)
+  bool haveLog = false;
   std::vector<UserModel> userModels;
   bool particleDirty = true;      // the sticking map needs recomputing
   std::vector<ParticleSpec> specs;      // vr_set_particles: > 1 entries = a multi-particle apply
@@ -856,6 +870,17 @@ int vr_register_particle_model_ex(vr_context *c, const char *name, const char *s
         return fail(c, VR_E_STATE, (std::string("vr_register_particle_model: kernel missing from the code object: ") + sym).c_str());
       }
     }
+  { // the rows its log_data hook writes (kLogRows), from the module itself
+    hipDeviceptr_t sym = nullptr;
+    size_t bytes = 0;
+    int32_t rows = 0;
+    if (hipModuleGetGlobal(&sym, &bytes, um.module, "vr_user_log_rows") != hipSuccess || bytes != sizeof(rows) ||
+        hipMemcpy(&rows, (const void *)sym, sizeof(rows), hipMemcpyDeviceToHost) != hipSuccess) {
+      (void)hipModuleUnload(um.module);
+      return fail(c, VR_E_STATE, "vr_register_particle_model: symbol missing from the code object: vr_user_log_rows");
+    }
+    um.logRows = rows;
+  }
   const int P = full ? (int)P_EXT_FULL : (int)P_EXT;
   for (int D = 2; D <= 3; ++D)
     for (int geo = 0; geo <= 1; ++geo)
@@ -1407,6 +1432,7 @@ struct PrepareState {
   bool smallScene = false;  // the whole scene goes into LDS (MODE 4)
   bool heightField = false; // the height field over the source plane is built (the frame's VR_F_HF_*)
   const int32_t *dMaterial = nullptr; // a stateful model's material ids (the frame's VR_F_MAT_*)
+  bool logs = false;        // the model has a log_data hook and the apply a data-log shape (the frame's VR_F_LOG_*)
 };
 
 // the largest coordinate of the BVH's root box (at least 1e-3): the scale of the float rounding the pads cover
@@ -1642,6 +1668,7 @@ static int choose_particle_kernel(vr_context *c, ParticleLaunch &L, PrepareState
                                    "source or a surface source");
   }
   S.stateful = c->userModel >= 0 && c->userModels[c->userModel].numState > 0;
+  S.logs = S.stateful && c->logActive && c->userModels[c->userModel].logRows > 0;
   L.kernelParticle = extended ? (extFull ? (int)P_EXT_FULL : (int)P_EXT) : c->particleKind;
   // a scene of a few hundred primitives goes into LDS as a whole (MODE 4: the general kernel — also for
   // absorbing particles — of whatever particle): pair nodes, records, neighbourhood, accumulators (one plane
@@ -2179,6 +2206,10 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
     addr(VR_F_STATE_LO, c->dRayState.p);
     addr(VR_F_MAT_LO, S.dMaterial);
   }
+  if (S.logs) {
+    addr(VR_F_LOG_LO, c->dDataLog.p);
+    addr(VR_F_LOGCTL_LO, c->dDataLog.p + c->logTotal);
+  }
   VR_HIP(c, hipMemcpyAsync(c->dWalls.p + (size_t)L.slot * VR_WALL_TABLE, f, VR_WALL_TABLE * 4, hipMemcpyHostToDevice, c->stream));
   return VR_OK;
 }
@@ -2235,6 +2266,51 @@ static int prepare_one(vr_context *c, ParticleLaunch &L) {
   c->prepared = true;
   c->launched = false;
   c->haveResult = false;
+  return VR_OK;
+}
+
+// The data log of the apply (vr_set_data_log_shape): every stateful model of the particle list with a log_data hook adds to
+// the one log (the reference keeps one dataLog_ per Trace).  Checks the shape against the hooks, sizes the buffer and
+// uploads the control words behind the sums; the sums themselves are zeroed when the apply launches.
+static int prepare_data_log(vr_context *c) {
+  c->logActive = false;
+  if (c->logRowSizes.empty())
+    return VR_OK;
+  int hooks = 0, rowsNeeded = 0;
+  auto look = [&](int userModel) {
+    if (userModel >= 0 && userModel < (int)c->userModels.size() && c->userModels[userModel].logRows > 0) {
+      ++hooks;
+      rowsNeeded = std::max(rowsNeeded, c->userModels[userModel].logRows);
+    }
+  };
+  if (c->specs.size() > 1)
+    for (const ParticleSpec &sp : c->specs)
+      look(sp.userModel);
+  else
+    look(c->userModel);
+  if (!hooks)
+    return fail(c, VR_E_INVALID, "a data-log shape is set (vr_set_data_log_shape) but no particle model of this apply has a "
+                                 "log_data hook (kLogRows == 0): nothing would fill the log; clear the shape or use a "
+                                 "stateful model that logs");
+  if ((int)c->logRowSizes.size() < rowsNeeded)
+    return fail(c, VR_E_INVALID, ("the data-log shape has " + std::to_string(c->logRowSizes.size()) + " rows, the particle "
+                                  "model's log_data hook writes " + std::to_string(rowsNeeded) + " (kLogRows): too few rows").c_str());
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_HIP(c, c->dDataLog.ensure((size_t)c->logTotal + VR_LOG_CTL_WORDS));
+  std::vector<unsigned long long> &h = c->logCtlHost;
+  h.assign(VR_LOG_CTL_WORDS, 0ull);
+  h[VR_LOG_ROWS] = c->logRowSizes.size();
+  while ((1u << h[VR_LOG_HEADROOM]) < c->worldSize) // the sums of `worldSize` ranks must still fit a signed int64
+    ++h[VR_LOG_HEADROOM];
+  h[VR_LOG_FLAGS] = c->knobs.logPlainAtomics ? 1ull : 0ull;
+  unsigned long long off = 0;
+  for (size_t r = 0; r < c->logRowSizes.size(); ++r) {
+    h[VR_LOG_OFFSETS + r] = off;
+    off += c->logRowSizes[r];
+  }
+  h[VR_LOG_OFFSETS + c->logRowSizes.size()] = off;
+  VR_HIP(c, hipMemcpyAsync(c->dDataLog.p + c->logTotal, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+  c->logActive = true;
   return VR_OK;
 }
 
@@ -2403,6 +2479,8 @@ int vr_apply_launch(vr_context *c) {
   const uint32_t N = c->geo.numPrims;
   VR_HIP(c, hipMemsetAsync(c->dFluxAcc.p, 0, (size_t)c->accStride * c->accReplicas * c->totalData * 8, c->stream));
   VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 80 * c->launches.size() * 8, c->stream));
+  if (c->logActive) // (the sums, the dropped counter and the overflow flag)
+    VR_HIP(c, hipMemsetAsync(c->dDataLog.p, 0, ((size_t)c->logTotal + 2) * 8, c->stream));
   VR_HIP(c, hipEventRecord(c->ev0, c->stream));
   // groups of particles that can share a generator pass: the same source distribution (cosine power: the rays of
   // index idx are then identical, gpu/raygTrace.hpp launches every particle with the apply's one seed) and the
@@ -2497,6 +2575,22 @@ int vr_apply_finish(vr_context *c) {
     return fail(c, VR_E_STATE, "flux accumulator overflow: a primitive collected more than 2^23 (8.39e6) weight units per rank-power-of-two "
                                "in one apply() (int64 fixed point, 2^-40 per unit) - result discarded; trace fewer rays per apply() "
                                "and sum the normalised results");
+  }
+  c->haveLog = false;
+  if (c->logActive) {
+    c->logHost.resize((size_t)c->logTotal + 2);
+    VR_HIP(c, hipMemcpy(c->logHost.data(), c->dDataLog.p, c->logHost.size() * 8, hipMemcpyDeviceToHost));
+    // a sum of the data log left 2^63 / ranks (rounded up to a power of two): raised by the add that saw it (gen_state_kernel)
+    if (c->logHost[(size_t)c->logTotal + VR_LOG_OVERFLOW]) {
+      c->launched = false;
+      c->prepared = false;
+      c->info.error = 1;
+      ++c->runNumber;
+      return fail(c, VR_E_STATE, "data log overflow: an entry collected more than 2^39 (5.5e11) units per rank-power-of-two in one "
+                                 "apply() (int64 fixed point, 2^-24 per unit) - result discarded; log fewer rays per apply()");
+    }
+    c->logHost.resize((size_t)c->logTotal + 1); // (sums + [dropped])
+    c->haveLog = true;
   }
   for (size_t q = 0; q < nPart; ++q) {
     // the walk's stack ran out (a tree deeper than SD + VR_STACK_GLOBAL levels of deferred children): the
@@ -2598,6 +2692,11 @@ int vr_apply_prepare(vr_context *c) {
     c->launches.clear();
     c->launches.resize(nPart);
   }
+  {
+    const int r = prepare_data_log(c);
+    if (r != VR_OK)
+      return r;
+  }
   uint32_t base = 0;
   for (size_t q = 0; q < nPart; ++q) {
     if (multi)
@@ -2679,6 +2778,8 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
     if (r == VR_OK) {
       VR_HIP(c, hipMemsetAsync(c->fluxOut(), 0, (size_t)N * c->totalData * 8, c->stream));
       VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 80 * 8 * std::max<size_t>(1, c->specs.size()), c->stream));
+      if (c->logActive)
+        VR_HIP(c, hipMemsetAsync(c->dDataLog.p, 0, ((size_t)c->logTotal + 2) * 8, c->stream));
       VR_HIP(c, hipEventRecord(c->ev0, c->stream));
       VR_HIP(c, hipEventRecord(c->ev1, c->stream));
       c->numGenLaunches = c->numTraceLaunches = 0;
@@ -2704,9 +2805,14 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
       (void)hipMemsetAsync(c->fluxOut(), 0, (size_t)N * c->totalData * 8, c->stream);
       (void)hipMemsetAsync(c->dCounters.p, 0, 80 * 8 * std::max<size_t>(1, c->specs.size()), c->stream);
       (void)hipMemcpyAsync(c->dCounters.p + 60, &one, 8, hipMemcpyHostToDevice, c->stream);
+      if (c->logActive)
+        (void)hipMemsetAsync(c->dDataLog.p, 0, ((size_t)c->logTotal + 2) * 8, c->stream);
     }
+    // (the data log's sums travel with their dropped counter and overflow flag: the two words behind them; a shape that
+    //  prepare refused is refused on every rank alike, so the ranks agree on logActive)
     if (reduce(user, c->fluxOut(), (size_t)N * c->totalData, (void *)c->stream) != 0 ||
-        reduce(user, c->dCounters.p, 80 * std::max<size_t>(1, c->specs.size()), (void *)c->stream) != 0)
+        reduce(user, c->dCounters.p, 80 * std::max<size_t>(1, c->specs.size()), (void *)c->stream) != 0 ||
+        (c->logActive && reduce(user, c->dDataLog.p, (size_t)c->logTotal + 2, (void *)c->stream) != 0))
       return fail(c, VR_E_HIP, "vr_apply_sharded: the all-reduce callback failed");
     if (r != VR_OK) {
       (void)hipStreamSynchronize(c->stream);
@@ -2820,6 +2926,77 @@ int vr_flux_accumulators(vr_context *c, void **devPtr, uint32_t *n) {
   *devPtr = c->fluxOut();
   if (n)
     *n = c->geo.numPrims * c->totalData;
+  return VR_OK;
+}
+
+// ---- the data log (DataLog / logData of the reference: rayTraceKernel.hpp:131-133, 345) ---------------------------
+int vr_set_data_log_shape(vr_context *c, const uint32_t *rowSizes, uint32_t rows) {
+  if (!c || (rows && !rowSizes))
+    return fail(c, VR_E_INVALID, "vr_set_data_log_shape: bad argument");
+  if (rows > (uint32_t)VR_LOG_MAX_ROWS)
+    return fail(c, VR_E_INVALID, "vr_set_data_log_shape: at most 16 rows");
+  uint64_t total = 0;
+  for (uint32_t r = 0; r < rows; ++r)
+    total += rowSizes[r];
+  if (total > VR_LOG_MAX_ENTRIES)
+    return fail(c, VR_E_INVALID, "vr_set_data_log_shape: at most 65536 entries in all rows together");
+  c->logRowSizes.assign(rowSizes, rowSizes + rows);
+  c->logTotal = (uint32_t)total;
+  c->logActive = false;
+  c->haveLog = false;
+  c->prepared = false; // (a prepared launch carries the old shape in its frame)
+  return VR_OK;
+}
+
+int vr_get_model_log_rows(const vr_context *c, int32_t kind, int32_t *rows) {
+  if (!c || !rows)
+    return VR_E_INVALID;
+  const int32_t u = kind - VR_PARTICLE_USER_BASE;
+  *rows = (u >= 0 && u < (int32_t)c->userModels.size()) ? c->userModels[u].logRows : 0; // (the built-in models log nothing)
+  return VR_OK;
+}
+
+int vr_get_data_log(vr_context *c, float *out, uint32_t n) {
+  if (!c || (n && !out))
+    return VR_E_INVALID;
+  if (!c->haveLog)
+    return fail(c, VR_E_STATE, "vr_get_data_log: no result (set a shape with vr_set_data_log_shape, then vr_apply)");
+  if (n != c->logHost.size() - 1)
+    return fail(c, VR_E_INVALID, "vr_get_data_log: n differs from the entries of the shape");
+  const double scale = std::ldexp(1.0, -VR_LOG_FRAC_BITS);
+  for (uint32_t i = 0; i < n; ++i)
+    out[i] = (float)((double)(long long)c->logHost[i] * scale);
+  return VR_OK;
+}
+
+int vr_get_data_log_i64(vr_context *c, int64_t *out, uint32_t n) {
+  if (!c || (n && !out))
+    return VR_E_INVALID;
+  if (!c->haveLog)
+    return fail(c, VR_E_STATE, "vr_get_data_log_i64: no result (set a shape with vr_set_data_log_shape, then vr_apply)");
+  if (n != c->logHost.size() - 1)
+    return fail(c, VR_E_INVALID, "vr_get_data_log_i64: n differs from the entries of the shape");
+  for (uint32_t i = 0; i < n; ++i)
+    out[i] = (int64_t)c->logHost[i];
+  return VR_OK;
+}
+
+int vr_get_data_log_dropped(vr_context *c, uint64_t *out) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  if (!c->haveLog)
+    return fail(c, VR_E_STATE, "vr_get_data_log_dropped: no result (set a shape with vr_set_data_log_shape, then vr_apply)");
+  *out = c->logHost.back();
+  return VR_OK;
+}
+
+int vr_data_log_accumulators(vr_context *c, void **devPtr, uint32_t *n) {
+  if (!c || !devPtr || !n)
+    return VR_E_INVALID;
+  if (!c->logActive || !c->dDataLog.p)
+    return fail(c, VR_E_STATE, "vr_data_log_accumulators: no data log (set a shape with vr_set_data_log_shape, then prepare or apply)");
+  *devPtr = c->dDataLog.p;
+  *n = c->logTotal;
   return VR_OK;
 }
 

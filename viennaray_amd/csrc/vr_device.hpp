@@ -387,7 +387,25 @@ enum { VR_F_SRC_PLANE = 96, VR_F_RAYDIR = 97, VR_F_FIRSTDIR = 98, VR_F_SECONDDIR
        // a stateful particle model (vr_particles.hpp; read only by the kernels of a module compiled around one): the
        // per-ray state of the batch (float4 per ray, indexed like TraceParams::recExtra) and the material id per ORIGINAL
        // primitive (0: none set).  (Here, not in TraceParams: the library's own kernels stay exactly as they are.)
-       VR_F_STATE_LO = 136, VR_F_STATE_HI = 137, VR_F_MAT_LO = 138, VR_F_MAT_HI = 139 };
+       VR_F_STATE_LO = 136, VR_F_STATE_HI = 137, VR_F_MAT_LO = 138, VR_F_MAT_HI = 139,
+       // the data log of a stateful model with a log_data hook (read only by gen_state_kernel of such a module; 0: no
+       // shape set, nothing is logged): the int64 sums, rows concatenated, and the log's control words (VR_LOG_*)
+       VR_F_LOG_LO = 140, VR_F_LOG_HI = 141, VR_F_LOGCTL_LO = 142, VR_F_LOGCTL_HI = 143 };
+// The data log (DataLog of the reference, rayTraceKernel.hpp:131-133, 345): int64 fixed-point sums, value * 2^24
+// (VR_LOG_FRAC_BITS, include/viennaray_amd.h).  The control words lie directly BEHIND the sums in the same buffer, so that
+// one all-reduce of entries + 2 words carries the dropped counter and the overflow flag along: [DROPPED] log calls refused
+// (row / bin outside the shape, value negative, not finite or above 2^15), [OVERFLOW] raised when a sum left
+// 2^(63 - [HEADROOM]), [ROWS] rows of the shape, [FLAGS] bit 0: no LDS copy (plain global atomics), [OFFSETS ...] first
+// entry of row r, rows + 1 words (the last: all entries).
+enum { VR_LOG_DROPPED = 0, VR_LOG_OVERFLOW = 1, VR_LOG_ROWS = 2, VR_LOG_HEADROOM = 3, VR_LOG_FLAGS = 4, VR_LOG_OFFSETS = 5 };
+constexpr int VR_LOG_MAX_ROWS = 16;
+constexpr unsigned VR_LOG_MAX_ENTRIES = 65536u;
+constexpr int VR_LOG_CTL_WORDS = VR_LOG_OFFSETS + VR_LOG_MAX_ROWS + 1;
+constexpr double VR_LOG_SCALE = 16777216.0; // 2^VR_LOG_FRAC_BITS
+constexpr float VR_LOG_MAX_VALUE = 32768.f; // a logged value lies in [0, 2^15]: its fixed-point form is at most 2^39
+// gen_state_kernel's private copy of the log in LDS.  The generator uses no LDS of its own and its grid is bounded by
+// 8 blocks per CU (launch_gen): 16 KiB per block keep all 8 resident in the CU's 160 KiB.  Larger logs go to HBM directly.
+constexpr unsigned VR_LOG_LDS_ENTRIES = 2048u;
 // a device address kept as two words of the frame (lo, hi)
 __device__ __forceinline__ unsigned long long frame_addr(const float *f, int lo) {
   return ((unsigned long long)__float_as_uint(f[lo + 1]) << 32) | __float_as_uint(f[lo]);

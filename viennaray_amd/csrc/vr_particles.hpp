@@ -30,6 +30,12 @@
 //   surface_reflection : sticking AND the new direction in one call (rayTraceKernel.hpp:310), may update the state and
 //                        draw from the engine; called after the hit's collide credits, also when it returns sticking >= 1
 //   collide            : as above, with the state (read only) and the material id of the primitive; no engine draws
+//   log_data           : logData (rayTraceKernel.hpp:131-133), opted into with kLogRows = 1 .. 16: once per ray, right after
+//                        init and before the source sample; log(row, bin, value) is dataLog.data[row][bin] += value on the
+//                        apply's data log (vr_set_data_log_shape).  No engine draws, the state is read only:
+//                          template <class Log> __device__ static void log_data(const ModelCtx &, const RayState &s, Log &&log);
+//                        A call outside the shape, or with a value that is negative, not finite or above 2^15, is dropped
+//                        and counted (vr_get_data_log_dropped).
 // materialId is the caller's id of the ORIGINAL primitive (vr_set_material_ids; 0 when none was set).  A stateful model
 // runs in the P_EXT_FULL instantiation (kNeedsFull), on SourceRandom only (plain or with a primary direction).
 #pragma once
@@ -166,6 +172,7 @@ struct ModelDiffuse {
   static constexpr int kNumData = 1;
   static constexpr bool kNeedsFull = false;
   static constexpr int kStateWords = 0; // (> 0: a stateful model, see the top of this file)
+  static constexpr int kLogRows = 0;    // (> 0: a stateful model with a log_data hook, rows of the data log it writes)
   __device__ static float sticking(const ModelCtx &, unsigned, float base) { return base; }
   template <int D>
   __device__ static V3 reflect(const ModelCtx &, const V3 &, const V3 &n, Rng &rng, unsigned &t2) {

@@ -1998,6 +1998,10 @@ static_assert(VrUserModel::kNumData == VR_USER_NUM_DATA, "kNumData differs from 
 static_assert(VrUserModel::kStateWords >= 0 && VrUserModel::kStateWords <= VR_MAX_STATE_WORDS, "a model has 0 .. 4 state words (kStateWords)");
 static_assert(VrUserModel::kStateWords == VR_USER_NUM_STATE, "kStateWords differs from the numState given at registration");
 static_assert(VrUserModel::kStateWords == 0 || VrUserModel::kNeedsFull, "a stateful model (kStateWords > 0) needs kNeedsFull = true");
+static_assert(VrUserModel::kLogRows >= 0 && VrUserModel::kLogRows <= VR_LOG_MAX_ROWS, "a model logs into 0 .. 16 rows of the data log (kLogRows)");
+static_assert(VrUserModel::kLogRows == 0 || VrUserModel::kStateWords > 0, "log_data (kLogRows > 0) logs the state init left: it needs a stateful model (kStateWords > 0)");
+// what the host asks the loaded module (vr_register_particle_model): the rows its log_data hook writes
+extern "C" __device__ __attribute__((used)) const int vr_user_log_rows = VrUserModel::kLogRows;
 constexpr int VR_USER_P = VrUserModel::kNeedsFull ? P_EXT_FULL : P_EXT;
 #define VR_INST(DD, GG, MM) template __global__ void trace_kernel<DD, GG, VR_USER_P, MM>(const TraceParams);
 VR_INST(2, 0, 0) VR_INST(2, 0, 4) VR_INST(2, 1, 0) VR_INST(2, 1, 4)
@@ -2010,12 +2014,44 @@ template __global__ void trace_kernel<3, 0, P_EXT, VrUserModel::kNeedsFull ? 0 :
 // rayTraceKernel.hpp:131-133) draws first, then the source sample from the same engine (the streaming generator of
 // gen_basis_kernel: the draw count varies), then the record with the true draw count — always with the side array
 // (TraceParams::recExtra) — and the ray's state at the same index (TraceParams::rayState).
+//
+// A model with a log_data hook (kLogRows > 0; the reference's logData, called right after initNew, and the per-thread DataLog
+// merged into Trace::getDataLog(), rayTraceKernel.hpp:131-133, 345) adds to the apply's data log here: int64 fixed-point
+// sums (value * 2^24), so the result does not depend on the grid, the batch split or the rank count.  A block sums into
+// a private copy of the log in LDS (VR_LOG_LDS_ENTRIES) and adds its non-zero entries to HBM once, when its loop ends;
+// a log beyond that budget (or VR_LOG_FLAGS bit 0) adds to HBM directly.  Overflow is detected by the adds themselves: every
+// add returns the sum it produced.  One add is at most 2^39, so a sum cannot pass from below 2^63 to beyond 2^64 without
+// one add seeing its top bit: an LDS sum with that bit raises the flag (the total is then out of range for any rank count),
+// and every add to HBM checks the carry and the bound 2^(63 - headroom) of the new total — sums only grow, so the add that
+// comes last sees the final value.  Without a shape (the frame's VR_F_LOG_* = 0) nothing of this runs.
 template <int D, class M = VrUserModel> __global__ __launch_bounds__(VR_BLOCK) void gen_state_kernel(const TraceParams p) {
   if constexpr (M::kStateWords > 0) {
     const unsigned tid = threadIdx.x;
     const unsigned gwave = (blockIdx.x * VR_BLOCK + tid) >> 6; // physical wave of this (bounded) grid
     u64 *scratchLane = p.rngScratch + (size_t)gwave * (312u * 64u) + (tid & 63u);
     const ModelCtx mctx = model_ctx(p);
+    constexpr bool LOG = M::kLogRows > 0;
+    __shared__ u64 logS[LOG ? VR_LOG_LDS_ENTRIES : 1];
+    __shared__ unsigned logOffS[LOG ? VR_LOG_MAX_ROWS + 1 : 1];
+    u64 *logG = nullptr, *logCtl = nullptr;
+    unsigned logRows = 0, logShift = 63, logDropped = 0;
+    bool logLds = false, logOverflow = false;
+    if constexpr (LOG) {
+      logG = reinterpret_cast<u64 *>(frame_addr(p.wallTable, VR_F_LOG_LO));
+      if (logG) {
+        logCtl = reinterpret_cast<u64 *>(frame_addr(p.wallTable, VR_F_LOGCTL_LO));
+        logRows = min((unsigned)logCtl[VR_LOG_ROWS], (unsigned)VR_LOG_MAX_ROWS);
+        logShift = 63u - (unsigned)logCtl[VR_LOG_HEADROOM];
+        if (tid <= logRows)
+          logOffS[tid] = (unsigned)logCtl[VR_LOG_OFFSETS + tid];
+        const unsigned total = (unsigned)logCtl[VR_LOG_OFFSETS + logRows];
+        logLds = total <= VR_LOG_LDS_ENTRIES && !(logCtl[VR_LOG_FLAGS] & 1ull);
+        if (logLds)
+          for (unsigned e = tid; e < total; e += VR_BLOCK)
+            logS[e] = 0ull;
+        __syncthreads();
+      }
+    }
     for (unsigned i = blockIdx.x * VR_BLOCK + tid; i < p.batchCount; i += gridDim.x * VR_BLOCK) {
       const unsigned long long idx = p.idxList ? p.idxList[i] : p.batchFirst + i;
       Rng rng;
@@ -2026,10 +2062,50 @@ template <int D, class M = VrUserModel> __global__ __launch_bounds__(VR_BLOCK) v
       for (int k = 0; k < 4; ++k)
         s.v[k] = 0.f;
       M::init(mctx, s, rng, t2);
+      if constexpr (LOG) {
+        if (logG) {
+          const RayState &born = s;
+          M::log_data(mctx, born, [&](int row, int bin, float value) {
+            bool ok = (unsigned)row < logRows && value >= 0.f && value <= VR_LOG_MAX_VALUE; // (a NaN fails both)
+            unsigned e = 0;
+            if (ok) {
+              e = logOffS[row] + (unsigned)bin;
+              ok = (unsigned)bin < logOffS[row + 1] - logOffS[row];
+            }
+            if (!ok) {
+              ++logDropped;
+              return;
+            }
+            const u64 q = (u64)((double)value * VR_LOG_SCALE + 0.5);
+            if (logLds)
+              logOverflow = logOverflow || ((atomicAdd(&logS[e], q) + q) >> 63) != 0ull;
+            else
+              logOverflow = logOverflow || ((atomicAdd(&logG[e], q) + q) >> logShift) != 0ull;
+          });
+        }
+      }
       V3 o, d;
       source_sample<D>(p, [&]() { return rng_next(rng, t2); }, o, d);
       gen_store<D, true>(p, i, o, d, rng.k, rng.lo, rng.hi); // (k >= 156: the trace kernel rebuilds tier 2 from the seed)
       reinterpret_cast<float4 *>(frame_addr(p.wallTable, VR_F_STATE_LO))[i] = make_float4(s.v[0], s.v[1], s.v[2], s.v[3]);
+    }
+    if constexpr (LOG) {
+      if (logG) {
+        if (logLds) {
+          __syncthreads();
+          for (unsigned e = tid; e < logOffS[logRows]; e += VR_BLOCK) {
+            const u64 v = logS[e];
+            if (v) {
+              const u64 now = atomicAdd(&logG[e], v) + v;
+              logOverflow = logOverflow || now < v || (now >> logShift) != 0ull;
+            }
+          }
+        }
+        if (logOverflow)
+          logCtl[VR_LOG_OVERFLOW] = 1ull;
+        if (logDropped)
+          atomicAdd(&logCtl[VR_LOG_DROPPED], (u64)logDropped);
+      }
     }
   }
 }

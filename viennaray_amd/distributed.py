@@ -18,6 +18,7 @@ import numpy as np
 COUNTER_KEYS = ("totalRaysTraced", "nonGeometryHits", "geometryHits", "particleHits",
                 "boundaryHits", "reflections", "raysTerminated")
 FLUX_FRAC_BITS = 40  # VR_FLUX_FRAC_BITS
+LOG_FRAC_BITS = 24   # VR_LOG_FRAC_BITS
 
 
 def ray_shard(num_rays, rank, world):
@@ -68,11 +69,27 @@ class GpuShard:
             info = None
             cnt = [0] * len(COUNTER_KEYS)
         self.last_info = info
+        self.log = self._local_log(count > 0)
         return self.acc, cnt
+
+    def _local_log(self, traced):
+        """This rank's data log (int64 sums + the dropped counter) as a tensor next to the accumulators; None without a
+        data-log shape.  An empty shard contributes zeros."""
+        import torch
+        rows = getattr(self.tr, "_logRows", [])
+        if not rows:
+            return None
+        n = sum(rows)
+        host = np.zeros(n + 1, dtype=np.int64)
+        if traced:
+            host[:n] = self.tr.dataLogAccumulators()
+            host[n] = self.tr.getDataLogDropped()
+        return torch.from_numpy(host).to(self.acc.device)
 
 
 def distributed_apply(shard, num_rays, rank=None, world=None, group=None, run_number=None):
-    """Trace this rank's slice of `num_rays` and all-reduce flux + counters.
+    """Trace this rank's slice of `num_rays` and all-reduce flux + counters (+ the data log, if a shape is set:
+    counters["dataLog"] holds the int64 sums per row, value * 2^24, counters["dataLogDropped"] the dropped calls).
     Returns (acc int64 tensor [numPrims] (sum over ranks), counters dict)."""
     import torch.distributed as dist
     if world is None:
@@ -99,6 +116,8 @@ def distributed_apply(shard, num_rays, rank=None, world=None, group=None, run_nu
         cnt_t = cnt if torch.is_tensor(cnt) else torch.tensor(cnt, dtype=torch.int64, device=acc.device)
         dist.all_reduce(cnt_t, op=dist.ReduceOp.SUM, group=group)
         cnt = cnt_t
+        if getattr(shard, "log", None) is not None:  # the data log travels with the flux: integers, exact
+            dist.all_reduce(shard.log, op=dist.ReduceOp.SUM, group=group)
         if on_gpu:
             e1.record()
             e1.synchronize()
@@ -110,6 +129,15 @@ def distributed_apply(shard, num_rays, rank=None, world=None, group=None, run_nu
     counters = {k: int(v) for k, v in zip(COUNTER_KEYS, cnt)}
     counters["numRays"] = int(num_rays)
     counters["allreduce_ms"] = allreduce_ms
+    log = getattr(shard, "log", None)
+    if log is not None:  # every rank holds the full log: int64 sums per row, and the dropped calls
+        flat = log.cpu().numpy()
+        rows, o = [], 0
+        for n in shard.tr._logRows:
+            rows.append(flat[o:o + n].copy())
+            o += n
+        counters["dataLog"] = rows
+        counters["dataLogDropped"] = int(flat[-1])
     return acc, counters
 
 

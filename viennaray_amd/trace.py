@@ -557,6 +557,47 @@ class Trace:
         self._check(self._L.vr_flux_accumulators(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    # --- the data log (DataLog / logData, rayTraceKernel.hpp:131-133, 345) --------
+    def setDataLogShape(self, rowSizes):
+        """Entries per row of the data log the log_data hook of a stateful model fills (at most 16 rows, 65536 entries
+        in all); an empty list clears the shape and nothing is logged."""
+        a = np.ascontiguousarray(rowSizes, dtype=np.uint32).reshape(-1)
+        self._check(self._L.vr_set_data_log_shape(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))
+        self._logRows = [int(v) for v in a]
+
+    def _log_rows(self, flat):
+        out, o = [], 0
+        for n in getattr(self, "_logRows", []):
+            out.append(flat[o:o + n].copy())
+            o += n
+        return out
+
+    def getDataLog(self):
+        """The last apply's log: one float32 array per row."""
+        flat = np.empty(sum(getattr(self, "_logRows", [])), dtype=np.float32)
+        self._check(self._L.vr_get_data_log(self._h, _fptr(flat), flat.size))
+        return self._log_rows(flat)
+
+    def dataLogAccumulators(self):
+        """The last apply's int64 fixed-point sums (value * 2^24), rows concatenated."""
+        flat = np.empty(sum(getattr(self, "_logRows", [])), dtype=np.int64)
+        self._check(self._L.vr_get_data_log_i64(self._h, flat.ctypes.data_as(C.POINTER(C.c_int64)), flat.size))
+        return flat
+
+    def getDataLogDropped(self):
+        """log calls of the last apply that were dropped: outside the shape, or a negative / non-finite / too large value"""
+        v = C.c_uint64(0)
+        self._check(self._L.vr_get_data_log_dropped(self._h, C.byref(v)))
+        return int(v.value)
+
+    def dataLogDevice(self):
+        """(device pointer, n) of the int64 sums for a caller's own collective; the dropped counter and the overflow flag
+        are the two words behind them (vr_data_log_accumulators)."""
+        p = C.c_void_p()
+        n = C.c_uint32()
+        self._check(self._L.vr_data_log_accumulators(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def bindFluxAccumulators(self, dev_ptr, n):
         """Use a caller-owned device buffer of n int64 (e.g. a torch tensor)."""
         self._check(self._L.vr_bind_flux_accumulators(self._h, C.c_void_p(dev_ptr), int(n)))
