@@ -42,6 +42,8 @@ enum { VR_REFLECTIVE_BOUNDARY = 0, VR_PERIODIC_BOUNDARY = 1, VR_IGNORE_BOUNDARY 
 enum { VR_POS_X = 0, VR_NEG_X = 1, VR_POS_Y = 2, VR_NEG_Y = 3, VR_POS_Z = 4, VR_NEG_Z = 5 };
 /* rayUtil.hpp:38 */
 enum { VR_NORM_SOURCE = 0, VR_NORM_MAX = 1 };
+/* vr_get_flux_device: no normalisation, the raw flux */
+enum { VR_NORM_NONE = -1 };
 /* particle kinds of the device registry (viennaray_amd/csrc/vr_particles.hpp):
  * 0, 1     the reference's built-ins DiffuseParticle / SpecularParticle (rayParticle.hpp:126-204)
  * 2        CONED_COSINE: surfaceReflection = ReflectionConedCosine(coneAngle) (rayReflection.hpp:52-120),
@@ -110,6 +112,17 @@ const char *vr_version(void);
  * gridDelta * DiskFactor<D> (rayUtil.hpp:99-101).                           */
 int vr_set_disks(vr_context *ctx, const float *points, const float *normals,
                  uint32_t n, float gridDelta, float diskRadius, int D);
+/* vr_set_disks for a surface that already lives on the device (an advection step written in torch or HIP).
+ * points / normals: DEVICE pointers on ctx's device, float32, row-major, `ld` floats per row (2 or 3; 2 only when
+ * D == 2; with D == 2 and ld == 3 the third column is ignored, as vr_set_disks ignores it).  `stream`: the hipStream_t
+ * the caller produced them on (NULL = the null stream); the library's stream waits for it by an event.  On return the
+ * library has taken its own copy: the caller may overwrite or free its buffers at once.  Same argument checks and
+ * effects as vr_set_disks; additionally refuses ld outside {2, 3} and pointers that are not device memory of ctx's
+ * device (host, pinned and managed memory included).  A refusal leaves the previous geometry in place.  What comes
+ * back to the host is the bounding box (six floats); the host copies of the rows are made only if a host path
+ * (VR_HOST_BUILD, VR_HOST_SMOOTH, a smoothing overflow) asks for them.                                   */
+int vr_set_disks_device(vr_context *ctx, const float *points, const float *normals, uint32_t n, uint32_t ld,
+                        float gridDelta, float diskRadius, int D, void *stream);
 /* TraceTriangle::setGeometry(TriangleMesh) (rayTraceTriangle.hpp:71-74;
  * normals per rayMesh.hpp:99-112).  verts: nverts x 3, tris: ntris x 3.      */
 int vr_set_triangles(vr_context *ctx, const float *verts, uint32_t nverts,
@@ -253,6 +266,15 @@ int vr_normalize_flux(vr_context *ctx, float *flux, uint32_t n, int normType);
  * the host (accumulators -> float -> flux * sourceArea / (numRays * area), one download)     */
 int vr_get_flux_normalized(vr_context *ctx, float *out, uint32_t n, int normType);
 int vr_smooth_flux(vr_context *ctx, float *flux, uint32_t n, int numNeighbors);
+/* The flux of data label `dataIdx` in the CALLER's primitive order, float32, written to DEVICE memory `out`
+ * (n = numPrims, on ctx's device): accumulators -> float -> normalizeFlux(normType; VR_NORM_NONE = raw) ->
+ * smoothFlux(numNeighbors; 0 = none), bit for bit what vr_get_flux_data, vr_normalize_flux and vr_smooth_flux return
+ * one after the other.  The work is enqueued on the context's stream behind what `stream` (the caller's, NULL = the
+ * null stream) holds at the call, and `stream` is made to wait for it by an event: without smoothing there is no host
+ * synchronisation and no host copy.  With smoothing one word is read back (the kernels' overflow flag); if it is set
+ * the host smoothing runs and its result is uploaded.                                                     */
+int vr_get_flux_device(vr_context *ctx, uint32_t dataIdx, float *out, uint32_t n, int normType, int numNeighbors,
+                       void *stream);
 /* geometry-derived values the reference exposes to its tests                */
 int vr_get_disk_areas(vr_context *ctx, float *out, uint32_t n);
 int vr_get_bounding_box(vr_context *ctx, float *out6 /* min xyz, max xyz, adjusted */);

@@ -1151,6 +1151,18 @@ public:
     inPlace(flux, [&](float *p, uint32_t n) { return vr_smooth_flux(ctx_, p, n, numNeighbors); });
   }
 
+  /// The flux of data label `dataIdx` written to DEVICE memory `dOut` (float32, one per primitive, caller's order):
+  /// getLocalData().getVectorData(dataIdx) -> normalizeFlux(norm) -> smoothFlux(numNeighbors; 0 = none), computed and
+  /// left on the device (vr_get_flux_device).  `stream`: the caller's hipStream_t (nullptr = the null stream), which is
+  /// made to wait for the result; without smoothing nothing synchronises with the host.  false if it was refused.
+  bool getFluxDevice(float *dOut, int dataIdx, NormalizationType norm, int numNeighbors, void *stream = nullptr) {
+    return fluxDevice(dOut, dataIdx, (int)norm, numNeighbors, stream);
+  }
+  /// ... the raw flux, neither normalised nor smoothed
+  bool getFluxDevice(float *dOut, int dataIdx = 0, void *stream = nullptr) {
+    return fluxDevice(dOut, dataIdx, VR_NORM_NONE, 0, stream);
+  }
+
   [[nodiscard]] TracingData<NumericType> &getLocalData() { return localData_; }
   // rayTrace.hpp:137-145: global data is a borrowed pointer handed to user particles; apply() copies its vectors and
   // scalars to the device, where the registry's particle models read them (ModelCtx::global)
@@ -1196,6 +1208,14 @@ protected:
       RTInfo_.error = true;
       std::cerr << "viennaray_amd: " << vr_last_error(ctx_) << "\n";
     }
+  }
+  bool fluxDevice(float *dOut, int dataIdx, int norm, int numNeighbors, void *stream) {
+    if (!ctx_)
+      return false;
+    const int rc = vr_get_flux_device(ctx_, (uint32_t)dataIdx, dOut, vr_num_primitives(ctx_), norm, numNeighbors, stream);
+    if (rc != VR_OK)
+      std::cerr << "viennaray_amd: " << vr_last_error(ctx_) << "\n";
+    return rc == VR_OK;
   }
   void geometryAccepted(int rc) { // a new geometry clears an earlier refusal
     setterError_ = false;
@@ -1333,6 +1353,19 @@ public:
     auto p = this->flatten3(mesh.nodes), n = this->flatten3(mesh.normals);
     if (this->ctx_)
       this->geometryAccepted(vr_set_disks(this->ctx_, p.data(), n.data(), (uint32_t)mesh.nodes.size(), mesh.gridDelta, 0.f, D));
+  }
+  /// setGeometry for a surface that already lives on the device (vr_set_disks_device): dPoints / dNormals are DEVICE
+  /// pointers to n rows of `ld` floats (2 or 3; 2 only for D == 2), produced on `stream` (the caller's hipStream_t,
+  /// nullptr = the null stream).  The library takes its own copy on the device: the buffers are free again on return.
+  void setGeometryDevice(const float *dPoints, const float *dNormals, size_t n, unsigned ld, NumericType gridDelta,
+                         void *stream = nullptr) {
+    setGeometryDevice(dPoints, dNormals, n, ld, gridDelta, NumericType(0), stream);
+  }
+  void setGeometryDevice(const float *dPoints, const float *dNormals, size_t n, unsigned ld, NumericType gridDelta,
+                         NumericType diskRadii, void *stream) {
+    if (this->ctx_)
+      this->geometryAccepted(vr_set_disks_device(this->ctx_, dPoints, dNormals, (uint32_t)n, ld, (float)gridDelta,
+                                                 (float)diskRadii, D, stream));
   }
   template <typename T> void setMaterialIds(std::vector<T> const &materialIds) {
     std::vector<int32_t> ids(materialIds.begin(), materialIds.end());

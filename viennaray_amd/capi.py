@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VR_LIB_PATH") or os.path.join(_HERE, "libviennaray_amd.so")  # (override: A/B runs of two builds)
 
 VR_OK, VR_E_INVALID, VR_E_HIP, VR_E_STATE = 0, -1, -2, -3
+VR_NORM_NONE = -1  # vr_get_flux_device: the raw flux
 
 
 class VrError(RuntimeError):
@@ -52,6 +53,7 @@ SIGNATURES = {
     "vr_device_available": (C.c_int, []),
     "vr_version": (C.c_char_p, []),
     "vr_set_disks": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_float, C.c_float, C.c_int]),
+    "vr_set_disks_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_int, _vp]),
     "vr_set_triangles": (C.c_int, [_vp, _fp, C.c_uint32, _u32p, C.c_uint32, C.c_float, C.c_int]),
     "vr_set_material_ids": (C.c_int, [_vp, _i32p, C.c_uint32]),
     "vr_set_boundary_conditions": (C.c_int, [_vp, _i32p, C.c_int]),
@@ -96,6 +98,7 @@ SIGNATURES = {
     "vr_normalize_flux": (C.c_int, [_vp, _fp, C.c_uint32, C.c_int]),
     "vr_get_flux_normalized": (C.c_int, [_vp, _fp, C.c_uint32, C.c_int]),
     "vr_smooth_flux": (C.c_int, [_vp, _fp, C.c_uint32, C.c_int]),
+    "vr_get_flux_device": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_int, C.c_int, _vp]),
     "vr_get_disk_areas": (C.c_int, [_vp, _fp, C.c_uint32]),
     "vr_get_bounding_box": (C.c_int, [_vp, _fp]),
     "vr_get_source_area": (C.c_float, [_vp]),

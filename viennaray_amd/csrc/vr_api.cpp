@@ -374,6 +374,14 @@ struct vr_context {
   uint32_t accReplicas = 1, accStride = 0;
   // device-side setup (vr_setup.hip)
   DevBuf<float> dDisk4, dNormal3, dPoints3, dVerts, dBox, dSBox, dNodeBox;
+  // The geometry's source.  vr_set_disks_device fills dPoints3 / dNormal3 / dDisk4 itself (geoOnDevice): build_scene then
+  // uploads nothing, and geo.points3 / normal3 / disk4 are a mirror that ensure_host_geometry downloads when a host path
+  // (VR_HOST_BUILD, VR_HOST_SMOOTH, a smoothing overflow) reads them.
+  bool geoOnDevice = false, hostGeoValid = false;
+  DevBuf<unsigned long long> dIngestKeys; // launch_ingest_disks' block partials
+  DevBuf<float> dIngestBounds;            // ... and its six bounds
+  DevBuf<double> dSortPlane;              // launch_sort_plane's block partials, then the 512 merged sums
+  hipEvent_t evIn = nullptr, evOut = nullptr; // hand-over between a caller's stream and this context's (device entry points)
   DevBuf<uint32_t> dTris, dBounds, dValsA, dValsB, dSortTable, dRangeLo, dRangeHi, dChildL, dChildR, dParentInt,
       dParentLeaf, dArrive, dOrder, dSubSize, dQNodes, dPNodes, dWalkStack;
   size_t walkStackWaves = 0;
@@ -508,6 +516,10 @@ void vr_destroy(vr_context *c) {
     (void)hipEventDestroy(e);
   for (auto e : c->evG)
     (void)hipEventDestroy(e);
+  if (c->evIn)
+    (void)hipEventDestroy(c->evIn);
+  if (c->evOut)
+    (void)hipEventDestroy(c->evOut);
   if (c->ev0)
     (void)hipEventDestroy(c->ev0);
   if (c->ev1)
@@ -525,12 +537,101 @@ int vr_set_disks(vr_context *c, const float *points, const float *normals, uint3
   if (!c || !points || !normals || (D != 2 && D != 3) || n >= (1u << 27))
     return fail(c, VR_E_INVALID, "vr_set_disks: bad argument");
   host_set_disks(c->geo, points, normals, n, gridDelta, diskRadius, D);
+  c->geoOnDevice = c->hostGeoValid = false;
   c->hostNeighborsValid = false;
   c->areasValid = false;
   c->boundFlux = nullptr;
   c->geometryDirty = true;
   c->configDirty = true;
   c->prepared = c->haveResult = false;
+  return VR_OK;
+}
+
+// `p` is device memory of `device` (hipMalloc / a torch tensor's storage; not host, pinned or managed memory)
+static bool is_device_memory_of(const void *p, int device) {
+  hipPointerAttribute_t a{};
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError(); // (an unregistered host pointer is an error of this call on some runtimes: not a sticky one)
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice && a.device == device;
+}
+
+// c->stream waits for what `stream` (the caller's; nullptr = the null stream) holds now
+static int wait_for_caller(vr_context *c, hipStream_t stream) {
+  if (!c->evIn)
+    VR_HIP(c, hipEventCreateWithFlags(&c->evIn, hipEventDisableTiming));
+  VR_HIP(c, hipEventRecord(c->evIn, stream));
+  VR_HIP(c, hipStreamWaitEvent(c->stream, c->evIn, 0));
+  return VR_OK;
+}
+// ... and the reverse: `stream` waits for what c->stream holds now
+static int caller_waits(vr_context *c, hipStream_t stream) {
+  if (!c->evOut)
+    VR_HIP(c, hipEventCreateWithFlags(&c->evOut, hipEventDisableTiming));
+  VR_HIP(c, hipEventRecord(c->evOut, c->stream));
+  VR_HIP(c, hipStreamWaitEvent(stream, c->evOut, 0));
+  return VR_OK;
+}
+
+// vr_set_disks for rows that live on the device: one kernel packs them into the builder's buffers and reduces the
+// bounding box; six floats come back.  Nothing of the previous geometry is touched before the arguments are accepted.
+int vr_set_disks_device(vr_context *c, const float *points, const float *normals, uint32_t n, uint32_t ld,
+                        float gridDelta, float diskRadius, int D, void *stream) {
+  if (!c || !points || !normals || (D != 2 && D != 3) || n >= (1u << 27))
+    return fail(c, VR_E_INVALID, "vr_set_disks_device: bad argument");
+  if (ld != 2 && ld != 3)
+    return fail(c, VR_E_INVALID, "vr_set_disks_device: ld (floats per row) must be 2 or 3");
+  if (ld == 2 && D != 2)
+    return fail(c, VR_E_INVALID, "vr_set_disks_device: rows of 2 floats need D == 2");
+  VR_HIP(c, hipSetDevice(c->device));
+  if (n && (!is_device_memory_of(points, c->device) || !is_device_memory_of(normals, c->device)))
+    return fail(c, VR_E_INVALID, "vr_set_disks_device: points / normals are not device memory of the context's device");
+  hipStream_t caller = (hipStream_t)stream;
+  const float radius = host_disk_radius(gridDelta, diskRadius, D);
+  VR_HIP(c, c->dPoints3.ensure((size_t)n * 3));
+  VR_HIP(c, c->dNormal3.ensure((size_t)n * 3));
+  VR_HIP(c, c->dDisk4.ensure((size_t)n * 4));
+  VR_HIP(c, c->dIngestKeys.ensure(ingest_partials_entries()));
+  VR_HIP(c, c->dIngestBounds.ensure(6));
+  // from here on the resident buffers no longer hold the previous geometry
+  c->geometryDirty = true;
+  c->configDirty = true;
+  c->prepared = c->haveResult = false;
+  c->hostNeighborsValid = false;
+  c->areasValid = false;
+  c->boundFlux = nullptr;
+  HostGeometry &g = c->geo;
+  g.numPrims = 0; // (until the new one is in place: an error below leaves "no geometry", not half of one)
+  g.disk4.clear();
+  g.normal3.clear();
+  g.points3.clear();
+  c->geoOnDevice = c->hostGeoValid = false;
+  int r = wait_for_caller(c, caller);
+  if (r != VR_OK)
+    return r;
+  VR_HIP(c, launch_ingest_disks(points, normals, n, ld, D, radius, c->dPoints3.p, c->dNormal3.p, c->dDisk4.p,
+                                c->dIngestKeys.p, c->dIngestBounds.p, c->stream));
+  float b[6];
+  VR_HIP(c, hipMemcpyAsync(b, c->dIngestBounds.p, sizeof(b), hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream)); // (the copy is taken: the caller may overwrite or free its rows)
+  g.D = D;
+  g.geo = 0;
+  g.numPrims = n;
+  g.gridDelta = gridDelta;
+  g.diskRadius = radius;
+  for (int k = 0; k < 3; ++k) {
+    g.minC[k] = k < D ? b[k] : 0.f;
+    g.maxC[k] = k < D ? b[3 + k] : 0.f;
+  }
+  if (g.materialIds.size() != n)
+    g.materialIds.assign(n, 0);
+  g.nbOff.clear();
+  g.nbIds.clear();
+  g.verts.clear();
+  g.tris.clear();
+  g.triAreas.clear();
+  c->geoOnDevice = true;
   return VR_OK;
 }
 
@@ -542,6 +643,7 @@ int vr_set_triangles(vr_context *c, const float *verts, uint32_t nverts, const u
     if (tris[i] >= nverts)
       return fail(c, VR_E_INVALID, "vr_set_triangles: vertex index out of range");
   host_set_triangles(c->geo, verts, nverts, tris, ntris, gridDelta, D);
+  c->geoOnDevice = c->hostGeoValid = false;
   c->areasValid = false;
   c->boundFlux = nullptr;
   c->geometryDirty = true;
@@ -1107,6 +1209,26 @@ int vr_set_ray_range(vr_context *c, uint64_t first, uint64_t count) {
 }
 
 // ---- scene build (device LBVH + neighbourhood; VR_HOST_BUILD=1 selects the host builder) -------
+// geo.points3 / normal3 / disk4 of a device-resident geometry, downloaded when a host path first reads them
+static int ensure_host_geometry(vr_context *c) {
+  if (!c->geoOnDevice || c->hostGeoValid)
+    return VR_OK;
+  HostGeometry &g = c->geo;
+  const size_t N = g.numPrims;
+  g.points3.resize(N * 3);
+  g.normal3.resize(N * 3);
+  g.disk4.resize(N * 4);
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  if (N) {
+    VR_HIP(c, hipMemcpy(g.points3.data(), c->dPoints3.p, N * 12, hipMemcpyDeviceToHost));
+    VR_HIP(c, hipMemcpy(g.normal3.data(), c->dNormal3.p, N * 12, hipMemcpyDeviceToHost));
+    VR_HIP(c, hipMemcpy(g.disk4.data(), c->dDisk4.p, N * 16, hipMemcpyDeviceToHost));
+  }
+  c->hostGeoValid = true;
+  return VR_OK;
+}
+
 static int ensure_host_order(vr_context *c) {
   if (c->hostOrderValid)
     return VR_OK;
@@ -1148,6 +1270,9 @@ static int ensure_host_neighbors(vr_context *c) {
       std::sort(g.nbIds.begin() + g.nbOff[c->bvh.order[q]], g.nbIds.begin() + w);
     }
   } else {
+    int r = ensure_host_geometry(c);
+    if (r != VR_OK)
+      return r;
     host_neighbors(g.D, g.points3.data(), N, 2 * g.diskRadius, g.minC, g.nbOff, g.nbIds);
   }
   c->hostNeighborsValid = true;
@@ -1198,6 +1323,11 @@ static int build_scene(vr_context *c) {
   VR_HIP(c, c->dNbOff.ensure((size_t)N + 1));
   if (K.hostBuild) {
     // host builder (validation path): LBVH + CSR on the CPU, uploaded
+    {
+      const int r = ensure_host_geometry(c);
+      if (r != VR_OK)
+        return r;
+    }
     if (disk)
       host_neighbors(g.D, g.points3.data(), N, 2 * g.diskRadius, g.minC, g.nbOff, g.nbIds);
     else
@@ -1250,14 +1380,18 @@ static int build_scene(vr_context *c) {
   s.D = g.D;
   s.nbDist = 2 * g.diskRadius;
   s.mortonAniso = K.mortonAniso;
-  VR_HIP(c, c->dNormal3.ensure((size_t)N * 3));
-  VR_HIP(c, hipMemcpyAsync(c->dNormal3.p, g.normal3.data(), (size_t)N * 12, hipMemcpyHostToDevice, c->stream));
-  if (disk) {
+  if (c->geoOnDevice) {
+    // (vr_set_disks_device left dPoints3 / dNormal3 / dDisk4 filled: nothing to upload)
+  } else if (disk) {
+    VR_HIP(c, c->dNormal3.ensure((size_t)N * 3));
+    VR_HIP(c, hipMemcpyAsync(c->dNormal3.p, g.normal3.data(), (size_t)N * 12, hipMemcpyHostToDevice, c->stream));
     VR_HIP(c, c->dDisk4.ensure((size_t)N * 4));
     VR_HIP(c, c->dPoints3.ensure((size_t)N * 3));
     VR_HIP(c, hipMemcpyAsync(c->dPoints3.p, g.points3.data(), (size_t)N * 12, hipMemcpyHostToDevice, c->stream));
     VR_HIP(c, launch_disk4(c->dPoints3.p, N, g.diskRadius, g.D, c->dDisk4.p, c->stream)); // (= g.disk4, made on the device)
   } else {
+    VR_HIP(c, c->dNormal3.ensure((size_t)N * 3));
+    VR_HIP(c, hipMemcpyAsync(c->dNormal3.p, g.normal3.data(), (size_t)N * 12, hipMemcpyHostToDevice, c->stream));
     VR_HIP(c, c->dVerts.ensure(g.verts.size()));
     VR_HIP(c, c->dTris.ensure(g.tris.size()));
     VR_HIP(c, hipMemcpyAsync(c->dVerts.p, g.verts.data(), g.verts.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1527,8 +1661,41 @@ static int check_settings(vr_context *c) {
   return VR_OK;
 }
 
+// host_sort_plane for a device-resident disk geometry: the histogram is made where the disks are (launch_sort_plane),
+// 512 doubles come back and the fullest slice is picked as the host function picks it.  (The sums are taken in another
+// order than the host threads take them: the plane may differ in its last bits; it only orders work.)
+static int device_sort_plane(vr_context *c, int axis, float fallback, float *coord, float *modeShare) {
+  const HostGeometry &g = c->geo;
+  const float lo = g.minC[axis], hi = g.maxC[axis];
+  *modeShare = 1.f;
+  if (g.numPrims == 0 || !(hi > lo)) {
+    *coord = g.numPrims ? lo : fallback;
+    return VR_OK;
+  }
+  constexpr int SL = 256;
+  const size_t scratch = sort_plane_partials_entries();
+  VR_HIP(c, c->dSortPlane.ensure(scratch + 2 * SL));
+  double h[2 * SL];
+  VR_HIP(c, launch_sort_plane(c->dDisk4.p, c->dNormal3.p, g.numPrims, axis, lo, hi, c->dSortPlane.p,
+                              c->dSortPlane.p + scratch, c->stream));
+  VR_HIP(c, hipMemcpyAsync(h, c->dSortPlane.p + scratch, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  const double *w = h, *wh = h + SL;
+  int best = 0;
+  double total = w[0];
+  for (int k = 1; k < SL; ++k) {
+    total += w[k];
+    if (w[k] > w[best])
+      best = k;
+  }
+  if (total > 0.)
+    *modeShare = (float)(w[best] / total);
+  *coord = w[best] > 0. ? (float)(wh[best] / w[best]) : fallback;
+  return VR_OK;
+}
+
 // bounding box, trace settings, walls, boundary conditions (rayTraceDisk.hpp:21-27), source area and the sort plane
-static void setup_source_frame(vr_context *c) {
+static int setup_source_frame(vr_context *c) {
   const int D = c->geo.D;
   for (int k = 0; k < 3; ++k) {
     c->bbLo[k] = c->geo.minC[k];
@@ -1553,7 +1720,11 @@ static void setup_source_frame(vr_context *c) {
   // SourceRandom::getSourceArea (raySourceRandom.hpp:40-47)
   const int f = c->ts[1], s = c->ts[2];
   c->sourceArea = D == 2 ? (c->bbHi[f] - c->bbLo[f]) : (c->bbHi[f] - c->bbLo[f]) * (c->bbHi[s] - c->bbLo[s]);
-  c->keyCoord = host_sort_plane(c->geo, c->ts[0], c->ts[3] ? c->geo.minC[c->ts[0]] : c->geo.maxC[c->ts[0]], &c->keyShare);
+  const float fallback = c->ts[3] ? c->geo.minC[c->ts[0]] : c->geo.maxC[c->ts[0]];
+  if (c->geoOnDevice)
+    return device_sort_plane(c, c->ts[0], fallback, &c->keyCoord, &c->keyShare);
+  c->keyCoord = host_sort_plane(c->geo, c->ts[0], fallback, &c->keyShare);
+  return VR_OK;
 }
 
 // exposed area of every primitive, resident on the device for normalizeFlux
@@ -1577,6 +1748,9 @@ static int compute_areas(vr_context *c) {
       ap.maxC[k] = c->geo.maxC[k];
     }
     if (c->knobs.hostBuild) {
+      const int r = ensure_host_geometry(c);
+      if (r != VR_OK)
+        return r;
       host_disk_areas(c->geo, ap, c->diskAreas);
       VR_HIP(c, hipMemcpy(c->dAreas.p, c->diskAreas.data(), (size_t)N * 4, hipMemcpyHostToDevice));
       c->diskAreasHostValid = true;
@@ -2229,7 +2403,7 @@ static int prepare_one(vr_context *c, ParticleLaunch &L) {
   const auto t0 = std::chrono::steady_clock::now();
   const bool redoConfig = c->configDirty || c->geometryDirty;
   if (redoConfig)
-    setup_source_frame(c);
+    VR_TRY(setup_source_frame(c));
   // the BVH's child order follows the source side: a new source direction rebuilds it
   if (c->builtOrderAxis != c->ts[0] || c->builtOrderSign != (c->ts[3] ? 1.f : -1.f))
     c->geometryDirty = true;
@@ -3013,8 +3187,8 @@ int vr_bind_flux_accumulators(vr_context *c, void *devPtr, uint32_t n) {
 void *vr_stream(vr_context *c) { return c ? (void *)c->stream : nullptr; }
 
 // normalizeFlux on the device (rayTraceDisk.hpp:103-142, rayTraceTriangle.hpp:92-130;
-// gpu/kernels/normKernels.cu:58-74): dFluxTmp holds the flux in the caller's order
-static int normalize_on_device(vr_context *c, uint32_t n, int normType) {
+// gpu/kernels/normKernels.cu:58-74): `flux` (device) holds the flux in the caller's order
+static int normalize_on_device(vr_context *c, float *flux, uint32_t n, int normType) {
   const bool disk = c->geo.geo == 0;
   if (!c->areasValid)
     return fail(c, VR_E_STATE, "vr_normalize_flux: call vr_apply first (primitive areas)");
@@ -3028,7 +3202,7 @@ static int normalize_on_device(vr_context *c, uint32_t n, int normType) {
   }
   const double totalDiskArea = c->geo.diskRadius * c->geo.diskRadius * M_PI;
   VR_HIP(c, c->dNormMax.ensure(1)); // (a word of its own: the builder's scratch does not exist under VR_HOST_BUILD)
-  VR_HIP(c, launch_normalize_flux(c->dFluxTmp.p, c->dAreas.p, n, disk ? 0 : 1, normType, normFactor, totalDiskArea,
+  VR_HIP(c, launch_normalize_flux(flux, c->dAreas.p, n, disk ? 0 : 1, normType, normFactor, totalDiskArea,
                                   c->dNormMax.p, c->stream));
   return VR_OK;
 }
@@ -3039,7 +3213,7 @@ int vr_normalize_flux(vr_context *c, float *flux, uint32_t n, int normType) {
   VR_HIP(c, hipSetDevice(c->device));
   VR_HIP(c, c->dFluxTmp.ensure(n));
   VR_HIP(c, hipMemcpyAsync(c->dFluxTmp.p, flux, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  int r = normalize_on_device(c, n, normType);
+  int r = normalize_on_device(c, c->dFluxTmp.p, n, normType);
   if (r != VR_OK)
     return r;
   VR_HIP(c, hipMemcpyAsync(flux, c->dFluxTmp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3059,7 +3233,7 @@ int vr_get_flux_normalized(vr_context *c, float *out, uint32_t n, int normType) 
   VR_HIP(c, hipSetDevice(c->device));
   VR_HIP(c, c->dFluxTmp.ensure(n));
   VR_HIP(c, launch_flux_from_acc(c->fluxOut(), n, c->dFluxTmp.p, c->stream));
-  int r = normalize_on_device(c, n, normType);
+  int r = normalize_on_device(c, c->dFluxTmp.p, n, normType);
   if (r != VR_OK)
     return r;
   VR_HIP(c, hipMemcpyAsync(out, c->dFluxTmp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3099,6 +3273,11 @@ int vr_smooth_flux(vr_context *c, float *flux, uint32_t n, int numNeighbors) {
       return VR_OK;
     } // (some neighbourhood longer than the kernel's buffer: host path below)
   }
+  {
+    const int r = ensure_host_geometry(c); // (the host path reads the normals, and the centres for k > 1)
+    if (r != VR_OK)
+      return r;
+  }
   if (numNeighbors == 1) {
     int r = ensure_host_neighbors(c);
     if (r != VR_OK)
@@ -3131,6 +3310,69 @@ int vr_smooth_flux(vr_context *c, float *flux, uint32_t n, int numNeighbors) {
     flux[i] = vv / sum;
   }
   return VR_OK;
+}
+
+// getLocalData().getVectorData(dataIdx) -> normalizeFlux -> smoothFlux with every stage on the device and the result left
+// in the caller's device buffer: the kernels vr_get_flux_data / vr_normalize_flux / vr_smooth_flux run, on the same floats,
+// so the result has their bits.  Without smoothing nothing comes back to the host and nothing waits; with smoothing one
+// word does (the kernels' overflow flag, which decides on the host fallback).
+int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, int normType, int numNeighbors,
+                       void *stream) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  if (!c->haveResult)
+    return fail(c, VR_E_STATE, "vr_get_flux_device: no result (call vr_apply)");
+  if (n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, "vr_get_flux_device: size mismatch");
+  if (dataIdx >= c->totalData)
+    return fail(c, VR_E_INVALID, "vr_get_flux_device: the particle has no such data label");
+  VR_HIP(c, hipSetDevice(c->device));
+  if (n && !is_device_memory_of(out, c->device))
+    return fail(c, VR_E_INVALID, "vr_get_flux_device: out is not device memory of the context's device");
+  hipStream_t caller = (hipStream_t)stream;
+  const bool smooth = c->geo.geo == 0 && numNeighbors >= 1;
+  int r = wait_for_caller(c, caller); // (out may still be in use by work the caller queued before this call)
+  if (r != VR_OK)
+    return r;
+  float *work = out;
+  if (smooth) { // (the smoothing kernels read one buffer and write another)
+    VR_HIP(c, c->dFluxTmp.ensure(n));
+    work = c->dFluxTmp.p;
+  }
+  VR_HIP(c, launch_flux_from_acc(c->fluxOut() + (size_t)dataIdx * n, n, work, c->stream));
+  if (normType == VR_NORM_SOURCE || normType == VR_NORM_MAX) {
+    r = normalize_on_device(c, work, n, normType);
+    if (r != VR_OK)
+      return r;
+  }
+  if (smooth) {
+    bool done = false;
+    if (c->haveSetup && !c->geometryDirty && !read_knobs().hostSmooth) {
+      DevBuf<uint32_t> dOv;
+      VR_HIP(c, dOv.ensure(1));
+      uint32_t ov = 0;
+      VR_HIP(c, hipMemsetAsync(dOv.p, 0, 4, c->stream));
+      if (numNeighbors == 1)
+        VR_HIP(c, launch_smooth_flux(work, out, c->dNormal3.p, c->dNbOff.p, c->dNbIds.p, c->dOrder.p, c->dLeafOfOrig.p, n,
+                                     dOv.p, c->stream));
+      else
+        VR_HIP(c, launch_smooth_wide(work, out, c->dNormal3.p, c->lastSetup, numNeighbors * 2 * c->geo.diskRadius, dOv.p,
+                                     c->stream));
+      VR_HIP(c, hipMemcpyAsync(&ov, dOv.p, 4, hipMemcpyDeviceToHost, c->stream));
+      VR_HIP(c, hipStreamSynchronize(c->stream));
+      done = ov == 0;
+    }
+    if (!done) { // the one path through the host: vr_smooth_flux's own fallback, then up again
+      std::vector<float> h(n);
+      VR_HIP(c, hipMemcpyAsync(h.data(), work, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+      VR_HIP(c, hipStreamSynchronize(c->stream));
+      r = vr_smooth_flux(c, h.data(), n, numNeighbors);
+      if (r != VR_OK)
+        return r;
+      VR_HIP(c, hipMemcpy(out, h.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+  }
+  return caller_waits(c, caller);
 }
 
 int vr_get_disk_areas(vr_context *c, float *out, uint32_t n) {

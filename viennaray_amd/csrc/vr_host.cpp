@@ -66,9 +66,7 @@ void host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_
   g.geo = 0;
   g.numPrims = n;
   g.gridDelta = gridDelta;
-  // rayTraceDisk.hpp:70 / rayUtil.hpp:99-101
-  const double factor = 0.5 * (D == 3 ? 1.7320508 : 1.41421356237) * (1 + 1e-5);
-  g.diskRadius = radius > 0.f ? radius : (float)(gridDelta * factor);
+  g.diskRadius = host_disk_radius(gridDelta, radius, D);
   g.disk4.resize((size_t)n * 4);
   g.normal3.resize((size_t)n * 3);
   g.points3.resize((size_t)n * 3); // (filled by the threads below: a serial copy of 12 MB was half of this function)

@@ -20,6 +20,7 @@ struct HostGeometry {
   std::vector<float> disk4;   // n x {x,y,z,r}
   std::vector<float> normal3; // n x 3 (disk normals / triangle unit normals)
   std::vector<float> points3; // caller's points (neighbourhood input)
+  // (a device-resident geometry, vr_set_disks_device, leaves these three empty until a host path asks for them)
   // triangles
   std::vector<float> verts;   // nv x 3
   std::vector<uint32_t> tris; // n x 3
@@ -36,6 +37,11 @@ struct Bvh {
   uint32_t numNodes = 0, numLeaves = 0, maxDepth = 0;
 };
 
+// the radius of every disk: the caller's, or gridDelta * DiskFactor<D> (rayTraceDisk.hpp:70 / rayUtil.hpp:99-101)
+inline float host_disk_radius(float gridDelta, float radius, int D) {
+  const double factor = 0.5 * (D == 3 ? 1.7320508 : 1.41421356237) * (1 + 1e-5);
+  return radius > 0.f ? radius : (float)(gridDelta * factor);
+}
 // geometry ingestion (restates rayGeometryDisk.hpp:101-193, rayGeometryTriangle.hpp:14-88 + rayMesh.hpp:99-112)
 void host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_t n, float gridDelta, float radius,
                     int D);

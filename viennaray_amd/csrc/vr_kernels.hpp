@@ -46,6 +46,18 @@ hipError_t launch_wide_tree(const SetupParams &s, unsigned *out3, hipStream_t st
 hipError_t launch_height_field(const HeightFieldParams &q, hipStream_t st);
 hipError_t launch_relief_field(const ReliefParams &q, hipStream_t st);
 hipError_t launch_disk4(const float *points3, unsigned n, float radius, int D, float *disk4, hipStream_t st);
+// device-resident disk geometry (vr_set_disks_device): the caller's DEVICE rows (ld = 2 or 3 floats) -> points3, normal3,
+// disk4 and the box of the first D columns, bounds6 = {min xyz, max xyz} (bit-equal to host_set_disks'); partials:
+// ingest_partials_entries() words of scratch
+size_t ingest_partials_entries();
+hipError_t launch_ingest_disks(const float *pts, const float *nrm, unsigned n, unsigned ld, int D, float radius,
+                               float *points3, float *normal3, float *disk4, unsigned long long *partials, float *bounds6,
+                               hipStream_t st);
+// host_sort_plane's histogram for resident disks: hist512 = 256 slice areas, then 256 slice area x coordinate sums;
+// partials: sort_plane_partials_entries() doubles of scratch
+size_t sort_plane_partials_entries();
+hipError_t launch_sort_plane(const float *disk4, const float *normal3, unsigned n, int axis, float lo, float hi,
+                             double *partials, double *hist512, hipStream_t st);
 // post-processing on the device (vr_setup.hip)
 hipError_t launch_disk_areas(const float *disk4, const float *normal3, unsigned n, const AreaParams &p, float *out,
                              hipStream_t st);

@@ -1174,4 +1174,214 @@ hipError_t launch_setup_neighbors(const SetupParams &s, int pass, hipStream_t st
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Device-resident disk geometry (vr_set_disks_device): the caller's rows are already in HBM, so what host_set_disks
+// and host_sort_plane do in host threads is done here — the packed copies the builder reads, the bounding box and the
+// sort-plane histogram.  What comes back to the host: six floats at set time, 512 doubles at prepare time.
+// ---------------------------------------------------------------------------
+// Key of a coordinate for the box reductions.  The host loop (host_set_disks) keeps the FIRST row among equal values
+// (std::min / std::max replace on a strict compare, threads merged in index order), and -0 == +0: which zero it ends with
+// depends on the row order.  So the high word orders by value with both zeros folded into one, and the low word makes
+// the lowest row index win among equals and carries that row's sign bit (rows < 2^27).  NaNs never win a compare on the
+// host: they map to the identity here.
+constexpr u64 kMinIdentity = ((u64)0xFF7FFFFFu << 32) | 0xFFFFFFFFull; // f2ord(FLT_MAX), behind every row
+constexpr u64 kMaxIdentity = ((u64)0x00800000u << 32);                 // f2ord(-FLT_MAX), behind every row
+__device__ __forceinline__ u64 box_min_key(float v, unsigned row) {
+  if (!(v == v))
+    return kMinIdentity;
+  const u64 sign = __float_as_uint(v) >> 31;
+  return ((u64)f2ord(v == 0.f ? 0.f : v) << 32) | ((u64)row << 1) | sign;
+}
+__device__ __forceinline__ u64 box_max_key(float v, unsigned row) {
+  if (!(v == v))
+    return kMaxIdentity;
+  const u64 sign = __float_as_uint(v) >> 31;
+  return ((u64)f2ord(v == 0.f ? 0.f : v) << 32) | ((u64)(0x7FFFFFFFu - row) << 1) | sign;
+}
+__device__ __forceinline__ float box_key_value(u64 key) {
+  const float v = ord2f((unsigned)(key >> 32));
+  return (v == 0.f && (key & 1ull)) ? -0.f : v;
+}
+__device__ __forceinline__ u64 wave_min_u64(u64 v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64 o = __shfl_down(v, off, 64);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+__device__ __forceinline__ u64 wave_max_u64(u64 v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64 o = __shfl_down(v, off, 64);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+constexpr unsigned INGEST_ROWS = 256;        // rows per tile = threads per block
+constexpr unsigned INGEST_MAX_BLOCKS = 1024; // grid-stride over the tiles; one set of six partial keys per block
+
+// One pass over the caller's rows (ld = 2 or 3 floats each; ld == 2 only with D == 2).  A tile of 256 rows is read as
+// the flat run of floats it is (consecutive lanes, consecutive addresses, whatever ld), staged in LDS, and written the
+// same way as packed rows of 3 with the z column zeroed for D == 2: points3 / normal3 are what host_set_disks makes,
+// disk4 what disk4_kernel makes of points3.  The box of the first D columns is reduced per wave, per block, and left as
+// six keys per block for ingest_bounds_kernel.
+__global__ __launch_bounds__(256) void ingest_disks_kernel(const float *pts, const float *nrm, unsigned n, unsigned ld,
+                                                           int D, float radius, float *points3, float *normal3,
+                                                           float4 *disk4, u64 *partials) {
+  __shared__ float sp[INGEST_ROWS * 3], sn[INGEST_ROWS * 3];
+  __shared__ u64 red[4][6];
+  u64 kmin[3] = {kMinIdentity, kMinIdentity, kMinIdentity}, kmax[3] = {kMaxIdentity, kMaxIdentity, kMaxIdentity};
+  const unsigned tiles = (n + INGEST_ROWS - 1) / INGEST_ROWS;
+  for (unsigned t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const unsigned row0 = t * INGEST_ROWS, rows = min(INGEST_ROWS, n - row0);
+    const size_t in0 = (size_t)row0 * ld, out0 = (size_t)row0 * 3;
+    for (unsigned j = threadIdx.x; j < rows * ld; j += INGEST_ROWS) {
+      sp[j] = pts[in0 + j];
+      sn[j] = nrm[in0 + j];
+    }
+    __syncthreads();
+    for (unsigned j = threadIdx.x; j < rows * 3; j += INGEST_ROWS) {
+      const unsigned r = j / 3, col = j - 3 * r;
+      const bool zero = col == 2 && D == 2; // (covers ld == 2: it comes with D == 2 only)
+      points3[out0 + j] = zero ? 0.f : sp[r * ld + col];
+      normal3[out0 + j] = zero ? 0.f : sn[r * ld + col];
+    }
+    if (threadIdx.x < rows) {
+      const unsigned r = threadIdx.x, row = row0 + r;
+      const float x = sp[r * ld], y = sp[r * ld + 1], z = D == 2 ? 0.f : sp[r * ld + 2];
+      disk4[row] = make_float4(x, y, z, radius);
+      const float p[3] = {x, y, z};
+      for (int k = 0; k < D; ++k) {
+        const u64 a = box_min_key(p[k], row), b = box_max_key(p[k], row);
+        kmin[k] = a < kmin[k] ? a : kmin[k];
+        kmax[k] = b > kmax[k] ? b : kmax[k];
+      }
+    }
+    __syncthreads(); // (the next tile overwrites the staging)
+  }
+  for (int k = 0; k < 3; ++k) {
+    const u64 a = wave_min_u64(kmin[k]), b = wave_max_u64(kmax[k]);
+    if ((threadIdx.x & 63) == 0) {
+      red[threadIdx.x >> 6][k] = a;
+      red[threadIdx.x >> 6][3 + k] = b;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    u64 v = red[0][threadIdx.x];
+    for (int w = 1; w < 4; ++w) {
+      const u64 o = red[w][threadIdx.x];
+      v = threadIdx.x < 3 ? (o < v ? o : v) : (o > v ? o : v);
+    }
+    partials[6 * (size_t)blockIdx.x + threadIdx.x] = v;
+  }
+}
+
+// block k (one wave) merges key k of every block of ingest_disks_kernel: bounds6 = {min xyz, max xyz} as floats
+__global__ __launch_bounds__(64) void ingest_bounds_kernel(const u64 *partials, unsigned blocks, float *bounds6) {
+  const unsigned k = blockIdx.x;
+  u64 v = k < 3 ? kMinIdentity : kMaxIdentity;
+  for (unsigned b = threadIdx.x; b < blocks; b += 64) {
+    const u64 o = partials[6 * (size_t)b + k];
+    v = k < 3 ? (o < v ? o : v) : (o > v ? o : v);
+  }
+  v = k < 3 ? wave_min_u64(v) : wave_max_u64(v);
+  if (threadIdx.x == 0)
+    bounds6[k] = box_key_value(v);
+}
+
+size_t ingest_partials_entries() { return 6 * (size_t)INGEST_MAX_BLOCKS; }
+
+hipError_t launch_ingest_disks(const float *pts, const float *nrm, unsigned n, unsigned ld, int D, float radius,
+                               float *points3, float *normal3, float *disk4, unsigned long long *partials, float *bounds6,
+                               hipStream_t st) {
+  const unsigned tiles = (n + INGEST_ROWS - 1) / INGEST_ROWS;
+  const unsigned blocks = tiles < INGEST_MAX_BLOCKS ? tiles : INGEST_MAX_BLOCKS;
+  if (blocks)
+    hipLaunchKernelGGL(ingest_disks_kernel, dim3(blocks), dim3(INGEST_ROWS), 0, st, pts, nrm, n, ld, D, radius, points3,
+                       normal3, reinterpret_cast<float4 *>(disk4), partials);
+  hipLaunchKernelGGL(ingest_bounds_kernel, dim3(6), dim3(64), 0, st, partials, blocks, bounds6); // (no rows: the identities)
+  return hipGetLastError();
+}
+
+// host_sort_plane for disks: 256 slices of [lo, hi] on the sort axis, each disk adds the area it shows the source
+// (r^2 |n_axis| / |n|) and that area times its coordinate, in double.  Double sums depend on their order, so the order is
+// fixed: a block takes one contiguous range of disks, a wave its 64-disk runs in turn; within a run the lanes of one
+// slice are summed by a butterfly (the same tree on every run) and added once to the wave's own LDS histogram; the
+// waves, then the blocks (sort_plane_merge_kernel), are merged in index order.  The same input gives the same bits.
+constexpr int SORT_SLICES = 256;
+constexpr unsigned SORT_MAX_BLOCKS = 256;
+__global__ __launch_bounds__(256) void sort_plane_kernel(const float4 *disk4, const float *normal3, unsigned n, int axis,
+                                                         float lo, float hi, double *partials) {
+  __shared__ double hw[4][SORT_SLICES], hwh[4][SORT_SLICES];
+  for (unsigned j = threadIdx.x; j < 4 * SORT_SLICES; j += 256) {
+    (&hw[0][0])[j] = 0.;
+    (&hwh[0][0])[j] = 0.;
+  }
+  __syncthreads();
+  const double inv = SORT_SLICES / ((double)hi - (double)lo);
+  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned perBlock = (((n + gridDim.x - 1) / gridDim.x) + 255u) & ~255u;
+  const unsigned begin = min(n, blockIdx.x * perBlock), end = min(n, begin + perBlock);
+  for (unsigned base = begin + wave * 64; base < end; base += 256) { // (wave-uniform)
+    const unsigned i = base + lane;
+    const bool valid = i < end;
+    int k = -1;
+    double a = 0., ah = 0.;
+    if (valid) {
+      const float4 d = disk4[i];
+      const float nx = normal3[3 * (size_t)i], ny = normal3[3 * (size_t)i + 1], nz = normal3[3 * (size_t)i + 2];
+      const double nn = sqrt((double)nx * nx + (double)ny * ny + (double)nz * nz);
+      const double h = axis == 0 ? d.x : axis == 1 ? d.y : d.z;
+      const float na = axis == 0 ? nx : axis == 1 ? ny : nz;
+      a = nn > 0. ? (double)d.w * d.w * fabs((double)na) / nn : 0.;
+      ah = a * h;
+      k = (int)((h - lo) * inv);
+      k = k < 0 ? 0 : (k >= SORT_SLICES ? SORT_SLICES - 1 : k);
+    }
+    u64 todo = __ballot(valid);
+    while (todo) { // one slice per turn, lowest waiting lane first
+      const int kk = __shfl(k, __ffsll((long long)todo) - 1, 64);
+      const bool mine = valid && k == kk;
+      double sa = mine ? a : 0., sah = mine ? ah : 0.;
+      for (int off = 32; off > 0; off >>= 1) {
+        sa += __shfl_xor(sa, off, 64);
+        sah += __shfl_xor(sah, off, 64);
+      }
+      if (lane == 0) {
+        hw[wave][kk] += sa;
+        hwh[wave][kk] += sah;
+      }
+      todo &= ~__ballot(mine);
+    }
+  }
+  __syncthreads();
+  const unsigned j = threadIdx.x; // (256 threads = SORT_SLICES)
+  partials[(2 * (size_t)blockIdx.x) * SORT_SLICES + j] = ((hw[0][j] + hw[1][j]) + hw[2][j]) + hw[3][j];
+  partials[(2 * (size_t)blockIdx.x + 1) * SORT_SLICES + j] = ((hwh[0][j] + hwh[1][j]) + hwh[2][j]) + hwh[3][j];
+}
+
+// hist[0 .. 255] = area per slice, hist[256 .. 511] = area x coordinate per slice: the blocks' partials in block order
+__global__ __launch_bounds__(256) void sort_plane_merge_kernel(const double *partials, unsigned blocks, double *hist) {
+  const unsigned j = blockIdx.x * 256 + threadIdx.x; // < 2 * SORT_SLICES
+  double s = 0.;
+  for (unsigned b = 0; b < blocks; ++b)
+    s += partials[(2 * (size_t)b) * SORT_SLICES + j];
+  hist[j] = s;
+}
+
+size_t sort_plane_partials_entries() { return 2 * (size_t)SORT_SLICES * SORT_MAX_BLOCKS; }
+
+hipError_t launch_sort_plane(const float *disk4, const float *normal3, unsigned n, int axis, float lo, float hi,
+                             double *partials, double *hist512, hipStream_t st) {
+  if (n == 0)
+    return hipSuccess;
+  const unsigned tiles = (n + 255) / 256;
+  const unsigned blocks = tiles < SORT_MAX_BLOCKS ? tiles : SORT_MAX_BLOCKS;
+  hipLaunchKernelGGL(sort_plane_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float4 *>(disk4), normal3, n,
+                     axis, lo, hi, partials);
+  hipLaunchKernelGGL(sort_plane_merge_kernel, dim3(2), dim3(256), 0, st, partials, blocks, hist512);
+  return hipGetLastError();
+}
+
 } // namespace vr

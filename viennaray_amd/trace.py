@@ -253,6 +253,11 @@ def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _is_device_tensor(x):
+    """a torch tensor in device memory, by duck typing (this module does not import torch)"""
+    return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+
+
 class Trace:
     """rayTrace.hpp:15-180 (NumericType = float)."""
 
@@ -264,6 +269,7 @@ class Trace:
         if rc != capi.VR_OK:
             raise VrError("vr_create failed: no usable HIP device (the accelerated path has no CPU fallback)")
         self._h = h
+        self._device = int(device)
         self._particle = None
         self._localData = TracingData()
         self._n = 0
@@ -468,12 +474,15 @@ class Trace:
         self._check(self._L.vr_set_world_size(self._h, int(world)))
 
     # --- run ---------------------------------------------------------------
-    def apply(self):
+    def apply(self, collect=True):
+        """collect=False leaves the flux on the device (getFluxTensor / getFluxNormalized fetch it): getLocalData() is
+        not filled"""
         if self._particle is None:
             # checkSettings (rayTraceDisk.hpp:197-200)
             raise VrError("No particle was specified in rayTrace. Aborting.")
         self._check(self._L.vr_apply(self._h))
-        self._collect()
+        if collect:
+            self._collect()
 
     def applySharded(self, rank, world, reduce_fn=None, user=None):
         """vr_apply_sharded: this rank's share of the rays, then `reduce_fn(user, devPtr, count, stream)` (a
@@ -534,6 +543,20 @@ class Trace:
         """raw flux -> normalizeFlux fused on the device (one download)"""
         out = np.empty(self._n, dtype=np.float32)
         self._check(self._L.vr_get_flux_normalized(self._h, _fptr(out), self._n, int(norm)))
+        return out
+
+    def getFluxTensor(self, dataIdx=0, norm=None, numNeighbors=0):
+        """The flux of data label `dataIdx` as a new torch.float32 tensor on the context's device, in the caller's
+        primitive order: raw (norm=None) or normalizeFlux(norm), then smoothFlux(numNeighbors) if numNeighbors > 0 —
+        computed and left on the device (vr_get_flux_device), ordered on the current torch stream: no host copy, and
+        without smoothing no synchronisation."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        out = torch.empty(self._n, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._L.vr_get_flux_device(self._h, int(dataIdx), C.c_void_p(out.data_ptr()), self._n,
+                                               capi.VR_NORM_NONE if norm is None else int(norm), int(numNeighbors),
+                                               C.c_void_p(stream)))
         return out
 
     def smoothFlux(self, flux, numNeighbors=1):
@@ -690,6 +713,12 @@ class TraceDisk(Trace):
     """rayTraceDisk.hpp:13-224"""
 
     def setGeometry(self, points, normals, gridDelta, diskRadius=0.0):
+        """points / normals: [n, 2] or [n, 3].  Two torch tensors on the context's device (float32, contiguous) are
+        handed over where they are (vr_set_disks_device): the library copies them on the device, ordered behind the
+        current torch stream, and the tensors may be overwritten as soon as this returns.  A tensor on a device that
+        cannot go that way raises ValueError — it is never copied through the host behind the caller's back."""
+        if _is_device_tensor(points) or _is_device_tensor(normals):
+            return self._setGeometryDevice(points, normals, gridDelta, diskRadius)
         p = np.ascontiguousarray(points, dtype=np.float32)
         n = np.ascontiguousarray(normals, dtype=np.float32)
         if p.shape[1] == 2:  # 2-D points: z := 0 (rayGeometryDisk.hpp:148-151)
@@ -701,6 +730,30 @@ class TraceDisk(Trace):
         self._n = p.shape[0]
         self._check(self._L.vr_set_disks(self._h, _fptr(p), _fptr(n), self._n, float(gridDelta),
                                          float(diskRadius), self.D))
+
+    def _setGeometryDevice(self, points, normals, gridDelta, diskRadius):
+        for name, x in (("points", points), ("normals", normals)):
+            if not _is_device_tensor(x):
+                raise ValueError(f"setGeometry: device: {name} is not a device tensor while the other argument is "
+                                 "(both on the device, or both on the host)")
+            if x.device.index != self._device:
+                raise ValueError(f"setGeometry: device: {name} is on {x.device}, the tracer on device {self._device}")
+            if str(x.dtype) != "torch.float32":
+                raise ValueError(f"setGeometry: dtype: {name} is {x.dtype}, device tensors must be torch.float32")
+            if x.dim() != 2 or x.shape[1] not in (2, 3):
+                raise ValueError(f"setGeometry: shape: {name} is {tuple(x.shape)}, expected [n, 2] or [n, 3]")
+            if x.shape[1] == 2 and self.D != 2:
+                raise ValueError(f"setGeometry: shape: {name} has 2 columns, a {self.D}-D tracer needs [n, 3]")
+            if not x.is_contiguous():
+                raise ValueError(f"setGeometry: contiguity: {name} is not contiguous (strides {tuple(x.stride())})")
+        if tuple(points.shape) != tuple(normals.shape):
+            raise ValueError(f"setGeometry: shape: points {tuple(points.shape)} and normals {tuple(normals.shape)} differ")
+        import torch
+        stream = torch.cuda.current_stream(points.device).cuda_stream
+        n, ld = int(points.shape[0]), int(points.shape[1])
+        self._check(self._L.vr_set_disks_device(self._h, C.c_void_p(points.data_ptr()), C.c_void_p(normals.data_ptr()),
+                                                n, ld, float(gridDelta), float(diskRadius), self.D, C.c_void_p(stream)))
+        self._n = n
 
     def getDiskAreas(self):
         out = np.empty(self._n, dtype=np.float32)
