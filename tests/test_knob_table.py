@@ -1,4 +1,4 @@
-"""The knob table (viennaray_amd/csrc/vr_api.cpp: struct Knobs, read_knobs).
+"""The knob table (viennaray_amd/csrc: struct Knobs in vr_context.hpp, read_knobs in vr_knobs.cpp).
 
 Every tuning or experiment switch of the library is read from the environment in read_knobs and nowhere else, and every
 switch the tests set is one read_knobs reads: a switch that a change silently dropped would leave the tests that set it
@@ -24,9 +24,9 @@ def _sources():
 
 
 def _read_knobs_body():
-    with open(os.path.join(CSRC, "vr_api.cpp")) as f:
+    with open(os.path.join(CSRC, "vr_knobs.cpp")) as f:
         text = f.read()
-    start = text.index("{", text.index("static Knobs read_knobs()"))
+    start = text.index("{", text.index("Knobs read_knobs()"))
     depth = 0
     for k in range(start, len(text)):
         depth += {"{": 1, "}": -1}.get(text[k], 0)
@@ -53,7 +53,7 @@ def test_getenv_only_in_read_knobs_and_model_registration():
     for name in re.findall(r"getenv\s*\(([^)]*)\)", body):
         assert re.fullmatch(r'"VR_[A-Z0-9_]+"', name.strip()), f"read_knobs reads getenv({name}): a literal VR_ name expected"
     for path, text in _sources():
-        if os.path.basename(path) == "vr_api.cpp":
+        if os.path.basename(path) == "vr_knobs.cpp":
             text = text.replace(body, "")
         for arg in re.findall(r"getenv\s*\(([^)]*)\)", text):
             lit = re.fullmatch(r'"([A-Za-z0-9_]+)"', arg.strip())

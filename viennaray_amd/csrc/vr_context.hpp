@@ -1,0 +1,402 @@
+// vr_context.hpp — private to the translation units of the C ABI (vr_api.cpp names them): the context behind
+// include/viennaray_amd.h, the types its fields are made of, and the few functions more than one of those files uses.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cstdint>
+#include <map>
+#include <optional>
+#include <string>
+#include <vector>
+
+#include "../../include/viennaray_amd.h"
+#include "vr_host.hpp"
+#include "vr_kernels.hpp"
+#include "vr_types.hpp"
+
+namespace vr {
+
+template <class T> struct DevBuf {
+  T *p = nullptr;
+  size_t cap = 0;
+  hipError_t ensure(size_t n) {
+    if (n <= cap && p)
+      return hipSuccess;
+    if (p)
+      (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e == hipSuccess)
+      cap = std::max<size_t>(n, 1);
+    return e;
+  }
+  // buffers whose size follows the ray count of an apply(): grown by half again, so a simulation whose
+  // ray count creeps up from step to step re-allocates O(log) times, not every step (hipMalloc of a
+  // multi-GB ray stream costs tens of ms)
+  hipError_t ensure_grow(size_t n) {
+    if (n <= cap && p)
+      return hipSuccess;
+    const size_t want = std::max(n, cap + cap / 2);
+    hipError_t e = ensure(want);
+    if (e != hipSuccess && want > n) { // (no room for the head-room: the exact size)
+      (void)hipGetLastError();
+      e = ensure(n);
+    }
+    return e;
+  }
+  // ensure(n), then n elements up from the host
+  hipError_t upload(const T *src, size_t n) {
+    const hipError_t e = ensure(n);
+    return e != hipSuccess ? e : hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
+  }
+  // n elements down to the host
+  hipError_t download(T *dst, size_t n) const { return hipMemcpy(dst, p, n * sizeof(T), hipMemcpyDeviceToHost); }
+  void release() {
+    if (p)
+      (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      std::swap(p, o.p);
+      std::swap(cap, o.cap);
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); } // (vr_destroy selects the device before the context goes away)
+};
+
+// Every tuning and experiment switch of the library, read from the environment in ONE place (read_knobs): an apply
+// reads them once, at vr_apply_prepare, into vr_context::knobs.  Unless its line says RESULTS, a switch only moves work
+// around: the flux and the TraceInfo counters stay bit-exact (tests/test_gpu_parity.py).  (VR_CSRC_DIR / VR_HIPCC /
+// VR_CACHE_DIR are configuration of vr_register_particle_model, read there.)
+struct Knobs {
+  // scene build
+  std::optional<uint32_t> accReplicas; // VR_ACC_REPLICAS: flux accumulator replicas, >= 1, rounded down to a power of two (unset: by scene size)
+  bool hostBuild = false;              // VR_HOST_BUILD (non-zero): LBVH, neighbourhood and disk areas on the host (validation path)
+  std::optional<uint32_t> leafMax;     // VR_LEAF_MAX [1, 15]: primitives per BVH leaf (unset: VR_LEAF_MAX disks, 3 triangles)
+  bool noChildOrder = false;           // VR_NO_CHILD_ORDER (non-zero): BVH children not ordered source side first
+  float mortonAniso = VR_MORTON_ANISO; // VR_MORTON_ANISO >= 1: largest aspect ratio of the Morton grid's cells
+  bool nbTwoPass = false;              // VR_NB_TWO_PASS (set): the neighbourhood query in two passes (count, fill)
+  // kernel choice
+  bool smallScene = true;              // VR_SMALL_SCENE (0: off): small scenes resident in LDS (MODE 4)
+  bool noRelief = false;               // VR_NO_RELIEF (set): no relief packets (MODE 5 / 6) on flat scenes with relief
+  float reliefMaxThick = 8.f;          // VR_RELIEF_MAX_THICK: thickest scene (grid cells along the source axis) for relief packets
+  float reliefTravel = 1.5f;           // VR_RELIEF_TRAVEL >= 0.05: a ray is loose when thickness x tan(theta) exceeds this (grid cells)
+  float reliefTile = 1.f;              // VR_RELIEF_TILE >= 0.25: fine relief tile side in grid cells
+  std::optional<int> reliefCoarseK;    // VR_RELIEF_COARSE_K >= 1: fine tiles per coarse tile side (unset: by field size)
+  float reliefShare = 0.3f;            // VR_RELIEF_SHARE: largest predicted share of loose rays for relief packets
+  float reliefSteps = 6.f;             // VR_RELIEF_STEPS >= 1: a ray crossing more tiles through the scene box is loose
+  int reliefLookups = 1;               // VR_RELIEF_LOOKUPS [0, 2]: coarse look-ups of the generator's hit prediction
+  bool noSpill = false;                // VR_NO_SPILL (set): the tight general relief kernel keeps its continuing rays
+  std::optional<bool> generalFlat;     // VR_GENERAL_FLAT (set): packet-query crediting in the general kernel on (non-zero) / off
+  std::optional<bool> absorbCarry;     // VR_ABSORB_CARRY (set): absorbing kernel with (non-zero) / without straggler carry-over
+  std::optional<int> traceBlocks;      // VR_TRACE_BLOCKS >= 1: blocks per CU of the trace launch (unset: by occupancy and rays)
+  std::optional<int> looseBlocks;      // VR_LOOSE_BLOCKS >= 1: ... of a relief scene's loose launch
+  // ray stream
+  std::optional<uint64_t> batchRays;   // VR_BATCH_RAYS >= 256: rays per batch (unset: 2^27)
+  uint32_t binCap = VR_BIN_CAP;        // VR_BIN_CAP >= 8: record slots per sort bin
+  uint32_t raysPerBin = 40;            // VR_RAYS_PER_BIN >= 1: rays per sort bin the grid is sized for
+  std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
+  std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
+  // kernel parameters (TraceParams)
+  uint32_t pqFrontier = 12;            // VR_PQ_FRONTIER [1, 24]: packet query gives up beyond this frontier
+  uint32_t pqCand = 24;                // VR_PQ_CAND [1, 24]: ... or beyond this many candidates
+  float pqMargin = 1.5f;               // VR_PQ_MARGIN >= 0: packet query's frontier-cache margin (units of 2 r / 1.7 cells)
+  std::optional<float> keyCoord;       // VR_KEY_COORD: sort plane of the ray stream (unset: host_sort_plane)
+  uint32_t packetBudget = 128;         // VR_PACKET_BUDGET >= 0: node visits of a packet traversal
+  std::optional<uint32_t> walkPark;    // VR_WALK_PARK [1, 100]: % of parked lanes that tests the leaves (unset: 25 disks, 10 triangles)
+  uint32_t walkExit = 16;              // VR_WALK_EXIT [1, 64]: a round's walk ends below this many walking lanes
+  uint32_t packetRatio = 3;            // VR_PACKET_RATIO >= 1: packet traversal gives up beyond ratio x mean path
+  uint32_t debugFlags = 0;             // VR_DEBUG_FLAGS: kernel experiment bits; many of them change RESULTS
+  bool noHeightField = false;          // VR_NO_HEIGHT_FIELD (set): no height field over the source plane
+  float hfTile = 4.f;                  // VR_HF_TILE >= 0.25: height-field tile side in grid cells
+  // diagnostics
+  bool printLaunches = false;          // VR_PRINT_LAUNCHES (set): trace-launch times and spilled rays on stderr
+  bool hostSmooth = false;             // VR_HOST_SMOOTH (set): vr_smooth_flux on the host
+  bool debugWalk = true;               // VR_DEBUG_WALK (0: the escape-link walk): vr_debug_intersect's walk
+  bool logPlainAtomics = false;        // VR_LOG_PLAIN_ATOMICS (set): the data log without its per-block LDS copy (A/B of DESIGN.md 8c)
+#ifdef VR_DIAG
+  bool skipTight = false;              // VR_SKIP_TIGHT (set): a relief scene's loose launch alone; INCOMPLETE results
+  bool skipLoose = false;              // VR_SKIP_LOOSE (set): ... its tight launch alone; INCOMPLETE results
+#endif
+};
+
+// one entry of vr_set_particles (a deep copy of the caller's vr_particle)
+struct ParticleSpec {
+  int kind = 0;
+  float sticking = 1.f, sourcePower = 1.f, coneAngle = 0.f, meanFreePath = -1.f;
+  float params[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int userModel = -1; // kind >= VR_PARTICLE_USER_BASE: index of the run-time model
+  std::vector<int32_t> matIds;
+  std::vector<float> matVals;
+};
+// a particle model registered at run time (vr_register_particle_model): its own code object with the extended trace
+// kernels, the model compiled in as entry VR_BUILTIN_MODELS of that module's registry
+struct UserModel {
+  std::string name;
+  hipModule_t module = nullptr;
+  int numData = 1;
+  bool needsFull = false;
+  int numState = 0;                     // kStateWords of a stateful model (0: stateless)
+  int logRows = 0;                      // kLogRows: rows of the data log its log_data hook writes (0: no hook)
+  std::map<int, hipFunction_t> kernels; // key: D * 100 + geo * 10 + mode
+  hipFunction_t gen[2] = {nullptr, nullptr}; // a stateful model's generator (gen_state_kernel), 2-D / 3-D
+};
+
+// The prepared launch of one particle of an apply() (vr_context::launches: one per particle of vr_set_particles).
+// params holds everything but the buffers all particles share — ray stream, scratch, counters, accumulators — whose
+// addresses launch_params adds when the launch runs.
+struct ParticleLaunch {
+  TraceParams params{};
+  uint32_t slot = 0;     // index of the particle: its counter block, wall-table / frame slot
+  uint32_t dataBase = 0; // its first accumulator plane
+  unsigned grid = 0;
+  int traceMode = 0, kernelParticle = 0;
+  bool absorb = false;
+  bool recExtra = false; // the records' side array (TraceParams::recExtra)
+  hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
+  hipFunction_t userGen = nullptr;    // ... and a stateful model's generator (nullptr: the library's)
+  DevBuf<float> primSticking;         // this particle's per-primitive sticking, leaf order (params.primSticking, or unused)
+  bool relief = false; // flat with relief: a second launch (looseMode, looseGrid) traces the loose bins
+  int looseMode = 0;
+  unsigned looseGrid = 0;
+  vr_trace_info info{};
+};
+
+} // namespace vr
+
+using namespace vr; // (struct vr_context is declared at global scope by the public header)
+
+struct vr_context {
+  int device = 0;
+  int numCUs = 256;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::string err;
+
+  HostGeometry geo;
+  bool geometryDirty = true; // BVH / uploads need rebuilding
+  bool configDirty = true;   // bbox / walls / areas / sticking map need recomputing
+  Bvh bvh;
+  std::vector<uint32_t> leafOfOrig;
+  std::vector<float> diskAreas;       // host mirror of dAreas (disks), downloaded on demand
+  bool diskAreasHostValid = false;
+
+  // Trace<T,D> configuration (rayTrace.hpp:157-179, rayUtil.hpp:83-94)
+  int bcs[3] = {0, 0, 0};
+  int sourceDirection = -1; // -1: default by D (POS_Y for 2-D, POS_Z for 3-D)
+  bool usePrimaryDirection = false;
+  float primaryDirection[3] = {0, 0, 0};
+  bool haveParticle = false;
+  int particleKind = 0;
+  float coneAngle = 0.f, meanFreePath = -1.f;
+  bool useWdist = false;
+  uint32_t numData = 1;           // data labels of the (active) particle
+  uint32_t totalData = 1;         // ... of all particles of the apply: accumulator planes, TracingData vectors
+  uint32_t accPlanes = 0;         // planes the accumulator buffers currently hold
+  float particleParams[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int userModel = -1;             // index into userModels when the active particle is a run-time model
+  DevBuf<float> dRayState;            // a stateful model's per-ray state of one batch (the frame's VR_F_STATE_*), float4 per ray
+  DevBuf<int32_t> dPrimMaterial;      // material id per original primitive for a stateful model (VR_F_MAT_*)
+  // the data log (vr_set_data_log_shape): int64 sums of the log_data hooks, rows concatenated, the control words behind
+  // them (VR_LOG_*, vr_device.hpp); zeroed at every launch, summed over the batches and particles of an apply on the device
+  std::vector<uint32_t> logRowSizes;
+  uint32_t logTotal = 0;              // entries of all rows
+  bool logActive = false;             // the prepared apply fills the log (a shape is set)
+  DevBuf<unsigned long long> dDataLog;
+  std::vector<unsigned long long> logCtlHost; // staging of the control words' upload
+  std::vector<unsigned long long> logHost;    // the last apply's sums + [dropped] (vr_get_data_log*)
+  bool haveLog = false;
+  std::vector<UserModel> userModels;
+  bool particleDirty = true;      // the sticking map needs recomputing
+  std::vector<ParticleSpec> specs;      // vr_set_particles: > 1 entries = a multi-particle apply
+  std::vector<ParticleLaunch> launches; // prepared by vr_apply_prepare: one per particle (at least one)
+  Knobs knobs;                          // the tuning switches, read by vr_apply_prepare
+  // Trace::setGlobalData: vectors (padded to one stride) and scalars, resident in HBM
+  std::vector<std::vector<float>> globalVecs;
+  std::vector<float> globalScalars;
+  bool globalDirty = false;
+  uint32_t globalStride = 0;
+  DevBuf<float> dGlobalVec, dGlobalScalars;
+  // sources other than SourceRandom
+  std::vector<float> gridPoints;  // SourceGrid origins (raySourceGrid.hpp)
+  std::vector<float> hostOrg, hostDir;
+  std::vector<uint32_t> hostDraws;
+  std::vector<float> hostWeights;  // Source::getInitialRayWeight(idx) of the host rays (empty: 1)
+  float sourceAreaOverride = 0.f;  // Source::getSourceArea() of a user source (<= 0: SourceRandom's, the bbox face)
+  // surface source (vr_set_surface_source): the tables live on the device, uploaded when they are set
+  uint32_t surfCount = 0;          // source points (0: no surface source)
+  float surfArea = 0.f, surfOffset = 0.f;
+  DevBuf<float> dSurfPos, dSurfNrm, dSurfWeights;
+  DevBuf<float> dSurfRayWeights;   // start weight of every ray of one batch (TraceParams::hostWeights of a surface source)
+  uint64_t reserveRays = 0;        // vr_reserve_rays: the ray-stream buffers hold at least this many rays
+  bool sourceDirty = false;
+  DevBuf<float> dGrid, dHostOrg, dHostDir, dHostWeights;
+  DevBuf<uint32_t> dHostDraws;
+  float sticking = 1.f, sourcePower = 1.f;
+  std::vector<int32_t> matStickIds;
+  std::vector<float> matStickVals;
+  uint64_t numRaysPerPoint = 1000, numRaysFixed = 0;
+  uint32_t maxReflections = 0xFFFFFFFFu, maxBoundaryHits = 1000;
+  uint32_t rngSeed = 0;
+  bool useRandomSeed = true;
+  uint32_t runNumber = 1;
+  uint64_t rayFirst = 0, rayCount = 0;
+  bool haveSharedSeed = false; // vr_apply_sharded + useRandomSeed: rank 0's draw, handed round by the all-reduce;
+                               // a multi-particle apply with random seeds: its one draw
+  bool keepSharedSeed = false; // (the sharded entry point clears the seed itself)
+  size_t numGenLaunches = 0, numTraceLaunches = 0;
+  uint32_t sharedSeed = 0;
+
+  // derived at prepare()
+  float bbLo[3], bbHi[3];
+  std::array<int, 5> ts{};
+  int boundaryConds[2] = {0, 0};
+  float sourceArea = 0.f;
+  uint64_t numRaysLast = 0;
+  bool prepared = false, launched = false, haveResult = false;
+
+  vr_trace_info info{};
+  double buildSeconds = 0.0;
+
+  // device buffers
+  DevBuf<float> dNodes, dPrims;
+  DevBuf<float> dAreas, dFluxTmp;     // exposed area per primitive (caller's order); normalisation scratch
+  DevBuf<uint32_t> dNormMax;          // flux_max_kernel's reduction word
+  bool areasValid = false;
+  DevBuf<uint32_t> dNbOff, dNbIds, dLeafOfOrig;
+  DevBuf<uint32_t> dNbTmp; // the one-pass neighbourhood query's fixed-stride lists (build scratch)
+  uint32_t nbTotal = 0;               // entries of the resident neighbourhood CSR
+  DevBuf<unsigned long long> dFluxAcc, dFluxOrig, dCounters, dScratch;
+  DevBuf<unsigned long long> dWorkQ;  // span cursors of the trace kernel's per-XCD queues
+  size_t scratchWaves = 0;
+  // flux accumulators are replicated accReplicas times (power of two, stride accStride
+  // elements); a block credits replica blockIdx & (accReplicas-1): small scenes would
+  // otherwise serialise every credit of the chip on a handful of cache lines
+  uint32_t accReplicas = 1, accStride = 0;
+  // device-side setup (vr_setup.hip)
+  DevBuf<float> dDisk4, dNormal3, dPoints3, dVerts, dBox, dSBox, dNodeBox;
+  // The geometry's source.  vr_set_disks_device fills dPoints3 / dNormal3 / dDisk4 itself (geoOnDevice): build_scene then
+  // uploads nothing, and geo.points3 / normal3 / disk4 are a mirror that ensure_host_geometry downloads when a host path
+  // (VR_HOST_BUILD, VR_HOST_SMOOTH, a smoothing overflow) reads them.
+  bool geoOnDevice = false, hostGeoValid = false;
+  DevBuf<unsigned long long> dIngestKeys; // launch_ingest_disks' block partials
+  DevBuf<float> dIngestBounds;            // ... and its six bounds
+  DevBuf<double> dSortPlane;              // launch_sort_plane's block partials, then the 512 merged sums
+  hipEvent_t evIn = nullptr, evOut = nullptr; // hand-over between a caller's stream and this context's (device entry points)
+  DevBuf<uint32_t> dTris, dBounds, dValsA, dValsB, dSortTable, dRangeLo, dRangeHi, dChildL, dChildR, dParentInt,
+      dParentLeaf, dArrive, dOrder, dSubSize, dQNodes, dPNodes, dWalkStack;
+  size_t walkStackWaves = 0;
+  DevBuf<float> dNodesPre, dWide;
+  uint32_t wideRoot[3] = {0, 0, 0};  // 64-ary tree: root's first child, count | flag, primitive base
+  bool haveWide = false;
+  float sceneLo[3] = {0, 0, 0}, sceneHi[3] = {0, 0, 0};
+  uint32_t numNodes = 0;         // traversal nodes emitted by the builder
+  float qbase[3] = {0, 0, 0}, qscale[3] = {0, 0, 0}; // frame of the 16-byte nodes
+  float keyCoord = 0.f;          // sort plane of the ray stream on the tracing axis (host_sort_plane)
+  float keyShare = 1.f;          // share of the surface shown to the source that lies in that plane
+  SetupParams lastSetup{};       // buffers of the resident device build (vr_debug_bvh_check)
+  bool haveSetup = false;
+  int builtOrderAxis = -1;       // child order of the resident BVH (source side first)
+  int bvhRefits = 0;             // 1 if the last build had to be re-fitted with agent-scope fences
+  uint32_t bvhBuilds = 0;        // scene builds of this context
+  float builtOrderSign = 0.f;
+  DevBuf<unsigned long long> dKeysA, dKeysB;
+  bool hostOrderValid = false;   // c->bvh.order mirrors dOrder
+  bool hostNeighborsValid = false;
+  // ray stream (one batch)
+  DevBuf<float> dSlotRec, dWalls;
+  DevBuf<uint32_t> dBinCount;
+  size_t slotStride = 0; // record slots of the ray-stream buffer (bins + overflow region)
+  uint32_t raysPerBin = 40;
+  DevBuf<uint32_t> dScanTmp;
+  uint32_t batchCap = 0;      // rays per batch the buffers hold
+  uint32_t numBins = 0;
+  uint64_t rayFirstLaunch = 0, rayEndLaunch = 0;
+  float wallsHost[96] = {0};        // the eight wall triangles (made with the bounding box)
+  std::vector<float> frameHostAll;  // wall table + scalar frame of every particle of the apply (staging of their uploads)
+  // relief field over the source plane (ReliefParams): scenes that are flat with relief
+  DevBuf<uint32_t> dRfRawLo, dRfRawHi, dRfStats;
+  DevBuf<float> dRfFine, dRfCoarse;
+  ReliefParams rf{};
+  uint32_t rfBuild = 0xFFFFFFFFu;
+  int rfAxes[4] = {-1, -1, -1, -1};
+  float rfLooseShare = 1.f;
+  DevBuf<float> dSpillRec;     // the general relief kernel's spill queue (TraceParams::spillRec), 16 floats per ray of a batch
+  DevBuf<uint32_t> dSpillCount;
+  DevBuf<uint32_t> dHfRaw;    // height field over the source plane (HeightFieldParams): built for particles that reflect
+  DevBuf<float> dHf;
+  HeightFieldParams hf{};
+  uint32_t hfBuild = 0xFFFFFFFFu; // the bvhBuilds count and source frame it was made for
+  int hfAxes[4] = {-1, -1, -1, -1};
+  DevBuf<float> dRecExtra;    // the records' side array (ParticleLaunch::recExtra)
+  std::vector<hipEvent_t> evK; // trace-kernel event pairs, one per batch
+  std::vector<hipEvent_t> evG; // generator event pairs, one per batch
+  double traceKernelSeconds = 0.0;
+  uint32_t worldSize = 1;     // ranks whose accumulators will be summed (vr_set_world_size): head-room of the overflow check
+  unsigned long long *boundFlux = nullptr; // caller-owned accumulator buffer
+  uint32_t boundFluxN = 0;
+  unsigned long long *fluxOut() { return boundFlux ? boundFlux : dFluxOrig.p; }
+};
+
+#define VR_HIP(ctx, call)                                                                                              \
+  do {                                                                                                                 \
+    hipError_t e__ = (call);                                                                                           \
+    if (e__ != hipSuccess) {                                                                                           \
+      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                                                 \
+      return VR_E_HIP;                                                                                                 \
+    }                                                                                                                  \
+  } while (0)
+
+#define VR_TRY(call)                                                                                                   \
+  do {                                                                                                                 \
+    const int r__ = (call);                                                                                            \
+    if (r__ != VR_OK)                                                                                                  \
+      return r__;                                                                                                      \
+  } while (0)
+
+namespace vr {
+
+// vr_api.cpp
+int fail(vr_context *c, int code, const char *msg);
+bool is_device_memory_of(const void *p, int device);
+int wait_for_caller(vr_context *c, hipStream_t stream);
+int caller_waits(vr_context *c, hipStream_t stream);
+void activate_particle(vr_context *c, const ParticleSpec &sp);
+// vr_knobs.cpp
+Knobs read_knobs();
+// vr_scene.cpp
+int ensure_host_geometry(vr_context *c);
+int ensure_host_order(vr_context *c);
+int ensure_host_neighbors(vr_context *c);
+int build_scene(vr_context *c);
+// vr_prepare.cpp
+uint64_t rays_of_apply(const vr_context *c);
+void size_bins(int D, uint64_t count, uint32_t perBin, TraceParams &p, uint32_t &numBins);
+void size_loose(int D, TraceParams &p);
+// vr_apply.cpp
+const ParticleLaunch &current_launch(const vr_context *c);
+TraceParams launch_params(const vr_context *c, const ParticleLaunch &L);
+
+// head-room bits of the overflow checks: the sums of `worldSize` ranks (vr_set_world_size) must still fit a signed int64
+inline unsigned rank_headroom(uint32_t worldSize) {
+  unsigned bits = 0;
+  while ((1u << bits) < worldSize)
+    ++bits;
+  return bits;
+}
+
+} // namespace vr

@@ -369,7 +369,7 @@ __device__ __forceinline__ void hit_clear(HitRec &h) {
 // the surface long before they could reach a wall plane, and for those the (long)
 // triangle tests are skipped.  A wall wins against geometry at equal t (closest-hit rule:
 // boundary first); among walls the lower id wins.
-// The launch's scalar frame, staged behind the walls in the kernels' LDS table (vr_api.cpp fills it at every prepare).
+// The launch's scalar frame, staged behind the walls in the kernels' LDS table (vr_prepare.cpp fills it at every prepare).
 // Loop-invariant kernel arguments are hoisted and held in SGPRs throughout; the spilled ones come back by v_readlane
 // at every use.  The compact ray records' decode (vr_trace.hip) reads its four scalars from here in every kernel; the
 // absorbing flat-scene kernel (8 waves per SIMD, 78 spilled SGPRs) also its wall and scene-box frame: the *_lds
@@ -1065,7 +1065,7 @@ struct PqCands {
   bool box;       // KEEPQ: records VR_PQ_BOX, + 1 hold the query's box (false: no ray reached the scene, nothing stored)
   unsigned mine;  // per lane: the candidate that is this lane's closest hit so far (valid where the hit came from the query)
 };
-constexpr unsigned VR_PQ_CANDS = 52; // >= 2 * pqMaxCand + 1 (pqMaxCand <= 24, vr_api.cpp) + the two records below
+constexpr unsigned VR_PQ_CANDS = 52; // >= 2 * pqMaxCand + 1 (pqMaxCand <= 24, vr_knobs.cpp) + the two records below
 // KEEPQ: records 50 / 51 keep the query's (padded) box {lo.xyz, -}{hi.xyz, -} for the round's follow-up segments
 // (trace_kernel, "follow-up segments"); PqCands::box says whether there is one (stored as an "empty box", two constant
 // 16-byte tuples were hoisted out of the round loop, spilled, and reloaded from scratch in every round)

@@ -1,0 +1,392 @@
+// vr_results.cpp — what an apply() left behind: flux, TraceInfo and the data log; normalizeFlux / smoothFlux; areas,
+// bounding box and neighbour counts of the geometry.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "vr_context.hpp"
+#include "vr_device.hpp"
+
+static_assert(VR_LOG_SCALE == (double)(1ull << VR_LOG_FRAC_BITS), "the kernels' log scale is 2^VR_LOG_FRAC_BITS");
+
+// Source::getSourceArea(): a surface source's own (gpu/raygTraceDisk.hpp:90-91), a user source's override, else
+// SourceRandom's — the source face of the bounding box
+static float effective_source_area(const vr_context *c) {
+  if (c->surfCount)
+    return c->surfArea;
+  return c->sourceAreaOverride > 0.f ? c->sourceAreaOverride : c->sourceArea;
+}
+
+extern "C" {
+
+// ---- results --------------------------------------------------------------------
+uint32_t vr_num_primitives(const vr_context *c) { return c ? c->geo.numPrims : 0; }
+
+uint32_t vr_num_data(const vr_context *c) { return c ? c->totalData : 0; }
+
+static int get_flux_plane_f64(vr_context *c, uint32_t dataIdx, double *out, uint32_t n);
+
+int vr_get_flux_f64(vr_context *c, double *out, uint32_t n) { return get_flux_plane_f64(c, 0, out, n); }
+
+// getLocalData().getVectorData(dataIdx): the particle's data label `dataIdx`, as the reference's float vector.
+// The int64 fixed-point sums become floats on the device (float(double(acc) * 2^-40), what the host conversion
+// did): one 4-byte-per-primitive download instead of 8 bytes and two host passes.
+int vr_get_flux_data(vr_context *c, uint32_t dataIdx, float *out, uint32_t n) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  if (!c->haveResult)
+    return fail(c, VR_E_STATE, "vr_get_flux: no result (call vr_apply)");
+  if (n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, "vr_get_flux: size mismatch");
+  if (dataIdx >= c->totalData)
+    return fail(c, VR_E_INVALID, "vr_get_flux_data: the particle has no such data label");
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_HIP(c, c->dFluxTmp.ensure(n));
+  VR_HIP(c, launch_flux_from_acc(c->fluxOut() + (size_t)dataIdx * n, n, c->dFluxTmp.p, c->stream));
+  VR_HIP(c, hipMemcpyAsync(out, c->dFluxTmp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  return VR_OK;
+}
+
+static int get_flux_plane_f64(vr_context *c, uint32_t dataIdx, double *out, uint32_t n) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  if (!c->haveResult)
+    return fail(c, VR_E_STATE, "vr_get_flux: no result (call vr_apply)");
+  if (n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, "vr_get_flux: size mismatch");
+  if (dataIdx >= c->totalData)
+    return fail(c, VR_E_INVALID, "vr_get_flux_data: the particle has no such data label");
+  VR_HIP(c, hipSetDevice(c->device));
+  std::vector<unsigned long long> acc(n);
+  VR_HIP(c, hipMemcpy(acc.data(), c->fluxOut() + (size_t)dataIdx * n, (size_t)n * 8, hipMemcpyDeviceToHost));
+  const double scale = std::ldexp(1.0, -VR_FLUX_FRAC_BITS);
+  for (uint32_t i = 0; i < n; ++i)
+    out[i] = (double)acc[i] * scale;
+  return VR_OK;
+}
+
+int vr_get_flux(vr_context *c, float *out, uint32_t n) { return vr_get_flux_data(c, 0, out, n); }
+
+int vr_get_trace_info(const vr_context *c, vr_trace_info *out) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  *out = c->info;
+  return VR_OK;
+}
+
+int vr_get_particle_trace_info(const vr_context *c, uint32_t q, vr_trace_info *out) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  if (c->specs.size() <= 1) {
+    if (q != 0)
+      return VR_E_INVALID;
+    *out = c->info;
+    return VR_OK;
+  }
+  if (q >= c->launches.size())
+    return VR_E_INVALID;
+  *out = c->launches[q].info;
+  return VR_OK;
+}
+
+int vr_get_trace_mode(const vr_context *c, int32_t *mode) {
+  if (!c || !mode)
+    return VR_E_INVALID;
+  *mode = c->launches.empty() ? 0 : current_launch(c).traceMode;
+  return VR_OK;
+}
+
+int vr_flux_accumulators(vr_context *c, void **devPtr, uint32_t *n) {
+  if (!c || !devPtr)
+    return VR_E_INVALID;
+  if (!c->haveResult)
+    return fail(c, VR_E_STATE, "vr_flux_accumulators: no result");
+  *devPtr = c->fluxOut();
+  if (n)
+    *n = c->geo.numPrims * c->totalData;
+  return VR_OK;
+}
+
+// ---- the data log (DataLog / logData of the reference: rayTraceKernel.hpp:131-133, 345) ---------------------------
+int vr_get_data_log(vr_context *c, float *out, uint32_t n) {
+  if (!c || (n && !out))
+    return VR_E_INVALID;
+  if (!c->haveLog)
+    return fail(c, VR_E_STATE, "vr_get_data_log: no result (set a shape with vr_set_data_log_shape, then vr_apply)");
+  if (n != c->logHost.size() - 1)
+    return fail(c, VR_E_INVALID, "vr_get_data_log: n differs from the entries of the shape");
+  const double scale = std::ldexp(1.0, -VR_LOG_FRAC_BITS);
+  for (uint32_t i = 0; i < n; ++i)
+    out[i] = (float)((double)(long long)c->logHost[i] * scale);
+  return VR_OK;
+}
+
+int vr_get_data_log_i64(vr_context *c, int64_t *out, uint32_t n) {
+  if (!c || (n && !out))
+    return VR_E_INVALID;
+  if (!c->haveLog)
+    return fail(c, VR_E_STATE, "vr_get_data_log_i64: no result (set a shape with vr_set_data_log_shape, then vr_apply)");
+  if (n != c->logHost.size() - 1)
+    return fail(c, VR_E_INVALID, "vr_get_data_log_i64: n differs from the entries of the shape");
+  for (uint32_t i = 0; i < n; ++i)
+    out[i] = (int64_t)c->logHost[i];
+  return VR_OK;
+}
+
+int vr_get_data_log_dropped(vr_context *c, uint64_t *out) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  if (!c->haveLog)
+    return fail(c, VR_E_STATE, "vr_get_data_log_dropped: no result (set a shape with vr_set_data_log_shape, then vr_apply)");
+  *out = c->logHost.back();
+  return VR_OK;
+}
+
+int vr_data_log_accumulators(vr_context *c, void **devPtr, uint32_t *n) {
+  if (!c || !devPtr || !n)
+    return VR_E_INVALID;
+  if (!c->logActive || !c->dDataLog.p)
+    return fail(c, VR_E_STATE, "vr_data_log_accumulators: no data log (set a shape with vr_set_data_log_shape, then prepare or apply)");
+  *devPtr = c->dDataLog.p;
+  *n = c->logTotal;
+  return VR_OK;
+}
+
+int vr_bind_flux_accumulators(vr_context *c, void *devPtr, uint32_t n) {
+  if (!c)
+    return VR_E_INVALID;
+  if (devPtr && n != c->geo.numPrims * c->totalData)
+    return fail(c, VR_E_INVALID, "vr_bind_flux_accumulators: size mismatch (numPrims x data labels; set geometry and particle first)");
+  c->boundFlux = (unsigned long long *)devPtr;
+  c->boundFluxN = devPtr ? n : 0;
+  return VR_OK;
+}
+
+// normalizeFlux on the device (rayTraceDisk.hpp:103-142, rayTraceTriangle.hpp:92-130;
+// gpu/kernels/normKernels.cu:58-74): `flux` (device) holds the flux in the caller's order
+static int normalize_on_device(vr_context *c, float *flux, uint32_t n, int normType) {
+  const bool disk = c->geo.geo == 0;
+  if (!c->areasValid)
+    return fail(c, VR_E_STATE, "vr_normalize_flux: call vr_apply first (primitive areas)");
+  float normFactor = 0.f;
+  if (normType == VR_NORM_SOURCE) {
+    if (c->numRaysLast == 0)
+      return fail(c, VR_E_STATE, "No source was specified in rayTrace for the normalization.");
+    normFactor = effective_source_area(c) / c->numRaysLast;
+  } else if (normType != VR_NORM_MAX) {
+    return VR_OK; // `default: break;` in the reference
+  }
+  const double totalDiskArea = c->geo.diskRadius * c->geo.diskRadius * M_PI;
+  VR_HIP(c, c->dNormMax.ensure(1)); // (a word of its own: the builder's scratch does not exist under VR_HOST_BUILD)
+  VR_HIP(c, launch_normalize_flux(flux, c->dAreas.p, n, disk ? 0 : 1, normType, normFactor, totalDiskArea,
+                                  c->dNormMax.p, c->stream));
+  return VR_OK;
+}
+
+int vr_normalize_flux(vr_context *c, float *flux, uint32_t n, int normType) {
+  if (!c || !flux || n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, "vr_normalize_flux: bad argument");
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_HIP(c, c->dFluxTmp.ensure(n));
+  VR_HIP(c, hipMemcpyAsync(c->dFluxTmp.p, flux, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  int r = normalize_on_device(c, c->dFluxTmp.p, n, normType);
+  if (r != VR_OK)
+    return r;
+  VR_HIP(c, hipMemcpyAsync(flux, c->dFluxTmp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  return VR_OK;
+}
+
+// getLocalData().getVectorData(0) followed by normalizeFlux, without the raw flux ever
+// visiting the host: int64 accumulators -> float -> normalised, one download
+int vr_get_flux_normalized(vr_context *c, float *out, uint32_t n, int normType) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  if (!c->haveResult)
+    return fail(c, VR_E_STATE, "vr_get_flux_normalized: no result (call vr_apply)");
+  if (n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, "vr_get_flux_normalized: size mismatch");
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_HIP(c, c->dFluxTmp.ensure(n));
+  VR_HIP(c, launch_flux_from_acc(c->fluxOut(), n, c->dFluxTmp.p, c->stream));
+  int r = normalize_on_device(c, c->dFluxTmp.p, n, normType);
+  if (r != VR_OK)
+    return r;
+  VR_HIP(c, hipMemcpyAsync(out, c->dFluxTmp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  return VR_OK;
+}
+
+// rayTraceDisk.hpp:146-193 (triangle version is a no-op: rayTraceTriangle.hpp:134-136)
+int vr_smooth_flux(vr_context *c, float *flux, uint32_t n, int numNeighbors) {
+  if (!c || !flux || n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, "vr_smooth_flux: bad argument");
+  if (c->geo.geo != 0 || numNeighbors < 1)
+    return VR_OK;
+  // device path: the geometry's own neighbourhood (numNeighbors == 1, what every reference example asks for) is
+  // resident with the device-built scene; a wider one (k > 1) is a range query of radius k * 2 r over the resident BVH,
+  // fused with the averaging.  No download of any neighbourhood.
+  if (c->haveSetup && !c->geometryDirty && !read_knobs().hostSmooth) {
+    VR_HIP(c, hipSetDevice(c->device));
+    DevBuf<float> dIn, dOut;
+    DevBuf<uint32_t> dOv;
+    VR_HIP(c, dIn.ensure(n));
+    VR_HIP(c, dOut.ensure(n));
+    VR_HIP(c, dOv.ensure(1));
+    uint32_t ov = 0;
+    VR_HIP(c, hipMemcpyAsync(dIn.p, flux, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    VR_HIP(c, hipMemsetAsync(dOv.p, 0, 4, c->stream));
+    if (numNeighbors == 1)
+      VR_HIP(c, launch_smooth_flux(dIn.p, dOut.p, c->dNormal3.p, c->dNbOff.p, c->dNbIds.p, c->dOrder.p,
+                                   c->dLeafOfOrig.p, n, dOv.p, c->stream));
+    else
+      VR_HIP(c, launch_smooth_wide(dIn.p, dOut.p, c->dNormal3.p, c->lastSetup, numNeighbors * 2 * c->geo.diskRadius,
+                                   dOv.p, c->stream));
+    VR_HIP(c, hipMemcpyAsync(&ov, dOv.p, 4, hipMemcpyDeviceToHost, c->stream));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    if (ov == 0) {
+      VR_HIP(c, hipMemcpy(flux, dOut.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+      return VR_OK;
+    } // (some neighbourhood longer than the kernel's buffer: host path below)
+  }
+  {
+    const int r = ensure_host_geometry(c); // (the host path reads the normals, and the centres for k > 1)
+    if (r != VR_OK)
+      return r;
+  }
+  if (numNeighbors == 1) {
+    int r = ensure_host_neighbors(c);
+    if (r != VR_OK)
+      return r;
+  }
+  const std::vector<uint32_t> *off = &c->geo.nbOff, *ids = &c->geo.nbIds;
+  std::vector<uint32_t> woff, wids;
+  if (numNeighbors != 1) {
+    std::vector<float> pts((size_t)n * 3);
+    for (uint32_t i = 0; i < n; ++i)
+      std::memcpy(&pts[3 * (size_t)i], &c->geo.disk4[4 * (size_t)i], 12);
+    host_neighbors(c->geo.D, pts.data(), n, numNeighbors * 2 * c->geo.diskRadius, c->geo.minC, woff, wids);
+    off = &woff;
+    ids = &wids;
+  }
+  std::vector<float> old(flux, flux + n);
+  const float *nr = c->geo.normal3.data();
+  for (uint32_t i = 0; i < n; ++i) {
+    float vv = old[i];
+    float sum = 1.f;
+    for (uint32_t j = (*off)[i]; j < (*off)[i + 1]; ++j) {
+      const uint32_t nb = (*ids)[j];
+      const float w = (nr[3 * (size_t)i] * nr[3 * (size_t)nb] + nr[3 * (size_t)i + 1] * nr[3 * (size_t)nb + 1]) +
+                      nr[3 * (size_t)i + 2] * nr[3 * (size_t)nb + 2];
+      if (w > 0.f) {
+        vv += old[nb] * w;
+        sum += w;
+      }
+    }
+    flux[i] = vv / sum;
+  }
+  return VR_OK;
+}
+
+// getLocalData().getVectorData(dataIdx) -> normalizeFlux -> smoothFlux with every stage on the device and the result left
+// in the caller's device buffer: the kernels vr_get_flux_data / vr_normalize_flux / vr_smooth_flux run, on the same floats,
+// so the result has their bits.  Without smoothing nothing comes back to the host and nothing waits; with smoothing one
+// word does (the kernels' overflow flag, which decides on the host fallback).
+int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, int normType, int numNeighbors,
+                       void *stream) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  if (!c->haveResult)
+    return fail(c, VR_E_STATE, "vr_get_flux_device: no result (call vr_apply)");
+  if (n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, "vr_get_flux_device: size mismatch");
+  if (dataIdx >= c->totalData)
+    return fail(c, VR_E_INVALID, "vr_get_flux_device: the particle has no such data label");
+  VR_HIP(c, hipSetDevice(c->device));
+  if (n && !is_device_memory_of(out, c->device))
+    return fail(c, VR_E_INVALID, "vr_get_flux_device: out is not device memory of the context's device");
+  hipStream_t caller = (hipStream_t)stream;
+  const bool smooth = c->geo.geo == 0 && numNeighbors >= 1;
+  int r = wait_for_caller(c, caller); // (out may still be in use by work the caller queued before this call)
+  if (r != VR_OK)
+    return r;
+  float *work = out;
+  if (smooth) { // (the smoothing kernels read one buffer and write another)
+    VR_HIP(c, c->dFluxTmp.ensure(n));
+    work = c->dFluxTmp.p;
+  }
+  VR_HIP(c, launch_flux_from_acc(c->fluxOut() + (size_t)dataIdx * n, n, work, c->stream));
+  if (normType == VR_NORM_SOURCE || normType == VR_NORM_MAX) {
+    r = normalize_on_device(c, work, n, normType);
+    if (r != VR_OK)
+      return r;
+  }
+  if (smooth) {
+    bool done = false;
+    if (c->haveSetup && !c->geometryDirty && !read_knobs().hostSmooth) {
+      DevBuf<uint32_t> dOv;
+      VR_HIP(c, dOv.ensure(1));
+      uint32_t ov = 0;
+      VR_HIP(c, hipMemsetAsync(dOv.p, 0, 4, c->stream));
+      if (numNeighbors == 1)
+        VR_HIP(c, launch_smooth_flux(work, out, c->dNormal3.p, c->dNbOff.p, c->dNbIds.p, c->dOrder.p, c->dLeafOfOrig.p, n,
+                                     dOv.p, c->stream));
+      else
+        VR_HIP(c, launch_smooth_wide(work, out, c->dNormal3.p, c->lastSetup, numNeighbors * 2 * c->geo.diskRadius, dOv.p,
+                                     c->stream));
+      VR_HIP(c, hipMemcpyAsync(&ov, dOv.p, 4, hipMemcpyDeviceToHost, c->stream));
+      VR_HIP(c, hipStreamSynchronize(c->stream));
+      done = ov == 0;
+    }
+    if (!done) { // the one path through the host: vr_smooth_flux's own fallback, then up again
+      std::vector<float> h(n);
+      VR_HIP(c, hipMemcpyAsync(h.data(), work, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+      VR_HIP(c, hipStreamSynchronize(c->stream));
+      r = vr_smooth_flux(c, h.data(), n, numNeighbors);
+      if (r != VR_OK)
+        return r;
+      VR_HIP(c, hipMemcpy(out, h.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+  }
+  return caller_waits(c, caller);
+}
+
+int vr_get_disk_areas(vr_context *c, float *out, uint32_t n) {
+  if (!c || !out || n != c->geo.numPrims || c->geo.geo != 0 || !c->areasValid)
+    return fail(c, VR_E_STATE, "vr_get_disk_areas: not available");
+  if (!c->diskAreasHostValid) {
+    VR_HIP(c, hipSetDevice(c->device));
+    c->diskAreas.resize(n);
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    VR_HIP(c, hipMemcpy(c->diskAreas.data(), c->dAreas.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    c->diskAreasHostValid = true;
+  }
+  std::memcpy(out, c->diskAreas.data(), (size_t)n * 4);
+  return VR_OK;
+}
+int vr_get_bounding_box(vr_context *c, float *out6) {
+  if (!c || !out6)
+    return VR_E_INVALID;
+  for (int k = 0; k < 3; ++k) {
+    out6[k] = c->bbLo[k];
+    out6[k + 3] = c->bbHi[k];
+  }
+  return VR_OK;
+}
+float vr_get_source_area(vr_context *c) {
+  return c ? effective_source_area(c) : 0.f;
+}
+float vr_get_disk_radius(const vr_context *c) { return c ? c->geo.diskRadius : 0.f; }
+int vr_get_neighbor_counts(vr_context *c, uint32_t *out, uint32_t n) {
+  if (!c || !out || n != c->geo.numPrims)
+    return VR_E_INVALID;
+  int r = ensure_host_neighbors(c);
+  if (r != VR_OK)
+    return r;
+  for (uint32_t i = 0; i < n; ++i)
+    out[i] = c->geo.nbOff[i + 1] - c->geo.nbOff[i];
+  return VR_OK;
+}
+
+} // extern "C"

@@ -628,7 +628,7 @@ __device__ __forceinline__ bool rises_clear(const float *__restrict__ wallS, con
 #endif
 #ifndef VR_FLAT_ORDERED
 #define VR_FLAT_ORDERED 0  // MODE 3 walks like MODE 1: the escape-link walk, no carry-over (1: the ordered pair walk).  It runs
-                           // only on scenes whose box is thin (vr_api.cpp: flatScene), where a wave walks in the 5 % of its
+                           // only on scenes whose box is thin (vr_prepare.cpp: flatScene), where a wave walks in the 5 % of its
                            // rounds whose query gives up; without the walk's 12 KB of LDS stack and ~10 VGPRs the kernel
                            // takes 6 waves per SIMD: C2 0.1 10.9 -> 10.0 ms.  (Forced onto a scene with relief
                            // — VR_GENERAL_FLAT=1 — it is 15 - 30 % slower than with the ordered walk at 5 waves.)
@@ -831,7 +831,7 @@ trace_kernel(const TraceParams p) {
   const unsigned totalBins = p.numBins + ovChunks + (RESUME ? (spillN + spillChunk - 1) / spillChunk : 0u);
   unsigned curBin = 0, spanStart = 0, spanEnd = 0, curOff = 0, curCnt = 0, curBase = 0;
   unsigned spanCounts = 0; // lane i: ray count of bin spanStart + i
-  // (only the general flat-scene kernel has the queues compiled in — it is the one they pay for, vr_api.cpp — the others
+  // (only the general flat-scene kernel has the queues compiled in — it is the one they pay for, vr_apply.cpp — the others
   //  keep the single queue's code: MODE 1 with the bookkeeping: L2 hit rate 74 -> 84 % but 6.60 -> 6.83 ms from the
   //  extra scalar spills of a kernel at 8 waves per SIMD)
   constexpr bool MULTIQ = MODE == 3;
