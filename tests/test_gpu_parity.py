@@ -2001,6 +2001,58 @@ def test_particle_model_registered_at_run_time(geom, model_cache, monkeypatch):
     assert t2.registerParticleModel(USER_TWO_LABELS, numData=2) >= 1000 and sorted(os.listdir(tmp_path)) == before
 
 
+def test_refused_particle_list_leaves_nothing_behind(model_cache, monkeypatch):
+    """A particle list whose SECOND entry prepare refuses (a run-time model registered without needsFull under WDIST
+    crediting: refused inside the per-particle loop, after the first particle — per-material sticking map included — was
+    prepared) fails the apply; a single built-in particle set on the same context afterwards then traces exactly what it
+    traces on a fresh context that ran a good two-particle list first: flux and every TraceInfo counter equal, no tolerance
+    (integer accumulators, fixed seed).  (The model is the one test_particle_model_registered_at_run_time compiles: found
+    in the module's cache.)"""
+    monkeypatch.setenv("VR_CACHE_DIR", model_cache)
+    pts, nrm = vr.io.plane_grid(20, 1.0)
+    mats = (np.arange(len(pts)) % 2).astype(np.int32)
+    first = vr.DiffuseParticle(0.6, "a", materialSticking={1: 0.9})
+    single = vr.SpecularParticle(0.3, 4.0, "s")
+
+    def tracer():
+        t = vr.TraceDisk(3)
+        t.setGeometry(pts, nrm, 1.0)
+        t.setMaterialIds(mats)
+        t.setBoundaryConditions([BC.REFLECTIVE_BOUNDARY] * 3)
+        t.setUseWdist(True)
+        t.setNumberOfRaysFixed(4000)
+        t.setRngSeed(7)
+        return t
+
+    def result(t):
+        i = t.getRayTraceInfo()
+        counters = {k: int(getattr(i, k)) for k in INFO_KEYS + ("rngFullStates", "warning", "error")}
+        return counters, t.getFluxF64(), t.getLocalData().getVectorData("s").copy(), t.numData(), t.traceMode()
+
+    used = tracer()
+    k = used.registerParticleModel(USER_TWO_LABELS, numData=2, name="twoLabels")
+    used.setParticleTypes([first, vr.UserModelParticle(k, 0.3, ["u", "ucos"])])
+    with pytest.raises(vr.VrError, match="VR_MODEL_NEEDS_FULL"):
+        used.apply()
+    assert used.getRunNumber() == 1          # (nothing was traced)
+    used.setParticleType(single)
+    used.apply()
+
+    fresh = tracer()
+    fresh.setParticleTypes([first, vr.DiffuseCosineParticle(0.3, "u", "ucos")])
+    fresh.apply()
+    assert fresh.numData() == 3
+    fresh.setParticleType(single)
+    fresh.setRunNumber(1)
+    fresh.apply()
+
+    cu, fu, lu, nu, mu = result(used)
+    cf, ff, lf, nf, mf = result(fresh)
+    assert cu == cf and cu["totalRaysTraced"] >= 4000 and cu["error"] == 0
+    assert nu == nf == 1 and mu == mf
+    assert fu.sum() > 0 and (fu == ff).all() and (lu == lf).all()
+
+
 def test_particle_model_that_does_not_compile_is_refused(tmp_path, monkeypatch):
     monkeypatch.setenv("VR_CACHE_DIR", str(tmp_path))
     t = vr.TraceDisk(3)

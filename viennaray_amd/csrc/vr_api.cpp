@@ -51,20 +51,17 @@ int caller_waits(vr_context *c, hipStream_t stream) {
   return VR_OK;
 }
 
-// make `sp` the particle the next prepare works on
-void activate_particle(vr_context *c, const ParticleSpec &sp) {
-  c->userModel = sp.userModel;
-  // (inside its own code object a run-time model is the registry's last entry)
-  c->particleKind = sp.userModel >= 0 ? VR_BUILTIN_MODELS : sp.kind;
-  c->sticking = sp.sticking;
-  c->sourcePower = sp.sourcePower;
-  c->coneAngle = sp.coneAngle;
-  c->meanFreePath = sp.meanFreePath;
-  std::memcpy(c->particleParams, sp.params, sizeof(sp.params));
-  c->numData = sp.userModel >= 0 ? (uint32_t)c->userModels[sp.userModel].numData : (uint32_t)Particles::numData(sp.kind);
-  c->matStickIds = sp.matIds;
-  c->matStickVals = sp.matVals;
-  c->particleDirty = true;
+// A new geometry is in c->geo (or on its way into the resident buffers): nothing derived from the previous one holds.
+// (hostNeighborsValid also for triangles, whose neighbourhood host_set_triangles has just written as ensure_host_neighbors
+//  would: empty lists for every triangle, whatever the flag says.)
+static void invalidate_geometry(vr_context *c) {
+  c->geoOnDevice = c->hostGeoValid = false;
+  c->hostNeighborsValid = false;
+  c->areasValid = false;
+  c->boundFlux = nullptr;
+  c->geometryDirty = true;
+  c->configDirty = true;
+  c->prepared = c->haveResult = false;
 }
 
 } // namespace vr
@@ -109,22 +106,6 @@ void vr_destroy(vr_context *c) {
   for (auto &um : c->userModels)
     if (um.module)
       (void)hipModuleUnload(um.module);
-  c->dNodes.release();
-  c->dPrims.release();
-  c->dNbOff.release();
-  c->dNbTmp.release();
-  c->dNbIds.release();
-  c->dHfRaw.release();
-  c->dHf.release();
-  c->dLeafOfOrig.release();
-  c->dFluxAcc.release();
-  c->dFluxOrig.release();
-  c->dCounters.release();
-  c->dScratch.release();
-  c->dWalls.release();
-  c->dSlotRec.release();
-  c->dBinCount.release();
-  c->dScanTmp.release();
   for (auto e : c->evK)
     (void)hipEventDestroy(e);
   for (auto e : c->evG)
@@ -139,7 +120,7 @@ void vr_destroy(vr_context *c) {
     (void)hipEventDestroy(c->ev1);
   if (c->stream)
     (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c; // (every DevBuf frees its memory: the device is selected and idle)
 }
 
 const char *vr_last_error(const vr_context *c) { return c ? c->err.c_str() : "null context"; }
@@ -150,13 +131,7 @@ int vr_set_disks(vr_context *c, const float *points, const float *normals, uint3
   if (!c || !points || !normals || (D != 2 && D != 3) || n >= (1u << 27))
     return fail(c, VR_E_INVALID, "vr_set_disks: bad argument");
   host_set_disks(c->geo, points, normals, n, gridDelta, diskRadius, D);
-  c->geoOnDevice = c->hostGeoValid = false;
-  c->hostNeighborsValid = false;
-  c->areasValid = false;
-  c->boundFlux = nullptr;
-  c->geometryDirty = true;
-  c->configDirty = true;
-  c->prepared = c->haveResult = false;
+  invalidate_geometry(c);
   return VR_OK;
 }
 
@@ -181,18 +156,12 @@ int vr_set_disks_device(vr_context *c, const float *points, const float *normals
   VR_HIP(c, c->dIngestKeys.ensure(ingest_partials_entries()));
   VR_HIP(c, c->dIngestBounds.ensure(6));
   // from here on the resident buffers no longer hold the previous geometry
-  c->geometryDirty = true;
-  c->configDirty = true;
-  c->prepared = c->haveResult = false;
-  c->hostNeighborsValid = false;
-  c->areasValid = false;
-  c->boundFlux = nullptr;
+  invalidate_geometry(c);
   HostGeometry &g = c->geo;
   g.numPrims = 0; // (until the new one is in place: an error below leaves "no geometry", not half of one)
   g.disk4.clear();
   g.normal3.clear();
   g.points3.clear();
-  c->geoOnDevice = c->hostGeoValid = false;
   int r = wait_for_caller(c, caller);
   if (r != VR_OK)
     return r;
@@ -229,12 +198,7 @@ int vr_set_triangles(vr_context *c, const float *verts, uint32_t nverts, const u
     if (tris[i] >= nverts)
       return fail(c, VR_E_INVALID, "vr_set_triangles: vertex index out of range");
   host_set_triangles(c->geo, verts, nverts, tris, ntris, gridDelta, D);
-  c->geoOnDevice = c->hostGeoValid = false;
-  c->areasValid = false;
-  c->boundFlux = nullptr;
-  c->geometryDirty = true;
-  c->configDirty = true;
-  c->prepared = c->haveResult = false;
+  invalidate_geometry(c);
   return VR_OK;
 }
 
@@ -290,6 +254,8 @@ static bool spec_from_pod(const vr_context *c, const vr_particle *p, ParticleSpe
   sp = ParticleSpec{};
   sp.kind = p->kind;
   sp.userModel = user ? p->kind - VR_PARTICLE_USER_BASE : -1;
+  sp.kernelKind = user ? VR_BUILTIN_MODELS : p->kind;
+  sp.numData = user ? (uint32_t)c->userModels[sp.userModel].numData : (uint32_t)Particles::numData(p->kind);
   sp.sticking = p->sticking;
   // rayParticle.hpp:158,199: only SpecularParticle-like particles carry a source power of their own
   sp.sourcePower = (p->kind == VR_PARTICLE_DIFFUSE || p->kind == VR_PARTICLE_DIFFUSE_COSINE ||
@@ -316,11 +282,10 @@ int vr_set_particles(vr_context *c, const vr_particle *list, uint32_t n) {
   for (uint32_t i = 0; i < n; ++i) {
     if (!spec_from_pod(c, &list[i], specs[i]))
       return fail(c, VR_E_INVALID, "vr_set_particle: unknown particle kind (not in the device registry, not registered)");
-    total += specs[i].userModel >= 0 ? (uint32_t)c->userModels[specs[i].userModel].numData
-                                     : (uint32_t)Particles::numData(specs[i].kind);
+    total += specs[i].numData;
   }
   c->specs = std::move(specs);
-  activate_particle(c, c->specs[0]);
+  c->particleDirty = true;
   c->totalData = total;
   // a caller's accumulator buffer (vr_bind_flux_accumulators) stays bound while it still has the right size: numPrims x
   // data labels of ALL particles; it is dropped only when the number of planes changed
@@ -328,7 +293,6 @@ int vr_set_particles(vr_context *c, const vr_particle *list, uint32_t n) {
     c->boundFlux = nullptr;
     c->boundFluxN = 0;
   }
-  c->haveParticle = true;
   c->prepared = false;
   return VR_OK;
 }

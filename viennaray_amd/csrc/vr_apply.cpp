@@ -42,7 +42,7 @@ TraceParams launch_params(const vr_context *c, const ParticleLaunch &L) {
   const bool spill = L.relief && L.looseMode == 7;
   p.spillRec = spill ? c->dSpillRec.p : nullptr;
   p.spillCount = spill ? c->dSpillCount.p : nullptr;
-  p.counters = c->dCounters.p + 80 * (size_t)L.slot;
+  p.counters = c->dCounters.p + C_BLOCK * (size_t)L.slot;
   p.fluxAcc = c->dFluxAcc.p + (size_t)L.dataBase * p.planeStride; // (this particle's planes)
   return p;
 }
@@ -184,7 +184,7 @@ int vr_apply_launch(vr_context *c) {
   VR_HIP(c, hipSetDevice(c->device));
   const uint32_t N = c->geo.numPrims;
   VR_HIP(c, hipMemsetAsync(c->dFluxAcc.p, 0, (size_t)c->accStride * c->accReplicas * c->totalData * 8, c->stream));
-  VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 80 * c->launches.size() * 8, c->stream));
+  VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, C_BLOCK * c->launches.size() * 8, c->stream));
   if (c->logActive) // (the sums, the dropped counter and the overflow flag)
     VR_HIP(c, hipMemsetAsync(c->dDataLog.p, 0, ((size_t)c->logTotal + 2) * 8, c->stream));
   VR_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -217,7 +217,7 @@ int vr_apply_launch(vr_context *c) {
     const unsigned headroom = rank_headroom(c->worldSize);
     for (uint32_t l = 0; l < c->totalData; ++l)
       VR_HIP(c, launch_gather_flux(c->dFluxAcc.p + (size_t)l * c->accStride * c->accReplicas, c->accStride, c->accReplicas,
-                                   c->dLeafOfOrig.p, N, c->fluxOut() + (size_t)l * N, headroom, c->dCounters.p + 61, c->stream));
+                                   c->dLeafOfOrig.p, N, c->fluxOut() + (size_t)l * N, headroom, c->dCounters.p + C_ACC_OVERFLOW, c->stream));
   }
   c->launched = true;
   return VR_OK;
@@ -242,12 +242,12 @@ int vr_apply_finish(vr_context *c) {
   VR_HIP(c, hipSetDevice(c->device));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   const size_t nPart = c->launches.size();
-  std::vector<unsigned long long> all(80 * nPart); // per particle: [0..7] TraceInfo counters, [60] the walk's stack-overflow flag
+  std::vector<unsigned long long> all(C_BLOCK * nPart); // every particle's counter block (vr_types.hpp: C_*)
   VR_HIP(c, hipMemcpy(all.data(), c->dCounters.p, all.size() * 8, hipMemcpyDeviceToHost));
 #ifdef VR_DIAG
   { // lane-occupancy diagnostics of a -DVR_DIAG build (see vr_trace.hip)
     unsigned long long dg[32];
-    VR_HIP(c, hipMemcpy(dg, c->dCounters.p + 16, sizeof(dg), hipMemcpyDeviceToHost));
+    VR_HIP(c, hipMemcpy(dg, c->dCounters.p + C_DIAG, sizeof(dg), hipMemcpyDeviceToHost));
     static const char *names[16] = {"rounds", "walk steps", "leaf prim tests", "packet visits", "packet prim tests",
                                     "state machine", "neighbour iters", "walk steps: unfinished", "refill reps", "wall init",
                                     "roulette", "credit", "pq attempts", "pq done", "visits: no child hit", "visits: both hit"};
@@ -256,7 +256,7 @@ int vr_apply_finish(vr_context *c) {
         std::fprintf(stderr, "diag %-18s wave-iters %12llu  lane-iters %14llu  (%.1f lanes)\n", names[k], dg[2 * k],
                      dg[2 * k + 1], (double)dg[2 * k + 1] / (double)dg[2 * k]);
     unsigned long long ph[16];
-    VR_HIP(c, hipMemcpy(ph, c->dCounters.p + 64, sizeof(ph), hipMemcpyDeviceToHost));
+    VR_HIP(c, hipMemcpy(ph, c->dCounters.p + C_PHASE, sizeof(ph), hipMemcpyDeviceToHost));
     static const char *pn[16] = {"refill", "packets", "walk: search", "walk: leaf tests", "walls", "state machine + credit",
                                  "packet-query credit", "tail", "  (of state machine) neighbour loop", "  (of state machine) reflection + roulette; (absorbing kernels: of packets) packet query: record loads + box tests of the last level", "  (of state machine) from its start to the back-face test (vote, miss / wall branches, normal fetch)", "  (of state machine) boundary hit",
                                  "  (of state machine) up to the aggregation vote", "  (of state machine) up to the end counters", "  (of packets) packet query: descent of the 64-ary tree", "  (of packets) packet query: exact tests of the candidates"};
@@ -271,7 +271,7 @@ int vr_apply_finish(vr_context *c) {
   // A flux accumulator ran out of range (gather_flux_kernel): 2^23 = 8.39e6 weight units per primitive and data label
   // in one apply() — divided by the rank count rounded up to a power of two — is what int64 at 2^-40 holds (signed: the
   // multi-GPU all-reduce).  The reference's float sums stall near 2^24; these would wrap: the apply fails instead.
-  if (all[61]) {
+  if (all[C_ACC_OVERFLOW]) {
     c->launched = false;
     c->prepared = false;
     c->info.error = 1;
@@ -299,7 +299,7 @@ int vr_apply_finish(vr_context *c) {
   for (size_t q = 0; q < nPart; ++q) {
     // the walk's stack ran out (a tree deeper than SD + VR_STACK_GLOBAL levels of deferred children): the
     // result would be wrong, so the apply fails
-    if (all[80 * q + 60]) {
+    if (all[C_BLOCK * q + C_WALK_OVERFLOW]) {
       c->launched = false;
       c->prepared = false;
       return fail(c, VR_E_STATE, "BVH traversal stack overflow (degenerate tree), or a rank of a sharded apply failed: result discarded");
@@ -307,32 +307,34 @@ int vr_apply_finish(vr_context *c) {
   }
 #ifdef VR_SELFCHECK
   {
-    unsigned long long sc[12];
-    VR_HIP(c, hipMemcpy(sc, c->dCounters.p + 48, sizeof(sc), hipMemcpyDeviceToHost));
+    unsigned long long sc[C_CHECK_GEOM - C_CHECK + 1];
+    VR_HIP(c, hipMemcpy(sc, c->dCounters.p + C_CHECK, sizeof(sc), hipMemcpyDeviceToHost));
+    const unsigned long long *const ray = sc + (C_CHECK_RAY - C_CHECK);
+    const unsigned long long pos = sc[C_CHECK_POS - C_CHECK], geom = sc[C_CHECK_GEOM - C_CHECK];
     std::fprintf(stderr, "[vr] self-check: %llu segments disagree with the escape-link walk\n", sc[0]);
     if (sc[0]) {
       float v[8];
       for (int k = 0; k < 8; ++k) {
-        const uint32_t u = (uint32_t)sc[2 + k];
+        const uint32_t u = (uint32_t)ray[k];
         std::memcpy(&v[k], &u, 4);
       }
       std::fprintf(stderr, "[vr]   first: o %.9g %.9g %.9g d %.9g %.9g %.9g  t %.9g pos %u geom %d | ref t %.9g pos %u geom %d\n",
-                   v[0], v[1], v[2], v[3], v[4], v[5], v[6], (unsigned)(sc[10] >> 32), (int)(sc[11] >> 32), v[7],
-                   (unsigned)(sc[10] & 0xFFFFFFFFu), (int)(sc[11] & 0xFFFFFFFFu));
+                   v[0], v[1], v[2], v[3], v[4], v[5], v[6], (unsigned)(pos >> 32), (int)(geom >> 32), v[7],
+                   (unsigned)(pos & 0xFFFFFFFFu), (int)(geom & 0xFFFFFFFFu));
     }
   }
 #endif
   float ms = 0.f;
   VR_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
   // per particle, and their sums in the context's TraceInfo
-  unsigned long long sum[80] = {};
+  unsigned long long sum[C_BLOCK] = {};
   for (size_t q = 0; q < nPart; ++q) {
     vr_trace_info &pi = c->launches[q].info;
     pi = vr_trace_info{};
     pi.numRays = c->numRaysLast;
-    info_from_counters(pi, all.data() + 80 * q);
-    for (size_t w = 0; w < 80; ++w)
-      sum[w] += all[80 * q + w];
+    info_from_counters(pi, all.data() + C_BLOCK * q);
+    for (size_t w = 0; w < C_BLOCK; ++w)
+      sum[w] += all[C_BLOCK * q + w];
   }
   vr_trace_info &i = c->info;
   i.numRays = c->numRaysLast;
@@ -401,20 +403,24 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
   const uint64_t first = total * (uint64_t)rank / (uint64_t)world;
   const uint64_t last = total * (uint64_t)(rank + 1) / (uint64_t)world;
   const uint32_t N = c->geo.numPrims;
-  VR_HIP(c, c->dCounters.ensure(80 * std::max<size_t>(1, c->specs.size())));
+  // The all-reduce below sums whole counter blocks, so that the TraceInfo counters and both failure words travel together.
+  static_assert(C_COUNT <= C_BLOCK && C_WALK_OVERFLOW < C_BLOCK && C_ACC_OVERFLOW < C_BLOCK,
+                "the reduced counter blocks must carry the TraceInfo counters and both failure words");
+  const size_t counterWords = C_BLOCK * c->numParticles();
+  VR_HIP(c, c->dCounters.ensure(counterWords));
   c->haveSharedSeed = false;
   if (world > 1 && c->useRandomSeed) {
     // setUseRandomSeeds(true): every rank would draw its own seed and the shards would belong to different
     // streams.  Rank 0 draws, the others contribute 0, and the all-reduce hands the seed round.
-    unsigned long long word = 0;
+    unsigned long long word = 0, *const seedWord = c->dCounters.p + C_SHARED_SEED;
     if (rank == 0) {
       std::random_device rd;
       word = (uint32_t)rd();
     }
-    VR_HIP(c, hipMemcpyAsync(c->dCounters.p + 63, &word, 8, hipMemcpyHostToDevice, c->stream));
-    if (reduce(user, c->dCounters.p + 63, 1, (void *)c->stream) != 0)
+    VR_HIP(c, hipMemcpyAsync(seedWord, &word, 8, hipMemcpyHostToDevice, c->stream));
+    if (reduce(user, seedWord, 1, (void *)c->stream) != 0)
       return fail(c, VR_E_HIP, "vr_apply_sharded: the all-reduce callback failed (seed)");
-    VR_HIP(c, hipMemcpyAsync(&word, c->dCounters.p + 63, 8, hipMemcpyDeviceToHost, c->stream));
+    VR_HIP(c, hipMemcpyAsync(&word, seedWord, 8, hipMemcpyDeviceToHost, c->stream));
     VR_HIP(c, hipStreamSynchronize(c->stream));
     c->sharedSeed = (uint32_t)word;
     c->haveSharedSeed = true;
@@ -437,7 +443,7 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
     r = vr_apply_prepare(c);
     if (r == VR_OK) {
       VR_HIP(c, hipMemsetAsync(c->fluxOut(), 0, (size_t)N * c->totalData * 8, c->stream));
-      VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 80 * 8 * std::max<size_t>(1, c->specs.size()), c->stream));
+      VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, counterWords * 8, c->stream));
       if (c->logActive)
         VR_HIP(c, hipMemsetAsync(c->dDataLog.p, 0, ((size_t)c->logTotal + 2) * 8, c->stream));
       VR_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -453,9 +459,9 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
   c->worldSize = worldBefore;
   if (world > 1) {
     // A rank that failed above still enters the collectives when it can (zeros and a raised failure word) —
-    // the others would hang in them otherwise.  The TraceInfo counters [0..7] AND the failure word [60] (the
-    // walk's stack overflow, or this) travel together: every rank fails together, none returns VR_OK
-    // holding sums that include a discarded share.
+    // the others would hang in them otherwise.  The TraceInfo counters AND the failure words (C_WALK_OVERFLOW:
+    // the walk's stack, or this; C_ACC_OVERFLOW) travel together, in counterWords: every rank fails together,
+    // none returns VR_OK holding sums that include a discarded share.
     const std::string firstErr = c->err;
     const bool haveBuf = c->boundFlux ? c->boundFluxN == N * c->totalData : c->dFluxOrig.cap >= (size_t)N * c->totalData;
     if (r != VR_OK) {
@@ -463,15 +469,15 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
         return r; // (failed before the accumulators existed: a configuration error, the same on every rank)
       const unsigned long long one = 1;
       (void)hipMemsetAsync(c->fluxOut(), 0, (size_t)N * c->totalData * 8, c->stream);
-      (void)hipMemsetAsync(c->dCounters.p, 0, 80 * 8 * std::max<size_t>(1, c->specs.size()), c->stream);
-      (void)hipMemcpyAsync(c->dCounters.p + 60, &one, 8, hipMemcpyHostToDevice, c->stream);
+      (void)hipMemsetAsync(c->dCounters.p, 0, counterWords * 8, c->stream);
+      (void)hipMemcpyAsync(c->dCounters.p + C_WALK_OVERFLOW, &one, 8, hipMemcpyHostToDevice, c->stream);
       if (c->logActive)
         (void)hipMemsetAsync(c->dDataLog.p, 0, ((size_t)c->logTotal + 2) * 8, c->stream);
     }
     // (the data log's sums travel with their dropped counter and overflow flag: the two words behind them; a shape that
     //  prepare refused is refused on every rank alike, so the ranks agree on logActive)
     if (reduce(user, c->fluxOut(), (size_t)N * c->totalData, (void *)c->stream) != 0 ||
-        reduce(user, c->dCounters.p, 80 * std::max<size_t>(1, c->specs.size()), (void *)c->stream) != 0 ||
+        reduce(user, c->dCounters.p, counterWords, (void *)c->stream) != 0 ||
         (c->logActive && reduce(user, c->dDataLog.p, (size_t)c->logTotal + 2, (void *)c->stream) != 0))
       return fail(c, VR_E_HIP, "vr_apply_sharded: the all-reduce callback failed");
     if (r != VR_OK) {

@@ -139,7 +139,9 @@ struct ParticleSpec {
   int kind = 0;
   float sticking = 1.f, sourcePower = 1.f, coneAngle = 0.f, meanFreePath = -1.f;
   float params[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int userModel = -1; // kind >= VR_PARTICLE_USER_BASE: index of the run-time model
+  int userModel = -1;   // kind >= VR_PARTICLE_USER_BASE: index of the run-time model
+  int kernelKind = 0;   // the kind its kernel sees: inside its own code object a run-time model is the registry's last entry
+  uint32_t numData = 1; // its data labels
   std::vector<int32_t> matIds;
   std::vector<float> matVals;
 };
@@ -200,15 +202,9 @@ struct vr_context {
   int sourceDirection = -1; // -1: default by D (POS_Y for 2-D, POS_Z for 3-D)
   bool usePrimaryDirection = false;
   float primaryDirection[3] = {0, 0, 0};
-  bool haveParticle = false;
-  int particleKind = 0;
-  float coneAngle = 0.f, meanFreePath = -1.f;
   bool useWdist = false;
-  uint32_t numData = 1;           // data labels of the (active) particle
-  uint32_t totalData = 1;         // ... of all particles of the apply: accumulator planes, TracingData vectors
+  uint32_t totalData = 1;         // data labels of all particles of the apply: accumulator planes, TracingData vectors
   uint32_t accPlanes = 0;         // planes the accumulator buffers currently hold
-  float particleParams[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int userModel = -1;             // index into userModels when the active particle is a run-time model
   DevBuf<float> dRayState;            // a stateful model's per-ray state of one batch (the frame's VR_F_STATE_*), float4 per ray
   DevBuf<int32_t> dPrimMaterial;      // material id per original primitive for a stateful model (VR_F_MAT_*)
   // the data log (vr_set_data_log_shape): int64 sums of the log_data hooks, rows concatenated, the control words behind
@@ -221,8 +217,9 @@ struct vr_context {
   std::vector<unsigned long long> logHost;    // the last apply's sums + [dropped] (vr_get_data_log*)
   bool haveLog = false;
   std::vector<UserModel> userModels;
-  bool particleDirty = true;      // the sticking map needs recomputing
-  std::vector<ParticleSpec> specs;      // vr_set_particles: > 1 entries = a multi-particle apply
+  bool particleDirty = true;      // vr_set_particles: the sticking map needs recomputing
+  std::vector<ParticleSpec> specs;      // vr_set_particles (empty: none set yet): > 1 entries = a multi-particle apply
+  size_t numParticles() const { return std::max<size_t>(1, specs.size()); } // (what the per-particle buffers are sized for)
   std::vector<ParticleLaunch> launches; // prepared by vr_apply_prepare: one per particle (at least one)
   Knobs knobs;                          // the tuning switches, read by vr_apply_prepare
   // Trace::setGlobalData: vectors (padded to one stride) and scalars, resident in HBM
@@ -246,9 +243,6 @@ struct vr_context {
   bool sourceDirty = false;
   DevBuf<float> dGrid, dHostOrg, dHostDir, dHostWeights;
   DevBuf<uint32_t> dHostDraws;
-  float sticking = 1.f, sourcePower = 1.f;
-  std::vector<int32_t> matStickIds;
-  std::vector<float> matStickVals;
   uint64_t numRaysPerPoint = 1000, numRaysFixed = 0;
   uint32_t maxReflections = 0xFFFFFFFFu, maxBoundaryHits = 1000;
   uint32_t rngSeed = 0;
@@ -375,7 +369,6 @@ int fail(vr_context *c, int code, const char *msg);
 bool is_device_memory_of(const void *p, int device);
 int wait_for_caller(vr_context *c, hipStream_t stream);
 int caller_waits(vr_context *c, hipStream_t stream);
-void activate_particle(vr_context *c, const ParticleSpec &sp);
 // vr_knobs.cpp
 Knobs read_knobs();
 // vr_scene.cpp

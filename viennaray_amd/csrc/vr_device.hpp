@@ -74,7 +74,7 @@ __device__ __forceinline__ bool all6(bool a, bool b, bool c, bool d, bool e, boo
 }
 
 // -DVR_DIAG: lane-occupancy counters.  DIAG(k) inside any (divergent) region counts one
-// wave-level execution and the lanes that took part; summed into counters[16 + 2k, +1].
+// wave-level execution and the lanes that took part; summed into counters[C_DIAG + 2k, +1].
 #ifdef VR_DIAG
 #define VR_DIAG_DECL unsigned diagW[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, diagL[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define DIAG(k)                                                                                                        \
@@ -85,7 +85,7 @@ __device__ __forceinline__ bool all6(bool a, bool b, bool c, bool d, bool e, boo
     ++diagL[k];                                                                                                        \
   } while (0)
 // TICK(k): wave time (s_memtime, core clock) since the previous TICK goes to phase k; phaseT = this wave's
-// row of an LDS table, summed into counters[64 + k] at the end of the kernel
+// row of an LDS table, summed into counters[C_PHASE + k] at the end of the kernel
 #define TICK(k)                                                                                                        \
   do {                                                                                                                 \
     const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                                      \
@@ -816,7 +816,7 @@ __device__ __forceinline__ void pair_walk_lanes(const TraceParams &p, const uint
     node = VR_END;
   sp = node == 0u ? 0u : sp;
   const float invDD = 1.0f / vdot(d, d);
-  unsigned long long *const errFlag = p.counters + 60;
+  unsigned long long *const errFlag = p.counters + C_WALK_OVERFLOW;
   unsigned pend = 0u; // pending leaf word or 0
   for (;;) {
     bool parked = false; // at a second leaf while the first is still pending

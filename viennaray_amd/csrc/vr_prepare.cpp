@@ -1,5 +1,5 @@
 // vr_prepare.cpp — vr_apply_prepare: everything an apply() needs before its kernels run, one stage after the other
-// (prepare_one), for every particle of the apply.
+// (prepare_one), for every particle of the apply: each stage reads the ParticleSpec it is given.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -115,7 +115,7 @@ static StreamExtent stream_extent(int D, uint32_t cap, uint32_t perBin, bool rel
 // through the error flag.
 static int check_settings(vr_context *c) {
   c->info = vr_trace_info{};
-  if (!c->haveParticle) {
+  if (c->specs.empty()) {
     c->info.error = 1;
     return fail(c, VR_E_INVALID, "No particle was specified in rayTrace. Aborting.");
   }
@@ -243,9 +243,9 @@ static int compute_areas(vr_context *c) {
 }
 
 // per-primitive sticking from the material map (gpu::Particle-style, rayParticle.hpp:208-218), the particle's own buffer
-static int prepare_sticking(vr_context *c, ParticleLaunch &L) {
+static int prepare_sticking(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L) {
   L.params.primSticking = nullptr;
-  if (c->matStickIds.empty())
+  if (sp.matIds.empty())
     return VR_OK;
   int ro = ensure_host_order(c);
   if (ro != VR_OK)
@@ -255,10 +255,10 @@ static int prepare_sticking(vr_context *c, ParticleLaunch &L) {
   for (uint32_t q = 0; q < N; ++q) {
     const uint32_t o = c->bvh.order[q];
     const int mat = o < c->geo.materialIds.size() ? c->geo.materialIds[o] : 0;
-    float s = c->sticking;
-    for (size_t m = 0; m < c->matStickIds.size(); ++m)
-      if (c->matStickIds[m] == mat)
-        s = c->matStickVals[m];
+    float s = sp.sticking;
+    for (size_t m = 0; m < sp.matIds.size(); ++m)
+      if (sp.matIds[m] == mat)
+        s = sp.matVals[m];
     ps[q] = s;
   }
   VR_HIP(c, L.primSticking.ensure(N));
@@ -290,37 +290,37 @@ static int upload_global_data(vr_context *c) {
 
 // the particle's kernel variant (absorbing, built-in, extended, stateful), the small-scene layout and whether the scene
 // is flat
-static int choose_particle_kernel(vr_context *c, ParticleLaunch &L, PrepareState &S) {
+static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, PrepareState &S) {
   TraceParams &p = L.params;
   const uint32_t N = c->geo.numPrims;
   // ABSORB: every hit takes the whole weight -> nothing after the first
   // surface hit is observable
-  L.absorb = c->sticking >= 1.f;
-  for (float v : c->matStickVals)
+  L.absorb = sp.sticking >= 1.f;
+  for (float v : sp.matVals)
     L.absorb = L.absorb && v >= 1.f;
   // the extended kernel (vr_particles.hpp) serves everything beyond the two built-in particles
-  const bool extended = c->particleKind >= VR_PARTICLE_CONED_COSINE || c->useWdist || c->meanFreePath > 0.f;
+  const bool extended = sp.kernelKind >= VR_PARTICLE_CONED_COSINE || c->useWdist || sp.meanFreePath > 0.f;
   if (extended)
     L.absorb = false;
   if ((!c->hostOrg.empty() && !c->hostWeights.empty()) || c->surfCount)
     L.absorb = false; // (the absorbing kernels credit unit weights)
   // (the rare, register-hungry options — coned-cosine model, WDIST crediting, mean free path — have an instantiation
   //  of their own: multi-label and per-material particles should not pay for them)
-  bool extFull = Particles::needsFull(c->particleKind) || c->useWdist || c->meanFreePath > 0.f;
-  if (c->userModel >= 0) {
-    const UserModel &um = c->userModels[c->userModel];
-    if (extFull && !um.needsFull)
+  bool extFull = Particles::needsFull(sp.kernelKind) || c->useWdist || sp.meanFreePath > 0.f;
+  const UserModel *um = sp.userModel >= 0 ? &c->userModels[sp.userModel] : nullptr;
+  if (um) {
+    if (extFull && !um->needsFull)
       return fail(c, VR_E_INVALID, "this particle model was registered without VR_MODEL_NEEDS_FULL: its code object has no "
                                    "kernel with WDIST crediting / mean-free-path scattering");
-    extFull = um.needsFull;
-    if (um.numState > 0 && (!c->gridPoints.empty() || !c->hostOrg.empty() || c->surfCount))
+    extFull = um->needsFull;
+    if (um->numState > 0 && (!c->gridPoints.empty() || !c->hostOrg.empty() || c->surfCount))
       return fail(c, VR_E_INVALID, "a stateful particle model (numState > 0) runs its init on the device before the source "
                                    "sample: SourceRandom only (plain or with a primary direction), not SourceGrid, a host "
                                    "source or a surface source");
   }
-  S.stateful = c->userModel >= 0 && c->userModels[c->userModel].numState > 0;
-  S.logs = S.stateful && c->logActive && c->userModels[c->userModel].logRows > 0;
-  L.kernelParticle = extended ? (extFull ? (int)P_EXT_FULL : (int)P_EXT) : c->particleKind;
+  S.stateful = um && um->numState > 0;
+  S.logs = S.stateful && c->logActive && um->logRows > 0;
+  L.kernelParticle = extended ? (extFull ? (int)P_EXT_FULL : (int)P_EXT) : sp.kernelKind;
   // a scene of a few hundred primitives goes into LDS as a whole (MODE 4: the general kernel — also for
   // absorbing particles — of whatever particle): pair nodes, records, neighbourhood, accumulators (one plane
   // per data label), per-material sticking
@@ -337,7 +337,7 @@ static int choose_particle_kernel(vr_context *c, ParticleLaunch &L, PrepareState
     put(1, (size_t)N * recB);
     put(2, ((size_t)N + 1) * 4);
     put(3, (size_t)nbTotal * 4);
-    put(4, (size_t)N * 8 * c->numData);
+    put(4, (size_t)N * 8 * sp.numData);
     put(5, p.primSticking ? (size_t)N * 4 : 0);
     S.smallScene = o <= VR_SMALL_LDS && c->numNodes > 0 && c->knobs.smallScene;
     for (int k = 0; k < 6; ++k)
@@ -356,7 +356,7 @@ static int choose_particle_kernel(vr_context *c, ParticleLaunch &L, PrepareState
 // stretch its box over hundreds of cells.  Where the scene is thin along the source axis and the relief field says that
 // few rays would be grazing ones (ReliefParams::stats), the rays are sorted by their predicted first hit, the grazing ones are filed apart
 // (bin_of_relief, vr_trace.hip) and the query clips to the LOCAL relief (relief_clip, vr_device.hpp): MODE 5 / 6.
-static int build_relief_field(vr_context *c, ParticleLaunch &L, const PrepareState &S) {
+static int build_relief_field(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, const PrepareState &S) {
   const Knobs &K = c->knobs;
   TraceParams &p = L.params;
   const int D = c->geo.D;
@@ -365,7 +365,7 @@ static int build_relief_field(vr_context *c, ParticleLaunch &L, const PrepareSta
   const float thickScene = c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]];
   const bool plainSource = !c->usePrimaryDirection && c->gridPoints.empty() && c->hostOrg.empty() && !c->surfCount;
   const bool kernelOk = L.absorb || (c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT);
-  const bool want = !S.flatScene && !S.smallScene && plainSource && kernelOk && c->userModel < 0 && c->geo.gridDelta > 0.f &&
+  const bool want = !S.flatScene && !S.smallScene && plainSource && kernelOk && sp.userModel < 0 && c->geo.gridDelta > 0.f &&
                     thickScene <= K.reliefMaxThick * c->geo.gridDelta && !K.noRelief;
   if (want) {
     const bool stale = c->rfBuild != c->bvhBuilds || c->rfAxes[0] != c->ts[0] || c->rfAxes[1] != c->ts[1] ||
@@ -519,7 +519,7 @@ static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState 
 }
 
 // launch geometry of the persistent kernels: trace mode, the loose launch of a relief scene, blocks per CU
-static int choose_trace_mode(vr_context *c, ParticleLaunch &L, const PrepareState &S) {
+static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, const PrepareState &S) {
   const Knobs &K = c->knobs;
   const int D = c->geo.D;
   // absorbing particles: a (nearly) flat surface is served by packets alone; a structured one
@@ -553,8 +553,8 @@ static int choose_trace_mode(vr_context *c, ParticleLaunch &L, const PrepareStat
   int blocks = 1;
   L.userKernel = nullptr;
   L.userGen = nullptr;
-  if (c->userModel >= 0) { // the kernel of the model's own code object
-    const UserModel &um = c->userModels[c->userModel];
+  if (sp.userModel >= 0) { // the kernel of the model's own code object
+    const UserModel &um = c->userModels[sp.userModel];
     if (S.stateful && (L.absorb || (L.traceMode != 0 && L.traceMode != 4)))
       return fail(c, VR_E_STATE, "stateful particle model: only the general kernels (MODE 0 / 4) carry the state");
     L.userGen = S.stateful ? um.gen[D == 3 ? 1 : 0] : nullptr;
@@ -616,7 +616,7 @@ static int size_scratch(vr_context *c, const ParticleLaunch &L, const PrepareSta
 }
 
 // the launch's TraceParams (the shared buffers' addresses: launch_params, at launch time)
-static int fill_trace_params(vr_context *c, ParticleLaunch &L, PrepareState &S) {
+static int fill_trace_params(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, PrepareState &S) {
   const Knobs &K = c->knobs;
   TraceParams &p = L.params;
   const uint32_t N = c->geo.numPrims;
@@ -661,10 +661,10 @@ static int fill_trace_params(vr_context *c, ParticleLaunch &L, PrepareState &S) 
   p.wallTable = c->dWalls.p + (size_t)L.slot * VR_WALL_TABLE;
   p.planeStride = c->accStride * c->accReplicas;
   p.accStride = c->accStride;
-  p.numData = c->numData;
-  p.particleKind = c->particleKind;
-  p.meanFreePath = c->meanFreePath;
-  std::memcpy(p.particleParams, c->particleParams, sizeof(p.particleParams));
+  p.numData = sp.numData;
+  p.particleKind = sp.kernelKind;
+  p.meanFreePath = sp.meanFreePath;
+  std::memcpy(p.particleParams, sp.params, sizeof(p.particleParams));
   p.globalVec = (c->globalStride && !c->globalVecs.empty()) ? c->dGlobalVec.p : nullptr;
   p.globalScalars = c->globalScalars.empty() ? nullptr : c->dGlobalScalars.p;
   p.numGlobalVec = p.globalVec ? (uint32_t)c->globalVecs.size() : 0u;
@@ -673,7 +673,7 @@ static int fill_trace_params(vr_context *c, ParticleLaunch &L, PrepareState &S) 
   p.useWdist = c->useWdist ? 1 : 0;
   p.gridPoints = c->gridPoints.empty() ? nullptr : c->dGrid.p;
   p.gridCount = (uint32_t)(c->gridPoints.size() / 3);
-  p.eeGrid = 2.f / (c->sourcePower + 1); // raySourceGrid.hpp:22
+  p.eeGrid = 2.f / (sp.sourcePower + 1); // raySourceGrid.hpp:22
   p.hostOrg = c->hostOrg.empty() ? nullptr : c->dHostOrg.p;
   p.hostDir = c->hostOrg.empty() ? nullptr : c->dHostDir.p;
   p.hostDraws = c->hostDraws.empty() ? nullptr : c->dHostDraws.p;
@@ -689,7 +689,7 @@ static int fill_trace_params(vr_context *c, ParticleLaunch &L, PrepareState &S) 
     p.surfOffset = c->surfOffset;
   }
   p.accMask = c->accReplicas - 1u;
-  VR_HIP(c, c->dCounters.ensure(80 * c->launches.size()));
+  VR_HIP(c, c->dCounters.ensure(C_BLOCK * c->launches.size()));
   VR_HIP(c, c->dWorkQ.ensure(VR_QUEUES * VR_QUEUE_STRIDE));
   p.numQueues = VR_QUEUES;
   // a stateful model: its state buffer and the material ids of its hooks (the caller's id of the original primitive) go
@@ -721,8 +721,8 @@ static int fill_trace_params(vr_context *c, ParticleLaunch &L, PrepareState &S) 
   p.secondDir = c->ts[2];
   p.minMax = c->ts[3];
   p.posNeg = (float)c->ts[4];
-  p.ee = 1.f / (c->sourcePower + 1); // raySourceRandom.hpp:21
-  p.sticking = c->sticking;
+  p.ee = 1.f / (sp.sourcePower + 1); // raySourceRandom.hpp:21
+  p.sticking = sp.sticking;
   p.bc0 = c->boundaryConds[0];
   p.bc1 = c->boundaryConds[1];
   p.useBasis = c->usePrimaryDirection ? 1 : 0;
@@ -865,11 +865,10 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
   return VR_OK;
 }
 
-// everything one particle's launch needs (scene build and areas only when they changed), into L.  Every device call
+// everything the launch of particle `sp` needs (scene build and areas only when they changed), into L.  Every device call
 // goes to c->stream in this order.
-static int prepare_one(vr_context *c, ParticleLaunch &L) {
+static int prepare_one(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L) {
   VR_HIP(c, hipSetDevice(c->device));
-  VR_TRY(check_settings(c));
   const auto t0 = std::chrono::steady_clock::now();
   const bool redoConfig = c->configDirty || c->geometryDirty;
   if (redoConfig)
@@ -886,22 +885,23 @@ static int prepare_one(vr_context *c, ParticleLaunch &L) {
   }
   if (redoConfig || !c->areasValid)
     VR_TRY(compute_areas(c));
-  if (redoConfig || c->particleDirty)
-    VR_TRY(prepare_sticking(c, L));
+  // (the sticking map: one particle keeps its own from apply to apply; the particles of a list are prepared in turn, each time)
+  if (redoConfig || c->particleDirty || c->specs.size() > 1)
+    VR_TRY(prepare_sticking(c, sp, L));
   c->configDirty = false;
   c->particleDirty = false;
   if (c->globalDirty)
     VR_TRY(upload_global_data(c));
   PrepareState S;
-  VR_TRY(choose_particle_kernel(c, L, S));
-  VR_TRY(build_relief_field(c, L, S));
+  VR_TRY(choose_particle_kernel(c, sp, L, S));
+  VR_TRY(build_relief_field(c, sp, L, S));
   VR_TRY(ensure_accumulators(c));
   if (c->sourceDirty)
     VR_TRY(upload_source_data(c));
   VR_TRY(size_ray_stream(c, L, S));
-  VR_TRY(choose_trace_mode(c, L, S)); // (after the ray stream: blocks follow the batch size; the buffers keep the relief layout)
+  VR_TRY(choose_trace_mode(c, sp, L, S)); // (after the ray stream: blocks follow the batch size; the buffers keep the relief layout)
   VR_TRY(size_scratch(c, L, S));
-  VR_TRY(fill_trace_params(c, L, S));
+  VR_TRY(fill_trace_params(c, sp, L, S));
   VR_TRY(build_height_field(c, L, S));
   VR_TRY(write_launch_frame(c, L, S));
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -921,17 +921,11 @@ static int prepare_data_log(vr_context *c) {
   if (c->logRowSizes.empty())
     return VR_OK;
   int hooks = 0, rowsNeeded = 0;
-  auto look = [&](int userModel) {
-    if (userModel >= 0 && userModel < (int)c->userModels.size() && c->userModels[userModel].logRows > 0) {
+  for (const ParticleSpec &sp : c->specs)
+    if (sp.userModel >= 0 && c->userModels[sp.userModel].logRows > 0) {
       ++hooks;
-      rowsNeeded = std::max(rowsNeeded, c->userModels[userModel].logRows);
+      rowsNeeded = std::max(rowsNeeded, c->userModels[sp.userModel].logRows);
     }
-  };
-  if (c->specs.size() > 1)
-    for (const ParticleSpec &sp : c->specs)
-      look(sp.userModel);
-  else
-    look(c->userModel);
   if (!hooks)
     return fail(c, VR_E_INVALID, "a data-log shape is set (vr_set_data_log_shape) but no particle model of this apply has a "
                                  "log_data hook (kLogRows == 0): nothing would fill the log; clear the shape or use a "
@@ -968,9 +962,8 @@ int vr_apply_prepare(vr_context *c) {
   if (!c)
     return VR_E_INVALID;
   c->knobs = read_knobs();
-  const size_t nPart = std::max<size_t>(1, c->specs.size());
-  const bool multi = nPart > 1; // (one particle: vr_set_particles made it the active one already)
-  if (multi && c->useRandomSeed && !c->haveSharedSeed) { // one draw for all particles of this apply
+  const size_t nPart = c->numParticles();
+  if (nPart > 1 && c->useRandomSeed && !c->haveSharedSeed) { // one draw for all particles of this apply
     std::random_device rd;
     c->sharedSeed = (uint32_t)rd();
     c->haveSharedSeed = true;
@@ -980,28 +973,16 @@ int vr_apply_prepare(vr_context *c) {
     c->launches.clear();
     c->launches.resize(nPart);
   }
-  {
-    const int r = prepare_data_log(c);
-    if (r != VR_OK)
-      return r;
-  }
+  VR_TRY(prepare_data_log(c));
+  VR_TRY(check_settings(c)); // (refuses an empty particle list: behind it specs.size() == nPart)
   uint32_t base = 0;
-  for (size_t q = 0; q < nPart; ++q) {
-    if (multi)
-      activate_particle(c, c->specs[q]);
+  for (size_t q = 0; q < c->specs.size(); ++q) {
     ParticleLaunch &L = c->launches[q];
     L.slot = (uint32_t)q;
     L.dataBase = base;
-    const int r = prepare_one(c, L);
-    if (r != VR_OK) {
-      if (multi)
-        activate_particle(c, c->specs[0]);
-      return r;
-    }
-    base += c->numData;
+    VR_TRY(prepare_one(c, c->specs[q], L));
+    base += c->specs[q].numData;
   }
-  if (multi)
-    activate_particle(c, c->specs[0]); // (between applies the first particle is the active one)
   return VR_OK;
 }
 

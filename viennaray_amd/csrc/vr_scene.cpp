@@ -118,7 +118,7 @@ int build_scene(vr_context *c) {
     c->accStride = (N + 15u) & ~15u; // replicas start on 128-byte lines
     c->accPlanes = 0;                // (buffers are sized per data label in vr_apply_prepare)
   }
-  VR_HIP(c, c->dCounters.ensure(80));
+  VR_HIP(c, c->dCounters.ensure(C_BLOCK));
   VR_HIP(c, c->dNbOff.ensure((size_t)N + 1));
   if (K.hostBuild) {
     // host builder (validation path): LBVH + CSR on the CPU, uploaded

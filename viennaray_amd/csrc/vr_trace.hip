@@ -22,8 +22,6 @@
 //                   state machine (rayTraceKernel.hpp:155-335).
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "vr_device.hpp"
 #include "vr_kernels.hpp"
 #include "vr_particles.hpp"
@@ -1101,7 +1099,7 @@ trace_kernel(const TraceParams p) {
     const bool fin = active && (ORDERED ? node == VR_END : node >= p.numNodes); // this lane's geometry walk is complete
 #ifdef VR_SELFCHECK
     { // -DVR_SELFCHECK build: every finished segment again with the escape-link walk; disagreements are
-      // counted in counters[48], the first one is kept in counters[50..]
+      // counted in counters[C_CHECK], the first one is kept in counters[C_CHECK_RAY..]
       HitRec hb;
       hit_clear(hb);
       unsigned nb = fin ? 0u : VR_END;
@@ -1114,12 +1112,12 @@ trace_kernel(const TraceParams p) {
         hit_walls(p, wallS, org, dir, tnear, hc);
       }
       if (fin && (hb.geom != hc.geom || hb.t != hc.t || (hb.geom == 1 && hb.pos != hc.pos) || (hb.geom == 0 && hb.prim != hc.prim))) {
-        if (atomicAdd(&p.counters[48], 1ull) == 0ull) {
+        if (atomicAdd(&p.counters[C_CHECK], 1ull) == 0ull) {
           const float v[8] = {org.x, org.y, org.z, dir.x, dir.y, dir.z, hc.t, hb.t};
           for (int k = 0; k < 8; ++k)
-            p.counters[50 + k] = (unsigned long long)__float_as_uint(v[k]);
-          p.counters[58] = ((unsigned long long)hc.pos << 32) | hb.pos;
-          p.counters[59] = ((unsigned long long)(unsigned)hc.geom << 32) | (unsigned)hb.geom;
+            p.counters[C_CHECK_RAY + k] = (unsigned long long)__float_as_uint(v[k]);
+          p.counters[C_CHECK_POS] = ((unsigned long long)hc.pos << 32) | hb.pos;
+          p.counters[C_CHECK_GEOM] = ((unsigned long long)(unsigned)hc.geom << 32) | (unsigned)hb.geom;
         }
       }
     }
@@ -1681,12 +1679,12 @@ trace_kernel(const TraceParams p) {
 #ifdef VR_DIAG
   TICK(7);
   if (lane < 16 && phaseT[lane])
-    atomicAdd(&p.counters[64 + lane], phaseT[lane]);
+    atomicAdd(&p.counters[C_PHASE + lane], phaseT[lane]);
   for (int k = 0; k < 16; ++k) {
     const unsigned long long sw = wave_sum(diagW[k]), sl = wave_sum(diagL[k]);
     if (lane == 0 && sl) {
-      atomicAdd(&p.counters[16 + 2 * k], sw);
-      atomicAdd(&p.counters[16 + 2 * k + 1], sl);
+      atomicAdd(&p.counters[C_DIAG + 2 * k], sw);
+      atomicAdd(&p.counters[C_DIAG + 2 * k + 1], sl);
     }
   }
 #endif
@@ -1707,39 +1705,33 @@ trace_kernel(const TraceParams p) {
 // ---------------------------------------------------------------------------
 // host-callable launchers
 // ---------------------------------------------------------------------------
+// every generator and every trace kernel of the library: a kernel over the launch's TraceParams
+using StreamKernel = void (*)(const TraceParams);
+
+// source: SourceRandom (0: axis-aligned, 1: tilted primary direction), SourceGrid (2), host rays (3), surface source (4)
+static StreamKernel gen_kernel_for(int source, int D, bool keepRng, bool relief) {
+  const int v = (D == 2 ? 0 : 2) + (keepRng ? 1 : 0); // 2-D / 3-D, records without / with the RNG cursors
+  if (source == 0 && relief) { // the plain generator on a scene with relief: predicted-hit key, loose bins
+    static const StreamKernel reliefGen[4] = {gen_kernel<2, false, true>, gen_kernel<2, true, true>, gen_kernel<3, false, true>,
+                                              gen_kernel<3, true, true>};
+    return reliefGen[v];
+  }
+#define VR_GEN(DD, KEEP)                                                                                               \
+  {gen_kernel<DD, KEEP, false>, gen_basis_kernel<DD, KEEP>, gen_grid_kernel<DD, KEEP>, gen_host_kernel<DD, KEEP>,      \
+   gen_surface_kernel<DD, KEEP>}
+  static const StreamKernel gen[4][5] = {VR_GEN(2, false), VR_GEN(2, true), VR_GEN(3, false), VR_GEN(3, true)};
+#undef VR_GEN
+  return gen[v][source];
+}
+
 hipError_t launch_gen(const TraceParams &p, int D, bool keepRng, unsigned maxBlocks, hipStream_t s) {
   unsigned grid = (p.batchCount + VR_BLOCK - 1) / VR_BLOCK;
   if (grid == 0)
     return hipSuccess;
   if (grid > maxBlocks)
     grid = maxBlocks; // grid-stride; bounds the tier-2 slabs to grid waves
-  // source: SourceRandom (0: axis-aligned, 1: tilted primary direction), SourceGrid (2), host rays (3), surface source (4)
   const int src = p.surfPos ? 4 : (p.hostOrg ? 3 : (p.gridPoints ? 2 : (p.useBasis ? 1 : 0)));
-  const int key = src * 4 + (D == 2 ? 0 : 2) + (keepRng ? 1 : 0);
-  if (src == 0 && p.reliefCoarse && p.binCount) { // the plain generator on a scene with relief: predicted-hit key, loose bins
-    if (D == 2 && !keepRng)
-      hipLaunchKernelGGL((gen_kernel<2, false, true>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-    else if (D == 2)
-      hipLaunchKernelGGL((gen_kernel<2, true, true>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-    else if (!keepRng)
-      hipLaunchKernelGGL((gen_kernel<3, false, true>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-    else
-      hipLaunchKernelGGL((gen_kernel<3, true, true>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-    return hipGetLastError();
-  }
-#define VR_GEN(K, DD, KEEP)                                                                                           \
-  case K: hipLaunchKernelGGL((gen_kernel<DD, KEEP, false>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;               \
-  case 4 + K: hipLaunchKernelGGL((gen_basis_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;            \
-  case 8 + K: hipLaunchKernelGGL((gen_grid_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;             \
-  case 12 + K: hipLaunchKernelGGL((gen_host_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;            \
-  case 16 + K: hipLaunchKernelGGL((gen_surface_kernel<DD, KEEP>), dim3(grid), dim3(VR_BLOCK), 0, s, p); break;
-  switch (key) {
-    VR_GEN(0, 2, false)
-    VR_GEN(1, 2, true)
-    VR_GEN(2, 3, false)
-    VR_GEN(3, 3, true)
-  }
-#undef VR_GEN
+  hipLaunchKernelGGL(gen_kernel_for(src, D, keepRng, p.reliefCoarse && p.binCount), dim3(grid), dim3(VR_BLOCK), 0, s, p);
   return hipGetLastError();
 }
 
@@ -1767,81 +1759,60 @@ hipError_t launch_scan(unsigned *data, unsigned n, unsigned *tmp /* >= 2 * ceil(
   return hipGetLastError();
 }
 
-template <int D, int GEO, int PARTICLE>
-static hipError_t launch_trace_t(const TraceParams &p, int mode, unsigned grid, hipStream_t s) {
-  if (mode == 1)
-    hipLaunchKernelGGL((trace_kernel<D, GEO, 0, 1>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  else if (mode == 2)
-    hipLaunchKernelGGL((trace_kernel<D, GEO, 0, 2>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  else if (mode == 3 && GEO == 0 && PARTICLE <= P_EXT)
-    hipLaunchKernelGGL((trace_kernel<D, 0, ((PARTICLE > P_EXT) ? 0 : PARTICLE), 3>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  else if (mode == 4)
-    hipLaunchKernelGGL((trace_kernel<D, GEO, PARTICLE, 4>), dim3(grid), dim3(VR_BLOCK), p.smallBytes, s, p);
-  else if (mode == 5)
-    hipLaunchKernelGGL((trace_kernel<D, GEO, 0, 5>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  else if (mode == 6 && GEO == 0 && PARTICLE <= P_EXT)
-    hipLaunchKernelGGL((trace_kernel<D, 0, ((PARTICLE > P_EXT) ? 0 : PARTICLE), 6>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  else if (mode == 7 && GEO == 0 && PARTICLE <= P_EXT)
-    hipLaunchKernelGGL((trace_kernel<D, 0, ((PARTICLE > P_EXT) ? 0 : PARTICLE), 7>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  else
-    hipLaunchKernelGGL((trace_kernel<D, GEO, PARTICLE, 0>), dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  return hipGetLastError();
-}
-
-// mode: 0 general, 1 absorbing + flat scene, 2 absorbing + structured scene
+// The trace kernel of a launch.
+// mode: 0 general, 1 absorbing + flat scene, 2 absorbing + structured scene, 3 general + flat scene of disks (packet-query
+// crediting), 4 scene resident in LDS, 5 / 6 the tight bins of a flat scene with relief (absorbing / general), 7 its
+// loose bins and the spilled rays (general); 3, 6 and 7 exist for disks and the lean particles only: otherwise mode 0
 // particle: 0 DiffuseParticle, 1 SpecularParticle, 2 (P_EXT) extended kernel, 3 (P_EXT_FULL) ... with the coned-cosine
 // model, WDIST crediting and mean-free-path scattering (always mode 0 or 4)
-template <class F> static auto dispatch_variant(int D, int geo, int particle, F &&f) {
-  const int key = (D == 2 ? 0 : 8) + (geo ? 4 : 0) + particle;
+template <int D, int GEO, int PARTICLE> static StreamKernel trace_kernel_of(int mode) {
+  constexpr bool FLAT = GEO == 0 && PARTICLE <= P_EXT; // (the flat-scene general kernels exist)
+  switch (mode) {
+  case 1: return trace_kernel<D, GEO, 0, 1>;
+  case 2: return trace_kernel<D, GEO, 0, 2>;
+  case 3:
+    if constexpr (FLAT)
+      return trace_kernel<D, 0, PARTICLE, 3>;
+    break;
+  case 4: return trace_kernel<D, GEO, PARTICLE, 4>;
+  case 5: return trace_kernel<D, GEO, 0, 5>;
+  case 6:
+    if constexpr (FLAT)
+      return trace_kernel<D, 0, PARTICLE, 6>;
+    break;
+  case 7:
+    if constexpr (FLAT)
+      return trace_kernel<D, 0, PARTICLE, 7>;
+    break;
+  }
+  return trace_kernel<D, GEO, PARTICLE, 0>;
+}
+static StreamKernel trace_kernel_for(int D, int geo, int particle, int mode) {
+  if (mode == 1 || mode == 2 || mode == 5)
+    particle = 0; // the reflection model is unobservable: one instantiation serves all
 #define VR_VARIANT(K, DD, GG, PP)                                                                                      \
-  case K: return f(std::integral_constant<int, DD>{}, std::integral_constant<int, GG>{}, std::integral_constant<int, PP>{});
-  switch (key) {
+  case K: return trace_kernel_of<DD, GG, PP>(mode);
+  switch ((D == 2 ? 0 : 8) + (geo ? 4 : 0) + particle) {
     VR_VARIANT(0, 2, 0, 0) VR_VARIANT(1, 2, 0, 1) VR_VARIANT(2, 2, 0, 2) VR_VARIANT(3, 2, 0, 3)
     VR_VARIANT(4, 2, 1, 0) VR_VARIANT(5, 2, 1, 1) VR_VARIANT(6, 2, 1, 2) VR_VARIANT(7, 2, 1, 3)
     VR_VARIANT(8, 3, 0, 0) VR_VARIANT(9, 3, 0, 1) VR_VARIANT(10, 3, 0, 2) VR_VARIANT(11, 3, 0, 3)
     VR_VARIANT(12, 3, 1, 0) VR_VARIANT(13, 3, 1, 1) VR_VARIANT(14, 3, 1, 2)
-  default: return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 3>{});
+  default: return trace_kernel_of<3, 1, 3>(mode);
   }
 #undef VR_VARIANT
 }
 
 hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid,
                         hipStream_t s) {
-  if (mode == 1 || mode == 2 || mode == 5)
-    particle = 0; // the reflection model is unobservable: one instantiation serves all
-  return dispatch_variant(D, geo, particle, [&](auto d, auto g, auto pt) {
-    return launch_trace_t<decltype(d)::value, decltype(g)::value, decltype(pt)::value>(p, mode, grid, s);
-  });
-}
-
-template <int D, int GEO, int PARTICLE> static int occ_t(int mode, unsigned smallBytes) {
-  int nb = 0;
-  hipError_t e;
-  if (mode == 1)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<D, GEO, 0, 1>, VR_BLOCK, 0);
-  else if (mode == 2)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<D, GEO, 0, 2>, VR_BLOCK, 0);
-  else if (mode == 3 && GEO == 0 && PARTICLE <= P_EXT)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<D, 0, ((PARTICLE > P_EXT) ? 0 : PARTICLE), 3>, VR_BLOCK, 0);
-  else if (mode == 4)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<D, GEO, PARTICLE, 4>, VR_BLOCK, smallBytes);
-  else if (mode == 5)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<D, GEO, 0, 5>, VR_BLOCK, 0);
-  else if (mode == 6 && GEO == 0 && PARTICLE <= P_EXT)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<D, 0, ((PARTICLE > P_EXT) ? 0 : PARTICLE), 6>, VR_BLOCK, 0);
-  else if (mode == 7 && GEO == 0 && PARTICLE <= P_EXT)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<D, 0, ((PARTICLE > P_EXT) ? 0 : PARTICLE), 7>, VR_BLOCK, 0);
-  else
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<D, GEO, PARTICLE, 0>, VR_BLOCK, 0);
-  return e == hipSuccess ? nb : 2;
+  hipLaunchKernelGGL(trace_kernel_for(D, geo, particle, mode), dim3(grid), dim3(VR_BLOCK), mode == 4 ? p.smallBytes : 0, s, p);
+  return hipGetLastError();
 }
 
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes) {
-  if (mode == 1 || mode == 2 || mode == 5)
-    particle = 0;
-  return dispatch_variant(D, geo, particle, [&](auto d, auto g, auto pt) {
-    return occ_t<decltype(d)::value, decltype(g)::value, decltype(pt)::value>(mode, smallBytes);
-  });
+  int nb = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel_for(D, geo, particle, mode), VR_BLOCK,
+                                                                    mode == 4 ? smallBytes : 0);
+  return e == hipSuccess ? nb : 2;
 }
 
 // ---- diagnostics -----------------------------------------------------------

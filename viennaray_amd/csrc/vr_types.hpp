@@ -100,7 +100,7 @@ struct TraceParams {
   float eeGrid;
   const float *hostOrg, *hostDir;
   const uint32_t *hostDraws;
-  unsigned long long *counters;  // [8]
+  unsigned long long *counters;  // [C_BLOCK]: the particle's counter block (C_*, below)
   unsigned long long *workCounter; // numQueues span cursors, VR_QUEUE_STRIDE words apart (a 128-byte line each)
   unsigned long long *rngScratch; // [waves][312][64]
   // ray stream of the current batch: VR_BIN_CAP record slots per sort bin, then the
@@ -265,7 +265,7 @@ enum { P_DIFFUSE = 0, P_SPECULAR = 1, P_CONED_COSINE = 2, P_DIFFUSE_COSINE = 3, 
                          (rare options that cost every particle of the instantiation registers: 157 spilled VGPRs
                          with them, 27 without) */ };
 
-// counters[] slots
+// counters[] slots: every particle of an apply has one block of C_BLOCK words (TraceParams::counters points at it)
 enum {
   C_TRACES = 0,
   C_NONGEO,
@@ -275,7 +275,19 @@ enum {
   C_REFLECTIONS,
   C_TERMINATED,
   C_TIER2,      // diagnostic: rays that needed the full-state RNG
-  C_COUNT
+  C_COUNT,
+  C_DIAG = 16,          // -DVR_DIAG: DIAG(k)'s wave-iterations at C_DIAG + 2k, its lane-iterations behind them, k < 16
+  C_CHECK = 48,         // -DVR_SELFCHECK: segments that disagree with the escape-link walk
+  C_CHECK_RAY = 50,     // ... the first of them: origin, direction, t of the kernel's hit and of the walk's (8 float words)
+  C_CHECK_POS = 58,     // ... its wall positions (kernel's << 32 | walk's)
+  C_CHECK_GEOM = 59,    // ... and its geometry ids, packed alike
+  C_WALK_OVERFLOW = 60, // the walk's stack ran out; a failed rank of a sharded apply raises it too
+  C_ACC_OVERFLOW = 61,  // a flux accumulator left its range (gather_flux_kernel; block 0)
+  C_SHARED_SEED = 63,   // vr_apply_sharded: rank 0's seed on its way round the all-reduce (block 0, before the launch)
+  C_PHASE = 64,         // -DVR_DIAG: wave time of TICK(k)'s phase at C_PHASE + k, k < 16
+  C_BLOCK = 80
 };
+static_assert(C_COUNT <= C_DIAG && C_DIAG + 2 * 16 <= C_CHECK && C_CHECK_GEOM < C_WALK_OVERFLOW && C_PHASE + 16 <= C_BLOCK,
+              "the parts of a counter block overlap");
 
 } // namespace vr
