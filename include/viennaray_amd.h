@@ -129,6 +129,12 @@ int vr_set_triangles(vr_context *ctx, const float *verts, uint32_t nverts,
                      const uint32_t *tris, uint32_t ntris, float gridDelta, int D);
 /* setMaterialIds (rayGeometry.hpp:17-24)                                    */
 int vr_set_material_ids(vr_context *ctx, const int32_t *ids, uint32_t n);
+/* vr_set_material_ids for ids that live on the device: ids is a DEVICE pointer on ctx's device to n int32 in the
+ * caller's primitive order, produced on `stream` (NULL = the null stream).  A primitive beyond n has id 0; a geometry
+ * with another primitive count resets the ids to 0.  One device-to-device copy, ordered by events on both sides as in
+ * vr_set_global_data_device; the per-primitive sticking of a material-dependent particle and a stateful model's
+ * material ids are then made on the device.  A refusal (not device memory of ctx's device) leaves the previous ids. */
+int vr_set_material_ids_device(vr_context *ctx, const int32_t *ids, uint32_t n, void *stream);
 
 /* ---- configuration (rayTrace.hpp:41-121) -------------------------------- */
 int vr_set_boundary_conditions(vr_context *ctx, const int32_t *bcs, int n /* = D */);
@@ -171,6 +177,15 @@ int vr_register_particle_model_ex(vr_context *ctx, const char *name, const char 
  * copied to HBM and readable by the device particle models.  data == NULL drops the vector and those behind it. */
 int vr_set_global_data(vr_context *ctx, uint32_t vecIdx, const float *data, uint32_t n);
 int vr_set_global_scalars(vr_context *ctx, const float *data, uint32_t n);
+/* vr_set_global_data for a vector that already lives on the device (coverages computed from the flux tensor).  data: a
+ * DEVICE pointer on ctx's device, n floats; `stream`: the hipStream_t it was produced on (NULL = the null stream).  Same
+ * semantics as vr_set_global_data (at most 16 vectors, any length, 0 beyond its length, data == NULL or n == 0 drops the
+ * vector and those behind it); host-set and device-set vectors may be mixed on one context in any order.  The library's
+ * stream waits for `stream` by an event, a kernel copies the vector into place, and `stream` waits for that copy: the
+ * caller may overwrite its buffer with work queued on `stream` afterwards.  No host synchronisation unless the resident
+ * rows have to move (a vector longer than any before, more vectors than before).  Refuses pointers that are not device
+ * memory of ctx's device; a refusal leaves the vectors as they were.                                           */
+int vr_set_global_data_device(vr_context *ctx, uint32_t vecIdx, const float *data, uint32_t n, void *stream);
 /* VIENNARAY_USE_WDIST (CMakeLists.txt:15, rayTraceKernel.hpp:258-296) as a run-time switch: a hit's
  * weight is shared among the credited disks by inverse impact distance                       */
 int vr_set_use_wdist(vr_context *ctx, int on);
@@ -195,6 +210,15 @@ int vr_set_source_area(vr_context *ctx, float area);
  * rays, and is replaced by them; n == 0 = clearSurfaceSource().  An invalid argument leaves the previous source set.   */
 int vr_set_surface_source(vr_context *ctx, const float *positions3, const float *normals3, const float *weights, uint32_t n,
                           float sourceArea, float sourceOffset);
+/* vr_set_surface_source for tables that live on the device (the surface the tracer already holds, weights computed from
+ * the first pass's flux tensor).  positions / normals: DEVICE pointers on ctx's device to n rows of `ld` floats (2 or 3;
+ * 2 only on a 2-D geometry, the third column then reads 0), weights: n floats, all produced on `stream` (NULL = the null
+ * stream).  sourceArea / sourceOffset are checked on the host; the rows are checked on the device by the kernel that
+ * packs them — position finite, normal of positive finite length, weight finite and >= 0 — and ONE word comes back: a
+ * refusal names the row and the check that vr_set_surface_source would have named, in the same words, and leaves the
+ * previous source in place.  On return the library holds its own copy.  n == 0 = clearSurfaceSource().              */
+int vr_set_surface_source_device(vr_context *ctx, const float *positions, const float *normals, const float *weights,
+                                 uint32_t n, uint32_t ld, float sourceArea, float sourceOffset, void *stream);
 int vr_set_number_of_rays_per_point(vr_context *ctx, uint64_t n);
 int vr_set_number_of_rays_fixed(vr_context *ctx, uint64_t n);
 int vr_set_max_reflections(vr_context *ctx, uint32_t n);

@@ -1141,6 +1141,28 @@ public:
     if (ctx_)
       check(vr_set_surface_source(ctx_, nullptr, nullptr, nullptr, 0, 0.f, 0.f));
   }
+  /// setSurfaceSource for tables that live on the device (vr_set_surface_source_device): dPositions / dNormals are
+  /// DEVICE pointers to n rows of `ld` floats (2 or 3; 2 only for D == 2), dWeights to n floats, produced on `stream`
+  /// (the caller's hipStream_t, nullptr = the null stream).  Packed and validated on the device; a refusal names the row
+  /// as the host setter would and leaves the previous source in place.  The buffers are free again on return.
+  void setSurfaceSourceDevice(const float *dPositions, const float *dNormals, const float *dWeights, size_t n, unsigned ld,
+                              NumericType sourceArea, NumericType sourceOffset, void *stream = nullptr) {
+    if (!ctx_)
+      return;
+    const int rc = vr_set_surface_source_device(ctx_, dPositions, dNormals, dWeights, (uint32_t)n, ld, (float)sourceArea,
+                                                (float)sourceOffset, stream);
+    check(rc);
+    if (rc == VR_OK && n) {
+      pSource_.reset();
+      sourceOnDevice_ = false;
+    }
+  }
+  /// setMaterialIds for ids that live on the device (vr_set_material_ids_device): n int32 in the caller's primitive
+  /// order, produced on `stream`; a primitive beyond n has id 0.
+  void setMaterialIdsDevice(const int32_t *dIds, size_t n, void *stream = nullptr) {
+    if (ctx_)
+      check(vr_set_material_ids_device(ctx_, dIds, (uint32_t)n, stream));
+  }
   void enableProgressBar() {}
   void disableProgressBar() {}
 
@@ -1167,7 +1189,27 @@ public:
   // rayTrace.hpp:137-145: global data is a borrowed pointer handed to user particles; apply() copies its vectors and
   // scalars to the device, where the registry's particle models read them (ModelCtx::global)
   [[nodiscard]] TracingData<NumericType> *getGlobalData() { return pGlobalData_; }
-  void setGlobalData(TracingData<NumericType> &data) { pGlobalData_ = &data; }
+  void setGlobalData(TracingData<NumericType> &data) {
+    pGlobalData_ = &data;
+    deviceGlobal_ = 0; // (the borrowed data is the global data again, all of it)
+  }
+  /// Vector `vecIdx` of the global data from DEVICE memory (vr_set_global_data_device): n floats produced on `stream`
+  /// (the caller's hipStream_t, nullptr = the null stream), copied into place on the device; the buffer is free for work
+  /// queued on `stream` afterwards.  The index then belongs to the device: apply() leaves it alone, whatever the
+  /// borrowed TracingData holds at that index, until setGlobalData(TracingData &) is called again.  dData == nullptr or
+  /// n == 0 drops the vector and those behind it.
+  void setGlobalDataDevice(unsigned vecIdx, const float *dData, size_t n, void *stream = nullptr) {
+    if (!ctx_)
+      return;
+    const int rc = vr_set_global_data_device(ctx_, vecIdx, dData, (uint32_t)n, stream);
+    check(rc);
+    if (rc != VR_OK)
+      return;
+    if (dData && n)
+      deviceGlobal_ |= 1u << vecIdx;
+    else
+      deviceGlobal_ &= (1u << vecIdx) - 1u;
+  }
   [[nodiscard]] TraceInfo getRayTraceInfo() const { return RTInfo_; }
   [[nodiscard]] DataLog<NumericType> &getDataLog() { return dataLog_; }
   /// the underlying C-ABI context (multi-GPU drivers use vr_set_ray_range etc.)
@@ -1226,20 +1268,49 @@ protected:
   void uploadGlobalData() {
     if (!ctx_)
       return;
-    check(vr_set_global_data(ctx_, 0, nullptr, 0));
+    if (deviceGlobal_) {
+      uploadGlobalDataAround();
+    } else {
+      check(vr_set_global_data(ctx_, 0, nullptr, 0));
+      if (pGlobalData_) {
+        const auto &vecs = pGlobalData_->getVectorData();
+        for (size_t v = 0; v < vecs.size() && v < 16; ++v) {
+          std::vector<float> tmp(vecs[v].begin(), vecs[v].end());
+          if (!tmp.empty())
+            check(vr_set_global_data(ctx_, (uint32_t)v, tmp.data(), (uint32_t)tmp.size()));
+        }
+      }
+    }
     check(vr_set_global_scalars(ctx_, nullptr, 0));
     if (!pGlobalData_)
       return;
-    const auto &vecs = pGlobalData_->getVectorData();
-    for (size_t v = 0; v < vecs.size() && v < 16; ++v) {
-      std::vector<float> tmp(vecs[v].begin(), vecs[v].end());
-      if (!tmp.empty())
-        check(vr_set_global_data(ctx_, (uint32_t)v, tmp.data(), (uint32_t)tmp.size()));
-    }
     const auto &sc = pGlobalData_->getScalarData();
     std::vector<float> st(sc.begin(), sc.end());
     if (!st.empty())
       check(vr_set_global_scalars(ctx_, st.data(), (uint32_t)st.size()));
+  }
+  // ... with indices that were set from the device (setGlobalDataDevice): those stay as they are; every other index up
+  // to the last one in use gets the borrowed vector, or one zero (which reads as the missing vector does: 0 everywhere)
+  // where the borrowed data has none — dropping a vector would take the device-set ones behind it along
+  void uploadGlobalDataAround() {
+    static const std::vector<std::vector<NumericType>> none;
+    const auto &vecs = pGlobalData_ ? pGlobalData_->getVectorData() : none;
+    unsigned last = 0;
+    for (unsigned v = 0; v < 16; ++v)
+      if (((deviceGlobal_ >> v) & 1u) || (v < vecs.size() && !vecs[v].empty()))
+        last = v;
+    for (unsigned v = 0; v <= last; ++v) {
+      if ((deviceGlobal_ >> v) & 1u)
+        continue;
+      std::vector<float> tmp;
+      if (v < vecs.size())
+        tmp.assign(vecs[v].begin(), vecs[v].end());
+      if (tmp.empty())
+        tmp.assign(1, 0.f);
+      check(vr_set_global_data(ctx_, v, tmp.data(), (uint32_t)tmp.size()));
+    }
+    if (last + 1 < 16)
+      check(vr_set_global_data(ctx_, last + 1, nullptr, 0));
   }
   // A user Source is a host callback (raySource.hpp:10-19): evaluate it for every ray of the coming
   // apply() exactly as the reference's loop would (rayTraceKernel.hpp:118-140: engine seeded with
@@ -1319,6 +1390,7 @@ protected:
   std::vector<std::unique_ptr<AbstractParticle<NumericType>>> moreParticles_; // setParticleTypes: particles 1 ..
   TracingData<NumericType> localData_;
   TracingData<NumericType> *pGlobalData_ = nullptr;
+  unsigned deviceGlobal_ = 0; // bit v: vector v of the global data was set from the device (setGlobalDataDevice)
   DataLog<NumericType> dataLog_;
   std::vector<int32_t> particleKinds_; // the device kinds of pParticle_ and moreParticles_
   std::shared_ptr<Source<NumericType>> pSource_;

@@ -56,6 +56,7 @@ SIGNATURES = {
     "vr_set_disks_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_int, _vp]),
     "vr_set_triangles": (C.c_int, [_vp, _fp, C.c_uint32, _u32p, C.c_uint32, C.c_float, C.c_int]),
     "vr_set_material_ids": (C.c_int, [_vp, _i32p, C.c_uint32]),
+    "vr_set_material_ids_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "vr_set_boundary_conditions": (C.c_int, [_vp, _i32p, C.c_int]),
     "vr_set_source_direction": (C.c_int, [_vp, C.c_int]),
     "vr_set_primary_direction": (C.c_int, [_vp, _fp]),
@@ -64,6 +65,7 @@ SIGNATURES = {
     "vr_register_particle_model": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, _i32p]),
     "vr_register_particle_model_ex": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, _i32p]),
     "vr_set_global_data": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
+    "vr_set_global_data_device": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     "vr_set_global_scalars": (C.c_int, [_vp, _fp, C.c_uint32]),
     "vr_get_particle_trace_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(TraceInfoPOD)]),
     "vr_set_use_wdist": (C.c_int, [_vp, C.c_int]),
@@ -72,6 +74,7 @@ SIGNATURES = {
     "vr_set_host_ray_weights": (C.c_int, [_vp, _fp, C.c_uint64]),
     "vr_set_source_area": (C.c_int, [_vp, C.c_float]),
     "vr_set_surface_source": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, C.c_float, C.c_float]),
+    "vr_set_surface_source_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, _vp]),
     "vr_reserve_rays": (C.c_int, [_vp, C.c_uint64]),
     "vr_set_number_of_rays_per_point": (C.c_int, [_vp, C.c_uint64]),
     "vr_set_number_of_rays_fixed": (C.c_int, [_vp, C.c_uint64]),

@@ -8,6 +8,7 @@
 //   vr_apply.cpp    vr_apply_launch / _finish, vr_apply, vr_apply_sharded
 //   vr_results.cpp  flux, TraceInfo and data-log getters, normalise, smooth, areas
 //   vr_debug.cpp    the vr_debug_* entry points
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -62,6 +63,58 @@ static void invalidate_geometry(vr_context *c) {
   c->geometryDirty = true;
   c->configDirty = true;
   c->prepared = c->haveResult = false;
+}
+
+// host_set_disks / host_set_triangles keep the material ids of a geometry with the same primitive count and reset them
+// to 0 otherwise: the same for ids that were set from the device (call before the new geometry is taken)
+static void material_ids_follow(vr_context *c, uint32_t n) {
+  if (c->materialOnDevice) {
+    if (c->materialCount == n)
+      return;
+    c->materialOnDevice = false;
+    c->geo.materialIds.clear(); // (host_set_* / vr_set_disks_device make it n zeros)
+    c->materialStale = true;
+  } else if (c->geo.materialIds.size() != n) {
+    c->materialStale = true;
+  }
+}
+
+// the per-row refusals of a surface source, in the order they are checked: 0 position, 1 normal, 2 weight
+static std::string surface_row_error(int kind, uint64_t row) {
+  const std::string j = std::to_string(row);
+  return kind == 0   ? "vr_set_surface_source: position " + j + " is not finite"
+         : kind == 1 ? "vr_set_surface_source: normal " + j + " has zero or non-finite length"
+                     : "vr_set_surface_source: weight " + j + " is negative or not finite";
+}
+// ... and of its scalars (nullptr: accepted)
+static const char *surface_scalar_error(float sourceArea, float sourceOffset) {
+  if (!(sourceArea > 0.f) || !std::isfinite(sourceArea))
+    return "vr_set_surface_source: sourceArea must be positive and finite";
+  if (!(sourceOffset >= 0.f) || !std::isfinite(sourceOffset))
+    return "vr_set_surface_source: sourceOffset must be finite and >= 0";
+  return nullptr;
+}
+// a surface source of n points is in dSurfPos / dSurfNrm / dSurfWeights: it takes the place of every other source
+static void surface_source_accepted(vr_context *c, uint32_t n, float sourceArea, float sourceOffset) {
+  c->surfCount = n;
+  c->surfArea = sourceArea;
+  c->surfOffset = sourceOffset;
+  c->gridPoints.clear();
+  c->hostOrg.clear();
+  c->hostDir.clear();
+  c->hostDraws.clear();
+  c->hostWeights.clear();
+  c->prepared = false;
+}
+
+// vector vecIdx and every one behind it are gone (vr_set_global_data* with no data)
+static void drop_global_from(vr_context *c, uint32_t vecIdx) {
+  c->globalRows.resize(c->globalVecs.size());
+  if (vecIdx < c->globalVecs.size()) {
+    c->globalVecs.resize(vecIdx);
+    c->globalRows.resize(vecIdx);
+  }
+  c->globalRowsLaid = std::min(c->globalRowsLaid, (uint32_t)c->globalVecs.size());
 }
 
 } // namespace vr
@@ -130,6 +183,7 @@ int vr_set_disks(vr_context *c, const float *points, const float *normals, uint3
                  float diskRadius, int D) {
   if (!c || !points || !normals || (D != 2 && D != 3) || n >= (1u << 27))
     return fail(c, VR_E_INVALID, "vr_set_disks: bad argument");
+  material_ids_follow(c, n);
   host_set_disks(c->geo, points, normals, n, gridDelta, diskRadius, D);
   invalidate_geometry(c);
   return VR_OK;
@@ -157,6 +211,7 @@ int vr_set_disks_device(vr_context *c, const float *points, const float *normals
   VR_HIP(c, c->dIngestBounds.ensure(6));
   // from here on the resident buffers no longer hold the previous geometry
   invalidate_geometry(c);
+  material_ids_follow(c, n);
   HostGeometry &g = c->geo;
   g.numPrims = 0; // (until the new one is in place: an error below leaves "no geometry", not half of one)
   g.disk4.clear();
@@ -179,7 +234,7 @@ int vr_set_disks_device(vr_context *c, const float *points, const float *normals
     g.minC[k] = k < D ? b[k] : 0.f;
     g.maxC[k] = k < D ? b[3 + k] : 0.f;
   }
-  if (g.materialIds.size() != n)
+  if (!c->materialOnDevice && g.materialIds.size() != n)
     g.materialIds.assign(n, 0);
   g.nbOff.clear();
   g.nbIds.clear();
@@ -197,6 +252,7 @@ int vr_set_triangles(vr_context *c, const float *verts, uint32_t nverts, const u
   for (size_t i = 0; i < (size_t)ntris * 3; ++i)
     if (tris[i] >= nverts)
       return fail(c, VR_E_INVALID, "vr_set_triangles: vertex index out of range");
+  material_ids_follow(c, ntris);
   host_set_triangles(c->geo, verts, nverts, tris, ntris, gridDelta, D);
   invalidate_geometry(c);
   return VR_OK;
@@ -206,8 +262,40 @@ int vr_set_material_ids(vr_context *c, const int32_t *ids, uint32_t n) {
   if (!c || !ids)
     return fail(c, VR_E_INVALID, "vr_set_material_ids: bad argument");
   c->geo.materialIds.assign(ids, ids + n);
+  c->materialOnDevice = false;
+  c->materialStale = true;
   c->prepared = false;
   c->configDirty = true;
+  return VR_OK;
+}
+
+// vr_set_material_ids for ids that live on the device: one device-to-device copy on the context's stream, behind what
+// `stream` holds; geo.materialIds is not filled.  Only the sticking maps follow from the ids: nothing else is redone.
+int vr_set_material_ids_device(vr_context *c, const int32_t *ids, uint32_t n, void *stream) {
+  if (!c || (n && !ids))
+    return fail(c, VR_E_INVALID, "vr_set_material_ids_device: bad argument");
+  VR_HIP(c, hipSetDevice(c->device));
+  if (n && !is_device_memory_of(ids, c->device))
+    return fail(c, VR_E_INVALID, "vr_set_material_ids_device: ids are not device memory of the context's device");
+  if (n == 0) { // (as vr_set_material_ids with no ids: every primitive has id 0)
+    c->geo.materialIds.clear();
+    c->materialOnDevice = false;
+    c->materialStale = true;
+  } else {
+    hipStream_t caller = (hipStream_t)stream;
+    if (n > c->dMaterialIds.cap || !c->dMaterialIds.p) {
+      VR_HIP(c, hipStreamSynchronize(c->stream)); // (the buffer moves: nothing may still read it)
+      VR_HIP(c, c->dMaterialIds.ensure(n));
+    }
+    VR_TRY(wait_for_caller(c, caller));
+    VR_HIP(c, hipMemcpyAsync(c->dMaterialIds.p, ids, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
+    VR_TRY(caller_waits(c, caller));
+    c->materialCount = n;
+    c->materialOnDevice = true;
+    c->materialStale = false;
+  }
+  c->particleDirty = true;
+  c->prepared = false;
   return VR_OK;
 }
 
@@ -305,15 +393,51 @@ int vr_set_global_data(vr_context *c, uint32_t vecIdx, const float *data, uint32
   if (!c || vecIdx >= 16 || (n && !data))
     return fail(c, VR_E_INVALID, "vr_set_global_data: bad argument (at most 16 vectors)");
   if (!data || n == 0) {
-    if (vecIdx < c->globalVecs.size())
-      c->globalVecs.resize(vecIdx);
+    drop_global_from(c, vecIdx);
   } else {
     if (c->globalVecs.size() <= vecIdx)
       c->globalVecs.resize(vecIdx + 1);
+    c->globalRows.resize(c->globalVecs.size());
     c->globalVecs[vecIdx].assign(data, data + n);
+    c->globalRows[vecIdx].len = n;
+    c->globalRows[vecIdx].onDevice = false;
+    c->globalRows[vecIdx].pending = true;
   }
   c->globalDirty = true;
   c->prepared = false;
+  return VR_OK;
+}
+// vr_set_global_data for a vector that lives on the device.  The row is written where the kernels read it, now: the
+// context's stream waits for `stream`, one kernel copies the vector into its row of dGlobalVec (zeros up to the stride),
+// and `stream` waits for that copy, so the caller may reuse its buffer at once.  Nothing synchronises with the host
+// unless the rows have to move (a longer vector than any before, more vectors than before).
+int vr_set_global_data_device(vr_context *c, uint32_t vecIdx, const float *data, uint32_t n, void *stream) {
+  if (!c || vecIdx >= 16)
+    return fail(c, VR_E_INVALID, "vr_set_global_data_device: bad argument (at most 16 vectors)");
+  if (!data || n == 0) { // (the rows that stay are where they were: nothing to upload)
+    drop_global_from(c, vecIdx);
+    c->prepared = false;
+    return VR_OK;
+  }
+  VR_HIP(c, hipSetDevice(c->device));
+  if (!is_device_memory_of(data, c->device))
+    return fail(c, VR_E_INVALID, "vr_set_global_data_device: data is not device memory of the context's device");
+  hipStream_t caller = (hipStream_t)stream;
+  c->globalRows.resize(c->globalVecs.size());
+  const uint32_t rows = std::max<uint32_t>((uint32_t)c->globalVecs.size(), vecIdx + 1);
+  VR_TRY(lay_global_rows(c, rows, n)); // (an error leaves the vectors as they were)
+  VR_TRY(wait_for_caller(c, caller));
+  VR_HIP(c, launch_global_row(data, n, c->dGlobalVec.p + (size_t)vecIdx * c->globalStride, c->globalStride, c->stream));
+  VR_TRY(caller_waits(c, caller));
+  for (uint32_t v = (uint32_t)c->globalVecs.size(); v < rows; ++v) { // (vectors in between that were never given: empty,
+    c->globalVecs.emplace_back();                                     //  and their rows are zero already)
+    c->globalRows.emplace_back();
+  }
+  c->globalVecs[vecIdx].clear();
+  c->globalRows[vecIdx].len = n;
+  c->globalRows[vecIdx].onDevice = true;
+  c->globalRows[vecIdx].pending = false;
+  c->prepared = false; // (the launch parameters carry the row count and the stride)
   return VR_OK;
 }
 int vr_set_global_scalars(vr_context *c, const float *data, uint32_t n) {
@@ -380,19 +504,17 @@ int vr_set_surface_source(vr_context *c, const float *positions3, const float *n
   }
   if (!positions3 || !normals3 || !weights)
     return fail(c, VR_E_INVALID, "vr_set_surface_source: positions, normals and weights must not be NULL when n > 0");
-  if (!(sourceArea > 0.f) || !std::isfinite(sourceArea))
-    return fail(c, VR_E_INVALID, "vr_set_surface_source: sourceArea must be positive and finite");
-  if (!(sourceOffset >= 0.f) || !std::isfinite(sourceOffset))
-    return fail(c, VR_E_INVALID, "vr_set_surface_source: sourceOffset must be finite and >= 0");
+  if (const char *msg = surface_scalar_error(sourceArea, sourceOffset))
+    return fail(c, VR_E_INVALID, msg);
   for (size_t j = 0; j < n; ++j) {
     const float *q = positions3 + 3 * j, *m = normals3 + 3 * j;
     if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]))
-      return fail(c, VR_E_INVALID, ("vr_set_surface_source: position " + std::to_string(j) + " is not finite").c_str());
+      return fail(c, VR_E_INVALID, surface_row_error(0, j).c_str());
     const float len = std::sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]); // (as the generator's vnormalize)
     if (!(len > 0.f) || !std::isfinite(len))
-      return fail(c, VR_E_INVALID, ("vr_set_surface_source: normal " + std::to_string(j) + " has zero or non-finite length").c_str());
+      return fail(c, VR_E_INVALID, surface_row_error(1, j).c_str());
     if (!(weights[j] >= 0.f) || !std::isfinite(weights[j]))
-      return fail(c, VR_E_INVALID, ("vr_set_surface_source: weight " + std::to_string(j) + " is negative or not finite").c_str());
+      return fail(c, VR_E_INVALID, surface_row_error(2, j).c_str());
   }
   VR_HIP(c, hipSetDevice(c->device));
   VR_HIP(c, hipStreamSynchronize(c->stream)); // (a launched apply may still read the previous tables)
@@ -402,15 +524,49 @@ int vr_set_surface_source(vr_context *c, const float *positions3, const float *n
   VR_HIP(c, hipMemcpy(c->dSurfPos.p, positions3, (size_t)n * 12, hipMemcpyHostToDevice));
   VR_HIP(c, hipMemcpy(c->dSurfNrm.p, normals3, (size_t)n * 12, hipMemcpyHostToDevice));
   VR_HIP(c, hipMemcpy(c->dSurfWeights.p, weights, (size_t)n * 4, hipMemcpyHostToDevice));
-  c->surfCount = n;
-  c->surfArea = sourceArea;
-  c->surfOffset = sourceOffset;
-  c->gridPoints.clear();
-  c->hostOrg.clear();
-  c->hostDir.clear();
-  c->hostDraws.clear();
-  c->hostWeights.clear();
-  c->prepared = false;
+  surface_source_accepted(c, n, sourceArea, sourceOffset);
+  return VR_OK;
+}
+// vr_set_surface_source for tables that live on the device (rows of ld = 2 or 3 floats; 2 only on a 2-D context, the
+// third column then reads 0).  One kernel packs the rows into staging tables and applies the host loop's three checks to
+// every row; one word comes back — the first refusal the host loop would have met, or none — and with it the message of
+// vr_set_surface_source.  Accepted, the staging tables are swapped in; refused, the previous source stays untouched.
+int vr_set_surface_source_device(vr_context *c, const float *positions, const float *normals, const float *weights,
+                                 uint32_t n, uint32_t ld, float sourceArea, float sourceOffset, void *stream) {
+  if (!c)
+    return VR_E_INVALID;
+  if (n == 0)
+    return vr_set_surface_source(c, nullptr, nullptr, nullptr, 0, 0.f, 0.f);
+  if (!positions || !normals || !weights)
+    return fail(c, VR_E_INVALID, "vr_set_surface_source: positions, normals and weights must not be NULL when n > 0");
+  if (ld != 2 && ld != 3)
+    return fail(c, VR_E_INVALID, "vr_set_surface_source_device: ld (floats per row) must be 2 or 3");
+  if (ld == 2 && c->geo.D != 2)
+    return fail(c, VR_E_INVALID, "vr_set_surface_source_device: rows of 2 floats need a 2-D geometry (D == 2)");
+  if (const char *msg = surface_scalar_error(sourceArea, sourceOffset))
+    return fail(c, VR_E_INVALID, msg);
+  VR_HIP(c, hipSetDevice(c->device));
+  if (!is_device_memory_of(positions, c->device) || !is_device_memory_of(normals, c->device) ||
+      !is_device_memory_of(weights, c->device))
+    return fail(c, VR_E_INVALID, "vr_set_surface_source_device: positions / normals / weights are not device memory of "
+                                 "the context's device");
+  VR_HIP(c, c->dSurfPosIn.ensure((size_t)n * 3));
+  VR_HIP(c, c->dSurfNrmIn.ensure((size_t)n * 3));
+  VR_HIP(c, c->dSurfWeightsIn.ensure(n));
+  VR_HIP(c, c->dSurfBad.ensure(1));
+  VR_TRY(wait_for_caller(c, (hipStream_t)stream));
+  VR_HIP(c, launch_surface_source(positions, normals, weights, n, ld, c->dSurfPosIn.p, c->dSurfNrmIn.p, c->dSurfWeightsIn.p,
+                                  c->dSurfBad.p, c->stream));
+  unsigned long long bad = 0;
+  VR_HIP(c, hipMemcpyAsync(&bad, c->dSurfBad.p, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+  // (the copy is taken, and an apply launched earlier no longer reads the previous tables: the caller may reuse its rows)
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  if (bad != ~0ull)
+    return fail(c, VR_E_INVALID, surface_row_error((int)(bad & 3ull), bad >> 2).c_str());
+  std::swap(c->dSurfPos, c->dSurfPosIn);
+  std::swap(c->dSurfNrm, c->dSurfNrmIn);
+  std::swap(c->dSurfWeights, c->dSurfWeightsIn);
+  surface_source_accepted(c, n, sourceArea, sourceOffset);
   return VR_OK;
 }
 // Source::getInitialRayWeight(idx) (raySource.hpp:18, rayTraceKernel.hpp:124) of the rays handed over with

@@ -172,6 +172,8 @@ struct ParticleLaunch {
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
   hipFunction_t userGen = nullptr;    // ... and a stateful model's generator (nullptr: the library's)
   DevBuf<float> primSticking;         // this particle's per-primitive sticking, leaf order (params.primSticking, or unused)
+  DevBuf<int32_t> matTable;           // its (id, value) table for launch_prim_sticking: the ids, then the values' bits
+  std::vector<int32_t> matTableHost;  // (staging of that upload)
   bool relief = false; // flat with relief: a second launch (looseMode, looseGrid) traces the loose bins
   int looseMode = 0;
   unsigned looseGrid = 0;
@@ -207,6 +209,11 @@ struct vr_context {
   uint32_t accPlanes = 0;         // planes the accumulator buffers currently hold
   DevBuf<float> dRayState;            // a stateful model's per-ray state of one batch (the frame's VR_F_STATE_*), float4 per ray
   DevBuf<int32_t> dPrimMaterial;      // material id per original primitive for a stateful model (VR_F_MAT_*)
+  // the material ids on the device, caller's order: what prepare_sticking and the stateful models read.  Set from the
+  // device (materialOnDevice: geo.materialIds is then a mirror nobody fills) or uploaded from geo.materialIds when stale.
+  DevBuf<int32_t> dMaterialIds;
+  uint32_t materialCount = 0;         // ids dMaterialIds holds (a primitive beyond them has id 0)
+  bool materialOnDevice = false, materialStale = true;
   // the data log (vr_set_data_log_shape): int64 sums of the log_data hooks, rows concatenated, the control words behind
   // them (VR_LOG_*, vr_device.hpp); zeroed at every launch, summed over the batches and particles of an apply on the device
   std::vector<uint32_t> logRowSizes;
@@ -228,6 +235,21 @@ struct vr_context {
   bool globalDirty = false;
   uint32_t globalStride = 0;
   DevBuf<float> dGlobalVec, dGlobalScalars;
+  // A vector set from device memory (vr_set_global_data_device) is written into its row of dGlobalVec when it is set:
+  // globalVecs[v] is then only a mirror, left empty as long as no host path asks for the values (none does today).
+  // Per vector: its length, whether the row on the device is the truth, whether a host-set vector still has to go up.
+  struct GlobalRow {
+    uint32_t len = 0;
+    bool onDevice = false, pending = false;
+  };
+  std::vector<GlobalRow> globalRows; // (one per entry of globalVecs)
+  uint32_t globalRowsLaid = 0;       // rows of dGlobalVec, at globalStride, that hold what they should
+  bool anyGlobalOnDevice() const {
+    for (const GlobalRow &r : globalRows)
+      if (r.onDevice)
+        return true;
+    return false;
+  }
   // sources other than SourceRandom
   std::vector<float> gridPoints;  // SourceGrid origins (raySourceGrid.hpp)
   std::vector<float> hostOrg, hostDir;
@@ -238,6 +260,8 @@ struct vr_context {
   uint32_t surfCount = 0;          // source points (0: no surface source)
   float surfArea = 0.f, surfOffset = 0.f;
   DevBuf<float> dSurfPos, dSurfNrm, dSurfWeights;
+  DevBuf<float> dSurfPosIn, dSurfNrmIn, dSurfWeightsIn; // vr_set_surface_source_device packs into these; accepted: swapped in
+  DevBuf<unsigned long long> dSurfBad;                  // ... and its one word of validation
   DevBuf<float> dSurfRayWeights;   // start weight of every ray of one batch (TraceParams::hostWeights of a surface source)
   uint64_t reserveRays = 0;        // vr_reserve_rays: the ray-stream buffers hold at least this many rays
   bool sourceDirty = false;
@@ -376,6 +400,8 @@ int ensure_host_geometry(vr_context *c);
 int ensure_host_order(vr_context *c);
 int ensure_host_neighbors(vr_context *c);
 int build_scene(vr_context *c);
+int ensure_device_material_ids(vr_context *c);
+int lay_global_rows(vr_context *c, uint32_t rows, uint32_t stride);
 // vr_prepare.cpp
 uint64_t rays_of_apply(const vr_context *c);
 void size_bins(int D, uint64_t count, uint32_t perBin, TraceParams &p, uint32_t &numBins);

@@ -58,6 +58,19 @@ hipError_t launch_ingest_disks(const float *pts, const float *nrm, unsigned n, u
 size_t sort_plane_partials_entries();
 hipError_t launch_sort_plane(const float *disk4, const float *normal3, unsigned n, int axis, float lo, float hi,
                              double *partials, double *hist512, hipStream_t st);
+// device-resident inputs of a time step (vr_setup.hip).  launch_global_row: one row of the global data, zero-padded to the
+// stride; launch_global_relayout: the rows at another stride / row count, zeros where there was nothing
+hipError_t launch_global_row(const float *src, unsigned n, float *dst, unsigned stride, hipStream_t st);
+hipError_t launch_global_relayout(const float *src, unsigned oldRows, unsigned oldStride, float *dst, unsigned newRows,
+                                  unsigned newStride, hipStream_t st);
+// out[q] = the particle's sticking for the material id of leaf q's primitive (ids in the caller's order, 0 beyond numIds;
+// the last table entry of an id wins)
+hipError_t launch_prim_sticking(const unsigned *order, const int *ids, unsigned numIds, const int *tabIds,
+                                const float *tabVals, unsigned tabN, float base, unsigned n, float *out, hipStream_t st);
+// the surface-source tables packed from device rows of ld floats and validated: *bad = the smallest
+// row * 4 + {0 position, 1 normal, 2 weight} that fails vr_set_surface_source's checks, all ones if none does
+hipError_t launch_surface_source(const float *pos, const float *nrm, const float *wgt, unsigned n, unsigned ld,
+                                 float *pos3, float *nrm3, float *w, unsigned long long *bad, hipStream_t st);
 // post-processing on the device (vr_setup.hip)
 hipError_t launch_disk_areas(const float *disk4, const float *normal3, unsigned n, const AreaParams &p, float *out,
                              hipStream_t st);

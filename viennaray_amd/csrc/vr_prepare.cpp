@@ -242,43 +242,72 @@ static int compute_areas(vr_context *c) {
   return VR_OK;
 }
 
-// per-primitive sticking from the material map (gpu::Particle-style, rayParticle.hpp:208-218), the particle's own buffer
+// per-primitive sticking from the material map (gpu::Particle-style, rayParticle.hpp:208-218), the particle's own buffer:
+// one kernel over the resident leaf order and material ids (host-set ids are uploaded first: ensure_device_material_ids),
+// so neither the order nor the ids come back to the host
 static int prepare_sticking(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L) {
   L.params.primSticking = nullptr;
   if (sp.matIds.empty())
     return VR_OK;
-  int ro = ensure_host_order(c);
-  if (ro != VR_OK)
-    return ro;
+  VR_TRY(ensure_device_material_ids(c));
   const uint32_t N = c->geo.numPrims;
-  std::vector<float> ps(N);
-  for (uint32_t q = 0; q < N; ++q) {
-    const uint32_t o = c->bvh.order[q];
-    const int mat = o < c->geo.materialIds.size() ? c->geo.materialIds[o] : 0;
-    float s = sp.sticking;
-    for (size_t m = 0; m < sp.matIds.size(); ++m)
-      if (sp.matIds[m] == mat)
-        s = sp.matVals[m];
-    ps[q] = s;
-  }
+  const size_t M = sp.matIds.size();
+  L.matTableHost.resize(2 * M);
+  std::memcpy(L.matTableHost.data(), sp.matIds.data(), M * 4);
+  std::memcpy(L.matTableHost.data() + M, sp.matVals.data(), M * 4);
+  VR_HIP(c, L.matTable.ensure(2 * M));
+  VR_HIP(c, hipMemcpyAsync(L.matTable.p, L.matTableHost.data(), 2 * M * 4, hipMemcpyHostToDevice, c->stream));
   VR_HIP(c, L.primSticking.ensure(N));
-  VR_HIP(c, hipMemcpy(L.primSticking.p, ps.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+  VR_HIP(c, launch_prim_sticking(c->dOrder.p, c->dMaterialIds.p, c->materialCount, L.matTable.p,
+                                 reinterpret_cast<const float *>(L.matTable.p + M), (unsigned)M, sp.sticking, N,
+                                 L.primSticking.p, c->stream));
   L.params.primSticking = L.primSticking.p;
   return VR_OK;
 }
 
-// Trace::setGlobalData: every vector padded to one stride, one upload
+// Trace::setGlobalData.  Host-set vectors only: every vector padded to one stride, one upload.  With vectors that were
+// set from the device (their rows are in place since they were set), only the host-set rows that changed go up, each into
+// its own row.
 static int upload_global_data(vr_context *c) {
-  uint32_t stride = 0;
-  for (const auto &v : c->globalVecs)
-    stride = std::max<uint32_t>(stride, (uint32_t)v.size());
-  c->globalStride = stride;
-  if (stride && !c->globalVecs.empty()) {
-    std::vector<float> flat((size_t)stride * c->globalVecs.size(), 0.f);
-    for (size_t v = 0; v < c->globalVecs.size(); ++v)
-      std::copy(c->globalVecs[v].begin(), c->globalVecs[v].end(), flat.begin() + v * stride);
-    VR_HIP(c, c->dGlobalVec.ensure(flat.size()));
-    VR_HIP(c, hipMemcpy(c->dGlobalVec.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
+  c->globalRows.resize(c->globalVecs.size());
+  if (!c->anyGlobalOnDevice()) {
+    if (c->globalRowsLaid) // (row kernels of earlier device sets may still be on their way)
+      VR_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t stride = 0;
+    for (const auto &v : c->globalVecs)
+      stride = std::max<uint32_t>(stride, (uint32_t)v.size());
+    c->globalStride = stride;
+    c->globalRowsLaid = 0;
+    if (stride && !c->globalVecs.empty()) {
+      std::vector<float> flat((size_t)stride * c->globalVecs.size(), 0.f);
+      for (size_t v = 0; v < c->globalVecs.size(); ++v)
+        std::copy(c->globalVecs[v].begin(), c->globalVecs[v].end(), flat.begin() + v * stride);
+      VR_HIP(c, c->dGlobalVec.ensure(flat.size()));
+      VR_HIP(c, hipMemcpy(c->dGlobalVec.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
+      c->globalRowsLaid = (uint32_t)c->globalVecs.size();
+    }
+    for (size_t v = 0; v < c->globalRows.size(); ++v) {
+      c->globalRows[v].len = (uint32_t)c->globalVecs[v].size();
+      c->globalRows[v].pending = false;
+    }
+  } else {
+    uint32_t stride = 0;
+    for (const auto &r : c->globalRows)
+      stride = std::max(stride, r.len);
+    VR_TRY(lay_global_rows(c, (uint32_t)c->globalRows.size(), stride));
+    bool pending = false;
+    for (const auto &r : c->globalRows)
+      pending = pending || (!r.onDevice && r.pending);
+    if (pending) // (lay_global_rows' fill of a new row comes first)
+      VR_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<float> row(pending ? c->globalStride : 0);
+    for (size_t v = 0; v < c->globalRows.size(); ++v) {
+      if (c->globalRows[v].onDevice || !c->globalRows[v].pending)
+        continue;
+      std::fill(std::copy(c->globalVecs[v].begin(), c->globalVecs[v].end(), row.begin()), row.end(), 0.f);
+      VR_HIP(c, hipMemcpy(c->dGlobalVec.p + v * (size_t)c->globalStride, row.data(), row.size() * 4, hipMemcpyHostToDevice));
+      c->globalRows[v].pending = false;
+    }
   }
   if (!c->globalScalars.empty()) {
     VR_HIP(c, c->dGlobalScalars.ensure(c->globalScalars.size()));
@@ -696,11 +725,14 @@ static int fill_trace_params(vr_context *c, const ParticleSpec &sp, ParticleLaun
   // into the launch frame (VR_F_STATE_*, VR_F_MAT_*).  (Both are sized by what every particle of an apply shares — rays
   // per batch, primitives — so a later particle's prepare does not move them.)
   S.dMaterial = nullptr;
-  if (S.stateful && !c->geo.materialIds.empty()) {
-    std::vector<int32_t> ids(N, 0);
-    std::copy(c->geo.materialIds.begin(), c->geo.materialIds.begin() + std::min<size_t>(N, c->geo.materialIds.size()), ids.begin());
+  if (S.stateful && (c->materialOnDevice || !c->geo.materialIds.empty())) { // (a device copy, zeros behind the ids given)
+    VR_TRY(ensure_device_material_ids(c));
+    const uint32_t given = std::min(N, c->materialCount);
     VR_HIP(c, c->dPrimMaterial.ensure(N));
-    VR_HIP(c, hipMemcpy(c->dPrimMaterial.p, ids.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    if (given)
+      VR_HIP(c, hipMemcpyAsync(c->dPrimMaterial.p, c->dMaterialIds.p, (size_t)given * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (N > given)
+      VR_HIP(c, hipMemsetAsync(c->dPrimMaterial.p + given, 0, (size_t)(N - given) * 4, c->stream));
     S.dMaterial = c->dPrimMaterial.p;
   }
   // the packet query's search margin (frontier reuse over neighbouring rounds, flat-scene kernels): in units of the

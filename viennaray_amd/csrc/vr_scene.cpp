@@ -38,6 +38,44 @@ int ensure_host_order(vr_context *c) {
   return VR_OK;
 }
 
+// dMaterialIds holds the material ids in force: ids set from the device are there already, ids set from the host go up
+// when they changed
+int ensure_device_material_ids(vr_context *c) {
+  if (c->materialOnDevice || !c->materialStale)
+    return VR_OK;
+  const std::vector<int32_t> &ids = c->geo.materialIds;
+  VR_HIP(c, hipStreamSynchronize(c->stream)); // (a kernel queued earlier may still read the previous ids)
+  VR_HIP(c, c->dMaterialIds.ensure(ids.size()));
+  if (!ids.empty())
+    VR_HIP(c, hipMemcpy(c->dMaterialIds.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
+  c->materialCount = (uint32_t)ids.size();
+  c->materialStale = false;
+  return VR_OK;
+}
+
+// dGlobalVec with room for `rows` rows of at least `stride` floats: the rows laid so far keep their values (re-laid by a
+// kernel when the stride grows or the buffer moves), rows that come new read 0.  The stride only grows here; with no
+// device-set vector left, upload_global_data lays everything anew at the exact stride.
+int lay_global_rows(vr_context *c, uint32_t rows, uint32_t stride) {
+  stride = std::max(stride, c->globalStride);
+  const uint32_t kept = std::min(c->globalRowsLaid, rows);
+  const size_t need = (size_t)rows * stride;
+  if (stride == c->globalStride && c->dGlobalVec.p && need <= c->dGlobalVec.cap) {
+    if (rows > kept)
+      VR_HIP(c, hipMemsetAsync(c->dGlobalVec.p + (size_t)kept * stride, 0, (size_t)(rows - kept) * stride * 4, c->stream));
+    c->globalRowsLaid = rows;
+    return VR_OK;
+  }
+  DevBuf<float> fresh;
+  VR_HIP(c, fresh.ensure(need));
+  VR_HIP(c, launch_global_relayout(c->dGlobalVec.p, kept, c->globalStride, fresh.p, rows, stride, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream)); // (the old buffer is freed below)
+  c->dGlobalVec = std::move(fresh);
+  c->globalStride = stride;
+  c->globalRowsLaid = rows;
+  return VR_OK;
+}
+
 // neighbourhood CSR in ORIGINAL ids on the host (smoothFlux, neighbour counts), lazily
 int ensure_host_neighbors(vr_context *c) {
   if (c->hostNeighborsValid)

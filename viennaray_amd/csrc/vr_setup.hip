@@ -1384,4 +1384,117 @@ hipError_t launch_sort_plane(const float *disk4, const float *normal3, unsigned 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Device-resident inputs of a time step (vr_set_global_data_device, vr_set_material_ids_device,
+// vr_set_surface_source_device): streaming kernels, one thread per element or row, grid-stride.
+// ---------------------------------------------------------------------------
+constexpr unsigned INPUT_MAX_BLOCKS = 2048;
+static unsigned input_blocks(size_t n) {
+  const size_t b = (n + 255) / 256;
+  return (unsigned)(b < INPUT_MAX_BLOCKS ? (b ? b : 1) : INPUT_MAX_BLOCKS);
+}
+
+// one row of the global data: dst[0 .. stride) = src[0 .. n), zeros behind it
+__global__ __launch_bounds__(256) void global_row_kernel(const float *src, unsigned n, float *dst, unsigned stride) {
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < stride; i += gridDim.x * 256)
+    dst[i] = i < n ? src[i] : 0.f;
+}
+hipError_t launch_global_row(const float *src, unsigned n, float *dst, unsigned stride, hipStream_t st) {
+  if (stride == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(global_row_kernel, dim3(input_blocks(stride)), dim3(256), 0, st, src, n, dst, stride);
+  return hipGetLastError();
+}
+
+// the global data re-laid at another stride / row count: dst[newRows][newStride] = src[oldRows][oldStride], zeros elsewhere
+__global__ __launch_bounds__(256) void global_relayout_kernel(const float *src, unsigned oldRows, unsigned oldStride,
+                                                              float *dst, unsigned newRows, unsigned newStride) {
+  const size_t total = (size_t)newRows * newStride;
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < total; j += (size_t)gridDim.x * 256) {
+    const unsigned r = (unsigned)(j / newStride), i = (unsigned)(j - (size_t)r * newStride);
+    dst[j] = (r < oldRows && i < oldStride) ? src[(size_t)r * oldStride + i] : 0.f;
+  }
+}
+hipError_t launch_global_relayout(const float *src, unsigned oldRows, unsigned oldStride, float *dst, unsigned newRows,
+                                  unsigned newStride, hipStream_t st) {
+  const size_t total = (size_t)newRows * newStride;
+  if (total == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(global_relayout_kernel, dim3(input_blocks(total)), dim3(256), 0, st, src, oldRows, oldStride, dst,
+                     newRows, newStride);
+  return hipGetLastError();
+}
+
+// per-primitive sticking in leaf order from the material ids in the caller's order (prepare_sticking): the particle's
+// (id, value) table is searched to its end, so the last entry of an id wins as in the reference's map; a primitive
+// beyond the ids given has id 0
+__global__ __launch_bounds__(256) void prim_sticking_kernel(const unsigned *order, const int *ids, unsigned numIds,
+                                                            const int *tabIds, const float *tabVals, unsigned tabN,
+                                                            float base, unsigned n, float *out) {
+  for (unsigned q = blockIdx.x * 256 + threadIdx.x; q < n; q += gridDim.x * 256) {
+    const unsigned o = order[q];
+    const int mat = o < numIds ? ids[o] : 0;
+    float s = base;
+    for (unsigned m = 0; m < tabN; ++m)
+      if (tabIds[m] == mat)
+        s = tabVals[m];
+    out[q] = s;
+  }
+}
+hipError_t launch_prim_sticking(const unsigned *order, const int *ids, unsigned numIds, const int *tabIds,
+                                const float *tabVals, unsigned tabN, float base, unsigned n, float *out, hipStream_t st) {
+  if (n == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(prim_sticking_kernel, dim3(input_blocks(n)), dim3(256), 0, st, order, ids, numIds, tabIds, tabVals,
+                     tabN, base, n, out);
+  return hipGetLastError();
+}
+
+// The surface-source tables from device rows (ld = 2 or 3 floats; a missing third column reads 0): packed into
+// pos3 / nrm3 / w and checked row by row as vr_set_surface_source checks them — position finite, normal length (the same
+// sums in the same order) positive and finite, weight >= 0 and finite.  *bad ends as the smallest row * 4 + kind
+// (0 position, 1 normal, 2 weight) of the failing checks, each row reporting its first: the host loop's first refusal.
+__global__ __launch_bounds__(256) void surface_source_kernel(const float *pos, const float *nrm, const float *wgt,
+                                                             unsigned n, unsigned ld, float *pos3, float *nrm3, float *w,
+                                                             u64 *bad) {
+  u64 worst = ~0ull;
+  for (unsigned j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
+    const float *q = pos + (size_t)j * ld, *m = nrm + (size_t)j * ld;
+    const float q0 = q[0], q1 = q[1], q2 = ld == 3 ? q[2] : 0.f;
+    const float m0 = m[0], m1 = m[1], m2 = ld == 3 ? m[2] : 0.f;
+    const float wj = wgt[j];
+    pos3[3 * (size_t)j] = q0;
+    pos3[3 * (size_t)j + 1] = q1;
+    pos3[3 * (size_t)j + 2] = q2;
+    nrm3[3 * (size_t)j] = m0;
+    nrm3[3 * (size_t)j + 1] = m1;
+    nrm3[3 * (size_t)j + 2] = m2;
+    w[j] = wj;
+    const float len = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(m0, m0), __fmul_rn(m1, m1)), __fmul_rn(m2, m2)));
+    int kind = -1;
+    if (!isfinite(q0) || !isfinite(q1) || !isfinite(q2))
+      kind = 0;
+    else if (!(len > 0.f) || !isfinite(len))
+      kind = 1;
+    else if (!(wj >= 0.f) || !isfinite(wj))
+      kind = 2;
+    if (kind >= 0) {
+      const u64 key = (u64)j * 4u + (u64)kind;
+      worst = key < worst ? key : worst;
+    }
+  }
+  worst = wave_min_u64(worst); // (lane 0 holds the wave's smallest)
+  if ((threadIdx.x & 63) == 0 && worst != ~0ull)
+    atomicMin(bad, worst);
+}
+hipError_t launch_surface_source(const float *pos, const float *nrm, const float *wgt, unsigned n, unsigned ld,
+                                 float *pos3, float *nrm3, float *w, unsigned long long *bad, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(bad, 0xFF, sizeof(u64), st);
+  if (e != hipSuccess || n == 0)
+    return e;
+  hipLaunchKernelGGL(surface_source_kernel, dim3(input_blocks(n)), dim3(256), 0, st, pos, nrm, wgt, n, ld, pos3, nrm3, w,
+                     bad);
+  return hipGetLastError();
+}
+
 } // namespace vr

@@ -258,6 +258,29 @@ def _is_device_tensor(x):
     return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
 
 
+def _check_device_tensor(what, name, x, device, dtype, shapes):
+    """a tensor handed over where it is must be on the tracer's device, of the one dtype, contiguous and of one of the
+    shapes (None: any size): anything else raises ValueError — nothing is copied through the host behind the caller's
+    back"""
+    if not _is_device_tensor(x):
+        raise ValueError(f"{what}: device: {name} is not a device tensor while another argument is "
+                         "(all on the device, or all on the host)")
+    if x.device.index != device:
+        raise ValueError(f"{what}: device: {name} is on {x.device}, the tracer on device {device}")
+    if str(x.dtype) != dtype:
+        raise ValueError(f"{what}: dtype: {name} is {x.dtype}, device tensors must be {dtype}")
+    shape = tuple(x.shape)
+    if not any(len(shape) == len(w) and all(b is None or a == b for a, b in zip(shape, w)) for w in shapes):
+        raise ValueError(f"{what}: shape: {name} is {shape}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: contiguity: {name} is not contiguous (strides {tuple(x.stride())})")
+
+
+def _on_any_device(x):
+    """a tensor that is not host memory, whatever device it lives on"""
+    return hasattr(x, "data_ptr") and getattr(getattr(x, "device", None), "type", "cpu") != "cpu"
+
+
 class Trace:
     """rayTrace.hpp:15-180 (NumericType = float)."""
 
@@ -342,8 +365,17 @@ class Trace:
     def setGlobalData(self, data):
         """rayTrace.hpp:141: a TracingData (or a list of per-primitive arrays) the device particle models may read"""
         vecs = data._vectors if isinstance(data, TracingData) else list(data)
+        for k, v in enumerate(vecs):  # (before anything is dropped: a refusal leaves the previous data in force)
+            if _on_any_device(v):
+                _check_device_tensor("setGlobalData", f"vector {k}", v, self._device, "torch.float32", [(None,)])
         self._check(self._L.vr_set_global_data(self._h, 0, None, 0))
         for k, v in enumerate(vecs):
+            if _on_any_device(v):
+                # a float32 tensor on the tracer's device stays there (vr_set_global_data_device): copied into place
+                # by a kernel ordered behind the current torch stream, which may overwrite the tensor afterwards
+                self._check(self._L.vr_set_global_data_device(self._h, k, C.c_void_p(v.data_ptr()), int(v.numel()),
+                                                              C.c_void_p(self._torch_stream())))
+                continue
             a = np.ascontiguousarray(v, dtype=np.float32)
             self._check(self._L.vr_set_global_data(self._h, k, _fptr(a), a.size))
         if isinstance(data, TracingData) and data._scalars:
@@ -352,6 +384,23 @@ class Trace:
         else:  # (no scalars in the new data: the previous ones must not linger on the device)
             self._check(self._L.vr_set_global_scalars(self._h, None, 0))
         self._globalData = data
+
+    def setGlobalVector(self, k, v):
+        """One vector of the global data, the others untouched: a float32 tensor on the tracer's device (set on the
+        device, as in setGlobalData) or a host array; None drops vector k and those behind it."""
+        if v is None:
+            self._check(self._L.vr_set_global_data(self._h, int(k), None, 0))
+        elif _on_any_device(v):
+            _check_device_tensor("setGlobalVector", f"vector {k}", v, self._device, "torch.float32", [(None,)])
+            self._check(self._L.vr_set_global_data_device(self._h, int(k), C.c_void_p(v.data_ptr()), int(v.numel()),
+                                                          C.c_void_p(self._torch_stream())))
+        else:
+            a = np.ascontiguousarray(v, dtype=np.float32)
+            self._check(self._L.vr_set_global_data(self._h, int(k), _fptr(a), a.size))
+
+    def _torch_stream(self):
+        import torch
+        return torch.cuda.current_stream(torch.device("cuda", self._device)).cuda_stream
 
     def getGlobalData(self):
         return getattr(self, "_globalData", None)
@@ -397,7 +446,12 @@ class Trace:
     def setSurfaceSource(self, positions, normals, weights, sourceArea, sourceOffset):
         """gpu/raygTrace.hpp:267-286: the rays start on the given points (numRaysFixed if set, else numRaysPerPoint,
         rays per point), leave along a cosine distribution about each point's normal from position + unit normal *
-        sourceOffset and carry the point's weight; sampled on the device.  normalizeFlux(SOURCE) uses sourceArea."""
+        sourceOffset and carry the point's weight; sampled on the device.  normalizeFlux(SOURCE) uses sourceArea.
+        Three torch tensors on the tracer's device (positions and normals [n, 2] or [n, 3] float32, weights [n] float32,
+        contiguous) are handed over where they are (vr_set_surface_source_device): packed and validated by one kernel
+        behind the current torch stream.  Tensors on a device that cannot go that way raise ValueError."""
+        if _on_any_device(positions) or _on_any_device(normals) or _on_any_device(weights):
+            return self._setSurfaceSourceDevice(positions, normals, weights, sourceArea, sourceOffset)
         q = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         m = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
         w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
@@ -405,6 +459,16 @@ class Trace:
             raise VrError("setSurfaceSource: one normal and one weight per position")
         self._check(self._L.vr_set_surface_source(self._h, _fptr(q), _fptr(m), _fptr(w), q.shape[0],
                                                   float(sourceArea), float(sourceOffset)))
+
+    def _setSurfaceSourceDevice(self, positions, normals, weights, sourceArea, sourceOffset):
+        cols = [(None, 2), (None, 3)] if self.D == 2 else [(None, 3)]
+        _check_device_tensor("setSurfaceSource", "positions", positions, self._device, "torch.float32", cols)
+        n, ld = int(positions.shape[0]), int(positions.shape[1])
+        _check_device_tensor("setSurfaceSource", "normals", normals, self._device, "torch.float32", [(n, ld)])
+        _check_device_tensor("setSurfaceSource", "weights", weights, self._device, "torch.float32", [(n,)])
+        self._check(self._L.vr_set_surface_source_device(
+            self._h, C.c_void_p(positions.data_ptr()), C.c_void_p(normals.data_ptr()), C.c_void_p(weights.data_ptr()),
+            n, ld, float(sourceArea), float(sourceOffset), C.c_void_p(self._torch_stream())))
 
     def clearSurfaceSource(self):
         """gpu/raygTrace.hpp:288-297"""
@@ -449,6 +513,13 @@ class Trace:
         self._check(self._L.vr_set_rng_seed(self._h, int(s)))
 
     def setMaterialIds(self, ids):
+        """rayGeometry.hpp:17-24.  An int32 tensor on the tracer's device (1-D, contiguous) stays there
+        (vr_set_material_ids_device); any other device tensor raises ValueError."""
+        if _on_any_device(ids):
+            _check_device_tensor("setMaterialIds", "ids", ids, self._device, "torch.int32", [(None,)])
+            self._check(self._L.vr_set_material_ids_device(self._h, C.c_void_p(ids.data_ptr()), int(ids.numel()),
+                                                           C.c_void_p(self._torch_stream())))
+            return
         a = np.ascontiguousarray(ids, dtype=np.int32)
         self._check(self._L.vr_set_material_ids(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size))
 
