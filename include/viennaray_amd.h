@@ -127,6 +127,19 @@ int vr_set_disks_device(vr_context *ctx, const float *points, const float *norma
  * normals per rayMesh.hpp:99-112).  verts: nverts x 3, tris: ntris x 3.      */
 int vr_set_triangles(vr_context *ctx, const float *verts, uint32_t nverts,
                      const uint32_t *tris, uint32_t ntris, float gridDelta, int D);
+/* vr_set_triangles for a mesh that already lives on the device (a meshing or advection step written in torch or HIP).
+ * verts: DEVICE pointer on ctx's device to nverts rows of 3 float32; tris: DEVICE pointer to ntris rows of 3 uint32;
+ * both produced on `stream` (the caller's hipStream_t, NULL = the null stream), which the library's stream waits for by
+ * an event.  Same effects as vr_set_triangles (ntris < 2^27; here also nverts < 2^31); additionally refuses pointers
+ * that are not device memory of ctx's device (host, pinned and managed memory included).  The indices are checked on the
+ * device before anything else happens: an index >= nverts is refused with vr_set_triangles' message and the lowest
+ * offending triangle.  Every refusal leaves the previous geometry in place and the context usable.  Accepted, one kernel
+ * copies both buffers and makes the unit normals and areas, bit for bit those of vr_set_triangles; `stream` is made to
+ * wait for it, so the caller may overwrite or free its buffers at once.  One synchronisation with the host per call:
+ * seven words come back (the bounding box over all vertices and the index check).  The host copies are made only if a
+ * host path (VR_HOST_BUILD) asks for them.  Non-finite vertices are the caller's error, as for vr_set_triangles. */
+int vr_set_triangles_device(vr_context *ctx, const float *verts, uint32_t nverts, const uint32_t *tris, uint32_t ntris,
+                            float gridDelta, int D, void *stream);
 /* setMaterialIds (rayGeometry.hpp:17-24)                                    */
 int vr_set_material_ids(vr_context *ctx, const int32_t *ids, uint32_t n);
 /* vr_set_material_ids for ids that live on the device: ids is a DEVICE pointer on ctx's device to n int32 in the
@@ -377,6 +390,9 @@ int vr_debug_surface_source_sample(vr_context *ctx, const uint64_t *idx, uint32_
 /* first `count` raw mt19937_64 outputs of the per-ray engine of ray idx      */
 int vr_debug_rng_outputs(vr_context *ctx, uint64_t idx, uint32_t seed,
                          uint32_t count, uint64_t *out);
+/* unit normals (ntris x 3) and areas (ntris) of the triangle mesh in force, as vr_set_triangles computed them or as
+ * vr_set_triangles_device left them on the device (downloaded on demand)     */
+int vr_debug_triangle_mesh(vr_context *ctx, float *normals3, float *areas, uint32_t ntris);
 /* BVH statistics: nodes, leaves, max depth */
 int vr_debug_bvh_stats(vr_context *ctx, uint32_t *out3);
 /* consistency of the resident device-built BVH: number of internal nodes whose box is not

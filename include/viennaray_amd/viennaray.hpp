@@ -1459,6 +1459,16 @@ public:
       this->geometryAccepted(vr_set_triangles(this->ctx_, p.data(), (uint32_t)points.size(), t.data(),
                                               (uint32_t)triangles.size(), (float)gridDelta, D));
   }
+  /// setGeometry for a mesh that already lives on the device (vr_set_triangles_device): dVerts is a DEVICE pointer to
+  /// nverts rows of 3 floats, dTris one to ntris rows of 3 unsigned, both produced on `stream` (the caller's hipStream_t,
+  /// nullptr = the null stream).  The library checks the indices and takes its own copy on the device: the buffers are
+  /// free again on return.
+  void setGeometryDevice(const float *dVerts, size_t nverts, const unsigned *dTris, size_t ntris, NumericType gridDelta,
+                         void *stream = nullptr) {
+    if (this->ctx_)
+      this->geometryAccepted(vr_set_triangles_device(this->ctx_, dVerts, (uint32_t)nverts, dTris, (uint32_t)ntris,
+                                                     (float)gridDelta, D, stream));
+  }
   void setGeometry(const TriangleMesh &mesh) {
     std::vector<VectorType<NumericType, 3>> pts(mesh.nodes.size());
     for (size_t i = 0; i < pts.size(); ++i)

@@ -9,7 +9,11 @@ in ONE process with one library, the two ways alternating step by step, on C2's 
 including a final torch.cuda.synchronize()) and per stage: set, prepare, launch (+ finish), result.  The points of a
 step are ready before its clock starts (a ring of surfaces, each a little different: the producer is not what is
 measured); apply() does not collect getLocalData() on either way.  Prints one JSON line.
-usage: tools/device_geometry_bench.py [steps=20] [warmup=3]"""
+
+--triangles: what handing over a triangle mesh costs — a rippled grid mesh of about 10^6 triangles, set-geometry +
+vr_apply_prepare timed for setGeometry(numpy arrays) and for setGeometry(torch tensors), alternating step by step in
+one process (a ring of meshes as above; the device way's clock includes a final torch.cuda.synchronize()).
+usage: tools/device_geometry_bench.py [--triangles] [steps=20] [warmup=3]"""
 import json
 import os
 import statistics
@@ -102,9 +106,70 @@ def case(name, rays, steps, warmup):
                 device_not_slower=med["device"]["step"] <= med["host"]["step"], flux_bit_equal=same, trace_mode=td.traceMode())
 
 
+def grid_mesh(n, phase):
+    """(n + 1)^2 vertices on the unit grid, z as rippled_plane's, two triangles per cell: 2 n^2 triangles"""
+    i, j = np.meshgrid(np.arange(n + 1), np.arange(n + 1), indexing="ij")
+    x, y = j.ravel().astype(np.float64), i.ravel().astype(np.float64)
+    v = np.stack([x, y, 0.5 * np.sin((x + phase) / 4.0) * np.cos(y / 4.0)], axis=1).astype(np.float32)
+    a = (i[:-1, :-1] * (n + 1) + j[:-1, :-1]).ravel()
+    b, d, e = a + 1, a + n + 1, a + n + 2
+    t = np.empty((2 * a.size, 3), dtype=np.uint32)
+    t[0::2] = np.stack([a, b, d], 1)
+    t[1::2] = np.stack([b, e, d], 1)
+    return v, t
+
+
+def triangle_case(rays, steps, warmup, n=707):
+    ring = [grid_mesh(n, 0.37 * k) for k in range(RING)]
+    dev = [(torch.from_numpy(v).cuda(), torch.from_numpy(t.view(np.int32)).cuda()) for v, t in ring]
+    torch.cuda.synchronize()
+    tracers = []
+    for _ in range(2):
+        t = vr.TraceTriangle(3)
+        t.setBoundaryConditions([vr.BoundaryCondition.PERIODIC_BOUNDARY] * 3)
+        t.setParticleType(vr.DiffuseParticle(1.0, "flux"))
+        t.setNumberOfRaysFixed(rays)
+        t.setUseRandomSeeds(False)
+        t.setRngSeed(12345)
+        tracers.append(t)
+    th, td = tracers
+    rows = {"host": [], "device": []}
+
+    def timed(t, v, tri, on_device):
+        c = [time.perf_counter()]
+        t.setGeometry(v, tri, 1.0)
+        c.append(time.perf_counter())
+        t.applyPrepare()
+        if on_device:
+            torch.cuda.synchronize()
+        c.append(time.perf_counter())
+        return dict(set=(c[1] - c[0]) * 1e3, prepare=(c[2] - c[1]) * 1e3, both=(c[2] - c[0]) * 1e3)
+
+    for k in range(warmup + steps):
+        a = timed(th, *ring[k % RING], False)
+        b = timed(td, *dev[k % RING], True)
+        if k >= warmup:
+            rows["host"].append(a)
+            rows["device"].append(b)
+    for t in tracers:  # one trace each on the last mesh: the two ways give the same flux
+        t.applyLaunch()
+        t.applyFinish(collect=False)
+    same = bool(np.array_equal(th.getFluxNormalized(SOURCE), td.getFluxNormalized(SOURCE)))
+    stat = {w: {s: dict(median=round(statistics.median(r[s] for r in rows[w]), 4), min=round(min(r[s] for r in rows[w]), 4),
+                        max=round(max(r[s] for r in rows[w]), 4)) for s in ("both", "set", "prepare")} for w in rows}
+    return dict(scene="grid_mesh", triangles=int(ring[0][1].shape[0]), vertices=int(ring[0][0].shape[0]), rays=rays,
+                steps=steps, ms=stat, device_not_slower=stat["device"]["both"]["median"] <= stat["host"]["both"]["median"],
+                flux_bit_equal=same)
+
+
 def main():
-    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    warmup = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    args = [a for a in sys.argv[1:] if a != "--triangles"]
+    steps = int(args[0]) if len(args) > 0 else 20
+    warmup = int(args[1]) if len(args) > 1 else 3
+    if "--triangles" in sys.argv[1:]:
+        print(json.dumps(dict(tool="device_geometry_bench", mode="triangles", device=torch.cuda.get_device_name(0),
+                              cases=[triangle_case(1_000_000, steps, warmup)])), flush=True)
+        return
     cases = [case(name, rays, steps, warmup) for name in ("C2_rippled", "trench3d") for rays in (1_000_000, 10_000_000)]
     print(json.dumps(dict(tool="device_geometry_bench", device=torch.cuda.get_device_name(0), cases=cases)), flush=True)
 

@@ -55,6 +55,7 @@ SIGNATURES = {
     "vr_set_disks": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_float, C.c_float, C.c_int]),
     "vr_set_disks_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_int, _vp]),
     "vr_set_triangles": (C.c_int, [_vp, _fp, C.c_uint32, _u32p, C.c_uint32, C.c_float, C.c_int]),
+    "vr_set_triangles_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_float, C.c_int, _vp]),
     "vr_set_material_ids": (C.c_int, [_vp, _i32p, C.c_uint32]),
     "vr_set_material_ids_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "vr_set_boundary_conditions": (C.c_int, [_vp, _i32p, C.c_int]),
@@ -124,6 +125,7 @@ SIGNATURES = {
     "vr_debug_surface_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp, _fp, _u32p]),
     "vr_debug_rng_outputs": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
     "vr_debug_issue_rate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_double)]),
+    "vr_debug_triangle_mesh": (C.c_int, [_vp, _fp, _fp, C.c_uint32]),
     "vr_debug_bvh_stats": (C.c_int, [_vp, _u32p]),
     "vr_debug_bvh_check": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
 }

@@ -258,6 +258,69 @@ int vr_set_triangles(vr_context *c, const float *verts, uint32_t nverts, const u
   return VR_OK;
 }
 
+// vr_set_triangles for a mesh that lives on the device, in two passes (vr_setup.hip).  The first reads the caller's
+// buffers only — box of all vertices, lowest triangle with an index out of range — and its seven words are the call's one
+// synchronisation with the host; nothing resident is touched before they say that the mesh is good.  The second copies
+// both buffers and makes the normals and areas of host_set_triangles; the caller's stream waits for it.
+int vr_set_triangles_device(vr_context *c, const float *verts, uint32_t nverts, const uint32_t *tris, uint32_t ntris,
+                            float gridDelta, int D, void *stream) {
+  // (nverts < 2^31: the box reduction's keys carry the row in 31 bits)
+  if (!c || (nverts && !verts) || (ntris && !tris) || (D != 2 && D != 3) || ntris >= (1u << 27) || nverts >= (1u << 31))
+    return fail(c, VR_E_INVALID, "vr_set_triangles_device: bad argument");
+  VR_HIP(c, hipSetDevice(c->device));
+  if ((nverts && !is_device_memory_of(verts, c->device)) || (ntris && !is_device_memory_of(tris, c->device)))
+    return fail(c, VR_E_INVALID, "vr_set_triangles_device: verts / tris are not device memory of the context's device");
+  hipStream_t caller = (hipStream_t)stream;
+  VR_HIP(c, c->dIngestKeys.ensure(ingest_partials_entries()));
+  VR_HIP(c, c->dIngestBounds.ensure(7));
+  VR_TRY(wait_for_caller(c, caller));
+  VR_HIP(c, launch_scan_mesh(verts, nverts, tris, ntris, c->dIngestKeys.p, c->dIngestBounds.p,
+                             reinterpret_cast<unsigned *>(c->dIngestBounds.p + 6), c->stream));
+  float b[7];
+  VR_HIP(c, hipMemcpyAsync(b, c->dIngestBounds.p, sizeof(b), hipMemcpyDeviceToHost, c->stream));
+  // (the one synchronisation; an apply launched earlier has finished too: the resident buffers may move below)
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  uint32_t bad;
+  std::memcpy(&bad, &b[6], 4);
+  if (bad != 0xFFFFFFFFu)
+    return fail(c, VR_E_INVALID,
+                ("vr_set_triangles: vertex index out of range (triangle " + std::to_string(bad) + ")").c_str());
+  // from here on the resident buffers no longer hold the previous geometry
+  invalidate_geometry(c);
+  material_ids_follow(c, ntris);
+  HostGeometry &g = c->geo;
+  g.numPrims = 0; // (until the new one is in place: an error below leaves "no geometry", not half of one)
+  g.verts.clear();
+  g.tris.clear();
+  g.normal3.clear();
+  g.triAreas.clear();
+  g.disk4.clear();
+  g.points3.clear();
+  g.nbOff.clear();
+  g.nbIds.clear();
+  VR_HIP(c, c->dVerts.ensure((size_t)nverts * 3));
+  VR_HIP(c, c->dTris.ensure((size_t)ntris * 3));
+  VR_HIP(c, c->dNormal3.ensure((size_t)ntris * 3));
+  VR_HIP(c, c->dTriAreas.ensure(ntris));
+  VR_HIP(c, launch_pack_mesh(verts, nverts, tris, ntris, D, c->dVerts.p, c->dTris.p, c->dNormal3.p, c->dTriAreas.p,
+                             c->stream));
+  VR_TRY(caller_waits(c, caller)); // (the copy is ordered before whatever the caller queues next on its stream)
+  g.D = D;
+  g.geo = 1;
+  g.numPrims = ntris;
+  g.gridDelta = gridDelta;
+  g.diskRadius = 0.f;
+  for (int k = 0; k < 3; ++k) { // (no vertices: the zeros of host_set_triangles)
+    g.minC[k] = nverts ? b[k] : 0.f;
+    g.maxC[k] = nverts ? b[3 + k] : 0.f;
+  }
+  if (!c->materialOnDevice && g.materialIds.size() != ntris)
+    g.materialIds.assign(ntris, 0);
+  c->deviceVerts = nverts;
+  c->geoOnDevice = true;
+  return VR_OK;
+}
+
 int vr_set_material_ids(vr_context *c, const int32_t *ids, uint32_t n) {
   if (!c || !ids)
     return fail(c, VR_E_INVALID, "vr_set_material_ids: bad argument");

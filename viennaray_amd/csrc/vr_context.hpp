@@ -309,10 +309,13 @@ struct vr_context {
   DevBuf<float> dDisk4, dNormal3, dPoints3, dVerts, dBox, dSBox, dNodeBox;
   // The geometry's source.  vr_set_disks_device fills dPoints3 / dNormal3 / dDisk4 itself (geoOnDevice): build_scene then
   // uploads nothing, and geo.points3 / normal3 / disk4 are a mirror that ensure_host_geometry downloads when a host path
-  // (VR_HOST_BUILD, VR_HOST_SMOOTH, a smoothing overflow) reads them.
+  // (VR_HOST_BUILD, VR_HOST_SMOOTH, a smoothing overflow) reads them.  vr_set_triangles_device likewise fills dVerts /
+  // dTris / dNormal3 / dTriAreas; the mirror is geo.verts / tris / normal3 / triAreas.
   bool geoOnDevice = false, hostGeoValid = false;
-  DevBuf<unsigned long long> dIngestKeys; // launch_ingest_disks' block partials
-  DevBuf<float> dIngestBounds;            // ... and its six bounds
+  uint32_t deviceVerts = 0;               // vertices dVerts holds for a device-resident mesh
+  DevBuf<float> dTriAreas;                // its areas, written by launch_pack_mesh only (compute_areas copies them into dAreas)
+  DevBuf<unsigned long long> dIngestKeys; // launch_ingest_disks' / launch_scan_mesh's block partials
+  DevBuf<float> dIngestBounds;            // ... their six bounds, and launch_scan_mesh's word behind them
   DevBuf<double> dSortPlane;              // launch_sort_plane's block partials, then the 512 merged sums
   hipEvent_t evIn = nullptr, evOut = nullptr; // hand-over between a caller's stream and this context's (device entry points)
   DevBuf<uint32_t> dTris, dBounds, dValsA, dValsB, dSortTable, dRangeLo, dRangeHi, dChildL, dChildR, dParentInt,

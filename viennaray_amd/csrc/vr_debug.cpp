@@ -253,6 +253,17 @@ int vr_debug_issue_rate(vr_context *c, int kind, int wavesPerSimd, uint32_t iter
   return VR_OK;
 }
 
+// the unit normals and areas of the triangle mesh in force, the caller's order (a device-resident mesh: its lazy host
+// mirror, ensure_host_geometry)
+int vr_debug_triangle_mesh(vr_context *c, float *normals3, float *areas, uint32_t ntris) {
+  if (!c || !normals3 || !areas || c->geo.geo != 1 || ntris != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, "vr_debug_triangle_mesh: bad argument (a triangle geometry of ntris triangles)");
+  VR_TRY(ensure_host_geometry(c));
+  std::copy(c->geo.normal3.begin(), c->geo.normal3.end(), normals3);
+  std::copy(c->geo.triAreas.begin(), c->geo.triAreas.end(), areas);
+  return VR_OK;
+}
+
 int vr_debug_bvh_stats(vr_context *c, uint32_t *out3) {
   if (!c || !out3)
     return VR_E_INVALID;

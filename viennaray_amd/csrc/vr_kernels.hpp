@@ -53,11 +53,20 @@ size_t ingest_partials_entries();
 hipError_t launch_ingest_disks(const float *pts, const float *nrm, unsigned n, unsigned ld, int D, float radius,
                                float *points3, float *normal3, float *disk4, unsigned long long *partials, float *bounds6,
                                hipStream_t st);
-// host_sort_plane's histogram for resident disks: hist512 = 256 slice areas, then 256 slice area x coordinate sums;
-// partials: sort_plane_partials_entries() doubles of scratch
+// device-resident triangle mesh (vr_set_triangles_device), pass 1: reads the caller's DEVICE buffers only — bounds6 = the
+// box of all nverts vertices (bit-equal to host_set_triangles'), *badTri = the lowest triangle that holds an index
+// >= nverts, all ones if none does; partials: ingest_partials_entries() words of scratch
+hipError_t launch_scan_mesh(const float *verts, unsigned nverts, const unsigned *tris, unsigned ntris,
+                            unsigned long long *partials, float *bounds6, unsigned *badTri, hipStream_t st);
+// ... pass 2 (every index in range): copies of both buffers, unit normals and areas bit-equal to host_set_triangles'
+hipError_t launch_pack_mesh(const float *verts, unsigned nverts, const unsigned *tris, unsigned ntris, int D,
+                            float *outVerts, unsigned *outTris, float *normal3, float *areas, hipStream_t st);
+// host_sort_plane's histogram for a resident geometry (geo 0: disk4 / normal3, geo 1: verts / tris; the other pair is not
+// read): hist512 = 256 slice areas, then 256 slice area x coordinate sums; partials: sort_plane_partials_entries()
+// doubles of scratch
 size_t sort_plane_partials_entries();
-hipError_t launch_sort_plane(const float *disk4, const float *normal3, unsigned n, int axis, float lo, float hi,
-                             double *partials, double *hist512, hipStream_t st);
+hipError_t launch_sort_plane(int geo, const float *disk4, const float *normal3, const float *verts, const unsigned *tris,
+                             unsigned n, int axis, float lo, float hi, double *partials, double *hist512, hipStream_t st);
 // device-resident inputs of a time step (vr_setup.hip).  launch_global_row: one row of the global data, zero-padded to the
 // stride; launch_global_relayout: the rows at another stride / row count, zeros where there was nothing
 hipError_t launch_global_row(const float *src, unsigned n, float *dst, unsigned stride, hipStream_t st);

@@ -138,7 +138,7 @@ static int check_settings(vr_context *c) {
   return VR_OK;
 }
 
-// host_sort_plane for a device-resident disk geometry: the histogram is made where the disks are (launch_sort_plane),
+// host_sort_plane for a device-resident geometry: the histogram is made where the primitives are (launch_sort_plane),
 // 512 doubles come back and the fullest slice is picked as the host function picks it.  (The sums are taken in another
 // order than the host threads take them: the plane may differ in its last bits; it only orders work.)
 static int device_sort_plane(vr_context *c, int axis, float fallback, float *coord, float *modeShare) {
@@ -153,8 +153,8 @@ static int device_sort_plane(vr_context *c, int axis, float fallback, float *coo
   const size_t scratch = sort_plane_partials_entries();
   VR_HIP(c, c->dSortPlane.ensure(scratch + 2 * SL));
   double h[2 * SL];
-  VR_HIP(c, launch_sort_plane(c->dDisk4.p, c->dNormal3.p, g.numPrims, axis, lo, hi, c->dSortPlane.p,
-                              c->dSortPlane.p + scratch, c->stream));
+  VR_HIP(c, launch_sort_plane(g.geo, c->dDisk4.p, c->dNormal3.p, c->dVerts.p, c->dTris.p, g.numPrims, axis, lo, hi,
+                              c->dSortPlane.p, c->dSortPlane.p + scratch, c->stream));
   VR_HIP(c, hipMemcpyAsync(h, c->dSortPlane.p + scratch, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   const double *w = h, *wh = h + SL;
@@ -198,8 +198,11 @@ static int setup_source_frame(vr_context *c) {
   const int f = c->ts[1], s = c->ts[2];
   c->sourceArea = D == 2 ? (c->bbHi[f] - c->bbLo[f]) : (c->bbHi[f] - c->bbLo[f]) * (c->bbHi[s] - c->bbLo[s]);
   const float fallback = c->ts[3] ? c->geo.minC[c->ts[0]] : c->geo.maxC[c->ts[0]];
-  if (c->geoOnDevice)
+  // (a device-resident mesh under VR_HOST_BUILD, the validation path: the host function on the downloaded mirror)
+  const bool hostMesh = c->geo.geo == 1 && c->knobs.hostBuild;
+  if (c->geoOnDevice && !hostMesh)
     return device_sort_plane(c, c->ts[0], fallback, &c->keyCoord, &c->keyShare);
+  VR_TRY(ensure_host_geometry(c));
   c->keyCoord = host_sort_plane(c->geo, c->ts[0], fallback, &c->keyShare);
   return VR_OK;
 }
@@ -234,6 +237,9 @@ static int compute_areas(vr_context *c) {
     } else {
       VR_HIP(c, launch_disk_areas(c->dDisk4.p, c->dNormal3.p, N, ap, c->dAreas.p, c->stream));
     }
+  } else if (c->geoOnDevice) {
+    // (launch_pack_mesh left them in dTriAreas, which nothing else writes: no upload)
+    VR_HIP(c, hipMemcpyAsync(c->dAreas.p, c->dTriAreas.p, (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
   } else {
     VR_HIP(c, hipMemcpyAsync(c->dAreas.p, c->geo.triAreas.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
     VR_HIP(c, hipStreamSynchronize(c->stream));

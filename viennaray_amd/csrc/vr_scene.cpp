@@ -8,12 +8,31 @@
 namespace vr {
 
 // ---- scene build (device LBVH + neighbourhood; VR_HOST_BUILD=1 selects the host builder) -------
-// geo.points3 / normal3 / disk4 of a device-resident geometry, downloaded when a host path first reads them
+// geo.points3 / normal3 / disk4 (disks) or geo.verts / tris / normal3 / triAreas (triangles) of a device-resident
+// geometry, downloaded when a host path first reads them
 int ensure_host_geometry(vr_context *c) {
   if (!c->geoOnDevice || c->hostGeoValid)
     return VR_OK;
   HostGeometry &g = c->geo;
   const size_t N = g.numPrims;
+  if (g.geo == 1) {
+    const size_t NV = c->deviceVerts;
+    g.verts.resize(NV * 3);
+    g.tris.resize(N * 3);
+    g.normal3.resize(N * 3);
+    g.triAreas.resize(N);
+    VR_HIP(c, hipSetDevice(c->device));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    if (NV)
+      VR_HIP(c, hipMemcpy(g.verts.data(), c->dVerts.p, NV * 12, hipMemcpyDeviceToHost));
+    if (N) {
+      VR_HIP(c, hipMemcpy(g.tris.data(), c->dTris.p, N * 12, hipMemcpyDeviceToHost));
+      VR_HIP(c, hipMemcpy(g.normal3.data(), c->dNormal3.p, N * 12, hipMemcpyDeviceToHost));
+      VR_HIP(c, hipMemcpy(g.triAreas.data(), c->dTriAreas.p, N * 4, hipMemcpyDeviceToHost));
+    }
+    c->hostGeoValid = true;
+    return VR_OK;
+  }
   g.points3.resize(N * 3);
   g.normal3.resize(N * 3);
   g.disk4.resize(N * 4);
@@ -218,7 +237,8 @@ int build_scene(vr_context *c) {
   s.nbDist = 2 * g.diskRadius;
   s.mortonAniso = K.mortonAniso;
   if (c->geoOnDevice) {
-    // (vr_set_disks_device left dPoints3 / dNormal3 / dDisk4 filled: nothing to upload)
+    // (vr_set_disks_device left dPoints3 / dNormal3 / dDisk4 filled, vr_set_triangles_device dVerts / dTris / dNormal3:
+    //  nothing to upload)
   } else if (disk) {
     VR_HIP(c, c->dNormal3.ensure((size_t)N * 3));
     VR_HIP(c, hipMemcpyAsync(c->dNormal3.p, g.normal3.data(), (size_t)N * 12, hipMemcpyHostToDevice, c->stream));

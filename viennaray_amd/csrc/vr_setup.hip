@@ -1304,15 +1304,169 @@ hipError_t launch_ingest_disks(const float *pts, const float *nrm, unsigned n, u
   return hipGetLastError();
 }
 
-// host_sort_plane for disks: 256 slices of [lo, hi] on the sort axis, each disk adds the area it shows the source
-// (r^2 |n_axis| / |n|) and that area times its coordinate, in double.  Double sums depend on their order, so the order is
-// fixed: a block takes one contiguous range of disks, a wave its 64-disk runs in turn; within a run the lanes of one
-// slice are summed by a butterfly (the same tree on every run) and added once to the wave's own LDS histogram; the
+// ---------------------------------------------------------------------------
+// Device-resident triangle mesh (vr_set_triangles_device), in two passes.  The first only reads the caller's buffers:
+// nothing resident may change before every index is known to be good.  The second, launched once the host has seen the
+// first one's seven words, makes what host_set_triangles makes.
+// ---------------------------------------------------------------------------
+constexpr unsigned kNoBadTriangle = 0xFFFFFFFFu;
+
+// Pass 1.  Both buffers are read as the flat runs they are (consecutive lanes, consecutive addresses).  The box of ALL
+// vertices, all three columns whatever D is (rayMesh.hpp:12-25), is reduced as ingest_disks_kernel reduces it and left
+// as six keys per block for ingest_bounds_kernel.  An index >= nverts is only compared, never followed: the lowest
+// triangle that holds one is reduced per wave, per block, and one atomic min per block (its result unused) leaves it in
+// *badTri (kNoBadTriangle before the launch).
+__global__ __launch_bounds__(256) void scan_mesh_kernel(const float *verts, unsigned nverts, const unsigned *tris,
+                                                        unsigned ntris, u64 *partials, unsigned *badTri) {
+  __shared__ u64 red[4][6];
+  __shared__ unsigned redBad[4];
+  u64 kmin[3] = {kMinIdentity, kMinIdentity, kMinIdentity}, kmax[3] = {kMaxIdentity, kMaxIdentity, kMaxIdentity};
+  const size_t step = (size_t)gridDim.x * INGEST_ROWS;
+  const size_t nf = (size_t)nverts * 3;
+  for (size_t j = (size_t)blockIdx.x * INGEST_ROWS + threadIdx.x; j < nf; j += step) {
+    const unsigned row = (unsigned)(j / 3), col = (unsigned)(j - 3 * (size_t)row);
+    const float v = verts[j];
+    const u64 a = box_min_key(v, row), b = box_max_key(v, row);
+#pragma unroll
+    for (unsigned k = 0; k < 3; ++k) { // (static register indices: the column only selects)
+      kmin[k] = (col == k && a < kmin[k]) ? a : kmin[k];
+      kmax[k] = (col == k && b > kmax[k]) ? b : kmax[k];
+    }
+  }
+  unsigned bad = kNoBadTriangle;
+  const size_t ni = (size_t)ntris * 3;
+  for (size_t j = (size_t)blockIdx.x * INGEST_ROWS + threadIdx.x; j < ni; j += step)
+    if (tris[j] >= nverts) {
+      const unsigned t = (unsigned)(j / 3);
+      bad = t < bad ? t : bad;
+    }
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned o = __shfl_down(bad, off, 64);
+    bad = o < bad ? o : bad;
+  }
+  for (int k = 0; k < 3; ++k) {
+    const u64 a = wave_min_u64(kmin[k]), b = wave_max_u64(kmax[k]);
+    if ((threadIdx.x & 63) == 0) {
+      red[threadIdx.x >> 6][k] = a;
+      red[threadIdx.x >> 6][3 + k] = b;
+    }
+  }
+  if ((threadIdx.x & 63) == 0)
+    redBad[threadIdx.x >> 6] = bad;
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    u64 v = red[0][threadIdx.x];
+    for (int w = 1; w < 4; ++w) {
+      const u64 o = red[w][threadIdx.x];
+      v = threadIdx.x < 3 ? (o < v ? o : v) : (o > v ? o : v);
+    }
+    partials[6 * (size_t)blockIdx.x + threadIdx.x] = v;
+  }
+  if (threadIdx.x == 64) { // (another wave than the one that writes the keys)
+    const unsigned b = min(min(redBad[0], redBad[1]), min(redBad[2], redBad[3]));
+    if (b != kNoBadTriangle)
+      atomicMin(badTri, b);
+  }
+}
+
+hipError_t launch_scan_mesh(const float *verts, unsigned nverts, const unsigned *tris, unsigned ntris,
+                            unsigned long long *partials, float *bounds6, unsigned *badTri, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(badTri, 0xFF, sizeof(unsigned), st);
+  if (e != hipSuccess)
+    return e;
+  const size_t rows = nverts > ntris ? nverts : ntris;
+  const size_t tiles = (rows * 3 + INGEST_ROWS - 1) / INGEST_ROWS;
+  const unsigned blocks = (unsigned)(tiles < INGEST_MAX_BLOCKS ? tiles : INGEST_MAX_BLOCKS);
+  if (blocks)
+    hipLaunchKernelGGL(scan_mesh_kernel, dim3(blocks), dim3(INGEST_ROWS), 0, st, verts, nverts, tris, ntris, partials,
+                       badTri);
+  hipLaunchKernelGGL(ingest_bounds_kernel, dim3(6), dim3(64), 0, st, partials, blocks, bounds6);
+  return hipGetLastError();
+}
+
+// Pass 2 (every index < nverts).  The vertices are copied as a flat run.  A tile of 256 triangles: its 768 indices are
+// read flat into LDS and written flat to outTris; thread r then gathers the three vertices of triangle r and computes the
+// normal and the area with host_set_triangles' operations in its order (vr_host.cpp: cross3 of v1 - v0 and v2 - v0, the
+// dot product summed (x + y) + z, sqrtf, three divisions, a zero-length normal left as it is; area = (float)(0.5 * norm)
+// with the product in double; D == 2: the even / odd edge rule of rayGeometryTriangle.hpp:62-75).  The normals leave
+// through LDS, flat again.
+__global__ __launch_bounds__(256) void pack_mesh_kernel(const float *verts, unsigned nverts, const unsigned *tris,
+                                                        unsigned ntris, int D, float *outVerts, unsigned *outTris,
+                                                        float *normal3, float *areas) {
+  __shared__ unsigned si[INGEST_ROWS * 3];
+  __shared__ float sn[INGEST_ROWS * 3];
+  const size_t step = (size_t)gridDim.x * INGEST_ROWS;
+  const size_t nf = (size_t)nverts * 3;
+  for (size_t j = (size_t)blockIdx.x * INGEST_ROWS + threadIdx.x; j < nf; j += step)
+    outVerts[j] = verts[j];
+  const unsigned tiles = (ntris + INGEST_ROWS - 1) / INGEST_ROWS;
+  for (unsigned t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const unsigned row0 = t * INGEST_ROWS, rows = min(INGEST_ROWS, ntris - row0);
+    const size_t o0 = (size_t)row0 * 3;
+    for (unsigned j = threadIdx.x; j < rows * 3; j += INGEST_ROWS) {
+      const unsigned v = tris[o0 + j];
+      si[j] = v;
+      outTris[o0 + j] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < rows) {
+      const unsigned r = threadIdx.x, i = row0 + r;
+      const float *a = verts + 3 * (size_t)si[3 * r], *b = verts + 3 * (size_t)si[3 * r + 1],
+                  *c = verts + 3 * (size_t)si[3 * r + 2];
+      // (plain operators: the build has -ffp-contract=off, and sqrt and division are the IEEE ones, as in vr_area.hpp)
+      const float ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2]; // v1 - v0
+      const float wx = c[0] - a[0], wy = c[1] - a[1], wz = c[2] - a[2]; // v2 - v0
+      float nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
+      const float nn = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
+      float len = nn; // (what the area is half of)
+      if (D == 2) {
+        const float ex = (i & 1u) ? wx : ux, ey = (i & 1u) ? wy : uy, ez = (i & 1u) ? wz : uz;
+        len = __builtin_sqrtf((ex * ex + ey * ey) + ez * ez);
+      }
+      areas[i] = (float)(0.5 * (double)len);
+      if (!(nn <= 0.f)) { // (normalize3 returns on n <= 0; a NaN length divides, as there)
+        nx /= nn;
+        ny /= nn;
+        nz /= nn;
+      }
+      sn[3 * r] = nx;
+      sn[3 * r + 1] = ny;
+      sn[3 * r + 2] = nz;
+    }
+    __syncthreads();
+    for (unsigned j = threadIdx.x; j < rows * 3; j += INGEST_ROWS)
+      normal3[o0 + j] = sn[j];
+    // (no barrier here: the next tile writes si, last read before the barrier above, and writes sn only behind its own
+    //  first barrier, which every thread reaches after these reads)
+  }
+}
+
+hipError_t launch_pack_mesh(const float *verts, unsigned nverts, const unsigned *tris, unsigned ntris, int D,
+                            float *outVerts, unsigned *outTris, float *normal3, float *areas, hipStream_t st) {
+  const size_t rows = nverts > ntris ? nverts : ntris;
+  const size_t tiles = (rows + INGEST_ROWS - 1) / INGEST_ROWS;
+  const unsigned blocks = (unsigned)(tiles < INGEST_MAX_BLOCKS ? tiles : INGEST_MAX_BLOCKS);
+  if (!blocks)
+    return hipSuccess;
+  hipLaunchKernelGGL(pack_mesh_kernel, dim3(blocks), dim3(INGEST_ROWS), 0, st, verts, nverts, tris, ntris, D, outVerts,
+                     outTris, normal3, areas);
+  return hipGetLastError();
+}
+
+// host_sort_plane on the device: 256 slices of [lo, hi] on the sort axis, each primitive adds the area it shows the source
+// and that area times its coordinate, in double — a disk (GEO 0) r^2 |n_axis| / |n| at its centre, a triangle (GEO 1)
+// the area of its projection along the axis at its centroid (vr_host.cpp, the two branches of host_sort_plane's loop).
+// Double sums depend on their order, so the order is
+// fixed: a block takes one contiguous range of primitives, a wave its 64-primitive runs in turn; within a run the lanes of
+// one slice are summed by a butterfly (the same tree on every run) and added once to the wave's own LDS histogram; the
 // waves, then the blocks (sort_plane_merge_kernel), are merged in index order.  The same input gives the same bits.
 constexpr int SORT_SLICES = 256;
 constexpr unsigned SORT_MAX_BLOCKS = 256;
-__global__ __launch_bounds__(256) void sort_plane_kernel(const float4 *disk4, const float *normal3, unsigned n, int axis,
-                                                         float lo, float hi, double *partials) {
+// GEO 0: disk4 / normal3;  GEO 1: verts / tris (passed in their places)
+template <int GEO>
+__global__ __launch_bounds__(256) void sort_plane_kernel(const float4 *disk4, const float *normal3, const float *verts,
+                                                         const unsigned *tris, unsigned n, int axis, float lo, float hi,
+                                                         double *partials) {
   __shared__ double hw[4][SORT_SLICES], hwh[4][SORT_SLICES];
   for (unsigned j = threadIdx.x; j < 4 * SORT_SLICES; j += 256) {
     (&hw[0][0])[j] = 0.;
@@ -1329,12 +1483,23 @@ __global__ __launch_bounds__(256) void sort_plane_kernel(const float4 *disk4, co
     int k = -1;
     double a = 0., ah = 0.;
     if (valid) {
-      const float4 d = disk4[i];
-      const float nx = normal3[3 * (size_t)i], ny = normal3[3 * (size_t)i + 1], nz = normal3[3 * (size_t)i + 2];
-      const double nn = sqrt((double)nx * nx + (double)ny * ny + (double)nz * nz);
-      const double h = axis == 0 ? d.x : axis == 1 ? d.y : d.z;
-      const float na = axis == 0 ? nx : axis == 1 ? ny : nz;
-      a = nn > 0. ? (double)d.w * d.w * fabs((double)na) / nn : 0.;
+      double h;
+      if constexpr (GEO == 0) {
+        const float4 d = disk4[i];
+        const float nx = normal3[3 * (size_t)i], ny = normal3[3 * (size_t)i + 1], nz = normal3[3 * (size_t)i + 2];
+        const double nn = sqrt((double)nx * nx + (double)ny * ny + (double)nz * nz);
+        h = axis == 0 ? d.x : axis == 1 ? d.y : d.z;
+        const float na = axis == 0 ? nx : axis == 1 ? ny : nz;
+        a = nn > 0. ? (double)d.w * d.w * fabs((double)na) / nn : 0.;
+      } else {
+        const float *v0 = verts + 3 * (size_t)tris[3 * (size_t)i], *v1 = verts + 3 * (size_t)tris[3 * (size_t)i + 1],
+                    *v2 = verts + 3 * (size_t)tris[3 * (size_t)i + 2];
+        const int a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
+        const double e10 = (double)v1[a1] - v0[a1], e11 = (double)v1[a2] - v0[a2];
+        const double e20 = (double)v2[a1] - v0[a1], e21 = (double)v2[a2] - v0[a2];
+        h = ((double)v0[axis] + v1[axis] + v2[axis]) / 3.;
+        a = 0.5 * fabs(e10 * e21 - e11 * e20);
+      }
       ah = a * h;
       k = (int)((h - lo) * inv);
       k = k < 0 ? 0 : (k >= SORT_SLICES ? SORT_SLICES - 1 : k);
@@ -1372,14 +1537,18 @@ __global__ __launch_bounds__(256) void sort_plane_merge_kernel(const double *par
 
 size_t sort_plane_partials_entries() { return 2 * (size_t)SORT_SLICES * SORT_MAX_BLOCKS; }
 
-hipError_t launch_sort_plane(const float *disk4, const float *normal3, unsigned n, int axis, float lo, float hi,
-                             double *partials, double *hist512, hipStream_t st) {
+hipError_t launch_sort_plane(int geo, const float *disk4, const float *normal3, const float *verts, const unsigned *tris,
+                             unsigned n, int axis, float lo, float hi, double *partials, double *hist512, hipStream_t st) {
   if (n == 0)
     return hipSuccess;
   const unsigned tiles = (n + 255) / 256;
   const unsigned blocks = tiles < SORT_MAX_BLOCKS ? tiles : SORT_MAX_BLOCKS;
-  hipLaunchKernelGGL(sort_plane_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float4 *>(disk4), normal3, n,
-                     axis, lo, hi, partials);
+  if (geo == 0)
+    hipLaunchKernelGGL(sort_plane_kernel<0>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float4 *>(disk4),
+                       normal3, verts, tris, n, axis, lo, hi, partials);
+  else
+    hipLaunchKernelGGL(sort_plane_kernel<1>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float4 *>(disk4),
+                       normal3, verts, tris, n, axis, lo, hi, partials);
   hipLaunchKernelGGL(sort_plane_merge_kernel, dim3(2), dim3(256), 0, st, partials, blocks, hist512);
   return hipGetLastError();
 }

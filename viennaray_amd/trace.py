@@ -844,15 +844,41 @@ class TraceTriangle(Trace):
     """rayTraceTriangle.hpp:13-154"""
 
     def setLineGeometry(self, nodes, lines, gridDelta):
-        """setGeometry(LineMesh) (rayTraceTriangle.hpp:76-81, D == 2): lines -> triangle strips"""
+        """setGeometry(LineMesh) (rayTraceTriangle.hpp:76-81, D == 2): lines -> triangle strips.  Host arrays only: the
+        strips are made on the host (io.lines_to_triangles); a device-side LineMesh is out of scope — convert on the
+        device and hand the triangles to setGeometry as tensors."""
         from . import io
         v, t, _ = io.lines_to_triangles(nodes, lines, gridDelta)
         self.setGeometry(v, t, gridDelta)
 
     def setGeometry(self, points, triangles, gridDelta):
+        """points: [nv, 3], triangles: [nt, 3] vertex indices.  Two torch tensors on the tracer's device (points
+        float32, triangles int32 — torch has no general uint32; a negative value reads as an index out of range and is
+        refused — both contiguous) are handed over where they are (vr_set_triangles_device): validated and copied on
+        the device, ordered behind the current torch stream, and the tensors may be overwritten as soon as this
+        returns.  A tensor that cannot go that way raises ValueError — it is never copied through the host behind the
+        caller's back."""
+        if _on_any_device(points) or _on_any_device(triangles):
+            return self._setGeometryDevice(points, triangles, gridDelta)
         v = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
         t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
         self._n = t.shape[0]
         self._check(self._L.vr_set_triangles(self._h, _fptr(v), v.shape[0],
                                              t.ctypes.data_as(C.POINTER(C.c_uint32)), self._n,
                                              float(gridDelta), self.D))
+
+    def debugTriangleMesh(self):
+        """(unit normals [nt, 3], areas [nt]) of the mesh in force (vr_debug_triangle_mesh)"""
+        nrm = np.empty((self._n, 3), dtype=np.float32)
+        area = np.empty(self._n, dtype=np.float32)
+        self._check(self._L.vr_debug_triangle_mesh(self._h, _fptr(nrm), _fptr(area), self._n))
+        return nrm, area
+
+    def _setGeometryDevice(self, points, triangles, gridDelta):
+        _check_device_tensor("setGeometry", "points", points, self._device, "torch.float32", [(None, 3)])
+        _check_device_tensor("setGeometry", "triangles", triangles, self._device, "torch.int32", [(None, 3)])
+        nv, nt = int(points.shape[0]), int(triangles.shape[0])
+        self._check(self._L.vr_set_triangles_device(self._h, C.c_void_p(points.data_ptr()), nv,
+                                                    C.c_void_p(triangles.data_ptr()), nt, float(gridDelta), self.D,
+                                                    C.c_void_p(self._torch_stream())))
+        self._n = nt
