@@ -402,7 +402,7 @@ int vr_debug_bvh_check(vr_context *ctx, uint32_t *violations);
 /* Measurement aid (bench.py's roofline): the instruction-issue ceiling of the device for one of
  * the instruction mixes the hot kernels are made of (0 f32 VALU independent, 1 f32 VALU dependent
  * chain, 2 mt19937_64 seeding steps, 3 SALU, 4 packet-traversal VALU+SALU mix,
- * 5 independent VALU+SALU mix), at `wavesPerSimd`
+ * 5 independent VALU+SALU mix, 7 the absorbing flat-scene tracer's 1.6 : 1 VALU+SALU mix), at `wavesPerSimd`
  * resident waves per SIMD.  out4 = {counted instructions / s, sustained clock Hz, seconds, count} */
 int vr_debug_issue_rate(vr_context *ctx, int kind, int wavesPerSimd, uint32_t iters, double *out4);
 

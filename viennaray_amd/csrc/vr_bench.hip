@@ -13,6 +13,10 @@
 //   KIND 4  packet-traversal mix: 24 VALU + 16 SALU interleaved, SALU consuming a VALU compare
 //           (v_cmp -> s_and_b64), i.e. the vote pattern of bvh_hit_packet
 //   KIND 5  24 VALU + 16 SALU interleaved, the two streams independent (can they co-issue?)
+//   KIND 7  32 VALU + 20 SALU interleaved: the 1.6 : 1 ratio of the absorbing flat-scene tracer's round
+//           (3.08e9 VALU : 1.91e9 SALU per launch), one vote per eight VALU, the other SALU bookkeeping.
+//           Every block is four waves, one per SIMD, so at w waves per SIMD all four SIMDs of a CU
+//           queue for its one scalar unit: SALU per CU-clock here is what that unit sustains in this mix.
 //
 // Every wave runs `iters` passes over an unrolled body with a known instruction count, so
 // rate = waves x iters x body / time (HIP events); rocprofv3's SQ_INSTS_VALU / SQ_INSTS_SALU
@@ -94,6 +98,16 @@ template <int KIND> __global__ __launch_bounds__(256) void issue_kernel(unsigned
                    : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+s"(s0), "+s"(s1)
                    : "v"(m), "v"(c)
                    : "scc");
+    } else if (KIND == 7) {
+      // 32 VALU + 20 SALU per pass: the tracer's ratio; a vote and four bookkeeping SALU per eight VALU
+      asm volatile(VR_REP4("v_fma_f32 %0, %0, %8, %9\n v_min_f32 %1, %1, %0\n s_add_u32 %4, %4, 1\n"
+                           "v_fma_f32 %2, %2, %8, %9\n v_max_f32 %3, %3, %2\n s_xor_b32 %5, %5, %4\n"
+                           "v_cmp_le_f32 vcc, %0, %1\n s_and_b64 vcc, vcc, exec\n v_fma_f32 %0, %0, %8, %9\n"
+                           "s_lshl_b32 %6, %6, 1\n v_fma_f32 %2, %2, %8, %9\n v_min_f32 %1, %1, %3\n"
+                           "s_and_b32 %7, %7, %5\n")
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3)
+                   : "v"(m), "v"(c)
+                   : "vcc", "scc");
     } else {
       // 24 VALU + 16 SALU per pass: slab-test arithmetic, a vote, scalar bookkeeping
       asm volatile(VR_REP8("v_fma_f32 %0, %0, %4, %5\n v_min_f32 %1, %1, %0\n s_add_u32 %2, %2, 1\n"
@@ -117,7 +131,7 @@ template <int KIND> __global__ __launch_bounds__(256) void issue_kernel(unsigned
 }
 
 // counted per pass of the body: 32 VALU (kinds 0, 1), 32 mt_step (kind 2: one 64-bit
-// multiply-add each), 32 SALU (kind 3), 24 VALU + 16 SALU (kind 4)
+// multiply-add each), 32 SALU (kind 3), 24 VALU + 16 SALU (kinds 4, 5), 32 VALU + 20 SALU (kind 7)
 hipError_t launch_issue_kernel(int kind, unsigned blocks, unsigned iters, void *out, hipStream_t s) {
   IssueOut *o = reinterpret_cast<IssueOut *>(out);
   switch (kind) {
@@ -127,6 +141,7 @@ hipError_t launch_issue_kernel(int kind, unsigned blocks, unsigned iters, void *
   case 3: hipLaunchKernelGGL((issue_kernel<3>), dim3(blocks), dim3(256), 0, s, iters, o, 1.0f); break;
   case 5: hipLaunchKernelGGL((issue_kernel<5>), dim3(blocks), dim3(256), 0, s, iters, o, 1.0f); break;
   case 6: hipLaunchKernelGGL((issue_kernel<6>), dim3(blocks), dim3(256), 0, s, iters, o, 1.0f); break;
+  case 7: hipLaunchKernelGGL((issue_kernel<7>), dim3(blocks), dim3(256), 0, s, iters, o, 1.0f); break;
   default: hipLaunchKernelGGL((issue_kernel<4>), dim3(blocks), dim3(256), 0, s, iters, o, 1.0f); break;
   }
   return hipGetLastError();

@@ -222,7 +222,7 @@ int vr_debug_bvh_check(vr_context *c, uint32_t *violations) {
 // out4 = {counted instructions per second, sustained clock in Hz (median over waves),
 //         seconds (HIP events), counted instructions}
 int vr_debug_issue_rate(vr_context *c, int kind, int wavesPerSimd, uint32_t iters, double *out4) {
-  if (!c || !out4 || kind < 0 || kind > 6 || wavesPerSimd < 1 || wavesPerSimd > 8 || iters == 0)
+  if (!c || !out4 || kind < 0 || kind > 7 || wavesPerSimd < 1 || wavesPerSimd > 8 || iters == 0)
     return fail(c, VR_E_INVALID, "vr_debug_issue_rate: bad argument");
   VR_HIP(c, hipSetDevice(c->device));
   const unsigned blocks = (unsigned)c->numCUs * (unsigned)wavesPerSimd;

@@ -1032,6 +1032,9 @@ __device__ __forceinline__ void wave_minmax6(float &a, float &b, float &c, float
 }
 
 __device__ __forceinline__ bool local_disc_hit(const V3 &ro, const V3 &rd, const float4 &c4, const V3 &n);
+__device__ __forceinline__ bool local_disc_hit_lds(const V3 &ro, const V3 &rd, const float4 &c4, const V3 &n);
+__device__ __forceinline__ bool hit_disc_lds(const V3 &o, const V3 &d, float tnear, const float4 &c4, const V3 &n, float &tOut);
+__device__ __forceinline__ bool hit_update_lds(HitRec &h, bool ok, float t, unsigned orig, unsigned q);
 
 __device__ __forceinline__ float lane_bcast(float v, int srcLane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), srcLane));
@@ -1087,7 +1090,8 @@ constexpr unsigned VR_PQ_RECORDS = 2 * 52;
 // lst[39]: valid; cboxes: the leaf nodes' own boxes); a later round whose box lies inside S filters the kept nodes by ITS
 // box — from LDS, no node load — and goes straight to the primitive records of those that meet it: the very nodes an
 // exact descent would have found.  The candidates are filtered with the round's own box as before: bit-identical.
-template <int GEO, bool CREDIT, bool FRAME_LDS = false, bool KEEPQ = false, bool RELIEF = false, bool CACHE = false>
+// LEAN (the 3-D absorbing flat-scene kernels): the candidate loop's disc tests in their branch-free forms (hit_disc_lds)
+template <int GEO, bool CREDIT, bool FRAME_LDS = false, bool KEEPQ = false, bool RELIEF = false, bool CACHE = false, bool LEAN = false>
 __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, const V3 &o, const V3 &d, float tnear,
                                               HitRec &h, volatile VR_LDS unsigned *lst, PqCands &cd,
                                               const float *__restrict__ wallS, volatile VR_LDS float *cboxes, float tWall VR_DIAG_ARGS) {
@@ -1362,8 +1366,14 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
         const float4 c4 = make_float4(lane_bcast(r0.x, k), lane_bcast(r0.y, k), lane_bcast(r0.z, k), lane_bcast(r0.w, k));
         const V3 n = mk(lane_bcast(r1.x, k), lane_bcast(r1.y, k), lane_bcast(r1.z, k));
         const unsigned orig = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(r1.w), k);
-        const bool ok = hit_disc(o, d, tnear, c4, n, t);
-        const bool took = hit_update(h, part && ok, t, orig, qq);
+        bool ok, took;
+        if constexpr (LEAN) { // (the absorbing flat-scene kernel: the branch-free forms, see hit_disc_lds)
+          ok = hit_disc_lds(o, d, tnear, c4, n, t);
+          took = hit_update_lds(h, part & ok, t, orig, qq);
+        } else {
+          ok = hit_disc(o, d, tnear, c4, n, t);
+          took = hit_update(h, part && ok, t, orig, qq);
+        }
         if (CREDIT) {
           const int c = (int)tests;
           cd.mine = took ? (unsigned)c : cd.mine;
@@ -1373,7 +1383,9 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
           }
           // (a wave-wide early out between the cheap sign tests and the division / distance part of
           //  these two tests was measured: the extra votes and branches cost more than they save)
-          if (part && local_disc_hit(o, d, c4, n))
+          if constexpr (LEAN)
+            cd.local |= (unsigned long long)(part & local_disc_hit_lds(o, d, c4, n)) << c;
+          else if (part && local_disc_hit(o, d, c4, n))
             cd.local |= 1ull << c;
           cd.count = tests + 1u;
         }
@@ -1394,6 +1406,43 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
     VR_PQ_MARK(15); // (diag: the exact tests)
   }
   return true;
+}
+
+// hit_disc / hit_update / local_disc_hit (below) for the candidate loop of the absorbing flat-scene kernel's packet query
+// (pq_hit_packet LEAN): the same arithmetic in the same order, every condition evaluated and combined at the end
+// instead of a nest of early returns.  Each early return was a divergent branch — saving and restoring the exec mask
+// on the CU's one scalar unit, which is what that kernel queues for (profiles/salu_inventory_mode1.md) — and saved
+// nothing: a candidate passed the query's box test, so some lane of the wave nearly always goes all the way.
+// (A lane that fails an early condition computes on with an infinity or a NaN and is masked out by that condition.)
+__device__ __forceinline__ bool hit_disc_lds(const V3 &o, const V3 &d, float tnear, const float4 &c4, const V3 &n,
+                                             float &tOut) {
+  const float divisor = edot(d, n);
+  const V3 co = V3{c4.x - o.x, c4.y - o.y, c4.z - o.z};
+  const float t = edot(co, n) / divisor;
+  const V3 p = V3{o.x + d.x * t - c4.x, o.y + d.y * t - c4.y, o.z + d.z * t - c4.z};
+  const float dist2 = edot(p, p);
+  tOut = t;
+  return (divisor != 0.f) & (tnear <= t) & (t <= 3.402823466e+38f) & (dist2 < c4.w * c4.w);
+}
+__device__ __forceinline__ bool hit_update_lds(HitRec &h, bool ok, float t, unsigned orig, unsigned q) {
+  const bool take = ok & ((t < h.t) | ((t == h.t) & (h.geom == 1) & (orig < h.prim)));
+  h.t = take ? t : h.t;
+  h.geom = take ? 1 : h.geom;
+  h.prim = take ? orig : h.prim;
+  h.pos = take ? q : h.pos;
+  return take;
+}
+__device__ __forceinline__ bool local_disc_hit_lds(const V3 &ro, const V3 &rd, const float4 &c4, const V3 &n) {
+  const float prod = vdot(n, rd);
+  const V3 c = V3{c4.x, c4.y, c4.z};
+  const float ddneg = vdot(c, n);
+  const float tt = (ddneg - vdot(n, ro)) / prod;
+  V3 hp = V3{rd.x * tt + ro.x, rd.y * tt + ro.y, rd.z * tt + ro.z};
+  hp.x = hp.x - c.x;
+  hp.y = hp.y - c.y;
+  hp.z = hp.z - c.z;
+  const float dist = sqrtf(vdot(hp, hp));
+  return !(prod > 0.f) & !(fabsf(prod) < 1e-6f) & !(tt <= 0.f) & (c4.w > dist);
 }
 
 // rayTraceKernel.hpp:462-507 (neighbour disk test)

@@ -671,6 +671,9 @@ trace_kernel(const TraceParams p) {
   constexpr bool RESUME = MODE_ == 7;
   constexpr int MODE = (SMALL || RESUME) ? 0 : (MODE_ == 5 ? 1 : (MODE_ == 6 ? 3 : MODE_));
   constexpr bool FRAME_LDS = MODE == 1; // (the wall / scene-box frame from LDS: hit_walls_lds, vr_device.hpp)
+  // (the scalar diet of the absorbing flat-scene kernel — branch-free candidate tests, lane-parallel crediting — in three
+  //  dimensions only: the 2-D instantiations answered it with vector spills, DESIGN_APPENDIX A)
+  constexpr bool LEAN = MODE == 1 && D == 3 && GEO == 0 && PARTICLE < P_EXT;
   constexpr bool FOLLOW = MODE == 3;    // (follow-up segments inside the round of a packet query: end of the round)
   constexpr bool ABSORB = MODE == 1 || MODE == 2;
   // PARTICLE 0 / 1: DiffuseParticle / SpecularParticle compiled in.  PARTICLE 2 (P_EXT): the
@@ -1063,7 +1066,7 @@ trace_kernel(const TraceParams p) {
             tWall = hw.geom == 0 ? hw.t : tWall;
           }
         }
-        packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
+        packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE, LEAN>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
         pqCredit = PQ_CREDIT && packetDone;
         pqFails = packetDone ? 0u : (pqFails < 6u ? pqFails + 1u : 6u);
         pqSkip = packetDone ? 0u : (1u << pqFails) - 1u;
@@ -1436,6 +1439,27 @@ trace_kernel(const TraceParams p) {
             candAcc[k] = 0ull;
           __builtin_amdgcn_wave_barrier();
         }
+        if constexpr (LEAN) {
+          // The absorbing flat-scene kernel: unit weights, so candidate c receives (lanes crediting it) x 2^40.  The vote
+          // per candidate leaves its count with LANE c, and the lanes then send all the counts in ONE wave instruction of
+          // atomics on distinct addresses.  (One single-lane atomic per candidate — behind a branch on the vote, a
+          // first-lane election and the scalar address of fluxAcc[q] — was 36 scalar instructions per candidate, a
+          // quarter of the scalar work of a round: profiles/salu_inventory_mode1.md.  Integer adds: the sums are the same.)
+          unsigned mine = 0u; // lane c: the number of lanes that credit candidate c (cands.count <= VR_PQ_CANDS < 64)
+          for (unsigned c = 0; c < cands.count; ++c) {
+            DIAG(6);
+            const U4 cr = cands.rec[c];
+            const float dx = px - __uint_as_float(cr.y), dy = py - __uint_as_float(cr.z), dz = pz - __uint_as_float(cr.w);
+            // (every condition evaluated, combined at the end: no divergent branch)
+            const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
+            const bool near = (ax <= dist) & (ay <= dist) & ((p.geoD == 2) | (az <= dist)) & (((dx * dx + dy * dy) + dz * dz) <= dist2);
+            const bool sel = creditLane & ((h.pos == cr.x) | (near & (((cands.local >> c) & 1ull) != 0ull)));
+            const unsigned n = (unsigned)__popcll(ballot64(sel));
+            mine = lane == c ? n : mine;
+          }
+          if (lane < cands.count && mine)
+            atomicAdd(&fluxAcc[cands.rec[lane].x], (u64)mine * 1099511627776ull); // unit weights: count x 2^40
+        } else
         for (unsigned c = 0; c < cands.count; ++c) {
           DIAG(6);
           const U4 cr = cands.rec[c];
