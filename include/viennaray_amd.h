@@ -135,7 +135,8 @@ int vr_set_triangles(vr_context *ctx, const float *verts, uint32_t nverts,
  * device before anything else happens: an index >= nverts is refused with vr_set_triangles' message and the lowest
  * offending triangle.  Every refusal leaves the previous geometry in place and the context usable.  Accepted, one kernel
  * copies both buffers and makes the unit normals and areas, bit for bit those of vr_set_triangles; `stream` is made to
- * wait for it, so the caller may overwrite or free its buffers at once.  One synchronisation with the host per call:
+ * wait for it, so the caller may reuse its buffers with work queued on `stream` at once (from the host, or to free them,
+ * after synchronising `stream`).  One synchronisation with the host per call:
  * seven words come back (the bounding box over all vertices and the index check).  The host copies are made only if a
  * host path (VR_HOST_BUILD) asks for them.  Non-finite vertices are the caller's error, as for vr_set_triangles. */
 int vr_set_triangles_device(vr_context *ctx, const float *verts, uint32_t nverts, const uint32_t *tris, uint32_t ntris,

@@ -1147,12 +1147,9 @@ public:
   /// as the host setter would and leaves the previous source in place.  The buffers are free again on return.
   void setSurfaceSourceDevice(const float *dPositions, const float *dNormals, const float *dWeights, size_t n, unsigned ld,
                               NumericType sourceArea, NumericType sourceOffset, void *stream = nullptr) {
-    if (!ctx_)
-      return;
-    const int rc = vr_set_surface_source_device(ctx_, dPositions, dNormals, dWeights, (uint32_t)n, ld, (float)sourceArea,
-                                                (float)sourceOffset, stream);
-    check(rc);
-    if (rc == VR_OK && n) {
+    if (deviceCall(false, vr_set_surface_source_device, dPositions, dNormals, dWeights, n, ld, sourceArea, sourceOffset,
+                   stream) &&
+        n) {
       pSource_.reset();
       sourceOnDevice_ = false;
     }
@@ -1160,8 +1157,7 @@ public:
   /// setMaterialIds for ids that live on the device (vr_set_material_ids_device): n int32 in the caller's primitive
   /// order, produced on `stream`; a primitive beyond n has id 0.
   void setMaterialIdsDevice(const int32_t *dIds, size_t n, void *stream = nullptr) {
-    if (ctx_)
-      check(vr_set_material_ids_device(ctx_, dIds, (uint32_t)n, stream));
+    deviceCall(false, vr_set_material_ids_device, dIds, n, stream);
   }
   void enableProgressBar() {}
   void disableProgressBar() {}
@@ -1199,11 +1195,7 @@ public:
   /// borrowed TracingData holds at that index, until setGlobalData(TracingData &) is called again.  dData == nullptr or
   /// n == 0 drops the vector and those behind it.
   void setGlobalDataDevice(unsigned vecIdx, const float *dData, size_t n, void *stream = nullptr) {
-    if (!ctx_)
-      return;
-    const int rc = vr_set_global_data_device(ctx_, vecIdx, dData, (uint32_t)n, stream);
-    check(rc);
-    if (rc != VR_OK)
+    if (!deviceCall(false, vr_set_global_data_device, vecIdx, dData, n, stream))
       return;
     if (dData && n)
       deviceGlobal_ |= 1u << vecIdx;
@@ -1262,6 +1254,16 @@ protected:
   void geometryAccepted(int rc) { // a new geometry clears an earlier refusal
     setterError_ = false;
     check(rc);
+  }
+  // One of the C ABI's device entry points (vr_*_device), whose last parameter is the caller's stream: the arguments
+  // converted to its parameter types, the result checked as a setter's (a geometry's: geometryAccepted).  true if it
+  // was accepted; without a context nothing is called.
+  template <class... P, class... A> bool deviceCall(bool geometry, int (*entry)(vr_context *, P...), A... args) {
+    if (!ctx_)
+      return false;
+    const int rc = entry(ctx_, static_cast<P>(args)...);
+    geometry ? geometryAccepted(rc) : check(rc);
+    return rc == VR_OK;
   }
   // rayTrace.hpp:137-145: the borrowed global data may have changed since the last apply — its vectors and scalars
   // go to HBM again (they are what the device particle models read; a few MB at most)
@@ -1435,9 +1437,7 @@ public:
   }
   void setGeometryDevice(const float *dPoints, const float *dNormals, size_t n, unsigned ld, NumericType gridDelta,
                          NumericType diskRadii, void *stream) {
-    if (this->ctx_)
-      this->geometryAccepted(vr_set_disks_device(this->ctx_, dPoints, dNormals, (uint32_t)n, ld, (float)gridDelta,
-                                                 (float)diskRadii, D, stream));
+    this->deviceCall(true, vr_set_disks_device, dPoints, dNormals, n, ld, gridDelta, diskRadii, D, stream);
   }
   template <typename T> void setMaterialIds(std::vector<T> const &materialIds) {
     std::vector<int32_t> ids(materialIds.begin(), materialIds.end());
@@ -1462,12 +1462,10 @@ public:
   /// setGeometry for a mesh that already lives on the device (vr_set_triangles_device): dVerts is a DEVICE pointer to
   /// nverts rows of 3 floats, dTris one to ntris rows of 3 unsigned, both produced on `stream` (the caller's hipStream_t,
   /// nullptr = the null stream).  The library checks the indices and takes its own copy on the device: the buffers are
-  /// free again on return.
+  /// free for work queued on `stream` afterwards.
   void setGeometryDevice(const float *dVerts, size_t nverts, const unsigned *dTris, size_t ntris, NumericType gridDelta,
                          void *stream = nullptr) {
-    if (this->ctx_)
-      this->geometryAccepted(vr_set_triangles_device(this->ctx_, dVerts, (uint32_t)nverts, dTris, (uint32_t)ntris,
-                                                     (float)gridDelta, D, stream));
+    this->deviceCall(true, vr_set_triangles_device, dVerts, nverts, dTris, ntris, gridDelta, D, stream);
   }
   void setGeometry(const TriangleMesh &mesh) {
     std::vector<VectorType<NumericType, 3>> pts(mesh.nodes.size());

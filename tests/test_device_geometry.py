@@ -54,6 +54,98 @@ def test_trace_module_does_not_import_torch():
         assert not line.startswith(("import torch", "from torch")), line  # (only inside the two methods that need it)
 
 
+class _StandInDevice:
+    def __init__(self, kind, index):
+        self.type, self.index = kind, index
+
+    def __str__(self):
+        return f"{self.type}:{self.index}"
+
+
+class _StandInTensor:
+    """what trace.py looks at in a torch tensor, with no torch and no device behind it"""
+
+    def __init__(self, shape, dtype="torch.float32", index=0, contiguous=True, kind="cuda"):
+        self.shape, self.dtype, self.device, self.is_cuda = tuple(shape), dtype, _StandInDevice(kind, index), kind == "cuda"
+        self._contiguous = contiguous
+
+    def data_ptr(self):
+        return 0x1000
+
+    def is_contiguous(self):
+        return self._contiguous
+
+    def stride(self):
+        return tuple(int(np.prod(self.shape[k + 1:])) + (0 if self._contiguous else 1) for k in range(len(self.shape)))
+
+    def __len__(self):
+        return self.shape[0]
+
+
+class _RecordingLibrary:
+    """stands in for the C ABI behind a TraceDisk that was never created: records the one call that gets through"""
+
+    def __init__(self):
+        self.calls = []
+
+    def vr_set_disks_device(self, *args):
+        self.calls.append(args)
+        return capi.VR_OK
+
+
+def _disk_tracer_without_context(D):
+    t = vr.TraceDisk.__new__(vr.TraceDisk)  # (no vr_create: no device is needed to be refused)
+    t.D, t._device, t._h, t._L = D, 0, None, _RecordingLibrary()
+    t._torch_stream = lambda: 0
+    return t
+
+
+_GOOD = dict(shape=(8, 3))
+# (what is wrong with the tensor, the category word of the refusal)
+DISK_TENSOR_REFUSALS = [
+    (dict(shape=(8, 3), index=1), "device"),            # the wrong device index
+    (dict(shape=(8, 3), kind="xpu"), "device"),         # a device type that cannot be handed over: not through the host
+    (dict(shape=(8, 3), dtype="torch.float64"), "dtype"),
+    (dict(shape=(24,)), "shape"),                       # 1-D
+    (dict(shape=(8, 4)), "shape"),                      # 4 columns
+    (dict(shape=(8, 2)), "shape"),                      # 2 columns on a 3-D tracer
+    (dict(shape=(8, 3), contiguous=False), "contiguity"),
+    (dict(shape=(7, 3)), "shape"),                      # points and normals differ
+]
+
+
+@pytest.mark.parametrize("defect,word,which", [(d, w, k) for d, w in DISK_TENSOR_REFUSALS for k in ("points", "normals", "both")
+                                               if not (k == "both" and d["shape"] == (7, 3))])  # (the same shape twice)
+def test_disk_tensors_that_cannot_be_handed_over_are_refused_without_a_device(defect, word, which):
+    """every refusal of TraceDisk.setGeometry on tensors, by its category word, for a defect in either argument or in
+    both; nothing reaches the C ABI"""
+    t = _disk_tracer_without_context(3)
+    p = _StandInTensor(**(defect if which != "normals" else _GOOD))
+    n = _StandInTensor(**(defect if which != "points" else _GOOD))
+    with pytest.raises(ValueError, match=rf"^setGeometry: {word}: "):
+        t.setGeometry(p, n, 1.0)
+    assert t._L.calls == []
+
+
+@pytest.mark.parametrize("host_side", ["points", "normals"])
+def test_one_disk_argument_on_the_host_is_refused_without_a_device(host_side):
+    t = _disk_tracer_without_context(3)
+    host, dev = np.zeros((8, 3), np.float32), _StandInTensor(**_GOOD)
+    with pytest.raises(ValueError, match=r"^setGeometry: device: "):
+        t.setGeometry(*((host, dev) if host_side == "points" else (dev, host)), 1.0)
+    assert t._L.calls == []
+
+
+@pytest.mark.parametrize("D,cols", [(3, 3), (2, 3), (2, 2)])
+def test_disk_tensors_that_can_be_handed_over_reach_the_entry_point(D, cols):
+    """(the control of the refusals above: the stand-in is accepted where a tensor would be)"""
+    t = _disk_tracer_without_context(D)
+    t.setGeometry(_StandInTensor((8, cols)), _StandInTensor((8, cols)), 0.5, 0.25)
+    (call,) = t._L.calls
+    assert [a.value if hasattr(a, "value") else a for a in call[1:]] == [0x1000, 0x1000, 8, cols, 0.5, 0.25, D, None]
+    assert t._n == 8
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------

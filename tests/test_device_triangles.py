@@ -280,6 +280,22 @@ def test_an_index_out_of_range_is_refused_and_names_the_triangle(trench_referenc
     assert tr._n == t.shape[0]
     tr.apply()
     _assert_same(trench_reference["obs"], _observe(tr))
+    # ... and after the two refusals of the C entry points themselves, one that comes with the scan's verdict and one
+    # that comes before anything is looked at: the code, and the previous geometry's flux exactly
+    L = capi.load()
+    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+    one_bad = t2.astype(np.int64)
+    one_bad[100, 0] = nv
+    ti = torch.from_numpy(one_bad.astype(np.int32)).cuda()
+    refusals = [lambda: L.vr_set_triangles_device(tr._h, ptr(tv2), nv, ptr(ti), t2.shape[0], gd2, 3, None),
+                lambda: L.vr_set_disks_device(tr._h, ptr(tv2), ptr(tv2), nv, 2, gd2, 0.0, 3, None)]  # ld = 2, D = 3
+    for refused, said in zip(refusals, (b"vertex index out of range (triangle 100)", b"D == 2")):
+        assert refused() == capi.VR_E_INVALID
+        assert said in L.vr_last_error(tr._h)
+        assert L.vr_num_primitives(tr._h) == t.shape[0]
+        tr.setRunNumber(1)  # (every apply advances it: the reference traced run 1)
+        tr.apply()
+        _assert_same(trench_reference["obs"], _observe(tr))
 
 
 class _ElsewhereTensor:
@@ -502,6 +518,56 @@ def test_switching_between_geometries_on_one_context():
     apply_and_compare(fresh_disk(), False)
     tr.setGeometry(*_tensors(vG, tG), gdG)  # (a device mesh over host disks)
     apply_and_compare(_host_run(3, gdG, vG, tG, sticking, PER, rays), True)
+
+
+@pytest.mark.gpu
+def test_every_kind_and_side_in_turn_on_one_context():
+    """host disks -> device disks -> host triangles -> device triangles -> host disks on ONE context, an 8 x 8 plane
+    patch as 64 disks and as 98 triangles, 2000 rays after each step: flux, box and primitive count are a fresh context's,
+    bit for bit.  Every setter ends in the same commit: nothing of the previous kind or side may survive it."""
+    torch = _torch()
+    L = capi.load()
+    rays = 2000
+    gd, v, t = grid_mesh(98, width=7, ripple=0.0)
+    p = v.copy()
+    n = np.zeros_like(p)
+    n[:, 2] = 1.0
+    assert p.shape == (64, 3) and t.shape == (98, 3)
+    tp, tn = torch.from_numpy(p).cuda(), torch.from_numpy(n).cuda()
+    tv, tt = _tensors(v, t)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+
+    def observe(tr, count):
+        tr._n = count
+        tr.setRunNumber(1)  # (every apply advances it)
+        tr.apply()
+        return dict(flux=tr.getLocalData().getVectorData(0).copy(), bbox=tr.getBoundingBox().copy(),
+                    count=int(L.vr_num_primitives(tr._h)))
+
+    def fresh(set_geometry, count):
+        f = vr.TraceTriangle(3)
+        _configure(f, 3, 0.1, PER, rays)
+        f._check(set_geometry(f))
+        return observe(f, count)
+
+    setters = dict(
+        host_disks=lambda tr: L.vr_set_disks(tr._h, fp(p), fp(n), 64, gd, 0.0, 3),
+        device_disks=lambda tr: L.vr_set_disks_device(tr._h, ptr(tp), ptr(tn), 64, 3, gd, 0.0, 3, None),
+        host_triangles=lambda tr: L.vr_set_triangles(tr._h, fp(v), 64, t.ctypes.data_as(C.POINTER(C.c_uint32)), 98, gd, 3),
+        device_triangles=lambda tr: L.vr_set_triangles_device(tr._h, ptr(tv), 64, ptr(tt), 98, gd, 3, None))
+    want = dict(disks=fresh(setters["host_disks"], 64), triangles=fresh(setters["host_triangles"], 98))
+    assert want["disks"]["count"] == 64 and want["triangles"]["count"] == 98
+    assert want["disks"]["flux"].any() and want["triangles"]["flux"].any()
+    tr = vr.TraceTriangle(3)
+    _configure(tr, 3, 0.1, PER, rays)
+    for step in ("host_disks", "device_disks", "host_triangles", "device_triangles", "host_disks"):
+        tr._check(setters[step](tr))
+        kind = step.split("_")[1]
+        got = observe(tr, want[kind]["count"])
+        assert got["count"] == want[kind]["count"], step
+        assert np.array_equal(_bits(got["bbox"]), _bits(want[kind]["bbox"])), step
+        assert np.array_equal(_bits(got["flux"]), _bits(want[kind]["flux"])), step
 
 
 @pytest.mark.gpu

@@ -25,8 +25,35 @@ int fail(vr_context *c, int code, const char *msg) {
   return code;
 }
 
+// ---- the hand-over of the device entry points -------------------------------
+// An entry point that takes (or, vr_get_flux_device, fills) a buffer in device memory works on the context's own stream,
+// between hand_over and one of two ends.  hand_over selects the device, refuses a buffer that is not device memory of the
+// context's device — before that nothing of the context is touched — and makes c->stream wait for what the caller's
+// stream (nullptr: the null stream) holds now.  The ends:
+//   host_waits     the host waits for c->stream: where a verdict or bounds must come back.  On return the library is done
+//                  with the caller's buffers, and an apply launched earlier has finished.
+//   caller_waits   the caller's stream waits for what c->stream holds now: where nothing comes back.  Nothing waits on the
+//                  host.  The caller may reuse its buffers in the order of its stream; to overwrite them from the host or
+//                  free them it synchronises its stream first.
+// Every kernel of an apply runs on c->stream, so what an entry point writes there is behind an apply launched earlier,
+// and what such an apply may still be reading is only ever replaced in that order.  A resident buffer that has to MOVE
+// (DevBuf::ensure frees the old one) is moved after host_waits only; at steady state, inputs that do not grow, none does.
+// Per entry point:
+//   vr_set_disks_device           host_waits, once (the box comes back).  Buffers: free on return.  The resident disk
+//                                 arrays are rewritten behind an earlier apply, which has finished on return.
+//   vr_set_triangles_device       host_waits once, for the scan's verdict and box, then caller_waits for the copy.
+//                                 Buffers: in stream order.  An earlier apply has finished before anything resident is
+//                                 touched.
+//   vr_set_material_ids_device    caller_waits.  Buffers: in stream order.  The ids are rewritten behind an earlier apply.
+//   vr_set_global_data_device     caller_waits.  Buffers: in stream order.  The row is rewritten behind an earlier apply;
+//                                 the other rows stay as they are (lay_global_rows re-lays them when they have to move).
+//   vr_set_surface_source_device  host_waits, once (the verdict comes back).  Buffers: free on return.  An earlier apply
+//                                 reads the previous tables, which are swapped out only once it has finished.
+//   vr_get_flux_device            caller_waits (vr_results.cpp; with smoothing one word comes back in between).  The
+//                                 result is ready in stream order.
+
 // `p` is device memory of `device` (hipMalloc / a torch tensor's storage; not host, pinned or managed memory)
-bool is_device_memory_of(const void *p, int device) {
+static bool is_device_memory_of(const void *p, int device) {
   hipPointerAttribute_t a{};
   if (hipPointerGetAttributes(&a, p) != hipSuccess) {
     (void)hipGetLastError(); // (an unregistered host pointer is an error of this call on some runtimes: not a sticky one)
@@ -34,29 +61,35 @@ bool is_device_memory_of(const void *p, int device) {
   }
   return a.type == hipMemoryTypeDevice && a.device == device;
 }
-
-// c->stream waits for what `stream` (the caller's; nullptr = the null stream) holds now
-int wait_for_caller(vr_context *c, hipStream_t stream) {
+// (`refusal`: the entry point's own wording; a buffer of no elements is passed as nullptr and not looked at)
+int hand_over(vr_context *c, std::initializer_list<const void *> buffers, const char *refusal, void *stream) {
+  VR_HIP(c, hipSetDevice(c->device));
+  for (const void *p : buffers)
+    if (p && !is_device_memory_of(p, c->device))
+      return fail(c, VR_E_INVALID, refusal);
   if (!c->evIn)
     VR_HIP(c, hipEventCreateWithFlags(&c->evIn, hipEventDisableTiming));
-  VR_HIP(c, hipEventRecord(c->evIn, stream));
+  VR_HIP(c, hipEventRecord(c->evIn, (hipStream_t)stream));
   VR_HIP(c, hipStreamWaitEvent(c->stream, c->evIn, 0));
   return VR_OK;
 }
-// ... and the reverse: `stream` waits for what c->stream holds now
-int caller_waits(vr_context *c, hipStream_t stream) {
+int host_waits(vr_context *c) {
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  return VR_OK;
+}
+int caller_waits(vr_context *c, void *stream) {
   if (!c->evOut)
     VR_HIP(c, hipEventCreateWithFlags(&c->evOut, hipEventDisableTiming));
   VR_HIP(c, hipEventRecord(c->evOut, c->stream));
-  VR_HIP(c, hipStreamWaitEvent(stream, c->evOut, 0));
+  VR_HIP(c, hipStreamWaitEvent((hipStream_t)stream, c->evOut, 0));
   return VR_OK;
 }
 
-// A new geometry is in c->geo (or on its way into the resident buffers): nothing derived from the previous one holds.
+// ---- the geometry commit ------------------------------------------------------
+// nothing derived from the previous geometry holds
 // (hostNeighborsValid also for triangles, whose neighbourhood host_set_triangles has just written as ensure_host_neighbors
 //  would: empty lists for every triangle, whatever the flag says.)
 static void invalidate_geometry(vr_context *c) {
-  c->geoOnDevice = c->hostGeoValid = false;
   c->hostNeighborsValid = false;
   c->areasValid = false;
   c->boundFlux = nullptr;
@@ -65,21 +98,43 @@ static void invalidate_geometry(vr_context *c) {
   c->prepared = c->haveResult = false;
 }
 
-// host_set_disks / host_set_triangles keep the material ids of a geometry with the same primitive count and reset them
-// to 0 otherwise: the same for ids that were set from the device (call before the new geometry is taken)
+// the material ids of a geometry with the same primitive count are kept, and reset to 0 otherwise: here for ids that
+// were set from the device (commit_geometry makes the host's n zeros)
 static void material_ids_follow(vr_context *c, uint32_t n) {
   if (c->materialOnDevice) {
     if (c->materialCount == n)
       return;
     c->materialOnDevice = false;
-    c->geo.materialIds.clear(); // (host_set_* / vr_set_disks_device make it n zeros)
+    c->materialIds.clear();
     c->materialStale = true;
-  } else if (c->geo.materialIds.size() != n) {
+  } else if (c->materialIds.size() != n) {
     c->materialStale = true;
   }
 }
 
-// the per-row refusals of a surface source, in the order they are checked: 0 position, 1 normal, 2 weight
+// Every geometry setter ends here, with nothing left that can fail: `d` describes what the mirror (a host setter) or the
+// resident buffers (fromDevice) hold now.  A device setter whose work failed after it had begun to write commits
+// GeometryDesc{}: "no geometry", not half of one.  The order: material_ids_follow first, it compares the new count with
+// the ids as the previous geometry left them, which the zero-fill below replaces; the rest is independent of each other.
+static void commit_geometry(vr_context *c, const GeometryDesc &d, bool fromDevice) {
+  material_ids_follow(c, d.numPrims);
+  invalidate_geometry(c);
+  if (fromDevice)
+    c->geo.clear(); // (the previous geometry's: ensure_host_geometry fills it when a host path asks)
+  static_cast<GeometryDesc &>(c->geo) = d;
+  if (!c->materialOnDevice && c->materialIds.size() != d.numPrims)
+    c->materialIds.assign(d.numPrims, 0);
+  c->geoOnDevice = fromDevice;
+  c->hostGeoValid = false;
+}
+
+// ---- messages that a host setter and its device twin share --------------------
+// (on purpose under the host setter's name: the device twin applies the host loop's checks and reports what it would)
+static const char kTriangleIndexError[] = "vr_set_triangles: vertex index out of range"; // (the device: + the triangle)
+static const char kSurfaceNullError[] =
+    "vr_set_surface_source: positions, normals and weights must not be NULL when n > 0";
+// the per-row refusals of a surface source, in the order they are checked: 0 position, 1 normal, 2 weight (shared
+// in the same way)
 static std::string surface_row_error(int kind, uint64_t row) {
   const std::string j = std::to_string(row);
   return kind == 0   ? "vr_set_surface_source: position " + j + " is not finite"
@@ -159,18 +214,11 @@ void vr_destroy(vr_context *c) {
   for (auto &um : c->userModels)
     if (um.module)
       (void)hipModuleUnload(um.module);
-  for (auto e : c->evK)
-    (void)hipEventDestroy(e);
-  for (auto e : c->evG)
-    (void)hipEventDestroy(e);
-  if (c->evIn)
-    (void)hipEventDestroy(c->evIn);
-  if (c->evOut)
-    (void)hipEventDestroy(c->evOut);
-  if (c->ev0)
-    (void)hipEventDestroy(c->ev0);
-  if (c->ev1)
-    (void)hipEventDestroy(c->ev1);
+  c->evK.insert(c->evK.end(), c->evG.begin(), c->evG.end());
+  c->evK.insert(c->evK.end(), {c->evIn, c->evOut, c->ev0, c->ev1});
+  for (hipEvent_t e : c->evK)
+    if (e)
+      (void)hipEventDestroy(e);
   if (c->stream)
     (void)hipStreamDestroy(c->stream);
   delete c; // (every DevBuf frees its memory: the device is selected and idle)
@@ -183,14 +231,12 @@ int vr_set_disks(vr_context *c, const float *points, const float *normals, uint3
                  float diskRadius, int D) {
   if (!c || !points || !normals || (D != 2 && D != 3) || n >= (1u << 27))
     return fail(c, VR_E_INVALID, "vr_set_disks: bad argument");
-  material_ids_follow(c, n);
-  host_set_disks(c->geo, points, normals, n, gridDelta, diskRadius, D);
-  invalidate_geometry(c);
+  commit_geometry(c, host_set_disks(c->geo, points, normals, n, gridDelta, diskRadius, D), false);
   return VR_OK;
 }
 
 // vr_set_disks for rows that live on the device: one kernel packs them into the builder's buffers and reduces the
-// bounding box; six floats come back.  Nothing of the previous geometry is touched before the arguments are accepted.
+// bounding box; six floats come back.
 int vr_set_disks_device(vr_context *c, const float *points, const float *normals, uint32_t n, uint32_t ld,
                         float gridDelta, float diskRadius, int D, void *stream) {
   if (!c || !points || !normals || (D != 2 && D != 3) || n >= (1u << 27))
@@ -199,50 +245,32 @@ int vr_set_disks_device(vr_context *c, const float *points, const float *normals
     return fail(c, VR_E_INVALID, "vr_set_disks_device: ld (floats per row) must be 2 or 3");
   if (ld == 2 && D != 2)
     return fail(c, VR_E_INVALID, "vr_set_disks_device: rows of 2 floats need D == 2");
-  VR_HIP(c, hipSetDevice(c->device));
-  if (n && (!is_device_memory_of(points, c->device) || !is_device_memory_of(normals, c->device)))
-    return fail(c, VR_E_INVALID, "vr_set_disks_device: points / normals are not device memory of the context's device");
-  hipStream_t caller = (hipStream_t)stream;
-  const float radius = host_disk_radius(gridDelta, diskRadius, D);
-  VR_HIP(c, c->dPoints3.ensure((size_t)n * 3));
-  VR_HIP(c, c->dNormal3.ensure((size_t)n * 3));
-  VR_HIP(c, c->dDisk4.ensure((size_t)n * 4));
-  VR_HIP(c, c->dIngestKeys.ensure(ingest_partials_entries()));
-  VR_HIP(c, c->dIngestBounds.ensure(6));
-  // from here on the resident buffers no longer hold the previous geometry
-  invalidate_geometry(c);
-  material_ids_follow(c, n);
-  HostGeometry &g = c->geo;
-  g.numPrims = 0; // (until the new one is in place: an error below leaves "no geometry", not half of one)
-  g.disk4.clear();
-  g.normal3.clear();
-  g.points3.clear();
-  int r = wait_for_caller(c, caller);
-  if (r != VR_OK)
-    return r;
-  VR_HIP(c, launch_ingest_disks(points, normals, n, ld, D, radius, c->dPoints3.p, c->dNormal3.p, c->dDisk4.p,
-                                c->dIngestKeys.p, c->dIngestBounds.p, c->stream));
-  float b[6];
-  VR_HIP(c, hipMemcpyAsync(b, c->dIngestBounds.p, sizeof(b), hipMemcpyDeviceToHost, c->stream));
-  VR_HIP(c, hipStreamSynchronize(c->stream)); // (the copy is taken: the caller may overwrite or free its rows)
-  g.D = D;
-  g.geo = 0;
-  g.numPrims = n;
-  g.gridDelta = gridDelta;
-  g.diskRadius = radius;
-  for (int k = 0; k < 3; ++k) {
-    g.minC[k] = k < D ? b[k] : 0.f;
-    g.maxC[k] = k < D ? b[3 + k] : 0.f;
-  }
-  if (!c->materialOnDevice && g.materialIds.size() != n)
-    g.materialIds.assign(n, 0);
-  g.nbOff.clear();
-  g.nbIds.clear();
-  g.verts.clear();
-  g.tris.clear();
-  g.triAreas.clear();
-  c->geoOnDevice = true;
-  return VR_OK;
+  VR_TRY(hand_over(c, {n ? points : nullptr, n ? normals : nullptr},
+                   "vr_set_disks_device: points / normals are not device memory of the context's device", stream));
+  GeometryDesc d{D, 0, n, 0, gridDelta, host_disk_radius(gridDelta, diskRadius, D)}; // (its box: below)
+  const int r = [&]() -> int { // from here on the resident buffers no longer hold the previous geometry
+    // (the kernel takes both passes in one, so the buffers are needed before the call's one synchronisation: where one
+    //  of them has to move, an apply launched earlier must have finished first)
+    if (!c->dPoints3.holds((size_t)n * 3) || !c->dNormal3.holds((size_t)n * 3) || !c->dDisk4.holds((size_t)n * 4))
+      VR_TRY(host_waits(c));
+    VR_HIP(c, c->dPoints3.ensure((size_t)n * 3));
+    VR_HIP(c, c->dNormal3.ensure((size_t)n * 3));
+    VR_HIP(c, c->dDisk4.ensure((size_t)n * 4));
+    VR_HIP(c, c->dIngestKeys.ensure(ingest_partials_entries()));
+    VR_HIP(c, c->dIngestBounds.ensure(6));
+    VR_HIP(c, launch_ingest_disks(points, normals, n, ld, D, d.diskRadius, c->dPoints3.p, c->dNormal3.p, c->dDisk4.p,
+                                  c->dIngestKeys.p, c->dIngestBounds.p, c->stream));
+    float b[6];
+    VR_HIP(c, hipMemcpyAsync(b, c->dIngestBounds.p, sizeof(b), hipMemcpyDeviceToHost, c->stream));
+    VR_TRY(host_waits(c));
+    for (int k = 0; k < D; ++k) {
+      d.minC[k] = b[k];
+      d.maxC[k] = b[3 + k];
+    }
+    return VR_OK;
+  }();
+  commit_geometry(c, r == VR_OK ? d : GeometryDesc{}, true);
+  return r;
 }
 
 int vr_set_triangles(vr_context *c, const float *verts, uint32_t nverts, const uint32_t *tris, uint32_t ntris,
@@ -251,80 +279,55 @@ int vr_set_triangles(vr_context *c, const float *verts, uint32_t nverts, const u
     return fail(c, VR_E_INVALID, "vr_set_triangles: bad argument");
   for (size_t i = 0; i < (size_t)ntris * 3; ++i)
     if (tris[i] >= nverts)
-      return fail(c, VR_E_INVALID, "vr_set_triangles: vertex index out of range");
-  material_ids_follow(c, ntris);
-  host_set_triangles(c->geo, verts, nverts, tris, ntris, gridDelta, D);
-  invalidate_geometry(c);
+      return fail(c, VR_E_INVALID, kTriangleIndexError);
+  commit_geometry(c, host_set_triangles(c->geo, verts, nverts, tris, ntris, gridDelta, D), false);
   return VR_OK;
 }
 
 // vr_set_triangles for a mesh that lives on the device, in two passes (vr_setup.hip).  The first reads the caller's
 // buffers only — box of all vertices, lowest triangle with an index out of range — and its seven words are the call's one
 // synchronisation with the host; nothing resident is touched before they say that the mesh is good.  The second copies
-// both buffers and makes the normals and areas of host_set_triangles; the caller's stream waits for it.
+// both buffers and makes the normals and areas of host_set_triangles.
 int vr_set_triangles_device(vr_context *c, const float *verts, uint32_t nverts, const uint32_t *tris, uint32_t ntris,
                             float gridDelta, int D, void *stream) {
   // (nverts < 2^31: the box reduction's keys carry the row in 31 bits)
   if (!c || (nverts && !verts) || (ntris && !tris) || (D != 2 && D != 3) || ntris >= (1u << 27) || nverts >= (1u << 31))
     return fail(c, VR_E_INVALID, "vr_set_triangles_device: bad argument");
-  VR_HIP(c, hipSetDevice(c->device));
-  if ((nverts && !is_device_memory_of(verts, c->device)) || (ntris && !is_device_memory_of(tris, c->device)))
-    return fail(c, VR_E_INVALID, "vr_set_triangles_device: verts / tris are not device memory of the context's device");
-  hipStream_t caller = (hipStream_t)stream;
+  VR_TRY(hand_over(c, {nverts ? verts : nullptr, ntris ? tris : nullptr},
+                   "vr_set_triangles_device: verts / tris are not device memory of the context's device", stream));
   VR_HIP(c, c->dIngestKeys.ensure(ingest_partials_entries()));
   VR_HIP(c, c->dIngestBounds.ensure(7));
-  VR_TRY(wait_for_caller(c, caller));
   VR_HIP(c, launch_scan_mesh(verts, nverts, tris, ntris, c->dIngestKeys.p, c->dIngestBounds.p,
                              reinterpret_cast<unsigned *>(c->dIngestBounds.p + 6), c->stream));
   float b[7];
   VR_HIP(c, hipMemcpyAsync(b, c->dIngestBounds.p, sizeof(b), hipMemcpyDeviceToHost, c->stream));
-  // (the one synchronisation; an apply launched earlier has finished too: the resident buffers may move below)
-  VR_HIP(c, hipStreamSynchronize(c->stream));
+  VR_TRY(host_waits(c));
   uint32_t bad;
   std::memcpy(&bad, &b[6], 4);
   if (bad != 0xFFFFFFFFu)
-    return fail(c, VR_E_INVALID,
-                ("vr_set_triangles: vertex index out of range (triangle " + std::to_string(bad) + ")").c_str());
-  // from here on the resident buffers no longer hold the previous geometry
-  invalidate_geometry(c);
-  material_ids_follow(c, ntris);
-  HostGeometry &g = c->geo;
-  g.numPrims = 0; // (until the new one is in place: an error below leaves "no geometry", not half of one)
-  g.verts.clear();
-  g.tris.clear();
-  g.normal3.clear();
-  g.triAreas.clear();
-  g.disk4.clear();
-  g.points3.clear();
-  g.nbOff.clear();
-  g.nbIds.clear();
-  VR_HIP(c, c->dVerts.ensure((size_t)nverts * 3));
-  VR_HIP(c, c->dTris.ensure((size_t)ntris * 3));
-  VR_HIP(c, c->dNormal3.ensure((size_t)ntris * 3));
-  VR_HIP(c, c->dTriAreas.ensure(ntris));
-  VR_HIP(c, launch_pack_mesh(verts, nverts, tris, ntris, D, c->dVerts.p, c->dTris.p, c->dNormal3.p, c->dTriAreas.p,
-                             c->stream));
-  VR_TRY(caller_waits(c, caller)); // (the copy is ordered before whatever the caller queues next on its stream)
-  g.D = D;
-  g.geo = 1;
-  g.numPrims = ntris;
-  g.gridDelta = gridDelta;
-  g.diskRadius = 0.f;
-  for (int k = 0; k < 3; ++k) { // (no vertices: the zeros of host_set_triangles)
-    g.minC[k] = nverts ? b[k] : 0.f;
-    g.maxC[k] = nverts ? b[3 + k] : 0.f;
+    return fail(c, VR_E_INVALID, (kTriangleIndexError + (" (triangle " + std::to_string(bad) + ")")).c_str());
+  GeometryDesc d{D, 1, ntris, nverts, gridDelta, 0.f};
+  for (int k = 0; k < 3 && nverts; ++k) { // (no vertices: the zeros of host_set_triangles)
+    d.minC[k] = b[k];
+    d.maxC[k] = b[3 + k];
   }
-  if (!c->materialOnDevice && g.materialIds.size() != ntris)
-    g.materialIds.assign(ntris, 0);
-  c->deviceVerts = nverts;
-  c->geoOnDevice = true;
-  return VR_OK;
+  const int r = [&]() -> int { // from here on the resident buffers no longer hold the previous geometry
+    VR_HIP(c, c->dVerts.ensure((size_t)nverts * 3));
+    VR_HIP(c, c->dTris.ensure((size_t)ntris * 3));
+    VR_HIP(c, c->dNormal3.ensure((size_t)ntris * 3));
+    VR_HIP(c, c->dTriAreas.ensure(ntris));
+    VR_HIP(c, launch_pack_mesh(verts, nverts, tris, ntris, D, c->dVerts.p, c->dTris.p, c->dNormal3.p, c->dTriAreas.p,
+                               c->stream));
+    return caller_waits(c, stream);
+  }();
+  commit_geometry(c, r == VR_OK ? d : GeometryDesc{}, true);
+  return r;
 }
 
 int vr_set_material_ids(vr_context *c, const int32_t *ids, uint32_t n) {
   if (!c || !ids)
     return fail(c, VR_E_INVALID, "vr_set_material_ids: bad argument");
-  c->geo.materialIds.assign(ids, ids + n);
+  c->materialIds.assign(ids, ids + n);
   c->materialOnDevice = false;
   c->materialStale = true;
   c->prepared = false;
@@ -332,27 +335,23 @@ int vr_set_material_ids(vr_context *c, const int32_t *ids, uint32_t n) {
   return VR_OK;
 }
 
-// vr_set_material_ids for ids that live on the device: one device-to-device copy on the context's stream, behind what
-// `stream` holds; geo.materialIds is not filled.  Only the sticking maps follow from the ids: nothing else is redone.
+// vr_set_material_ids for ids that live on the device: one device-to-device copy; materialIds is not filled.  Only the
+// sticking maps follow from the ids: nothing else is redone.
 int vr_set_material_ids_device(vr_context *c, const int32_t *ids, uint32_t n, void *stream) {
   if (!c || (n && !ids))
     return fail(c, VR_E_INVALID, "vr_set_material_ids_device: bad argument");
-  VR_HIP(c, hipSetDevice(c->device));
-  if (n && !is_device_memory_of(ids, c->device))
-    return fail(c, VR_E_INVALID, "vr_set_material_ids_device: ids are not device memory of the context's device");
   if (n == 0) { // (as vr_set_material_ids with no ids: every primitive has id 0)
-    c->geo.materialIds.clear();
+    c->materialIds.clear();
     c->materialOnDevice = false;
     c->materialStale = true;
   } else {
-    hipStream_t caller = (hipStream_t)stream;
-    if (n > c->dMaterialIds.cap || !c->dMaterialIds.p) {
-      VR_HIP(c, hipStreamSynchronize(c->stream)); // (the buffer moves: nothing may still read it)
+    VR_TRY(hand_over(c, {ids}, "vr_set_material_ids_device: ids are not device memory of the context's device", stream));
+    if (!c->dMaterialIds.holds(n)) {
+      VR_TRY(host_waits(c)); // (the buffer moves: nothing may still read it)
       VR_HIP(c, c->dMaterialIds.ensure(n));
     }
-    VR_TRY(wait_for_caller(c, caller));
     VR_HIP(c, hipMemcpyAsync(c->dMaterialIds.p, ids, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
-    VR_TRY(caller_waits(c, caller));
+    VR_TRY(caller_waits(c, stream));
     c->materialCount = n;
     c->materialOnDevice = true;
     c->materialStale = false;
@@ -470,10 +469,9 @@ int vr_set_global_data(vr_context *c, uint32_t vecIdx, const float *data, uint32
   c->prepared = false;
   return VR_OK;
 }
-// vr_set_global_data for a vector that lives on the device.  The row is written where the kernels read it, now: the
-// context's stream waits for `stream`, one kernel copies the vector into its row of dGlobalVec (zeros up to the stride),
-// and `stream` waits for that copy, so the caller may reuse its buffer at once.  Nothing synchronises with the host
-// unless the rows have to move (a longer vector than any before, more vectors than before).
+// vr_set_global_data for a vector that lives on the device.  The row is written where the kernels read it, now: one
+// kernel copies the vector into its row of dGlobalVec (zeros up to the stride).  The rows have to move for a longer
+// vector than any before, or more vectors than before.
 int vr_set_global_data_device(vr_context *c, uint32_t vecIdx, const float *data, uint32_t n, void *stream) {
   if (!c || vecIdx >= 16)
     return fail(c, VR_E_INVALID, "vr_set_global_data_device: bad argument (at most 16 vectors)");
@@ -482,16 +480,12 @@ int vr_set_global_data_device(vr_context *c, uint32_t vecIdx, const float *data,
     c->prepared = false;
     return VR_OK;
   }
-  VR_HIP(c, hipSetDevice(c->device));
-  if (!is_device_memory_of(data, c->device))
-    return fail(c, VR_E_INVALID, "vr_set_global_data_device: data is not device memory of the context's device");
-  hipStream_t caller = (hipStream_t)stream;
+  VR_TRY(hand_over(c, {data}, "vr_set_global_data_device: data is not device memory of the context's device", stream));
   c->globalRows.resize(c->globalVecs.size());
   const uint32_t rows = std::max<uint32_t>((uint32_t)c->globalVecs.size(), vecIdx + 1);
   VR_TRY(lay_global_rows(c, rows, n)); // (an error leaves the vectors as they were)
-  VR_TRY(wait_for_caller(c, caller));
   VR_HIP(c, launch_global_row(data, n, c->dGlobalVec.p + (size_t)vecIdx * c->globalStride, c->globalStride, c->stream));
-  VR_TRY(caller_waits(c, caller));
+  VR_TRY(caller_waits(c, stream));
   for (uint32_t v = (uint32_t)c->globalVecs.size(); v < rows; ++v) { // (vectors in between that were never given: empty,
     c->globalVecs.emplace_back();                                     //  and their rows are zero already)
     c->globalRows.emplace_back();
@@ -566,7 +560,7 @@ int vr_set_surface_source(vr_context *c, const float *positions3, const float *n
     return VR_OK;
   }
   if (!positions3 || !normals3 || !weights)
-    return fail(c, VR_E_INVALID, "vr_set_surface_source: positions, normals and weights must not be NULL when n > 0");
+    return fail(c, VR_E_INVALID, kSurfaceNullError);
   if (const char *msg = surface_scalar_error(sourceArea, sourceOffset))
     return fail(c, VR_E_INVALID, msg);
   for (size_t j = 0; j < n; ++j) {
@@ -592,8 +586,8 @@ int vr_set_surface_source(vr_context *c, const float *positions3, const float *n
 }
 // vr_set_surface_source for tables that live on the device (rows of ld = 2 or 3 floats; 2 only on a 2-D context, the
 // third column then reads 0).  One kernel packs the rows into staging tables and applies the host loop's three checks to
-// every row; one word comes back — the first refusal the host loop would have met, or none — and with it the message of
-// vr_set_surface_source.  Accepted, the staging tables are swapped in; refused, the previous source stays untouched.
+// every row; one word comes back: the first refusal the host loop would have met, or none.  Accepted, the staging tables
+// are swapped in; refused, the previous source stays untouched.
 int vr_set_surface_source_device(vr_context *c, const float *positions, const float *normals, const float *weights,
                                  uint32_t n, uint32_t ld, float sourceArea, float sourceOffset, void *stream) {
   if (!c)
@@ -601,29 +595,26 @@ int vr_set_surface_source_device(vr_context *c, const float *positions, const fl
   if (n == 0)
     return vr_set_surface_source(c, nullptr, nullptr, nullptr, 0, 0.f, 0.f);
   if (!positions || !normals || !weights)
-    return fail(c, VR_E_INVALID, "vr_set_surface_source: positions, normals and weights must not be NULL when n > 0");
+    return fail(c, VR_E_INVALID, kSurfaceNullError);
   if (ld != 2 && ld != 3)
     return fail(c, VR_E_INVALID, "vr_set_surface_source_device: ld (floats per row) must be 2 or 3");
   if (ld == 2 && c->geo.D != 2)
     return fail(c, VR_E_INVALID, "vr_set_surface_source_device: rows of 2 floats need a 2-D geometry (D == 2)");
   if (const char *msg = surface_scalar_error(sourceArea, sourceOffset))
     return fail(c, VR_E_INVALID, msg);
-  VR_HIP(c, hipSetDevice(c->device));
-  if (!is_device_memory_of(positions, c->device) || !is_device_memory_of(normals, c->device) ||
-      !is_device_memory_of(weights, c->device))
-    return fail(c, VR_E_INVALID, "vr_set_surface_source_device: positions / normals / weights are not device memory of "
-                                 "the context's device");
+  VR_TRY(hand_over(c, {positions, normals, weights},
+                   "vr_set_surface_source_device: positions / normals / weights are not device memory of the context's "
+                   "device",
+                   stream));
   VR_HIP(c, c->dSurfPosIn.ensure((size_t)n * 3));
   VR_HIP(c, c->dSurfNrmIn.ensure((size_t)n * 3));
   VR_HIP(c, c->dSurfWeightsIn.ensure(n));
   VR_HIP(c, c->dSurfBad.ensure(1));
-  VR_TRY(wait_for_caller(c, (hipStream_t)stream));
   VR_HIP(c, launch_surface_source(positions, normals, weights, n, ld, c->dSurfPosIn.p, c->dSurfNrmIn.p, c->dSurfWeightsIn.p,
                                   c->dSurfBad.p, c->stream));
   unsigned long long bad = 0;
   VR_HIP(c, hipMemcpyAsync(&bad, c->dSurfBad.p, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
-  // (the copy is taken, and an apply launched earlier no longer reads the previous tables: the caller may reuse its rows)
-  VR_HIP(c, hipStreamSynchronize(c->stream));
+  VR_TRY(host_waits(c));
   if (bad != ~0ull)
     return fail(c, VR_E_INVALID, surface_row_error((int)(bad & 3ull), bad >> 2).c_str());
   std::swap(c->dSurfPos, c->dSurfPosIn);

@@ -21,8 +21,9 @@ namespace vr {
 template <class T> struct DevBuf {
   T *p = nullptr;
   size_t cap = 0;
+  bool holds(size_t n) const { return p && n <= cap; } // (ensure(n) leaves the buffer where it is)
   hipError_t ensure(size_t n) {
-    if (n <= cap && p)
+    if (holds(n))
       return hipSuccess;
     if (p)
       (void)hipFree(p);
@@ -37,7 +38,7 @@ template <class T> struct DevBuf {
   // ray count creeps up from step to step re-allocates O(log) times, not every step (hipMalloc of a
   // multi-GB ray stream costs tens of ms)
   hipError_t ensure_grow(size_t n) {
-    if (n <= cap && p)
+    if (holds(n))
       return hipSuccess;
     const size_t want = std::max(n, cap + cap / 2);
     hipError_t e = ensure(want);
@@ -191,7 +192,9 @@ struct vr_context {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::string err;
 
-  HostGeometry geo;
+  HostGeometry geo;          // the scene's description, and the host mirror of its arrays (vr_host.hpp says which is which)
+  bool geoOnDevice = false;  // a device setter filled the resident buffers itself: build_scene uploads nothing
+  bool hostGeoValid = false; // ... and ensure_host_geometry has downloaded the mirror since
   bool geometryDirty = true; // BVH / uploads need rebuilding
   bool configDirty = true;   // bbox / walls / areas / sticking map need recomputing
   Bvh bvh;
@@ -210,7 +213,8 @@ struct vr_context {
   DevBuf<float> dRayState;            // a stateful model's per-ray state of one batch (the frame's VR_F_STATE_*), float4 per ray
   DevBuf<int32_t> dPrimMaterial;      // material id per original primitive for a stateful model (VR_F_MAT_*)
   // the material ids on the device, caller's order: what prepare_sticking and the stateful models read.  Set from the
-  // device (materialOnDevice: geo.materialIds is then a mirror nobody fills) or uploaded from geo.materialIds when stale.
+  // device (materialOnDevice: materialIds is then a mirror nobody fills) or uploaded from materialIds when stale.
+  std::vector<int32_t> materialIds;
   DevBuf<int32_t> dMaterialIds;
   uint32_t materialCount = 0;         // ids dMaterialIds holds (a primitive beyond them has id 0)
   bool materialOnDevice = false, materialStale = true;
@@ -307,13 +311,7 @@ struct vr_context {
   uint32_t accReplicas = 1, accStride = 0;
   // device-side setup (vr_setup.hip)
   DevBuf<float> dDisk4, dNormal3, dPoints3, dVerts, dBox, dSBox, dNodeBox;
-  // The geometry's source.  vr_set_disks_device fills dPoints3 / dNormal3 / dDisk4 itself (geoOnDevice): build_scene then
-  // uploads nothing, and geo.points3 / normal3 / disk4 are a mirror that ensure_host_geometry downloads when a host path
-  // (VR_HOST_BUILD, VR_HOST_SMOOTH, a smoothing overflow) reads them.  vr_set_triangles_device likewise fills dVerts /
-  // dTris / dNormal3 / dTriAreas; the mirror is geo.verts / tris / normal3 / triAreas.
-  bool geoOnDevice = false, hostGeoValid = false;
-  uint32_t deviceVerts = 0;               // vertices dVerts holds for a device-resident mesh
-  DevBuf<float> dTriAreas;                // its areas, written by launch_pack_mesh only (compute_areas copies them into dAreas)
+  DevBuf<float> dTriAreas;                // a device-set mesh's areas, written by launch_pack_mesh only (compute_areas copies them into dAreas)
   DevBuf<unsigned long long> dIngestKeys; // launch_ingest_disks' / launch_scan_mesh's block partials
   DevBuf<float> dIngestBounds;            // ... their six bounds, and launch_scan_mesh's word behind them
   DevBuf<double> dSortPlane;              // launch_sort_plane's block partials, then the 512 merged sums
@@ -393,9 +391,9 @@ namespace vr {
 
 // vr_api.cpp
 int fail(vr_context *c, int code, const char *msg);
-bool is_device_memory_of(const void *p, int device);
-int wait_for_caller(vr_context *c, hipStream_t stream);
-int caller_waits(vr_context *c, hipStream_t stream);
+int hand_over(vr_context *c, std::initializer_list<const void *> buffers, const char *refusal, void *stream);
+int host_waits(vr_context *c);
+int caller_waits(vr_context *c, void *stream);
 // vr_knobs.cpp
 Knobs read_knobs();
 // vr_scene.cpp

@@ -60,22 +60,18 @@ template <class F> static void parallel_ranges(uint32_t n, F fn) {
 }
 constexpr unsigned kMaxHostThreads = 16;
 
-void host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_t n, float gridDelta, float radius,
-                    int D) {
-  g.D = D;
-  g.geo = 0;
-  g.numPrims = n;
-  g.gridDelta = gridDelta;
-  g.diskRadius = host_disk_radius(gridDelta, radius, D);
+GeometryDesc host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_t n, float gridDelta, float radius,
+                            int D) {
+  GeometryDesc d{D, 0, n, 0, gridDelta, host_disk_radius(gridDelta, radius, D)};
   g.disk4.resize((size_t)n * 4);
   g.normal3.resize((size_t)n * 3);
   g.points3.resize((size_t)n * 3); // (filled by the threads below: a serial copy of 12 MB was half of this function)
   for (int k = 0; k < D; ++k) {
-    g.minC[k] = std::numeric_limits<float>::max();
-    g.maxC[k] = std::numeric_limits<float>::lowest();
+    d.minC[k] = std::numeric_limits<float>::max();
+    d.maxC[k] = std::numeric_limits<float>::lowest();
   }
   if (D == 2)
-    g.minC[2] = g.maxC[2] = 0.f;
+    d.minC[2] = d.maxC[2] = 0.f;
   float tmin[kMaxHostThreads][3], tmax[kMaxHostThreads][3];
   for (unsigned t = 0; t < kMaxHostThreads; ++t)
     for (int k = 0; k < 3; ++k) {
@@ -86,11 +82,11 @@ void host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_
     float lmin[3] = {tmin[t][0], tmin[t][1], tmin[t][2]}, lmax[3] = {tmax[t][0], tmax[t][1], tmax[t][2]};
     for (uint32_t i = b; i < e; ++i) {
       const float *p = pts + 3 * (size_t)i;
-      float *d = &g.disk4[4 * (size_t)i];
-      d[0] = p[0];
-      d[1] = p[1];
-      d[2] = D == 2 ? 0.f : p[2];
-      d[3] = g.diskRadius;
+      float *q = &g.disk4[4 * (size_t)i];
+      q[0] = p[0];
+      q[1] = p[1];
+      q[2] = D == 2 ? 0.f : p[2];
+      q[3] = d.diskRadius;
       g.points3[3 * (size_t)i] = p[0];
       g.points3[3 * (size_t)i + 1] = p[1];
       g.points3[3 * (size_t)i + 2] = D == 2 ? 0.f : p[2]; // (2-D: the z column is ignored, rayGeometryDisk.hpp:148-151)
@@ -109,11 +105,9 @@ void host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_
   });
   for (unsigned t = 0; t < kMaxHostThreads; ++t)
     for (int k = 0; k < D; ++k) { // (min/max: any order gives the same result)
-      g.minC[k] = std::min(g.minC[k], tmin[t][k]);
-      g.maxC[k] = std::max(g.maxC[k], tmax[t][k]);
+      d.minC[k] = std::min(d.minC[k], tmin[t][k]);
+      d.maxC[k] = std::max(d.maxC[k], tmax[t][k]);
     }
-  if (g.materialIds.size() != n)
-    g.materialIds.assign(n, 0);
   // the neighbourhood (rayGeometryDisk.hpp:191-192, radius = 2 * disk radius) is built
   // on the device with the BVH (vr_setup.hip); the host version is a validation path
   g.nbOff.clear();
@@ -121,26 +115,23 @@ void host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_
   g.verts.clear();
   g.tris.clear();
   g.triAreas.clear();
+  return d;
 }
 
-void host_set_triangles(HostGeometry &g, const float *verts, uint32_t nv, const uint32_t *tris, uint32_t nt,
-                        float gridDelta, int D) {
-  g.D = D;
-  g.geo = 1;
-  g.numPrims = nt;
-  g.gridDelta = gridDelta;
-  g.diskRadius = 0.f;
+GeometryDesc host_set_triangles(HostGeometry &g, const float *verts, uint32_t nv, const uint32_t *tris, uint32_t nt,
+                                float gridDelta, int D) {
+  GeometryDesc d{D, 1, nt, nv, gridDelta, 0.f};
   g.verts.assign(verts, verts + (size_t)nv * 3);
   g.tris.assign(tris, tris + (size_t)nt * 3);
   // rayMesh.hpp:12-25: bounding box over all nodes
   for (int k = 0; k < 3; ++k) {
-    g.minC[k] = nv ? verts[k] : 0.f;
-    g.maxC[k] = nv ? verts[k] : 0.f;
+    d.minC[k] = nv ? verts[k] : 0.f;
+    d.maxC[k] = nv ? verts[k] : 0.f;
   }
   for (uint32_t i = 0; i < nv; ++i)
     for (int k = 0; k < 3; ++k) {
-      g.minC[k] = std::min(g.minC[k], verts[3 * (size_t)i + k]);
-      g.maxC[k] = std::max(g.maxC[k], verts[3 * (size_t)i + k]);
+      d.minC[k] = std::min(d.minC[k], verts[3 * (size_t)i + k]);
+      d.maxC[k] = std::max(d.maxC[k], verts[3 * (size_t)i + k]);
     }
   g.normal3.resize((size_t)nt * 3);
   g.triAreas.resize(nt);
@@ -160,12 +151,11 @@ void host_set_triangles(HostGeometry &g, const float *verts, uint32_t nv, const 
     g.normal3[3 * (size_t)i + 1] = nn.y;
     g.normal3[3 * (size_t)i + 2] = nn.z;
   }
-  if (g.materialIds.size() != nt)
-    g.materialIds.assign(nt, 0);
   g.disk4.clear();
   g.points3.clear();
   g.nbOff.assign((size_t)nt + 1, 0u);
   g.nbIds.clear();
+  return d;
 }
 
 // ---------------------------------------------------------------------------

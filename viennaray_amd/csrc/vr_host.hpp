@@ -3,6 +3,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -11,24 +12,35 @@
 
 namespace vr {
 
-struct HostGeometry {
+// What the scene is: valid from the moment a geometry is set, whichever side it came from (commit_geometry, vr_api.cpp,
+// is its only writer; the setters make one as {D, geo, numPrims, numVerts, gridDelta, diskRadius} and fill in the box).
+struct GeometryDesc {
   int D = 3;
   int geo = 0; // 0 disk, 1 triangle
   uint32_t numPrims = 0;
+  uint32_t numVerts = 0; // triangles: the mesh's vertices
   float gridDelta = 0.f, diskRadius = 0.f;
-  // disks: Embree-style buffers (rayGeometryDisk.hpp:363-375)
-  std::vector<float> disk4;   // n x {x,y,z,r}
-  std::vector<float> normal3; // n x 3 (disk normals / triangle unit normals)
-  std::vector<float> points3; // caller's points (neighbourhood input)
-  // (a device-resident geometry, vr_set_disks_device, leaves these three empty until a host path asks for them)
-  // triangles
-  std::vector<float> verts;   // nv x 3
-  std::vector<uint32_t> tris; // n x 3
-  std::vector<float> triAreas;
   float minC[3] = {0, 0, 0}, maxC[3] = {0, 0, 0};
-  std::vector<int32_t> materialIds;
-  // neighbourhood CSR in ORIGINAL ids, lists ascending
-  std::vector<uint32_t> nbOff, nbIds;
+};
+
+// ... and the host's mirror of the arrays behind it.  Which array mirrors which device buffer, and who fills it:
+//   disks      points3 = dPoints3 (the caller's points, the neighbourhood's input), normal3 = dNormal3, disk4 = dDisk4
+//              (n x {x, y, z, r}, rayGeometryDisk.hpp:363-375)
+//   triangles  verts = dVerts (numVerts x 3), tris = dTris (n x 3), normal3 = dNormal3 (unit normals), triAreas = dTriAreas
+//   both       nbOff / nbIds: the neighbourhood CSR in ORIGINAL ids, lists ascending (dNbOff / dNbIds hold it in leaf order)
+// A host setter (host_set_disks / host_set_triangles) fills its kind's arrays and empties the others; build_scene uploads
+// them.  A device setter fills the device buffers itself (vr_context::geoOnDevice) and leaves the mirror empty until a
+// host path (VR_HOST_BUILD, VR_HOST_SMOOTH, a smoothing overflow) asks for it: ensure_host_geometry then downloads the
+// kind's arrays (vr_context::hostGeoValid).  nbOff / nbIds are ensure_host_neighbors' on either side.
+struct HostGeometry : GeometryDesc {
+  std::vector<float> disk4, normal3, points3, verts, triAreas;
+  std::vector<uint32_t> tris, nbOff, nbIds;
+  void clear() {
+    for (std::vector<float> *v : {&disk4, &normal3, &points3, &verts, &triAreas})
+      v->clear();
+    for (std::vector<uint32_t> *v : {&tris, &nbOff, &nbIds})
+      v->clear();
+  }
 };
 
 struct Bvh {
@@ -43,10 +55,11 @@ inline float host_disk_radius(float gridDelta, float radius, int D) {
   return radius > 0.f ? radius : (float)(gridDelta * factor);
 }
 // geometry ingestion (restates rayGeometryDisk.hpp:101-193, rayGeometryTriangle.hpp:14-88 + rayMesh.hpp:99-112)
-void host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_t n, float gridDelta, float radius,
-                    int D);
-void host_set_triangles(HostGeometry &g, const float *verts, uint32_t nv, const uint32_t *tris, uint32_t nt,
-                        float gridDelta, int D);
+// (they fill g's arrays and return the description: g's own stays the previous geometry's until it is committed)
+GeometryDesc host_set_disks(HostGeometry &g, const float *pts, const float *nrm, uint32_t n, float gridDelta, float radius,
+                            int D);
+GeometryDesc host_set_triangles(HostGeometry &g, const float *verts, uint32_t nv, const uint32_t *tris, uint32_t nt,
+                                float gridDelta, int D);
 // Sort plane of the ray stream: rays are binned by where they cross one plane normal to
 // the tracing axis, and a wavefront's rays are coherent where they HIT if that plane is
 // where most first hits happen.  Estimated from the geometry alone: histogram of the

@@ -731,7 +731,7 @@ static int fill_trace_params(vr_context *c, const ParticleSpec &sp, ParticleLaun
   // into the launch frame (VR_F_STATE_*, VR_F_MAT_*).  (Both are sized by what every particle of an apply shares — rays
   // per batch, primitives — so a later particle's prepare does not move them.)
   S.dMaterial = nullptr;
-  if (S.stateful && (c->materialOnDevice || !c->geo.materialIds.empty())) { // (a device copy, zeros behind the ids given)
+  if (S.stateful && (c->materialOnDevice || !c->materialIds.empty())) { // (a device copy, zeros behind the ids given)
     VR_TRY(ensure_device_material_ids(c));
     const uint32_t given = std::min(N, c->materialCount);
     VR_HIP(c, c->dPrimMaterial.ensure(N));

@@ -303,25 +303,18 @@ int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, 
     return fail(c, VR_E_INVALID, "vr_get_flux_device: size mismatch");
   if (dataIdx >= c->totalData)
     return fail(c, VR_E_INVALID, "vr_get_flux_device: the particle has no such data label");
-  VR_HIP(c, hipSetDevice(c->device));
-  if (n && !is_device_memory_of(out, c->device))
-    return fail(c, VR_E_INVALID, "vr_get_flux_device: out is not device memory of the context's device");
-  hipStream_t caller = (hipStream_t)stream;
+  // (the hand-over of the device setters, vr_api.cpp, the other way round: out may still be in use by work the caller
+  //  queued before this call)
+  VR_TRY(hand_over(c, {n ? out : nullptr}, "vr_get_flux_device: out is not device memory of the context's device", stream));
   const bool smooth = c->geo.geo == 0 && numNeighbors >= 1;
-  int r = wait_for_caller(c, caller); // (out may still be in use by work the caller queued before this call)
-  if (r != VR_OK)
-    return r;
   float *work = out;
   if (smooth) { // (the smoothing kernels read one buffer and write another)
     VR_HIP(c, c->dFluxTmp.ensure(n));
     work = c->dFluxTmp.p;
   }
   VR_HIP(c, launch_flux_from_acc(c->fluxOut() + (size_t)dataIdx * n, n, work, c->stream));
-  if (normType == VR_NORM_SOURCE || normType == VR_NORM_MAX) {
-    r = normalize_on_device(c, work, n, normType);
-    if (r != VR_OK)
-      return r;
-  }
+  if (normType == VR_NORM_SOURCE || normType == VR_NORM_MAX)
+    VR_TRY(normalize_on_device(c, work, n, normType));
   if (smooth) {
     bool done = false;
     if (c->haveSetup && !c->geometryDirty && !read_knobs().hostSmooth) {
@@ -343,13 +336,11 @@ int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, 
       std::vector<float> h(n);
       VR_HIP(c, hipMemcpyAsync(h.data(), work, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
       VR_HIP(c, hipStreamSynchronize(c->stream));
-      r = vr_smooth_flux(c, h.data(), n, numNeighbors);
-      if (r != VR_OK)
-        return r;
+      VR_TRY(vr_smooth_flux(c, h.data(), n, numNeighbors));
       VR_HIP(c, hipMemcpy(out, h.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     }
   }
-  return caller_waits(c, caller);
+  return caller_waits(c, stream);
 }
 
 int vr_get_disk_areas(vr_context *c, float *out, uint32_t n) {

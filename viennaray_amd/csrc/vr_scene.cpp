@@ -8,41 +8,27 @@
 namespace vr {
 
 // ---- scene build (device LBVH + neighbourhood; VR_HOST_BUILD=1 selects the host builder) -------
-// geo.points3 / normal3 / disk4 (disks) or geo.verts / tris / normal3 / triAreas (triangles) of a device-resident
-// geometry, downloaded when a host path first reads them
+// the mirror of a device-set geometry (HostGeometry, vr_host.hpp), downloaded when a host path first reads it
 int ensure_host_geometry(vr_context *c) {
   if (!c->geoOnDevice || c->hostGeoValid)
     return VR_OK;
   HostGeometry &g = c->geo;
   const size_t N = g.numPrims;
-  if (g.geo == 1) {
-    const size_t NV = c->deviceVerts;
-    g.verts.resize(NV * 3);
-    g.tris.resize(N * 3);
-    g.normal3.resize(N * 3);
-    g.triAreas.resize(N);
-    VR_HIP(c, hipSetDevice(c->device));
-    VR_HIP(c, hipStreamSynchronize(c->stream));
-    if (NV)
-      VR_HIP(c, hipMemcpy(g.verts.data(), c->dVerts.p, NV * 12, hipMemcpyDeviceToHost));
-    if (N) {
-      VR_HIP(c, hipMemcpy(g.tris.data(), c->dTris.p, N * 12, hipMemcpyDeviceToHost));
-      VR_HIP(c, hipMemcpy(g.normal3.data(), c->dNormal3.p, N * 12, hipMemcpyDeviceToHost));
-      VR_HIP(c, hipMemcpy(g.triAreas.data(), c->dTriAreas.p, N * 4, hipMemcpyDeviceToHost));
-    }
-    c->hostGeoValid = true;
-    return VR_OK;
-  }
-  g.points3.resize(N * 3);
-  g.normal3.resize(N * 3);
-  g.disk4.resize(N * 4);
   VR_HIP(c, hipSetDevice(c->device));
   VR_HIP(c, hipStreamSynchronize(c->stream));
-  if (N) {
-    VR_HIP(c, hipMemcpy(g.points3.data(), c->dPoints3.p, N * 12, hipMemcpyDeviceToHost));
-    VR_HIP(c, hipMemcpy(g.normal3.data(), c->dNormal3.p, N * 12, hipMemcpyDeviceToHost));
-    VR_HIP(c, hipMemcpy(g.disk4.data(), c->dDisk4.p, N * 16, hipMemcpyDeviceToHost));
+  auto download = [](auto &to, const auto &from, size_t n) { // (no elements: nothing to copy)
+    to.resize(n);
+    return n ? from.download(to.data(), n) : hipSuccess;
+  };
+  if (g.geo == 1) {
+    VR_HIP(c, download(g.verts, c->dVerts, (size_t)g.numVerts * 3));
+    VR_HIP(c, download(g.tris, c->dTris, N * 3));
+    VR_HIP(c, download(g.triAreas, c->dTriAreas, N));
+  } else {
+    VR_HIP(c, download(g.points3, c->dPoints3, N * 3));
+    VR_HIP(c, download(g.disk4, c->dDisk4, N * 4));
   }
+  VR_HIP(c, download(g.normal3, c->dNormal3, N * 3));
   c->hostGeoValid = true;
   return VR_OK;
 }
@@ -62,7 +48,7 @@ int ensure_host_order(vr_context *c) {
 int ensure_device_material_ids(vr_context *c) {
   if (c->materialOnDevice || !c->materialStale)
     return VR_OK;
-  const std::vector<int32_t> &ids = c->geo.materialIds;
+  const std::vector<int32_t> &ids = c->materialIds;
   VR_HIP(c, hipStreamSynchronize(c->stream)); // (a kernel queued earlier may still read the previous ids)
   VR_HIP(c, c->dMaterialIds.ensure(ids.size()));
   if (!ids.empty())

@@ -253,16 +253,17 @@ def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def _is_device_tensor(x):
-    """a torch tensor in device memory, by duck typing (this module does not import torch)"""
-    return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+def _on_any_device(x):
+    """a tensor that is not host memory, whatever device it lives on, by duck typing (this module does not import torch):
+    what sends a setter down its device path"""
+    return hasattr(x, "data_ptr") and getattr(getattr(x, "device", None), "type", "cpu") != "cpu"
 
 
 def _check_device_tensor(what, name, x, device, dtype, shapes):
     """a tensor handed over where it is must be on the tracer's device, of the one dtype, contiguous and of one of the
     shapes (None: any size): anything else raises ValueError — nothing is copied through the host behind the caller's
     back"""
-    if not _is_device_tensor(x):
+    if not (hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))):
         raise ValueError(f"{what}: device: {name} is not a device tensor while another argument is "
                          "(all on the device, or all on the host)")
     if x.device.index != device:
@@ -274,11 +275,6 @@ def _check_device_tensor(what, name, x, device, dtype, shapes):
         raise ValueError(f"{what}: shape: {name} is {shape}")
     if not x.is_contiguous():
         raise ValueError(f"{what}: contiguity: {name} is not contiguous (strides {tuple(x.stride())})")
-
-
-def _on_any_device(x):
-    """a tensor that is not host memory, whatever device it lives on"""
-    return hasattr(x, "data_ptr") and getattr(getattr(x, "device", None), "type", "cpu") != "cpu"
 
 
 class Trace:
@@ -788,7 +784,7 @@ class TraceDisk(Trace):
         handed over where they are (vr_set_disks_device): the library copies them on the device, ordered behind the
         current torch stream, and the tensors may be overwritten as soon as this returns.  A tensor on a device that
         cannot go that way raises ValueError — it is never copied through the host behind the caller's back."""
-        if _is_device_tensor(points) or _is_device_tensor(normals):
+        if _on_any_device(points) or _on_any_device(normals):
             return self._setGeometryDevice(points, normals, gridDelta, diskRadius)
         p = np.ascontiguousarray(points, dtype=np.float32)
         n = np.ascontiguousarray(normals, dtype=np.float32)
@@ -803,27 +799,16 @@ class TraceDisk(Trace):
                                          float(diskRadius), self.D))
 
     def _setGeometryDevice(self, points, normals, gridDelta, diskRadius):
-        for name, x in (("points", points), ("normals", normals)):
-            if not _is_device_tensor(x):
-                raise ValueError(f"setGeometry: device: {name} is not a device tensor while the other argument is "
-                                 "(both on the device, or both on the host)")
-            if x.device.index != self._device:
-                raise ValueError(f"setGeometry: device: {name} is on {x.device}, the tracer on device {self._device}")
-            if str(x.dtype) != "torch.float32":
-                raise ValueError(f"setGeometry: dtype: {name} is {x.dtype}, device tensors must be torch.float32")
-            if x.dim() != 2 or x.shape[1] not in (2, 3):
-                raise ValueError(f"setGeometry: shape: {name} is {tuple(x.shape)}, expected [n, 2] or [n, 3]")
-            if x.shape[1] == 2 and self.D != 2:
-                raise ValueError(f"setGeometry: shape: {name} has 2 columns, a {self.D}-D tracer needs [n, 3]")
-            if not x.is_contiguous():
-                raise ValueError(f"setGeometry: contiguity: {name} is not contiguous (strides {tuple(x.stride())})")
+        # (two columns need D == 2: refused as a shape, where the shape is looked at)
+        cols = [(None, 2), (None, 3)] if self.D == 2 else [(None, 3)]
+        _check_device_tensor("setGeometry", "points", points, self._device, "torch.float32", cols)
+        _check_device_tensor("setGeometry", "normals", normals, self._device, "torch.float32", cols)
         if tuple(points.shape) != tuple(normals.shape):
             raise ValueError(f"setGeometry: shape: points {tuple(points.shape)} and normals {tuple(normals.shape)} differ")
-        import torch
-        stream = torch.cuda.current_stream(points.device).cuda_stream
         n, ld = int(points.shape[0]), int(points.shape[1])
         self._check(self._L.vr_set_disks_device(self._h, C.c_void_p(points.data_ptr()), C.c_void_p(normals.data_ptr()),
-                                                n, ld, float(gridDelta), float(diskRadius), self.D, C.c_void_p(stream)))
+                                                n, ld, float(gridDelta), float(diskRadius), self.D,
+                                                C.c_void_p(self._torch_stream())))
         self._n = n
 
     def getDiskAreas(self):
