@@ -215,6 +215,40 @@ int vr_set_host_ray_weights(vr_context *ctx, const float *weights, uint64_t n);
 /* Source::getSourceArea() (raySource.hpp:17) for normalizeFlux(SOURCE) (rayTraceDisk.hpp:127,
  * rayTraceTriangle.hpp:113); area <= 0: SourceRandom's (raySourceRandom.hpp:40-47, the bbox source face)       */
 int vr_set_source_area(vr_context *ctx, float area);
+/* A user Source (raySource.hpp:10-19: getOriginAndDirection(idx, rng), getInitialRayWeight(idx)) as DEVICE code, sampled in
+ * the ray generator instead of on the host.  `source` is HIP text that defines
+ *     struct VrUserSource {
+ *       static constexpr bool kHasWeight = false;  // true: `weight` is the ray's start weight (getInitialRayWeight)
+ *       template <int D, class Draw>
+ *       __device__ static void sample(const SourceCtx &s, unsigned long long idx, Draw &&draw, V3 &org, V3 &dir, float &weight);
+ *     };
+ * draw() returns the next raw 64-bit output of ray idx's engine — any number of calls, different from ray to ray;
+ * canon_f32(draw()) / canon_f64(draw()) are the reference's uniform float / double.  `dir` is used as returned: the model
+ * normalises it (vnormalize), as the reference's callback does.  SourceCtx (viennaray_amd/csrc/vr_types.hpp): the adjusted
+ * bounding box, the source plane, rayDir / firstDir / secondDir / posNeg, gridDelta, the particle's source power,
+ * params[16] and one float table in device memory (table, tableCount).  The library compiles the ray generator around the
+ * text for gfx950 (hipcc --genco, cached by content like a particle model's; no trace kernel is compiled) and loads it;
+ * *sourceId is then valid for vr_set_source_model on this context.  flags: VR_SOURCE_HAS_WEIGHT exactly when kHasWeight is
+ * true.  A text that does not compile returns VR_E_INVALID with the compiler's error lines in vr_last_error; the context
+ * stays usable.  Needs hipcc at run time.                                                                            */
+enum { VR_SOURCE_HAS_WEIGHT = 1 };
+int vr_register_source_model(vr_context *ctx, const char *name, const char *source, int flags, int32_t *sourceId);
+/* The source of the next applies is model `sourceId` (< 0: back to SourceRandom) with params[0 .. nparams) (nparams <= 16,
+ * zeros behind them) and a table of ntable floats, copied to the device here (NULL / 0: none).  numRays == 0: the ray
+ * count is SourceRandom's (numRaysFixed, or numRaysPerPoint per primitive); > 0: the source's own (<= 2^32 - 1, as for
+ * host rays).  It replaces and is replaced by a source grid, host rays and a surface source; vr_set_source_area keeps
+ * supplying getSourceArea().  Without kHasWeight every ray starts with weight 1 and an absorbing particle keeps its
+ * absorbing kernel, as under weightless host rays.  vr_set_ray_range and vr_apply_sharded work unchanged: the sample
+ * depends on the global ray index only.  A stateful particle model cannot be combined with it (refused at prepare).
+ * A refused call leaves the source in force as it was.                                                              */
+int vr_set_source_model(vr_context *ctx, int32_t sourceId, const float *params, uint32_t nparams, const float *table,
+                        uint32_t ntable, uint64_t numRays);
+/* ... its table from DEVICE memory of the context's device (ntable == 0: no table): copied on the context's stream behind
+ * what `stream` (NULL: the null stream) holds now, and `stream` then waits for the copy — the contract of
+ * vr_set_global_data_device: the caller may reuse dTable in the order of its stream; nothing waits on the host unless the
+ * library's buffer has to grow.  Refused (no source model in force, not device memory of this device): the previous
+ * table stays.                                                                                                      */
+int vr_set_source_model_table_device(vr_context *ctx, const float *dTable, uint32_t ntable, void *stream);
 /* setSurfaceSource / clearSurfaceSource (gpu/raygTrace.hpp:267-297; sample: gpu/raygSource.hpp:13-26, 65-81, 105-118):
  * the rays start ON the n given points — numRaysFixed if set, else numRaysPerPoint, rays per point (:134-149), global ray
  * idx at point idx / raysPerPoint — from positions3[3 j] + unit normal * sourceOffset, along a power-1 cosine
@@ -388,6 +422,10 @@ int vr_debug_model_source_sample(vr_context *ctx, const uint64_t *idx, uint32_t 
  * runs: origin, direction, start weight and the engine outputs consumed (2) of global ray indices idx[]    */
 int vr_debug_surface_source_sample(vr_context *ctx, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
                                    float *weight, uint32_t *draws);
+/* ... of the source model in force (vr_set_source_model), by the device function its generator runs: origin, direction,
+ * start weight (1 without kHasWeight) and the engine outputs consumed of global ray indices idx[], kernel seed `seed`  */
+int vr_debug_user_source_sample(vr_context *ctx, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
+                                float *weight, uint32_t *draws);
 /* first `count` raw mt19937_64 outputs of the per-ray engine of ray idx      */
 int vr_debug_rng_outputs(vr_context *ctx, uint64_t idx, uint32_t seed,
                          uint32_t count, uint64_t *out);

@@ -1141,6 +1141,33 @@ public:
     if (ctx_)
       check(vr_set_surface_source(ctx_, nullptr, nullptr, nullptr, 0, 0.f, 0.f));
   }
+  /// NOT in the reference's CPU Trace: a user Source as DEVICE code (vr_register_source_model: HIP text of `struct
+  /// VrUserSource`, see include/viennaray_amd.h), compiled into the ray generator.  Returns the id setSourceModel takes,
+  /// -1 (and sets TraceInfo.error) if the text does not compile.  hasWeight = the text's kHasWeight.
+  int registerSourceModel(const std::string &name, const std::string &source, bool hasWeight = false) {
+    int32_t id = -1;
+    if (ctx_ && vr_register_source_model(ctx_, name.c_str(), source.c_str(), hasWeight ? VR_SOURCE_HAS_WEIGHT : 0, &id) != VR_OK) {
+      RTInfo_.error = true; // (nothing was set: the source in force stays, and later applies run)
+      std::cerr << "viennaray_amd: " << vr_last_error(ctx_) << "\n";
+      id = -1;
+    }
+    return id;
+  }
+  /// The rays of the next applies are sampled on the device by source model `id` (registerSourceModel; < 0: back to
+  /// SourceRandom) with up to 16 params and one table; numRays == 0 keeps the ray count of setNumberOfRaysPerPoint /
+  /// setNumberOfRaysFixed, > 0 is the source's own.  Takes the place of any other source — setSource(std::shared_ptr<Source>)
+  /// stays the host path — and a refusal leaves the previous one in place.
+  void setSourceModel(int id, const std::vector<float> &params = {}, const std::vector<float> &table = {}, size_t numRays = 0) {
+    if (!ctx_)
+      return;
+    const int rc = vr_set_source_model(ctx_, id, params.data(), (uint32_t)std::min<size_t>(params.size(), 0xFFFFFFFFull),
+                                       table.data(), (uint32_t)std::min<size_t>(table.size(), 0xFFFFFFFFull), numRays);
+    check(rc);
+    if (rc == VR_OK && id >= 0) {
+      pSource_.reset();
+      sourceOnDevice_ = false;
+    }
+  }
   /// setSurfaceSource for tables that live on the device (vr_set_surface_source_device): dPositions / dNormals are
   /// DEVICE pointers to n rows of `ld` floats (2 or 3; 2 only for D == 2), dWeights to n floats, produced on `stream`
   /// (the caller's hipStream_t, nullptr = the null stream).  Packed and validated on the device; a refusal names the row

@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("VR_LIB_PATH") or os.path.join(_HERE, "libviennaray_am
 
 VR_OK, VR_E_INVALID, VR_E_HIP, VR_E_STATE = 0, -1, -2, -3
 VR_NORM_NONE = -1  # vr_get_flux_device: the raw flux
+VR_SOURCE_HAS_WEIGHT = 1  # vr_register_source_model: the model's kHasWeight is true
+VR_SOURCE_PARAMS = 16  # vr_set_source_model: parameters a source model reads
 
 
 class VrError(RuntimeError):
@@ -74,6 +76,9 @@ SIGNATURES = {
     "vr_set_host_rays": (C.c_int, [_vp, _fp, _fp, _u32p, C.c_uint64]),
     "vr_set_host_ray_weights": (C.c_int, [_vp, _fp, C.c_uint64]),
     "vr_set_source_area": (C.c_int, [_vp, C.c_float]),
+    "vr_register_source_model": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_int, _i32p]),
+    "vr_set_source_model": (C.c_int, [_vp, C.c_int32, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint64]),
+    "vr_set_source_model_table_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "vr_set_surface_source": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, C.c_float, C.c_float]),
     "vr_set_surface_source_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, _vp]),
     "vr_reserve_rays": (C.c_int, [_vp, C.c_uint64]),
@@ -123,6 +128,7 @@ SIGNATURES = {
     "vr_debug_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp]),
     "vr_debug_model_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp, _u32p]),
     "vr_debug_surface_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp, _fp, _u32p]),
+    "vr_debug_user_source_sample": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _fp, _fp, _fp, _u32p]),
     "vr_debug_rng_outputs": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
     "vr_debug_issue_rate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_double)]),
     "vr_debug_triangle_mesh": (C.c_int, [_vp, _fp, _fp, C.c_uint32]),

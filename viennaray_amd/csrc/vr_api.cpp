@@ -2,7 +2,7 @@
 // (vr_trace.hip, vr_setup.hip).  This file: create / destroy and the setters.  The rest of the ABI, by stage:
 //   vr_context.hpp  struct vr_context and what the files below share
 //   vr_knobs.cpp    read_knobs: the tuning switches of the environment
-//   vr_models.cpp   run-time particle models (vr_register_particle_model)
+//   vr_models.cpp   run-time particle and source models (vr_register_particle_model, vr_register_source_model)
 //   vr_scene.cpp    host mirrors of the resident geometry, build_scene
 //   vr_prepare.cpp  vr_apply_prepare and its stages
 //   vr_apply.cpp    vr_apply_launch / _finish, vr_apply, vr_apply_sharded
@@ -159,6 +159,7 @@ static void surface_source_accepted(vr_context *c, uint32_t n, float sourceArea,
   c->hostDir.clear();
   c->hostDraws.clear();
   c->hostWeights.clear();
+  c->sourceModel = -1;
   c->prepared = false;
 }
 
@@ -211,6 +212,9 @@ void vr_destroy(vr_context *c) {
   (void)hipSetDevice(c->device);
   if (c->stream)
     (void)hipStreamSynchronize(c->stream);
+  for (auto &sm : c->sourceModels)
+    if (sm.module)
+      (void)hipModuleUnload(sm.module);
   for (auto &um : c->userModels)
     if (um.module)
       (void)hipModuleUnload(um.module);
@@ -522,6 +526,7 @@ int vr_set_source_grid(vr_context *c, const float *points3, uint32_t n) {
   c->hostDraws.clear();
   c->hostWeights.clear();
   c->surfCount = 0;
+  c->sourceModel = -1;
   c->sourceDirty = true;
   c->prepared = false;
   return VR_OK;
@@ -540,7 +545,77 @@ int vr_set_host_rays(vr_context *c, const float *org3, const float *dir3, const 
   c->hostWeights.clear();
   c->gridPoints.clear();
   c->surfCount = 0;
+  c->sourceModel = -1;
   c->sourceDirty = true;
+  c->prepared = false;
+  return VR_OK;
+}
+// Source model (vr_register_source_model): the next applies sample their rays on the device with model `sourceId`
+// (< 0: back to SourceRandom), which reads params[0 .. nparams) (at most 16; zeros behind them) and the table — ntable
+// floats, copied to the device here (NULL or 0: none).  numRays == 0: the ray count is SourceRandom's (numRaysFixed, or
+// numRaysPerPoint per primitive); > 0: the source's own (at most 2^32 - 1, as for host rays).  It takes the place of a
+// source grid, host rays and a surface source, and each of those takes its place; vr_set_source_area keeps supplying
+// getSourceArea().  A refused call leaves the source in force as it was.
+int vr_set_source_model(vr_context *c, int32_t sourceId, const float *params, uint32_t nparams, const float *table,
+                        uint32_t ntable, uint64_t numRays) {
+  if (!c)
+    return VR_E_INVALID;
+  if (sourceId < 0) {
+    if (c->sourceModel >= 0) {
+      c->sourceModel = -1;
+      c->prepared = false;
+    }
+    return VR_OK;
+  }
+  if ((size_t)sourceId >= c->sourceModels.size())
+    return fail(c, VR_E_INVALID, "vr_set_source_model: unknown source model id (vr_register_source_model returns it)");
+  if (nparams > (uint32_t)VR_SOURCE_PARAMS || (nparams && !params))
+    return fail(c, VR_E_INVALID, "vr_set_source_model: at most 16 parameters (and params must not be NULL when nparams > 0)");
+  if (numRays > 0xFFFFFFFFull)
+    return fail(c, VR_E_INVALID, "vr_set_source_model: at most 2^32 - 1 rays");
+  if (table && ntable) {
+    VR_HIP(c, hipSetDevice(c->device));
+    VR_HIP(c, hipStreamSynchronize(c->stream)); // (a launched apply may still read the previous table)
+    VR_HIP(c, c->dSrcTable.upload(table, ntable));
+    c->srcTableCount = ntable;
+  } else {
+    c->srcTableCount = 0;
+  }
+  std::fill(std::copy(params, params + nparams, c->srcParams), c->srcParams + VR_SOURCE_PARAMS, 0.f);
+  c->srcNumRays = numRays;
+  c->sourceModel = sourceId;
+  c->gridPoints.clear();
+  c->hostOrg.clear();
+  c->hostDir.clear();
+  c->hostDraws.clear();
+  c->hostWeights.clear();
+  c->surfCount = 0;
+  c->prepared = false;
+  return VR_OK;
+}
+// The table of the source model in force, from device memory: copied into the library's own buffer on the context's
+// stream behind what `stream` holds now, and `stream` then waits for the copy (the ordering contract of
+// vr_set_global_data_device: the caller may reuse its buffer in the order of its stream).  The copy runs behind an apply
+// launched earlier.  ntable == 0 drops the table.  Refused — no source model in force, dTable not device memory of the
+// context's device — the previous table stays.
+int vr_set_source_model_table_device(vr_context *c, const float *dTable, uint32_t ntable, void *stream) {
+  if (!c)
+    return VR_E_INVALID;
+  if (c->sourceModel < 0)
+    return fail(c, VR_E_STATE, "vr_set_source_model_table_device: no source model is set (vr_set_source_model first)");
+  if (!dTable || ntable == 0) {
+    c->srcTableCount = 0;
+    c->prepared = false;
+    return VR_OK;
+  }
+  VR_TRY(hand_over(c, {dTable}, "vr_set_source_model_table_device: the table is not device memory of the context's device", stream));
+  if (!c->dSrcTable.holds(ntable)) { // (the buffer has to move: only once nothing reads the old one)
+    VR_TRY(host_waits(c));
+    VR_HIP(c, c->dSrcTable.ensure(ntable));
+  }
+  VR_HIP(c, hipMemcpyAsync(c->dSrcTable.p, dTable, (size_t)ntable * 4, hipMemcpyDeviceToDevice, c->stream));
+  VR_TRY(caller_waits(c, stream));
+  c->srcTableCount = ntable;
   c->prepared = false;
   return VR_OK;
 }

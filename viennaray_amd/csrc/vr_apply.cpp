@@ -60,7 +60,7 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   // a surface source has no sort bins: its records lie in index order in the overflow region (gen_surface_kernel),
   // which the trace kernel reads as virtual bins of binCap rays
   const bool unbinned = p.surfPos != nullptr;
-  if (p.surfPos) // the batch's start weights, addressed by GLOBAL ray index like a host source's (gen_surface_kernel writes them)
+  if (L.genWeights) // the batch's start weights, addressed by GLOBAL ray index like a host source's (gen_surface_kernel / a source model's generator writes them)
     p.hostWeights = c->dSurfRayWeights.p - first;
   if (unbinned)
     p.numBins = 0;
@@ -108,9 +108,10 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
   if (rc != VR_OK)
     return rc;
   VR_HIP(c, hipEventRecord(g0, c->stream));
-  if (G.userGen) { // a stateful model: its module's generator (init, then the source sample)
+  if (G.userGen) { // a stateful model: its module's generator (init, then the source sample); a source model: its generator
     TraceParams pk = pg;
-    void *args[] = {&pk};
+    SourceCtx sc = G.source;
+    void *args[] = {&pk, &sc}; // (gen_state_kernel takes the first alone)
     const unsigned grid = std::min<unsigned>((count + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
     VR_HIP(c, hipModuleLaunchKernel(G.userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
   } else {

@@ -158,6 +158,16 @@ struct UserModel {
   std::map<int, hipFunction_t> kernels; // key: D * 100 + geo * 10 + mode
   hipFunction_t gen[2] = {nullptr, nullptr}; // a stateful model's generator (gen_state_kernel), 2-D / 3-D
 };
+// a source model registered at run time (vr_register_source_model): its own code object with the generator
+// (gen_user_source_kernel) and its debug twin, no trace kernel
+struct SourceModel {
+  std::string name;
+  std::string codeObject;                                         // path of the cached code object: the text's identity
+  hipModule_t module = nullptr;
+  bool hasWeight = false;                                         // VrUserSource::kHasWeight
+  hipFunction_t gen[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; // [2-D / 3-D][records without / with the RNG cursors]
+  hipFunction_t debug[2] = {nullptr, nullptr};                    // debug_user_source_kernel, 2-D / 3-D
+};
 
 // The prepared launch of one particle of an apply() (vr_context::launches: one per particle of vr_set_particles).
 // params holds everything but the buffers all particles share — ray stream, scratch, counters, accumulators — whose
@@ -172,6 +182,9 @@ struct ParticleLaunch {
   bool recExtra = false; // the records' side array (TraceParams::recExtra)
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
   hipFunction_t userGen = nullptr;    // ... and a stateful model's generator (nullptr: the library's)
+  bool userSource = false;            // userGen is a source model's generator: it takes `source` as its second argument
+  bool genWeights = false;            // the generator writes the batch's start weights (surface source, source model with kHasWeight)
+  SourceCtx source{};                 // what the source model sees of this launch
   DevBuf<float> primSticking;         // this particle's per-primitive sticking, leaf order (params.primSticking, or unused)
   DevBuf<int32_t> matTable;           // its (id, value) table for launch_prim_sticking: the ids, then the values' bits
   std::vector<int32_t> matTableHost;  // (staging of that upload)
@@ -267,6 +280,16 @@ struct vr_context {
   DevBuf<float> dSurfPosIn, dSurfNrmIn, dSurfWeightsIn; // vr_set_surface_source_device packs into these; accepted: swapped in
   DevBuf<unsigned long long> dSurfBad;                  // ... and its one word of validation
   DevBuf<float> dSurfRayWeights;   // start weight of every ray of one batch (TraceParams::hostWeights of a surface source)
+  // source model (vr_set_source_model): sampled on the device by its own generator; the table lives on the device
+  std::vector<SourceModel> sourceModels;
+  int32_t sourceModel = -1;        // index of the model in force (< 0: none)
+  float srcParams[VR_SOURCE_PARAMS] = {0};
+  uint32_t srcTableCount = 0;
+  DevBuf<float> dSrcTable;
+  uint64_t srcNumRays = 0;         // its own ray count (0: numRaysPerPoint / numRaysFixed over the primitives)
+  bool sourceModelWeights() const { return sourceModel >= 0 && sourceModels[sourceModel].hasWeight; }
+  // host rays, or a source model: the launch configuration is the same (records with a side array, any origin and draw count)
+  bool hostLikeSource() const { return !hostOrg.empty() || sourceModel >= 0; }
   uint64_t reserveRays = 0;        // vr_reserve_rays: the ray-stream buffers hold at least this many rays
   bool sourceDirty = false;
   DevBuf<float> dGrid, dHostOrg, dHostDir, dHostWeights;

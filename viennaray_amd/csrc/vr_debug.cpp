@@ -74,6 +74,8 @@ int vr_debug_process_hit(vr_context *c, const float *org, const float *dir, cons
 int vr_debug_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir) {
   if (!c || !idx || !org || !dir)
     return VR_E_INVALID;
+  if (c->sourceModel >= 0)
+    return fail(c, VR_E_STATE, "vr_debug_source_sample: a source model is set: its sample is vr_debug_user_source_sample's");
   VR_TRY(ensure_prepared(c));
   if (n > c->slotStride)
     return fail(c, VR_E_INVALID, "vr_debug_source_sample: more rays than one batch holds");
@@ -140,6 +142,45 @@ int vr_debug_surface_source_sample(vr_context *c, const uint64_t *idx, uint32_t 
   return VR_OK;
 }
 
+// The sample of the source model in force (vr_set_source_model), by the device function its generator calls, for the global
+// ray indices idx[] and kernel seed `seed`: origin, direction, start weight (1 without kHasWeight) and the engine outputs
+// consumed.  Any index: the sample depends on nothing else.
+int vr_debug_user_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
+                                float *weight, uint32_t *draws) {
+  if (!c || !idx || !org || !dir || !weight || !draws)
+    return VR_E_INVALID;
+  if (c->sourceModel < 0)
+    return fail(c, VR_E_STATE, "vr_debug_user_source_sample: no source model is set");
+  VR_TRY(ensure_prepared(c));
+  if (n == 0)
+    return VR_OK;
+  const ParticleLaunch &L = current_launch(c);
+  TraceParams p = launch_params(c, L);
+  SourceCtx sc = L.source;
+  p.seed = seed;
+  p.batchCount = n;
+  DevBuf<unsigned long long> dI;
+  DevBuf<float> dO, dD, dW;
+  DevBuf<uint32_t> dK;
+  VR_HIP(c, dI.upload((const unsigned long long *)idx, n));
+  VR_HIP(c, dO.ensure((size_t)n * 3));
+  VR_HIP(c, dD.ensure((size_t)n * 3));
+  VR_HIP(c, dW.ensure(n));
+  VR_HIP(c, dK.ensure(n));
+  p.idxList = dI.p;
+  void *args[] = {&p, &sc, &dO.p, &dD.p, &dW.p, &dK.p};
+  // (the grid bound of the generators: the RNG slabs are sized for it, size_scratch)
+  const unsigned grid = std::min<unsigned>((n + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
+  VR_HIP(c, hipModuleLaunchKernel(c->sourceModels[c->sourceModel].debug[c->geo.D == 3 ? 1 : 0], grid, 1, 1, VR_BLOCK, 1, 1, 0,
+                                  c->stream, args, nullptr));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  VR_HIP(c, dO.download(org, (size_t)n * 3));
+  VR_HIP(c, dD.download(dir, (size_t)n * 3));
+  VR_HIP(c, dW.download(weight, n));
+  VR_HIP(c, dK.download(draws, n));
+  return VR_OK;
+}
+
 // vr_debug_source_sample for the active STATEFUL model: its generator (init, then the source sample) for the global ray
 // indices idx[]; the first origin, direction and the engine outputs consumed before the trace (init + source)
 int vr_debug_model_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
@@ -148,7 +189,7 @@ int vr_debug_model_source_sample(vr_context *c, const uint64_t *idx, uint32_t n,
     return VR_E_INVALID;
   VR_TRY(ensure_prepared(c));
   const ParticleLaunch &L = current_launch(c);
-  if (c->specs.size() > 1 || !L.userGen)
+  if (c->specs.size() > 1 || !L.userGen || L.userSource)
     return fail(c, VR_E_STATE, "vr_debug_model_source_sample: the active particle is not (the only) stateful model");
   if (n > c->batchCap)
     return fail(c, VR_E_INVALID, "vr_debug_model_source_sample: more rays than one batch holds");

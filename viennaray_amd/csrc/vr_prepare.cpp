@@ -24,10 +24,13 @@ static int effective_direction(const vr_context *c) {
 static uint64_t surface_rays_per_point(const vr_context *c) { return c->numRaysFixed ? c->numRaysFixed : c->numRaysPerPoint; }
 
 // rayTraceKernel.hpp:57-61: numRaysFixed, or source.getNumPoints() * numRaysPerPoint
-// (SourceRandom: the geometry's points; SourceGrid: the grid's; host rays: exactly those given)
+// (SourceRandom: the geometry's points; SourceGrid: the grid's; host rays: exactly those given; a source model: its own
+//  count if it has one, else SourceRandom's)
 uint64_t rays_of_apply(const vr_context *c) {
   if (c->surfCount)
     return (uint64_t)c->surfCount * surface_rays_per_point(c);
+  if (c->sourceModel >= 0 && c->srcNumRays)
+    return c->srcNumRays;
   if (!c->hostOrg.empty())
     return c->hostOrg.size() / 3;
   const uint64_t srcPoints = !c->gridPoints.empty() ? c->gridPoints.size() / 3 : c->geo.numPrims;
@@ -337,7 +340,7 @@ static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, Particl
   const bool extended = sp.kernelKind >= VR_PARTICLE_CONED_COSINE || c->useWdist || sp.meanFreePath > 0.f;
   if (extended)
     L.absorb = false;
-  if ((!c->hostOrg.empty() && !c->hostWeights.empty()) || c->surfCount)
+  if ((!c->hostOrg.empty() && !c->hostWeights.empty()) || c->surfCount || c->sourceModelWeights())
     L.absorb = false; // (the absorbing kernels credit unit weights)
   // (the rare, register-hungry options — coned-cosine model, WDIST crediting, mean free path — have an instantiation
   //  of their own: multi-label and per-material particles should not pay for them)
@@ -348,10 +351,10 @@ static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, Particl
       return fail(c, VR_E_INVALID, "this particle model was registered without VR_MODEL_NEEDS_FULL: its code object has no "
                                    "kernel with WDIST crediting / mean-free-path scattering");
     extFull = um->needsFull;
-    if (um->numState > 0 && (!c->gridPoints.empty() || !c->hostOrg.empty() || c->surfCount))
+    if (um->numState > 0 && (!c->gridPoints.empty() || c->hostLikeSource() || c->surfCount))
       return fail(c, VR_E_INVALID, "a stateful particle model (numState > 0) runs its init on the device before the source "
                                    "sample: SourceRandom only (plain or with a primary direction), not SourceGrid, a host "
-                                   "source or a surface source");
+                                   "source, a surface source or a source model");
   }
   S.stateful = um && um->numState > 0;
   S.logs = S.stateful && c->logActive && um->logRows > 0;
@@ -398,7 +401,7 @@ static int build_relief_field(vr_context *c, const ParticleSpec &sp, ParticleLau
   const float travel = K.reliefTravel;
   L.relief = false;
   const float thickScene = c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]];
-  const bool plainSource = !c->usePrimaryDirection && c->gridPoints.empty() && c->hostOrg.empty() && !c->surfCount;
+  const bool plainSource = !c->usePrimaryDirection && c->gridPoints.empty() && !c->hostLikeSource() && !c->surfCount;
   const bool kernelOk = L.absorb || (c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT);
   const bool want = !S.flatScene && !S.smallScene && plainSource && kernelOk && sp.userModel < 0 && c->geo.gridDelta > 0.f &&
                     thickScene <= K.reliefMaxThick * c->geo.gridDelta && !K.noRelief;
@@ -534,10 +537,11 @@ static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState 
   // 32-byte records for every particle (vr_types.hpp); a non-absorbing particle under a source whose origin plane or
   // draw count varies (tilted, grid, host rays) adds 16 bytes per ray in a side array
   // (a stateful model's init draws before the source sample: its draw count varies too)
-  L.recExtra = !L.absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || !c->hostOrg.empty() || c->surfCount || S.stateful);
+  L.recExtra = !L.absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || c->hostLikeSource() || c->surfCount || S.stateful);
   if (L.recExtra)
     VR_HIP(c, c->dRecExtra.ensure_grow((size_t)c->batchCap * 4));
-  if (c->surfCount)
+  L.genWeights = c->surfCount || c->sourceModelWeights(); // (the generator writes the batch's start weights)
+  if (L.genWeights)
     VR_HIP(c, c->dSurfRayWeights.ensure_grow(c->batchCap));
   if (S.stateful) // (the state of every ray of a batch, float4 per ray; room for vr_reserve_rays' largest batch)
     VR_HIP(c, c->dRayState.ensure_grow((size_t)std::max<uint64_t>(c->batchCap, std::min<uint64_t>(c->reserveRays, 1ull << 27)) * 4));
@@ -604,6 +608,9 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   } else {
     blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.traceMode, L.params.smallBytes));
   }
+  L.userSource = c->sourceModel >= 0;
+  if (L.userSource) // the generator of the source model's code object, records without / with the RNG cursors
+    L.userGen = c->sourceModels[c->sourceModel].gen[D == 3 ? 1 : 0][L.absorb ? 0 : 1];
   // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
   // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of
   // them — about sqrt(rays / 10^5).  10^6 rays: 0.69 -> 0.49 ms (absorbing 0.47 -> 0.31)
@@ -635,8 +642,8 @@ static int size_scratch(vr_context *c, const ParticleLaunch &L, const PrepareSta
     size_t waves = 0;
     if (!L.absorb)
       waves = (size_t)std::max(L.grid, L.looseGrid) * (VR_BLOCK / 64);
-    if (c->usePrimaryDirection || !c->hostOrg.empty() || S.stateful)
-      waves = std::max(waves, (size_t)c->numCUs * 8u * (VR_BLOCK / 64)); // launch_gen's grid bound (gen_state_kernel's too)
+    if (c->usePrimaryDirection || c->hostLikeSource() || S.stateful)
+      waves = std::max(waves, (size_t)c->numCUs * 8u * (VR_BLOCK / 64)); // launch_gen's grid bound (gen_state_kernel's and gen_user_source_kernel's too)
     if (waves > c->scratchWaves) {
       VR_HIP(c, c->dScratch.ensure(waves * 312u * 64u));
       c->scratchWaves = waves;
@@ -722,6 +729,24 @@ static int fill_trace_params(vr_context *c, const ParticleSpec &sp, ParticleLaun
     p.surfWeights = c->dSurfWeights.p;
     p.surfRays = (uint32_t)surface_rays_per_point(c);
     p.surfOffset = c->surfOffset;
+  }
+  L.source = SourceCtx{};
+  if (L.userSource) { // what the source model sees (its table's address as it is now: a later setter clears `prepared`)
+    SourceCtx &sc = L.source;
+    for (int k = 0; k < 3; ++k) {
+      sc.bbLo[k] = c->bbLo[k];
+      sc.bbHi[k] = c->bbHi[k];
+    }
+    sc.srcCoord = c->ts[3] ? c->bbHi[c->ts[0]] : c->bbLo[c->ts[0]];
+    sc.rayDir = c->ts[0];
+    sc.firstDir = c->ts[1];
+    sc.secondDir = c->ts[2];
+    sc.posNeg = (float)c->ts[4];
+    sc.gridDelta = c->geo.gridDelta;
+    sc.sourcePower = sp.sourcePower;
+    sc.tableCount = c->srcTableCount;
+    sc.table = c->srcTableCount ? c->dSrcTable.p : nullptr;
+    std::memcpy(sc.params, c->srcParams, sizeof(sc.params));
   }
   p.accMask = c->accReplicas - 1u;
   VR_HIP(c, c->dCounters.ensure(C_BLOCK * c->launches.size()));

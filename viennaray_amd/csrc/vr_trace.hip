@@ -32,7 +32,8 @@ namespace vr {
 __device__ __forceinline__ u64 weight_fx(float w) { return (u64)((double)w * 1099511627776.0 + 0.5); }
 
 // (a run-time compiled particle module holds the trace kernels and — for a stateful model — its own generator, built from
-//  the source sampling and the record store below; see the end of the file)
+//  the source sampling and the record store below; a run-time compiled SOURCE module holds a generator alone; see the end
+//  of the file)
 // ---------------------------------------------------------------------------
 // source sampling (raySourceRandom.hpp:25-116)
 // ---------------------------------------------------------------------------
@@ -1977,6 +1978,89 @@ hipError_t launch_gather_flux(const unsigned long long *acc, unsigned stride, un
                      outAcc, headroomBits, overflowFlag);
   return hipGetLastError();
 }
+
+#elif defined(VR_USER_SOURCE_MODULE)
+// ---------------------------------------------------------------------------
+// A SOURCE model registered at RUN TIME (vr_register_source_model, include/viennaray_amd.h): the reference's second
+// extension point, Source<NumericType> (raySource.hpp:10-19: getOriginAndDirection(idx, rng), getInitialRayWeight(idx)),
+// as device code.  The library writes a translation unit that defines VR_USER_MODULE, VR_USER_SOURCE_MODULE and
+// VR_USER_SOURCE_FILE — the caller's text, which defines
+//
+//   struct VrUserSource {
+//     static constexpr bool kHasWeight = ...; // false: every ray starts with weight 1 and the absorbing kernels stay eligible
+//     template <int D, class Draw>
+//     __device__ static void sample(const SourceCtx &s, unsigned long long idx, Draw &&draw, V3 &org, V3 &dir, float &weight);
+//   };
+//
+// — and includes this file: a code object with the generator and its debug twin only, no trace kernel.  draw() is the next
+// raw 64-bit output of ray idx's engine (tea3(idx, seed), rng_next): any number of them, lane by lane; canon_f32 / canon_f64
+// turn one into the reference's uniform float / double.  `dir` is used as returned: the model normalises it (vnormalize).
+// `weight` is 1 on entry and read only with kHasWeight.  SourceCtx: vr_types.hpp.
+//
+// The record, its sort bin and the side array are a host-ray apply's (gen_host_kernel): the trace launch is that launch.
+// ---------------------------------------------------------------------------
+#include VR_USER_SOURCE_FILE
+static_assert(VrUserSource::kHasWeight == (VR_USER_SOURCE_HAS_WEIGHT != 0), "kHasWeight differs from the VR_SOURCE_HAS_WEIGHT flag given at registration");
+
+template <int D>
+__device__ __forceinline__ void user_source_sample(const SourceCtx &sc, unsigned long long idx, Rng &rng, V3 &o, V3 &d, float &w) {
+  unsigned t2 = 0; // (a full state built HERE is the generator's own: the tracer rebuilds it from k and counts it then)
+  o = mk(0.f, 0.f, 0.f);
+  d = mk(0.f, 0.f, 0.f);
+  w = 1.f;
+  VrUserSource::template sample<D>(sc, idx, [&]() { return rng_next(rng, t2); }, o, d, w);
+  if (!VrUserSource::kHasWeight)
+    w = 1.f;
+}
+
+template <int D, bool KEEP> __global__ __launch_bounds__(VR_BLOCK) void gen_user_source_kernel(const TraceParams p, const SourceCtx sc) {
+  const unsigned tid = threadIdx.x;
+  const unsigned gwave = (blockIdx.x * VR_BLOCK + tid) >> 6; // physical wave of this (bounded) grid
+  u64 *scratchLane = p.rngScratch + (size_t)gwave * (312u * 64u) + (tid & 63u);
+  for (unsigned i = blockIdx.x * VR_BLOCK + tid; i < p.batchCount; i += gridDim.x * VR_BLOCK) {
+    const unsigned long long idx = p.idxList ? p.idxList[i] : p.batchFirst + i;
+    Rng rng;
+    rng_init(rng, tea3((unsigned)idx, p.seed), scratchLane);
+    V3 o, d;
+    float w;
+    user_source_sample<D>(sc, idx, rng, o, d, w);
+    gen_store<D, KEEP>(p, i, o, d, rng.k, rng.lo, rng.hi); // (k >= 156: the trace kernel rebuilds the full state from the seed and skips k outputs)
+    // the start weight goes where gen_surface_kernel puts it: the batch's buffer, addressed by GLOBAL ray index
+    if (VrUserSource::kHasWeight && p.hostWeights)
+      const_cast<float *>(p.hostWeights)[p.batchFirst + i] = w;
+  }
+}
+
+// vr_debug_user_source_sample: what the generator's sample gives for the p.batchCount ray indices p.idxList[]
+template <int D>
+__global__ __launch_bounds__(VR_BLOCK) void debug_user_source_kernel(const TraceParams p, const SourceCtx sc, float *org, float *dir,
+                                                                     float *weight, unsigned *draws) {
+  const unsigned tid = threadIdx.x;
+  const unsigned gwave = (blockIdx.x * VR_BLOCK + tid) >> 6;
+  u64 *scratchLane = p.rngScratch + (size_t)gwave * (312u * 64u) + (tid & 63u);
+  for (unsigned i = blockIdx.x * VR_BLOCK + tid; i < p.batchCount; i += gridDim.x * VR_BLOCK) {
+    const unsigned long long idx = p.idxList[i];
+    Rng rng;
+    rng_init(rng, tea3((unsigned)idx, p.seed), scratchLane);
+    V3 o, d;
+    float w;
+    user_source_sample<D>(sc, idx, rng, o, d, w);
+    org[3 * (size_t)i] = o.x;
+    org[3 * (size_t)i + 1] = o.y;
+    org[3 * (size_t)i + 2] = o.z;
+    dir[3 * (size_t)i] = d.x;
+    dir[3 * (size_t)i + 1] = d.y;
+    dir[3 * (size_t)i + 2] = d.z;
+    weight[i] = w;
+    draws[i] = rng.k;
+  }
+}
+template __global__ void gen_user_source_kernel<2, false>(const TraceParams, const SourceCtx);
+template __global__ void gen_user_source_kernel<2, true>(const TraceParams, const SourceCtx);
+template __global__ void gen_user_source_kernel<3, false>(const TraceParams, const SourceCtx);
+template __global__ void gen_user_source_kernel<3, true>(const TraceParams, const SourceCtx);
+template __global__ void debug_user_source_kernel<2>(const TraceParams, const SourceCtx, float *, float *, float *, unsigned *);
+template __global__ void debug_user_source_kernel<3>(const TraceParams, const SourceCtx, float *, float *, float *, unsigned *);
 
 #else // VR_USER_MODULE
 // ---------------------------------------------------------------------------

@@ -184,6 +184,21 @@ struct TraceParams {
   float surfOffset;                // origin = position + unit normal * surfOffset
 };
 
+// What a run-time SOURCE model (vr_register_source_model; vr_trace.hip, the source-module section) sees of the launch:
+// the second argument of its generator, by value.  The library's own kernels never take it: TraceParams stays as it is.
+constexpr int VR_SOURCE_PARAMS = 16;
+struct SourceCtx {
+  float bbLo[3], bbHi[3];          // the bounding box the source plane and the walls are made from (vr_get_bounding_box)
+  float srcCoord;                  // the source plane's coordinate on axis rayDir
+  int32_t rayDir, firstDir, secondDir; // tracing axis and the two axes of the source plane (0 / 1 / 2)
+  float posNeg;                    // +1 / -1: sign of a ray's component along rayDir
+  float gridDelta;
+  float sourcePower;               // the particle's getSourceDistributionPower()
+  uint32_t tableCount;             // entries of `table`
+  const float *table;              // vr_set_source_model's table (device memory; nullptr: none)
+  float params[VR_SOURCE_PARAMS];  // vr_set_source_model's parameters, zeros behind those given
+};
+
 // Relief field over the source plane (vr_setup.hip: relief_field_kernel): per fine tile the [lo, hi] range — along the
 // source axis, padded — of every primitive whose (padded) box meets the tile.  A ray can only meet geometry inside a
 // tile while its own height is within that range: relief_clip (vr_device.hpp) walks the tiles under a ray and returns

@@ -173,6 +173,53 @@ class SourceGrid:
         return self.points.shape[0]
 
 
+class SourceModel:
+    """A user Source (raySource.hpp:10-19) as device code: `source` is HIP text defining `struct VrUserSource` (kHasWeight,
+    sample<D>(ctx, idx, draw, org, dir, weight); include/viennaray_amd.h: vr_register_source_model), compiled into the ray
+    generator when a tracer's setSource(model) first sees the text (the tracer keeps the registration: one model object
+    may serve any number of tracers, one after the other or side by side).  params: up to 16 floats the model reads as ctx.params; table:
+    one float32 table it reads as ctx.table[0 .. ctx.tableCount) — a host array, or a 1-D contiguous float32 torch tensor
+    on the tracer's device, which stays there; numRays: 0 keeps numRaysPerPoint / numRaysFixed over the primitives, > 0
+    is the source's own ray count; hasWeight: the text's kHasWeight."""
+
+    def __init__(self, name, source, params=(), table=None, numRays=0, hasWeight=False):
+        if not isinstance(source, str) or not source.strip():
+            raise ValueError("SourceModel: source must be the HIP text of struct VrUserSource")
+        self.name = str(name)
+        self.source = source
+        self.hasWeight = bool(hasWeight)
+        self.params = self._checked_params(params)
+        self.table = self._checked_table(table)
+        self.numRays = int(numRays)
+        if not 0 <= self.numRays <= 0xFFFFFFFF:
+            raise ValueError("SourceModel: numRays must be 0 .. 2^32 - 1")
+
+    @staticmethod
+    def _checked_params(params):
+        a = np.ascontiguousarray(params, dtype=np.float32)
+        if a.ndim != 1 or a.size > capi.VR_SOURCE_PARAMS:
+            raise ValueError(f"SourceModel: params: at most {capi.VR_SOURCE_PARAMS} floats in one dimension, got shape {a.shape}")
+        return a
+
+    @staticmethod
+    def _checked_table(table):
+        """None, a device tensor (checked against the tracer's device when it is set) or a host float32 vector"""
+        if table is None:
+            return None
+        if hasattr(table, "data_ptr"):  # a torch tensor: handed over where it is, or refused
+            if not _on_any_device(table):
+                raise ValueError("SourceModel: table: device: a torch tensor must be on the tracer's device "
+                                 "(pass a host table as a numpy array)")
+            return table
+        a = np.asarray(table)
+        if a.dtype != np.float32 and not isinstance(table, (list, tuple)):
+            raise ValueError(f"SourceModel: table: dtype: {a.dtype}, a table is float32")
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 1:
+            raise ValueError(f"SourceModel: table: shape: {a.shape}, a table has one dimension")
+        return a
+
+
 class TracingData:
     """rayTracingData.hpp:16-219: labelled vectors and scalars with a merge type each.  The
     device path fills vector 0 of Trace.getLocalData() (merge type SUM)."""
@@ -290,6 +337,7 @@ class Trace:
         self._h = h
         self._device = int(device)
         self._particle = None
+        self._sourceIds = {}  # (text, hasWeight) of a SourceModel -> its id on this context
         self._localData = TracingData()
         self._n = 0
 
@@ -411,13 +459,58 @@ class Trace:
         self._check(self._L.vr_set_use_wdist(self._h, int(bool(on))))
 
     def setSource(self, source):
-        """rayTrace.hpp:53-56.  SourceGrid runs natively in the generator kernel; any other object with
-        getOriginAndDirection(idx, rng) is a host callback: it is evaluated here for every ray (rng = a
-        counting stand-in of the per-ray engine) and the rays are handed to the device."""
+        """rayTrace.hpp:53-56.  SourceGrid runs natively in the generator kernel; a SourceModel is compiled into the
+        generator and sampled on the device (None: back to SourceRandom); the rays of a host-callback source
+        (getOriginAndDirection(idx, rng) evaluated by the caller) go through setHostRays."""
         if isinstance(source, SourceGrid):
             self._check(self._L.vr_set_source_grid(self._h, _fptr(source.points), source.points.shape[0]))
             return
+        if source is None or isinstance(source, SourceModel):
+            return self._setSourceModel(source)
         raise VrError("setSource: host-callback sources go through setHostRays(origins, directions, draws)")
+
+    def registerSourceModel(self, name, source, hasWeight=False):
+        """vr_register_source_model: HIP text of `struct VrUserSource` -> the id vr_set_source_model takes"""
+        k = C.c_int32(-1)
+        self._check(self._L.vr_register_source_model(self._h, str(name).encode(), source.encode(),
+                                                     capi.VR_SOURCE_HAS_WEIGHT if hasWeight else 0, C.byref(k)))
+        return int(k.value)
+
+    def _setSourceModel(self, model):
+        """A SourceModel becomes the source (None: back to SourceRandom).  Everything is checked before anything is set:
+        a refusal leaves the previous source, and its table, in force."""
+        if model is None:
+            self._check(self._L.vr_set_source_model(self._h, -1, None, 0, None, 0, 0))
+            return
+        params = SourceModel._checked_params(model.params)
+        table = SourceModel._checked_table(model.table)
+        onDevice = table is not None and hasattr(table, "data_ptr")
+        if onDevice:
+            _check_device_tensor("setSource", "table", table, self._device, "torch.float32", [(None,)])
+        # the registration belongs to THIS tracer's context and to the text: kept here, by content, so that a model object
+        # may outlive a tracer or serve several, and a model object rebuilt for new parameters registers nothing again
+        key = (model.source, model.hasWeight)
+        if key not in self._sourceIds:
+            self._sourceIds[key] = self.registerSourceModel(model.name, model.source, model.hasWeight)
+        host = None if (onDevice or table is None) else table
+        self._check(self._L.vr_set_source_model(self._h, self._sourceIds[key], _fptr(params) if params.size else None, params.size,
+                                                _fptr(host) if host is not None and host.size else None,
+                                                host.size if host is not None else 0, int(model.numRays)))
+        if onDevice:
+            # a float32 tensor on the tracer's device stays there (vr_set_source_model_table_device): copied by the
+            # library behind the current torch stream, which may overwrite the tensor afterwards
+            self._check(self._L.vr_set_source_model_table_device(self._h, C.c_void_p(table.data_ptr()), int(table.numel()),
+                                                                 C.c_void_p(self._torch_stream())))
+
+    def setSourceModelTable(self, table):
+        """The table of the source model in force alone: a host float32 vector is not taken here (set the model again);
+        a float32 1-D contiguous tensor on the tracer's device is copied on the device.  Anything else raises
+        ValueError and the previous table stays."""
+        if not hasattr(table, "data_ptr") or not _on_any_device(table):
+            raise ValueError("setSourceModelTable: device: the table must be a torch tensor on the tracer's device")
+        _check_device_tensor("setSourceModelTable", "table", table, self._device, "torch.float32", [(None,)])
+        self._check(self._L.vr_set_source_model_table_device(self._h, C.c_void_p(table.data_ptr()), int(table.numel()),
+                                                             C.c_void_p(self._torch_stream())))
 
     def setHostRays(self, origins, directions, draws=None, weights=None, sourceArea=None):
         """Rays of a host-callback Source (raySource.hpp:10-19): origin, direction, engine outputs consumed and —
@@ -743,6 +836,19 @@ class Trace:
         self._check(self._L.vr_debug_surface_source_sample(self._h, i.ctypes.data_as(C.POINTER(C.c_uint64)), i.size,
                                                            int(seed), _fptr(o), _fptr(d), _fptr(w),
                                                            k.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return o, d, w, k
+
+    def debugUserSourceSample(self, idx, seed):
+        """the sample of the source model in force for global ray indices idx and kernel seed `seed`, by the generator's
+        own device function: origin, direction, start weight, engine outputs consumed"""
+        i = np.ascontiguousarray(idx, dtype=np.uint64)
+        o = np.empty((i.size, 3), dtype=np.float32)
+        d = np.empty((i.size, 3), dtype=np.float32)
+        w = np.empty(i.size, dtype=np.float32)
+        k = np.empty(i.size, dtype=np.uint32)
+        self._check(self._L.vr_debug_user_source_sample(self._h, i.ctypes.data_as(C.POINTER(C.c_uint64)), i.size,
+                                                        int(seed), _fptr(o), _fptr(d), _fptr(w),
+                                                        k.ctypes.data_as(C.POINTER(C.c_uint32))))
         return o, d, w, k
 
     def debugSourceSample(self, idx, seed):
