@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Register / LDS / scratch budget of every trace and generator kernel, from hipcc's
 -Rpass-analysis=kernel-resource-usage remarks.
-usage: hipcc ... -Rpass-analysis=kernel-resource-usage -c vr_trace.hip 2> usage.txt; tools/kernel_usage.py usage.txt"""
+usage: hipcc ... -Rpass-analysis=kernel-resource-usage -c vr_trace.hip 2> usage.txt; tools/kernel_usage.py usage.txt
+(three .hip files hold kernels: vr_trace.hip has the generators and the trace kernels, vr_diag.hip the diagnostic
+kernels, vr_setup.hip the scene set-up and the results stage; the remarks of any of them, or of all, will do)"""
 import re
 import subprocess
 import sys

@@ -6,12 +6,16 @@ from the kernel's ISA compiled with line tables, weighted by trip counts.
         viennaray_amd/csrc/vr_trace.hip -o k.s
     tools/salu_inventory.py k.s [mangled kernel name]
 
+(Three .hip files hold kernels: vr_trace.hip — the generators of vr_generate.hpp and the trace kernels of
+vr_trace_kernel.hpp — vr_diag.hip and vr_setup.hip.  The trace kernels are in vr_trace.hip's assembly.)
+
 (The tool prints the kernel's instruction count: compare it with tools/spill_by_depth.py on the plain build — line
 tables can move a kernel's register allocation, and an inventory of other code than the library's is worthless.)
 
 What is counted as SALU: every s_* instruction but scalar memory loads (SQ_INSTS_SMEM), branches
 (SQ_INSTS_BRANCH) and s_waitcnt / s_nop / s_barrier / s_endpgm / s_sleep / s_setprio, which never reach the scalar ALU.
-A phase is a range of source lines (the innermost inlined location of each instruction); a loop is named by
+A phase is a range of source lines (the innermost inlined location of each instruction), found at run time: in
+vr_trace_kernel.hpp it runs from one marker comment of the kernel body (MARKERS) to the next; a loop is named by
 its header's label.  Weights (WEIGHTS below): executions per packet round of each loop's body, from the committed
 profile of the headline launch (profiles/r04_C2_s1.0_summary.txt)."""
 import re
@@ -19,20 +23,39 @@ import sys
 
 DEFAULT = "_ZN2vr12trace_kernelILi3ELi0ELi0ELi1EEEvNS_11TraceParamsE"
 
-# phases by source line of vr_trace.hip (T) and vr_device.hpp (D); first match wins
-PHASES = [
-    ("queue pull", "T", 871, 916),
-    ("refill bin walk", "T", 855, 1019),
-    ("round set-up / votes", "T", 1020, 1051),
-    ("walls", "T", 1052, 1065),
-    ("packet query (call, back-off)", "T", 1066, 1079),
-    ("fall-back packet / walk", "T", 1080, 1125),
-    ("walls", "T", 1126, 1131),
-    ("state machine", "T", 1132, 1416),
-    ("crediting", "T", 1417, 1497),
-    ("prologue / epilogue", "T", 0, 854),
-    ("prologue / epilogue", "T", 1498, 99999),
+# phases of the kernel body in vr_trace_kernel.hpp: each begins at the line of its marker comment and ends before the next
+# marker's; what lies before the first marker belongs to the prologue.  Every marker must be there exactly once, in this order.
+MARKERS = [
+    ("// ---- wave-wide compaction / restart", "refill bin walk"),
+    ("// ---- queue pull", "queue pull"),
+    ("// ---- (end of the queue pull", "refill bin walk"),
+    ("// ---- round set-up", "round set-up / votes"),
+    ("// ---- walls first", "walls"),
+    ("// ---- packet query", "packet query (call, back-off)"),
+    ("// ---- fall-back", "fall-back packet / walk"),
+    ("// ---- walls of the finished segments", "walls"),
+    ("// ---- the aggregation vote", "state machine"),
+    ("// ---- crediting", "crediting"),
+    ("// ---- end of crediting", "prologue / epilogue"),
 ]
+
+
+def kernel_phases(path):
+    """[(phase, first line, last line)] of vr_trace_kernel.hpp, from MARKERS"""
+    src = open(path).read().split("\n")
+    at = []
+    for text, _ in MARKERS:
+        hits = [i for i, l in enumerate(src, 1) if l.strip().startswith(text)]
+        if len(hits) != 1 or (at and hits[0] <= at[-1]):
+            sys.exit(f"{path}: the marker comment '{text}' must be there exactly once, behind the marker before it "
+                     f"(found at lines {hits}): the kernel body has changed, bring MARKERS and its comments back in line")
+        at.append(hits[0])
+    out = [("prologue / epilogue", 0, at[0] - 1)]
+    for k, (_, phase) in enumerate(MARKERS):
+        out.append((phase, at[k], at[k + 1] - 1 if k + 1 < len(at) else 10 ** 9))
+    return out
+
+
 # functions of vr_device.hpp that ARE a phase; every other function there (edot, hit_disc, ballot64, ...) and every
 # system header is a helper inlined into its caller: its instructions stay with the phase seen last
 DEVICE_FUNCS = {
@@ -89,6 +112,7 @@ def main():
     import os
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     dev = device_ranges(os.path.join(here, "viennaray_amd", "csrc", "vr_device.hpp"))
+    phases = kernel_phases(os.path.join(here, "viennaray_amd", "csrc", "vr_trace_kernel.hpp"))
     src = open(os.path.join(here, "viennaray_amd", "csrc", "vr_device.hpp")).read().split("\n")
     # the candidate loop of pq_hit_packet starts at its "unsigned tests = 0;"
     pq = [r for r in dev if r[2] == "pq_hit_packet"][0]
@@ -102,8 +126,8 @@ def main():
 
     def phase_of(fno, line, last):
         f = files.get(fno, "")
-        if f.endswith("vr_trace.hip"):
-            for name, _, lo, hi in PHASES:
+        if f.endswith("vr_trace_kernel.hpp"):
+            for name, lo, hi in phases:
                 if lo <= line <= hi:
                     return name
         if f.endswith("vr_device.hpp"):

@@ -177,7 +177,7 @@ struct ParticleLaunch {
   uint32_t slot = 0;     // index of the particle: its counter block, wall-table / frame slot
   uint32_t dataBase = 0; // its first accumulator plane
   unsigned grid = 0;
-  int traceMode = 0, kernelParticle = 0;
+  int traceMode = MODE_GENERAL, kernelParticle = 0;
   bool absorb = false;
   bool recExtra = false; // the records' side array (TraceParams::recExtra)
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
@@ -189,7 +189,7 @@ struct ParticleLaunch {
   DevBuf<int32_t> matTable;           // its (id, value) table for launch_prim_sticking: the ids, then the values' bits
   std::vector<int32_t> matTableHost;  // (staging of that upload)
   bool relief = false; // flat with relief: a second launch (looseMode, looseGrid) traces the loose bins
-  int looseMode = 0;
+  int looseMode = MODE_GENERAL;
   unsigned looseGrid = 0;
   vr_trace_info info{};
 };

@@ -106,7 +106,7 @@ int vr_debug_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint3
   return VR_OK;
 }
 
-// The surface source's sample (vr_trace.hip: surface_sample, the device function of its generator) for the global ray
+// The surface source's sample (vr_generate.hpp: surface_sample, the device function of its generator) for the global ray
 // indices idx[]: origin, direction, start weight and the engine outputs consumed (2)
 int vr_debug_surface_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir,
                                    float *weight, uint32_t *draws) {

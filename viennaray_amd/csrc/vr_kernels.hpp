@@ -7,15 +7,16 @@
 
 namespace vr {
 
+// generators and trace kernels (vr_trace.hip); mode: a TraceMode (vr_types.hpp)
 hipError_t launch_gen(const TraceParams &p, int D, bool keepRng, unsigned maxBlocks, hipStream_t s);
-// surface_sample (the surface source's generator) for the p.batchCount ray indices p.idxList[]
-hipError_t launch_debug_surface_sample(const TraceParams &p, unsigned maxBlocks, float *org, float *dir, float *weight,
-                                       unsigned *draws, hipStream_t s);
-hipError_t launch_scan(unsigned *data, unsigned n, unsigned *tmp, hipStream_t s);
 hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid,
                         hipStream_t s);
 // resident 256-thread blocks per CU of the trace kernel instantiation (occupancy API)
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes);
+// diagnostics (vr_diag.hip)
+// surface_sample (the surface source's generator) for the p.batchCount ray indices p.idxList[]
+hipError_t launch_debug_surface_sample(const TraceParams &p, unsigned maxBlocks, float *org, float *dir, float *weight,
+                                       unsigned *draws, hipStream_t s);
 hipError_t launch_debug_intersect(const TraceParams &p, int geo, const float *org, const float *dir,
                                   const float *tnear, unsigned n, int *geomID, unsigned *primID, float *t, int ordered,
                                   unsigned walkStackWaves, hipStream_t s);
@@ -25,6 +26,8 @@ hipError_t launch_debug_process_hit(const TraceParams &p, int D, const float *or
 hipError_t launch_debug_rng(unsigned seed32, unsigned count, unsigned long long *scratch, unsigned long long *out,
                             hipStream_t s);
 // device-side setup (vr_setup.hip)
+// in-place exclusive scan; tmp: >= 2 * ceil(n / 2048) + 2 words
+hipError_t launch_scan(unsigned *data, unsigned n, unsigned *tmp, hipStream_t s);
 hipError_t launch_setup_bvh(const SetupParams &s, unsigned *scanTmp, hipStream_t st);
 hipError_t launch_fit_bvh(const SetupParams &s, hipStream_t st);
 hipError_t launch_bvh_check(const SetupParams &s, unsigned *bad, hipStream_t st);
@@ -36,9 +39,6 @@ hipError_t launch_smooth_wide(const float *fluxIn, float *fluxOut, const float *
 hipError_t launch_quantize_nodes(const float *nodes, unsigned numNodes, const float *base3, const float *scale3,
                                  uint32_t *qnodes, uint32_t *pnodes, hipStream_t st);
 hipError_t launch_setup_neighbors(const SetupParams &s, int pass, hipStream_t st);
-hipError_t launch_gather_flux(const unsigned long long *acc, unsigned stride, unsigned replicas,
-                              const unsigned *leafOfOrig, unsigned n, unsigned long long *outAcc, unsigned headroomBits,
-                              unsigned long long *overflowFlag, hipStream_t s);
 
 // 64-ary box tree for the packet query (vr_setup.hip)
 size_t wide_tree_entries(unsigned n);
@@ -84,6 +84,10 @@ hipError_t launch_surface_source(const float *pos, const float *nrm, const float
 hipError_t launch_disk_areas(const float *disk4, const float *normal3, unsigned n, const AreaParams &p, float *out,
                              hipStream_t st);
 hipError_t launch_flux_from_acc(const unsigned long long *acc, unsigned n, float *flux, hipStream_t st);
+// the replicas of the leaf-ordered accumulators summed into the caller's primitive order; overflow raises *overflowFlag
+hipError_t launch_gather_flux(const unsigned long long *acc, unsigned stride, unsigned replicas,
+                              const unsigned *leafOfOrig, unsigned n, unsigned long long *outAcc, unsigned headroomBits,
+                              unsigned long long *overflowFlag, hipStream_t s);
 hipError_t launch_normalize_flux(float *flux, const float *area, unsigned n, int geo, int normType, float normFactor,
                                  double totalDiskArea, unsigned *maxOrd, hipStream_t st);
 // issue-ceiling microbenchmarks (vr_bench.hip); out: one {cycles, realtime, sink} triple of u64 per wave

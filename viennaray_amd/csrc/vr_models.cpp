@@ -1,5 +1,5 @@
 // vr_models.cpp — particle models and source models registered at run time: the caller's text is compiled around the
-// library's own kernel sources (a hipcc child, cached by content: build_code_object) and loaded as a code object.
+// library's own kernel sources (vr_trace.hip and what it includes: the Makefile's MODEL_SRCS; a hipcc child, cached by content: build_code_object) and loaded as a code object.
 #include <dlfcn.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -24,6 +24,11 @@ static uint64_t fnv1a(uint64_t h, const void *data, size_t n) {
   }
   return h;
 }
+
+// the files a run-time module is compiled from, blank separated: the Makefile's MODEL_SRCS, the one place that names them
+#ifndef VR_MODEL_SRCS
+#error "VR_MODEL_SRCS is not defined: build vr_models.cpp through the Makefile, which names a module's sources"
+#endif
 
 static bool slurp(const std::string &path, std::string &out) {
   std::ifstream f(path, std::ios::binary);
@@ -111,7 +116,8 @@ static int build_code_object(vr_context *c, const ModuleKind &kind, uint64_t h, 
   const std::string hipcc = std::getenv("VR_HIPCC") ? std::getenv("VR_HIPCC") : "/opt/rocm/bin/hipcc";
   const std::string ccFlags = " --genco --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -Wno-unused-function";
   std::string cksums;
-  for (const char *fn : {"vr_trace.hip", "vr_device.hpp", "vr_particles.hpp", "vr_types.hpp", "vr_libm.hpp", "vr_kernels.hpp"}) {
+  std::istringstream names(VR_MODEL_SRCS);
+  for (std::string fn; names >> fn;) {
     std::string text;
     if (!slurp(csrc + "/" + fn, text))
       return fail(c, VR_E_STATE, (api + ": kernel source not found: " + csrc + "/" + fn +
@@ -269,8 +275,8 @@ int vr_register_particle_model_ex(vr_context *c, const char *name, const char *s
   const int P = full ? (int)P_EXT_FULL : (int)P_EXT;
   for (int D = 2; D <= 3; ++D)
     for (int geo = 0; geo <= 1; ++geo)
-      for (int mode : {0, 3, 4}) {
-        if (mode == 3 && (geo != 0 || full))
+      for (int mode : {MODE_GENERAL, MODE_GENERAL_FLAT, MODE_SMALL}) {
+        if (mode == MODE_GENERAL_FLAT && (geo != 0 || full))
           continue;
         char sym[128];
         std::snprintf(sym, sizeof(sym), "_ZN2vr12trace_kernelILi%dELi%dELi%dELi%dEEEvNS_11TraceParamsE", D, geo, P, mode);
@@ -287,7 +293,7 @@ int vr_register_particle_model_ex(vr_context *c, const char *name, const char *s
 }
 
 // A SOURCE model registered at run time: the reference's Source<NumericType> (raySource.hpp:10-19) as device code.  `source`
-// is HIP text that defines `struct VrUserSource` (vr_trace.hip, the source-module section, says what it looks like); the
+// is HIP text that defines `struct VrUserSource` (vr_modules.hpp, the source-module section, says what it looks like); the
 // library compiles the generator around it for gfx950 — no trace kernel: a fraction of a particle module's compile time —
 // caches the code object by content and loads it (a text this context has registered already gives its id again: nothing
 // is loaded twice).  flags: VR_SOURCE_HAS_WEIGHT exactly when the model's kHasWeight is true.

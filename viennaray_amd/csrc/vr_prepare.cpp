@@ -393,7 +393,7 @@ static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, Particl
 // query, and the query clips its rays to the SCENE box: half a grid cell of relief lets the grazing rays of a wave
 // stretch its box over hundreds of cells.  Where the scene is thin along the source axis and the relief field says that
 // few rays would be grazing ones (ReliefParams::stats), the rays are sorted by their predicted first hit, the grazing ones are filed apart
-// (bin_of_relief, vr_trace.hip) and the query clips to the LOCAL relief (relief_clip, vr_device.hpp): MODE 5 / 6.
+// (bin_of_relief, vr_generate.hpp) and the query clips to the LOCAL relief (relief_clip, vr_device.hpp): MODE 5 / 6.
 static int build_relief_field(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, const PrepareState &S) {
   const Knobs &K = c->knobs;
   TraceParams &p = L.params;
@@ -561,31 +561,32 @@ static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState 
 static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, const PrepareState &S) {
   const Knobs &K = c->knobs;
   const int D = c->geo.D;
+  // (the modes: enum TraceMode, vr_types.hpp)
   // absorbing particles: a (nearly) flat surface is served by packets alone; a structured one
-  // ends most rounds in per-lane walks and wants the straggler carry-over (MODE 2)
-  // general particles on a flat surface of disks: the general kernel with the packet query's crediting (MODE 3)
+  // ends most rounds in per-lane walks and wants the straggler carry-over (MODE_ABSORB)
+  // general particles on a flat surface of disks: the general kernel with the packet query's crediting (MODE_GENERAL_FLAT)
   // (the lean extended kernel P_EXT — data labels, per-material sticking, global data — has the packet query's
-  //  crediting too; P_EXT_FULL, the instantiation with the rare options, stays on MODE 0)
+  //  crediting too; P_EXT_FULL, the instantiation with the rare options, stays on MODE_GENERAL)
   // "flat": 95 % of the surface shown to the source lies in one plane AND the scene box is thin along the source
   // axis — the packet query clips its rays to that box, and a box half a grid cell thick already lets the few
   // grazing rays of a wave stretch its query over dozens of primitives (a 10^6-disk plane with ONE 50 x 50 bump of
   // 0.3 cells: the absorbing kernel 6.4 -> 8.3 ms, the general one 11 -> 18; the kernels for structured scenes are
   // then 2 - 6 % ahead of the flat ones.  DESIGN.md section 10: a flat layer + relief decomposition would close this)
   const bool generalFlatOk = !L.absorb && c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT;
-  L.traceMode = !L.absorb ? ((S.flatScene && generalFlatOk) ? 3 : 0) : (S.flatScene ? 1 : 2);
+  L.traceMode = !L.absorb ? ((S.flatScene && generalFlatOk) ? MODE_GENERAL_FLAT : MODE_GENERAL) : (S.flatScene ? MODE_ABSORB_FLAT : MODE_ABSORB);
   L.looseMode = L.traceMode;
   if (L.relief) { // flat with relief: the flat-scene kernels on the tight bins, the structured-scene ones on the loose
-    L.traceMode = L.absorb ? 5 : 6;
+    L.traceMode = L.absorb ? MODE_ABSORB_RELIEF : MODE_GENERAL_RELIEF;
     if (!L.absorb && !K.noSpill)
-      L.looseMode = 7; // ... which also resume the rays the tight general kernel spills (TraceParams::spillRec)
+      L.looseMode = MODE_RESUME; // ... which also resume the rays the tight general kernel spills (TraceParams::spillRec)
   }
   if (K.generalFlat.has_value() && generalFlatOk)
-    L.traceMode = *K.generalFlat ? 3 : 0;
+    L.traceMode = *K.generalFlat ? MODE_GENERAL_FLAT : MODE_GENERAL;
   if (K.absorbCarry.has_value() && L.absorb)
-    L.traceMode = *K.absorbCarry ? 2 : 1;
+    L.traceMode = *K.absorbCarry ? MODE_ABSORB : MODE_ABSORB_FLAT;
   if (S.smallScene)
-    L.traceMode = 4;
-  if (L.traceMode != 5 && L.traceMode != 6) { // (a switch above took the mode back)
+    L.traceMode = MODE_SMALL;
+  if (L.traceMode != MODE_ABSORB_RELIEF && L.traceMode != MODE_GENERAL_RELIEF) { // (a switch above took the mode back)
     L.relief = false;
     L.params.reliefCoarse = nullptr;
   }
@@ -594,7 +595,7 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   L.userGen = nullptr;
   if (sp.userModel >= 0) { // the kernel of the model's own code object
     const UserModel &um = c->userModels[sp.userModel];
-    if (S.stateful && (L.absorb || (L.traceMode != 0 && L.traceMode != 4)))
+    if (S.stateful && (L.absorb || (L.traceMode != MODE_GENERAL && L.traceMode != MODE_SMALL)))
       return fail(c, VR_E_STATE, "stateful particle model: only the general kernels (MODE 0 / 4) carry the state");
     L.userGen = S.stateful ? um.gen[D == 3 ? 1 : 0] : nullptr;
     auto it = um.kernels.find(D * 100 + c->geo.geo * 10 + L.traceMode);
@@ -602,7 +603,7 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
       return fail(c, VR_E_STATE, "run-time particle model: no kernel for this geometry / mode in its code object");
     L.userKernel = it->second;
     int nb = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, L.userKernel, VR_BLOCK, L.traceMode == 4 ? L.params.smallBytes : 0) != hipSuccess)
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, L.userKernel, VR_BLOCK, L.traceMode == MODE_SMALL ? L.params.smallBytes : 0) != hipSuccess)
       nb = 2;
     blocks = std::max(1, nb);
   } else {
@@ -614,7 +615,7 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
   // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of
   // them — about sqrt(rays / 10^5).  10^6 rays: 0.69 -> 0.49 ms (absorbing 0.47 -> 0.31)
-  if (L.traceMode != 4)
+  if (L.traceMode != MODE_SMALL)
     blocks = std::min(blocks, std::max(1, (int)std::lround(std::sqrt((double)c->batchCap / 1e5))));
   L.grid = (unsigned)c->numCUs * (unsigned)K.traceBlocks.value_or(blocks);
   L.looseGrid = 0;
@@ -649,7 +650,7 @@ static int size_scratch(vr_context *c, const ParticleLaunch &L, const PrepareSta
       c->scratchWaves = waves;
     }
   }
-  if (L.relief && L.looseMode == 7) { // the spill queue of the tight general relief kernel
+  if (L.relief && L.looseMode == MODE_RESUME) { // the spill queue of the tight general relief kernel
     // (a record per ray of a batch + the unused end of every wave's last 64-record block)
     VR_HIP(c, c->dSpillRec.ensure_grow(((size_t)c->batchCap + (size_t)L.grid * (VR_BLOCK / 64) * 64u) * 16));
     VR_HIP(c, c->dSpillCount.ensure(1));
@@ -820,7 +821,7 @@ static int fill_trace_params(vr_context *c, const ParticleSpec &sp, ParticleLaun
   return VR_OK;
 }
 
-// height field over the source plane: for particles that go on after a hit ("segments that rise clear", vr_trace.hip)
+// height field over the source plane: for particles that go on after a hit ("segments that rise clear", vr_trace_kernel.hpp)
 static int build_height_field(vr_context *c, const ParticleLaunch &L, PrepareState &S) {
   S.heightField = !L.absorb && c->geo.numPrims && !c->knobs.noHeightField;
   if (!S.heightField)

@@ -581,6 +581,77 @@ __global__ void nb_compact_kernel(SetupParams s) {
 }
 
 // ---------------------------------------------------------------------------
+// exclusive scan (in place), 2048 elements per block: radix-sort digit tables, neighbour offsets
+// ---------------------------------------------------------------------------
+constexpr unsigned SCAN_PER_THREAD = 8;
+constexpr unsigned SCAN_PER_BLOCK = SCAN_PER_THREAD * VR_BLOCK;
+
+__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned *sh, unsigned &total) {
+  const unsigned tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+  unsigned x = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    unsigned y = __shfl_up(x, off, 64);
+    if ((int)lane >= off)
+      x += y;
+  }
+  if (lane == 63)
+    sh[w] = x;
+  __syncthreads();
+  unsigned base = 0;
+  for (unsigned k = 0; k < w; ++k)
+    base += sh[k];
+  total = sh[0] + sh[1] + sh[2] + sh[3];
+  __syncthreads();
+  return base + x - v;
+}
+
+__global__ __launch_bounds__(VR_BLOCK) void scan_block_kernel(unsigned *data, unsigned n, unsigned *blockSums) {
+  __shared__ unsigned sh[4];
+  const unsigned base = blockIdx.x * SCAN_PER_BLOCK + threadIdx.x * SCAN_PER_THREAD;
+  unsigned v[SCAN_PER_THREAD];
+  unsigned sum = 0;
+#pragma unroll
+  for (unsigned k = 0; k < SCAN_PER_THREAD; ++k) {
+    v[k] = base + k < n ? data[base + k] : 0u;
+    sum += v[k];
+  }
+  unsigned total;
+  unsigned ex = block_exclusive_scan(sum, sh, total);
+#pragma unroll
+  for (unsigned k = 0; k < SCAN_PER_THREAD; ++k) {
+    if (base + k < n)
+      data[base + k] = ex;
+    ex += v[k];
+  }
+  if (threadIdx.x == 0 && blockSums)
+    blockSums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(VR_BLOCK) void scan_add_kernel(unsigned *data, unsigned n, const unsigned *blockOffsets) {
+  const unsigned off = blockOffsets[blockIdx.x];
+  const unsigned base = blockIdx.x * SCAN_PER_BLOCK + threadIdx.x * SCAN_PER_THREAD;
+#pragma unroll
+  for (unsigned k = 0; k < SCAN_PER_THREAD; ++k)
+    if (base + k < n)
+      data[base + k] += off;
+}
+
+hipError_t launch_scan(unsigned *data, unsigned n, unsigned *tmp /* >= 2 * ceil(n/2048) + 2 */, hipStream_t s) {
+  const unsigned blocks = (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
+  if (blocks <= 1) {
+    hipLaunchKernelGGL(scan_block_kernel, dim3(1), dim3(VR_BLOCK), 0, s, data, n, (unsigned *)nullptr);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(scan_block_kernel, dim3(blocks), dim3(VR_BLOCK), 0, s, data, n, tmp);
+  hipError_t e = launch_scan(tmp, blocks, tmp + blocks, s);
+  if (e != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(scan_add_kernel, dim3(blocks), dim3(VR_BLOCK), 0, s, data, n, tmp);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 hipError_t launch_setup_bvh(const SetupParams &sp, unsigned *scanTmp, hipStream_t st) {
   SetupParams s = sp;
   const unsigned n = s.n;
@@ -864,6 +935,40 @@ hipError_t launch_flux_from_acc(const unsigned long long *acc, unsigned n, float
   if (n == 0)
     return hipSuccess;
   hipLaunchKernelGGL(flux_from_acc_kernel, dim3((n + 255) / 256), dim3(256), 0, st, acc, n, flux);
+  return hipGetLastError();
+}
+
+// un-permute the leaf-ordered accumulators into the caller's primitive order.
+// Overflow is DETECTED, never silent: the accumulators are 64-bit fixed point (2^-40 per unit), summed over the replicas
+// here and — as SIGNED int64 — over the ranks of a multi-GPU apply afterwards.  A primitive's sum must therefore stay
+// below 2^(63 - headroomBits) (headroomBits = ceil(log2(ranks))): a replica with its top bit set, a carry out of the
+// replica sum or a sum at or beyond that bound raises *overflowFlag, and vr_apply_finish fails the apply.
+__global__ void gather_flux_kernel(const unsigned long long *acc, unsigned stride, unsigned replicas,
+                                   const unsigned *leafOfOrig, unsigned n, unsigned long long *outAcc, unsigned headroomBits,
+                                   unsigned long long *overflowFlag) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const unsigned q = leafOfOrig[i];
+    unsigned long long s = 0; // (integer sum: replica order is irrelevant)
+    bool bad = false;
+    for (unsigned r = 0; r < replicas; ++r) {
+      const unsigned long long v = acc[(size_t)r * stride + q];
+      bad = bad || (v >> 63) != 0ull;
+      s += v;
+      bad = bad || s < v; // carry out of 64 bits
+    }
+    bad = bad || (s >> (63u - headroomBits)) != 0ull;
+    outAcc[i] = s;
+    if (bad)
+      *overflowFlag = 1ull;
+  }
+}
+
+hipError_t launch_gather_flux(const unsigned long long *acc, unsigned stride, unsigned replicas,
+                              const unsigned *leafOfOrig, unsigned n, unsigned long long *outAcc, unsigned headroomBits,
+                              unsigned long long *overflowFlag, hipStream_t s) {
+  hipLaunchKernelGGL(gather_flux_kernel, dim3((n + 255) / 256), dim3(256), 0, s, acc, stride, replicas, leafOfOrig, n,
+                     outAcc, headroomBits, overflowFlag);
   return hipGetLastError();
 }
 

@@ -53,7 +53,7 @@ constexpr unsigned VR_STACK_GLOBAL = 48;
 #endif
 constexpr int VR_STACK_LDS = VR_STACK_LDS_ENTRIES;
 // scenes of a few hundred primitives (2-D simulations) live in LDS as a whole — pair nodes, primitive records,
-// neighbourhood, flux accumulators: trace_kernel MODE 4 stages up to this many bytes per block (dynamic LDS)
+// neighbourhood, flux accumulators: trace_kernel MODE_SMALL stages up to this many bytes per block (dynamic LDS)
 constexpr int VR_RELIEF_STEPS = 16; // tiles relief_clip walks under one ray before it falls back to the scene box's exit
 constexpr unsigned VR_SMALL_LDS = 25600; // (up to 17.5 KB: five blocks per CU; up to this: four, still ahead of the HBM path)
 constexpr int VR_SMALL_STACK = 6; // LDS stack entries of that kernel (its trees are shallow)
@@ -139,7 +139,7 @@ struct TraceParams {
   uint32_t debugFlags;            // VR_DEBUG_FLAGS (timing experiments; 0 in production)
   // ---- round 3 (appended: the kernels' scalar loads of the fields above keep their offsets and alignment — the
   //      absorbing kernels sit at a fragile optimum of the register allocator) ----
-  uint32_t numQueues;              // 1, or 8: one queue of sort bins per XCD (vr_trace.hip, refill)
+  uint32_t numQueues;              // 1, or 8: one queue of sort bins per XCD (vr_trace_kernel.hpp, refill)
   const float *recExtra;           // [batchCount] x {origin[rayDir], bits(k), s[k] lo, hi} for the sources whose origin plane or
                                    // draw count varies (tilted, grid, host rays); nullptr for the plain SourceRandom generator
   const float *hostWeights;        // Source::getInitialRayWeight(idx) of a host-callback source (nullptr: 1, raySource.hpp:18)
@@ -165,7 +165,7 @@ struct TraceParams {
   // was not finished inside the round of its packet query — leaves the kernel as a 64-byte full-state record
   //   {org.xyz, weight} {rayDirection.xyz, bits(seed)} {bits(k), bits(reflections), bits(boundaryHits | back << 31), 0 (~0: no ray)}
   //   {s[k] lo, hi, s[k+156] lo, hi}
-  // in blocks of 64 records (VR_SPILL_BLOCK, vr_trace.hip), one wave per block: a wave reserves a block with ONE atomic
+  // in blocks of 64 records (VR_SPILL_BLOCK, vr_trace_kernel.hpp), one wave per block: a wave reserves a block with ONE atomic
   // on spillCount and fills it over its next rounds; the unused end of a wave's last block is marked empty
   // and the launch over the loose bins (MODE 7 = MODE 0 + these records) traces it to its end: the tight kernel's waves
   // then hold fresh, sorted primary rays only, whose packet queries stay small.
@@ -176,7 +176,7 @@ struct TraceParams {
   float pqMargin;                  // flat-scene kernels: a packet query searches the 64-ary tree with its box enlarged by this
                                    // much, and the frontier it finds serves the following rounds whose boxes lie inside (0: off)
   // ---- surface source (appended; gpu/raygSource.hpp:65-81, gpu/raygTrace.hpp:267-297): ray idx leaves source point
-  //      idx / surfRays along a cosine distribution about that point's normal (vr_trace.hip: surface_sample).  Its start
+  //      idx / surfRays along a cosine distribution about that point's normal (vr_generate.hpp: surface_sample).  Its start
   //      weight is the POINT's: the generator writes it to hostWeights[global ray index], a buffer of one batch then.
   const float *surfPos, *surfNrm;  // [points] x 3: positions, normals (any non-zero length); nullptr: no surface source
   const float *surfWeights;        // [points]
@@ -184,7 +184,7 @@ struct TraceParams {
   float surfOffset;                // origin = position + unit normal * surfOffset
 };
 
-// What a run-time SOURCE model (vr_register_source_model; vr_trace.hip, the source-module section) sees of the launch:
+// What a run-time SOURCE model (vr_register_source_model; vr_modules.hpp, the source-module section) sees of the launch:
 // the second argument of its generator, by value.  The library's own kernels never take it: TraceParams stays as it is.
 constexpr int VR_SOURCE_PARAMS = 16;
 struct SourceCtx {
@@ -279,6 +279,26 @@ enum { P_DIFFUSE = 0, P_SPECULAR = 1, P_CONED_COSINE = 2, P_DIFFUSE_COSINE = 3, 
        P_EXT_FULL = 3 /* ... with the coned-cosine model, WDIST crediting and mean-free-path scattering compiled in
                          (rare options that cost every particle of the instantiation registers: 157 spilled VGPRs
                          with them, 27 without) */ };
+
+// The modes of trace_kernel (its template parameter MODE_, an int: a module's kernels are found by mangled name;
+// vr_get_trace_mode reports these numbers).  vr_prepare.cpp chooses one per launch, vr_trace.hip maps it to a kernel.
+enum TraceMode : int {
+  MODE_GENERAL = 0,        // the general kernel: any scene, any particle; per-lane ordered walks with straggler carry-over
+  MODE_ABSORB_FLAT = 1,    // absorbing particle (sticking >= 1 everywhere), flat scene: the packet query carries the load
+  MODE_ABSORB = 2,         // absorbing particle, structured scene: most rounds end in per-lane walks, carry-over on
+  MODE_GENERAL_FLAT = 3,   // MODE_GENERAL for a flat scene of disks: the packet query's wave-uniform crediting, follow-up
+                           // segments inside the round, one queue of bins per XCD
+  MODE_SMALL = 4,          // MODE_GENERAL for scenes of a few hundred primitives (2-D simulations): pair nodes, primitive
+                           // records, neighbourhood and flux accumulators are staged in LDS (VR_SMALL_LDS bytes per block)
+                           // and every access of the round but the ray records stays there; no packets
+  MODE_ABSORB_RELIEF = 5,  // MODE_ABSORB_FLAT / MODE_GENERAL_FLAT for the tight bins of a scene that is flat WITH RELIEF:
+  MODE_GENERAL_RELIEF = 6, // the packet query clips its rays to the local relief (relief_clip, vr_device.hpp), not to the
+                           // scene box; the generator has filed the grazing rays in loose bins, which a MODE_ABSORB /
+                           // MODE_GENERAL launch of their own traces.  MODE_GENERAL_RELIEF spills the rays that go on
+  MODE_RESUME = 7          // MODE_GENERAL over those loose bins that also resumes the rays of MODE_GENERAL_RELIEF's spill
+                           // queue (TraceParams::spillRec)
+};
+// (MODE_GENERAL_FLAT, MODE_GENERAL_RELIEF and MODE_RESUME exist for disks and the lean particles only: otherwise MODE_GENERAL)
 
 // counters[] slots: every particle of an apply has one block of C_BLOCK words (TraceParams::counters points at it)
 enum {
