@@ -59,7 +59,7 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   p.numBins = nbBatch;
   // a surface source has no sort bins: its records lie in index order in the overflow region (gen_surface_kernel),
   // which the trace kernel reads as virtual bins of binCap rays
-  const bool unbinned = p.surfPos != nullptr;
+  const bool unbinned = L.gen == GEN_SURFACE;
   if (L.genWeights) // the batch's start weights, addressed by GLOBAL ray index like a host source's (gen_surface_kernel / a source model's generator writes them)
     p.hostWeights = c->dSurfRayWeights.p - first;
   if (unbinned)
@@ -115,7 +115,7 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
     const unsigned grid = std::min<unsigned>((count + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
     VR_HIP(c, hipModuleLaunchKernel(G.userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
   } else {
-    VR_HIP(c, launch_gen(pg, c->geo.D, keepRng, (unsigned)c->numCUs * 8u, c->stream));
+    VR_HIP(c, launch_gen(pg, G.gen, c->geo.D, keepRng, (unsigned)c->numCUs * 8u, c->stream));
   }
   VR_HIP(c, hipEventRecord(g1, c->stream));
   ++genNo;

@@ -14,6 +14,7 @@
 #include "../../include/viennaray_amd.h"
 #include "vr_host.hpp"
 #include "vr_kernels.hpp"
+#include "vr_source.hpp"
 #include "vr_types.hpp"
 
 namespace vr {
@@ -181,8 +182,9 @@ struct ParticleLaunch {
   bool absorb = false;
   bool recExtra = false; // the records' side array (TraceParams::recExtra)
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
-  hipFunction_t userGen = nullptr;    // ... and a stateful model's generator (nullptr: the library's)
-  bool userSource = false;            // userGen is a source model's generator: it takes `source` as its second argument
+  Generator gen = GEN_RANDOM;         // the generator of the launch, by the source in force (fill_trace_params)
+  hipFunction_t userGen = nullptr;    // a module's generator that runs instead: a stateful model's (init, then the sample of
+                                      // `gen`), or the source model's where gen == GEN_SOURCE_MODEL (nullptr: the library's `gen`)
   bool genWeights = false;            // the generator writes the batch's start weights (surface source, source model with kHasWeight)
   SourceCtx source{};                 // what the source model sees of this launch
   DevBuf<float> primSticking;         // this particle's per-primitive sticking, leaf order (params.primSticking, or unused)
@@ -267,33 +269,18 @@ struct vr_context {
         return true;
     return false;
   }
-  // sources other than SourceRandom
-  std::vector<float> gridPoints;  // SourceGrid origins (raySourceGrid.hpp)
-  std::vector<float> hostOrg, hostDir;
-  std::vector<uint32_t> hostDraws;
-  std::vector<float> hostWeights;  // Source::getInitialRayWeight(idx) of the host rays (empty: 1)
+  // the ray source in force (vr_source.hpp) and the device buffers of the sources, which are kept across switches
+  RaySource src;
   float sourceAreaOverride = 0.f;  // Source::getSourceArea() of a user source (<= 0: SourceRandom's, the bbox face)
-  // surface source (vr_set_surface_source): the tables live on the device, uploaded when they are set
-  uint32_t surfCount = 0;          // source points (0: no surface source)
-  float surfArea = 0.f, surfOffset = 0.f;
-  DevBuf<float> dSurfPos, dSurfNrm, dSurfWeights;
+  DevBuf<float> dSurfPos, dSurfNrm, dSurfWeights;       // a surface source's tables, uploaded when they are set
   DevBuf<float> dSurfPosIn, dSurfNrmIn, dSurfWeightsIn; // vr_set_surface_source_device packs into these; accepted: swapped in
   DevBuf<unsigned long long> dSurfBad;                  // ... and its one word of validation
-  DevBuf<float> dSurfRayWeights;   // start weight of every ray of one batch (TraceParams::hostWeights of a surface source)
-  // source model (vr_set_source_model): sampled on the device by its own generator; the table lives on the device
-  std::vector<SourceModel> sourceModels;
-  int32_t sourceModel = -1;        // index of the model in force (< 0: none)
-  float srcParams[VR_SOURCE_PARAMS] = {0};
-  uint32_t srcTableCount = 0;
-  DevBuf<float> dSrcTable;
-  uint64_t srcNumRays = 0;         // its own ray count (0: numRaysPerPoint / numRaysFixed over the primitives)
-  bool sourceModelWeights() const { return sourceModel >= 0 && sourceModels[sourceModel].hasWeight; }
-  // host rays, or a source model: the launch configuration is the same (records with a side array, any origin and draw count)
-  bool hostLikeSource() const { return !hostOrg.empty() || sourceModel >= 0; }
-  uint64_t reserveRays = 0;        // vr_reserve_rays: the ray-stream buffers hold at least this many rays
-  bool sourceDirty = false;
-  DevBuf<float> dGrid, dHostOrg, dHostDir, dHostWeights;
+  DevBuf<float> dSurfRayWeights;   // start weight of every ray of one batch (TraceParams::hostWeights where the generator writes them)
+  std::vector<SourceModel> sourceModels; // vr_register_source_model
+  DevBuf<float> dSrcTable;         // the table of the source model in force
+  DevBuf<float> dGrid, dHostOrg, dHostDir, dHostWeights; // a grid's / the host rays' arrays, uploaded at prepare (upload_source_data)
   DevBuf<uint32_t> dHostDraws;
+  uint64_t reserveRays = 0;        // vr_reserve_rays: the ray-stream buffers hold at least this many rays
   uint64_t numRaysPerPoint = 1000, numRaysFixed = 0;
   uint32_t maxReflections = 0xFFFFFFFFu, maxBoundaryHits = 1000;
   uint32_t rngSeed = 0;
@@ -427,12 +414,15 @@ int build_scene(vr_context *c);
 int ensure_device_material_ids(vr_context *c);
 int lay_global_rows(vr_context *c, uint32_t rows, uint32_t stride);
 // vr_prepare.cpp
-uint64_t rays_of_apply(const vr_context *c);
 void size_bins(int D, uint64_t count, uint32_t perBin, TraceParams &p, uint32_t &numBins);
 void size_loose(int D, TraceParams &p);
 // vr_apply.cpp
 const ParticleLaunch &current_launch(const vr_context *c);
 TraceParams launch_params(const vr_context *c, const ParticleLaunch &L);
+
+inline uint64_t rays_of_apply(const vr_context *c) {
+  return c->src.rays_of_apply(c->geo.numPrims, c->numRaysPerPoint, c->numRaysFixed);
+}
 
 // head-room bits of the overflow checks: the sums of `worldSize` ranks (vr_set_world_size) must still fit a signed int64
 inline unsigned rank_headroom(uint32_t worldSize) {

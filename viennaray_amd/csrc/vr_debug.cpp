@@ -74,23 +74,24 @@ int vr_debug_process_hit(vr_context *c, const float *org, const float *dir, cons
 int vr_debug_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, uint32_t seed, float *org, float *dir) {
   if (!c || !idx || !org || !dir)
     return VR_E_INVALID;
-  if (c->sourceModel >= 0)
+  if (c->src.kind == SourceKind::Model)
     return fail(c, VR_E_STATE, "vr_debug_source_sample: a source model is set: its sample is vr_debug_user_source_sample's");
   VR_TRY(ensure_prepared(c));
   if (n > c->slotStride)
     return fail(c, VR_E_INVALID, "vr_debug_source_sample: more rays than one batch holds");
-  if (c->surfCount) // (the surface generator looks its point up by the index)
+  if (c->src.kind == SourceKind::Surface) // (the surface generator looks its point up by the index)
     for (uint32_t i = 0; i < n; ++i)
       if (idx[i] >= rays_of_apply(c))
         return fail(c, VR_E_INVALID, "vr_debug_source_sample: ray index beyond the surface source's ray count");
-  TraceParams p = launch_params(c, current_launch(c));
+  const ParticleLaunch &L = current_launch(c);
+  TraceParams p = launch_params(c, L);
   p.seed = seed;
   p.batchCount = n;
   p.binCount = nullptr; // no binning: record i goes to slot i
   DevBuf<unsigned long long> dI;
   VR_HIP(c, dI.upload((const unsigned long long *)idx, n));
   p.idxList = dI.p;
-  VR_HIP(c, launch_gen(p, c->geo.D, false, (unsigned)c->numCUs * 8u, c->stream));
+  VR_HIP(c, launch_gen(p, L.gen, c->geo.D, false, (unsigned)c->numCUs * 8u, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   std::vector<float> A((size_t)n * 8);
   VR_HIP(c, c->dSlotRec.download(A.data(), (size_t)n * 8));
@@ -112,7 +113,7 @@ int vr_debug_surface_source_sample(vr_context *c, const uint64_t *idx, uint32_t 
                                    float *weight, uint32_t *draws) {
   if (!c || !idx || !org || !dir || !weight || !draws)
     return VR_E_INVALID;
-  if (!c->surfCount)
+  if (c->src.kind != SourceKind::Surface)
     return fail(c, VR_E_STATE, "vr_debug_surface_source_sample: no surface source is set");
   VR_TRY(ensure_prepared(c));
   const uint64_t total = rays_of_apply(c);
@@ -149,7 +150,7 @@ int vr_debug_user_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, 
                                 float *weight, uint32_t *draws) {
   if (!c || !idx || !org || !dir || !weight || !draws)
     return VR_E_INVALID;
-  if (c->sourceModel < 0)
+  if (c->src.kind != SourceKind::Model)
     return fail(c, VR_E_STATE, "vr_debug_user_source_sample: no source model is set");
   VR_TRY(ensure_prepared(c));
   if (n == 0)
@@ -171,7 +172,7 @@ int vr_debug_user_source_sample(vr_context *c, const uint64_t *idx, uint32_t n, 
   void *args[] = {&p, &sc, &dO.p, &dD.p, &dW.p, &dK.p};
   // (the grid bound of the generators: the RNG slabs are sized for it, size_scratch)
   const unsigned grid = std::min<unsigned>((n + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
-  VR_HIP(c, hipModuleLaunchKernel(c->sourceModels[c->sourceModel].debug[c->geo.D == 3 ? 1 : 0], grid, 1, 1, VR_BLOCK, 1, 1, 0,
+  VR_HIP(c, hipModuleLaunchKernel(c->sourceModels[c->src.sourceModel].debug[c->geo.D == 3 ? 1 : 0], grid, 1, 1, VR_BLOCK, 1, 1, 0,
                                   c->stream, args, nullptr));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   VR_HIP(c, dO.download(org, (size_t)n * 3));
@@ -189,7 +190,7 @@ int vr_debug_model_source_sample(vr_context *c, const uint64_t *idx, uint32_t n,
     return VR_E_INVALID;
   VR_TRY(ensure_prepared(c));
   const ParticleLaunch &L = current_launch(c);
-  if (c->specs.size() > 1 || !L.userGen || L.userSource)
+  if (c->specs.size() > 1 || !L.userGen || L.gen == GEN_SOURCE_MODEL)
     return fail(c, VR_E_STATE, "vr_debug_model_source_sample: the active particle is not (the only) stateful model");
   if (n > c->batchCap)
     return fail(c, VR_E_INVALID, "vr_debug_model_source_sample: more rays than one batch holds");

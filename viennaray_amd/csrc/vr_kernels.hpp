@@ -7,8 +7,8 @@
 
 namespace vr {
 
-// generators and trace kernels (vr_trace.hip); mode: a TraceMode (vr_types.hpp)
-hipError_t launch_gen(const TraceParams &p, int D, bool keepRng, unsigned maxBlocks, hipStream_t s);
+// generators and trace kernels (vr_trace.hip); gen: one of the library's generators, mode: a TraceMode (vr_types.hpp)
+hipError_t launch_gen(const TraceParams &p, Generator gen, int D, bool keepRng, unsigned maxBlocks, hipStream_t s);
 hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid,
                         hipStream_t s);
 // resident 256-thread blocks per CU of the trace kernel instantiation (occupancy API)

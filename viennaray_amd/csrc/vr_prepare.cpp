@@ -20,23 +20,6 @@ static int effective_direction(const vr_context *c) {
   return c->geo.D == 2 ? VR_POS_Y : VR_POS_Z; // rayTrace.hpp:166-167
 }
 
-// rays per point of a surface source (gpu/raygTrace.hpp:134-149: the fixed count, if set, is the launch's x extent)
-static uint64_t surface_rays_per_point(const vr_context *c) { return c->numRaysFixed ? c->numRaysFixed : c->numRaysPerPoint; }
-
-// rayTraceKernel.hpp:57-61: numRaysFixed, or source.getNumPoints() * numRaysPerPoint
-// (SourceRandom: the geometry's points; SourceGrid: the grid's; host rays: exactly those given; a source model: its own
-//  count if it has one, else SourceRandom's)
-uint64_t rays_of_apply(const vr_context *c) {
-  if (c->surfCount)
-    return (uint64_t)c->surfCount * surface_rays_per_point(c);
-  if (c->sourceModel >= 0 && c->srcNumRays)
-    return c->srcNumRays;
-  if (!c->hostOrg.empty())
-    return c->hostOrg.size() / 3;
-  const uint64_t srcPoints = !c->gridPoints.empty() ? c->gridPoints.size() / 3 : c->geo.numPrims;
-  return c->numRaysFixed == 0 ? srcPoints * c->numRaysPerPoint : c->numRaysFixed;
-}
-
 // ---- apply() set-up: prepare_one and its stages ------------------------------------------------------------------
 
 // what the stages of one prepare_one hand on to each other
@@ -134,7 +117,7 @@ static int check_settings(vr_context *c) {
   if (c->geo.geo == 0 && c->geo.diskRadius > c->geo.gridDelta)
     c->info.warning = 1;
   // (a surface source divides the ray index by the rays per point in 32 bits: the index is tea3's 32-bit input anyway)
-  if (c->surfCount && rays_of_apply(c) > 0xFFFFFFFFull) {
+  if (c->src.kind == SourceKind::Surface && rays_of_apply(c) > 0xFFFFFFFFull) {
     c->info.error = 1;
     return fail(c, VR_E_INVALID, "surface source: points x rays per point exceeds the 32-bit ray index of one apply");
   }
@@ -340,7 +323,7 @@ static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, Particl
   const bool extended = sp.kernelKind >= VR_PARTICLE_CONED_COSINE || c->useWdist || sp.meanFreePath > 0.f;
   if (extended)
     L.absorb = false;
-  if ((!c->hostOrg.empty() && !c->hostWeights.empty()) || c->surfCount || c->sourceModelWeights())
+  if (c->src.rays_start_weighted())
     L.absorb = false; // (the absorbing kernels credit unit weights)
   // (the rare, register-hungry options — coned-cosine model, WDIST crediting, mean free path — have an instantiation
   //  of their own: multi-label and per-material particles should not pay for them)
@@ -351,7 +334,7 @@ static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, Particl
       return fail(c, VR_E_INVALID, "this particle model was registered without VR_MODEL_NEEDS_FULL: its code object has no "
                                    "kernel with WDIST crediting / mean-free-path scattering");
     extFull = um->needsFull;
-    if (um->numState > 0 && (!c->gridPoints.empty() || c->hostLikeSource() || c->surfCount))
+    if (um->numState > 0 && !c->src.admits_stateful_model())
       return fail(c, VR_E_INVALID, "a stateful particle model (numState > 0) runs its init on the device before the source "
                                    "sample: SourceRandom only (plain or with a primary direction), not SourceGrid, a host "
                                    "source, a surface source or a source model");
@@ -401,7 +384,7 @@ static int build_relief_field(vr_context *c, const ParticleSpec &sp, ParticleLau
   const float travel = K.reliefTravel;
   L.relief = false;
   const float thickScene = c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]];
-  const bool plainSource = !c->usePrimaryDirection && c->gridPoints.empty() && !c->hostLikeSource() && !c->surfCount;
+  const bool plainSource = c->src.is_plain(c->usePrimaryDirection);
   const bool kernelOk = L.absorb || (c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT);
   const bool want = !S.flatScene && !S.smallScene && plainSource && kernelOk && sp.userModel < 0 && c->geo.gridDelta > 0.f &&
                     thickScene <= K.reliefMaxThick * c->geo.gridDelta && !K.noRelief;
@@ -481,27 +464,22 @@ static int ensure_accumulators(vr_context *c) {
   return VR_OK;
 }
 
-// sources other than SourceRandom: SourceGrid origins, host rays (+ draw counts, weights)
+// the sources whose payload comes up from the host: SourceGrid origins, host rays (+ draw counts, weights)
 static int upload_source_data(vr_context *c) {
-  if (!c->gridPoints.empty()) {
-    VR_HIP(c, c->dGrid.ensure(c->gridPoints.size()));
-    VR_HIP(c, hipMemcpy(c->dGrid.p, c->gridPoints.data(), c->gridPoints.size() * 4, hipMemcpyHostToDevice));
+  RaySource &src = c->src;
+  if (src.kind == SourceKind::Grid)
+    VR_HIP(c, c->dGrid.upload(src.gridPoints.data(), src.gridPoints.size()));
+  if (src.kind == SourceKind::HostRays) {
+    VR_HIP(c, c->dHostOrg.ensure(src.hostOrg.size()));
+    VR_HIP(c, c->dHostDir.ensure(src.hostDir.size()));
+    VR_HIP(c, hipMemcpy(c->dHostOrg.p, src.hostOrg.data(), src.hostOrg.size() * 4, hipMemcpyHostToDevice));
+    VR_HIP(c, hipMemcpy(c->dHostDir.p, src.hostDir.data(), src.hostDir.size() * 4, hipMemcpyHostToDevice));
+    if (!src.hostDraws.empty())
+      VR_HIP(c, c->dHostDraws.upload(src.hostDraws.data(), src.hostDraws.size()));
+    if (!src.hostWeights.empty())
+      VR_HIP(c, c->dHostWeights.upload(src.hostWeights.data(), src.hostWeights.size()));
   }
-  if (!c->hostOrg.empty()) {
-    VR_HIP(c, c->dHostOrg.ensure(c->hostOrg.size()));
-    VR_HIP(c, c->dHostDir.ensure(c->hostDir.size()));
-    VR_HIP(c, hipMemcpy(c->dHostOrg.p, c->hostOrg.data(), c->hostOrg.size() * 4, hipMemcpyHostToDevice));
-    VR_HIP(c, hipMemcpy(c->dHostDir.p, c->hostDir.data(), c->hostDir.size() * 4, hipMemcpyHostToDevice));
-    if (!c->hostDraws.empty()) {
-      VR_HIP(c, c->dHostDraws.ensure(c->hostDraws.size()));
-      VR_HIP(c, hipMemcpy(c->dHostDraws.p, c->hostDraws.data(), c->hostDraws.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (!c->hostWeights.empty()) {
-      VR_HIP(c, c->dHostWeights.ensure(c->hostWeights.size()));
-      VR_HIP(c, hipMemcpy(c->dHostWeights.p, c->hostWeights.data(), c->hostWeights.size() * 4, hipMemcpyHostToDevice));
-    }
-  }
-  c->sourceDirty = false;
+  src.sourceDirty = false;
   return VR_OK;
 }
 
@@ -537,10 +515,10 @@ static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState 
   // 32-byte records for every particle (vr_types.hpp); a non-absorbing particle under a source whose origin plane or
   // draw count varies (tilted, grid, host rays) adds 16 bytes per ray in a side array
   // (a stateful model's init draws before the source sample: its draw count varies too)
-  L.recExtra = !L.absorb && (c->usePrimaryDirection || !c->gridPoints.empty() || c->hostLikeSource() || c->surfCount || S.stateful);
+  L.recExtra = c->src.records_carry_side_array(c->usePrimaryDirection, S.stateful, L.absorb);
   if (L.recExtra)
     VR_HIP(c, c->dRecExtra.ensure_grow((size_t)c->batchCap * 4));
-  L.genWeights = c->surfCount || c->sourceModelWeights(); // (the generator writes the batch's start weights)
+  L.genWeights = c->src.generator_writes_weights();
   if (L.genWeights)
     VR_HIP(c, c->dSurfRayWeights.ensure_grow(c->batchCap));
   if (S.stateful) // (the state of every ray of a batch, float4 per ray; room for vr_reserve_rays' largest batch)
@@ -609,9 +587,6 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   } else {
     blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.traceMode, L.params.smallBytes));
   }
-  L.userSource = c->sourceModel >= 0;
-  if (L.userSource) // the generator of the source model's code object, records without / with the RNG cursors
-    L.userGen = c->sourceModels[c->sourceModel].gen[D == 3 ? 1 : 0][L.absorb ? 0 : 1];
   // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
   // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of
   // them — about sqrt(rays / 10^5).  10^6 rays: 0.69 -> 0.49 ms (absorbing 0.47 -> 0.31)
@@ -643,7 +618,7 @@ static int size_scratch(vr_context *c, const ParticleLaunch &L, const PrepareSta
     size_t waves = 0;
     if (!L.absorb)
       waves = (size_t)std::max(L.grid, L.looseGrid) * (VR_BLOCK / 64);
-    if (c->usePrimaryDirection || c->hostLikeSource() || S.stateful)
+    if (c->src.generator_draws_past_tier1(c->usePrimaryDirection, S.stateful))
       waves = std::max(waves, (size_t)c->numCUs * 8u * (VR_BLOCK / 64)); // launch_gen's grid bound (gen_state_kernel's and gen_user_source_kernel's too)
     if (waves > c->scratchWaves) {
       VR_HIP(c, c->dScratch.ensure(waves * 312u * 64u));
@@ -714,25 +689,41 @@ static int fill_trace_params(vr_context *c, const ParticleSpec &sp, ParticleLaun
   p.globalStride = c->globalStride;
   p.numGlobalScalars = (uint32_t)c->globalScalars.size();
   p.useWdist = c->useWdist ? 1 : 0;
-  p.gridPoints = c->gridPoints.empty() ? nullptr : c->dGrid.p;
-  p.gridCount = (uint32_t)(c->gridPoints.size() / 3);
+  // the source fields: every pointer of a kind that is not in force is null
+  p.gridPoints = nullptr;
+  p.gridCount = 0;
   p.eeGrid = 2.f / (sp.sourcePower + 1); // raySourceGrid.hpp:22
-  p.hostOrg = c->hostOrg.empty() ? nullptr : c->dHostOrg.p;
-  p.hostDir = c->hostOrg.empty() ? nullptr : c->dHostDir.p;
-  p.hostDraws = c->hostDraws.empty() ? nullptr : c->dHostDraws.p;
-  p.hostWeights = (c->hostOrg.empty() || c->hostWeights.empty()) ? nullptr : c->dHostWeights.p;
+  p.hostOrg = p.hostDir = nullptr;
+  p.hostDraws = nullptr;
+  p.hostWeights = nullptr;
   p.surfPos = p.surfNrm = p.surfWeights = nullptr;
   p.surfRays = 0;
   p.surfOffset = 0.f;
-  if (c->surfCount) { // (hostWeights: the batch's start weights, written by the generator — batch_params)
+  L.source = SourceCtx{};
+  L.gen = c->src.generator(c->usePrimaryDirection);
+  const RaySource &src = c->src;
+  switch (src.kind) {
+  case SourceKind::Random: break;
+  case SourceKind::Grid:
+    p.gridPoints = c->dGrid.p;
+    p.gridCount = (uint32_t)(src.gridPoints.size() / 3);
+    break;
+  case SourceKind::HostRays:
+    p.hostOrg = c->dHostOrg.p;
+    p.hostDir = c->dHostDir.p;
+    p.hostDraws = src.hostDraws.empty() ? nullptr : c->dHostDraws.p;
+    p.hostWeights = src.hostWeights.empty() ? nullptr : c->dHostWeights.p;
+    break;
+  case SourceKind::Surface: // (hostWeights: the batch's start weights, written by the generator — batch_params)
     p.surfPos = c->dSurfPos.p;
     p.surfNrm = c->dSurfNrm.p;
     p.surfWeights = c->dSurfWeights.p;
-    p.surfRays = (uint32_t)surface_rays_per_point(c);
-    p.surfOffset = c->surfOffset;
-  }
-  L.source = SourceCtx{};
-  if (L.userSource) { // what the source model sees (its table's address as it is now: a later setter clears `prepared`)
+    p.surfRays = (uint32_t)RaySource::rays_per_surface_point(c->numRaysPerPoint, c->numRaysFixed);
+    p.surfOffset = src.surfOffset;
+    break;
+  case SourceKind::Model: { // the generator of the model's code object, records without / with the RNG cursors, and what
+                            // it sees (its table's address as it is now: a later setter clears `prepared`)
+    L.userGen = c->sourceModels[src.sourceModel].gen[c->geo.D == 3 ? 1 : 0][L.absorb ? 0 : 1];
     SourceCtx &sc = L.source;
     for (int k = 0; k < 3; ++k) {
       sc.bbLo[k] = c->bbLo[k];
@@ -745,9 +736,11 @@ static int fill_trace_params(vr_context *c, const ParticleSpec &sp, ParticleLaun
     sc.posNeg = (float)c->ts[4];
     sc.gridDelta = c->geo.gridDelta;
     sc.sourcePower = sp.sourcePower;
-    sc.tableCount = c->srcTableCount;
-    sc.table = c->srcTableCount ? c->dSrcTable.p : nullptr;
-    std::memcpy(sc.params, c->srcParams, sizeof(sc.params));
+    sc.tableCount = src.srcTableCount;
+    sc.table = src.srcTableCount ? c->dSrcTable.p : nullptr;
+    std::memcpy(sc.params, src.srcParams, sizeof(sc.params));
+    break;
+  }
   }
   p.accMask = c->accReplicas - 1u;
   VR_HIP(c, c->dCounters.ensure(C_BLOCK * c->launches.size()));
@@ -960,7 +953,7 @@ static int prepare_one(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L)
   VR_TRY(choose_particle_kernel(c, sp, L, S));
   VR_TRY(build_relief_field(c, sp, L, S));
   VR_TRY(ensure_accumulators(c));
-  if (c->sourceDirty)
+  if (c->src.sourceDirty)
     VR_TRY(upload_source_data(c));
   VR_TRY(size_ray_stream(c, L, S));
   VR_TRY(choose_trace_mode(c, sp, L, S)); // (after the ray stream: blocks follow the batch size; the buffers keep the relief layout)

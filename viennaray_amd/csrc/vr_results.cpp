@@ -12,8 +12,8 @@ static_assert(VR_LOG_SCALE == (double)(1ull << VR_LOG_FRAC_BITS), "the kernels' 
 // Source::getSourceArea(): a surface source's own (gpu/raygTraceDisk.hpp:90-91), a user source's override, else
 // SourceRandom's — the source face of the bounding box
 static float effective_source_area(const vr_context *c) {
-  if (c->surfCount)
-    return c->surfArea;
+  if (c->src.kind == SourceKind::Surface)
+    return c->src.surfArea;
   return c->sourceAreaOverride > 0.f ? c->sourceAreaOverride : c->sourceArea;
 }
 

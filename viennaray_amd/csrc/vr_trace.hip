@@ -48,10 +48,10 @@ namespace vr {
 // every generator and every trace kernel of the library: a kernel over the launch's TraceParams
 using StreamKernel = void (*)(const TraceParams);
 
-// source: SourceRandom (0: axis-aligned, 1: tilted primary direction), SourceGrid (2), host rays (3), surface source (4)
-static StreamKernel gen_kernel_for(int source, int D, bool keepRng, bool relief) {
+// source: one of the library's five generators (enum Generator, vr_types.hpp)
+static StreamKernel gen_kernel_for(Generator source, int D, bool keepRng, bool relief) {
   const int v = (D == 2 ? 0 : 2) + (keepRng ? 1 : 0); // 2-D / 3-D, records without / with the RNG cursors
-  if (source == 0 && relief) { // the plain generator on a scene with relief: predicted-hit key, loose bins
+  if (source == GEN_RANDOM && relief) { // the plain generator on a scene with relief: predicted-hit key, loose bins
     static const StreamKernel reliefGen[4] = {gen_kernel<2, false, true>, gen_kernel<2, true, true>, gen_kernel<3, false, true>,
                                               gen_kernel<3, true, true>};
     return reliefGen[v];
@@ -64,14 +64,15 @@ static StreamKernel gen_kernel_for(int source, int D, bool keepRng, bool relief)
   return gen[v][source];
 }
 
-hipError_t launch_gen(const TraceParams &p, int D, bool keepRng, unsigned maxBlocks, hipStream_t s) {
+hipError_t launch_gen(const TraceParams &p, Generator gen, int D, bool keepRng, unsigned maxBlocks, hipStream_t s) {
+  if (gen < GEN_RANDOM || gen > GEN_SURFACE) // (a source model's generator is its module's: not in the table)
+    return hipErrorInvalidValue;
   unsigned grid = (p.batchCount + VR_BLOCK - 1) / VR_BLOCK;
   if (grid == 0)
     return hipSuccess;
   if (grid > maxBlocks)
     grid = maxBlocks; // grid-stride; bounds the tier-2 slabs to grid waves
-  const int src = p.surfPos ? 4 : (p.hostOrg ? 3 : (p.gridPoints ? 2 : (p.useBasis ? 1 : 0)));
-  hipLaunchKernelGGL(gen_kernel_for(src, D, keepRng, p.reliefCoarse && p.binCount), dim3(grid), dim3(VR_BLOCK), 0, s, p);
+  hipLaunchKernelGGL(gen_kernel_for(gen, D, keepRng, p.reliefCoarse && p.binCount), dim3(grid), dim3(VR_BLOCK), 0, s, p);
   return hipGetLastError();
 }
 

@@ -300,6 +300,18 @@ enum TraceMode : int {
 };
 // (MODE_GENERAL_FLAT, MODE_GENERAL_RELIEF and MODE_RESUME exist for disks and the lean particles only: otherwise MODE_GENERAL)
 
+// The generator of a launch.  vr_prepare.cpp records one per launch from the source in force (RaySource::generator,
+// vr_source.hpp); 0 - 4 are the library's own, in the order of vr_trace.hip's table (launch_gen takes one of these).
+enum Generator : int {
+  GEN_RANDOM = 0,      // SourceRandom, axis-aligned (gen_kernel; on a scene with relief its predicted-hit variant)
+  GEN_BASIS = 1,       // SourceRandom with a tilted primary direction (gen_basis_kernel)
+  GEN_GRID = 2,        // SourceGrid (gen_grid_kernel)
+  GEN_HOST = 3,        // host rays (gen_host_kernel)
+  GEN_SURFACE = 4,     // surface source (gen_surface_kernel): no sort bins, the records lie in index order
+  GEN_SOURCE_MODEL = 5 // not the library's: gen_user_source_kernel of the source model's code object, which takes the
+                       // launch's SourceCtx as its second argument (ParticleLaunch::userGen, ::source)
+};
+
 // counters[] slots: every particle of an apply has one block of C_BLOCK words (TraceParams::counters points at it)
 enum {
   C_TRACES = 0,
