@@ -347,6 +347,38 @@ int vr_smooth_flux(vr_context *ctx, float *flux, uint32_t n, int numNeighbors);
  * the host smoothing runs and its result is uploaded.                                                     */
 int vr_get_flux_device(vr_context *ctx, uint32_t dataIdx, float *out, uint32_t n, int normType, int numNeighbors,
                        void *stream);
+/* ---- flux statistics (not in the reference): per-primitive hit counts and the Monte-Carlo error of the flux ----------
+ * vr_set_flux_statistics(on != 0): every later apply() keeps, for each particle and alongside its data label 0 (the flux
+ * label of every built-in model), two more int64 sums per primitive:
+ *   hits[i]   the number of credits to label 0 of primitive i — the closest primitive and every overlapping neighbour disk
+ *             count one each — in units of ONE;
+ *   sumsq[i]  the sum over those credits of (double)v * (double)v, v the float handed to credit(0, v) (after WDIST
+ *             weighting), quantised like the flux: * 2^VR_FLUX_FRAC_BITS + 0.5.
+ * Exact integer sums like the flux: independent of grid, batch split and rank count.  They are planes numData and
+ * numData + 1 of the particle, BEHIND its data labels, in the same array: vr_flux_accumulators / vr_bind_flux_accumulators
+ * then hold numPrims x (data labels + 2 per particle) words, particle after particle, and vr_apply_sharded all-reduces
+ * them with the flux.  vr_num_data and the dataIdx of the flux getters do not change.  Off by default; switching discards
+ * the last result and a bound accumulator buffer of the other size.
+ *   sigma[i]    = sqrt(max(sumsq[i] - S1[i]^2 / N, 0)), S1 the raw label-0 sum, N the rays of the WHOLE apply (with
+ *                 vr_set_ray_range / vr_apply_sharded: of all shards together, so summed accumulators give the apply's value)
+ *   relative[i] = sigma[i] / S1[i], +inf where S1[i] == 0; the same for every normalisation.  The absolute error is in raw
+ *                 flux units.
+ * A PER-CREDIT estimator: it ignores the correlation between several credits of one ray to the same primitive
+ * ("Flux statistics", has the calibration against the run-to-run scatter).
+ * Launches: an absorbing launch (sticking 1 everywhere, unit start weights) keeps its kernel and trace mode — unit
+ * weights, hits = sumsq = flux, filled from the flux plane; every other launch runs the extended kernels with the
+ * statistics compiled in (modes 0, 4 and, on flat disk scenes without the rare options, 3; no relief modes 6 / 7), a
+ * run-time model in a twin of its code object compiled on first use.  With statistics on a particle model may have at
+ * most VR_MAX_LABELS - 2 = 2 data labels (refused at prepare).
+ * The getters fail (message in vr_last_error) with statistics off, before an apply has finished, with n != numPrims or
+ * particleIdx beyond the particle list.  vr_get_flux_sum_squares: acc * 2^-40, exact.  vr_get_flux_error: kind 0
+ * relative, 1 absolute, float32, computed on the device in double.  vr_get_flux_error_device: the same floats into DEVICE
+ * memory, under vr_get_flux_device's stream rules.                                                                     */
+int vr_set_flux_statistics(vr_context *ctx, int on);
+int vr_get_hit_counts(vr_context *ctx, uint32_t particleIdx, uint64_t *out, uint32_t n);
+int vr_get_flux_sum_squares(vr_context *ctx, uint32_t particleIdx, double *out, uint32_t n);
+int vr_get_flux_error(vr_context *ctx, uint32_t particleIdx, int kind, float *out, uint32_t n);
+int vr_get_flux_error_device(vr_context *ctx, uint32_t particleIdx, int kind, float *out, uint32_t n, void *stream);
 /* geometry-derived values the reference exposes to its tests                */
 int vr_get_disk_areas(vr_context *ctx, float *out, uint32_t n);
 int vr_get_bounding_box(vr_context *ctx, float *out6 /* min xyz, max xyz, adjusted */);

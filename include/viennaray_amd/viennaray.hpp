@@ -1208,6 +1208,31 @@ public:
     return fluxDevice(dOut, dataIdx, VR_NORM_NONE, 0, stream);
   }
 
+  // ---- flux statistics (not in the reference; vr_set_flux_statistics): per-primitive hit counts and the Monte-Carlo
+  //      error of the flux label.  A per-credit estimator: it ignores the correlation between several credits of one ray
+  //      to the same primitive.  Off by default; an absorbing particle keeps its kernels, every other launch runs the
+  //      extended kernels with the statistics compiled in.  With statistics on a particle has at most two data labels.
+  void setCalculateFluxError(const bool on) {
+    if (ctx_)
+      check(vr_set_flux_statistics(ctx_, on ? 1 : 0));
+  }
+  /// credits to the flux label of every primitive in the last apply (particle `particleIdx` of a particle list);
+  /// empty, with the library's message on std::cerr, if the getter was refused (statistics off, no apply yet)
+  [[nodiscard]] std::vector<uint64_t> getHitCounts(unsigned particleIdx = 0) {
+    std::vector<uint64_t> out(ctx_ ? vr_num_primitives(ctx_) : 0);
+    if (!ctx_ || !reported(vr_get_hit_counts(ctx_, particleIdx, out.data(), (uint32_t)out.size())))
+      out.clear();
+    return out;
+  }
+  /// sigma / S1 per primitive, +inf where nothing was credited; the same for every NormalizationType
+  [[nodiscard]] std::vector<NumericType> getFluxRelativeError(unsigned particleIdx = 0) { return fluxError(particleIdx, 0); }
+  /// sigma = sqrt(max(sumsq - S1^2 / N, 0)) per primitive, in raw flux units; N: the rays of the whole apply
+  [[nodiscard]] std::vector<NumericType> getFluxAbsoluteError(unsigned particleIdx = 0) { return fluxError(particleIdx, 1); }
+  /// ... written to DEVICE memory `dOut` (float32, one per primitive) under getFluxDevice's stream rules; false if refused
+  bool getFluxErrorDevice(float *dOut, unsigned particleIdx = 0, bool relative = true, void *stream = nullptr) {
+    return ctx_ && reported(vr_get_flux_error_device(ctx_, particleIdx, relative ? 0 : 1, dOut, vr_num_primitives(ctx_), stream));
+  }
+
   [[nodiscard]] TracingData<NumericType> &getLocalData() { return localData_; }
   // rayTrace.hpp:137-145: global data is a borrowed pointer handed to user particles; apply() copies its vectors and
   // scalars to the device, where the registry's particle models read them (ModelCtx::global)
@@ -1269,6 +1294,18 @@ protected:
       RTInfo_.error = true;
       std::cerr << "viennaray_amd: " << vr_last_error(ctx_) << "\n";
     }
+  }
+  // a getter's result: refused -> the library's message on std::cerr (the trace's error flag is a setter's business)
+  bool reported(int rc) {
+    if (rc != VR_OK)
+      std::cerr << "viennaray_amd: " << vr_last_error(ctx_) << "\n";
+    return rc == VR_OK;
+  }
+  std::vector<NumericType> fluxError(unsigned particleIdx, int kind) {
+    std::vector<float> raw(ctx_ ? vr_num_primitives(ctx_) : 0);
+    if (!ctx_ || !reported(vr_get_flux_error(ctx_, particleIdx, kind, raw.data(), (uint32_t)raw.size())))
+      raw.clear();
+    return std::vector<NumericType>(raw.begin(), raw.end());
   }
   bool fluxDevice(float *dOut, int dataIdx, int norm, int numNeighbors, void *stream) {
     if (!ctx_)

@@ -114,6 +114,11 @@ SIGNATURES = {
     "vr_get_disk_radius": (C.c_float, [_vp]),
     "vr_get_neighbor_counts": (C.c_int, [_vp, _u32p, C.c_uint32]),
     "vr_flux_accumulators": (C.c_int, [_vp, C.POINTER(_vp), _u32p]),
+    "vr_set_flux_statistics": (C.c_int, [_vp, C.c_int]),
+    "vr_get_hit_counts": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32]),
+    "vr_get_flux_sum_squares": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32]),
+    "vr_get_flux_error": (C.c_int, [_vp, C.c_uint32, C.c_int, _vp, C.c_uint32]),
+    "vr_get_flux_error_device": (C.c_int, [_vp, C.c_uint32, C.c_int, _vp, C.c_uint32, _vp]),
     "vr_bind_flux_accumulators": (C.c_int, [_vp, _vp, C.c_uint32]),
     "vr_set_data_log_shape": (C.c_int, [_vp, _u32p, C.c_uint32]),
     "vr_get_model_log_rows": (C.c_int, [_vp, C.c_int32, _i32p]),

@@ -185,9 +185,12 @@ void vr_destroy(vr_context *c) {
   for (auto &sm : c->sourceModels)
     if (sm.module)
       (void)hipModuleUnload(sm.module);
-  for (auto &um : c->userModels)
+  for (auto &um : c->userModels) {
     if (um.module)
       (void)hipModuleUnload(um.module);
+    if (um.statsModule)
+      (void)hipModuleUnload(um.statsModule);
+  }
   c->evK.insert(c->evK.end(), c->evG.begin(), c->evG.end());
   c->evK.insert(c->evK.end(), {c->evIn, c->evOut, c->ev0, c->ev1});
   for (hipEvent_t e : c->evK)
@@ -413,7 +416,7 @@ int vr_set_particles(vr_context *c, const vr_particle *list, uint32_t n) {
   c->totalData = total;
   // a caller's accumulator buffer (vr_bind_flux_accumulators) stays bound while it still has the right size: numPrims x
   // data labels of ALL particles; it is dropped only when the number of planes changed
-  if (c->boundFlux && c->boundFluxN != c->geo.numPrims * total) {
+  if (c->boundFlux && c->boundFluxN != c->geo.numPrims * c->totalPlanes()) {
     c->boundFlux = nullptr;
     c->boundFluxN = 0;
   }
@@ -477,6 +480,23 @@ int vr_set_global_scalars(vr_context *c, const float *data, uint32_t n) {
   c->globalScalars.assign(data, data + n);
   c->globalDirty = true;
   c->prepared = false;
+  return VR_OK;
+}
+// flux statistics: two companion planes per particle behind its data labels (vr_context::fluxStats).  The planes of the
+// accumulator array move: the last result and a bound buffer of the other size do not survive the switch.
+int vr_set_flux_statistics(vr_context *c, int on) {
+  if (!c)
+    return VR_E_INVALID;
+  if (c->fluxStats == (on != 0))
+    return VR_OK;
+  c->fluxStats = on != 0;
+  if (c->boundFlux && c->boundFluxN != c->geo.numPrims * c->totalPlanes()) {
+    c->boundFlux = nullptr;
+    c->boundFluxN = 0;
+  }
+  c->prepared = false;
+  c->launched = false;
+  c->haveResult = false;
   return VR_OK;
 }
 int vr_set_use_wdist(vr_context *c, int on) {

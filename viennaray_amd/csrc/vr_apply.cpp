@@ -184,7 +184,7 @@ int vr_apply_launch(vr_context *c) {
     return fail(c, VR_E_STATE, "vr_apply_launch: call vr_apply_prepare first");
   VR_HIP(c, hipSetDevice(c->device));
   const uint32_t N = c->geo.numPrims;
-  VR_HIP(c, hipMemsetAsync(c->dFluxAcc.p, 0, (size_t)c->accStride * c->accReplicas * c->totalData * 8, c->stream));
+  VR_HIP(c, hipMemsetAsync(c->dFluxAcc.p, 0, (size_t)c->accStride * c->accReplicas * c->totalPlanes() * 8, c->stream));
   VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, C_BLOCK * c->launches.size() * 8, c->stream));
   if (c->logActive) // (the sums, the dropped counter and the overflow flag)
     VR_HIP(c, hipMemsetAsync(c->dDataLog.p, 0, ((size_t)c->logTotal + 2) * 8, c->stream));
@@ -216,10 +216,16 @@ int vr_apply_launch(vr_context *c) {
   VR_HIP(c, hipEventRecord(c->ev1, c->stream));
   {
     const unsigned headroom = rank_headroom(c->worldSize);
-    for (uint32_t l = 0; l < c->totalData; ++l)
+    for (uint32_t l = 0; l < c->totalPlanes(); ++l)
       VR_HIP(c, launch_gather_flux(c->dFluxAcc.p + (size_t)l * c->accStride * c->accReplicas, c->accStride, c->accReplicas,
                                    c->dLeafOfOrig.p, N, c->fluxOut() + (size_t)l * N, headroom, c->dCounters.p + C_ACC_OVERFLOW, c->stream));
   }
+  // flux statistics of the absorbing launches: unit weights, so both companion planes follow from the flux plane
+  for (const ParticleLaunch &L : c->launches)
+    if (L.stats && L.absorb) {
+      unsigned long long *flux = c->fluxOut() + (size_t)L.dataBase * N;
+      VR_HIP(c, launch_stats_fill_absorbing(flux, N, flux + (size_t)L.params.numData * N, flux + (size_t)(L.params.numData + 1u) * N, c->stream));
+    }
   c->launched = true;
   return VR_OK;
 }
@@ -443,7 +449,7 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
     c->rayCount = 1;
     r = vr_apply_prepare(c);
     if (r == VR_OK) {
-      VR_HIP(c, hipMemsetAsync(c->fluxOut(), 0, (size_t)N * c->totalData * 8, c->stream));
+      VR_HIP(c, hipMemsetAsync(c->fluxOut(), 0, (size_t)N * c->totalPlanes() * 8, c->stream));
       VR_HIP(c, hipMemsetAsync(c->dCounters.p, 0, counterWords * 8, c->stream));
       if (c->logActive)
         VR_HIP(c, hipMemsetAsync(c->dDataLog.p, 0, ((size_t)c->logTotal + 2) * 8, c->stream));
@@ -464,12 +470,12 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
     // the walk's stack, or this; C_ACC_OVERFLOW) travel together, in counterWords: every rank fails together,
     // none returns VR_OK holding sums that include a discarded share.
     const std::string firstErr = c->err;
-    const bool haveBuf = c->boundFlux ? c->boundFluxN == N * c->totalData : c->dFluxOrig.cap >= (size_t)N * c->totalData;
+    const bool haveBuf = c->boundFlux ? c->boundFluxN == N * c->totalPlanes() : c->dFluxOrig.cap >= (size_t)N * c->totalPlanes();
     if (r != VR_OK) {
       if (!haveBuf)
         return r; // (failed before the accumulators existed: a configuration error, the same on every rank)
       const unsigned long long one = 1;
-      (void)hipMemsetAsync(c->fluxOut(), 0, (size_t)N * c->totalData * 8, c->stream);
+      (void)hipMemsetAsync(c->fluxOut(), 0, (size_t)N * c->totalPlanes() * 8, c->stream);
       (void)hipMemsetAsync(c->dCounters.p, 0, counterWords * 8, c->stream);
       (void)hipMemcpyAsync(c->dCounters.p + C_WALK_OVERFLOW, &one, 8, hipMemcpyHostToDevice, c->stream);
       if (c->logActive)
@@ -477,7 +483,7 @@ int vr_apply_sharded(vr_context *c, int rank, int world, vr_allreduce_fn reduce,
     }
     // (the data log's sums travel with their dropped counter and overflow flag: the two words behind them; a shape that
     //  prepare refused is refused on every rank alike, so the ranks agree on logActive)
-    if (reduce(user, c->fluxOut(), (size_t)N * c->totalData, (void *)c->stream) != 0 ||
+    if (reduce(user, c->fluxOut(), (size_t)N * c->totalPlanes(), (void *)c->stream) != 0 ||
         reduce(user, c->dCounters.p, counterWords, (void *)c->stream) != 0 ||
         (c->logActive && reduce(user, c->dDataLog.p, (size_t)c->logTotal + 2, (void *)c->stream) != 0))
       return fail(c, VR_E_HIP, "vr_apply_sharded: the all-reduce callback failed");

@@ -158,6 +158,11 @@ struct UserModel {
   int logRows = 0;                      // kLogRows: rows of the data log its log_data hook writes (0: no hook)
   std::map<int, hipFunction_t> kernels; // key: D * 100 + geo * 10 + mode
   hipFunction_t gen[2] = {nullptr, nullptr}; // a stateful model's generator (gen_state_kernel), 2-D / 3-D
+  // flux statistics: the module's twin with the statistics compiled in (VR_USER_FLUX_STATS), built from the kept text
+  // when a statistics-on apply first needs it, under a cache key of its own
+  std::string source;
+  hipModule_t statsModule = nullptr;
+  std::map<int, hipFunction_t> statsKernels; // key as `kernels`
 };
 // a source model registered at run time (vr_register_source_model): its own code object with the generator
 // (gen_user_source_kernel) and its debug twin, no trace kernel
@@ -177,6 +182,7 @@ struct ParticleLaunch {
   TraceParams params{};
   uint32_t slot = 0;     // index of the particle: its counter block, wall-table / frame slot
   uint32_t dataBase = 0; // its first accumulator plane
+  bool stats = false;    // flux statistics: two companion planes behind its data labels (planes numData, numData + 1)
   unsigned grid = 0;
   int traceMode = MODE_GENERAL, kernelParticle = 0;
   bool absorb = false;
@@ -225,6 +231,30 @@ struct vr_context {
   bool useWdist = false;
   uint32_t totalData = 1;         // data labels of all particles of the apply: accumulator planes, TracingData vectors
   uint32_t accPlanes = 0;         // planes the accumulator buffers currently hold
+  // flux statistics (vr_set_flux_statistics): every particle of the apply keeps VR_STAT_PLANES companion planes behind
+  // its data labels — the sum of squares and the hit count of label 0 — in the same array, so gather, overflow check,
+  // bound buffers and the sharded all-reduce see them like any other plane
+  bool fluxStats = false;
+  uint32_t totalPlanes() const { return totalData + (fluxStats ? (uint32_t)VR_STAT_PLANES * (uint32_t)numParticles() : 0u); }
+  // the plane of data label `dataIdx` (counted over all particles, as vr_get_flux_data counts them)
+  uint32_t planeOfData(uint32_t dataIdx) const {
+    if (!fluxStats)
+      return dataIdx;
+    uint32_t base = 0;
+    for (size_t q = 0; q < specs.size(); ++q) {
+      if (dataIdx < base + specs[q].numData)
+        return dataIdx + (uint32_t)VR_STAT_PLANES * (uint32_t)q;
+      base += specs[q].numData;
+    }
+    return dataIdx;
+  }
+  // the first plane of particle q
+  uint32_t planeBase(uint32_t q) const {
+    uint32_t base = 0;
+    for (size_t k = 0; k < q && k < specs.size(); ++k)
+      base += specs[k].numData + (fluxStats ? (uint32_t)VR_STAT_PLANES : 0u);
+    return base;
+  }
   DevBuf<float> dRayState;            // a stateful model's per-ray state of one batch (the frame's VR_F_STATE_*), float4 per ray
   DevBuf<int32_t> dPrimMaterial;      // material id per original primitive for a stateful model (VR_F_MAT_*)
   // the material ids on the device, caller's order: what prepare_sticking and the stateful models read.  Set from the
@@ -406,6 +436,8 @@ int host_waits(vr_context *c);
 int caller_waits(vr_context *c, void *stream);
 // vr_knobs.cpp
 Knobs read_knobs();
+// vr_models.cpp
+int ensure_stats_module(vr_context *c, UserModel &um);
 // vr_scene.cpp
 int ensure_host_geometry(vr_context *c);
 int ensure_host_order(vr_context *c);

@@ -13,6 +13,10 @@ hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int 
                         hipStream_t s);
 // resident 256-thread blocks per CU of the trace kernel instantiation (occupancy API)
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes);
+// ... the kernels with flux statistics (vr_trace_stats.hip; particle: P_EXT_STATS / P_EXT_FULL_STATS); launch_trace and
+// trace_blocks_per_cu forward to them
+hipError_t launch_trace_stats(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid, hipStream_t s);
+int trace_stats_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes);
 // diagnostics (vr_diag.hip)
 // surface_sample (the surface source's generator) for the p.batchCount ray indices p.idxList[]
 hipError_t launch_debug_surface_sample(const TraceParams &p, unsigned maxBlocks, float *org, float *dir, float *weight,
@@ -88,6 +92,14 @@ hipError_t launch_flux_from_acc(const unsigned long long *acc, unsigned n, float
 hipError_t launch_gather_flux(const unsigned long long *acc, unsigned stride, unsigned replicas,
                               const unsigned *leafOfOrig, unsigned n, unsigned long long *outAcc, unsigned headroomBits,
                               unsigned long long *overflowFlag, hipStream_t s);
+// flux statistics (vr_set_flux_statistics), planes in the caller's order.  launch_stats_fill_absorbing: an absorbing launch
+// credits unit weights only, so its two companion planes follow from its flux plane: sumsq = flux, hits = flux >> 40.
+// launch_flux_error: (S1, sum of squares, N rays) -> sigma = sqrt(max(sumsq - S1^2 / N, 0)) in raw flux units (kind 1) or
+// sigma / S1, +inf where S1 == 0 (kind 0), in double, as float32
+hipError_t launch_stats_fill_absorbing(const unsigned long long *flux, unsigned n, unsigned long long *sumsq,
+                                       unsigned long long *hits, hipStream_t st);
+hipError_t launch_flux_error(const unsigned long long *s1, const unsigned long long *sumsq, unsigned n, double numRays,
+                             int kind, float *out, hipStream_t st);
 hipError_t launch_normalize_flux(float *flux, const float *area, unsigned n, int geo, int normType, float normFactor,
                                  double totalDiskArea, unsigned *maxOrd, hipStream_t st);
 // issue-ceiling microbenchmarks (vr_bench.hip); out: one {cycles, realtime, sink} triple of u64 per wave

@@ -212,6 +212,66 @@ static int build_code_object(vr_context *c, const ModuleKind &kind, uint64_t h, 
   return VR_OK;
 }
 
+// A particle model's code object: the extended trace kernels around the caller's text, or (stats) its twin with the flux
+// statistics compiled in (VR_USER_FLUX_STATS, vr_modules.hpp) — a code object and a cache key of its own.
+static int build_particle_module(vr_context *c, const char *source, int numData, int numState, bool full, bool stats, std::string &hsaco) {
+  uint64_t h = 1469598103934665603ull;
+  h = fnv1a(h, source, std::strlen(source));
+  h = fnv1a(h, &numData, sizeof(numData));
+  h = fnv1a(h, &full, sizeof(full));
+  h = fnv1a(h, &numState, sizeof(numState));
+  if (stats) // (statistics off: the key the module always had)
+    h = fnv1a(h, "flux-statistics", 15);
+  static const ModuleKind kind{"vr_register_particle_model", "model_", "_model.hpp", "VR_USER_MODEL_FILE", "model"};
+  return build_code_object(c, kind, h, source,
+                           "#define VR_USER_MODULE 1\n#define VR_USER_NUM_DATA " + std::to_string(numData) +
+                               "\n#define VR_USER_NUM_STATE " + std::to_string(numState) + "\n" +
+                               (stats ? "#define VR_USER_FLUX_STATS 1\n" : ""),
+                           std::string("static_assert(vr::VrUserModel::kNeedsFull == ") + (full ? "true" : "false") +
+                               ", \"kNeedsFull differs from the VR_MODEL_NEEDS_FULL flag given at registration\");\n",
+                           hsaco);
+}
+
+// the trace kernels of a loaded particle module, by their mangled names (key: D * 100 + geo * 10 + mode)
+static int find_trace_kernels(vr_context *c, hipModule_t module, bool full, bool stats, std::map<int, hipFunction_t> &kernels) {
+  const int P = stats ? (full ? (int)P_EXT_FULL_STATS : (int)P_EXT_STATS) : (full ? (int)P_EXT_FULL : (int)P_EXT);
+  for (int D = 2; D <= 3; ++D)
+    for (int geo = 0; geo <= 1; ++geo)
+      for (int mode : {MODE_GENERAL, MODE_GENERAL_FLAT, MODE_SMALL}) {
+        if (mode == MODE_GENERAL_FLAT && (geo != 0 || full))
+          continue;
+        char sym[128];
+        std::snprintf(sym, sizeof(sym), "_ZN2vr12trace_kernelILi%dELi%dELi%dELi%dEEEvNS_11TraceParamsE", D, geo, P, mode);
+        hipFunction_t f = nullptr;
+        if (hipModuleGetFunction(&f, module, sym) != hipSuccess || !f)
+          return fail(c, VR_E_STATE, (std::string("vr_register_particle_model: kernel missing from the code object: ") + sym).c_str());
+        kernels[D * 100 + geo * 10 + mode] = f;
+      }
+  return VR_OK;
+}
+
+namespace vr {
+// flux statistics: the model's twin module, built (or found in the cache) and loaded when a statistics-on apply first needs it
+int ensure_stats_module(vr_context *c, UserModel &um) {
+  if (um.statsModule)
+    return VR_OK;
+  VR_HIP(c, hipSetDevice(c->device));
+  std::string hsaco;
+  VR_TRY(build_particle_module(c, um.source.c_str(), um.numData, um.numState, um.needsFull, true, hsaco));
+  hipModule_t m = nullptr;
+  VR_HIP(c, hipModuleLoad(&m, hsaco.c_str()));
+  std::map<int, hipFunction_t> kernels;
+  const int r = find_trace_kernels(c, m, um.needsFull, true, kernels);
+  if (r != VR_OK) {
+    (void)hipModuleUnload(m);
+    return r;
+  }
+  um.statsModule = m;
+  um.statsKernels = std::move(kernels);
+  return VR_OK;
+}
+} // namespace vr
+
 extern "C" {
 
 // The reference's GPU path registers user callables per particle at run time (gpu/raygCallableConfig.hpp:7-18: OptiX
@@ -233,21 +293,11 @@ int vr_register_particle_model_ex(vr_context *c, const char *name, const char *s
     return fail(c, VR_E_INVALID, "vr_register_particle_model_ex: numState (the model's kStateWords) must be 0 .. 4");
   VR_HIP(c, hipSetDevice(c->device));
   const bool full = (flags & VR_MODEL_NEEDS_FULL) != 0 || numState > 0;
-  uint64_t h = 1469598103934665603ull;
-  h = fnv1a(h, source, std::strlen(source));
-  h = fnv1a(h, &numData, sizeof(numData));
-  h = fnv1a(h, &full, sizeof(full));
-  h = fnv1a(h, &numState, sizeof(numState));
-  static const ModuleKind kind{"vr_register_particle_model", "model_", "_model.hpp", "VR_USER_MODEL_FILE", "model"};
   std::string hsaco;
-  VR_TRY(build_code_object(c, kind, h, source,
-                           "#define VR_USER_MODULE 1\n#define VR_USER_NUM_DATA " + std::to_string(numData) +
-                               "\n#define VR_USER_NUM_STATE " + std::to_string(numState) + "\n",
-                           std::string("static_assert(vr::VrUserModel::kNeedsFull == ") + (full ? "true" : "false") +
-                               ", \"kNeedsFull differs from the VR_MODEL_NEEDS_FULL flag given at registration\");\n",
-                           hsaco));
+  VR_TRY(build_particle_module(c, source, numData, numState, full, false, hsaco));
   UserModel um;
   um.name = name ? name : "";
+  um.source = source;
   um.numData = numData;
   um.needsFull = full;
   um.numState = numState;
@@ -272,21 +322,10 @@ int vr_register_particle_model_ex(vr_context *c, const char *name, const char *s
     }
     um.logRows = rows;
   }
-  const int P = full ? (int)P_EXT_FULL : (int)P_EXT;
-  for (int D = 2; D <= 3; ++D)
-    for (int geo = 0; geo <= 1; ++geo)
-      for (int mode : {MODE_GENERAL, MODE_GENERAL_FLAT, MODE_SMALL}) {
-        if (mode == MODE_GENERAL_FLAT && (geo != 0 || full))
-          continue;
-        char sym[128];
-        std::snprintf(sym, sizeof(sym), "_ZN2vr12trace_kernelILi%dELi%dELi%dELi%dEEEvNS_11TraceParamsE", D, geo, P, mode);
-        hipFunction_t f = nullptr;
-        if (hipModuleGetFunction(&f, um.module, sym) != hipSuccess || !f) {
-          (void)hipModuleUnload(um.module);
-          return fail(c, VR_E_STATE, (std::string("vr_register_particle_model: kernel missing from the code object: ") + sym).c_str());
-        }
-        um.kernels[D * 100 + geo * 10 + mode] = f;
-      }
+  if (const int r = find_trace_kernels(c, um.module, full, false, um.kernels); r != VR_OK) {
+    (void)hipModuleUnload(um.module);
+    return r;
+  }
   c->userModels.push_back(std::move(um));
   *kindOut = VR_PARTICLE_USER_BASE + (int32_t)c->userModels.size() - 1;
   return VR_OK;

@@ -114,13 +114,19 @@ static_assert(VrUserModel::kLogRows >= 0 && VrUserModel::kLogRows <= VR_LOG_MAX_
 static_assert(VrUserModel::kLogRows == 0 || VrUserModel::kStateWords > 0, "log_data (kLogRows > 0) logs the state init left: it needs a stateful model (kStateWords > 0)");
 // what the host asks the loaded module (vr_register_particle_model): the rows its log_data hook writes
 extern "C" __device__ __attribute__((used)) const int vr_user_log_rows = VrUserModel::kLogRows;
-constexpr int VR_USER_P = VrUserModel::kNeedsFull ? P_EXT_FULL : P_EXT;
+// (VR_USER_FLUX_STATS: the module's twin with flux statistics compiled in, built when a statistics-on apply first needs it)
+#ifndef VR_USER_FLUX_STATS
+#define VR_USER_FLUX_STATS 0
+#endif
+static_assert(!VR_USER_FLUX_STATS || VrUserModel::kNumData <= VR_MAX_LABELS - VR_STAT_PLANES, "flux statistics take two of a particle's planes");
+constexpr int VR_USER_P = VR_USER_FLUX_STATS ? (VrUserModel::kNeedsFull ? P_EXT_FULL_STATS : P_EXT_STATS) : (VrUserModel::kNeedsFull ? P_EXT_FULL : P_EXT);
+constexpr int VR_USER_P_LEAN = VR_USER_FLUX_STATS ? P_EXT_STATS : P_EXT;
 #define VR_INST(DD, GG, MM) template __global__ void trace_kernel<DD, GG, VR_USER_P, MM>(const TraceParams);
 VR_INST(2, 0, 0) VR_INST(2, 0, 4) VR_INST(2, 1, 0) VR_INST(2, 1, 4)
 VR_INST(3, 0, 0) VR_INST(3, 0, 4) VR_INST(3, 1, 0) VR_INST(3, 1, 4)
 #undef VR_INST
-template __global__ void trace_kernel<2, 0, P_EXT, VrUserModel::kNeedsFull ? 0 : 3>(const TraceParams);
-template __global__ void trace_kernel<3, 0, P_EXT, VrUserModel::kNeedsFull ? 0 : 3>(const TraceParams);
+template __global__ void trace_kernel<2, 0, VR_USER_P_LEAN, VrUserModel::kNeedsFull ? 0 : 3>(const TraceParams);
+template __global__ void trace_kernel<3, 0, VR_USER_P_LEAN, VrUserModel::kNeedsFull ? 0 : 3>(const TraceParams);
 
 // The generator of a STATEFUL model (SourceRandom, plain or with a primary direction): the model's init (initNew,
 // rayTraceKernel.hpp:131-133) draws first, then the source sample from the same engine (the streaming generator of

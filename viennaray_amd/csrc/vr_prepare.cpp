@@ -314,6 +314,13 @@ static int upload_global_data(vr_context *c) {
 static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, PrepareState &S) {
   TraceParams &p = L.params;
   const uint32_t N = c->geo.numPrims;
+  // flux statistics: the two companion planes count against the planes one particle may have
+  L.stats = c->fluxStats;
+  if (L.stats && sp.numData > (uint32_t)(VR_MAX_LABELS - VR_STAT_PLANES))
+    return fail(c, VR_E_INVALID, ("flux statistics (vr_set_flux_statistics) take " + std::to_string(VR_STAT_PLANES) + " of a particle's " +
+                                  std::to_string(VR_MAX_LABELS) + " accumulator planes (VR_MAX_LABELS): a particle model may have at most " +
+                                  std::to_string(VR_MAX_LABELS - VR_STAT_PLANES) + " data labels with statistics on, this one has " +
+                                  std::to_string(sp.numData)).c_str());
   // ABSORB: every hit takes the whole weight -> nothing after the first
   // surface hit is observable
   L.absorb = sp.sticking >= 1.f;
@@ -358,7 +365,7 @@ static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, Particl
     put(1, (size_t)N * recB);
     put(2, ((size_t)N + 1) * 4);
     put(3, (size_t)nbTotal * 4);
-    put(4, (size_t)N * 8 * sp.numData);
+    put(4, (size_t)N * 8 * (sp.numData + (c->fluxStats ? (uint32_t)VR_STAT_PLANES : 0u)));
     put(5, p.primSticking ? (size_t)N * 4 : 0);
     S.smallScene = o <= VR_SMALL_LDS && c->numNodes > 0 && c->knobs.smallScene;
     for (int k = 0; k < 6; ++k)
@@ -368,6 +375,11 @@ static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, Particl
     if (S.smallScene)
       L.absorb = false; // (ray records with the RNG cursors: the general kernel reads them)
   }
+  // Flux statistics: an absorbing launch keeps its kernel (unit weights: its companion planes are filled from the flux
+  // plane after the gather, vr_apply_launch); every other launch runs the extended instantiation with the statistics
+  // compiled in — the built-in particles as models 0 / 1 of the registry
+  if (L.stats && !L.absorb)
+    L.kernelParticle = extFull ? (int)P_EXT_FULL_STATS : (int)P_EXT_STATS;
   S.flatScene = c->keyShare >= 0.95f && (c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]]) <= 0.25f * c->geo.gridDelta;
   return VR_OK;
 }
@@ -454,13 +466,13 @@ static int build_relief_field(vr_context *c, const ParticleSpec &sp, ParticleLau
 // accumulators: one plane per data label of all particles, each replicated accReplicas times
 static int ensure_accumulators(vr_context *c) {
   const uint32_t N = c->geo.numPrims;
-  if (c->accPlanes != c->totalData) {
-    VR_HIP(c, c->dFluxAcc.ensure((size_t)c->accStride * c->accReplicas * c->totalData));
-    VR_HIP(c, c->dFluxOrig.ensure((size_t)N * c->totalData));
-    c->accPlanes = c->totalData;
+  if (c->accPlanes != c->totalPlanes()) {
+    VR_HIP(c, c->dFluxAcc.ensure((size_t)c->accStride * c->accReplicas * c->totalPlanes()));
+    VR_HIP(c, c->dFluxOrig.ensure((size_t)N * c->totalPlanes()));
+    c->accPlanes = c->totalPlanes();
   }
-  if (c->boundFlux && c->boundFluxN != N * c->totalData)
-    return fail(c, VR_E_STATE, "bound accumulator buffer does not hold numPrims x numData int64");
+  if (c->boundFlux && c->boundFluxN != N * c->totalPlanes())
+    return fail(c, VR_E_STATE, "bound accumulator buffer does not hold numPrims x numData int64 (flux statistics: two more planes per particle)");
   return VR_OK;
 }
 
@@ -550,7 +562,8 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   // grazing rays of a wave stretch its query over dozens of primitives (a 10^6-disk plane with ONE 50 x 50 bump of
   // 0.3 cells: the absorbing kernel 6.4 -> 8.3 ms, the general one 11 -> 18; the kernels for structured scenes are
   // then 2 - 6 % ahead of the flat ones.  DESIGN.md section 10: a flat layer + relief decomposition would close this)
-  const bool generalFlatOk = !L.absorb && c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT;
+  // (with flux statistics the lean extended kernel has MODE_GENERAL_FLAT too, but no relief modes: vr_trace_stats.hip)
+  const bool generalFlatOk = !L.absorb && c->geo.geo == 0 && (L.kernelParticle <= (int)P_EXT || L.kernelParticle == (int)P_EXT_STATS);
   L.traceMode = !L.absorb ? ((S.flatScene && generalFlatOk) ? MODE_GENERAL_FLAT : MODE_GENERAL) : (S.flatScene ? MODE_ABSORB_FLAT : MODE_ABSORB);
   L.looseMode = L.traceMode;
   if (L.relief) { // flat with relief: the flat-scene kernels on the tight bins, the structured-scene ones on the loose
@@ -572,12 +585,15 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   L.userKernel = nullptr;
   L.userGen = nullptr;
   if (sp.userModel >= 0) { // the kernel of the model's own code object
-    const UserModel &um = c->userModels[sp.userModel];
+    UserModel &um = c->userModels[sp.userModel];
+    if (L.stats) // (the module's twin with the statistics compiled in: built on first use)
+      VR_TRY(ensure_stats_module(c, um));
     if (S.stateful && (L.absorb || (L.traceMode != MODE_GENERAL && L.traceMode != MODE_SMALL)))
       return fail(c, VR_E_STATE, "stateful particle model: only the general kernels (MODE 0 / 4) carry the state");
     L.userGen = S.stateful ? um.gen[D == 3 ? 1 : 0] : nullptr;
-    auto it = um.kernels.find(D * 100 + c->geo.geo * 10 + L.traceMode);
-    if (it == um.kernels.end())
+    const std::map<int, hipFunction_t> &kernels = L.stats ? um.statsKernels : um.kernels;
+    auto it = kernels.find(D * 100 + c->geo.geo * 10 + L.traceMode);
+    if (it == kernels.end())
       return fail(c, VR_E_STATE, "run-time particle model: no kernel for this geometry / mode in its code object");
     L.userKernel = it->second;
     int nb = 0;
@@ -1038,7 +1054,7 @@ int vr_apply_prepare(vr_context *c) {
     L.slot = (uint32_t)q;
     L.dataBase = base;
     VR_TRY(prepare_one(c, c->specs[q], L));
-    base += c->specs[q].numData;
+    base += c->specs[q].numData + (c->fluxStats ? (uint32_t)VR_STAT_PLANES : 0u);
   }
   return VR_OK;
 }

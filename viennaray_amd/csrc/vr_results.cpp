@@ -42,7 +42,7 @@ int vr_get_flux_data(vr_context *c, uint32_t dataIdx, float *out, uint32_t n) {
     return fail(c, VR_E_INVALID, "vr_get_flux_data: the particle has no such data label");
   VR_HIP(c, hipSetDevice(c->device));
   VR_HIP(c, c->dFluxTmp.ensure(n));
-  VR_HIP(c, launch_flux_from_acc(c->fluxOut() + (size_t)dataIdx * n, n, c->dFluxTmp.p, c->stream));
+  VR_HIP(c, launch_flux_from_acc(c->fluxOut() + (size_t)c->planeOfData(dataIdx) * n, n, c->dFluxTmp.p, c->stream));
   VR_HIP(c, hipMemcpyAsync(out, c->dFluxTmp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   return VR_OK;
@@ -59,7 +59,7 @@ static int get_flux_plane_f64(vr_context *c, uint32_t dataIdx, double *out, uint
     return fail(c, VR_E_INVALID, "vr_get_flux_data: the particle has no such data label");
   VR_HIP(c, hipSetDevice(c->device));
   std::vector<unsigned long long> acc(n);
-  VR_HIP(c, hipMemcpy(acc.data(), c->fluxOut() + (size_t)dataIdx * n, (size_t)n * 8, hipMemcpyDeviceToHost));
+  VR_HIP(c, hipMemcpy(acc.data(), c->fluxOut() + (size_t)c->planeOfData(dataIdx) * n, (size_t)n * 8, hipMemcpyDeviceToHost));
   const double scale = std::ldexp(1.0, -VR_FLUX_FRAC_BITS);
   for (uint32_t i = 0; i < n; ++i)
     out[i] = (double)acc[i] * scale;
@@ -104,7 +104,7 @@ int vr_flux_accumulators(vr_context *c, void **devPtr, uint32_t *n) {
     return fail(c, VR_E_STATE, "vr_flux_accumulators: no result");
   *devPtr = c->fluxOut();
   if (n)
-    *n = c->geo.numPrims * c->totalData;
+    *n = c->geo.numPrims * c->totalPlanes();
   return VR_OK;
 }
 
@@ -156,7 +156,7 @@ int vr_data_log_accumulators(vr_context *c, void **devPtr, uint32_t *n) {
 int vr_bind_flux_accumulators(vr_context *c, void *devPtr, uint32_t n) {
   if (!c)
     return VR_E_INVALID;
-  if (devPtr && n != c->geo.numPrims * c->totalData)
+  if (devPtr && n != c->geo.numPrims * c->totalPlanes())
     return fail(c, VR_E_INVALID, "vr_bind_flux_accumulators: size mismatch (numPrims x data labels; set geometry and particle first)");
   c->boundFlux = (unsigned long long *)devPtr;
   c->boundFluxN = devPtr ? n : 0;
@@ -312,7 +312,7 @@ int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, 
     VR_HIP(c, c->dFluxTmp.ensure(n));
     work = c->dFluxTmp.p;
   }
-  VR_HIP(c, launch_flux_from_acc(c->fluxOut() + (size_t)dataIdx * n, n, work, c->stream));
+  VR_HIP(c, launch_flux_from_acc(c->fluxOut() + (size_t)c->planeOfData(dataIdx) * n, n, work, c->stream));
   if (normType == VR_NORM_SOURCE || normType == VR_NORM_MAX)
     VR_TRY(normalize_on_device(c, work, n, normType));
   if (smooth) {
@@ -340,6 +340,74 @@ int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, 
       VR_HIP(c, hipMemcpy(out, h.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     }
   }
+  return caller_waits(c, stream);
+}
+
+// ---- flux statistics (vr_set_flux_statistics) ------------------------------------------------------------------------
+// the planes of particle q in fluxOut(): *flux its label 0, *sumsq and *hits its two companions
+static int stats_planes(vr_context *c, const char *api, uint32_t q, const void *out, uint32_t n, unsigned long long **flux,
+                        unsigned long long **sumsq, unsigned long long **hits) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  const std::string name = api;
+  if (!c->fluxStats)
+    return fail(c, VR_E_STATE, (name + ": flux statistics are off (vr_set_flux_statistics)").c_str());
+  if (!c->haveResult)
+    return fail(c, VR_E_STATE, (name + ": no result (call vr_apply with flux statistics on; after vr_apply_launch, vr_apply_finish)").c_str());
+  if (n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, (name + ": size mismatch (n must be the number of primitives)").c_str());
+  if (q >= c->numParticles())
+    return fail(c, VR_E_INVALID, (name + ": particleIdx is beyond the particle list").c_str());
+  const uint32_t numData = c->specs.empty() ? 1u : c->specs[q].numData;
+  *flux = c->fluxOut() + (size_t)c->planeBase(q) * n;
+  *sumsq = *flux + (size_t)numData * n;
+  *hits = *sumsq + n;
+  return VR_OK;
+}
+
+int vr_get_hit_counts(vr_context *c, uint32_t q, uint64_t *out, uint32_t n) {
+  unsigned long long *flux, *sumsq, *hits;
+  VR_TRY(stats_planes(c, "vr_get_hit_counts", q, out, n, &flux, &sumsq, &hits));
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_HIP(c, hipMemcpyAsync(out, hits, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  return VR_OK;
+}
+
+int vr_get_flux_sum_squares(vr_context *c, uint32_t q, double *out, uint32_t n) {
+  unsigned long long *flux, *sumsq, *hits;
+  VR_TRY(stats_planes(c, "vr_get_flux_sum_squares", q, out, n, &flux, &sumsq, &hits));
+  VR_HIP(c, hipSetDevice(c->device));
+  std::vector<unsigned long long> acc(n);
+  VR_HIP(c, hipMemcpyAsync(acc.data(), sumsq, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  const double scale = std::ldexp(1.0, -VR_FLUX_FRAC_BITS);
+  for (uint32_t i = 0; i < n; ++i)
+    out[i] = (double)acc[i] * scale;
+  return VR_OK;
+}
+
+int vr_get_flux_error(vr_context *c, uint32_t q, int kind, float *out, uint32_t n) {
+  unsigned long long *flux, *sumsq, *hits;
+  VR_TRY(stats_planes(c, "vr_get_flux_error", q, out, n, &flux, &sumsq, &hits));
+  if (kind != 0 && kind != 1)
+    return fail(c, VR_E_INVALID, "vr_get_flux_error: kind is 0 (relative) or 1 (absolute)");
+  VR_HIP(c, hipSetDevice(c->device));
+  VR_HIP(c, c->dFluxTmp.ensure(n));
+  VR_HIP(c, launch_flux_error(flux, sumsq, n, (double)c->numRaysLast, kind, c->dFluxTmp.p, c->stream));
+  VR_HIP(c, hipMemcpyAsync(out, c->dFluxTmp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  return VR_OK;
+}
+
+// ... into the caller's device buffer, ordered like vr_get_flux_device: no host copy, nothing waits on the host
+int vr_get_flux_error_device(vr_context *c, uint32_t q, int kind, float *out, uint32_t n, void *stream) {
+  unsigned long long *flux, *sumsq, *hits;
+  VR_TRY(stats_planes(c, "vr_get_flux_error_device", q, out, n, &flux, &sumsq, &hits));
+  if (kind != 0 && kind != 1)
+    return fail(c, VR_E_INVALID, "vr_get_flux_error_device: kind is 0 (relative) or 1 (absolute)");
+  VR_TRY(hand_over(c, {n ? out : nullptr}, "vr_get_flux_error_device: out is not device memory of the context's device", stream));
+  VR_HIP(c, launch_flux_error(flux, sumsq, n, (double)c->numRaysLast, kind, out, c->stream));
   return caller_waits(c, stream);
 }
 

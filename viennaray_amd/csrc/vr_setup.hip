@@ -938,6 +938,56 @@ hipError_t launch_flux_from_acc(const unsigned long long *acc, unsigned n, float
   return hipGetLastError();
 }
 
+// ---- flux statistics (vr_set_flux_statistics) ----
+// An absorbing launch credits unit weights only: every credit adds 2^40 to the flux plane, 1 * 1 * 2^40 to the sum of
+// squares and 1 to the hit count — the companion planes follow from the flux plane, and its kernels stay as they are.
+__global__ void stats_fill_absorbing_kernel(const unsigned long long *flux, unsigned n, unsigned long long *sumsq,
+                                            unsigned long long *hits) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const unsigned long long f = flux[i];
+    sumsq[i] = f;
+    hits[i] = f >> 40;
+  }
+}
+
+// The per-credit estimator of the Monte-Carlo error of a raw flux sum S1 = sum w over N rays: sigma^2 = sum w^2 - S1^2 / N
+// (N x the sample variance of a ray's contribution, the rays that miss counted as zeros).  KIND 1: sigma in raw flux
+// units; KIND 0: sigma / S1, +inf for a primitive nothing reached.  In double, like flux_from_acc_kernel.
+template <int KIND>
+__global__ void flux_error_kernel(const unsigned long long *s1Acc, const unsigned long long *sqAcc, unsigned n, double numRays,
+                                  float *out) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  const double s1 = (double)s1Acc[i] * 9.094947017729282379150390625e-13; // 2^-40
+  const double sq = (double)sqAcc[i] * 9.094947017729282379150390625e-13;
+  const double sigma = sqrt(fmax(sq - s1 * s1 / numRays, 0.0));
+  if (KIND == 1)
+    out[i] = (float)sigma;
+  else
+    out[i] = s1Acc[i] == 0ull ? __int_as_float(0x7F800000) : (float)(sigma / s1);
+}
+
+hipError_t launch_stats_fill_absorbing(const unsigned long long *flux, unsigned n, unsigned long long *sumsq,
+                                       unsigned long long *hits, hipStream_t st) {
+  if (n == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(stats_fill_absorbing_kernel, dim3((n + 255) / 256), dim3(256), 0, st, flux, n, sumsq, hits);
+  return hipGetLastError();
+}
+
+hipError_t launch_flux_error(const unsigned long long *s1, const unsigned long long *sumsq, unsigned n, double numRays,
+                             int kind, float *out, hipStream_t st) {
+  if (n == 0)
+    return hipSuccess;
+  if (kind == 1)
+    hipLaunchKernelGGL(flux_error_kernel<1>, dim3((n + 255) / 256), dim3(256), 0, st, s1, sumsq, n, numRays, out);
+  else
+    hipLaunchKernelGGL(flux_error_kernel<0>, dim3((n + 255) / 256), dim3(256), 0, st, s1, sumsq, n, numRays, out);
+  return hipGetLastError();
+}
+
 // un-permute the leaf-ordered accumulators into the caller's primitive order.
 // Overflow is DETECTED, never silent: the accumulators are 64-bit fixed point (2^-40 per unit), summed over the replicas
 // here and — as SIGNED int64 — over the ranks of a multi-GPU apply afterwards.  A primitive's sum must therefore stay

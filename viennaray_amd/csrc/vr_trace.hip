@@ -28,6 +28,7 @@
 //                        and stateful generator
 //   vr_trace.hip         this file: the library's tables of kernels and their launchers, or — compiled as a run-time
 //                        module (VR_USER_MODULE, vr_models.cpp) — the module section
+//   vr_trace_stats.hip   the library's trace kernels with flux statistics compiled in, a table and launchers of their own
 //   vr_diag.hip          the diagnostic kernels of the vr_debug_* entry points
 //   vr_setup.hip         scene set-up (with its exclusive scan) and the results stage (flux gather, normalisation)
 // A run-time module is compiled from this file and what it includes: the Makefile's MODEL_SRCS names those files once.
@@ -120,11 +121,15 @@ static StreamKernel trace_kernel_for(int D, int geo, int particle, int mode) {
 
 hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid,
                         hipStream_t s) {
+  if (particle >= P_EXT_STATS) // (flux statistics: the kernels of vr_trace_stats.hip; this table is the statistics-off one)
+    return launch_trace_stats(p, D, geo, particle, mode, grid, s);
   hipLaunchKernelGGL(trace_kernel_for(D, geo, particle, mode), dim3(grid), dim3(VR_BLOCK), mode == MODE_SMALL ? p.smallBytes : 0, s, p);
   return hipGetLastError();
 }
 
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes) {
+  if (particle >= P_EXT_STATS)
+    return trace_stats_blocks_per_cu(D, geo, particle, mode, smallBytes);
   int nb = 0;
   const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel_for(D, geo, particle, mode), VR_BLOCK,
                                                                     mode == MODE_SMALL ? smallBytes : 0);

@@ -13,6 +13,8 @@ namespace vr {
 
 // fixed-point weight: 2^40 per unit (order-independent integer accumulation)
 __device__ __forceinline__ u64 weight_fx(float w) { return (u64)((double)w * 1099511627776.0 + 0.5); }
+// flux statistics: the square of a credited value, taken in double and quantised like the value itself
+__device__ __forceinline__ u64 weight_sq_fx(float w) { return (u64)((double)w * (double)w * 1099511627776.0 + 0.5); }
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
   unsigned long long s = v;
@@ -201,8 +203,12 @@ trace_kernel(const TraceParams p) {
   // PARTICLE 0 / 1: DiffuseParticle / SpecularParticle compiled in.  PARTICLE 2 (P_EXT): the
   // extended kernel — particle kind, data labels, WDIST crediting and mean-free-path scattering
   // decided at run time from TraceParams (vr_particles.hpp)
-  constexpr bool EXT = PARTICLE >= P_EXT;           // (P_EXT, P_EXT_FULL)
-  constexpr bool EXT_FULL = PARTICLE == P_EXT_FULL; // ... with the coned-cosine model, WDIST crediting and the mean free path
+  constexpr bool EXT = PARTICLE >= P_EXT;           // (P_EXT, P_EXT_FULL and their twins with flux statistics)
+  constexpr bool EXT_FULL = PARTICLE == P_EXT_FULL || PARTICLE == P_EXT_FULL_STATS; // ... with the coned-cosine model, WDIST crediting and the mean free path
+  // Flux statistics (vr_set_flux_statistics): every credit(0, v) of the model's collide also adds weight_sq_fx(v) to plane
+  // numData (the sum of squares, 2^-40 per unit like the flux) and 1 to plane numData + 1 (the hit count, in units of ONE).
+  // Integer sums like the flux: exact, whatever the grid, the batch split or the rank count.
+  constexpr bool STATS = PARTICLE == P_EXT_STATS || PARTICLE == P_EXT_FULL_STATS;
   // per-ray state words of a stateful model (vr_particles.hpp): only a module compiled around one has them (0 in the library)
   constexpr int SW = EXT_FULL ? Particles::stateWords : 0;
   // packet-query rounds credit disks wave-uniformly from the candidate list (pq_credit) instead of
@@ -278,7 +284,7 @@ trace_kernel(const TraceParams p) {
     for (unsigned k = tid; k < p.smallNb; k += VR_BLOCK)
       li[k] = p.nbIds[k];
     unsigned long long *lf = reinterpret_cast<unsigned long long *>(sceneB + p.smallOff[4]);
-    for (unsigned k = tid; k < p.numPrims * p.numData; k += VR_BLOCK) // (one plane per data label)
+    for (unsigned k = tid; k < p.numPrims * (p.numData + (STATS ? (unsigned)VR_STAT_PLANES : 0u)); k += VR_BLOCK) // (one plane per data label)
       lf[k] = 0ull;
     if (p.primSticking) {
       float *ls = reinterpret_cast<float *>(sceneB + p.smallOff[5]);
@@ -810,6 +816,18 @@ trace_kernel(const TraceParams p) {
               const ModelCtx mctx = model_ctx(p);
               // (a coarse scene under sorted rays: a good share of the wave credits ONE disk — merged per distinct
               //  weight like the built-in particles' credits, or the 64 lanes queue up on one address in L2)
+              // (flux statistics: label 0's two companions, through the same path as the credit itself)
+              [[maybe_unused]] auto creditStats = [&](unsigned q, float v) {
+                unsigned long long *sq = fluxAcc + (size_t)p.numData * (SMALL ? p.numPrims : p.planeStride);
+                unsigned long long *hits = sq + (SMALL ? p.numPrims : p.planeStride);
+                if (aggregate && !SMALL) {
+                  credit_aggregated(sq, true, q, weight_sq_fx(v));
+                  credit_aggregated(hits, true, q, 1ull);
+                } else {
+                  atomicAdd(&sq[q], weight_sq_fx(v));
+                  atomicAdd(&hits[q], 1ull);
+                }
+              };
               auto creditTo = [&](unsigned q, float w, const V3 &nq, unsigned origId) {
                 if constexpr (SW > 0) { // (a stateful model: the ray's state and the primitive's material id too)
                   Particles::collide<EXT_FULL>(kind, mctx, rayState, w, rayDirection, nq, origId, material_of(wallS, origId),
@@ -819,6 +837,10 @@ trace_kernel(const TraceParams p) {
                                                    credit_aggregated(plane, true, q, weight_fx(v));
                                                  else
                                                    atomicAdd(&plane[q], weight_fx(v));
+                                                 if constexpr (STATS) {
+                                                   if (label == 0)
+                                                     creditStats(q, v);
+                                                 }
                                                });
                 } else {
                   Particles::collide<EXT_FULL>(kind, mctx, w, rayDirection, nq, origId, [&](int label, float v) {
@@ -827,6 +849,10 @@ trace_kernel(const TraceParams p) {
                       credit_aggregated(plane, true, q, weight_fx(v));
                     else
                       atomicAdd(&plane[q], weight_fx(v));
+                    if constexpr (STATS) {
+                      if (label == 0)
+                        creditStats(q, v);
+                    }
                   });
                 }
               };
@@ -1008,13 +1034,24 @@ trace_kernel(const TraceParams p) {
 #pragma unroll
               for (int l = 0; l < VR_MAX_LABELS; ++l)
                 val[l] = 0.f;
+              [[maybe_unused]] u64 statSq = 0ull, statHits = 0ull; // (flux statistics: this lane's credits to label 0 of q)
               if (sel)
                 Particles::collide<EXT_FULL>(p.particleKind, model_ctx(p), creditWf, creditDir, mk(n4.x, n4.y, n4.z),
                                              __float_as_uint(n4.w), [&](int label, float v) {
 #pragma unroll
                                                for (int l = 0; l < VR_MAX_LABELS; ++l)
                                                  val[l] = l == label ? val[l] + v : val[l];
+                                               if constexpr (STATS) {
+                                                 if (label == 0) {
+                                                   statSq += weight_sq_fx(v);
+                                                   statHits += 1ull;
+                                                 }
+                                               }
                                              });
+              if constexpr (STATS) { // (one integer wave sum and one atomic per plane, like the labels beyond the LDS sums)
+                credit_wave_sum(fluxAcc + (size_t)p.numData * p.planeStride, q, statSq);
+                credit_wave_sum(fluxAcc + (size_t)(p.numData + 1u) * p.planeStride, q, statHits);
+              }
 #pragma unroll
               for (int l = 0; l < VR_MAX_LABELS; ++l) {
                 if ((unsigned)l >= p.numData)
@@ -1227,7 +1264,7 @@ trace_kernel(const TraceParams p) {
   if (SMALL) {
     // every wave of the block has left the loop: the block's LDS accumulators go to its replica in HBM
     __syncthreads();
-    for (unsigned l = 0; l < p.numData; ++l)
+    for (unsigned l = 0; l < p.numData + (STATS ? (unsigned)VR_STAT_PLANES : 0u); ++l)
       for (unsigned k = tid; k < p.numPrims; k += VR_BLOCK)
         if (fluxAcc[(size_t)l * p.numPrims + k])
           atomicAdd(&fluxGlobal[(size_t)l * p.planeStride + k], fluxAcc[(size_t)l * p.numPrims + k]);

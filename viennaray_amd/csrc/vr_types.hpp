@@ -89,6 +89,7 @@ struct TraceParams {
   unsigned long long *fluxAcc;   // [numData][replicas][accStride] leaf order, fixed point 2^-40
   uint32_t accStride, accMask;   // replica r of the accumulators starts at fluxAcc + r * accStride; r = blockIdx & accMask
   uint32_t numData, planeStride; // data label l (TracingData vector l) lives at fluxAcc + l * planeStride
+                                 // (flux statistics: planes numData and numData + 1 are label 0's sum of squares and hit count)
   // particle plug-ins (vr_particles.hpp): run-time kind of the extended kernel instantiation
   int32_t particleKind;
   float reserved0, meanFreePath;
@@ -278,7 +279,12 @@ enum { P_DIFFUSE = 0, P_SPECULAR = 1, P_CONED_COSINE = 2, P_DIFFUSE_COSINE = 3, 
        P_EXT = 2 /* template id of the extended kernel */,
        P_EXT_FULL = 3 /* ... with the coned-cosine model, WDIST crediting and mean-free-path scattering compiled in
                          (rare options that cost every particle of the instantiation registers: 157 spilled VGPRs
-                         with them, 27 without) */ };
+                         with them, 27 without) */,
+       // ... and the two with FLUX STATISTICS compiled in (vr_set_flux_statistics): every credit to label 0 also adds to the
+       // particle's two companion planes (vr_trace_kernel.hpp: STATS).  Instantiations of their own — the ids above keep
+       // their kernels as they are — that serve EVERY particle of a statistics-on launch which is not absorbing
+       P_EXT_STATS = 4, P_EXT_FULL_STATS = 5 };
+constexpr int VR_STAT_PLANES = 2; // companion planes of a particle, behind its data labels: [numData] sum of squares, [numData + 1] hits
 
 // The modes of trace_kernel (its template parameter MODE_, an int: a module's kernels are found by mangled name;
 // vr_get_trace_mode reports these numbers).  vr_prepare.cpp chooses one per launch, vr_trace.hip maps it to a kernel.

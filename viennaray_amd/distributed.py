@@ -43,7 +43,8 @@ class GpuShard:
         """(Re-)bind the accumulator tensor.  setGeometry() drops an external binding (the
         primitive count may have changed), so this runs before every launch."""
         import torch
-        n = self.tr._n * max(1, self.tr.numData())
+        planes = self.tr.numAccumulatorPlanes() if hasattr(self.tr, "numAccumulatorPlanes") else max(1, self.tr.numData())
+        n = self.tr._n * planes
         if self.acc is None or self.acc.numel() != n:
             self.acc = torch.zeros(n, dtype=torch.int64, device=self.device)
         self.tr.bindFluxAccumulators(self.acc.data_ptr(), n)
@@ -90,7 +91,10 @@ class GpuShard:
 def distributed_apply(shard, num_rays, rank=None, world=None, group=None, run_number=None):
     """Trace this rank's slice of `num_rays` and all-reduce flux + counters (+ the data log, if a shape is set:
     counters["dataLog"] holds the int64 sums per row, value * 2^24, counters["dataLogDropped"] the dropped calls).
-    Returns (acc int64 tensor [numPrims] (sum over ranks), counters dict)."""
+    With flux statistics on (Trace.setCalculateFluxError) the companion planes travel in the same tensor, and
+    counters["hitCounts"] / counters["fluxRelativeError"] hold, per particle, the all-reduced hit counts (uint64) and the
+    relative error of the whole apply (float32; N = num_rays, not a shard's count; +inf where nothing was credited).
+    Returns (acc int64 tensor [numPrims x planes] (sum over ranks), counters dict)."""
     import torch.distributed as dist
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -129,6 +133,10 @@ def distributed_apply(shard, num_rays, rank=None, world=None, group=None, run_nu
     counters = {k: int(v) for k, v in zip(COUNTER_KEYS, cnt)}
     counters["numRays"] = int(num_rays)
     counters["allreduce_ms"] = allreduce_ms
+    tr = getattr(shard, "tr", None)
+    if tr is not None and getattr(tr, "_fluxStats", False):
+        counters["hitCounts"], counters["fluxRelativeError"] = flux_statistics_from_accumulators(
+            acc, tr._n, [len(q.getLocalDataLabels()) for q in getattr(tr, "_particles", None) or [tr._particle]], num_rays)
     log = getattr(shard, "log", None)
     if log is not None:  # every rank holds the full log: int64 sums per row, and the dropped calls
         flat = log.cpu().numpy()
@@ -154,6 +162,24 @@ def rank_report(values, group=None):
     rows = [torch.zeros_like(row) for _ in range(dist.get_world_size(group))]
     dist.all_gather(rows, row, group=group)
     return [r.cpu().tolist() for r in rows]
+
+
+def flux_statistics_from_accumulators(acc, num_prims, labels_per_particle, num_rays):
+    """Per particle the hit counts and the relative error from (summed) accumulators laid out as the tracer lays them
+    out with flux statistics on: each particle's data labels, then its sum of squares and its hit count.  The library's
+    formula (vr_get_flux_error) in float64: sigma = sqrt(max(sumsq - S1^2 / N, 0)), relative = sigma / S1, +inf at S1 == 0."""
+    a = (acc.detach().cpu().numpy() if hasattr(acc, "detach") else np.asarray(acc)).reshape(-1, num_prims)
+    hits, rel, base = [], [], 0
+    scale = 2.0 ** -FLUX_FRAC_BITS
+    for nl in labels_per_particle:
+        s1 = a[base].astype(np.float64) * scale
+        sq = a[base + nl].astype(np.float64) * scale
+        hits.append(a[base + nl + 1].astype(np.uint64))
+        sigma = np.sqrt(np.maximum(sq - s1 * s1 / float(num_rays), 0.0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel.append(np.where(a[base] == 0, np.inf, sigma / s1).astype(np.float32))
+        base += nl + 2
+    return hits, rel
 
 
 def accumulators_to_flux(acc):

@@ -11,6 +11,7 @@ the reference's tests.
 """
 import ctypes as C
 import enum
+import math
 
 import numpy as np
 
@@ -718,6 +719,74 @@ class Trace:
                                                capi.VR_NORM_NONE if norm is None else int(norm), int(numNeighbors),
                                                C.c_void_p(stream)))
         return out
+
+    # --- flux statistics: per-primitive hit counts and the Monte-Carlo error of the flux --------------------------
+    def setCalculateFluxError(self, on=True):
+        """Keep two more sums per primitive and particle alongside the flux label (vr_set_flux_statistics): the number of
+        credits and the sum of their squares.  Off by default.  A per-credit estimator: it ignores the correlation
+        between several credits of one ray to the same primitive."""
+        self._check(self._L.vr_set_flux_statistics(self._h, int(bool(on))))
+        self._fluxStats = bool(on)
+
+    def numAccumulatorPlanes(self):
+        """planes of numPrims int64 the accumulator array holds (fluxAccumulators / bindFluxAccumulators): the data labels
+        of all particles and, with flux statistics on, two more behind each particle's labels"""
+        parts = max(1, len(getattr(self, "_particles", None) or [None]))
+        return max(1, self.numData()) + (2 * parts if getattr(self, "_fluxStats", False) else 0)
+
+    def getHitCounts(self, particleIdx=0):
+        """credits to the flux label of every primitive in the last apply (uint64)"""
+        out = np.empty(self._n, dtype=np.uint64)
+        self._check(self._L.vr_get_hit_counts(self._h, int(particleIdx), C.c_void_p(out.ctypes.data), self._n))
+        return out
+
+    def getFluxSumSquares(self, particleIdx=0):
+        """sum over those credits of the squared credited value (float64, exact: acc / 2^40)"""
+        out = np.empty(self._n, dtype=np.float64)
+        self._check(self._L.vr_get_flux_sum_squares(self._h, int(particleIdx), C.c_void_p(out.ctypes.data), self._n))
+        return out
+
+    def _fluxError(self, particleIdx, kind):
+        out = np.empty(self._n, dtype=np.float32)
+        self._check(self._L.vr_get_flux_error(self._h, int(particleIdx), int(kind), C.c_void_p(out.ctypes.data), self._n))
+        return out
+
+    def getFluxRelativeError(self, particleIdx=0):
+        """sigma / S1 per primitive, +inf where nothing was credited; the same for every NormalizationType"""
+        return self._fluxError(particleIdx, 0)
+
+    def getFluxAbsoluteError(self, particleIdx=0):
+        """sigma = sqrt(max(sumsq - S1^2 / N, 0)) per primitive, in raw flux units (N: the rays of the whole apply)"""
+        return self._fluxError(particleIdx, 1)
+
+    def getFluxErrorTensor(self, particleIdx=0, kind="relative"):
+        """The relative or absolute error as a new torch.float32 tensor on the tracer's device, computed and left there
+        (vr_get_flux_error_device), ordered on the current torch stream; works after apply(collect=False)."""
+        import torch
+        if kind not in ("relative", "absolute"):
+            raise ValueError("getFluxErrorTensor: kind is 'relative' or 'absolute'")
+        dev = torch.device("cuda", self._device)
+        out = torch.empty(self._n, dtype=torch.float32, device=dev)
+        self._check(self._L.vr_get_flux_error_device(self._h, int(particleIdx), 0 if kind == "relative" else 1,
+                                                     C.c_void_p(out.data_ptr()), self._n,
+                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def getFluxErrorDevice(self, particleIdx=0, kind="relative"):
+        """the façade's name for getFluxErrorTensor"""
+        return self.getFluxErrorTensor(particleIdx, kind)
+
+    def raysForRelativeError(self, target, quantile=0.95, particleIdx=0):
+        """The ray count at which the `quantile` of the finite relative errors of the last apply would reach `target`:
+        ceil(N * (q / target)^2), N the rays of that apply (the error falls with 1 / sqrt(N))."""
+        if not target > 0:
+            raise ValueError("raysForRelativeError: target must be positive")
+        rel = self.getFluxRelativeError(particleIdx)
+        rel = rel[np.isfinite(rel)]
+        if rel.size == 0:
+            raise VrError("raysForRelativeError: no primitive received any flux in the last apply")
+        q = float(np.quantile(rel.astype(np.float64), float(quantile)))
+        return int(math.ceil(float(self.getRayTraceInfo().numRays) * (q / float(target)) ** 2))
 
     def smoothFlux(self, flux, numNeighbors=1):
         f = np.ascontiguousarray(flux, dtype=np.float32).copy()
