@@ -594,6 +594,14 @@ __device__ __forceinline__ V3 safe_inverse(const V3 &d) {
   return V3{1.0f / dx, 1.0f / dy, 1.0f / dz};
 }
 
+// The per-lane walks' slab test rounds its bounds at the magnitude of o * inv, i.e. by a few ulp of the DISTANCE to the
+// box (seven roundings: < 1.3e-6 of it once the origin is two scene extents away).  The boxes' own padding (4e-6 of the
+// scene's scale, in space) covers that only while the origin lies within a few extents of the scene, and nothing covered
+// the comparison with the closest hit so far: from far away, a box whose primitive TIES with that hit (two disks of one
+// plane, the lower original id in the box visited second) was culled when its entry bound came out an ulp above h.t.
+// The entry bound is therefore taken this much short before it is compared with the exit bound and with h.t.
+constexpr float VR_SLAB_SLACK = 1.0f - 4e-6f;
+
 // closest-hit rule: min t; ties -> boundary first, then lower original id
 __device__ __forceinline__ bool hit_update(HitRec &h, bool ok, float t, unsigned orig, unsigned q) {
   const bool take = ok && (t < h.t || (t == h.t && h.geom == 1 && orig < h.prim));
@@ -677,7 +685,7 @@ __device__ __forceinline__ void bvh_walk_lanes(const TraceParams &p, bool part, 
         const float tx0 = __builtin_fmaf(lx, inv.x, -oi.x), tx1 = __builtin_fmaf(hx, inv.x, -oi.x);
         const float ty0 = __builtin_fmaf(ly, inv.y, -oi.y), ty1 = __builtin_fmaf(hy, inv.y, -oi.y);
         const float tz0 = __builtin_fmaf(lz, inv.z, -oi.z), tz1 = __builtin_fmaf(hz, inv.z, -oi.z);
-        const float tEntry = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tnear));
+        const float tEntry = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tnear)) * VR_SLAB_SLACK;
         const float tExit = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fmaxf(tz0, tz1));
         const unsigned link = nd.w;
         const bool leaf = (link & VR_LEAF) != 0u;
@@ -850,7 +858,7 @@ __device__ __forceinline__ void pair_walk_lanes(const TraceParams &p, const uint
           const float tx0 = __builtin_fmaf(lx, inv.x, -oi.x), tx1 = __builtin_fmaf(hx, inv.x, -oi.x);
           const float ty0 = __builtin_fmaf(ly, inv.y, -oi.y), ty1 = __builtin_fmaf(hy, inv.y, -oi.y);
           const float tz0 = __builtin_fmaf(lz, inv.z, -oi.z), tz1 = __builtin_fmaf(hz, inv.z, -oi.z);
-          e0 = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tnear));
+          e0 = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tnear)) * VR_SLAB_SLACK;
           const float x0 = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fmaxf(tz0, tz1));
           hit0 = e0 <= x0 && e0 <= h.t;
         }
@@ -860,7 +868,7 @@ __device__ __forceinline__ void pair_walk_lanes(const TraceParams &p, const uint
           const float tx0 = __builtin_fmaf(lx, inv.x, -oi.x), tx1 = __builtin_fmaf(hx, inv.x, -oi.x);
           const float ty0 = __builtin_fmaf(ly, inv.y, -oi.y), ty1 = __builtin_fmaf(hy, inv.y, -oi.y);
           const float tz0 = __builtin_fmaf(lz, inv.z, -oi.z), tz1 = __builtin_fmaf(hz, inv.z, -oi.z);
-          e1 = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tnear));
+          e1 = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tnear)) * VR_SLAB_SLACK;
           const float x1 = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fmaxf(tz0, tz1));
           hit1 = e1 <= x1 && e1 <= h.t;
         }
