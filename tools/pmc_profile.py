@@ -60,9 +60,17 @@ def main_mean(per_dispatch):
     return sum(main) / len(main)
 
 
+PASS_TIMEOUT_S = 300  # one run of the program under the profiler
+
+
 def run(cmd, log):
+    """one pass under its own time limit; a pass that fails ends the whole profile (nothing more is started on the GPU)"""
     with open(log, "w") as fh:
-        return subprocess.call(cmd, stdout=fh, stderr=subprocess.STDOUT, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"))
+        rc = subprocess.call(["timeout", "-k", "10", str(PASS_TIMEOUT_S)] + cmd, stdout=fh, stderr=subprocess.STDOUT, cwd="/tmp",
+                             env=dict(os.environ, TMPDIR="/tmp"))
+    if rc != 0:
+        print(f"pass failed with status {rc}: {' '.join(cmd[:6])} ... (log: {log})", flush=True)
+        raise SystemExit(rc if 0 < rc < 256 else 1)
 
 
 def derive(o, segments):
@@ -100,15 +108,15 @@ def main():
     outdir = os.path.abspath(outdir)
     work = os.path.join(outdir, case + "_raw")
     os.makedirs(work, exist_ok=True)
-    rc = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(work, "stats"), "--"] + prog,
-             os.path.join(work, "stats.log"))
-    print(f"[{case}] stats rc={rc}", flush=True)
+    run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(work, "stats"), "--"] + prog,
+        os.path.join(work, "stats.log"))
+    print(f"[{case}] stats done", flush=True)
     for name, ctrs in PASSES:
         if name in skip:
             continue
-        rc = run(["rocprofv3", "--pmc"] + ctrs + ["--output-format", "csv", "-d", os.path.join(work, "pmc_" + name), "--"] + prog,
-                 os.path.join(work, f"pmc_{name}.log"))
-        print(f"[{case}] pmc {name} rc={rc}", flush=True)
+        run(["rocprofv3", "--pmc"] + ctrs + ["--output-format", "csv", "-d", os.path.join(work, "pmc_" + name), "--"] + prog,
+            os.path.join(work, f"pmc_{name}.log"))
+        print(f"[{case}] pmc {name} done", flush=True)
 
     # what the program says about itself
     rays = segments = None

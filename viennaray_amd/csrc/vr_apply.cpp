@@ -53,9 +53,17 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   TraceParams p = launch_params(c, L);
   p.batchFirst = first;
   p.batchCount = count;
-  uint32_t nbBatch = c->numBins;
-  size_bins(c->geo.D, count, c->raysPerBin, p, nbBatch); // (<= the grid the buffers were sized for)
-  nbBatch = std::min(nbBatch, c->numBins);
+  // (the grid of THIS launch's full batch, L.params: the particles of a list differ in it where one has relief packets)
+  const TraceParams &s = L.params;
+  uint32_t nbBatch = s.numBins;
+  size_bins(c, L.binAlign, count, c->batchCap, p, nbBatch);
+  if (nbBatch > s.numBins) { // (the aligned rule is not monotonic in the ray count: the grid the buffers were sized for)
+    // (p.looseT* stay the smaller count's: only a launch with relief reads them, and such a launch has the plain grid, which
+    //  never has more bins for fewer rays and so never comes here)
+    p.binT1 = s.binT1, p.binT2 = s.binT2, p.binTiles = s.binTiles;
+    p.binScale1 = s.binScale1, p.binBias1 = s.binBias1, p.binScale2 = s.binScale2, p.binBias2 = s.binBias2;
+    nbBatch = s.numBins;
+  }
   p.numBins = nbBatch;
   // a surface source has no sort bins: its records lie in index order in the overflow region (gen_surface_kernel),
   // which the trace kernel reads as virtual bins of binCap rays
@@ -197,7 +205,7 @@ int vr_apply_launch(vr_context *c) {
     bool placed = false;
     for (auto &g : groups) // (a stateful model's generator runs its own init: a generator pass of its own)
       if (!g[0]->userGen && !L.userGen && g[0]->absorb == L.absorb && g[0]->params.ee == L.params.ee &&
-          g[0]->params.eeGrid == L.params.eeGrid && g[0]->relief == L.relief) { // (relief: the generator's bins are laid out differently)
+          g[0]->params.eeGrid == L.params.eeGrid && g[0]->relief == L.relief && g[0]->binAlign == L.binAlign) { // (relief, binAlign: the generator's bins are laid out differently)
         g.push_back(&L);
         placed = true;
         break;
@@ -356,6 +364,14 @@ int vr_apply_finish(vr_context *c) {
       std::fprintf(stderr, "[vr] trace launch %zu: %.3f ms\n", b, m);
   }
   i.timeTraceKernel = kms * 1e-3;
+  if (c->knobs.printLaunches) // (every launch's sort-bin grid of a full batch; cells in units of gridDelta)
+    for (size_t q = 0; q < nPart; ++q) {
+      const ParticleLaunch &L = c->launches[q];
+      const BinGrid &g = L.binGrid;
+      const double d = c->geo.gridDelta > 0.f ? (double)c->geo.gridDelta : 1.0;
+      std::fprintf(stderr, "[vr] sort bins: %u (%d x %d cells), VR_BIN_ALIGN %d, aligned %d, cell %.4g x %.4g gridDelta, mean rays per bin %.1f, particle %zu\n",
+                   L.params.numBins, g.T1, g.T2, (int)c->knobs.binAlign, g.aligned, g.cell1 / d, g.cell2 / d, g.meanRays, q);
+    }
   const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
   if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)
     uint32_t sp = 0;

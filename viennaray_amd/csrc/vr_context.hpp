@@ -16,6 +16,7 @@
 #include "vr_kernels.hpp"
 #include "vr_source.hpp"
 #include "vr_types.hpp"
+#include "vr_bin_grid.hpp"
 
 namespace vr {
 
@@ -111,6 +112,7 @@ struct Knobs {
   std::optional<uint64_t> batchRays;   // VR_BATCH_RAYS >= 256: rays per batch (unset: 2^27)
   uint32_t binCap = VR_BIN_CAP;        // VR_BIN_CAP >= 8: record slots per sort bin
   uint32_t raysPerBin = 40;            // VR_RAYS_PER_BIN >= 1: rays per sort bin the grid is sized for
+  bool binAlign = true;                // VR_BIN_ALIGN (0: off): sort bins aligned with the disk lattice (3-D, disks; vr_bin_grid.hpp)
   std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
   std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
   // kernel parameters (TraceParams)
@@ -197,6 +199,8 @@ struct ParticleLaunch {
   DevBuf<int32_t> matTable;           // its (id, value) table for launch_prim_sticking: the ids, then the values' bits
   std::vector<int32_t> matTableHost;  // (staging of that upload)
   bool relief = false; // flat with relief: a second launch (looseMode, looseGrid) traces the loose bins
+  bool binAlign = false; // the sort bins follow the disk lattice where size_bins can make them (VR_BIN_ALIGN)
+  BinGrid binGrid;       // the sort-bin grid of a full batch (VR_PRINT_LAUNCHES)
   int looseMode = MODE_GENERAL;
   unsigned looseGrid = 0;
   vr_trace_info info{};
@@ -446,7 +450,7 @@ int build_scene(vr_context *c);
 int ensure_device_material_ids(vr_context *c);
 int lay_global_rows(vr_context *c, uint32_t rows, uint32_t stride);
 // vr_prepare.cpp
-void size_bins(int D, uint64_t count, uint32_t perBin, TraceParams &p, uint32_t &numBins);
+BinGrid size_bins(const vr_context *c, bool align, uint64_t count, uint32_t ovCap, TraceParams &p, uint32_t &numBins);
 void size_loose(int D, TraceParams &p);
 // vr_apply.cpp
 const ParticleLaunch &current_launch(const vr_context *c);

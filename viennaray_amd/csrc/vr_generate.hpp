@@ -7,6 +7,7 @@
 #pragma once
 #include "vr_device.hpp"
 #include "vr_types.hpp"
+#include "vr_bin_grid.hpp"
 
 namespace vr {
 
@@ -69,16 +70,7 @@ __device__ __forceinline__ unsigned part1by1(unsigned v) {
 // rays of a wavefront walk (almost) the same nodes and leaves.  Cells are
 // Morton-ordered so consecutive bins are spatial neighbours.  The key only
 // orders the work; it has no influence on any result.
-__device__ __forceinline__ float fold_unit(float u, int bc) {
-  if (bc == 1) // periodic
-    return u - floorf(u);
-  if (bc == 0) { // reflective: mirror fold with period 2
-    float v = u - 2.f * floorf(0.5f * u);
-    return v > 1.f ? 2.f - v : v;
-  }
-  return u; // ignore: clamped below
-}
-
+// (fold_unit, bin_cell and bin_index: vr_bin_grid.hpp, which the host tests compile too)
 template <int D> __device__ __forceinline__ unsigned bin_of(const TraceParams &p, const V3 &org, const V3 &dir) {
   // sort plane: the coordinate on the tracing axis where most first hits are expected
   const float keyCoord = p.keyCoord;
@@ -86,21 +78,11 @@ template <int D> __device__ __forceinline__ unsigned bin_of(const TraceParams &p
   float t = (keyCoord - p.srcCoord) / (fabsf(dr) > 1e-6f ? dr : copysignf(1e-6f, dr == 0.f ? -p.posNeg : dr));
   t = (p.debugFlags & 2u) ? 0.f : (t > 0.f ? t : 0.f); // flag 2: key on the origin instead
   const float u1 = fold_unit((getc(org, p.firstDir) + getc(dir, p.firstDir) * t - p.lo1) * p.invExt1, p.bc0);
-  int c1 = (int)(u1 * (float)p.binT1);
-  c1 = c1 < 0 ? 0 : (c1 >= p.binT1 ? p.binT1 - 1 : c1);
+  const int c1 = bin_cell(u1, p.binScale1, p.binBias1, p.binT1);
   if (D == 2)
     return (unsigned)c1;
   const float u2 = fold_unit((getc(org, p.secondDir) + getc(dir, p.secondDir) * t - p.lo2) * p.invExt2, p.bc1);
-  int c2 = (int)(u2 * (float)p.binT2);
-  c2 = c2 < 0 ? 0 : (c2 >= p.binT2 ? p.binT2 - 1 : c2);
-  // 8x8 tiles in row-major order; inside a tile the COLUMNS run in alternating directions (boustrophedon: up
-  // column 0, down column 1, ...), so consecutive bins are always adjacent cells — also from one tile to the next
-  // in a row of tiles (a tile ends bottom right, its neighbour starts bottom left).  A round of the trace kernel
-  // swallows two or three bins; with plain row-major cells one round in four straddled a row end: a packet box
-  // eight cells wide.
-  const unsigned tile = (unsigned)(c2 >> 3) * (unsigned)p.binTiles + (unsigned)(c1 >> 3);
-  const unsigned row = (unsigned)c2 & 7u, col = (unsigned)c1 & 7u;
-  return tile * 64u + (col << 3 | ((col & 1u) ? 7u - row : row));
+  return bin_index(c1, bin_cell(u2, p.binScale2, p.binBias2, p.binT2), p.binTiles);
 }
 
 // Sort key on a scene that is flat WITH RELIEF (TraceParams, round 4): the cell of the ray's PREDICTED first hit — the
@@ -140,17 +122,15 @@ template <int D> __device__ __forceinline__ unsigned bin_of_relief(const TracePa
   const float u1 = fold_unit((__builtin_fmaf(d1, t, o1) - p.lo1) * p.invExt1, p.bc0);
   const float sin2 = fmaxf(0.f, 1.f - dr * dr);
   const bool loose = thick * thick * sin2 > p.reliefTravel * p.reliefTravel * (drs * drs) || sin2 > p.reliefTanMax * p.reliefTanMax * (drs * drs);
+  // (both sets of bins of a launch with relief packets are PLAIN grids — size_ray_stream, vr_prepare.cpp: the aligned grid
+  //  measured slower here — so the key helper gets {T, 0} and the generator reads nothing the parent grid did not have)
   const int T1 = loose ? p.looseT1 : p.binT1, T2 = loose ? p.looseT2 : p.binT2, tiles = loose ? p.looseTiles : p.binTiles;
-  int c1 = (int)(u1 * (float)T1);
-  c1 = c1 < 0 ? 0 : (c1 >= T1 ? T1 - 1 : c1);
+  const int c1 = bin_cell(u1, (float)T1, 0.f, T1);
   if (D == 2)
     return (unsigned)c1 | (loose ? 0x80000000u : 0u);
   const float u2 = fold_unit((__builtin_fmaf(d2, t, o2) - p.lo2) * p.invExt2, p.bc1);
-  int c2 = (int)(u2 * (float)T2);
-  c2 = c2 < 0 ? 0 : (c2 >= T2 ? T2 - 1 : c2);
-  const unsigned tile = (unsigned)(c2 >> 3) * (unsigned)tiles + (unsigned)(c1 >> 3);
-  const unsigned row = (unsigned)c2 & 7u, col = (unsigned)c1 & 7u;
-  return (tile * 64u + (col << 3 | ((col & 1u) ? 7u - row : row))) | (loose ? 0x80000000u : 0u);
+  const int c2 = bin_cell(u2, (float)T2, 0.f, T2);
+  return bin_index(c1, c2, tiles) | (loose ? 0x80000000u : 0u);
 }
 
 // ---------------------------------------------------------------------------

@@ -40,32 +40,56 @@ static float scene_scale(const vr_context *c) {
   return scale;
 }
 
-// sort-bin grid for a batch of `count` rays: far-plane cells holding ~perBin rays each
-void size_bins(int D, uint64_t count, uint32_t perBin, TraceParams &p, uint32_t &numBins) {
-  const uint64_t target = std::max<uint64_t>(count / std::max<uint32_t>(perBin, 1u), 1);
-  if (D == 2) {
-    p.binT1 = (int)std::min<uint64_t>(target, 1u << 22);
-    p.binT2 = 1;
-    p.binTiles = 1;
-    numBins = (uint32_t)p.binT1;
-  } else {
-    p.binT1 = p.binT2 = (int)std::min<double>(4096.0, std::max(1.0, std::ceil(std::sqrt((double)target))));
-    p.binTiles = (p.binT1 + 7) / 8;
-    numBins = (uint32_t)p.binTiles * (uint32_t)p.binTiles * 64u;
+// Sort-bin grid for a batch of `count` rays whose overflow region has `ovCap` slots: far-plane cells holding ~raysPerBin
+// rays each.  A 3-D launch on disks (`align`: VR_BIN_ALIGN and the launch's geometry) gets the grid aligned with the disk
+// lattice where vr_bin_grid.hpp's rule can be met, every other one the plain grid.  The lattice's phase is the smallest
+// disk centre per axis: on a cloud made from a level set that IS a lattice line, on any other cloud any phase will do.
+BinGrid size_bins(const vr_context *c, bool align, uint64_t count, uint32_t ovCap, TraceParams &p, uint32_t &numBins) {
+  const int D = c->geo.D;
+  const BinGrid plain = bin_grid_plain(D, count, c->raysPerBin);
+  BinGrid g = plain;
+  if (align && D == 3 && c->geo.geo == 0 && c->geo.gridDelta > 0.f) {
+    BinGridIn in;
+    in.rays = count;
+    in.perBin = c->raysPerBin;
+    in.binCap = p.binCap;
+    in.ovCap = ovCap;
+    in.lo1 = c->bbLo[c->ts[1]];
+    in.hi1 = c->bbHi[c->ts[1]];
+    in.lo2 = c->bbLo[c->ts[2]];
+    in.hi2 = c->bbHi[c->ts[2]];
+    in.phase1 = c->geo.minC[c->ts[1]];
+    in.phase2 = c->geo.minC[c->ts[2]];
+    in.pitch = c->geo.gridDelta;
+    bin_grid_aligned(in, g); // (false: g is still the plain grid)
   }
+  if (!g.aligned) { // (diagnostics: the plain grid's cells)
+    g.cell1 = ((double)c->bbHi[c->ts[1]] - (double)c->bbLo[c->ts[1]]) / g.T1;
+    g.cell2 = D == 3 ? ((double)c->bbHi[c->ts[2]] - (double)c->bbLo[c->ts[2]]) / g.T2 : 0.;
+  }
+  p.binT1 = g.T1;
+  p.binT2 = g.T2;
+  p.binTiles = g.tiles;
+  p.binScale1 = g.scale1;
+  p.binBias1 = g.bias1;
+  p.binScale2 = g.scale2;
+  p.binBias2 = g.bias2;
+  // (the loose bins of a relief scene keep the plain grid's cells: size_loose)
+  p.looseT1 = std::max(1, plain.T1 / 3);
+  p.looseT2 = D == 2 ? 1 : std::max(1, plain.T2 / 3);
+  numBins = g.numBins;
+  return g;
 }
 
-// The LOOSE bins of a scene with relief (TraceParams, round 4): a grid a third as fine per axis as the tight one p.binT*
-// describes — they hold the grazing rays, about a tenth of all — whose cursors and record slots (+ an overflow region of
-// p.ovCap slots) lie behind the tight bins' in the same two buffers.
+// The LOOSE bins of a scene with relief (TraceParams, round 4): a grid a third as fine per axis as the PLAIN tight one
+// (size_bins left its cells per axis in p.looseT*) — they hold the grazing rays, about a tenth of all — whose cursors and
+// record slots (+ an overflow region of p.ovCap slots) lie behind the tight bins' in the same two buffers.
 void size_loose(int D, TraceParams &p) {
-  p.looseT1 = std::max(1, p.binT1 / 3);
   if (D == 2) {
     p.looseT2 = 1;
     p.looseTiles = 1;
     p.looseNumBins = (uint32_t)p.looseT1;
   } else {
-    p.looseT2 = std::max(1, p.binT2 / 3);
     p.looseTiles = (p.looseT1 + 7) / 8;
     p.looseNumBins = (uint32_t)p.looseTiles * (uint32_t)((p.looseT2 + 7) / 8) * 64u;
   }
@@ -79,10 +103,12 @@ struct StreamExtent {
   uint32_t numBins = 0;
   size_t slots = 0, cntWords = 0;
   size_t looseSlots = 0; // (relief) record slots of the loose bins + their overflow region
+  BinGrid grid;
 };
-static StreamExtent stream_extent(int D, uint32_t cap, uint32_t perBin, bool relief, TraceParams &p) {
+static StreamExtent stream_extent(const vr_context *c, bool align, uint32_t cap, bool relief, TraceParams &p) {
+  const int D = c->geo.D;
   StreamExtent e;
-  size_bins(D, cap, perBin, p, e.numBins);
+  e.grid = size_bins(c, align, cap, cap, p, e.numBins);
   e.slots = (size_t)e.numBins * p.binCap + cap;
   e.cntWords = (size_t)e.numBins + 1;
   if (relief) {
@@ -499,7 +525,6 @@ static int upload_source_data(vr_context *c) {
 static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState &S) {
   const Knobs &K = c->knobs;
   TraceParams &p = L.params;
-  const int D = c->geo.D;
   const uint64_t numRays = rays_of_apply(c);
   c->numRaysLast = numRays;
   uint64_t first = 0, last = numRays;
@@ -518,8 +543,12 @@ static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState 
   // 5.0 -> 4.75 ms, C2 +2.5 %)
   p.binCap = K.binCap;
   c->raysPerBin = K.raysPerBin;
-  const StreamExtent e = stream_extent(D, c->batchCap, K.raysPerBin, L.relief, p);
+  // (not on a scene with relief: the rippled plane measured 5 % slower in its tight launch with the aligned grid — its
+  //  packets are set by the predicted-hit key and the relief clip, not by the lattice: profiles/aligned_bins_ab.txt)
+  L.binAlign = K.binAlign && !L.relief;
+  const StreamExtent e = stream_extent(c, L.binAlign, c->batchCap, L.relief, p);
   c->numBins = e.numBins;
+  L.binGrid = e.grid;
   // (the loose launch numbers its slots from looseSlotBase on, and bit 31 of such a number marks a spill-queue record)
   if (L.relief && (e.slots >= (1ull << 32) || e.looseSlots >= (1ull << 31)))
     return fail(c, VR_E_STATE, "ray stream too large for 32-bit record slots (relief bins)");
@@ -538,7 +567,7 @@ static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState 
   size_t slotsWant = e.slots, binsWant = e.cntWords;
   if (c->reserveRays > span) { // vr_reserve_rays: room for the largest apply() announced
     TraceParams q = p;
-    const StreamExtent r = stream_extent(D, (uint32_t)std::min<uint64_t>(c->reserveRays, 1ull << 27), K.raysPerBin, L.relief, q);
+    const StreamExtent r = stream_extent(c, L.binAlign, (uint32_t)std::min<uint64_t>(c->reserveRays, 1ull << 27), L.relief, q);
     slotsWant = std::max(slotsWant, r.slots);
     binsWant = std::max(binsWant, r.cntWords);
   }

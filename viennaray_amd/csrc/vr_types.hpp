@@ -183,6 +183,10 @@ struct TraceParams {
   const float *surfWeights;        // [points]
   uint32_t surfRays;               // rays per source point
   float surfOffset;                // origin = position + unit normal * surfOffset
+  // ---- the sort-bin grid's cell mapping (appended; vr_bin_grid.hpp: bin_cell).  Cell of the folded position u along an
+  //      axis = (int)fma(u, binScale, binBias), clamped to [0, binT): the plain grid has {binT, 0}; the grid aligned with
+  //      the disk lattice has its first edge on a lattice line at or below lo and cells of m or 1 / k lattice cells.
+  float binScale1, binBias1, binScale2, binBias2;
 };
 
 // What a run-time SOURCE model (vr_register_source_model; vr_modules.hpp, the source-module section) sees of the launch:
