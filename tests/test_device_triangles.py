@@ -22,7 +22,7 @@ INFO_KEYS = ("numRays", "totalRaysTraced", "nonGeometryHits", "geometryHits", "p
 FACADE_FLAGS = ["-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include",
                 "-I", os.path.join(ROOT, "include", "viennaray_amd"), "-I", os.path.join(ROOT, "include")]
 FACADE_SRC = os.path.join(ROOT, "tests", "aux", "facade_device_triangles.cpp")
-INGEST_MAX_BLOCKS = 1024  # vr_setup.hip: the grid-stride cap of the ingest kernels, tiles of 256 rows
+INGEST_MAX_BLOCKS = 1024  # vr_ingest.hip: the grid-stride cap of the ingest kernels, tiles of 256 rows
 
 
 # ---------------------------------------------------------------------------------------------------------------------

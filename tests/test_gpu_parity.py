@@ -1179,7 +1179,7 @@ def test_long_bounce_chains_use_the_full_engine_state():
 
 def test_device_bvh_is_consistent_after_every_rebuild():
     """The bottom-up fit hands boxes from one workgroup to another with atomic stores and a
-    wait instead of an L2 write-back fence (vr_setup.hip, fit_kernel): every internal box must
+    wait instead of an L2 write-back fence (vr_bvh.hip, fit_kernel): every internal box must
     still be exactly the union of its children's, on a big scene, on every rebuild."""
     pts, nrm = vr.io.plane_grid(700, 1.0)
     rng = np.random.default_rng(3)

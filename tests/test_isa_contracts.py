@@ -12,10 +12,10 @@ CSRC = os.path.join(ROOT, "viennaray_amd", "csrc")
 
 @pytest.fixture(scope="module")
 def setup_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "vr_setup.s"
+    out = tmp_path_factory.mktemp("isa") / "vr_bvh.s"
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                            "-fno-fast-math", "-S", "--cuda-device-only", "-o", str(out),
-                           os.path.join(CSRC, "vr_setup.hip")], stderr=subprocess.DEVNULL)
+                           os.path.join(CSRC, "vr_bvh.hip")], stderr=subprocess.DEVNULL)
     return open(out).read()
 
 

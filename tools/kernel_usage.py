@@ -2,8 +2,9 @@
 """Register / LDS / scratch budget of every trace and generator kernel, from hipcc's
 -Rpass-analysis=kernel-resource-usage remarks.
 usage: hipcc ... -Rpass-analysis=kernel-resource-usage -c vr_trace.hip 2> usage.txt; tools/kernel_usage.py usage.txt
-(three .hip files hold kernels: vr_trace.hip has the generators and the trace kernels, vr_diag.hip the diagnostic
-kernels, vr_setup.hip the scene set-up and the results stage; the remarks of any of them, or of all, will do)"""
+(vr_trace.hip has the generators and the trace kernels, vr_diag.hip the diagnostic kernels; the scene set-up is in
+vr_bvh.hip and vr_sort.hip, the fields in vr_fields.hip, the device-resident inputs in vr_ingest.hip, the results stage
+in vr_post.hip; the remarks of any of them, or of all, will do)"""
 import re
 import subprocess
 import sys

@@ -6,8 +6,8 @@ from the kernel's ISA compiled with line tables, weighted by trip counts.
         viennaray_amd/csrc/vr_trace.hip -o k.s
     tools/salu_inventory.py k.s [mangled kernel name]
 
-(Three .hip files hold kernels: vr_trace.hip — the generators of vr_generate.hpp and the trace kernels of
-vr_trace_kernel.hpp — vr_diag.hip and vr_setup.hip.  The trace kernels are in vr_trace.hip's assembly.)
+(vr_trace.hip holds the generators of vr_generate.hpp and the trace kernels of vr_trace_kernel.hpp; the other .hip files
+— its header has the map — hold none of them.  The trace kernels are in vr_trace.hip's assembly.)
 
 (The tool prints the kernel's instruction count: compare it with tools/spill_by_depth.py on the plain build — line
 tables can move a kernel's register allocation, and an inventory of other code than the library's is worthless.)

@@ -1,5 +1,5 @@
 // vr_api.cpp — the C ABI (include/viennaray_amd.h) on top of the host setup (vr_host.cpp) and the HIP kernels
-// (vr_trace.hip, vr_setup.hip).  This file: create / destroy and the setters.  The rest of the ABI, by stage:
+// (the .hip files: vr_trace.hip has their map).  This file: create / destroy and the setters.  The rest of the ABI, by stage:
 //   vr_context.hpp  struct vr_context and what the files below share
 //   vr_source.hpp   RaySource: the ray source in force, its one transition, the questions the stages ask about it
 //   vr_source.cpp   the setters of the ray sources (grid, host rays, surface source, source model)
@@ -261,7 +261,7 @@ int vr_set_triangles(vr_context *c, const float *verts, uint32_t nverts, const u
   return VR_OK;
 }
 
-// vr_set_triangles for a mesh that lives on the device, in two passes (vr_setup.hip).  The first reads the caller's
+// vr_set_triangles for a mesh that lives on the device, in two passes (vr_ingest.hip).  The first reads the caller's
 // buffers only — box of all vertices, lowest triangle with an index out of range — and its seven words are the call's one
 // synchronisation with the host; nothing resident is touched before they say that the mesh is good.  The second copies
 // both buffers and makes the normals and areas of host_set_triangles.

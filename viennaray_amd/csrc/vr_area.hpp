@@ -2,7 +2,7 @@
 //
 // Restates rayGeometryDisk.hpp:266-354 (computeDiskAreas) and
 // rayDiskBoundingBoxIntersector.hpp:39-432 (DiskBoundingBoxXYIntersector).  ONE source for the
-// device kernel (vr_setup.hip: disk_areas_kernel, one thread per disk) and for the host
+// device kernel (vr_post.hip: disk_areas_kernel, one thread per disk) and for the host
 // validation path (VR_HOST_BUILD=1): float operations in the reference's order, no contraction,
 // glibc's acosf / sinf reproduced bit for bit (vr_libm.hpp), IEEE sqrt and division — so both
 // give the bits the reference's CPU loop gives, and the CPU oracle (an independent restatement

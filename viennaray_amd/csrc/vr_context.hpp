@@ -353,7 +353,7 @@ struct vr_context {
   // elements); a block credits replica blockIdx & (accReplicas-1): small scenes would
   // otherwise serialise every credit of the chip on a handful of cache lines
   uint32_t accReplicas = 1, accStride = 0;
-  // device-side setup (vr_setup.hip)
+  // device-side setup (vr_ingest.hip, vr_bvh.hip, vr_sort.hip)
   DevBuf<float> dDisk4, dNormal3, dPoints3, dVerts, dBox, dSBox, dNodeBox;
   DevBuf<float> dTriAreas;                // a device-set mesh's areas, written by launch_pack_mesh only (compute_areas copies them into dAreas)
   DevBuf<unsigned long long> dIngestKeys; // launch_ingest_disks' / launch_scan_mesh's block partials

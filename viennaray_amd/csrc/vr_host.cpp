@@ -109,7 +109,7 @@ GeometryDesc host_set_disks(HostGeometry &g, const float *pts, const float *nrm,
       d.maxC[k] = std::max(d.maxC[k], tmax[t][k]);
     }
   // the neighbourhood (rayGeometryDisk.hpp:191-192, radius = 2 * disk radius) is built
-  // on the device with the BVH (vr_setup.hip); the host version is a validation path
+  // on the device with the BVH (vr_bvh.hip); the host version is a validation path
   g.nbOff.clear();
   g.nbIds.clear();
   g.verts.clear();
@@ -505,7 +505,7 @@ void host_build_bvh(const HostGeometry &g, Bvh &bvh, float mortonAniso) {
     }
   // Morton codes of the box centres
   std::vector<uint64_t> code(n);
-  float inv[3]; // (cells in the scene box's proportions, at most mortonAniso : 1 — as morton_kernel, vr_setup.hip)
+  float inv[3]; // (cells in the scene box's proportions, at most mortonAniso : 1 — as morton_kernel, vr_bvh.hip)
   {
     const float extMax = std::max(std::max(shi[0] - slo[0], shi[1] - slo[1]), shi[2] - slo[2]);
     for (int k = 0; k < 3; ++k) {

@@ -29,26 +29,27 @@ hipError_t launch_debug_process_hit(const TraceParams &p, int D, const float *or
                                     hipStream_t s);
 hipError_t launch_debug_rng(unsigned seed32, unsigned count, unsigned long long *scratch, unsigned long long *out,
                             hipStream_t s);
-// device-side setup (vr_setup.hip)
-// in-place exclusive scan; tmp: >= 2 * ceil(n / 2048) + 2 words
-hipError_t launch_scan(unsigned *data, unsigned n, unsigned *tmp, hipStream_t s);
+// scene build: LBVH, bvh_check, 16-byte and pair nodes, neighbourhood CSR (vr_bvh.hip)
 hipError_t launch_setup_bvh(const SetupParams &s, unsigned *scanTmp, hipStream_t st);
 hipError_t launch_fit_bvh(const SetupParams &s, hipStream_t st);
 hipError_t launch_bvh_check(const SetupParams &s, unsigned *bad, hipStream_t st);
-hipError_t launch_smooth_flux(const float *fluxIn, float *fluxOut, const float *normal3, const uint32_t *nbOff,
-                              const uint32_t *nbIds, const uint32_t *order, const uint32_t *leafOfOrig, unsigned n,
-                              unsigned *overflow, hipStream_t st);
-hipError_t launch_smooth_wide(const float *fluxIn, float *fluxOut, const float *normal3, const SetupParams &s, float dist,
-                              unsigned *overflow, hipStream_t st);
 hipError_t launch_quantize_nodes(const float *nodes, unsigned numNodes, const float *base3, const float *scale3,
                                  uint32_t *qnodes, uint32_t *pnodes, hipStream_t st);
 hipError_t launch_setup_neighbors(const SetupParams &s, int pass, hipStream_t st);
-
-// 64-ary box tree for the packet query (vr_setup.hip)
+// ... and the 64-ary box tree for the packet query
 size_t wide_tree_entries(unsigned n);
 hipError_t launch_wide_tree(const SetupParams &s, unsigned *out3, hipStream_t st);
+// sort and scan (vr_sort.hip)
+// in-place exclusive scan; tmp: >= 2 * ceil(n / 2048) + 2 words
+hipError_t launch_scan(unsigned *data, unsigned n, unsigned *tmp, hipStream_t s);
+// n (key, value) pairs of A sorted by key (stable; 8 passes of 8 bits ping-pong with B and end in A); sortTable: 256 *
+// ceil(n / 1024) words, scanTmp: launch_scan's tmp for that many; a failed launch is left to the caller's hipGetLastError
+hipError_t launch_sort_pairs(unsigned long long *keysA, unsigned *valsA, unsigned long long *keysB, unsigned *valsB,
+                             unsigned n, unsigned *sortTable, unsigned *scanTmp, hipStream_t st);
+// height field and relief field over the source plane (vr_fields.hip)
 hipError_t launch_height_field(const HeightFieldParams &q, hipStream_t st);
 hipError_t launch_relief_field(const ReliefParams &q, hipStream_t st);
+// device-resident inputs (vr_ingest.hip)
 hipError_t launch_disk4(const float *points3, unsigned n, float radius, int D, float *disk4, hipStream_t st);
 // device-resident disk geometry (vr_set_disks_device): the caller's DEVICE rows (ld = 2 or 3 floats) -> points3, normal3,
 // disk4 and the box of the first D columns, bounds6 = {min xyz, max xyz} (bit-equal to host_set_disks'); partials:
@@ -71,8 +72,8 @@ hipError_t launch_pack_mesh(const float *verts, unsigned nverts, const unsigned 
 size_t sort_plane_partials_entries();
 hipError_t launch_sort_plane(int geo, const float *disk4, const float *normal3, const float *verts, const unsigned *tris,
                              unsigned n, int axis, float lo, float hi, double *partials, double *hist512, hipStream_t st);
-// device-resident inputs of a time step (vr_setup.hip).  launch_global_row: one row of the global data, zero-padded to the
-// stride; launch_global_relayout: the rows at another stride / row count, zeros where there was nothing
+// device-resident inputs of a time step.  launch_global_row: one row of the global data, zero-padded to the stride;
+// launch_global_relayout: the rows at another stride / row count, zeros where there was nothing
 hipError_t launch_global_row(const float *src, unsigned n, float *dst, unsigned stride, hipStream_t st);
 hipError_t launch_global_relayout(const float *src, unsigned oldRows, unsigned oldStride, float *dst, unsigned newRows,
                                   unsigned newStride, hipStream_t st);
@@ -84,7 +85,12 @@ hipError_t launch_prim_sticking(const unsigned *order, const int *ids, unsigned 
 // row * 4 + {0 position, 1 normal, 2 weight} that fails vr_set_surface_source's checks, all ones if none does
 hipError_t launch_surface_source(const float *pos, const float *nrm, const float *wgt, unsigned n, unsigned ld,
                                  float *pos3, float *nrm3, float *w, unsigned long long *bad, hipStream_t st);
-// post-processing on the device (vr_setup.hip)
+// the results stage: smoothing, areas, normalisation, statistics, gather (vr_post.hip)
+hipError_t launch_smooth_flux(const float *fluxIn, float *fluxOut, const float *normal3, const uint32_t *nbOff,
+                              const uint32_t *nbIds, const uint32_t *order, const uint32_t *leafOfOrig, unsigned n,
+                              unsigned *overflow, hipStream_t st);
+hipError_t launch_smooth_wide(const float *fluxIn, float *fluxOut, const float *normal3, const SetupParams &s, float dist,
+                              unsigned *overflow, hipStream_t st);
 hipError_t launch_disk_areas(const float *disk4, const float *normal3, unsigned n, const AreaParams &p, float *out,
                              hipStream_t st);
 hipError_t launch_flux_from_acc(const unsigned long long *acc, unsigned n, float *flux, hipStream_t st);

@@ -30,7 +30,12 @@
 //                        module (VR_USER_MODULE, vr_models.cpp) — the module section
 //   vr_trace_stats.hip   the library's trace kernels with flux statistics compiled in, a table and launchers of their own
 //   vr_diag.hip          the diagnostic kernels of the vr_debug_* entry points
-//   vr_setup.hip         scene set-up (with its exclusive scan) and the results stage (flux gather, normalisation)
+//   vr_bvh.hip           scene build: LBVH, 64-ary box tree, neighbourhood CSR, bvh_check
+//   vr_sort.hip          the radix sort of the build and the exclusive scan
+//   vr_fields.hip        height field and relief field over the source plane (every prepare)
+//   vr_ingest.hip        device-resident inputs: disks, meshes, sort-plane histogram, global data, sticking, surface source
+//   vr_post.hip          the results stage: smoothing, areas, flux gather, normalisation, statistics
+//   vr_setup_common.hpp  private to those five: the ordered-uint trick
 // A run-time module is compiled from this file and what it includes: the Makefile's MODEL_SRCS names those files once.
 #include <hip/hip_runtime.h>
 

@@ -204,7 +204,7 @@ struct SourceCtx {
   float params[VR_SOURCE_PARAMS];  // vr_set_source_model's parameters, zeros behind those given
 };
 
-// Relief field over the source plane (vr_setup.hip: relief_field_kernel): per fine tile the [lo, hi] range — along the
+// Relief field over the source plane (vr_fields.hip: relief_field_kernel): per fine tile the [lo, hi] range — along the
 // source axis, padded — of every primitive whose (padded) box meets the tile.  A ray can only meet geometry inside a
 // tile while its own height is within that range: relief_clip (vr_device.hpp) walks the tiles under a ray and returns
 // the stretch that covers all such tiles, which replaces the clip to the SCENE box in the packet query of the
@@ -226,7 +226,7 @@ struct ReliefParams {
                             //     that would be loose there: T^2 / (T^2 + travel^2), T the tile's largest fine thickness
 };
 
-// Height field over the source plane (vr_setup.hip: height_field_kernel): per tile of side `tile` the highest point —
+// Height field over the source plane (vr_fields.hip: height_field_kernel): per tile of side `tile` the highest point —
 // along the source axis, towards the source — of any primitive that reaches into the tile or one of its eight
 // neighbours, plus a rounding margin.  A ray that is above it from tnear on, and rises above the whole scene before it
 // has travelled one tile sideways, cannot meet the geometry (trace_kernel, "segments that rise clear").
@@ -241,7 +241,7 @@ struct HeightFieldParams {
   float *field;         // nx * ny: the 3 x 3 dilation of raw
 };
 
-// device-side scene setup (vr_setup.hip)
+// device-side scene setup (vr_bvh.hip)
 // Morton grid of the LBVH: the cell is the scene box's proportions, but at most VR_MORTON_ANISO : 1 (see morton_kernel)
 constexpr float VR_MORTON_ANISO = 2.0f;
 constexpr unsigned VR_NB_KEEP = 24; // ids the one-pass neighbourhood query keeps per primitive (more: the two-pass path)
