@@ -150,7 +150,7 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
       VR_HIP(c, hipModuleLaunchKernel(L.userKernel, gridBatch, 1, 1, VR_BLOCK, 1, 1, L.traceMode == MODE_SMALL ? p.smallBytes : 0, c->stream,
                                       args, nullptr));
     } else if (tight) {
-      VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.traceMode, gridBatch, c->stream));
+      VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.kernel_mode(), gridBatch, c->stream));
     }
     VR_HIP(c, hipEventRecord(k1, c->stream));
     ++traceNo;
@@ -371,6 +371,9 @@ int vr_apply_finish(vr_context *c) {
       const double d = c->geo.gridDelta > 0.f ? (double)c->geo.gridDelta : 1.0;
       std::fprintf(stderr, "[vr] sort bins: %u (%d x %d cells), VR_BIN_ALIGN %d, aligned %d, cell %.4g x %.4g gridDelta, mean rays per bin %.1f, particle %zu\n",
                    L.params.numBins, g.T1, g.T2, (int)c->knobs.binAlign, g.aligned, g.cell1 / d, g.cell2 / d, g.meanRays, q);
+      // (the scene's fact, and whether this launch ran the uniform-disk kernel on it)
+      std::fprintf(stderr, "[vr] uniform disks: scene %d, VR_UNIFORM_DISKS %d, launch %d, particle %zu\n", (int)c->uniformDisks,
+                   (int)c->knobs.uniformDisks, (int)L.uniformDisks, q);
     }
   const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
   if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)

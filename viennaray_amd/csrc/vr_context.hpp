@@ -113,6 +113,7 @@ struct Knobs {
   uint32_t binCap = VR_BIN_CAP;        // VR_BIN_CAP >= 8: record slots per sort bin
   uint32_t raysPerBin = 40;            // VR_RAYS_PER_BIN >= 1: rays per sort bin the grid is sized for
   bool binAlign = true;                // VR_BIN_ALIGN (0: off): sort bins aligned with the disk lattice (3-D, disks; vr_bin_grid.hpp)
+  bool uniformDisks = true;            // VR_UNIFORM_DISKS (0: off): the absorbing flat-scene kernel's uniform-disk variant where the scene allows it
   std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
   std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
   // kernel parameters (TraceParams)
@@ -187,6 +188,11 @@ struct ParticleLaunch {
   bool stats = false;    // flux statistics: two companion planes behind its data labels (planes numData, numData + 1)
   unsigned grid = 0;
   int traceMode = MODE_GENERAL, kernelParticle = 0;
+  // every disk of the scene has one normal and one radius (vr_context::uniformDisks), VR_UNIFORM_DISKS is on and the
+  // launch runs the library's 3-D MODE_ABSORB_FLAT kernel: it runs that kernel's uniform-disk variant, with the
+  // normal, the radius and the square-root threshold in its frame (VR_F_UD_*)
+  bool uniformDisks = false;
+  int kernel_mode() const { return uniformDisks ? (int)MODE_ABSORB_FLAT_UNIFORM : traceMode; } // the mode launch_trace takes
   bool absorb = false;
   bool recExtra = false; // the records' side array (TraceParams::recExtra)
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
@@ -371,6 +377,11 @@ struct vr_context {
   float qbase[3] = {0, 0, 0}, qscale[3] = {0, 0, 0}; // frame of the 16-byte nodes
   float keyCoord = 0.f;          // sort plane of the ray stream on the tracing axis (host_sort_plane)
   float keyShare = 1.f;          // share of the surface shown to the source that lies in that plane
+  // uniform disks (build_scene, once per geometry commit: launch_uniform_disks over the packed records): every disk has
+  // record 0's normal and radius, word for word.  false for a mesh and for an empty scene.
+  bool uniformDisks = false;
+  uint32_t uniformWords[4] = {0, 0, 0, 0}; // ... those words: n.x, n.y, n.z, radius
+  DevBuf<uint32_t> dUniformDisks;          // launch_uniform_disks' five words
   SetupParams lastSetup{};       // buffers of the resident device build (vr_debug_bvh_check)
   bool haveSetup = false;
   int builtOrderAxis = -1;       // child order of the resident BVH (source side first)

@@ -381,6 +381,11 @@ enum { VR_F_SRC_PLANE = 96, VR_F_RAYDIR = 97, VR_F_FIRSTDIR = 98, VR_F_SECONDDIR
        // the height field over the source plane (HeightFieldParams; NX = 0: none)
        VR_F_HF_LO1 = 118, VR_F_HF_LO2 = 119, VR_F_HF_INVT = 120, VR_F_HF_TILE = 121, VR_F_HF_TOP = 122, VR_F_HF_SIGN = 123,
        VR_F_HF_NX = 124, VR_F_HF_NY = 125, VR_F_HF_PTR_LO = 126, VR_F_HF_PTR_HI = 127,
+       // a launch with uniform disks (ParticleLaunch::uniformDisks; read only by trace_kernel MODE_ABSORB_FLAT_UNIFORM): the
+       // one normal of every disk, their one radius, and the threshold T with radius > sqrtf(x) <=> x < T for every x
+       // (vr_uniform_disks.hpp).  They share the height field's first words: that field is built for launches that go on
+       // after a hit, this kernel is an absorbing one (write_launch_frame fills one or the other)
+       VR_F_UD_N = VR_F_HF_LO1 /* n.x, n.y, n.z */, VR_F_UD_RADIUS = VR_F_HF_TILE, VR_F_UD_T = VR_F_HF_TOP,
        // the relief field's fine tiles (ReliefParams; NX = 0: none): relief_clip below
        VR_F_RF_LO1 = 128, VR_F_RF_LO2 = 129, VR_F_RF_INVT = 130, VR_F_RF_TILE = 131, VR_F_RF_NX = 132, VR_F_RF_NY = 133,
        VR_F_RF_PTR_LO = 134, VR_F_RF_PTR_HI = 135,
@@ -1043,6 +1048,10 @@ __device__ __forceinline__ bool local_disc_hit(const V3 &ro, const V3 &rd, const
 __device__ __forceinline__ bool local_disc_hit_lds(const V3 &ro, const V3 &rd, const float4 &c4, const V3 &n);
 __device__ __forceinline__ bool hit_disc_lds(const V3 &o, const V3 &d, float tnear, const float4 &c4, const V3 &n, float &tOut);
 __device__ __forceinline__ bool hit_update_lds(HitRec &h, bool ok, float t, unsigned orig, unsigned q);
+__device__ __forceinline__ bool hit_disc_uniform(const V3 &o, const V3 &d, float tnear, const V3 &c, const V3 &n, float divisor,
+                                                 float radius, float &tOut);
+__device__ __forceinline__ bool local_disc_hit_uniform(const V3 &ro, const V3 &rd, const V3 &c, const V3 &n, float prod, float nro,
+                                                       float thresh);
 
 __device__ __forceinline__ float lane_bcast(float v, int srcLane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), srcLane));
@@ -1099,7 +1108,10 @@ constexpr unsigned VR_PQ_RECORDS = 2 * 52;
 // box — from LDS, no node load — and goes straight to the primitive records of those that meet it: the very nodes an
 // exact descent would have found.  The candidates are filtered with the round's own box as before: bit-identical.
 // LEAN (the 3-D absorbing flat-scene kernels): the candidate loop's disc tests in their branch-free forms (hit_disc_lds)
-template <int GEO, bool CREDIT, bool FRAME_LDS = false, bool KEEPQ = false, bool RELIEF = false, bool CACHE = false, bool LEAN = false>
+// UNIFORM (LEAN, for a launch whose disks all have one normal and one radius — the frame's VR_F_UD_*): what those tests
+// take from the ray and the normal alone is computed once per round, before the candidate loop (hit_disc_uniform)
+template <int GEO, bool CREDIT, bool FRAME_LDS = false, bool KEEPQ = false, bool RELIEF = false, bool CACHE = false, bool LEAN = false,
+          bool UNIFORM = false>
 __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, const V3 &o, const V3 &d, float tnear,
                                               HitRec &h, volatile VR_LDS unsigned *lst, PqCands &cd,
                                               const float *__restrict__ wallS, volatile VR_LDS float *cboxes, float tWall VR_DIAG_ARGS) {
@@ -1332,6 +1344,20 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
       return false;
     }
   }
+  // UNIFORM: every candidate has the frame's normal and radius, so the three dot products of the ray with the normal are
+  // the same for all of them — the same functions on the same operands as in hit_disc_lds / local_disc_hit_lds, hence
+  // the same bits — and the neighbour test's square root becomes a comparison with the frame's threshold
+  V3 un = mk(0.f, 0.f, 0.f);
+  float uRadius = 0.f, uThresh = 0.f, uDivisor = 0.f, uProd = 0.f, uNro = 0.f;
+  if constexpr (UNIFORM) {
+    static_assert(GEO == 0 && LEAN, "the uniform-disk tests are forms of the branch-free disc tests");
+    un = mk(wallS[VR_F_UD_N], wallS[VR_F_UD_N + 1], wallS[VR_F_UD_N + 2]);
+    uRadius = wallS[VR_F_UD_RADIUS];
+    uThresh = wallS[VR_F_UD_T];
+    uDivisor = edot(d, un);
+    uProd = vdot(un, d);
+    uNro = vdot(un, o);
+  }
   unsigned tests = 0;
   VR_PQ_MARK(14); // (diag: the descent)
   for (unsigned j = 0; j < nF; ++j) {
@@ -1370,7 +1396,22 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
       }
       const unsigned qq = first + (unsigned)k;
       float t;
-      if (GEO == 0) {
+      if constexpr (UNIFORM) { // (the centre and the original id alone are the candidate's own)
+        const V3 cc = mk(lane_bcast(r0.x, k), lane_bcast(r0.y, k), lane_bcast(r0.z, k));
+        const unsigned orig = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(r1.w), k);
+        const bool ok = hit_disc_uniform(o, d, tnear, cc, un, uDivisor, uRadius, t);
+        const bool took = hit_update_lds(h, part & ok, t, orig, qq);
+        if (CREDIT) {
+          const int c = (int)tests;
+          cd.mine = took ? (unsigned)c : cd.mine;
+          if ((int)lane == k) { // (the records as crediting reads them: the lane's own r0 / r1)
+            cd.rec[c] = mk_u4(qq, __float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r0.z));
+            cd.rec[VR_PQ_NRM + c] = mk_u4(__float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), __float_as_uint(r0.w));
+          }
+          cd.local |= (unsigned long long)(part & local_disc_hit_uniform(o, d, cc, un, uProd, uNro, uThresh)) << c;
+          cd.count = tests + 1u;
+        }
+      } else if (GEO == 0) {
         const float4 c4 = make_float4(lane_bcast(r0.x, k), lane_bcast(r0.y, k), lane_bcast(r0.z, k), lane_bcast(r0.w, k));
         const V3 n = mk(lane_bcast(r1.x, k), lane_bcast(r1.y, k), lane_bcast(r1.z, k));
         const unsigned orig = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(r1.w), k);
@@ -1451,6 +1492,29 @@ __device__ __forceinline__ bool local_disc_hit_lds(const V3 &ro, const V3 &rd, c
   hp.z = hp.z - c.z;
   const float dist = sqrtf(vdot(hp, hp));
   return !(prod > 0.f) & !(fabsf(prod) < 1e-6f) & !(tt <= 0.f) & (c4.w > dist);
+}
+// hit_disc_lds / local_disc_hit_lds for a cloud whose disks all have the normal n and one radius (pq_hit_packet UNIFORM).
+// divisor = edot(d, n), prod = vdot(n, rd) and nro = vdot(n, ro) are the caller's, computed once per ray and round; every
+// other operation is the one above, in its order.  thresh is the smallest float x with sqrtf(x) >= radius: the correctly
+// rounded square root is monotone, so radius > sqrtf(x) <=> x < thresh for every x (an infinity or a NaN: both false).
+__device__ __forceinline__ bool hit_disc_uniform(const V3 &o, const V3 &d, float tnear, const V3 &c, const V3 &n, float divisor,
+                                                 float radius, float &tOut) {
+  const V3 co = V3{c.x - o.x, c.y - o.y, c.z - o.z};
+  const float t = edot(co, n) / divisor;
+  const V3 p = V3{o.x + d.x * t - c.x, o.y + d.y * t - c.y, o.z + d.z * t - c.z};
+  const float dist2 = edot(p, p);
+  tOut = t;
+  return (divisor != 0.f) & (tnear <= t) & (t <= 3.402823466e+38f) & (dist2 < radius * radius);
+}
+__device__ __forceinline__ bool local_disc_hit_uniform(const V3 &ro, const V3 &rd, const V3 &c, const V3 &n, float prod, float nro,
+                                                       float thresh) {
+  const float ddneg = vdot(c, n);
+  const float tt = (ddneg - nro) / prod;
+  V3 hp = V3{rd.x * tt + ro.x, rd.y * tt + ro.y, rd.z * tt + ro.z};
+  hp.x = hp.x - c.x;
+  hp.y = hp.y - c.y;
+  hp.z = hp.z - c.z;
+  return !(prod > 0.f) & !(fabsf(prod) < 1e-6f) & !(tt <= 0.f) & (vdot(hp, hp) < thresh);
 }
 
 // rayTraceKernel.hpp:462-507 (neighbour disk test)

@@ -1,5 +1,6 @@
 // vr_fields.hip — the two fields over the source plane that every prepare builds from the resident primitive records:
-// the height field (HeightFieldParams) and the relief field (ReliefParams), both in vr_types.hpp.
+// the height field (HeightFieldParams) and the relief field (ReliefParams), both in vr_types.hpp; and the one per-scene
+// fact a geometry commit reads off those records: whether the disks are uniform (launch_uniform_disks).
 #include <hip/hip_runtime.h>
 
 #include "vr_kernels.hpp"
@@ -160,6 +161,36 @@ hipError_t launch_relief_field(const ReliefParams &q, hipStream_t st) {
   if (q.n)
     hipLaunchKernelGGL(relief_field_kernel, dim3((q.n + 255) / 256), dim3(256), 0, st, q);
   hipLaunchKernelGGL(relief_finish_kernel, dim3((q.cnx * q.cny + 255) / 256), dim3(256), 0, st, q);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// uniform disks: one normal and one radius for the whole cloud (a disk cloud made from a planar level set), compared as
+// 32-bit words (a -0 is not a +0, a NaN equals itself): where it holds, record 0's four words stand for every record's
+// ---------------------------------------------------------------------------
+__global__ void uniform_disks_kernel(const uint4 *__restrict__ recs, unsigned n, unsigned *out) {
+  const uint4 c0 = recs[0], n0 = recs[1];
+  bool same = true;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint4 c = recs[2 * (size_t)i], nn = recs[2 * (size_t)i + 1];
+    same = same && nn.x == n0.x && nn.y == n0.y && nn.z == n0.z && c.w == c0.w;
+  }
+  if (!same)
+    out[0] = 1u; // (every writer writes the same word)
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    out[1] = n0.x;
+    out[2] = n0.y;
+    out[3] = n0.z;
+    out[4] = c0.w;
+  }
+}
+
+hipError_t launch_uniform_disks(const float *prims, unsigned n, unsigned *out, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(out, 0, 5 * 4, st);
+  if (e != hipSuccess || n == 0)
+    return e;
+  const unsigned grid = (unsigned)((n + 255u) / 256u < 1024u ? (n + 255u) / 256u : 1024u);
+  hipLaunchKernelGGL(uniform_disks_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint4 *>(prims), n, out);
   return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 
 #include "vr_context.hpp"
 #include "vr_particles.hpp"
+#include "vr_uniform_disks.hpp"
 
 namespace vr {
 
@@ -610,6 +611,9 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
     L.relief = false;
     L.params.reliefCoarse = nullptr;
   }
+  // one normal and one radius for the whole cloud (build_scene: vr_context::uniformDisks): the library's 3-D absorbing
+  // flat-scene kernel in its uniform-disk variant (a run-time model's code object has no such kernel)
+  L.uniformDisks = K.uniformDisks && c->uniformDisks && L.traceMode == MODE_ABSORB_FLAT && D == 3 && c->geo.geo == 0 && sp.userModel < 0;
   int blocks = 1;
   L.userKernel = nullptr;
   L.userGen = nullptr;
@@ -630,7 +634,7 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
       nb = 2;
     blocks = std::max(1, nb);
   } else {
-    blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.traceMode, L.params.smallBytes));
+    blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.kernel_mode(), L.params.smallBytes));
   }
   // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
   // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of
@@ -944,6 +948,16 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
     f[VR_F_HF_NX] = bits(q.nx);
     f[VR_F_HF_NY] = bits(q.ny);
     addr(VR_F_HF_PTR_LO, q.field);
+  }
+  if (L.uniformDisks) { // (an absorbing launch: no height field, whose first words these are — vr_device.hpp, VR_F_UD_*)
+    if (S.heightField)
+      return fail(c, VR_E_STATE, "a launch with uniform disks has no height field: their frame words are the same");
+    float w[4];
+    std::memcpy(w, c->uniformWords, sizeof(w));
+    for (int k = 0; k < 3; ++k)
+      f[VR_F_UD_N + k] = w[k];
+    f[VR_F_UD_RADIUS] = w[3];
+    f[VR_F_UD_T] = uniform_disk_threshold(w[3]);
   }
   if (L.relief) { // the relief field's fine tiles (relief_clip, vr_device.hpp)
     const ReliefParams &q = c->rf;

@@ -139,6 +139,20 @@ static int quantize_scene(vr_context *c, const float *preNodes, const float *roo
   return VR_OK;
 }
 
+// Uniform disks (vr_context::uniformDisks): the reduction over the packed disk records on the stream, its five words
+// on their way into `words`; the caller's next synchronisation of the stream delivers them, set_uniform_disks files them.
+static int read_uniform_disks(vr_context *c, uint32_t (&words)[5]) {
+  VR_HIP(c, c->dUniformDisks.ensure(5));
+  VR_HIP(c, launch_uniform_disks(c->dPrims.p, c->geo.numPrims, c->dUniformDisks.p, c->stream));
+  VR_HIP(c, hipMemcpyAsync(words, c->dUniformDisks.p, sizeof(words), hipMemcpyDeviceToHost, c->stream));
+  return VR_OK;
+}
+static void set_uniform_disks(vr_context *c, const uint32_t (&words)[5]) {
+  c->uniformDisks = words[0] == 0u && c->geo.geo == 0 && c->geo.numPrims > 0; // (a mesh: nothing was launched)
+  for (int k = 0; k < 4; ++k)
+    c->uniformWords[k] = words[1 + k];
+}
+
 int build_scene(vr_context *c) {
   const Knobs &K = c->knobs;
   HostGeometry &g = c->geo;
@@ -204,7 +218,11 @@ int build_scene(vr_context *c) {
       VR_HIP(c, hipMemcpyAsync(c->dNbIds.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
     VR_HIP(c, hipMemcpyAsync(c->dLeafOfOrig.p, c->leafOfOrig.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
     VR_HIP(c, hipMemcpyAsync(c->dOrder.p, c->bvh.order.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    uint32_t uni[5] = {0, 0, 0, 0, 0};
+    if (disk) // (the same pass over the resident records as behind the device builder)
+      VR_TRY(read_uniform_disks(c, uni));
     VR_HIP(c, hipStreamSynchronize(c->stream));
+    set_uniform_disks(c, uni);
     c->numNodes = c->bvh.numNodes;
     c->haveWide = false; // (validation path: walks only)
     return quantize_scene(c, c->dNodes.p, c->bvh.nodes.data()); // (host builder: pre-order already)
@@ -327,10 +345,14 @@ int build_scene(vr_context *c) {
   }
   float root8[8];
   uint32_t sz = 0, bad = 0;
+  uint32_t uni[5] = {0, 0, 0, 0, 0};
+  if (disk) // (the packed records never change behind launch_setup_bvh: a re-fit below leaves them as they are)
+    VR_TRY(read_uniform_disks(c, uni));
   VR_HIP(c, hipMemcpyAsync(root8, c->dNodesPre.p, sizeof(root8), hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipMemcpyAsync(&sz, c->dSubSize.p, 4, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipMemcpyAsync(&bad, c->dBounds.p + 6, 4, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
+  set_uniform_disks(c, uni);
   c->bvhRefits = 0;
   if (bad != 0) {
     // never observed; the textbook agent-scope fences cost 3 ms per 10^6 primitives

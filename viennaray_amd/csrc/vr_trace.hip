@@ -91,6 +91,10 @@ template <int D, int GEO, int PARTICLE> static StreamKernel trace_kernel_of(int 
   constexpr bool FLAT = GEO == 0 && PARTICLE <= P_EXT; // (the flat-scene general kernels exist)
   switch (mode) {
   case MODE_ABSORB_FLAT: return trace_kernel<D, GEO, 0, MODE_ABSORB_FLAT>;
+  case MODE_ABSORB_FLAT_UNIFORM: // (3-D disks only: vr_prepare.cpp asks for it nowhere else)
+    if constexpr (D == 3 && GEO == 0)
+      return trace_kernel<3, 0, 0, MODE_ABSORB_FLAT_UNIFORM>;
+    return trace_kernel<D, GEO, 0, MODE_ABSORB_FLAT>;
   case MODE_ABSORB: return trace_kernel<D, GEO, 0, MODE_ABSORB>;
   case MODE_GENERAL_FLAT:
     if constexpr (FLAT)
@@ -110,7 +114,7 @@ template <int D, int GEO, int PARTICLE> static StreamKernel trace_kernel_of(int 
   return trace_kernel<D, GEO, PARTICLE, MODE_GENERAL>;
 }
 static StreamKernel trace_kernel_for(int D, int geo, int particle, int mode) {
-  if (mode == MODE_ABSORB_FLAT || mode == MODE_ABSORB || mode == MODE_ABSORB_RELIEF)
+  if (mode == MODE_ABSORB_FLAT || mode == MODE_ABSORB || mode == MODE_ABSORB_RELIEF || mode == MODE_ABSORB_FLAT_UNIFORM)
     particle = 0; // the reflection model is unobservable: one instantiation serves all
 #define VR_VARIANT(K, DD, GG, PP)                                                                                      \
   case K: return trace_kernel_of<DD, GG, PP>(mode);

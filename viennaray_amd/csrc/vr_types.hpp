@@ -305,8 +305,12 @@ enum TraceMode : int {
   MODE_GENERAL_RELIEF = 6, // the packet query clips its rays to the local relief (relief_clip, vr_device.hpp), not to the
                            // scene box; the generator has filed the grazing rays in loose bins, which a MODE_ABSORB /
                            // MODE_GENERAL launch of their own traces.  MODE_GENERAL_RELIEF spills the rays that go on
-  MODE_RESUME = 7          // MODE_GENERAL over those loose bins that also resumes the rays of MODE_GENERAL_RELIEF's spill
+  MODE_RESUME = 7,         // MODE_GENERAL over those loose bins that also resumes the rays of MODE_GENERAL_RELIEF's spill
                            // queue (TraceParams::spillRec)
+  MODE_ABSORB_FLAT_UNIFORM = 8 // MODE_ABSORB_FLAT's kernel for a launch whose disks all have one normal and one radius
+                           // (ParticleLaunch::uniformDisks; 3-D disks only): the per-ray terms of the candidate tests once
+                           // per round (pq_hit_packet UNIFORM).  A kernel of the library's table, never a launch's
+                           // traceMode: that stays MODE_ABSORB_FLAT (ParticleLaunch::kernel_mode)
 };
 // (MODE_GENERAL_FLAT, MODE_GENERAL_RELIEF and MODE_RESUME exist for disks and the lean particles only: otherwise MODE_GENERAL)
 
