@@ -376,7 +376,7 @@ def bvh_walk(name, family):
 #   far_tie_*: from 64 scene sizes away two overlapping disks of one plane are met at the SAME t; the lower original id
 #   wins.  Both per-lane walks compared a box's entry bound with the closest hit so far without allowance for the bound's
 #   own rounding (a few ulp of the distance): the box of the lower id, visited second, was culled when its bound came out
-#   an ulp above that t, and the higher id was returned (VR_SLAB_SLACK, vr_device.hpp).
+#   an ulp above that t, and the higher id was returned (VR_SLAB_SLACK, vr_walk.hpp).
 KNOWN_ANSWERS = {
     "far_tie_plane": ("plane", ("-0x1.2a2dbcp+5", "-0x1.67c5b8p+7", "0x1.61f1eep+10"),
                       ("0x1.2f9e92p-6", "0x1.e3ee74p-4", "-0x1.fc5350p-1"), 1, 2002, "0x1.6480eep+10"),

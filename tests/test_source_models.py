@@ -118,7 +118,7 @@ F = np.float32
 
 
 def _canon(raw):
-    """canon_f32 (vr_device.hpp): float(u64) * 2^-64, clamped below 1"""
+    """canon_f32 (vr_rng.hpp): float(u64) * 2^-64, clamped below 1"""
     f = F(np.uint64(raw)) * F(2.0 ** -64)
     return F(0.99999994) if f >= F(1.0) else f
 

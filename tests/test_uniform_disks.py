@@ -1,4 +1,4 @@
-"""Uniform disks (VR_UNIFORM_DISKS; pq_hit_packet UNIFORM, vr_device.hpp): where every disk of the scene has one normal and
+"""Uniform disks (VR_UNIFORM_DISKS; pq_hit_packet UNIFORM, vr_packet_query.hpp): where every disk of the scene has one normal and
 one radius, word for word, the 3-D absorbing flat-scene kernel computes the per-ray terms of its candidate tests once per
 round and replaces the neighbour test's square root by a comparison.  That only removes repeated work: every case that
 takes the variant runs once with VR_UNIFORM_DISKS=1 and once with =0, and the raw flux arrays are equal element for

@@ -56,11 +56,13 @@ def kernel_phases(path):
     return out
 
 
-# functions of vr_device.hpp that ARE a phase; every other function there (edot, hit_disc, ballot64, ...) and every
+# the role headers behind vr_device.hpp (its map says which holds what) whose functions can be a phase
+DEVICE_HEADERS = ("vr_math.hpp", "vr_rng.hpp", "vr_intersect.hpp", "vr_walk.hpp", "vr_packet_query.hpp")
+# functions of those headers that ARE a phase; every other function there (edot, hit_disc, ballot64, ...) and every
 # system header is a helper inlined into its caller: its instructions stay with the phase seen last
 DEVICE_FUNCS = {
     "pq_hit_packet": None,  # split: box + descent / candidate loop
-    "hit_walls_lds": "walls", "hit_walls": "walls", "wall_reachable": "walls", "hit_tri": "walls: exact test",
+    "hit_walls_from": "walls", "hit_walls_lds": "walls", "hit_walls": "walls", "wall_reachable": "walls", "hit_tri": "walls: exact test",
     "relief_clip": "packet query: box + descent", "wave_minmax6": "packet query: box + descent",
     "bvh_hit_packet": "fall-back packet / walk", "bvh_walk_lanes": "fall-back packet / walk",
     "pair_walk_lanes": "fall-back packet / walk", "process_boundary_hit": "state machine",
@@ -92,7 +94,7 @@ NOT_SALU = ("s_load", "s_buffer_load", "s_waitcnt", "s_nop", "s_barrier", "s_end
 
 
 def device_ranges(path):
-    """[(first line, last line, function name)] of the __device__ functions of vr_device.hpp"""
+    """[(first line, last line, function name)] of the __device__ functions of one header"""
     out, name, start = [], None, 0
     for i, l in enumerate(open(path), 1):
         m = re.match(r'(?:template[^\n]*>\s*)?__device__\s+(?:__forceinline__\s+)?[\w:<> \*&]+?\b(\w+)\(', l)
@@ -111,11 +113,12 @@ def main():
     kern = args[1] if len(args) > 1 else DEFAULT
     import os
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dev = device_ranges(os.path.join(here, "viennaray_amd", "csrc", "vr_device.hpp"))
+    csrc = os.path.join(here, "viennaray_amd", "csrc")
+    dev = {h: device_ranges(os.path.join(csrc, h)) for h in DEVICE_HEADERS}
     phases = kernel_phases(os.path.join(here, "viennaray_amd", "csrc", "vr_trace_kernel.hpp"))
-    src = open(os.path.join(here, "viennaray_amd", "csrc", "vr_device.hpp")).read().split("\n")
+    src = open(os.path.join(csrc, "vr_packet_query.hpp")).read().split("\n")
     # the candidate loop of pq_hit_packet starts at its "unsigned tests = 0;"
-    pq = [r for r in dev if r[2] == "pq_hit_packet"][0]
+    pq = [r for r in dev["vr_packet_query.hpp"] if r[2] == "pq_hit_packet"][0]
     pq_split = next(i for i in range(pq[0], pq[1]) if "unsigned tests = 0;" in src[i - 1])
 
     files = {}
@@ -130,8 +133,8 @@ def main():
             for name, lo, hi in phases:
                 if lo <= line <= hi:
                     return name
-        if f.endswith("vr_device.hpp"):
-            for lo, hi, fn in dev:
+        if os.path.basename(f) in dev:
+            for lo, hi, fn in dev[os.path.basename(f)]:
                 if lo <= line <= hi and fn in DEVICE_FUNCS:
                     if fn == "pq_hit_packet":
                         return "candidate loop" if line >= pq_split else "packet query: box + descent"

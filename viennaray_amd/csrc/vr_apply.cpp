@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "vr_context.hpp"
-#include "vr_device.hpp"
+#include "vr_frame.hpp"
 
 namespace vr {
 

@@ -71,7 +71,7 @@ template <int KIND> __global__ __launch_bounds__(256) void issue_kernel(unsigned
         x = mt_step_v(mm, x, j);
     } else if (KIND == 6) {
       // the step with its high word by two more v_mad_u64_u32 chained onto the first (5 VALU + a move): faster in
-      // isolation, slower in the generator (vr_device.hpp, mt_step_v)
+      // isolation, slower in the generator (vr_rng.hpp, mt_step_v)
       unsigned al = 0x4C957F2Du, ah = 0x5851F42Du, zero = 0u;
       asm volatile("" : "+v"(al), "+v"(ah), "+v"(zero));
 #pragma unroll

@@ -478,7 +478,7 @@ __global__ void quantize_nodes_kernel(const float4 *nodes, unsigned numNodes, fl
   qnodes[i] = make_uint4(ql[0] | (ql[1] << 16), ql[2] | (qh[0] << 16), qh[1] | (qh[2] << 16), w);
 }
 
-// PAIR nodes for the ordered per-lane walk (vr_device.hpp: pair_walk_lanes): entry i (i = pre-order index of
+// PAIR nodes for the ordered per-lane walk (vr_walk.hpp: pair_walk_lanes): entry i (i = pre-order index of
 // an internal node) holds BOTH children — {box(c0), link(c0)} {box(c1), link(c1)}, 32 bytes in one cache
 // line — so one visit decides both, descends into the nearer one and defers the other.
 //   link: leaf -> its leaf word (VR_LEAF | cnt << 27 | first), internal -> its pre-order index

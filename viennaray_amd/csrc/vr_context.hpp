@@ -274,7 +274,7 @@ struct vr_context {
   uint32_t materialCount = 0;         // ids dMaterialIds holds (a primitive beyond them has id 0)
   bool materialOnDevice = false, materialStale = true;
   // the data log (vr_set_data_log_shape): int64 sums of the log_data hooks, rows concatenated, the control words behind
-  // them (VR_LOG_*, vr_device.hpp); zeroed at every launch, summed over the batches and particles of an apply on the device
+  // them (VR_LOG_*, vr_frame.hpp); zeroed at every launch, summed over the batches and particles of an apply on the device
   std::vector<uint32_t> logRowSizes;
   uint32_t logTotal = 0;              // entries of all rows
   bool logActive = false;             // the prepared apply fills the log (a shape is set)

@@ -228,7 +228,7 @@ int vr_debug_rng_outputs(vr_context *c, uint64_t idx, uint32_t seed, uint32_t co
   if (!c || !out)
     return VR_E_INVALID;
   VR_HIP(c, hipSetDevice(c->device));
-  // tea<3>(idx, seed) on the host (same mix as vr_device.hpp)
+  // tea<3>(idx, seed) on the host (same mix as tea3, vr_rng.hpp)
   unsigned v0 = (unsigned)idx, v1 = seed, s0 = 0;
   for (int n = 0; n < 3; ++n) {
     s0 += 0x9e3779b9u;

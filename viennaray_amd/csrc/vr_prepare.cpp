@@ -415,7 +415,7 @@ static int choose_particle_kernel(vr_context *c, const ParticleSpec &sp, Particl
 // query, and the query clips its rays to the SCENE box: half a grid cell of relief lets the grazing rays of a wave
 // stretch its box over hundreds of cells.  Where the scene is thin along the source axis and the relief field says that
 // few rays would be grazing ones (ReliefParams::stats), the rays are sorted by their predicted first hit, the grazing ones are filed apart
-// (bin_of_relief, vr_generate.hpp) and the query clips to the LOCAL relief (relief_clip, vr_device.hpp): MODE 5 / 6.
+// (bin_of_relief, vr_generate.hpp) and the query clips to the LOCAL relief (relief_clip, vr_packet_query.hpp): MODE 5 / 6.
 static int build_relief_field(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, const PrepareState &S) {
   const Knobs &K = c->knobs;
   TraceParams &p = L.params;
@@ -903,7 +903,7 @@ static int build_height_field(vr_context *c, const ParticleLaunch &L, PrepareSta
   return VR_OK;
 }
 
-// the launch's wall table and scalar frame (VR_F_*, vr_device.hpp), staged in LDS by the trace kernels
+// the launch's wall table and scalar frame (VR_F_*, vr_frame.hpp), staged in LDS by the trace kernels
 static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const PrepareState &S) {
   const TraceParams &p = L.params;
   float *const f = c->frameHostAll.data() + (size_t)L.slot * VR_WALL_TABLE;
@@ -949,7 +949,7 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
     f[VR_F_HF_NY] = bits(q.ny);
     addr(VR_F_HF_PTR_LO, q.field);
   }
-  if (L.uniformDisks) { // (an absorbing launch: no height field, whose first words these are — vr_device.hpp, VR_F_UD_*)
+  if (L.uniformDisks) { // (an absorbing launch: no height field, whose first words these are — vr_frame.hpp, VR_F_UD_*)
     if (S.heightField)
       return fail(c, VR_E_STATE, "a launch with uniform disks has no height field: their frame words are the same");
     float w[4];
@@ -959,7 +959,7 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
     f[VR_F_UD_RADIUS] = w[3];
     f[VR_F_UD_T] = uniform_disk_threshold(w[3]);
   }
-  if (L.relief) { // the relief field's fine tiles (relief_clip, vr_device.hpp)
+  if (L.relief) { // the relief field's fine tiles (relief_clip, vr_packet_query.hpp)
     const ReliefParams &q = c->rf;
     f[VR_F_RF_LO1] = q.lo1;
     f[VR_F_RF_LO2] = q.lo2;

@@ -5,7 +5,7 @@
 #include <vector>
 
 #include "vr_context.hpp"
-#include "vr_device.hpp"
+#include "vr_frame.hpp"
 
 static_assert(VR_LOG_SCALE == (double)(1ull << VR_LOG_FRAC_BITS), "the kernels' log scale is 2^VR_LOG_FRAC_BITS");
 

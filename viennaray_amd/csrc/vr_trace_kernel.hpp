@@ -195,7 +195,7 @@ trace_kernel(const TraceParams p) {
   constexpr bool RESUME = MODE_ == MODE_RESUME;
   constexpr bool UNIFORM = MODE_ == MODE_ABSORB_FLAT_UNIFORM; // (MODE_ABSORB_FLAT with pq_hit_packet's UNIFORM candidate tests)
   constexpr int MODE = (SMALL || RESUME) ? MODE_GENERAL : ((MODE_ == MODE_ABSORB_RELIEF || UNIFORM) ? MODE_ABSORB_FLAT : (MODE_ == MODE_GENERAL_RELIEF ? MODE_GENERAL_FLAT : MODE_));
-  constexpr bool FRAME_LDS = MODE == MODE_ABSORB_FLAT; // (the wall / scene-box frame from LDS: hit_walls_lds, vr_device.hpp)
+  constexpr bool FRAME_LDS = MODE == MODE_ABSORB_FLAT; // (the wall / scene-box frame from LDS: hit_walls_lds, vr_intersect.hpp)
   // (the scalar diet of the absorbing flat-scene kernel — branch-free candidate tests, lane-parallel crediting — in three
   //  dimensions only: the 2-D instantiations answered it with vector spills, DESIGN_APPENDIX A)
   constexpr bool LEAN = MODE == MODE_ABSORB_FLAT && D == 3 && GEO == 0 && PARTICLE < P_EXT;
@@ -227,7 +227,7 @@ trace_kernel(const TraceParams p) {
   // The absorbing kernel for flat scenes does without: its rounds are packets, and the extra
   // live registers would cost it the 8th wave per SIMD.
   constexpr bool CARRY = MODE != MODE_ABSORB_FLAT && (MODE != MODE_GENERAL_FLAT || VR_FLAT_ORDERED);
-  __shared__ float wallS[VR_WALL_TABLE]; // (96 .. : the launch's scalar frame, vr_device.hpp)
+  __shared__ float wallS[VR_WALL_TABLE]; // (96 .. : the launch's scalar frame, vr_frame.hpp)
   // per-lane event counters live in LDS (fire-and-forget ds_add), not in 8 VGPRs.  (Five of them counted per WAVE in
   // scalar registers — 5 KB of LDS less, room for a 7th block per CU — was built and measured in round 3: slower at
   // 7 waves per SIMD and at 6; removed.)

@@ -32,7 +32,7 @@ struct Tri {       // boundary wall triangle, Embree's precomputed form
 //   32 B: A = {org.x, org.y, org.z, dir.x}   B = {dir.y, dir.z, bits(idx - batchFirst), bits(k)}
 //   k = number of engine outputs the source sampling consumed
 //   (the form the absorbing kernels read: nothing after the first hit is observable, no engine state needed)
-// Particles that keep going after a hit need the engine's streaming cursors {s[k], s[k+156]} (vr_device.hpp, struct
+// Particles that keep going after a hit need the engine's streaming cursors {s[k], s[k+156]} (vr_rng.hpp, struct
 // Rng) as well — in 32 bytes too (round 3; it had been 48, and a 48-byte record straddles two 64-byte write bursts
 // every other time: 96 bytes of fabric writes per ray against 64):
 //   A = {org[firstDir], org[secondDir], dir.x, dir.y}   B = {dir.z, bits(idx - batchFirst), s[k+156] lo, hi}
@@ -67,7 +67,7 @@ struct TraceParams {
   uint32_t numNodes;
   float qbase[3], qscale[3];  // quantised coordinate = (x - qbase) * qscale
   const float *prims;         // float4 records
-  // 64-ary box tree over the primitives in leaf order (packet query, vr_device.hpp: pq_hit_packet):
+  // 64-ary box tree over the primitives in leaf order (packet query, vr_packet_query.hpp: pq_hit_packet):
   // entries of two float4 {lo.xyz, bits(first child)} {hi.xyz, bits(child count | VR_WIDE_PRIMS)};
   // children of a VR_WIDE_PRIMS node are the primitives at leaf positions first .. first + count - 1
   const float *wide;
@@ -206,7 +206,7 @@ struct SourceCtx {
 
 // Relief field over the source plane (vr_fields.hip: relief_field_kernel): per fine tile the [lo, hi] range — along the
 // source axis, padded — of every primitive whose (padded) box meets the tile.  A ray can only meet geometry inside a
-// tile while its own height is within that range: relief_clip (vr_device.hpp) walks the tiles under a ray and returns
+// tile while its own height is within that range: relief_clip (vr_packet_query.hpp) walks the tiles under a ray and returns
 // the stretch that covers all such tiles, which replaces the clip to the SCENE box in the packet query of the
 // flat-scene kernels (trace_kernel MODE 5 / 6).  The coarse field (<= 256 x 256, L2 resident for the generator's random
 // look-ups) holds per coarse tile the mid height of its geometry and the largest thickness of its fine tiles.
@@ -302,7 +302,7 @@ enum TraceMode : int {
                            // records, neighbourhood and flux accumulators are staged in LDS (VR_SMALL_LDS bytes per block)
                            // and every access of the round but the ray records stays there; no packets
   MODE_ABSORB_RELIEF = 5,  // MODE_ABSORB_FLAT / MODE_GENERAL_FLAT for the tight bins of a scene that is flat WITH RELIEF:
-  MODE_GENERAL_RELIEF = 6, // the packet query clips its rays to the local relief (relief_clip, vr_device.hpp), not to the
+  MODE_GENERAL_RELIEF = 6, // the packet query clips its rays to the local relief (relief_clip, vr_packet_query.hpp), not to the
                            // scene box; the generator has filed the grazing rays in loose bins, which a MODE_ABSORB /
                            // MODE_GENERAL launch of their own traces.  MODE_GENERAL_RELIEF spills the rays that go on
   MODE_RESUME = 7,         // MODE_GENERAL over those loose bins that also resumes the rays of MODE_GENERAL_RELIEF's spill

@@ -1,4 +1,4 @@
-// vr_uniform_disks.hpp — the host side of the uniform-disk candidate tests (pq_hit_packet UNIFORM, vr_device.hpp): the
+// vr_uniform_disks.hpp — the host side of the uniform-disk candidate tests (pq_hit_packet UNIFORM, vr_packet_query.hpp): the
 // threshold that replaces the neighbour test's square root.  Host code only (vr_prepare.cpp; tests/aux/uniform_threshold.cpp).
 #pragma once
 #include <cmath>
