@@ -374,6 +374,9 @@ int vr_apply_finish(vr_context *c) {
       // (the scene's fact, and whether this launch ran the uniform-disk kernel on it)
       std::fprintf(stderr, "[vr] uniform disks: scene %d, VR_UNIFORM_DISKS %d, launch %d, particle %zu\n", (int)c->uniformDisks,
                    (int)c->knobs.uniformDisks, (int)L.uniformDisks, q);
+      // (launch 1 above: a kernel of the uniform family ran; here: whether it was the planar one)
+      std::fprintf(stderr, "[vr] planar disks: scene %d, VR_PLANAR_DISKS %d, launch %d, particle %zu\n", (int)c->planarDisks,
+                   (int)c->knobs.planarDisks, (int)L.planarDisks, q);
     }
   const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
   if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)

@@ -113,7 +113,8 @@ struct Knobs {
   uint32_t binCap = VR_BIN_CAP;        // VR_BIN_CAP >= 8: record slots per sort bin
   uint32_t raysPerBin = 40;            // VR_RAYS_PER_BIN >= 1: rays per sort bin the grid is sized for
   bool binAlign = true;                // VR_BIN_ALIGN (0: off): sort bins aligned with the disk lattice (3-D, disks; vr_bin_grid.hpp)
-  bool uniformDisks = true;            // VR_UNIFORM_DISKS (0: off): the absorbing flat-scene kernel's uniform-disk variant where the scene allows it
+  bool uniformDisks = true;            // VR_UNIFORM_DISKS (0: off): the absorbing flat-scene kernel's uniform-disk variants where the scene allows them
+  bool planarDisks = true;             // VR_PLANAR_DISKS (0: off): ... the planar one of them (off: planar disks run the uniform-disk kernel)
   std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
   std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
   // kernel parameters (TraceParams)
@@ -192,7 +193,12 @@ struct ParticleLaunch {
   // launch runs the library's 3-D MODE_ABSORB_FLAT kernel: it runs that kernel's uniform-disk variant, with the
   // normal, the radius and the square-root threshold in its frame (VR_F_UD_*)
   bool uniformDisks = false;
-  int kernel_mode() const { return uniformDisks ? (int)MODE_ABSORB_FLAT_UNIFORM : traceMode; } // the mode launch_trace takes
+  // ... and the scene's disks are planar (vr_context::planarDisks) with VR_PLANAR_DISKS on: the planar variant of that
+  // kernel, the plane's axis and coordinate in the frame as well (VR_F_PD_*).  Only ever set with uniformDisks
+  bool planarDisks = false;
+  int kernel_mode() const { // the mode launch_trace takes
+    return planarDisks ? (int)MODE_ABSORB_FLAT_PLANAR : (uniformDisks ? (int)MODE_ABSORB_FLAT_UNIFORM : traceMode);
+  }
   bool absorb = false;
   bool recExtra = false; // the records' side array (TraceParams::recExtra)
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
@@ -381,7 +387,12 @@ struct vr_context {
   // record 0's normal and radius, word for word.  false for a mesh and for an empty scene.
   bool uniformDisks = false;
   uint32_t uniformWords[4] = {0, 0, 0, 0}; // ... those words: n.x, n.y, n.z, radius
-  DevBuf<uint32_t> dUniformDisks;          // launch_uniform_disks' five words
+  // ... and planar (vr_planar_disks.hpp): that normal is +-1 along planarAxis and +-0 along the two others, every centre
+  // carries planarWord in that coordinate, every centre coordinate is finite
+  bool planarDisks = false;
+  int planarAxis = 0;
+  uint32_t planarWord = 0;
+  DevBuf<uint32_t> dUniformDisks;          // launch_uniform_disks' VR_UNIFORM_WORDS words
   SetupParams lastSetup{};       // buffers of the resident device build (vr_debug_bvh_check)
   bool haveSetup = false;
   int builtOrderAxis = -1;       // child order of the resident BVH (source side first)

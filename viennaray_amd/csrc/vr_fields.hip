@@ -166,27 +166,47 @@ hipError_t launch_relief_field(const ReliefParams &q, hipStream_t st) {
 
 // ---------------------------------------------------------------------------
 // uniform disks: one normal and one radius for the whole cloud (a disk cloud made from a planar level set), compared as
-// 32-bit words (a -0 is not a +0, a NaN equals itself): where it holds, record 0's four words stand for every record's
+// 32-bit words (a -0 is not a +0, a NaN equals itself): where it holds, record 0's four words stand for every record's.
+// In the same pass, for the planar variant (vr_planar_disks.hpp): per coordinate, whether every centre carries record
+// 0's word in it, and whether every centre coordinate is finite.  out: VR_UNIFORM_WORDS words —
+// [0] a normal or radius differs, [1..4] record 0's n.x, n.y, n.z, radius, [5..7] a centre's x / y / z differs from
+// record 0's, [8] a centre coordinate is not finite, [9..11] record 0's c.x, c.y, c.z
 // ---------------------------------------------------------------------------
 __global__ void uniform_disks_kernel(const uint4 *__restrict__ recs, unsigned n, unsigned *out) {
   const uint4 c0 = recs[0], n0 = recs[1];
-  bool same = true;
+  bool same = true, sameX = true, sameY = true, sameZ = true, finite = true;
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const uint4 c = recs[2 * (size_t)i], nn = recs[2 * (size_t)i + 1];
     same = same && nn.x == n0.x && nn.y == n0.y && nn.z == n0.z && c.w == c0.w;
+    sameX = sameX && c.x == c0.x;
+    sameY = sameY && c.y == c0.y;
+    sameZ = sameZ && c.z == c0.z;
+    // (an all-ones exponent: an infinity or a NaN)
+    finite = finite && (c.x & 0x7F800000u) != 0x7F800000u && (c.y & 0x7F800000u) != 0x7F800000u && (c.z & 0x7F800000u) != 0x7F800000u;
   }
   if (!same)
     out[0] = 1u; // (every writer writes the same word)
+  if (!sameX)
+    out[5] = 1u;
+  if (!sameY)
+    out[6] = 1u;
+  if (!sameZ)
+    out[7] = 1u;
+  if (!finite)
+    out[8] = 1u;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     out[1] = n0.x;
     out[2] = n0.y;
     out[3] = n0.z;
     out[4] = c0.w;
+    out[9] = c0.x;
+    out[10] = c0.y;
+    out[11] = c0.z;
   }
 }
 
 hipError_t launch_uniform_disks(const float *prims, unsigned n, unsigned *out, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(out, 0, 5 * 4, st);
+  hipError_t e = hipMemsetAsync(out, 0, VR_UNIFORM_WORDS * 4, st);
   if (e != hipSuccess || n == 0)
     return e;
   const unsigned grid = (unsigned)((n + 255u) / 256u < 1024u ? (n + 255u) / 256u : 1024u);

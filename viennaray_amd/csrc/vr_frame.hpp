@@ -20,6 +20,10 @@ enum { VR_F_SRC_PLANE = 96, VR_F_RAYDIR = 97, VR_F_FIRSTDIR = 98, VR_F_SECONDDIR
        // (vr_uniform_disks.hpp).  They share the height field's first words: that field is built for launches that go on
        // after a hit, this kernel is an absorbing one (write_launch_frame fills one or the other)
        VR_F_UD_N = VR_F_HF_LO1 /* n.x, n.y, n.z */, VR_F_UD_RADIUS = VR_F_HF_TILE, VR_F_UD_T = VR_F_HF_TOP,
+       // ... whose disks are planar as well (ParticleLaunch::planarDisks; read only by trace_kernel MODE_ABSORB_FLAT_PLANAR):
+       // the axis a of the normal's +-1 (an int) and the one coordinate a of every centre (vr_planar_disks.hpp), in the
+       // next words of the same block
+       VR_F_PD_AXIS = VR_F_HF_SIGN, VR_F_PD_COORD = VR_F_HF_NX,
        // the relief field's fine tiles (ReliefParams; NX = 0: none): relief_clip below
        VR_F_RF_LO1 = 128, VR_F_RF_LO2 = 129, VR_F_RF_INVT = 130, VR_F_RF_TILE = 131, VR_F_RF_NX = 132, VR_F_RF_NY = 133,
        VR_F_RF_PTR_LO = 134, VR_F_RF_PTR_HI = 135,

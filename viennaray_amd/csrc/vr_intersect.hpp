@@ -232,6 +232,8 @@ __device__ __forceinline__ bool local_disc_hit_lds(const V3 &ro, const V3 &rd, c
 // divisor = edot(d, n), prod = vdot(n, rd) and nro = vdot(n, ro) are the caller's, computed once per ray and round; every
 // other operation is the one above, in its order.  thresh is the smallest float x with sqrtf(x) >= radius: the correctly
 // rounded square root is monotone, so radius > sqrtf(x) <=> x < thresh for every x (an infinity or a NaN: both false).
+// (Where the disks share a plane normal to a coordinate axis as well, t, tt and the two points are the ray's too:
+//  vr_planar_disks.hpp has those forms, pq_hit_packet PLANAR uses them in place of these two.)
 __device__ __forceinline__ bool hit_disc_uniform(const V3 &o, const V3 &d, float tnear, const V3 &c, const V3 &n, float divisor,
                                                  float radius, float &tOut) {
   const V3 co = V3{c.x - o.x, c.y - o.y, c.z - o.z};

@@ -50,7 +50,10 @@ hipError_t launch_sort_pairs(unsigned long long *keysA, unsigned *valsA, unsigne
 hipError_t launch_height_field(const HeightFieldParams &q, hipStream_t st);
 hipError_t launch_relief_field(const ReliefParams &q, hipStream_t st);
 // are the packed disk records (2 x float4 each, leaf order) uniform: every record's {n.x, n.y, n.z, radius} equal, as 32-bit
-// words, to record 0's?  out[0] <- 0: yes, 1: some record differs; out[1 .. 4] <- record 0's four words (n > 0)
+// words, to record 0's?  out[0] <- 0: yes, 1: some record differs; out[1 .. 4] <- record 0's four words (n > 0).  And are
+// they planar: out[5 .. 7] <- 1 where some centre's x / y / z differs from record 0's word, out[8] <- 1 where a centre
+// coordinate is not finite, out[9 .. 11] <- record 0's centre.  out: VR_UNIFORM_WORDS words
+constexpr unsigned VR_UNIFORM_WORDS = 12;
 hipError_t launch_uniform_disks(const float *prims, unsigned n, unsigned *out, hipStream_t st);
 // device-resident inputs (vr_ingest.hip)
 hipError_t launch_disk4(const float *points3, unsigned n, float radius, int D, float *disk4, hipStream_t st);

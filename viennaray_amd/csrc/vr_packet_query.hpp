@@ -1,5 +1,6 @@
 // vr_packet_query.hpp — the wave-uniform search by box (packet query) and the relief clip of its rays (gfx950).
 #pragma once
+#include "vr_planar_disks.hpp"
 #include "vr_walk.hpp"
 namespace vr {
 
@@ -143,8 +144,11 @@ constexpr unsigned VR_PQ_RECORDS = 2 * 52;
 // LEAN (the 3-D absorbing flat-scene kernels): the candidate loop's disc tests in their branch-free forms (hit_disc_lds)
 // UNIFORM (LEAN, for a launch whose disks all have one normal and one radius — the frame's VR_F_UD_*): what those tests
 // take from the ray and the normal alone is computed once per round, before the candidate loop (hit_disc_uniform)
+// PLANAR (UNIFORM, for disks that also share a plane normal to a coordinate axis — the frame's VR_F_PD_*): the point where the
+// ray crosses that plane is the ray's own; the two divisions, the two points and the range tests once per round, a
+// distance to the centre per candidate (vr_planar_disks.hpp has the argument)
 template <int GEO, bool CREDIT, bool FRAME_LDS = false, bool KEEPQ = false, bool RELIEF = false, bool CACHE = false, bool LEAN = false,
-          bool UNIFORM = false>
+          bool UNIFORM = false, bool PLANAR = false>
 __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, const V3 &o, const V3 &d, float tnear,
                                               HitRec &h, volatile VR_LDS unsigned *lst, PqCands &cd,
                                               const float *__restrict__ wallS, volatile VR_LDS float *cboxes, float tWall VR_DIAG_ARGS) {
@@ -391,6 +395,16 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
     uProd = vdot(un, d);
     uNro = vdot(un, o);
   }
+  PlanarHit pdH{};
+  PlanarLocal pdL{};
+  if constexpr (PLANAR) {
+    static_assert(UNIFORM, "planar disks are uniform disks");
+    const int pa = __float_as_int(wallS[VR_F_PD_AXIS]);
+    const float ca = wallS[VR_F_PD_COORD], s = getc(un, pa);
+    pdH = planar_hit_round(part, o.x, o.y, o.z, d.x, d.y, d.z, getc(o, pa), tnear, ca, s, uDivisor);
+    if (CREDIT)
+      pdL = planar_local_round(part, o.x, o.y, o.z, d.x, d.y, d.z, ca, s, uProd, uNro);
+  }
   unsigned tests = 0;
   VR_PQ_MARK(14); // (diag: the descent)
   for (unsigned j = 0; j < nF; ++j) {
@@ -432,8 +446,14 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
       if constexpr (UNIFORM) { // (the centre and the original id alone are the candidate's own)
         const V3 cc = mk(lane_bcast(r0.x, k), lane_bcast(r0.y, k), lane_bcast(r0.z, k));
         const unsigned orig = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(r1.w), k);
-        const bool ok = hit_disc_uniform(o, d, tnear, cc, un, uDivisor, uRadius, t);
-        const bool took = hit_update_lds(h, part & ok, t, orig, qq);
+        bool ok;
+        if constexpr (PLANAR) { // (the range tests and `part` are in the round's point: vr_planar_disks.hpp)
+          ok = planar_hit_cand(pdH, cc.x, cc.y, cc.z, uRadius);
+          t = pdH.t;
+        } else {
+          ok = part & hit_disc_uniform(o, d, tnear, cc, un, uDivisor, uRadius, t);
+        }
+        const bool took = hit_update_lds(h, ok, t, orig, qq);
         if (CREDIT) {
           const int c = (int)tests;
           cd.mine = took ? (unsigned)c : cd.mine;
@@ -441,7 +461,10 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
             cd.rec[c] = mk_u4(qq, __float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r0.z));
             cd.rec[VR_PQ_NRM + c] = mk_u4(__float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), __float_as_uint(r0.w));
           }
-          cd.local |= (unsigned long long)(part & local_disc_hit_uniform(o, d, cc, un, uProd, uNro, uThresh)) << c;
+          if constexpr (PLANAR)
+            cd.local |= (unsigned long long)planar_local_cand(pdL, cc.x, cc.y, cc.z, uThresh) << c;
+          else
+            cd.local |= (unsigned long long)(part & local_disc_hit_uniform(o, d, cc, un, uProd, uNro, uThresh)) << c;
           cd.count = tests + 1u;
         }
       } else if (GEO == 0) {

@@ -614,6 +614,8 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   // one normal and one radius for the whole cloud (build_scene: vr_context::uniformDisks): the library's 3-D absorbing
   // flat-scene kernel in its uniform-disk variant (a run-time model's code object has no such kernel)
   L.uniformDisks = K.uniformDisks && c->uniformDisks && L.traceMode == MODE_ABSORB_FLAT && D == 3 && c->geo.geo == 0 && sp.userModel < 0;
+  // ... in its planar variant where the disks also share a plane normal to a coordinate axis (vr_context::planarDisks)
+  L.planarDisks = L.uniformDisks && K.planarDisks && c->planarDisks;
   int blocks = 1;
   L.userKernel = nullptr;
   L.userGen = nullptr;
@@ -958,6 +960,10 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
       f[VR_F_UD_N + k] = w[k];
     f[VR_F_UD_RADIUS] = w[3];
     f[VR_F_UD_T] = uniform_disk_threshold(w[3]);
+    if (L.planarDisks) { // (VR_F_PD_*: the next words of the same block)
+      f[VR_F_PD_AXIS] = bits(c->planarAxis);
+      f[VR_F_PD_COORD] = bits((int32_t)c->planarWord);
+    }
   }
   if (L.relief) { // the relief field's fine tiles (relief_clip, vr_packet_query.hpp)
     const ReliefParams &q = c->rf;

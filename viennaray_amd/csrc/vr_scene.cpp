@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "vr_context.hpp"
+#include "vr_planar_disks.hpp"
 
 namespace vr {
 
@@ -139,18 +140,25 @@ static int quantize_scene(vr_context *c, const float *preNodes, const float *roo
   return VR_OK;
 }
 
-// Uniform disks (vr_context::uniformDisks): the reduction over the packed disk records on the stream, its five words
-// on their way into `words`; the caller's next synchronisation of the stream delivers them, set_uniform_disks files them.
-static int read_uniform_disks(vr_context *c, uint32_t (&words)[5]) {
-  VR_HIP(c, c->dUniformDisks.ensure(5));
+// Uniform disks (vr_context::uniformDisks, planarDisks): the reduction over the packed disk records on the stream, its
+// words on their way into `words`; the caller's next synchronisation of the stream delivers them, set_uniform_disks files them.
+static int read_uniform_disks(vr_context *c, uint32_t (&words)[VR_UNIFORM_WORDS]) {
+  VR_HIP(c, c->dUniformDisks.ensure(VR_UNIFORM_WORDS));
   VR_HIP(c, launch_uniform_disks(c->dPrims.p, c->geo.numPrims, c->dUniformDisks.p, c->stream));
   VR_HIP(c, hipMemcpyAsync(words, c->dUniformDisks.p, sizeof(words), hipMemcpyDeviceToHost, c->stream));
   return VR_OK;
 }
-static void set_uniform_disks(vr_context *c, const uint32_t (&words)[5]) {
+static void set_uniform_disks(vr_context *c, const uint32_t (&words)[VR_UNIFORM_WORDS]) {
   c->uniformDisks = words[0] == 0u && c->geo.geo == 0 && c->geo.numPrims > 0; // (a mesh: nothing was launched)
   for (int k = 0; k < 4; ++k)
     c->uniformWords[k] = words[1 + k];
+  // planar as well: the shared normal is +-1 along one axis and +-0 along the others (the rule of vr_planar_disks.hpp),
+  // every centre carries one word in that coordinate, every centre coordinate is finite
+  const uint32_t nw[3] = {words[1], words[2], words[3]};
+  const int axis = planar_disk_axis(nw);
+  c->planarDisks = c->uniformDisks && axis >= 0 && words[5 + axis] == 0u && words[8] == 0u;
+  c->planarAxis = c->planarDisks ? axis : 0;
+  c->planarWord = c->planarDisks ? words[9 + axis] : 0u;
 }
 
 int build_scene(vr_context *c) {
@@ -218,7 +226,7 @@ int build_scene(vr_context *c) {
       VR_HIP(c, hipMemcpyAsync(c->dNbIds.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
     VR_HIP(c, hipMemcpyAsync(c->dLeafOfOrig.p, c->leafOfOrig.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
     VR_HIP(c, hipMemcpyAsync(c->dOrder.p, c->bvh.order.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-    uint32_t uni[5] = {0, 0, 0, 0, 0};
+    uint32_t uni[VR_UNIFORM_WORDS] = {};
     if (disk) // (the same pass over the resident records as behind the device builder)
       VR_TRY(read_uniform_disks(c, uni));
     VR_HIP(c, hipStreamSynchronize(c->stream));
@@ -345,7 +353,7 @@ int build_scene(vr_context *c) {
   }
   float root8[8];
   uint32_t sz = 0, bad = 0;
-  uint32_t uni[5] = {0, 0, 0, 0, 0};
+  uint32_t uni[VR_UNIFORM_WORDS] = {};
   if (disk) // (the packed records never change behind launch_setup_bvh: a re-fit below leaves them as they are)
     VR_TRY(read_uniform_disks(c, uni));
   VR_HIP(c, hipMemcpyAsync(root8, c->dNodesPre.p, sizeof(root8), hipMemcpyDeviceToHost, c->stream));

@@ -184,7 +184,7 @@ __device__ __forceinline__ void spill_pad(const TraceParams &p, unsigned base, u
     reinterpret_cast<float4 *>(p.spillRec)[4 * (size_t)(base + lane) + 2] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xFFFFFFFFu));
 }
 constexpr int vr_mode_waves(int m) {
-  return m == MODE_ABSORB_RELIEF ? VR_RELIEF_WAVES : (m == MODE_ABSORB_FLAT || m == MODE_ABSORB_FLAT_UNIFORM) ? 8 : (m == MODE_ABSORB ? 7 : ((m == MODE_GENERAL_FLAT || m == MODE_GENERAL_RELIEF) ? VR_FLAT_WAVES : (m == MODE_SMALL ? VR_SMALL_WAVES : VR_GENERAL_WAVES)));
+  return m == MODE_ABSORB_RELIEF ? VR_RELIEF_WAVES : (m == MODE_ABSORB_FLAT || m == MODE_ABSORB_FLAT_UNIFORM || m == MODE_ABSORB_FLAT_PLANAR) ? 8 : (m == MODE_ABSORB ? 7 : ((m == MODE_GENERAL_FLAT || m == MODE_GENERAL_RELIEF) ? VR_FLAT_WAVES : (m == MODE_SMALL ? VR_SMALL_WAVES : VR_GENERAL_WAVES)));
 }
 template <int D, int GEO, int PARTICLE, int MODE_>
 __global__ __launch_bounds__(VR_BLOCK) __attribute__((amdgpu_num_sgpr(80)))
@@ -193,7 +193,8 @@ trace_kernel(const TraceParams p) {
   constexpr bool SMALL = MODE_ == MODE_SMALL;
   constexpr bool RELIEF = MODE_ == MODE_ABSORB_RELIEF || MODE_ == MODE_GENERAL_RELIEF;
   constexpr bool RESUME = MODE_ == MODE_RESUME;
-  constexpr bool UNIFORM = MODE_ == MODE_ABSORB_FLAT_UNIFORM; // (MODE_ABSORB_FLAT with pq_hit_packet's UNIFORM candidate tests)
+  constexpr bool PLANAR = MODE_ == MODE_ABSORB_FLAT_PLANAR;   // (... with its PLANAR candidate tests, which are UNIFORM ones)
+  constexpr bool UNIFORM = MODE_ == MODE_ABSORB_FLAT_UNIFORM || PLANAR; // (MODE_ABSORB_FLAT with pq_hit_packet's UNIFORM candidate tests)
   constexpr int MODE = (SMALL || RESUME) ? MODE_GENERAL : ((MODE_ == MODE_ABSORB_RELIEF || UNIFORM) ? MODE_ABSORB_FLAT : (MODE_ == MODE_GENERAL_RELIEF ? MODE_GENERAL_FLAT : MODE_));
   constexpr bool FRAME_LDS = MODE == MODE_ABSORB_FLAT; // (the wall / scene-box frame from LDS: hit_walls_lds, vr_intersect.hpp)
   // (the scalar diet of the absorbing flat-scene kernel — branch-free candidate tests, lane-parallel crediting — in three
@@ -601,7 +602,7 @@ trace_kernel(const TraceParams p) {
           }
         }
         // ---- packet query: the call and its back-off ----
-        packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE, LEAN, UNIFORM>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
+        packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE, LEAN, UNIFORM, PLANAR>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
         pqCredit = PQ_CREDIT && packetDone;
         pqFails = packetDone ? 0u : (pqFails < 6u ? pqFails + 1u : 6u);
         pqSkip = packetDone ? 0u : (1u << pqFails) - 1u;

@@ -307,10 +307,13 @@ enum TraceMode : int {
                            // MODE_GENERAL launch of their own traces.  MODE_GENERAL_RELIEF spills the rays that go on
   MODE_RESUME = 7,         // MODE_GENERAL over those loose bins that also resumes the rays of MODE_GENERAL_RELIEF's spill
                            // queue (TraceParams::spillRec)
-  MODE_ABSORB_FLAT_UNIFORM = 8 // MODE_ABSORB_FLAT's kernel for a launch whose disks all have one normal and one radius
+  MODE_ABSORB_FLAT_UNIFORM = 8, // MODE_ABSORB_FLAT's kernel for a launch whose disks all have one normal and one radius
                            // (ParticleLaunch::uniformDisks; 3-D disks only): the per-ray terms of the candidate tests once
                            // per round (pq_hit_packet UNIFORM).  A kernel of the library's table, never a launch's
                            // traceMode: that stays MODE_ABSORB_FLAT (ParticleLaunch::kernel_mode)
+  MODE_ABSORB_FLAT_PLANAR = 9 // ... whose disks also share a plane normal to a coordinate axis (ParticleLaunch::planarDisks):
+                           // one plane hit per ray and round, a distance per candidate (pq_hit_packet PLANAR).  Like
+                           // MODE_ABSORB_FLAT_UNIFORM a kernel of the table, never a launch's traceMode
 };
 // (MODE_GENERAL_FLAT, MODE_GENERAL_RELIEF and MODE_RESUME exist for disks and the lean particles only: otherwise MODE_GENERAL)
 
