@@ -347,6 +347,45 @@ int vr_smooth_flux(vr_context *ctx, float *flux, uint32_t n, int numNeighbors);
  * the host smoothing runs and its result is uploaded.                                                     */
 int vr_get_flux_device(vr_context *ctx, uint32_t dataIdx, float *out, uint32_t n, int normType, int numNeighbors,
                        void *stream);
+/* ---- per-primitive values at the caller's points (not in the reference) ------------------------------------------------
+ * One float per primitive of the geometry in force — a flux, a coverage, anything — is mapped to m query points that
+ * need not be primitives: grid points, the next surface's points, a coarser or finer point set.  The definition:
+ *   f[j]   one float per primitive, in the caller's primitive order;  p_i: the m query points;  m_i: optional query
+ *          normals of any non-zero length, normalised in the kernel;  R >= 0: a radius.
+ *   c_j    the centre of primitive j: a disk's is the caller's point; a triangle's is its centroid
+ *          ((v0 + v1) + v2) * (1.f / 3.f), taken per component in float32.
+ *   D == 2 the z components of p_i, c_j and of the normals are ignored (2-D triangle strips included).
+ *   d_ij = |p_i - c_j|, plain Euclidean: the side walls' periodicity is NOT applied.  Primitive j is in range iff d_ij < R.
+ *   w_ij = (1 - d_ij / R) * g_ij;  g_ij = 1 without query normals, else max(0, n_j . m^_i), n_j the unit normal the
+ *          library holds for the primitive.
+ *   out[i] = sum_j w_ij f[j] / sum_j w_ij over the primitives in range, if sum_j w_ij > 0;
+ *          = f[j*] otherwise, j* the primitive whose centre is nearest to p_i, the lowest original id on an exact tie;
+ *            normals play no part in this fallback.  It covers R == 0, nothing in range and every in-range normal
+ *            facing away.
+ *   A query point with a coordinate that is not finite gives out[i] = NaN; the call still returns VR_OK.
+ *   m == 0 is VR_OK and touches nothing.
+ * Two calls with the same inputs on the same built scene give the same bits.  Another build of the same geometry (a
+ * geometry set anew) may differ in the last bits: the sums run in the order of the walk over the resident BVH.
+ * Refused, `out` untouched and the context usable, message in vr_last_error:
+ *   VR_E_INVALID  n != vr_num_primitives, ld outside {2, 3}, ld == 2 with D == 3, a radius that is negative or not
+ *                 finite, a null pointer where one is needed; a pointer that is not device memory of ctx's device;
+ *   VR_E_STATE    no scene build is resident for the geometry in force: nothing has been prepared yet (vr_apply or
+ *                 vr_apply_prepare builds it), or the geometry was set since.  vr_get_flux_at_points_device: whatever
+ *                 vr_get_flux_device refuses as well.
+ * Streams: as vr_get_flux_device — enqueued on the context's stream behind what `stream` holds at the call, `stream`
+ * made to wait for the result by an event; no host synchronisation unless a work buffer of the library has to grow
+ * (the first call, a larger m), or, with smoothing, for vr_get_flux_device's one word.
+ *
+ * values: DEVICE, n = vr_num_primitives floats, caller's order; points / normals: DEVICE, m rows of ld (2 or 3; 2 only with D == 2)
+ * floats, normals may be NULL; out: DEVICE, m floats; stream rules of vr_get_flux_device */
+int vr_map_to_points_device(vr_context *ctx, const float *values, uint32_t n, const float *points, const float *normals,
+                            uint32_t m, uint32_t ld, float radius, float *out, void *stream);
+/* the same from and to host arrays (m x 3): upload, kernel, download */
+int vr_map_to_points(vr_context *ctx, const float *values, uint32_t n, const float *points3, const float *normals3,
+                     uint32_t m, float radius, float *out);
+/* vr_get_flux_device(dataIdx, normType, numNeighbors) into a work buffer, then the map: the flux never leaves the device */
+int vr_get_flux_at_points_device(vr_context *ctx, uint32_t dataIdx, int normType, int numNeighbors, const float *points,
+                                 const float *normals, uint32_t m, uint32_t ld, float radius, float *out, void *stream);
 /* ---- flux statistics (not in the reference): per-primitive hit counts and the Monte-Carlo error of the flux ----------
  * vr_set_flux_statistics(on != 0): every later apply() keeps, for each particle and alongside its data label 0 (the flux
  * label of every built-in model), two more int64 sums per primitive:

@@ -1208,6 +1208,51 @@ public:
     return fluxDevice(dOut, dataIdx, VR_NORM_NONE, 0, stream);
   }
 
+  // ---- per-primitive values at the caller's points (not in the reference; vr_map_to_points*, whose header comment
+  //      has the definition): the mean of the values over the primitive centres within `radius`, weighted by
+  //      (1 - d / radius) * max(0, n_j . normal_i) — no gate without normals — or the nearest centre's value where that
+  //      sum of weights is not positive.  Plain Euclidean distances; a 2-D scene ignores z.  Needs the scene build of the
+  //      geometry in force: apply() first.
+  /// dValues (one float per primitive, caller's order), dPoints / dNormals (m rows of ld = 2 or 3 floats, 2 only with
+  /// D == 2; dNormals may be nullptr) and dOut (m floats) are DEVICE memory; getFluxDevice's stream rules.  false if it
+  /// was refused.
+  bool mapToPointsDevice(const float *dValues, const float *dPoints, const float *dNormals, size_t m, unsigned ld,
+                         float radius, float *dOut, void *stream = nullptr) {
+    return ctx_ && reported(vr_map_to_points_device(ctx_, dValues, vr_num_primitives(ctx_), dPoints, dNormals, (uint32_t)m,
+                                                    ld, radius, dOut, stream));
+  }
+  /// getFluxDevice(dataIdx, norm, numNeighbors) mapped to the points, the flux never leaving the device
+  bool getFluxAtPointsDevice(const float *dPoints, const float *dNormals, size_t m, unsigned ld, float radius, float *dOut,
+                             int dataIdx, NormalizationType norm, int numNeighbors, void *stream = nullptr) {
+    return ctx_ && reported(vr_get_flux_at_points_device(ctx_, (uint32_t)dataIdx, (int)norm, numNeighbors, dPoints, dNormals,
+                                                         (uint32_t)m, ld, radius, dOut, stream));
+  }
+  /// ... the raw flux, neither normalised nor smoothed
+  bool getFluxAtPointsDevice(const float *dPoints, const float *dNormals, size_t m, unsigned ld, float radius, float *dOut,
+                             int dataIdx = 0, void *stream = nullptr) {
+    return ctx_ && reported(vr_get_flux_at_points_device(ctx_, (uint32_t)dataIdx, VR_NORM_NONE, 0, dPoints, dNormals,
+                                                         (uint32_t)m, ld, radius, dOut, stream));
+  }
+  /// the host form: `values` per primitive, `points` (and `normals`, empty = no gate) as rows of three; the mapped
+  /// values, empty (with the library's message on std::cerr) if it was refused
+  [[nodiscard]] std::vector<NumericType> mapToPoints(const std::vector<NumericType> &values,
+                                                     const std::vector<std::array<NumericType, 3>> &points,
+                                                     const std::vector<std::array<NumericType, 3>> &normals, float radius) {
+    const std::vector<float> v(values.begin(), values.end());
+    std::vector<float> p(3 * points.size()), q(3 * normals.size()), raw(points.size());
+    for (size_t i = 0; i < points.size(); ++i)
+      for (int k = 0; k < 3; ++k)
+        p[3 * i + k] = (float)points[i][k];
+    for (size_t i = 0; i < normals.size(); ++i)
+      for (int k = 0; k < 3; ++k)
+        q[3 * i + k] = (float)normals[i][k];
+    if (!ctx_ || (!normals.empty() && normals.size() != points.size()) ||
+        !reported(vr_map_to_points(ctx_, v.data(), (uint32_t)v.size(), p.data(), q.empty() ? nullptr : q.data(),
+                                   (uint32_t)points.size(), radius, raw.data())))
+      raw.clear();
+    return std::vector<NumericType>(raw.begin(), raw.end());
+  }
+
   // ---- flux statistics (not in the reference; vr_set_flux_statistics): per-primitive hit counts and the Monte-Carlo
   //      error of the flux label.  A per-credit estimator: it ignores the correlation between several credits of one ray
   //      to the same primitive.  Off by default; an absorbing particle keeps its kernels, every other launch runs the

@@ -108,6 +108,10 @@ SIGNATURES = {
     "vr_get_flux_normalized": (C.c_int, [_vp, _fp, C.c_uint32, C.c_int]),
     "vr_smooth_flux": (C.c_int, [_vp, _fp, C.c_uint32, C.c_int]),
     "vr_get_flux_device": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_int, C.c_int, _vp]),
+    "vr_map_to_points_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, _vp, _vp]),
+    "vr_map_to_points": (C.c_int, [_vp, _fp, C.c_uint32, _fp, _fp, C.c_uint32, C.c_float, _fp]),
+    "vr_get_flux_at_points_device": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, C.c_uint32, C.c_uint32,
+                                               C.c_float, _vp, _vp]),
     "vr_get_disk_areas": (C.c_int, [_vp, _fp, C.c_uint32]),
     "vr_get_bounding_box": (C.c_int, [_vp, _fp]),
     "vr_get_source_area": (C.c_float, [_vp]),

@@ -81,6 +81,9 @@ template <class T> struct DevBuf {
   ~DevBuf() { release(); } // (vr_destroy selects the device before the context goes away)
 };
 
+// vr_map_to_points*: from this many query points on they are walked in Morton order (DESIGN.md 8n has the measurement)
+constexpr uint32_t VR_MAP_SORT_MIN = 1u << 19;
+
 // Every tuning and experiment switch of the library, read from the environment in ONE place (read_knobs): an apply
 // reads them once, at vr_apply_prepare, into vr_context::knobs.  Unless its line says RESULTS, a switch only moves work
 // around: the flux and the TraceInfo counters stay bit-exact (tests/test_gpu_parity.py).  (VR_CSRC_DIR / VR_HIPCC /
@@ -129,6 +132,8 @@ struct Knobs {
   uint32_t debugFlags = 0;             // VR_DEBUG_FLAGS: kernel experiment bits; many of them change RESULTS
   bool noHeightField = false;          // VR_NO_HEIGHT_FIELD (set): no height field over the source plane
   float hfTile = 4.f;                  // VR_HF_TILE >= 0.25: height-field tile side in grid cells
+  // results
+  uint32_t mapSortMin = VR_MAP_SORT_MIN; // VR_MAP_SORT_MIN: vr_map_to_points* sorts its queries by Morton key from this many on (0: always, 4294967295: never; read at every call, like VR_HOST_SMOOTH); same bits either way
   // diagnostics
   bool printLaunches = false;          // VR_PRINT_LAUNCHES (set): trace-launch times and spilled rays on stderr
   bool hostSmooth = false;             // VR_HOST_SMOOTH (set): vr_smooth_flux on the host
@@ -354,6 +359,11 @@ struct vr_context {
   DevBuf<float> dNodes, dPrims;
   DevBuf<float> dAreas, dFluxTmp;     // exposed area per primitive (caller's order); normalisation scratch
   DevBuf<uint32_t> dNormMax;          // flux_max_kernel's reduction word
+  // vr_map_to_points*: the query sort's pairs and tables, the flux variant's per-primitive values, the host form's
+  // staging (values, points, normals, out) and, in a VR_DIAG build, the node-visit counter.  Grown behind host_waits only
+  DevBuf<unsigned long long> dMapKeysA, dMapKeysB, dMapVisits;
+  DevBuf<uint32_t> dMapValsA, dMapValsB, dMapSortTable, dMapScanTmp;
+  DevBuf<float> dMapFlux, dMapValues, dMapPoints, dMapNormals, dMapOut;
   bool areasValid = false;
   DevBuf<uint32_t> dNbOff, dNbIds, dLeafOfOrig;
   DevBuf<uint32_t> dNbTmp; // the one-pass neighbourhood query's fixed-stride lists (build scratch)

@@ -114,6 +114,17 @@ hipError_t launch_flux_error(const unsigned long long *s1, const unsigned long l
                              int kind, float *out, hipStream_t st);
 hipError_t launch_normalize_flux(float *flux, const float *area, unsigned n, int geo, int normType, float normFactor,
                                  double totalDiskArea, unsigned *maxOrd, hipStream_t st);
+// per-primitive values at the caller's points (vr_map.hip).  launch_map_keys: the 63-bit Morton key of every query row
+// (ld floats; the first D looked at) in the scene box, vals[t] = t — the pairs launch_sort_pairs orders.
+// launch_map_points: one walk of s.nodes per query, out[i] = the weighted mean of values[] over the primitive centres
+// within `radius` (normals: nullptr = no gate), else the nearest centre's value, NaN for a row that is not finite; perm:
+// nullptr = query t is row t, else row perm[t] (the walk's order, not the result, depends on it); visits: a VR_DIAG
+// build adds every query's node visits (nullptr, or any other build: nothing).  Reads s.nodes, s.prims, s.verts, s.tris
+hipError_t launch_map_keys(const float *pts, unsigned m, unsigned ld, int D, const float *sceneLo, const float *sceneHi,
+                           unsigned long long *keys, unsigned *vals, hipStream_t st);
+hipError_t launch_map_points(const SetupParams &s, const float *values, const float *pts, const float *normals, unsigned m,
+                             unsigned ld, float radius, const unsigned *perm, float *out, unsigned long long *visits,
+                             hipStream_t st);
 // issue-ceiling microbenchmarks (vr_bench.hip); out: one {cycles, realtime, sink} triple of u64 per wave
 hipError_t launch_issue_kernel(int kind, unsigned blocks, unsigned iters, void *out, hipStream_t s);
 

@@ -83,6 +83,8 @@ Knobs read_knobs() {
   k.noHeightField = std::getenv("VR_NO_HEIGHT_FIELD") != nullptr;
   if (const char *e = std::getenv("VR_HF_TILE"))
     k.hfTile = std::max(0.25f, (float)std::atof(e));
+  if (const char *e = std::getenv("VR_MAP_SORT_MIN"))
+    k.mapSortMin = (uint32_t)std::min<unsigned long long>(0xFFFFFFFFull, std::strtoull(e, nullptr, 10));
   k.printLaunches = std::getenv("VR_PRINT_LAUNCHES") != nullptr;
   k.hostSmooth = std::getenv("VR_HOST_SMOOTH") != nullptr;
   if (const char *e = std::getenv("VR_DEBUG_WALK"))

@@ -1,7 +1,9 @@
 // vr_results.cpp — what an apply() left behind: flux, TraceInfo and the data log; normalizeFlux / smoothFlux; areas,
-// bounding box and neighbour counts of the geometry.
+// bounding box and neighbour counts of the geometry; per-primitive values mapped to the caller's points.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "vr_context.hpp"
@@ -15,6 +17,18 @@ static float effective_source_area(const vr_context *c) {
   if (c->src.kind == SourceKind::Surface)
     return c->src.surfArea;
   return c->sourceAreaOverride > 0.f ? c->sourceAreaOverride : c->sourceArea;
+}
+
+// a work buffer of the map grows behind host_waits only (vr_api.cpp: a buffer that moves)
+template <class T> static int map_grow(vr_context *c, DevBuf<T> &b, size_t n, bool &waited) {
+  if (b.holds(n))
+    return VR_OK;
+  if (!waited) {
+    VR_TRY(host_waits(c));
+    waited = true;
+  }
+  VR_HIP(c, b.ensure_grow(n));
+  return VR_OK;
 }
 
 extern "C" {
@@ -289,23 +303,20 @@ int vr_smooth_flux(vr_context *c, float *flux, uint32_t n, int numNeighbors) {
   return VR_OK;
 }
 
-// getLocalData().getVectorData(dataIdx) -> normalizeFlux -> smoothFlux with every stage on the device and the result left
-// in the caller's device buffer: the kernels vr_get_flux_data / vr_normalize_flux / vr_smooth_flux run, on the same floats,
-// so the result has their bits.  Without smoothing nothing comes back to the host and nothing waits; with smoothing one
-// word does (the kernels' overflow flag, which decides on the host fallback).
-int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, int normType, int numNeighbors,
-                       void *stream) {
-  if (!c || !out)
-    return VR_E_INVALID;
+// vr_get_flux_device in three parts, the first two shared with vr_get_flux_at_points_device: what it refuses before it
+// touches anything ...
+static int flux_device_refusal(vr_context *c, uint32_t dataIdx, uint32_t n) {
   if (!c->haveResult)
     return fail(c, VR_E_STATE, "vr_get_flux_device: no result (call vr_apply)");
   if (n != c->geo.numPrims)
     return fail(c, VR_E_INVALID, "vr_get_flux_device: size mismatch");
   if (dataIdx >= c->totalData)
     return fail(c, VR_E_INVALID, "vr_get_flux_device: the particle has no such data label");
-  // (the hand-over of the device setters, vr_api.cpp, the other way round: out may still be in use by work the caller
-  //  queued before this call)
-  VR_TRY(hand_over(c, {n ? out : nullptr}, "vr_get_flux_device: out is not device memory of the context's device", stream));
+  return VR_OK;
+}
+
+// ... its work, queued on the context's stream between the hand-over and its end (`out` is device memory) ...
+static int flux_on_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, int normType, int numNeighbors) {
   const bool smooth = c->geo.geo == 0 && numNeighbors >= 1;
   float *work = out;
   if (smooth) { // (the smoothing kernels read one buffer and write another)
@@ -340,6 +351,148 @@ int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, 
       VR_HIP(c, hipMemcpy(out, h.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     }
   }
+  return VR_OK;
+}
+
+// getLocalData().getVectorData(dataIdx) -> normalizeFlux -> smoothFlux with every stage on the device and the result left
+// in the caller's device buffer: the kernels vr_get_flux_data / vr_normalize_flux / vr_smooth_flux run, on the same floats,
+// so the result has their bits.  Without smoothing nothing comes back to the host and nothing waits; with smoothing one
+// word does (the kernels' overflow flag, which decides on the host fallback).
+int vr_get_flux_device(vr_context *c, uint32_t dataIdx, float *out, uint32_t n, int normType, int numNeighbors,
+                       void *stream) {
+  if (!c || !out)
+    return VR_E_INVALID;
+  VR_TRY(flux_device_refusal(c, dataIdx, n));
+  // (the hand-over of the device setters, vr_api.cpp, the other way round: out may still be in use by work the caller
+  //  queued before this call)
+  VR_TRY(hand_over(c, {n ? out : nullptr}, "vr_get_flux_device: out is not device memory of the context's device", stream));
+  VR_TRY(flux_on_device(c, dataIdx, out, n, normType, numNeighbors));
+  return caller_waits(c, stream);
+}
+
+// ---- per-primitive values at the caller's points (include/viennaray_amd.h has the definition; vr_map.hip the walk) -----
+// what every form refuses before it touches anything; `api`: the entry point's name
+static int map_refusal(vr_context *c, const char *api, uint32_t n, uint32_t ld, float radius) {
+  const std::string name = api;
+  if (n != c->geo.numPrims)
+    return fail(c, VR_E_INVALID, (name + ": size mismatch (n must be the number of primitives)").c_str());
+  if (ld != 2 && ld != 3)
+    return fail(c, VR_E_INVALID, (name + ": ld is 2 or 3 floats per row").c_str());
+  if (ld == 2 && c->geo.D != 2)
+    return fail(c, VR_E_INVALID, (name + ": rows of 2 floats need a 2-D scene").c_str());
+  if (!(radius >= 0.f) || !std::isfinite(radius))
+    return fail(c, VR_E_INVALID, (name + ": the radius must be finite and not negative").c_str());
+  return VR_OK;
+}
+// the walk needs the device build of the geometry in force: its float4 nodes and packed records (kept for disks and
+// triangles alike; the host builder, VR_HOST_BUILD, leaves none)
+static int map_state_refusal(vr_context *c, const char *api) {
+  if (!c->haveSetup || c->geometryDirty || c->knobs.hostBuild || c->geo.numPrims == 0)
+    return fail(c, VR_E_STATE, (std::string(api) + ": no scene build is resident for the geometry in force (call vr_apply or "
+                                                   "vr_apply_prepare after setting it)").c_str());
+  return VR_OK;
+}
+// the kernels, on the context's stream: every pointer is device memory, the arguments have been accepted
+static int map_on_device(vr_context *c, const float *values, const float *points, const float *normals, uint32_t m,
+                         uint32_t ld, float radius, float *out) {
+  const uint32_t *perm = nullptr;
+  bool waited = false;
+  // (beyond 2^31 queries the pairs alone would take 48 GiB: walked in the caller's order)
+  if (m >= read_knobs().mapSortMin && m <= (1u << 31)) {
+    const size_t tiles = ((size_t)m + 1023) / 1024;
+    VR_TRY(map_grow(c, c->dMapKeysA, m, waited));
+    VR_TRY(map_grow(c, c->dMapKeysB, m, waited));
+    VR_TRY(map_grow(c, c->dMapValsA, m, waited));
+    VR_TRY(map_grow(c, c->dMapValsB, m, waited));
+    VR_TRY(map_grow(c, c->dMapSortTable, 256 * tiles, waited));
+    VR_TRY(map_grow(c, c->dMapScanTmp, 2 * ((256 * tiles) / 2048 + 4) + 64, waited));
+    VR_HIP(c, launch_map_keys(points, m, ld, c->geo.D, c->sceneLo, c->sceneHi, c->dMapKeysA.p, c->dMapValsA.p, c->stream));
+    VR_HIP(c, launch_sort_pairs(c->dMapKeysA.p, c->dMapValsA.p, c->dMapKeysB.p, c->dMapValsB.p, m, c->dMapSortTable.p,
+                                c->dMapScanTmp.p, c->stream));
+    perm = c->dMapValsA.p;
+  }
+  unsigned long long *visits = nullptr;
+#ifdef VR_DIAG
+  VR_TRY(map_grow(c, c->dMapVisits, 1, waited));
+  visits = c->dMapVisits.p;
+  VR_HIP(c, hipMemsetAsync(visits, 0, 8, c->stream));
+#endif
+  VR_HIP(c, launch_map_points(c->lastSetup, values, points, normals, m, ld, radius, perm, out, visits, c->stream));
+#ifdef VR_DIAG
+  if (c->knobs.printLaunches) { // (the diagnostic build's figure, for tools/map_points_bench.py)
+    unsigned long long v = 0;
+    VR_HIP(c, hipMemcpyAsync(&v, visits, 8, hipMemcpyDeviceToHost, c->stream));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    std::fprintf(stderr, "map_points: m=%u sorted=%d node visits per query %.2f\n", m, perm ? 1 : 0, (double)v / m);
+  }
+#endif
+  return VR_OK;
+}
+
+int vr_map_to_points_device(vr_context *c, const float *values, uint32_t n, const float *points, const float *normals,
+                            uint32_t m, uint32_t ld, float radius, float *out, void *stream) {
+  if (!c)
+    return VR_E_INVALID;
+  VR_TRY(map_refusal(c, "vr_map_to_points_device", n, ld, radius));
+  if (m == 0)
+    return VR_OK;
+  if (!values || !points || !out)
+    return fail(c, VR_E_INVALID, "vr_map_to_points_device: values, points and out must not be null");
+  VR_TRY(map_state_refusal(c, "vr_map_to_points_device"));
+  VR_TRY(hand_over(c, {values, points, normals, out},
+                   "vr_map_to_points_device: values, points, normals and out must be device memory of the context's device",
+                   stream));
+  VR_TRY(map_on_device(c, values, points, normals, m, ld, radius, out));
+  return caller_waits(c, stream);
+}
+
+int vr_map_to_points(vr_context *c, const float *values, uint32_t n, const float *points3, const float *normals3,
+                     uint32_t m, float radius, float *out) {
+  if (!c)
+    return VR_E_INVALID;
+  VR_TRY(map_refusal(c, "vr_map_to_points", n, 3, radius));
+  if (m == 0)
+    return VR_OK;
+  if (!values || !points3 || !out)
+    return fail(c, VR_E_INVALID, "vr_map_to_points: values, points3 and out must not be null");
+  VR_TRY(map_state_refusal(c, "vr_map_to_points"));
+  VR_HIP(c, hipSetDevice(c->device));
+  bool waited = false;
+  VR_TRY(map_grow(c, c->dMapValues, n, waited));
+  VR_TRY(map_grow(c, c->dMapPoints, (size_t)m * 3, waited));
+  if (normals3)
+    VR_TRY(map_grow(c, c->dMapNormals, (size_t)m * 3, waited));
+  VR_TRY(map_grow(c, c->dMapOut, m, waited));
+  VR_HIP(c, hipMemcpyAsync(c->dMapValues.p, values, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  VR_HIP(c, hipMemcpyAsync(c->dMapPoints.p, points3, (size_t)m * 12, hipMemcpyHostToDevice, c->stream));
+  if (normals3)
+    VR_HIP(c, hipMemcpyAsync(c->dMapNormals.p, normals3, (size_t)m * 12, hipMemcpyHostToDevice, c->stream));
+  VR_TRY(map_on_device(c, c->dMapValues.p, c->dMapPoints.p, normals3 ? c->dMapNormals.p : nullptr, m, 3, radius,
+                       c->dMapOut.p));
+  VR_HIP(c, hipMemcpyAsync(out, c->dMapOut.p, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  return VR_OK;
+}
+
+int vr_get_flux_at_points_device(vr_context *c, uint32_t dataIdx, int normType, int numNeighbors, const float *points,
+                                 const float *normals, uint32_t m, uint32_t ld, float radius, float *out, void *stream) {
+  if (!c)
+    return VR_E_INVALID;
+  const uint32_t n = c->geo.numPrims;
+  VR_TRY(map_refusal(c, "vr_get_flux_at_points_device", n, ld, radius));
+  VR_TRY(flux_device_refusal(c, dataIdx, n));
+  if (m == 0)
+    return VR_OK;
+  if (!points || !out)
+    return fail(c, VR_E_INVALID, "vr_get_flux_at_points_device: points and out must not be null");
+  VR_TRY(map_state_refusal(c, "vr_get_flux_at_points_device"));
+  VR_TRY(hand_over(c, {points, normals, out},
+                   "vr_get_flux_at_points_device: points, normals and out must be device memory of the context's device",
+                   stream));
+  bool waited = false;
+  VR_TRY(map_grow(c, c->dMapFlux, n, waited));
+  VR_TRY(flux_on_device(c, dataIdx, c->dMapFlux.p, n, normType, numNeighbors));
+  VR_TRY(map_on_device(c, c->dMapFlux.p, points, normals, m, ld, radius, out));
   return caller_waits(c, stream);
 }
 

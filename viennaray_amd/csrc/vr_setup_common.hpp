@@ -1,5 +1,5 @@
 // vr_setup_common.hpp — what the set-up, ingest, field and results kernels share: the 64-bit word and the ordered-uint
-// trick.  Private to vr_bvh.hip, vr_sort.hip, vr_fields.hip, vr_ingest.hip and vr_post.hip.
+// trick.  Private to vr_bvh.hip, vr_sort.hip, vr_fields.hip, vr_ingest.hip, vr_post.hip and vr_map.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

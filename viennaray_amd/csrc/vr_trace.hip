@@ -35,7 +35,8 @@
 //   vr_fields.hip        height field and relief field over the source plane (every prepare)
 //   vr_ingest.hip        device-resident inputs: disks, meshes, sort-plane histogram, global data, sticking, surface source
 //   vr_post.hip          the results stage: smoothing, areas, flux gather, normalisation, statistics
-//   vr_setup_common.hpp  private to those five: the ordered-uint trick
+//   vr_map.hip           per-primitive values at the caller's points: a range / nearest walk of the resident BVH
+//   vr_setup_common.hpp  private to those six: the ordered-uint trick
 // A run-time module is compiled from this file and what it includes: the Makefile's MODEL_SRCS names those files once.
 #include <hip/hip_runtime.h>
 

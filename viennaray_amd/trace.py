@@ -720,6 +720,72 @@ class Trace:
                                                C.c_void_p(stream)))
         return out
 
+    # --- per-primitive values at the caller's points (vr_map_to_points*, include/viennaray_amd.h has the definition) ----
+    def _mapArgs(self, what, points, normals, radius):
+        """(device?, points, normals, m, ld, radius): float32 torch tensors on the tracer's device go as they are
+        (anything else about a tensor raises ValueError), host arrays as contiguous [m, 3] float32"""
+        radius = 2.0 * getattr(self, "_gridDelta", 0.0) if radius is None else float(radius)
+        if _on_any_device(points) or (normals is not None and _on_any_device(normals)) or hasattr(points, "data_ptr"):
+            cols = [(None, 2), (None, 3)] if self.D == 2 else [(None, 3)]
+            _check_device_tensor(what, "points", points, self._device, "torch.float32", cols)
+            if normals is not None:
+                _check_device_tensor(what, "normals", normals, self._device, "torch.float32", [tuple(points.shape)])
+            return True, points, normals, int(points.shape[0]), int(points.shape[1]), radius
+        p = np.asarray(points, dtype=np.float32)
+        p = p.reshape(-1, p.shape[-1]) if p.ndim == 2 else p.reshape(-1, 3)
+        q = None if normals is None else np.asarray(normals, dtype=np.float32).reshape(p.shape)
+        if p.shape[1] == 2:  # 2-D rows: z := 0, as setGeometry does
+            p = np.concatenate([p, np.zeros((p.shape[0], 1), np.float32)], axis=1)
+            q = None if q is None else np.concatenate([q, np.zeros((q.shape[0], 1), np.float32)], axis=1)
+        p = np.ascontiguousarray(p)
+        q = None if q is None else np.ascontiguousarray(q)
+        return False, p, q, int(p.shape[0]), 3, radius
+
+    def mapToPoints(self, values, points, normals=None, radius=None):
+        """One float per primitive (caller's order) mapped to the m query points: the mean of `values` over the primitive
+        centres within `radius` (None: 2 * gridDelta) weighted by (1 - d / radius) * max(0, n_j . normal_i) — no gate
+        without normals — or the value of the nearest centre where that sum of weights is not positive (radius 0,
+        nothing in range, every normal facing away).  Plain Euclidean distances, no periodic wrap; 2-D scenes ignore z.
+        float32 torch tensors on the tracer's device in give a tensor out, computed on the device and ordered on the
+        current torch stream (vr_map_to_points_device; a tensor of another dtype or device, or a non-contiguous one,
+        raises ValueError); host arrays in give a numpy array out (vr_map_to_points).  Needs the scene build of the
+        geometry in force: call apply() (or applyPrepare()) first."""
+        dev, p, q, m, ld, radius = self._mapArgs("mapToPoints", points, normals, radius)
+        if dev:
+            import torch
+            _check_device_tensor("mapToPoints", "values", values, self._device, "torch.float32", [(None,)])
+            out = torch.empty(m, dtype=torch.float32, device=p.device)
+            self._check(self._L.vr_map_to_points_device(
+                self._h, C.c_void_p(values.data_ptr()), int(values.shape[0]), C.c_void_p(p.data_ptr()),
+                C.c_void_p(q.data_ptr()) if q is not None else None, m, ld, radius, C.c_void_p(out.data_ptr()),
+                C.c_void_p(self._torch_stream())))
+            return out
+        if hasattr(values, "data_ptr"):
+            raise ValueError("mapToPoints: device: values is a tensor while points is a host array "
+                             "(all on the device, or all on the host)")
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        out = np.empty(m, dtype=np.float32)
+        self._check(self._L.vr_map_to_points(self._h, _fptr(v), v.size, _fptr(p), _fptr(q) if q is not None else None, m,
+                                             radius, _fptr(out)))
+        return out
+
+    def getFluxAtPoints(self, points, normals=None, radius=None, dataIdx=0, norm=None, numNeighbors=0):
+        """getFluxTensor(dataIdx, norm, numNeighbors) mapped to the query points as mapToPoints maps values, without the
+        flux leaving the device (vr_get_flux_at_points_device); works after apply(collect=False).  Tensors in: a tensor
+        out on the current torch stream.  Host arrays in: they are uploaded, and a numpy array comes back."""
+        dev, p, q, m, ld, radius = self._mapArgs("getFluxAtPoints", points, normals, radius)
+        import torch
+        tdev = torch.device("cuda", self._device)
+        if not dev:
+            p = torch.from_numpy(p).to(tdev)
+            q = None if q is None else torch.from_numpy(q).to(tdev)
+        out = torch.empty(m, dtype=torch.float32, device=tdev)
+        self._check(self._L.vr_get_flux_at_points_device(
+            self._h, int(dataIdx), capi.VR_NORM_NONE if norm is None else int(norm), int(numNeighbors),
+            C.c_void_p(p.data_ptr()), C.c_void_p(q.data_ptr()) if q is not None else None, m, ld, radius,
+            C.c_void_p(out.data_ptr()), C.c_void_p(self._torch_stream())))
+        return out if dev else out.cpu().numpy()
+
     # --- flux statistics: per-primitive hit counts and the Monte-Carlo error of the flux --------------------------
     def setCalculateFluxError(self, on=True):
         """Keep two more sums per primitive and particle alongside the flux label (vr_set_flux_statistics): the number of
@@ -972,6 +1038,7 @@ class TraceDisk(Trace):
         self._n = p.shape[0]
         self._check(self._L.vr_set_disks(self._h, _fptr(p), _fptr(n), self._n, float(gridDelta),
                                          float(diskRadius), self.D))
+        self._gridDelta = float(gridDelta)
 
     def _setGeometryDevice(self, points, normals, gridDelta, diskRadius):
         # (two columns need D == 2: refused as a shape, where the shape is looked at)
@@ -985,6 +1052,7 @@ class TraceDisk(Trace):
                                                 n, ld, float(gridDelta), float(diskRadius), self.D,
                                                 C.c_void_p(self._torch_stream())))
         self._n = n
+        self._gridDelta = float(gridDelta)
 
     def getDiskAreas(self):
         out = np.empty(self._n, dtype=np.float32)
@@ -1026,6 +1094,7 @@ class TraceTriangle(Trace):
         self._check(self._L.vr_set_triangles(self._h, _fptr(v), v.shape[0],
                                              t.ctypes.data_as(C.POINTER(C.c_uint32)), self._n,
                                              float(gridDelta), self.D))
+        self._gridDelta = float(gridDelta)
 
     def debugTriangleMesh(self):
         """(unit normals [nt, 3], areas [nt]) of the mesh in force (vr_debug_triangle_mesh)"""
@@ -1042,3 +1111,4 @@ class TraceTriangle(Trace):
                                                     C.c_void_p(triangles.data_ptr()), nt, float(gridDelta), self.D,
                                                     C.c_void_p(self._torch_stream())))
         self._n = nt
+        self._gridDelta = float(gridDelta)
