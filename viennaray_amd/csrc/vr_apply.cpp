@@ -377,6 +377,9 @@ int vr_apply_finish(vr_context *c) {
       // (launch 1 above: a kernel of the uniform family ran; here: whether it was the planar one)
       std::fprintf(stderr, "[vr] planar disks: scene %d, VR_PLANAR_DISKS %d, launch %d, particle %zu\n", (int)c->planarDisks,
                    (int)c->knobs.planarDisks, (int)L.planarDisks, q);
+      // (... and whether it was that kernel's one-point-per-round form)
+      std::fprintf(stderr, "[vr] planar disks: round: VR_PLANAR_ROUND %d, launch %d, particle %zu\n", (int)c->knobs.planarRound,
+                   (int)L.planarRound, q);
     }
   const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
   if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)

@@ -118,6 +118,7 @@ struct Knobs {
   bool binAlign = true;                // VR_BIN_ALIGN (0: off): sort bins aligned with the disk lattice (3-D, disks; vr_bin_grid.hpp)
   bool uniformDisks = true;            // VR_UNIFORM_DISKS (0: off): the absorbing flat-scene kernel's uniform-disk variants where the scene allows them
   bool planarDisks = true;             // VR_PLANAR_DISKS (0: off): ... the planar one of them (off: planar disks run the uniform-disk kernel)
+  bool planarRound = true;             // VR_PLANAR_ROUND (0: off): ... in its one-point-per-round form (off: the planar kernel as it was)
   std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
   std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
   // kernel parameters (TraceParams)
@@ -201,7 +202,12 @@ struct ParticleLaunch {
   // ... and the scene's disks are planar (vr_context::planarDisks) with VR_PLANAR_DISKS on: the planar variant of that
   // kernel, the plane's axis and coordinate in the frame as well (VR_F_PD_*).  Only ever set with uniformDisks
   bool planarDisks = false;
+  // ... with VR_PLANAR_ROUND on: that kernel's one-point-per-round form, its words in the frame as well (VR_F_PR_*).  Only
+  // ever set with planarDisks
+  bool planarRound = false;
   int kernel_mode() const { // the mode launch_trace takes
+    if (planarRound)
+      return (int)MODE_ABSORB_FLAT_PLANAR_ROUND;
     return planarDisks ? (int)MODE_ABSORB_FLAT_PLANAR : (uniformDisks ? (int)MODE_ABSORB_FLAT_UNIFORM : traceMode);
   }
   bool absorb = false;

@@ -24,6 +24,13 @@ enum { VR_F_SRC_PLANE = 96, VR_F_RAYDIR = 97, VR_F_FIRSTDIR = 98, VR_F_SECONDDIR
        // the axis a of the normal's +-1 (an int) and the one coordinate a of every centre (vr_planar_disks.hpp), in the
        // next words of the same block
        VR_F_PD_AXIS = VR_F_HF_SIGN, VR_F_PD_COORD = VR_F_HF_NX,
+       // ... and that runs the one-point-per-round kernel (ParticleLaunch::planarRound; read only by trace_kernel
+       // MODE_ABSORB_FLAT_PLANAR_ROUND; vr_planar_disks.hpp (2), (3)).  Such a launch has neither a height field nor a
+       // relief field: these are words of theirs.  QLO / QHI: the query box along the plane's axis, coordinate -+ pad;
+       // IN: the wall rectangle shrunk by the wall-free margin {lo1, hi1, lo2, hi2} (empty where the rule does not hold);
+       // SB: the scene box along the two in-plane axes, widened by the pad {lo1, hi1, lo2, hi2}
+       VR_F_PR_QLO = VR_F_HF_NY, VR_F_PR_QHI = VR_F_HF_PTR_LO, VR_F_PR_IN = 128 /* VR_F_RF_LO1 .. VR_F_RF_TILE */,
+       VR_F_PR_SB = 132 /* VR_F_RF_NX .. VR_F_RF_PTR_HI */,
        // the relief field's fine tiles (ReliefParams; NX = 0: none): relief_clip below
        VR_F_RF_LO1 = 128, VR_F_RF_LO2 = 129, VR_F_RF_INVT = 130, VR_F_RF_TILE = 131, VR_F_RF_NX = 132, VR_F_RF_NY = 133,
        VR_F_RF_PTR_LO = 134, VR_F_RF_PTR_HI = 135,

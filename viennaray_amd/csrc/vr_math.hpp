@@ -83,6 +83,23 @@ __device__ __forceinline__ void wave_minmax6(float &a, float &b, float &c, float
   f = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f), 63));
 }
 
+// ... four of them (two minima, two maxima): every chain's next step stands four instructions behind the last, which
+// still fills the two wait states of a DPP read
+__device__ __forceinline__ void wave_minmax4(float &a, float &b, float &c, float &d) {
+#define VR_DPP4(ctrl)                                                                                                  \
+  "v_min_f32_dpp %0, %0, %0 " ctrl "\n v_min_f32_dpp %1, %1, %1 " ctrl "\n"                                             \
+  "v_max_f32_dpp %2, %2, %2 " ctrl "\n v_max_f32_dpp %3, %3, %3 " ctrl "\n"
+  asm volatile("s_nop 4\n" VR_DPP4("row_shr:1 row_mask:0xf bank_mask:0xf") VR_DPP4("row_shr:2 row_mask:0xf bank_mask:0xf")
+                   VR_DPP4("row_shr:4 row_mask:0xf bank_mask:0xf") VR_DPP4("row_shr:8 row_mask:0xf bank_mask:0xf")
+                       VR_DPP4("row_bcast:15 row_mask:0xa bank_mask:0xf") VR_DPP4("row_bcast:31 row_mask:0xc bank_mask:0xf")
+               : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+#undef VR_DPP4
+  a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63));
+  b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), 63));
+  c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), 63));
+  d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), 63));
+}
+
 // Pointers into LDS carry their address space in the type where they are volatile or travel through a struct: address-
 // space inference leaves such accesses on GENERIC pointers, i.e. flat_load / flat_store (the slow path to LDS, waiting on
 // both memory counters) — the packet query's frontier lists were read and written that way until round 3.

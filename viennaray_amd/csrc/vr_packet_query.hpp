@@ -118,6 +118,7 @@ struct PqCands {
   unsigned count; // wave-uniform
   bool box;       // KEEPQ: records VR_PQ_BOX, + 1 hold the query's box (false: no ray reached the scene, nothing stored)
   unsigned mine;  // per lane: the candidate that is this lane's closest hit so far (valid where the hit came from the query)
+  PlanarRound round; // ROUND: the round's point and thresholds, the caller's (trace_kernel computes them before the walls)
 };
 constexpr unsigned VR_PQ_CANDS = 52; // >= 2 * pqMaxCand + 1 (pqMaxCand <= 24, vr_knobs.cpp) + the two records below
 // KEEPQ: records 50 / 51 keep the query's (padded) box {lo.xyz, -}{hi.xyz, -} for the round's follow-up segments
@@ -147,8 +148,11 @@ constexpr unsigned VR_PQ_RECORDS = 2 * 52;
 // PLANAR (UNIFORM, for disks that also share a plane normal to a coordinate axis — the frame's VR_F_PD_*): the point where the
 // ray crosses that plane is the ray's own; the two divisions, the two points and the range tests once per round, a
 // distance to the centre per candidate (vr_planar_disks.hpp has the argument)
+// ROUND (PLANAR): that point is computed once, by the caller (cd.round), and serves both candidate tests; the query's box is
+// the box around the wave's points, four reductions and no division, in place of the box around the rays' stretches
+// through the scene box (vr_planar_disks.hpp (1), (2))
 template <int GEO, bool CREDIT, bool FRAME_LDS = false, bool KEEPQ = false, bool RELIEF = false, bool CACHE = false, bool LEAN = false,
-          bool UNIFORM = false, bool PLANAR = false>
+          bool UNIFORM = false, bool PLANAR = false, bool ROUND = false>
 __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, const V3 &o, const V3 &d, float tnear,
                                               HitRec &h, volatile VR_LDS unsigned *lst, PqCands &cd,
                                               const float *__restrict__ wallS, volatile VR_LDS float *cboxes, float tWall VR_DIAG_ARGS) {
@@ -169,7 +173,7 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
   cd.local = 0ull;
   const float big = 3.0e38f;
   cd.box = false;
-  if (!ballot64(valid))
+  if (!ROUND && !ballot64(valid))
     return true; // nobody reaches the scene box: every ray misses the geometry
   // (Q starts at the ray's origin where that lies inside the box, not at tnear: the neighbour test
   //  accepts any t > 0)
@@ -188,7 +192,8 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
   const float bx = o.x + d.x * tEnd, by = o.y + d.y * tEnd, bz = o.z + d.z * tEnd;
   float qlx = valid ? fminf(ax, bx) : big, qly = valid ? fminf(ay, by) : big, qlz = valid ? fminf(az, bz) : big;
   float qhx = valid ? fmaxf(ax, bx) : -big, qhy = valid ? fmaxf(ay, by) : -big, qhz = valid ? fmaxf(az, bz) : -big;
-  wave_minmax6(qlx, qly, qlz, qhx, qhy, qhz);
+  if constexpr (!ROUND)
+    wave_minmax6(qlx, qly, qlz, qhx, qhy, qhz);
   const float pad = FRAME_LDS ? wallS[VR_F_PQ_PAD] : p.pqPad;
   qlx -= pad;
   qly -= pad;
@@ -196,6 +201,30 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
   qhx += pad;
   qhy += pad;
   qhz += pad;
+  if constexpr (ROUND) { // the box around the wave's points instead (everything above it is then dead code)
+    static_assert(PLANAR && FRAME_LDS && !KEEPQ && !RELIEF, "the round's point is a planar launch's");
+    const int pa = __float_as_int(wallS[VR_F_PD_AXIS]);
+    int b1, b2;
+    planar_in_plane_axes(pa, b1, b2);
+    const V3 q = mk(cd.round.qx, cd.round.qy, cd.round.qz);
+    const float u = getc(q, b1), v = getc(q, b2);
+    const bool in = planar_round_valid(cd.round, u, v, tWall, wallS[VR_F_PR_SB], wallS[VR_F_PR_SB + 1], wallS[VR_F_PR_SB + 2], wallS[VR_F_PR_SB + 3]);
+    if (!ballot64(in))
+      return true; // nobody's point lies in the scene: every ray misses the geometry
+    float ulo = in ? u : big, vlo = in ? v : big, uhi = in ? u : -big, vhi = in ? v : -big;
+    wave_minmax4(ulo, vlo, uhi, vhi);
+    ulo -= pad;
+    vlo -= pad;
+    uhi += pad;
+    vhi += pad;
+    const float alo = wallS[VR_F_PR_QLO], ahi = wallS[VR_F_PR_QHI];
+    qlx = pa == 0 ? alo : ulo;
+    qhx = pa == 0 ? ahi : uhi;
+    qly = pa == 1 ? alo : (pa == 0 ? ulo : vlo);
+    qhy = pa == 1 ? ahi : (pa == 0 ? uhi : vhi);
+    qlz = pa == 2 ? alo : vlo;
+    qhz = pa == 2 ? ahi : vhi;
+  }
   if (KEEPQ) {
     cd.box = true;
     if (lane == 0u) {
@@ -397,7 +426,7 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
   }
   PlanarHit pdH{};
   PlanarLocal pdL{};
-  if constexpr (PLANAR) {
+  if constexpr (PLANAR && !ROUND) {
     static_assert(UNIFORM, "planar disks are uniform disks");
     const int pa = __float_as_int(wallS[VR_F_PD_AXIS]);
     const float ca = wallS[VR_F_PD_COORD], s = getc(un, pa);
@@ -447,7 +476,11 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
         const V3 cc = mk(lane_bcast(r0.x, k), lane_bcast(r0.y, k), lane_bcast(r0.z, k));
         const unsigned orig = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(r1.w), k);
         bool ok;
-        if constexpr (PLANAR) { // (the range tests and `part` are in the round's point: vr_planar_disks.hpp)
+        [[maybe_unused]] bool okLocal = false;
+        if constexpr (ROUND) { // (one difference and one square per coordinate for both tests: vr_planar_disks.hpp (1))
+          planar_round_cand(cd.round, cc.x, cc.y, cc.z, ok, okLocal);
+          t = cd.round.t;
+        } else if constexpr (PLANAR) { // (the range tests and `part` are in the round's point: vr_planar_disks.hpp)
           ok = planar_hit_cand(pdH, cc.x, cc.y, cc.z, uRadius);
           t = pdH.t;
         } else {
@@ -461,7 +494,9 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
             cd.rec[c] = mk_u4(qq, __float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r0.z));
             cd.rec[VR_PQ_NRM + c] = mk_u4(__float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), __float_as_uint(r0.w));
           }
-          if constexpr (PLANAR)
+          if constexpr (ROUND)
+            cd.local |= (unsigned long long)okLocal << c;
+          else if constexpr (PLANAR)
             cd.local |= (unsigned long long)planar_local_cand(pdL, cc.x, cc.y, cc.z, uThresh) << c;
           else
             cd.local |= (unsigned long long)(part & local_disc_hit_uniform(o, d, cc, un, uProd, uNro, uThresh)) << c;

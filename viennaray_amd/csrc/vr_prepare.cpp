@@ -10,6 +10,7 @@
 
 #include "vr_context.hpp"
 #include "vr_particles.hpp"
+#include "vr_planar_disks.hpp"
 #include "vr_uniform_disks.hpp"
 
 namespace vr {
@@ -616,6 +617,8 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   L.uniformDisks = K.uniformDisks && c->uniformDisks && L.traceMode == MODE_ABSORB_FLAT && D == 3 && c->geo.geo == 0 && sp.userModel < 0;
   // ... in its planar variant where the disks also share a plane normal to a coordinate axis (vr_context::planarDisks)
   L.planarDisks = L.uniformDisks && K.planarDisks && c->planarDisks;
+  // ... and that one in its one-point-per-round form (vr_planar_disks.hpp (1) - (3))
+  L.planarRound = L.planarDisks && K.planarRound;
   int blocks = 1;
   L.userKernel = nullptr;
   L.userGen = nullptr;
@@ -963,6 +966,22 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
     if (L.planarDisks) { // (VR_F_PD_*: the next words of the same block)
       f[VR_F_PD_AXIS] = bits(c->planarAxis);
       f[VR_F_PD_COORD] = bits((int32_t)c->planarWord);
+    }
+    if (L.planarRound) { // (VR_F_PR_*: words of the height field and of the relief field, which such a launch has not)
+      if (L.relief)
+        return fail(c, VR_E_STATE, "a planar-round launch has no relief field: their frame words are the same");
+      float ca;
+      std::memcpy(&ca, &c->planarWord, 4);
+      f[VR_F_PR_QLO] = ca - p.pqPad;
+      f[VR_F_PR_QHI] = ca + p.pqPad;
+      planar_wall_inner(p.lo1, p.hi1, f[VR_F_PR_IN], f[VR_F_PR_IN + 1]);
+      planar_wall_inner(p.lo2, p.hi2, f[VR_F_PR_IN + 2], f[VR_F_PR_IN + 3]);
+      int b1, b2;
+      planar_in_plane_axes(c->planarAxis, b1, b2);
+      f[VR_F_PR_SB] = p.sceneLo[b1] - p.pqPad;
+      f[VR_F_PR_SB + 1] = p.sceneHi[b1] + p.pqPad;
+      f[VR_F_PR_SB + 2] = p.sceneLo[b2] - p.pqPad;
+      f[VR_F_PR_SB + 3] = p.sceneHi[b2] + p.pqPad;
     }
   }
   if (L.relief) { // the relief field's fine tiles (relief_clip, vr_packet_query.hpp)

@@ -100,6 +100,10 @@ template <int D, int GEO, int PARTICLE> static StreamKernel trace_kernel_of(int 
     if constexpr (D == 3 && GEO == 0)
       return trace_kernel<3, 0, 0, MODE_ABSORB_FLAT_PLANAR>;
     return trace_kernel<D, GEO, 0, MODE_ABSORB_FLAT>;
+  case MODE_ABSORB_FLAT_PLANAR_ROUND: // (likewise)
+    if constexpr (D == 3 && GEO == 0)
+      return trace_kernel<3, 0, 0, MODE_ABSORB_FLAT_PLANAR_ROUND>;
+    return trace_kernel<D, GEO, 0, MODE_ABSORB_FLAT>;
   case MODE_ABSORB:return trace_kernel<D, GEO, 0, MODE_ABSORB>;
   case MODE_GENERAL_FLAT:
     if constexpr (FLAT)
@@ -120,7 +124,7 @@ template <int D, int GEO, int PARTICLE> static StreamKernel trace_kernel_of(int 
 }
 static StreamKernel trace_kernel_for(int D, int geo, int particle, int mode) {
   if (mode == MODE_ABSORB_FLAT || mode == MODE_ABSORB || mode == MODE_ABSORB_RELIEF || mode == MODE_ABSORB_FLAT_UNIFORM ||
-      mode == MODE_ABSORB_FLAT_PLANAR)
+      mode == MODE_ABSORB_FLAT_PLANAR || mode == MODE_ABSORB_FLAT_PLANAR_ROUND)
     particle = 0; // the reflection model is unobservable: one instantiation serves all
 #define VR_VARIANT(K, DD, GG, PP)                                                                                      \
   case K: return trace_kernel_of<DD, GG, PP>(mode);

@@ -184,7 +184,7 @@ __device__ __forceinline__ void spill_pad(const TraceParams &p, unsigned base, u
     reinterpret_cast<float4 *>(p.spillRec)[4 * (size_t)(base + lane) + 2] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xFFFFFFFFu));
 }
 constexpr int vr_mode_waves(int m) {
-  return m == MODE_ABSORB_RELIEF ? VR_RELIEF_WAVES : (m == MODE_ABSORB_FLAT || m == MODE_ABSORB_FLAT_UNIFORM || m == MODE_ABSORB_FLAT_PLANAR) ? 8 : (m == MODE_ABSORB ? 7 : ((m == MODE_GENERAL_FLAT || m == MODE_GENERAL_RELIEF) ? VR_FLAT_WAVES : (m == MODE_SMALL ? VR_SMALL_WAVES : VR_GENERAL_WAVES)));
+  return m == MODE_ABSORB_RELIEF ? VR_RELIEF_WAVES : (m == MODE_ABSORB_FLAT || m == MODE_ABSORB_FLAT_UNIFORM || m == MODE_ABSORB_FLAT_PLANAR || m == MODE_ABSORB_FLAT_PLANAR_ROUND) ? 8 : (m == MODE_ABSORB ? 7 : ((m == MODE_GENERAL_FLAT || m == MODE_GENERAL_RELIEF) ? VR_FLAT_WAVES : (m == MODE_SMALL ? VR_SMALL_WAVES : VR_GENERAL_WAVES)));
 }
 template <int D, int GEO, int PARTICLE, int MODE_>
 __global__ __launch_bounds__(VR_BLOCK) __attribute__((amdgpu_num_sgpr(80)))
@@ -193,7 +193,8 @@ trace_kernel(const TraceParams p) {
   constexpr bool SMALL = MODE_ == MODE_SMALL;
   constexpr bool RELIEF = MODE_ == MODE_ABSORB_RELIEF || MODE_ == MODE_GENERAL_RELIEF;
   constexpr bool RESUME = MODE_ == MODE_RESUME;
-  constexpr bool PLANAR = MODE_ == MODE_ABSORB_FLAT_PLANAR;   // (... with its PLANAR candidate tests, which are UNIFORM ones)
+  constexpr bool PLANAR_ROUND = MODE_ == MODE_ABSORB_FLAT_PLANAR_ROUND; // (... with the plane hit as the round's one point: pq_hit_packet ROUND, wall-free rounds)
+  constexpr bool PLANAR = MODE_ == MODE_ABSORB_FLAT_PLANAR || PLANAR_ROUND; // (... with its PLANAR candidate tests, which are UNIFORM ones)
   constexpr bool UNIFORM = MODE_ == MODE_ABSORB_FLAT_UNIFORM || PLANAR; // (MODE_ABSORB_FLAT with pq_hit_packet's UNIFORM candidate tests)
   constexpr int MODE = (SMALL || RESUME) ? MODE_GENERAL : ((MODE_ == MODE_ABSORB_RELIEF || UNIFORM) ? MODE_ABSORB_FLAT : (MODE_ == MODE_GENERAL_RELIEF ? MODE_GENERAL_FLAT : MODE_));
   constexpr bool FRAME_LDS = MODE == MODE_ABSORB_FLAT; // (the wall / scene-box frame from LDS: hit_walls_lds, vr_intersect.hpp)
@@ -580,6 +581,7 @@ trace_kernel(const TraceParams p) {
         !(p.debugFlags & 32u) && carried == 0ull && packetSkip == 0 && __popcll(ballot64(active)) >= 8;
     bool packetDone = false;
     bool pqCredit = false; // this round's surface hits are credited from the packet's candidate list
+    [[maybe_unused]] bool wallFree = false; // PLANAR_ROUND: no active lane of this round can meet a wall before its plane hit (wave-uniform)
     if (!SMALL && usePacket && p.wide && !(p.debugFlags & 128u)) {
       // first choice: the box query (one wide-tree search for the whole wave)
       if (pqSkip == 0) {
@@ -590,8 +592,23 @@ trace_kernel(const TraceParams p) {
         // (the walls first for the flat-scene kernels' queries: see pq_hit_packet, tWall.  The conservative pre-tests of
         //  hit_walls let only the rays near a side wall through to the exact test)
         float tWall = 3.402823466e+38f;
+        if constexpr (PLANAR_ROUND) {
+          // the round's point (vr_planar_disks.hpp (1)), and the vote on its walls (3): where every active lane starts
+          // inside the walls and lands well inside them, no wall can come before a plane hit — no wall test before the
+          // query (tWall stays infinite), and behind it only for the lanes the query left without a hit
+          const int pa = __float_as_int(wallS[VR_F_PD_AXIS]);
+          const float s = wallS[VR_F_UD_N + pa];
+          cands.round = planar_round_point(active, org.x, org.y, org.z, dir.x, dir.y, dir.z, getc(org, pa), getc(dir, pa) * s, tnear,
+                                           wallS[VR_F_PD_COORD], s, wallS[VR_F_UD_RADIUS], wallS[VR_F_UD_T]);
+          const int a1 = __float_as_int(wallS[VR_F_FIRSTDIR]), a2 = __float_as_int(wallS[VR_F_SECONDDIR]);
+          const V3 q = mk(cands.round.qx, cands.round.qy, cands.round.qz);
+          const PlanarWallRect wr{wallS[VR_F_LO1], wallS[VR_F_LO1 + 1], wallS[VR_F_LO1 + 2], wallS[VR_F_LO1 + 3]};
+          const PlanarWallRect wi{wallS[VR_F_PR_IN], wallS[VR_F_PR_IN + 1], wallS[VR_F_PR_IN + 2], wallS[VR_F_PR_IN + 3]};
+          const bool walled = active && !planar_wall_free(getc(org, a1), getc(org, a2), getc(q, a1), getc(q, a2), wr, wi);
+          wallFree = ballot64(walled) == 0ull;
+        }
         if constexpr ((MODE == MODE_ABSORB_FLAT || MODE == MODE_GENERAL_FLAT) && VR_PQ_WALLS_FIRST) {
-          if (active && !(p.debugFlags & 65536u)) { // (flag 65536: off, for comparison)
+          if (active && !wallFree && !(p.debugFlags & 65536u)) { // (flag 65536: off, for comparison)
             HitRec hw;
             hit_clear(hw);
             if constexpr (FRAME_LDS)
@@ -602,7 +619,7 @@ trace_kernel(const TraceParams p) {
           }
         }
         // ---- packet query: the call and its back-off ----
-        packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE, LEAN, UNIFORM, PLANAR>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
+        packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE, LEAN, UNIFORM, PLANAR, PLANAR_ROUND>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
         pqCredit = PQ_CREDIT && packetDone;
         pqFails = packetDone ? 0u : (pqFails < 6u ? pqFails + 1u : 6u);
         pqSkip = packetDone ? 0u : (1u << pqFails) - 1u;
@@ -664,7 +681,7 @@ trace_kernel(const TraceParams p) {
 #endif
     TICK(3);
     // ---- walls of the finished segments ----
-    if (fin) { // boundary walls, where one can come before the hit
+    if (fin && !(PLANAR_ROUND && wallFree && h.geom >= 0)) { // boundary walls, where one can come before the hit
       if constexpr (FRAME_LDS)
         hit_walls_lds(p, wallS, org, dir, tnear, h);
       else

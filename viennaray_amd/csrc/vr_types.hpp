@@ -311,9 +311,13 @@ enum TraceMode : int {
                            // (ParticleLaunch::uniformDisks; 3-D disks only): the per-ray terms of the candidate tests once
                            // per round (pq_hit_packet UNIFORM).  A kernel of the library's table, never a launch's
                            // traceMode: that stays MODE_ABSORB_FLAT (ParticleLaunch::kernel_mode)
-  MODE_ABSORB_FLAT_PLANAR = 9 // ... whose disks also share a plane normal to a coordinate axis (ParticleLaunch::planarDisks):
+  MODE_ABSORB_FLAT_PLANAR = 9, // ... whose disks also share a plane normal to a coordinate axis (ParticleLaunch::planarDisks):
                            // one plane hit per ray and round, a distance per candidate (pq_hit_packet PLANAR).  Like
                            // MODE_ABSORB_FLAT_UNIFORM a kernel of the table, never a launch's traceMode
+  MODE_ABSORB_FLAT_PLANAR_ROUND = 10 // ... with that plane hit as the round's one point (ParticleLaunch::planarRound): both
+                           // candidate tests from it, the query's box around it, no wall test in a round whose rays
+                           // start and land well inside the walls (pq_hit_packet ROUND, vr_planar_disks.hpp).  Likewise
+                           // a kernel of the table alone
 };
 // (MODE_GENERAL_FLAT, MODE_GENERAL_RELIEF and MODE_RESUME exist for disks and the lean particles only: otherwise MODE_GENERAL)
 
