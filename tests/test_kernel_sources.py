@@ -60,9 +60,9 @@ def test_models_cpp_has_no_source_list_of_its_own():
 
 
 @pytest.mark.parametrize("define", [None, "-DVR_DIAG"])
-@pytest.mark.parametrize("header", ROLE_HEADERS + ["vr_device.hpp"])
+@pytest.mark.parametrize("header", ROLE_HEADERS + ["vr_device.hpp", "vr_kernel_table.hpp"])
 def test_device_header_stands_alone(header, define, tmp_path):
-    """each role header, and the umbrella, compiles as the only include of an otherwise empty .hip file"""
+    """each role header, the umbrella, and the kernel table's header compiles as the only include of an otherwise empty .hip file"""
     assert os.path.isfile(HIPCC), "hipcc is needed: " + HIPCC
     unit = tmp_path / "only.hip"
     unit.write_text('#include "%s"\n' % header)

@@ -85,7 +85,7 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
     // (a round that straddles two spans mixes rays of two places: its packet query gives up — every failed query of a flat
     //  plane is one of these, 4.9 % of the rounds at 32 bins, 2 % at 64 — which costs the absorbing kernel nothing
     //  measurable but the general flat-scene kernels 3 % (their failed round also loses its follow-up segments))
-    uint64_t spanBins = L.traceMode == MODE_GENERAL ? 16 : ((L.traceMode == MODE_GENERAL_FLAT || L.traceMode == MODE_GENERAL_RELIEF) ? 64 : 32);
+    uint64_t spanBins = (uint64_t)mode_traits(L.traceMode).spanBins; // (16 general, 64 general flat-scene kernels, 32 the others)
     if (K.spanBins)
       spanBins = *K.spanBins;
     const uint64_t binsToDeal = unbinned ? ((uint64_t)count + p.binCap - 1) / p.binCap : nbBatch;
@@ -96,7 +96,7 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   // 0.1 15.62 -> 15.16 ms, C2 1.0 6.67 -> 6.62, plane 100^2 +-0; L2 hit rate of the C2 launch 74 -> 84 %, fabric reads
   // 9.0 -> 5.2 GB).  A structured scene is L2 resident anyway and its bins differ in cost — an eighth of the trench is
   // not an eighth of the work: trench3D +3 %, C5 +6 %: one queue.
-  const bool flat = L.traceMode == MODE_GENERAL_FLAT; // (the absorbing kernels have the single queue compiled in)
+  const bool flat = mode_traits(L.traceMode).xcdQueues; // (MODE_GENERAL_FLAT alone; the absorbing kernels have the single queue compiled in)
   p.numQueues = (flat && c->geo.numPrims > (1u << 17) && p.numBins >= 64u * VR_QUEUES * p.chunk) ? VR_QUEUES : 1u;
   if (K.numQueues)
     p.numQueues = *K.numQueues;
@@ -147,7 +147,7 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
     if (tight && L.userKernel) {
       TraceParams pk = p;
       void *args[] = {&pk};
-      VR_HIP(c, hipModuleLaunchKernel(L.userKernel, gridBatch, 1, 1, VR_BLOCK, 1, 1, L.traceMode == MODE_SMALL ? p.smallBytes : 0, c->stream,
+      VR_HIP(c, hipModuleLaunchKernel(L.userKernel, gridBatch, 1, 1, VR_BLOCK, 1, 1, trace_dynamic_lds(L.traceMode, p.smallBytes), c->stream,
                                       args, nullptr));
     } else if (tight) {
       VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.kernel_mode(), gridBatch, c->stream));

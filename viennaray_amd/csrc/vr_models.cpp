@@ -232,13 +232,14 @@ static int build_particle_module(vr_context *c, const char *source, int numData,
                            hsaco);
 }
 
-// the trace kernels of a loaded particle module, by their mangled names (key: D * 100 + geo * 10 + mode)
+// the trace kernels of a loaded particle module — the catalogue's KERNELS_MODULE set (vr_types.hpp) under the module's
+// particle id — by their mangled names (key: D * 100 + geo * 10 + mode)
 static int find_trace_kernels(vr_context *c, hipModule_t module, bool full, bool stats, std::map<int, hipFunction_t> &kernels) {
   const int P = stats ? (full ? (int)P_EXT_FULL_STATS : (int)P_EXT_STATS) : (full ? (int)P_EXT_FULL : (int)P_EXT);
   for (int D = 2; D <= 3; ++D)
     for (int geo = 0; geo <= 1; ++geo)
-      for (int mode : {MODE_GENERAL, MODE_GENERAL_FLAT, MODE_SMALL}) {
-        if (mode == MODE_GENERAL_FLAT && (geo != 0 || full))
+      for (int mode = 0; mode < VR_NUM_MODES; ++mode) {
+        if (!trace_kernel_exists(KERNELS_MODULE, D, geo, P, mode))
           continue;
         char sym[128];
         std::snprintf(sym, sizeof(sym), "_ZN2vr12trace_kernelILi%dELi%dELi%dELi%dEEEvNS_11TraceParamsE", D, geo, P, mode);

@@ -7,7 +7,7 @@
 #pragma once
 #include "vr_generate.hpp"
 #ifndef VR_USER_SOURCE_MODULE
-#include "vr_trace_kernel.hpp"
+#include "vr_kernel_table.hpp"
 #endif
 
 namespace vr {
@@ -119,14 +119,10 @@ extern "C" __device__ __attribute__((used)) const int vr_user_log_rows = VrUserM
 #define VR_USER_FLUX_STATS 0
 #endif
 static_assert(!VR_USER_FLUX_STATS || VrUserModel::kNumData <= VR_MAX_LABELS - VR_STAT_PLANES, "flux statistics take two of a particle's planes");
+// the module's one particle id, and its trace kernels: what the catalogue (trace_kernel_exists, vr_types.hpp) lists for
+// KERNELS_MODULE under that id — the table is what instantiates them (vr_models.cpp, find_trace_kernels, asks the same predicate)
 constexpr int VR_USER_P = VR_USER_FLUX_STATS ? (VrUserModel::kNeedsFull ? P_EXT_FULL_STATS : P_EXT_STATS) : (VrUserModel::kNeedsFull ? P_EXT_FULL : P_EXT);
-constexpr int VR_USER_P_LEAN = VR_USER_FLUX_STATS ? P_EXT_STATS : P_EXT;
-#define VR_INST(DD, GG, MM) template __global__ void trace_kernel<DD, GG, VR_USER_P, MM>(const TraceParams);
-VR_INST(2, 0, 0) VR_INST(2, 0, 4) VR_INST(2, 1, 0) VR_INST(2, 1, 4)
-VR_INST(3, 0, 0) VR_INST(3, 0, 4) VR_INST(3, 1, 0) VR_INST(3, 1, 4)
-#undef VR_INST
-template __global__ void trace_kernel<2, 0, VR_USER_P_LEAN, VrUserModel::kNeedsFull ? 0 : 3>(const TraceParams);
-template __global__ void trace_kernel<3, 0, VR_USER_P_LEAN, VrUserModel::kNeedsFull ? 0 : 3>(const TraceParams);
+template struct TraceKernelTable<VR_USER_P, VR_USER_P>;
 
 // The generator of a STATEFUL model (SourceRandom, plain or with a primary direction): the model's init (initNew,
 // rayTraceKernel.hpp:131-133) draws first, then the source sample from the same engine (the streaming generator of

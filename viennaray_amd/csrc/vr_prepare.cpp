@@ -425,7 +425,8 @@ static int build_relief_field(vr_context *c, const ParticleSpec &sp, ParticleLau
   L.relief = false;
   const float thickScene = c->sceneHi[c->ts[0]] - c->sceneLo[c->ts[0]];
   const bool plainSource = c->src.is_plain(c->usePrimaryDirection);
-  const bool kernelOk = L.absorb || (c->geo.geo == 0 && L.kernelParticle <= (int)P_EXT);
+  const int tightMode = L.absorb ? MODE_ABSORB_RELIEF : MODE_GENERAL_RELIEF; // (the catalogue has MODE_RESUME where it has the latter)
+  const bool kernelOk = trace_kernel_exists(KERNELS_LIBRARY, D, c->geo.geo, trace_kernel_particle(L.kernelParticle, tightMode), tightMode);
   const bool want = !S.flatScene && !S.smallScene && plainSource && kernelOk && sp.userModel < 0 && c->geo.gridDelta > 0.f &&
                     thickScene <= K.reliefMaxThick * c->geo.gridDelta && !K.noRelief;
   if (want) {
@@ -593,8 +594,10 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   // grazing rays of a wave stretch its query over dozens of primitives (a 10^6-disk plane with ONE 50 x 50 bump of
   // 0.3 cells: the absorbing kernel 6.4 -> 8.3 ms, the general one 11 -> 18; the kernels for structured scenes are
   // then 2 - 6 % ahead of the flat ones.  DESIGN.md section 10: a flat layer + relief decomposition would close this)
-  // (with flux statistics the lean extended kernel has MODE_GENERAL_FLAT too, but no relief modes: vr_trace_stats.hip)
-  const bool generalFlatOk = !L.absorb && c->geo.geo == 0 && (L.kernelParticle <= (int)P_EXT || L.kernelParticle == (int)P_EXT_STATS);
+  // (with flux statistics the lean extended kernel has MODE_GENERAL_FLAT too, but no relief modes: the catalogue,
+  //  trace_kernel_exists, vr_types.hpp — what prepare may ask for is what it lists)
+  const KernelSet set = sp.userModel >= 0 ? KERNELS_MODULE : KERNELS_LIBRARY;
+  const bool generalFlatOk = !L.absorb && trace_kernel_exists(set, D, c->geo.geo, L.kernelParticle, MODE_GENERAL_FLAT);
   L.traceMode = !L.absorb ? ((S.flatScene && generalFlatOk) ? MODE_GENERAL_FLAT : MODE_GENERAL) : (S.flatScene ? MODE_ABSORB_FLAT : MODE_ABSORB);
   L.looseMode = L.traceMode;
   if (L.relief) { // flat with relief: the flat-scene kernels on the tight bins, the structured-scene ones on the loose
@@ -614,7 +617,8 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   }
   // one normal and one radius for the whole cloud (build_scene: vr_context::uniformDisks): the library's 3-D absorbing
   // flat-scene kernel in its uniform-disk variant (a run-time model's code object has no such kernel)
-  L.uniformDisks = K.uniformDisks && c->uniformDisks && L.traceMode == MODE_ABSORB_FLAT && D == 3 && c->geo.geo == 0 && sp.userModel < 0;
+  L.uniformDisks = K.uniformDisks && c->uniformDisks && L.traceMode == MODE_ABSORB_FLAT &&
+                   trace_kernel_exists(set, D, c->geo.geo, trace_kernel_particle(L.kernelParticle, MODE_ABSORB_FLAT_UNIFORM), MODE_ABSORB_FLAT_UNIFORM);
   // ... in its planar variant where the disks also share a plane normal to a coordinate axis (vr_context::planarDisks)
   L.planarDisks = L.uniformDisks && K.planarDisks && c->planarDisks;
   // ... and that one in its one-point-per-round form (vr_planar_disks.hpp (1) - (3))
@@ -626,19 +630,21 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
     UserModel &um = c->userModels[sp.userModel];
     if (L.stats) // (the module's twin with the statistics compiled in: built on first use)
       VR_TRY(ensure_stats_module(c, um));
-    if (S.stateful && (L.absorb || (L.traceMode != MODE_GENERAL && L.traceMode != MODE_SMALL)))
-      return fail(c, VR_E_STATE, "stateful particle model: only the general kernels (MODE 0 / 4) carry the state");
-    L.userGen = S.stateful ? um.gen[D == 3 ? 1 : 0] : nullptr;
-    const std::map<int, hipFunction_t> &kernels = L.stats ? um.statsKernels : um.kernels;
+    const std::map<int, hipFunction_t> &kernels = L.stats ? um.statsKernels : um.kernels; // (find_trace_kernels: the same predicate)
     auto it = kernels.find(D * 100 + c->geo.geo * 10 + L.traceMode);
-    if (it == kernels.end())
-      return fail(c, VR_E_STATE, "run-time particle model: no kernel for this geometry / mode in its code object");
+    if (!trace_kernel_exists(set, D, c->geo.geo, L.kernelParticle, L.traceMode) || it == kernels.end())
+      return fail(c, VR_E_STATE, S.stateful ? "stateful particle model: only the general kernels (MODE 0 / 4) carry the state"
+                                            : "run-time particle model: no kernel for this geometry / mode in its code object");
+    L.userGen = S.stateful ? um.gen[D == 3 ? 1 : 0] : nullptr;
     L.userKernel = it->second;
     int nb = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, L.userKernel, VR_BLOCK, L.traceMode == MODE_SMALL ? L.params.smallBytes : 0) != hipSuccess)
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, L.userKernel, VR_BLOCK, trace_dynamic_lds(L.traceMode, L.params.smallBytes)) != hipSuccess)
       nb = 2;
     blocks = std::max(1, nb);
   } else {
+    for (int m : {L.kernel_mode(), L.relief ? L.looseMode : L.kernel_mode()}) // (launch_trace would refuse it: said here, by name)
+      if (!trace_kernel_exists(set, D, c->geo.geo, trace_kernel_particle(L.kernelParticle, m), m))
+        return fail(c, VR_E_STATE, ("no trace kernel for this geometry / particle in MODE " + std::to_string(m)).c_str());
     blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.kernel_mode(), L.params.smallBytes));
   }
   // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on

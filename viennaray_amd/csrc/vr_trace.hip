@@ -26,9 +26,10 @@
 //   vr_trace_kernel.hpp  the trace kernel, its helpers and its tuning knobs (the modes: enum TraceMode, vr_types.hpp)
 //   vr_modules.hpp       the two run-time module sections: a source model's generator; a particle model's trace kernels
 //                        and stateful generator
-//   vr_trace.hip         this file: the library's tables of kernels and their launchers, or — compiled as a run-time
-//                        module (VR_USER_MODULE, vr_models.cpp) — the module section
-//   vr_trace_stats.hip   the library's trace kernels with flux statistics compiled in, a table and launchers of their own
+//   vr_kernel_table.hpp  the catalogue's trace kernels (trace_kernel_exists, vr_types.hpp) as a table: lookup, launcher, occupancy
+//   vr_trace.hip         this file: the library's generators and its statistics-off trace kernels, or — compiled as a
+//                        run-time module (VR_USER_MODULE, vr_models.cpp) — the module section
+//   vr_trace_stats.hip   the library's trace kernels with flux statistics compiled in: the same table over their two ids
 //   vr_diag.hip          the diagnostic kernels of the vr_debug_* entry points
 //   vr_bvh.hip           scene build: LBVH, 64-ary box tree, neighbourhood CSR, bvh_check
 //   vr_sort.hip          the radix sort of the build and the exclusive scan
@@ -44,16 +45,13 @@
 #include "vr_modules.hpp"
 #else
 #include "vr_generate.hpp"
-#include "vr_kernels.hpp"
-#include "vr_trace_kernel.hpp"
+#include "vr_kernel_table.hpp"
 
 namespace vr {
 
 // ---------------------------------------------------------------------------
 // host-callable launchers
 // ---------------------------------------------------------------------------
-// every generator and every trace kernel of the library: a kernel over the launch's TraceParams
-using StreamKernel = void (*)(const TraceParams);
 
 // source: one of the library's five generators (enum Generator, vr_types.hpp)
 static StreamKernel gen_kernel_for(Generator source, int D, bool keepRng, bool relief) {
@@ -83,76 +81,21 @@ hipError_t launch_gen(const TraceParams &p, Generator gen, int D, bool keepRng, 
   return hipGetLastError();
 }
 
-// The trace kernel of a launch.
-// mode: a TraceMode (vr_types.hpp); MODE_GENERAL_FLAT, MODE_GENERAL_RELIEF and MODE_RESUME exist for disks and the lean
-// particles only: otherwise MODE_GENERAL
-// particle: 0 DiffuseParticle, 1 SpecularParticle, 2 (P_EXT) extended kernel, 3 (P_EXT_FULL) ... with the coned-cosine
-// model, WDIST crediting and mean-free-path scattering (always MODE_GENERAL or MODE_SMALL)
-template <int D, int GEO, int PARTICLE> static StreamKernel trace_kernel_of(int mode) {
-  constexpr bool FLAT = GEO == 0 && PARTICLE <= P_EXT; // (the flat-scene general kernels exist)
-  switch (mode) {
-  case MODE_ABSORB_FLAT: return trace_kernel<D, GEO, 0, MODE_ABSORB_FLAT>;
-  case MODE_ABSORB_FLAT_UNIFORM: // (3-D disks only: vr_prepare.cpp asks for it nowhere else)
-    if constexpr (D == 3 && GEO == 0)
-      return trace_kernel<3, 0, 0, MODE_ABSORB_FLAT_UNIFORM>;
-    return trace_kernel<D, GEO, 0, MODE_ABSORB_FLAT>;
-  case MODE_ABSORB_FLAT_PLANAR: // (likewise)
-    if constexpr (D == 3 && GEO == 0)
-      return trace_kernel<3, 0, 0, MODE_ABSORB_FLAT_PLANAR>;
-    return trace_kernel<D, GEO, 0, MODE_ABSORB_FLAT>;
-  case MODE_ABSORB_FLAT_PLANAR_ROUND: // (likewise)
-    if constexpr (D == 3 && GEO == 0)
-      return trace_kernel<3, 0, 0, MODE_ABSORB_FLAT_PLANAR_ROUND>;
-    return trace_kernel<D, GEO, 0, MODE_ABSORB_FLAT>;
-  case MODE_ABSORB:return trace_kernel<D, GEO, 0, MODE_ABSORB>;
-  case MODE_GENERAL_FLAT:
-    if constexpr (FLAT)
-      return trace_kernel<D, 0, PARTICLE, MODE_GENERAL_FLAT>;
-    break;
-  case MODE_SMALL: return trace_kernel<D, GEO, PARTICLE, MODE_SMALL>;
-  case MODE_ABSORB_RELIEF: return trace_kernel<D, GEO, 0, MODE_ABSORB_RELIEF>;
-  case MODE_GENERAL_RELIEF:
-    if constexpr (FLAT)
-      return trace_kernel<D, 0, PARTICLE, MODE_GENERAL_RELIEF>;
-    break;
-  case MODE_RESUME:
-    if constexpr (FLAT)
-      return trace_kernel<D, 0, PARTICLE, MODE_RESUME>;
-    break;
-  }
-  return trace_kernel<D, GEO, PARTICLE, MODE_GENERAL>;
-}
-static StreamKernel trace_kernel_for(int D, int geo, int particle, int mode) {
-  if (mode == MODE_ABSORB_FLAT || mode == MODE_ABSORB || mode == MODE_ABSORB_RELIEF || mode == MODE_ABSORB_FLAT_UNIFORM ||
-      mode == MODE_ABSORB_FLAT_PLANAR || mode == MODE_ABSORB_FLAT_PLANAR_ROUND)
-    particle = 0; // the reflection model is unobservable: one instantiation serves all
-#define VR_VARIANT(K, DD, GG, PP)                                                                                      \
-  case K: return trace_kernel_of<DD, GG, PP>(mode);
-  switch ((D == 2 ? 0 : 8) + (geo ? 4 : 0) + particle) {
-    VR_VARIANT(0, 2, 0, 0) VR_VARIANT(1, 2, 0, 1) VR_VARIANT(2, 2, 0, 2) VR_VARIANT(3, 2, 0, 3)
-    VR_VARIANT(4, 2, 1, 0) VR_VARIANT(5, 2, 1, 1) VR_VARIANT(6, 2, 1, 2) VR_VARIANT(7, 2, 1, 3)
-    VR_VARIANT(8, 3, 0, 0) VR_VARIANT(9, 3, 0, 1) VR_VARIANT(10, 3, 0, 2) VR_VARIANT(11, 3, 0, 3)
-    VR_VARIANT(12, 3, 1, 0) VR_VARIANT(13, 3, 1, 1) VR_VARIANT(14, 3, 1, 2)
-  default: return trace_kernel_of<3, 1, 3>(mode);
-  }
-#undef VR_VARIANT
-}
+// The trace kernel of a launch: the statistics-off particle ids of the catalogue (0 DiffuseParticle, 1 SpecularParticle,
+// P_EXT, P_EXT_FULL; the two statistics ids: vr_trace_stats.hip's table).  mode: a TraceMode
+using LibraryKernels = TraceKernelTable<0, P_EXT_FULL>;
 
 hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid,
                         hipStream_t s) {
-  if (particle >= P_EXT_STATS) // (flux statistics: the kernels of vr_trace_stats.hip; this table is the statistics-off one)
+  if (particle >= P_EXT_STATS)
     return launch_trace_stats(p, D, geo, particle, mode, grid, s);
-  hipLaunchKernelGGL(trace_kernel_for(D, geo, particle, mode), dim3(grid), dim3(VR_BLOCK), mode == MODE_SMALL ? p.smallBytes : 0, s, p);
-  return hipGetLastError();
+  return LibraryKernels::launch(p, D, geo, particle, mode, grid, s);
 }
 
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes) {
   if (particle >= P_EXT_STATS)
     return trace_stats_blocks_per_cu(D, geo, particle, mode, smallBytes);
-  int nb = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel_for(D, geo, particle, mode), VR_BLOCK,
-                                                                    mode == MODE_SMALL ? smallBytes : 0);
-  return e == hipSuccess ? nb : 2;
+  return LibraryKernels::blocks_per_cu(D, geo, particle, mode, smallBytes);
 }
 
 } // namespace vr

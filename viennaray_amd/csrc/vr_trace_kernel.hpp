@@ -148,19 +148,13 @@ __device__ __forceinline__ bool rises_clear(const float *__restrict__ wallS, con
 // The modes (template parameter MODE_): enum TraceMode, vr_types.hpp.
 // (SGPR budget: 256-thread blocks per CU = min(8, 800 / (ceil(sgpr/16)*16 + 16)) on gfx950,
 //  MI355X_MICROARCH.md; 80 keeps 8 blocks resident)
-// The tuning knobs:
-#ifndef VR_GENERAL_WAVES
-#define VR_GENERAL_WAVES 6 // waves per SIMD of the general kernel (MODE_GENERAL)
-#endif
+// The tuning knobs (the waves per SIMD of each mode: VR_*_WAVES next to mode_traits, vr_types.hpp):
 #ifndef VR_FLAT_ORDERED
 #define VR_FLAT_ORDERED 0  // MODE_GENERAL_FLAT walks like MODE_ABSORB_FLAT: the escape-link walk, no carry-over (1: the ordered pair walk).  It runs
                            // only on scenes whose box is thin (vr_prepare.cpp: flatScene), where a wave walks in the 5 % of its
                            // rounds whose query gives up; without the walk's 12 KB of LDS stack and ~10 VGPRs the kernel
                            // takes 6 waves per SIMD: C2 0.1 10.9 -> 10.0 ms.  (Forced onto a scene with relief
                            // — VR_GENERAL_FLAT=1 — it is 15 - 30 % slower than with the ordered walk at 5 waves.)
-#endif
-#ifndef VR_SMALL_WAVES
-#define VR_SMALL_WAVES 5   // ... of the LDS-resident kernel (MODE_SMALL; 6: C5 20.15 -> 21.9 ms)
 #endif
 #ifndef VR_PQ_CACHE
 #define VR_PQ_CACHE 1      // flat-scene kernels: the packet query's frontier serves the neighbouring rounds (pq_hit_packet CACHE)
@@ -171,37 +165,36 @@ __device__ __forceinline__ bool rises_clear(const float *__restrict__ wallS, con
 #ifndef VR_PQ_CACHE_RELIEF
 #define VR_PQ_CACHE_RELIEF 1 // ... in the relief kernels MODE_ABSORB_RELIEF / MODE_GENERAL_RELIEF too
 #endif
-#ifndef VR_FLAT_WAVES
-#define VR_FLAT_WAVES 6    // ... of the general flat-scene kernel (MODE_GENERAL_FLAT)
-#endif
-#ifndef VR_RELIEF_WAVES
-#define VR_RELIEF_WAVES 8  // waves per SIMD of the absorbing relief kernel (MODE_ABSORB_RELIEF)
-#endif
 constexpr unsigned VR_SPILL_BLOCK = 64u; // records of the spill queue a wave reserves at a time (TraceParams::spillRec)
 // the unused records [used, VR_SPILL_BLOCK) of a wave's block marked empty (word 11 = ~0: no ray)
 __device__ __forceinline__ void spill_pad(const TraceParams &p, unsigned base, unsigned used, unsigned lane) {
   if (used < VR_SPILL_BLOCK && lane >= used)
     reinterpret_cast<float4 *>(p.spillRec)[4 * (size_t)(base + lane) + 2] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xFFFFFFFFu));
 }
-constexpr int vr_mode_waves(int m) {
-  return m == MODE_ABSORB_RELIEF ? VR_RELIEF_WAVES : (m == MODE_ABSORB_FLAT || m == MODE_ABSORB_FLAT_UNIFORM || m == MODE_ABSORB_FLAT_PLANAR || m == MODE_ABSORB_FLAT_PLANAR_ROUND) ? 8 : (m == MODE_ABSORB ? 7 : ((m == MODE_GENERAL_FLAT || m == MODE_GENERAL_RELIEF) ? VR_FLAT_WAVES : (m == MODE_SMALL ? VR_SMALL_WAVES : VR_GENERAL_WAVES)));
-}
+// the catalogue's set this translation unit instantiates from (trace_kernel_exists, vr_types.hpp)
+#ifdef VR_USER_MODULE
+constexpr KernelSet VR_KERNEL_SET = KERNELS_MODULE;
+#else
+constexpr KernelSet VR_KERNEL_SET = KERNELS_LIBRARY;
+#endif
 template <int D, int GEO, int PARTICLE, int MODE_>
 __global__ __launch_bounds__(VR_BLOCK) __attribute__((amdgpu_num_sgpr(80)))
-__attribute__((amdgpu_waves_per_eu(vr_mode_waves(MODE_), vr_mode_waves(MODE_)))) void
+__attribute__((amdgpu_waves_per_eu(mode_traits(MODE_).waves, mode_traits(MODE_).waves))) void
 trace_kernel(const TraceParams p) {
-  constexpr bool SMALL = MODE_ == MODE_SMALL;
-  constexpr bool RELIEF = MODE_ == MODE_ABSORB_RELIEF || MODE_ == MODE_GENERAL_RELIEF;
-  constexpr bool RESUME = MODE_ == MODE_RESUME;
-  constexpr bool PLANAR_ROUND = MODE_ == MODE_ABSORB_FLAT_PLANAR_ROUND; // (... with the plane hit as the round's one point: pq_hit_packet ROUND, wall-free rounds)
-  constexpr bool PLANAR = MODE_ == MODE_ABSORB_FLAT_PLANAR || PLANAR_ROUND; // (... with its PLANAR candidate tests, which are UNIFORM ones)
-  constexpr bool UNIFORM = MODE_ == MODE_ABSORB_FLAT_UNIFORM || PLANAR; // (MODE_ABSORB_FLAT with pq_hit_packet's UNIFORM candidate tests)
-  constexpr int MODE = (SMALL || RESUME) ? MODE_GENERAL : ((MODE_ == MODE_ABSORB_RELIEF || UNIFORM) ? MODE_ABSORB_FLAT : (MODE_ == MODE_GENERAL_RELIEF ? MODE_GENERAL_FLAT : MODE_));
+  constexpr ModeTraits T = mode_traits(MODE_); // (what the mode is: vr_types.hpp)
+  constexpr bool SMALL = T.small;
+  constexpr bool RELIEF = T.relief;
+  constexpr bool RESUME = T.resume;
+  constexpr bool PLANAR_ROUND = T.planarRound; // (... with the plane hit as the round's one point: pq_hit_packet ROUND, wall-free rounds)
+  constexpr bool PLANAR = T.planar; // (... with its PLANAR candidate tests, which are UNIFORM ones)
+  constexpr bool UNIFORM = T.uniform; // (MODE_ABSORB_FLAT with pq_hit_packet's UNIFORM candidate tests)
+  constexpr int MODE = T.base;
   constexpr bool FRAME_LDS = MODE == MODE_ABSORB_FLAT; // (the wall / scene-box frame from LDS: hit_walls_lds, vr_intersect.hpp)
   // (the scalar diet of the absorbing flat-scene kernel — branch-free candidate tests, lane-parallel crediting — in three
   //  dimensions only: the 2-D instantiations answered it with vector spills, DESIGN_APPENDIX A)
   constexpr bool LEAN = MODE == MODE_ABSORB_FLAT && D == 3 && GEO == 0 && PARTICLE < P_EXT;
-  static_assert(!UNIFORM || LEAN, "MODE_ABSORB_FLAT_UNIFORM: 3-D disks, the library's absorbing particle");
+  static_assert(trace_kernel_exists(VR_KERNEL_SET, D, GEO, PARTICLE, MODE_), "not a kernel of the catalogue (trace_kernel_exists, vr_types.hpp)");
+  static_assert(!UNIFORM || LEAN, "the uniform-disk variants are written for the LEAN kernel");
   constexpr bool FOLLOW = MODE == MODE_GENERAL_FLAT;    // (follow-up segments inside the round of a packet query: end of the round)
   constexpr bool ABSORB = MODE == MODE_ABSORB_FLAT || MODE == MODE_ABSORB;
   // PARTICLE 0 / 1: DiffuseParticle / SpecularParticle compiled in.  PARTICLE 2 (P_EXT): the

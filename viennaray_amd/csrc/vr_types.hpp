@@ -291,7 +291,8 @@ enum { P_DIFFUSE = 0, P_SPECULAR = 1, P_CONED_COSINE = 2, P_DIFFUSE_COSINE = 3, 
 constexpr int VR_STAT_PLANES = 2; // companion planes of a particle, behind its data labels: [numData] sum of squares, [numData + 1] hits
 
 // The modes of trace_kernel (its template parameter MODE_, an int: a module's kernels are found by mangled name;
-// vr_get_trace_mode reports these numbers).  vr_prepare.cpp chooses one per launch, vr_trace.hip maps it to a kernel.
+// vr_get_trace_mode reports these numbers).  vr_prepare.cpp chooses one per launch; what a mode means to the kernel and
+// to the host is mode_traits below, which kernels exist trace_kernel_exists.
 enum TraceMode : int {
   MODE_GENERAL = 0,        // the general kernel: any scene, any particle; per-lane ordered walks with straggler carry-over
   MODE_ABSORB_FLAT = 1,    // absorbing particle (sticking >= 1 everywhere), flat scene: the packet query carries the load
@@ -319,7 +320,97 @@ enum TraceMode : int {
                            // start and land well inside the walls (pq_hit_packet ROUND, vr_planar_disks.hpp).  Likewise
                            // a kernel of the table alone
 };
-// (MODE_GENERAL_FLAT, MODE_GENERAL_RELIEF and MODE_RESUME exist for disks and the lean particles only: otherwise MODE_GENERAL)
+constexpr int VR_NUM_MODES = MODE_ABSORB_FLAT_PLANAR_ROUND + 1;
+
+// Waves per SIMD of the trace kernels (tuning knobs: a -DVR_..._WAVES=n build overrides one)
+#ifndef VR_GENERAL_WAVES
+#define VR_GENERAL_WAVES 6 // waves per SIMD of the general kernel (MODE_GENERAL)
+#endif
+#ifndef VR_SMALL_WAVES
+#define VR_SMALL_WAVES 5   // ... of the LDS-resident kernel (MODE_SMALL; 6: C5 20.15 -> 21.9 ms)
+#endif
+#ifndef VR_FLAT_WAVES
+#define VR_FLAT_WAVES 6    // ... of the general flat-scene kernel (MODE_GENERAL_FLAT)
+#endif
+#ifndef VR_RELIEF_WAVES
+#define VR_RELIEF_WAVES 8  // waves per SIMD of the absorbing relief kernel (MODE_ABSORB_RELIEF)
+#endif
+
+// What a mode IS: the one place the kernel (vr_trace_kernel.hpp) and the host (vr_prepare.cpp, vr_apply.cpp) read it from.
+struct ModeTraits {
+  // the kernel's view: the base mode (one of MODE_GENERAL .. MODE_GENERAL_FLAT: the round structure) and what is added to it
+  int base = -1; // (-1: not a TraceMode)
+  bool small = false, relief = false, resume = false;
+  bool uniform = false, planar = false, planarRound = false; // pq_hit_packet UNIFORM / PLANAR / ROUND: each implies the one before
+  int waves = 0; // waves per SIMD (amdgpu_waves_per_eu)
+  // the host's view
+  bool absorbing = false;  // nothing after the first hit is observable: one instantiation, particle id 0, serves every particle
+  bool multiQueue = false; // the kernel reads TraceParams::numQueues (MULTIQ); every other kernel has the single queue compiled in
+  bool xcdQueues = false;  // ... and a launch of it gets one queue per XCD on a large scene (vr_apply.cpp, batch_params)
+  int spanBins = 0;        // sort bins per queue grab, before the batch's size caps it (batch_params says why they differ)
+  bool dynamicLds = false; // the launch passes TraceParams::smallBytes of dynamic LDS (the scene copy)
+};
+constexpr ModeTraits make_mode_traits(int mode, int base, int waves, int spanBins, int variant = 0, bool relief = false) {
+  ModeTraits t;
+  t.base = base;
+  t.small = mode == MODE_SMALL;
+  t.relief = relief;
+  t.resume = mode == MODE_RESUME;
+  t.uniform = variant >= 1, t.planar = variant >= 2, t.planarRound = variant >= 3;
+  t.waves = waves;
+  t.absorbing = base == MODE_ABSORB_FLAT || base == MODE_ABSORB;
+  t.multiQueue = base == MODE_GENERAL_FLAT;
+  t.xcdQueues = mode == MODE_GENERAL_FLAT; // (the relief kernel's tight bins: one queue)
+  t.spanBins = spanBins;
+  t.dynamicLds = t.small;
+  return t;
+}
+constexpr ModeTraits mode_traits(int mode) {
+  switch (mode) { //                                                mode, base mode,         waves,            span, variant, relief
+  case MODE_GENERAL:                  return make_mode_traits(mode, MODE_GENERAL,      VR_GENERAL_WAVES, 16);
+  case MODE_ABSORB_FLAT:              return make_mode_traits(mode, MODE_ABSORB_FLAT,  8,                32);
+  case MODE_ABSORB:                   return make_mode_traits(mode, MODE_ABSORB,       7,                32);
+  case MODE_GENERAL_FLAT:             return make_mode_traits(mode, MODE_GENERAL_FLAT, VR_FLAT_WAVES,    64);
+  case MODE_SMALL:                    return make_mode_traits(mode, MODE_GENERAL,      VR_SMALL_WAVES,   32);
+  case MODE_ABSORB_RELIEF:            return make_mode_traits(mode, MODE_ABSORB_FLAT,  VR_RELIEF_WAVES,  32, 0, true);
+  case MODE_GENERAL_RELIEF:           return make_mode_traits(mode, MODE_GENERAL_FLAT, VR_FLAT_WAVES,    64, 0, true);
+  case MODE_RESUME:                   return make_mode_traits(mode, MODE_GENERAL,      VR_GENERAL_WAVES, 32);
+  case MODE_ABSORB_FLAT_UNIFORM:      return make_mode_traits(mode, MODE_ABSORB_FLAT,  8,                32, 1);
+  case MODE_ABSORB_FLAT_PLANAR:       return make_mode_traits(mode, MODE_ABSORB_FLAT,  8,                32, 2);
+  case MODE_ABSORB_FLAT_PLANAR_ROUND: return make_mode_traits(mode, MODE_ABSORB_FLAT,  8,                32, 3);
+  }
+  return ModeTraits{};
+}
+// dynamic LDS of a launch of `mode`
+constexpr unsigned trace_dynamic_lds(int mode, unsigned smallBytes) { return mode_traits(mode).dynamicLds ? smallBytes : 0u; }
+
+// The catalogue: which trace_kernel<D, GEO, PARTICLE, MODE_> exist.  The library's two tables (vr_kernel_table.hpp: particle
+// ids 0 .. P_EXT_FULL in vr_trace.hip, the two statistics ids in vr_trace_stats.hip), a module's instantiations
+// (vr_modules.hpp), the search for a module's kernels (vr_models.cpp) and prepare's view of what it may ask for
+// (vr_prepare.cpp) all come from this predicate; a request it denies is an error, never another kernel.
+//   KERNELS_LIBRARY  particle ids 0 .. P_EXT_FULL_STATS
+//   KERNELS_MODULE   a run-time particle model's code object, which holds ONE extended id: P_EXT / P_EXT_FULL (lean /
+//                    kNeedsFull model), or their statistics twins in the module's statistics-on twin
+enum KernelSet : int { KERNELS_LIBRARY = 0, KERNELS_MODULE = 1 };
+// the particle id a request is served by: the reflection model of an absorbing launch is unobservable, id 0 serves all
+constexpr int trace_kernel_particle(int particle, int mode) { return mode_traits(mode).absorbing ? 0 : particle; }
+constexpr bool trace_kernel_exists(KernelSet set, int D, int geo, int particle, int mode) {
+  const ModeTraits t = mode_traits(mode);
+  if (D < 2 || D > 3 || geo < 0 || geo > 1 || particle < 0 || particle > P_EXT_FULL_STATS || t.base < 0)
+    return false;
+  if (set == KERNELS_MODULE && particle < P_EXT)
+    return false;
+  if (t.absorbing) // the library's, particle id 0 alone; the uniform-disk variants: 3-D disks (the kernel's LEAN)
+    return set == KERNELS_LIBRARY && particle == 0 && (!t.uniform || (D == 3 && geo == 0));
+  if (mode == MODE_GENERAL || mode == MODE_SMALL) // any geometry, any particle
+    return true;
+  // the general flat-scene kernels: disks, and not the instantiations with the rare options
+  if (geo != 0 || particle == P_EXT_FULL || particle == P_EXT_FULL_STATS)
+    return false;
+  if (mode == MODE_GENERAL_FLAT)
+    return true;
+  return set == KERNELS_LIBRARY && particle < P_EXT_STATS; // MODE_GENERAL_RELIEF, MODE_RESUME
+}
 
 // The generator of a launch.  vr_prepare.cpp records one per launch from the source in force (RaySource::generator,
 // vr_source.hpp); 0 - 4 are the library's own, in the order of vr_trace.hip's table (launch_gen takes one of these).
