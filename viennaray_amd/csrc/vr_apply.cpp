@@ -150,7 +150,10 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
       VR_HIP(c, hipModuleLaunchKernel(L.userKernel, gridBatch, 1, 1, VR_BLOCK, 1, 1, trace_dynamic_lds(L.traceMode, p.smallBytes), c->stream,
                                       args, nullptr));
     } else if (tight) {
-      VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.kernel_mode(), gridBatch, c->stream));
+      if (L.planarLattice) // (the lattice cloud's kernel: not a mode of the table)
+        VR_HIP(c, launch_trace_lattice(p, gridBatch, c->stream));
+      else
+        VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.kernel_mode(), gridBatch, c->stream));
     }
     VR_HIP(c, hipEventRecord(k1, c->stream));
     ++traceNo;
@@ -380,6 +383,9 @@ int vr_apply_finish(vr_context *c) {
       // (... and whether it was that kernel's one-point-per-round form)
       std::fprintf(stderr, "[vr] planar disks: round: VR_PLANAR_ROUND %d, launch %d, particle %zu\n", (int)c->knobs.planarRound,
                    (int)L.planarRound, q);
+      // (... and whether its candidates came from the lattice table)
+      std::fprintf(stderr, "[vr] planar disks: lattice: scene %d, VR_PLANAR_LATTICE %d, launch %d, particle %zu\n", (int)c->planarLattice,
+                   (int)c->knobs.planarLattice, (int)L.planarLattice, q);
     }
   const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
   if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)

@@ -119,6 +119,7 @@ struct Knobs {
   bool uniformDisks = true;            // VR_UNIFORM_DISKS (0: off): the absorbing flat-scene kernel's uniform-disk variants where the scene allows them
   bool planarDisks = true;             // VR_PLANAR_DISKS (0: off): ... the planar one of them (off: planar disks run the uniform-disk kernel)
   bool planarRound = true;             // VR_PLANAR_ROUND (0: off): ... in its one-point-per-round form (off: the planar kernel as it was)
+  bool planarLattice = true;           // VR_PLANAR_LATTICE (0: off): ... with its candidates from the lattice table where the cloud is a lattice cloud (off: the one-point-per-round kernel as it was)
   std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
   std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
   // kernel parameters (TraceParams)
@@ -205,6 +206,10 @@ struct ParticleLaunch {
   // ... with VR_PLANAR_ROUND on: that kernel's one-point-per-round form, its words in the frame as well (VR_F_PR_*).  Only
   // ever set with planarDisks
   bool planarRound = false;
+  // ... on a lattice cloud (vr_context::planarLattice) with VR_PLANAR_LATTICE on: that kernel with the round's candidates
+  // from the lattice table, the table's words in the frame as well (VR_F_PL_*).  Only ever set with planarRound.  Not a mode:
+  // the launch takes launch_trace_lattice in place of launch_trace(kernel_mode())
+  bool planarLattice = false;
   int kernel_mode() const { // the mode launch_trace takes
     if (planarRound)
       return (int)MODE_ABSORB_FLAT_PLANAR_ROUND;
@@ -409,6 +414,13 @@ struct vr_context {
   int planarAxis = 0;
   uint32_t planarWord = 0;
   DevBuf<uint32_t> dUniformDisks;          // launch_uniform_disks' VR_UNIFORM_WORDS words
+  // ... and a lattice cloud (vr_planar_lattice.hpp; build_scene, behind the BVH's leaf order): dLattice holds the table
+  // uint32[latticeN[1]][latticeN[0]] of leaf positions, and behind it launch_lattice_table's flag word.  The phases are the
+  // smallest centre coordinates along the plane's two in-plane axes, the pitch is the scene's gridDelta
+  bool planarLattice = false;
+  int latticeN[2] = {0, 0};
+  float latticePhase[2] = {0.f, 0.f};
+  DevBuf<uint32_t> dLattice;
   SetupParams lastSetup{};       // buffers of the resident device build (vr_debug_bvh_check)
   bool haveSetup = false;
   int builtOrderAxis = -1;       // child order of the resident BVH (source side first)

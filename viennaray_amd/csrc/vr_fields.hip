@@ -1,9 +1,11 @@
 // vr_fields.hip — the two fields over the source plane that every prepare builds from the resident primitive records:
 // the height field (HeightFieldParams) and the relief field (ReliefParams), both in vr_types.hpp; and the one per-scene
-// fact a geometry commit reads off those records: whether the disks are uniform (launch_uniform_disks).
+// fact a geometry commit reads off those records: whether the disks are uniform (launch_uniform_disks); and the lattice
+// table of a planar cloud (launch_lattice_table).
 #include <hip/hip_runtime.h>
 
 #include "vr_kernels.hpp"
+#include "vr_planar_lattice.hpp"
 #include "vr_setup_common.hpp"
 #include "vr_types.hpp"
 
@@ -211,6 +213,42 @@ hipError_t launch_uniform_disks(const float *prims, unsigned n, unsigned *out, h
     return e;
   const unsigned grid = (unsigned)((n + 255u) / 256u < 1024u ? (n + 255u) / 256u : 1024u);
   hipLaunchKernelGGL(uniform_disks_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint4 *>(prims), n, out);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// lattice table of a planar cloud (vr_planar_lattice.hpp): one pass over the packed records, in leaf order, validates and
+// fills.  Every disk claims the word of its lattice point with a compare-and-swap on the empty word; a centre off the
+// lattice (lattice_cell_of) raises bit 0 of the flag word, a second disk at one point bit 1.  Every index is formed by
+// lattice_cell_of, which hands out nothing outside n1 x n2.
+// ---------------------------------------------------------------------------
+__global__ void lattice_table_kernel(const float4 *__restrict__ recs, unsigned n, int b1, int b2, float phase1, float phase2,
+                                     float invDelta, int n1, int n2, unsigned *table, unsigned *flag) {
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float4 c = recs[2 * (size_t)i];
+    const float u = b1 == 0 ? c.x : c.y, v = b2 == 2 ? c.z : c.y; // (b1 < b2: planar_in_plane_axes)
+    int ci, cj;
+    const bool on1 = lattice_cell_of(u, phase1, invDelta, n1, ci), on2 = lattice_cell_of(v, phase2, invDelta, n2, cj);
+    if (!(on1 && on2))
+      atomicOr(flag, 1u);
+    else if (atomicCAS(&table[(size_t)cj * (size_t)n1 + (size_t)ci], VR_LATTICE_EMPTY, i) != VR_LATTICE_EMPTY)
+      atomicOr(flag, 2u);
+  }
+}
+
+hipError_t launch_lattice_table(const float *prims, unsigned n, int b1, int b2, float phase1, float phase2, float invDelta,
+                                int n1, int n2, unsigned *table, hipStream_t st) {
+  if (n1 < 1 || n2 < 1 || n == 0)
+    return hipErrorInvalidValue;
+  const size_t cells = (size_t)n1 * (size_t)n2;
+  hipError_t e = hipMemsetAsync(table, 0xFF, cells * 4, st); // (VR_LATTICE_EMPTY in every word)
+  if (e == hipSuccess)
+    e = hipMemsetAsync(table + cells, 0, 4, st);
+  if (e != hipSuccess)
+    return e;
+  const unsigned grid = (unsigned)((n + 255u) / 256u < 1024u ? (n + 255u) / 256u : 1024u);
+  hipLaunchKernelGGL(lattice_table_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float4 *>(prims), n, b1, b2,
+                     phase1, phase2, invDelta, n1, n2, table, table + cells);
   return hipGetLastError();
 }
 

@@ -38,6 +38,12 @@ enum { VR_F_SRC_PLANE = 96, VR_F_RAYDIR = 97, VR_F_FIRSTDIR = 98, VR_F_SECONDDIR
        // per-ray state of the batch (float4 per ray, indexed like TraceParams::recExtra) and the material id per ORIGINAL
        // primitive (0: none set).  (Here, not in TraceParams: the library's own kernels stay exactly as they are.)
        VR_F_STATE_LO = 136, VR_F_STATE_HI = 137, VR_F_MAT_LO = 138, VR_F_MAT_HI = 139,
+       // ... a planar-round launch on a lattice cloud (ParticleLaunch::planarLattice; read only by
+       // trace_kernel_lattice; vr_planar_lattice.hpp): the lattice table's address, its n1 x n2 points (ints),
+       // the lattice's phase along the two in-plane axes, 1 / delta and the window's reach.  Such a launch runs a kernel
+       // of the library on a built-in particle: it has neither a stateful model nor a data log, these are words of theirs
+       VR_F_PL_PTR_LO = VR_F_STATE_LO, VR_F_PL_PTR_HI = VR_F_STATE_HI, VR_F_PL_N1 = VR_F_MAT_LO, VR_F_PL_N2 = VR_F_MAT_HI,
+       VR_F_PL_PHASE1 = 140 /* VR_F_LOG_LO */, VR_F_PL_PHASE2 = 141, VR_F_PL_INVD = 142, VR_F_PL_REACH = 143,
        // the data log of a stateful model with a log_data hook (read only by gen_state_kernel of such a module; 0: no
        // shape set, nothing is logged): the int64 sums, rows concatenated, and the log's control words (VR_LOG_*)
        VR_F_LOG_LO = 140, VR_F_LOG_HI = 141, VR_F_LOGCTL_LO = 142, VR_F_LOGCTL_HI = 143 };

@@ -13,6 +13,9 @@ hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int 
                         hipStream_t s);
 // resident 256-thread blocks per CU of the trace kernel instantiation (occupancy API)
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes);
+// ... and the one-point-per-round kernel of a lattice cloud (trace_kernel_lattice, vr_trace.hip): 3-D disks, particle id 0
+hipError_t launch_trace_lattice(const TraceParams &p, unsigned grid, hipStream_t s);
+int trace_lattice_blocks_per_cu();
 // ... the kernels with flux statistics (vr_trace_stats.hip; particle: P_EXT_STATS / P_EXT_FULL_STATS); launch_trace and
 // trace_blocks_per_cu forward to them
 hipError_t launch_trace_stats(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid, hipStream_t s);
@@ -55,6 +58,11 @@ hipError_t launch_relief_field(const ReliefParams &q, hipStream_t st);
 // coordinate is not finite, out[9 .. 11] <- record 0's centre.  out: VR_UNIFORM_WORDS words
 constexpr unsigned VR_UNIFORM_WORDS = 12;
 hipError_t launch_uniform_disks(const float *prims, unsigned n, unsigned *out, hipStream_t st);
+// the lattice table of a planar cloud (vr_planar_lattice.hpp) from the packed disk records in leaf order: table[j * n1 + i]
+// <- the leaf position of the disk at lattice point (i, j) along the in-plane axes b1 < b2, VR_LATTICE_EMPTY where there is
+// none; table[n1 * n2] <- flags: bit 0 a centre is off the lattice, bit 1 two disks share a point.  table: n1 * n2 + 1 words
+hipError_t launch_lattice_table(const float *prims, unsigned n, int b1, int b2, float phase1, float phase2, float invDelta,
+                                int n1, int n2, unsigned *table, hipStream_t st);
 // device-resident inputs (vr_ingest.hip)
 hipError_t launch_disk4(const float *points3, unsigned n, float radius, int D, float *disk4, hipStream_t st);
 // device-resident disk geometry (vr_set_disks_device): the caller's DEVICE rows (ld = 2 or 3 floats) -> points3, normal3,

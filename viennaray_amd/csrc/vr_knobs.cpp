@@ -60,6 +60,8 @@ Knobs read_knobs() {
     k.planarDisks = std::atoi(e) != 0;
   if (const char *e = std::getenv("VR_PLANAR_ROUND"))
     k.planarRound = std::atoi(e) != 0;
+  if (const char *e = std::getenv("VR_PLANAR_LATTICE"))
+    k.planarLattice = std::atoi(e) != 0;
   if (const char *e = std::getenv("VR_SPAN_BINS"))
     k.spanBins = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
   if (const char *e = std::getenv("VR_QUEUES"))

@@ -1,6 +1,7 @@
 // vr_packet_query.hpp — the wave-uniform search by box (packet query) and the relief clip of its rays (gfx950).
 #pragma once
 #include "vr_planar_disks.hpp"
+#include "vr_planar_lattice.hpp"
 #include "vr_walk.hpp"
 namespace vr {
 
@@ -545,6 +546,132 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
     }
     VR_PQ_MARK(15); // (diag: the exact tests)
   }
+  return true;
+}
+
+// ---------------------------------------------------------------------------
+// The packet query of a LATTICE cloud (trace_kernel_lattice, vr_trace.hip; vr_planar_lattice.hpp has the table and
+// the argument): the contract of pq_hit_packet<... ROUND> — the same inputs, the same h, cd.rec, cd.local, cd.count and
+// cd.mine behind it, false with nothing touched — without the search.  The round's box is the parent's (planar_round_valid,
+// wave_minmax4 of the plane hits, the pad); the disks that can meet it are the lattice points of an index window that
+// follows from the box, lane l owns cell l of the window: one table word, then the disk's two record words, then THE
+// PARENT'S ball-box filter on those record bits.  The ballot of that filter feeds the parent's candidate loop; the leaf
+// position of a candidate comes from its owning lane.  No tree, no frontier lists, no leaf-node boxes in LDS.
+// Gives up (false, nothing touched) where the window has more cells than the wave has lanes, or more candidates pass the
+// filter than 2 * pqMaxCand (the parent's bound on the exact tests of a round; VR_PQ_CANDS holds that many records).
+// Every table index is formed from window indices clamped to the table (lattice_axis_window) by a lane inside the window,
+// every record index is a table word that is not VR_LATTICE_EMPTY: the table's kernel wrote leaf positions below numPrims.
+// ---------------------------------------------------------------------------
+template <bool CREDIT>
+__device__ __forceinline__ bool pq_hit_lattice(const TraceParams &p, HitRec &h, PqCands &cd, const float *__restrict__ wallS,
+                                               float tWall VR_DIAG_ARGS) {
+  const unsigned lane = threadIdx.x & 63u;
+  cd.count = 0;
+  cd.local = 0ull;
+  cd.box = false;
+  const float big = 3.0e38f;
+  const int pa = __float_as_int(wallS[VR_F_PD_AXIS]);
+  int b1, b2;
+  planar_in_plane_axes(pa, b1, b2);
+  const V3 q = mk(cd.round.qx, cd.round.qy, cd.round.qz);
+  const float u = getc(q, b1), v = getc(q, b2);
+  const bool in = planar_round_valid(cd.round, u, v, tWall, wallS[VR_F_PR_SB], wallS[VR_F_PR_SB + 1], wallS[VR_F_PR_SB + 2], wallS[VR_F_PR_SB + 3]);
+  if (!ballot64(in))
+    return true; // nobody's point lies in the scene: every ray misses the geometry
+  float ulo = in ? u : big, vlo = in ? v : big, uhi = in ? u : -big, vhi = in ? v : -big;
+  wave_minmax4(ulo, vlo, uhi, vhi);
+  const float pad = wallS[VR_F_PQ_PAD];
+  ulo -= pad;
+  vlo -= pad;
+  uhi += pad;
+  vhi += pad;
+#ifdef VR_DIAG
+  unsigned long long pqT0 = __builtin_amdgcn_s_memtime();
+#endif
+  // the window of lattice points around the box (wave-uniform: every operand is)
+  const int n1 = __float_as_int(wallS[VR_F_PL_N1]), n2 = __float_as_int(wallS[VR_F_PL_N2]);
+  const float invD = wallS[VR_F_PL_INVD], reach = wallS[VR_F_PL_REACH];
+  int i0, i1, j0, j1;
+  lattice_axis_window(ulo, uhi, wallS[VR_F_PL_PHASE1], invD, reach, n1, i0, i1);
+  lattice_axis_window(vlo, vhi, wallS[VR_F_PL_PHASE2], invD, reach, n2, j0, j1);
+  i0 = __builtin_amdgcn_readfirstlane(i0);
+  i1 = __builtin_amdgcn_readfirstlane(i1);
+  j0 = __builtin_amdgcn_readfirstlane(j0);
+  j1 = __builtin_amdgcn_readfirstlane(j1);
+  const int w = i1 - i0 + 1, rows = j1 - j0 + 1;
+  if (w <= 0 || rows <= 0)
+    return true; // no lattice point near the box: every ray misses the geometry
+  if (w > VR_LATTICE_WINDOW || rows > VR_LATTICE_WINDOW || w * rows > VR_LATTICE_WINDOW) {
+    DIAG(14); // (diag: gave up on the window)
+    return false; // (nothing touched yet)
+  }
+  const float qlx = pa == 0 ? wallS[VR_F_PR_QLO] : ulo, qhx = pa == 0 ? wallS[VR_F_PR_QHI] : uhi;
+  const float qly = pa == 1 ? wallS[VR_F_PR_QLO] : (pa == 0 ? ulo : vlo), qhy = pa == 1 ? wallS[VR_F_PR_QHI] : (pa == 0 ? uhi : vhi);
+  const float qlz = pa == 2 ? wallS[VR_F_PR_QLO] : vlo, qhz = pa == 2 ? wallS[VR_F_PR_QHI] : vhi;
+  typedef const __attribute__((address_space(1))) unsigned *GlobalU32;
+  const GlobalU32 table = reinterpret_cast<GlobalU32>(frame_addr(wallS, VR_F_PL_PTR_LO));
+  const float4 *__restrict__ prims = reinterpret_cast<const float4 *>(p.prims);
+  unsigned pos = VR_LATTICE_EMPTY; // this lane's disk: its leaf position
+  bool cand = false;
+  float4 r0 = make_float4(0, 0, 0, 0), r1 = r0;
+  if ((int)lane < w * rows) {
+    int col, row;
+    lattice_lane_cell((int)lane, w, __builtin_amdgcn_rcpf((float)w), col, row);
+    // (inside the window for every rounding of the reciprocal: the clamp costs two instructions, a load outside the table a fault)
+    col = col < 0 ? 0 : (col >= w ? w - 1 : col);
+    row = row < 0 ? 0 : (row >= rows ? rows - 1 : row);
+    pos = table[(unsigned)(j0 + row) * (unsigned)n1 + (unsigned)(i0 + col)];
+    if (pos != VR_LATTICE_EMPTY) {
+      DIAG(3);
+      r0 = prims[2 * (size_t)pos];
+      r1 = prims[2 * (size_t)pos + 1];
+      // a disc lies inside the ball of its radius (the parent's filter, on the same box)
+      cand = all6(r0.x - r0.w <= qhx, r0.x + r0.w >= qlx, r0.y - r0.w <= qhy, r0.y + r0.w >= qly, r0.z - r0.w <= qhz, r0.z + r0.w >= qlz);
+    }
+  }
+  unsigned long long m = ballot64(cand);
+  if ((unsigned)__popcll(m) > 2u * p.pqMaxCand) {
+    DIAG(15); // (diag: gave up on the candidate count)
+    return false; // (nothing touched yet)
+  }
+#ifdef VR_DIAG
+  {
+    const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+    if (lane == 0u)
+      phaseT[9] += now_ - pqT0; // (diag: the window, the candidates' record loads + box tests)
+    pqT0 = now_;
+  }
+#endif
+  unsigned tests = 0;
+  while (m) {
+    const int k = __ffsll((long long)m) - 1;
+    m &= m - 1ull;
+    DIAG(4);
+    const unsigned qq = (unsigned)__builtin_amdgcn_readlane((int)pos, k);
+    const V3 cc = mk(lane_bcast(r0.x, k), lane_bcast(r0.y, k), lane_bcast(r0.z, k));
+    const unsigned orig = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(r1.w), k);
+    bool ok, okLocal;
+    planar_round_cand(cd.round, cc.x, cc.y, cc.z, ok, okLocal); // (one difference and one square per coordinate for both tests)
+    const bool took = hit_update_lds(h, ok, cd.round.t, orig, qq);
+    if (CREDIT) {
+      const int c = (int)tests;
+      cd.mine = took ? (unsigned)c : cd.mine;
+      if ((int)lane == k) { // (the records as crediting reads them: the lane's own r0 / r1)
+        cd.rec[c] = mk_u4(qq, __float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r0.z));
+        cd.rec[VR_PQ_NRM + c] = mk_u4(__float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), __float_as_uint(r0.w));
+      }
+      cd.local |= (unsigned long long)okLocal << c;
+      cd.count = tests + 1u;
+    }
+    ++tests;
+  }
+#ifdef VR_DIAG
+  {
+    const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+    if (lane == 0u)
+      phaseT[15] += now_ - pqT0; // (diag: the exact tests)
+  }
+#endif
   return true;
 }
 

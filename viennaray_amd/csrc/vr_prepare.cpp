@@ -11,6 +11,7 @@
 #include "vr_context.hpp"
 #include "vr_particles.hpp"
 #include "vr_planar_disks.hpp"
+#include "vr_planar_lattice.hpp"
 #include "vr_uniform_disks.hpp"
 
 namespace vr {
@@ -623,6 +624,10 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   L.planarDisks = L.uniformDisks && K.planarDisks && c->planarDisks;
   // ... and that one in its one-point-per-round form (vr_planar_disks.hpp (1) - (3))
   L.planarRound = L.planarDisks && K.planarRound;
+  // ... with its candidates from the lattice table where the cloud is a lattice cloud (vr_context::planarLattice) whose
+  // windows fit a wave (vr_planar_lattice.hpp)
+  L.planarLattice = L.planarRound && K.planarLattice && c->planarLattice &&
+                    lattice_window_pays(lattice_reach(c->geo.diskRadius, c->geo.gridDelta, 1e-5f * scene_scale(c)), 1.f / c->geo.gridDelta);
   int blocks = 1;
   L.userKernel = nullptr;
   L.userGen = nullptr;
@@ -645,7 +650,8 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
     for (int m : {L.kernel_mode(), L.relief ? L.looseMode : L.kernel_mode()}) // (launch_trace would refuse it: said here, by name)
       if (!trace_kernel_exists(set, D, c->geo.geo, trace_kernel_particle(L.kernelParticle, m), m))
         return fail(c, VR_E_STATE, ("no trace kernel for this geometry / particle in MODE " + std::to_string(m)).c_str());
-    blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.kernel_mode(), L.params.smallBytes));
+    blocks = std::max(1, L.planarLattice ? trace_lattice_blocks_per_cu()
+                                         : trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.kernel_mode(), L.params.smallBytes));
   }
   // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
   // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of
@@ -988,6 +994,17 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
       f[VR_F_PR_SB + 1] = p.sceneHi[b1] + p.pqPad;
       f[VR_F_PR_SB + 2] = p.sceneLo[b2] - p.pqPad;
       f[VR_F_PR_SB + 3] = p.sceneHi[b2] + p.pqPad;
+    }
+    if (L.planarLattice) { // (VR_F_PL_*: words of a stateful model and of the data log, which such a launch has not)
+      if (S.stateful || S.logs)
+        return fail(c, VR_E_STATE, "a planar-lattice launch has no stateful model: their frame words are the same");
+      addr(VR_F_PL_PTR_LO, c->dLattice.p);
+      f[VR_F_PL_N1] = bits(c->latticeN[0]);
+      f[VR_F_PL_N2] = bits(c->latticeN[1]);
+      f[VR_F_PL_PHASE1] = c->latticePhase[0];
+      f[VR_F_PL_PHASE2] = c->latticePhase[1];
+      f[VR_F_PL_INVD] = 1.f / c->geo.gridDelta;
+      f[VR_F_PL_REACH] = lattice_reach(w[3], c->geo.gridDelta, p.pqPad);
     }
   }
   if (L.relief) { // the relief field's fine tiles (relief_clip, vr_packet_query.hpp)

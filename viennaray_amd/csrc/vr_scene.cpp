@@ -5,6 +5,7 @@
 
 #include "vr_context.hpp"
 #include "vr_planar_disks.hpp"
+#include "vr_planar_lattice.hpp"
 
 namespace vr {
 
@@ -161,6 +162,33 @@ static void set_uniform_disks(vr_context *c, const uint32_t (&words)[VR_UNIFORM_
   c->planarWord = c->planarDisks ? words[9 + axis] : 0u;
 }
 
+// Lattice cloud (vr_context::planarLattice, vr_planar_lattice.hpp): where the planar cloud's extent fits a table, one kernel
+// over the records in their NEW leaf order validates and fills it, and one word read back decides.  Called at the end of
+// every device build — the table holds leaf positions — behind set_uniform_disks; synchronises the stream.
+static int build_lattice_table(vr_context *c) {
+  c->planarLattice = false;
+  const HostGeometry &g = c->geo;
+  if (!c->planarDisks || g.D != 3 || !c->haveWide)
+    return VR_OK;
+  int b1, b2;
+  planar_in_plane_axes(c->planarAxis, b1, b2);
+  const int n1 = lattice_axis_points(g.minC[b1], g.maxC[b1], g.gridDelta), n2 = lattice_axis_points(g.minC[b2], g.maxC[b2], g.gridDelta);
+  if (!lattice_table_fits(n1, n2, g.numPrims))
+    return VR_OK;
+  const size_t cells = (size_t)n1 * (size_t)n2;
+  VR_HIP(c, c->dLattice.ensure(cells + 1));
+  VR_HIP(c, launch_lattice_table(c->dPrims.p, g.numPrims, b1, b2, g.minC[b1], g.minC[b2], 1.f / g.gridDelta, n1, n2, c->dLattice.p, c->stream));
+  uint32_t flag = 1u;
+  VR_HIP(c, hipMemcpyAsync(&flag, c->dLattice.p + cells, 4, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  c->planarLattice = flag == 0u;
+  c->latticeN[0] = n1;
+  c->latticeN[1] = n2;
+  c->latticePhase[0] = g.minC[b1];
+  c->latticePhase[1] = g.minC[b2];
+  return VR_OK;
+}
+
 int build_scene(vr_context *c) {
   const Knobs &K = c->knobs;
   HostGeometry &g = c->geo;
@@ -233,6 +261,7 @@ int build_scene(vr_context *c) {
     set_uniform_disks(c, uni);
     c->numNodes = c->bvh.numNodes;
     c->haveWide = false; // (validation path: walks only)
+    c->planarLattice = false; // (... and no packet query to look candidates up for)
     return quantize_scene(c, c->dNodes.p, c->bvh.nodes.data()); // (host builder: pre-order already)
   }
 
@@ -398,7 +427,9 @@ int build_scene(vr_context *c) {
   c->bvh.maxDepth = 0;
   const int rq = quantize_scene(c, c->dNodesPre.p, root8);
   c->dNodesPre.release(); // (build-time scratch)
-  return rq;
+  if (rq != VR_OK)
+    return rq;
+  return build_lattice_table(c); // (the records' order is final: a re-fit above leaves it as it is)
 }
 
 } // namespace vr

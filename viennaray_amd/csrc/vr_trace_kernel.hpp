@@ -5,7 +5,14 @@
 //
 // tools/salu_inventory.py finds the phases of a round by the `// ---- ` marker comments of the kernel body: their texts
 // are listed there, and each must stay unique and in order.
-#pragma once
+//
+// The kernel's text compiles under a second name as well: a translation unit that includes this file AGAIN with
+// VR_TRACE_KERNEL_TWIN defined as a name gets that text alone — none of the helpers — as a kernel template of that name
+// with PLANAR_LATTICE on, the one variant that is not a mode of the catalogue (vr_trace.hip: trace_kernel_lattice).  Same
+// text, another symbol: trace_kernel itself compiles exactly as if the twin did not exist.
+#if !defined(VR_TRACE_KERNEL_HPP) || defined(VR_TRACE_KERNEL_TWIN)
+#ifndef VR_TRACE_KERNEL_TWIN
+#define VR_TRACE_KERNEL_HPP
 #include "vr_device.hpp"
 #include "vr_particles.hpp"
 
@@ -177,14 +184,25 @@ constexpr KernelSet VR_KERNEL_SET = KERNELS_MODULE;
 #else
 constexpr KernelSet VR_KERNEL_SET = KERNELS_LIBRARY;
 #endif
+#define VR_TRACE_KERNEL_NAME trace_kernel
+#else // VR_TRACE_KERNEL_TWIN: the kernel's text alone, under that name
+namespace vr {
+#define VR_TRACE_KERNEL_NAME VR_TRACE_KERNEL_TWIN
+#endif
 template <int D, int GEO, int PARTICLE, int MODE_>
 __global__ __launch_bounds__(VR_BLOCK) __attribute__((amdgpu_num_sgpr(80)))
 __attribute__((amdgpu_waves_per_eu(mode_traits(MODE_).waves, mode_traits(MODE_).waves))) void
-trace_kernel(const TraceParams p) {
+VR_TRACE_KERNEL_NAME(const TraceParams p) {
   constexpr ModeTraits T = mode_traits(MODE_); // (what the mode is: vr_types.hpp)
   constexpr bool SMALL = T.small;
   constexpr bool RELIEF = T.relief;
   constexpr bool RESUME = T.resume;
+#ifdef VR_TRACE_KERNEL_TWIN // (... with the round's candidates from the lattice table: pq_hit_lattice, vr_planar_lattice.hpp)
+  constexpr bool PLANAR_LATTICE = true;
+  static_assert(T.planarRound, "the lattice table serves the one-point-per-round kernel");
+#else
+  constexpr bool PLANAR_LATTICE = false;
+#endif
   constexpr bool PLANAR_ROUND = T.planarRound; // (... with the plane hit as the round's one point: pq_hit_packet ROUND, wall-free rounds)
   constexpr bool PLANAR = T.planar; // (... with its PLANAR candidate tests, which are UNIFORM ones)
   constexpr bool UNIFORM = T.uniform; // (MODE_ABSORB_FLAT with pq_hit_packet's UNIFORM candidate tests)
@@ -228,7 +246,7 @@ trace_kernel(const TraceParams p) {
   // 7 waves per SIMD and at 6; removed.)
   __shared__ unsigned cntS[8 * VR_BLOCK];
   __shared__ unsigned pqS[(VR_BLOCK / 64) * 128]; // packet query: per-wave frontier lists
-  constexpr bool PQ_CACHE = (MODE == MODE_ABSORB_FLAT || MODE == MODE_GENERAL_FLAT) && (!RELIEF || VR_PQ_CACHE_RELIEF) && VR_PQ_CACHE != 0; // (pq_hit_packet CACHE: flat-scene kernels)
+  constexpr bool PQ_CACHE = (MODE == MODE_ABSORB_FLAT || MODE == MODE_GENERAL_FLAT) && (!RELIEF || VR_PQ_CACHE_RELIEF) && VR_PQ_CACHE != 0 && !PLANAR_LATTICE; // (pq_hit_packet CACHE: flat-scene kernels; the lattice kernel searches no tree)
   __shared__ float pqBoxS[PQ_CACHE ? (VR_BLOCK / 64) * 6 * VR_PQ_KEEP : 1];         // ... the kept leaf nodes' boxes, VR_PQ_KEEP x 6 per wave
   __shared__ uint4 candS[PQ_CREDIT ? (VR_BLOCK / 64) * VR_PQ_RECORDS : 1]; // ... and candidate records (pq_credit)
   // ... and, where the credits of a round carry different weights (the general kernels), one int64 sum per candidate
@@ -612,7 +630,10 @@ trace_kernel(const TraceParams p) {
           }
         }
         // ---- packet query: the call and its back-off ----
-        packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE, LEAN, UNIFORM, PLANAR, PLANAR_ROUND>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
+        if constexpr (PLANAR_LATTICE) // (the lattice table's window in place of the search: no frontier lists, no leaf-node boxes)
+          packetDone = pq_hit_lattice<PQ_CREDIT>(p, h, cands, wallS, tWall VR_DIAG_PASS);
+        else
+          packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE, LEAN, UNIFORM, PLANAR, PLANAR_ROUND>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
         pqCredit = PQ_CREDIT && packetDone;
         pqFails = packetDone ? 0u : (pqFails < 6u ? pqFails + 1u : 6u);
         pqSkip = packetDone ? 0u : (1u << pqFails) - 1u;
@@ -1306,5 +1327,7 @@ trace_kernel(const TraceParams p) {
       atomicAdd(&p.counters[i], s);
   }
 }
+#undef VR_TRACE_KERNEL_NAME
 
 } // namespace vr
+#endif // !VR_TRACE_KERNEL_HPP || VR_TRACE_KERNEL_TWIN
