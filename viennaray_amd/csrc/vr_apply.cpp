@@ -150,7 +150,9 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
       VR_HIP(c, hipModuleLaunchKernel(L.userKernel, gridBatch, 1, 1, VR_BLOCK, 1, 1, trace_dynamic_lds(L.traceMode, p.smallBytes), c->stream,
                                       args, nullptr));
     } else if (tight) {
-      if (L.planarLattice) // (the lattice cloud's kernel: not a mode of the table)
+      if (L.latticeLanes) // (the lattice cloud's kernels: not modes of the table)
+        VR_HIP(c, launch_trace_lattice_lanes(p, gridBatch, c->stream));
+      else if (L.planarLattice)
         VR_HIP(c, launch_trace_lattice(p, gridBatch, c->stream));
       else
         VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.kernel_mode(), gridBatch, c->stream));
@@ -386,6 +388,9 @@ int vr_apply_finish(vr_context *c) {
       // (... and whether its candidates came from the lattice table)
       std::fprintf(stderr, "[vr] planar disks: lattice: scene %d, VR_PLANAR_LATTICE %d, launch %d, particle %zu\n", (int)c->planarLattice,
                    (int)c->knobs.planarLattice, (int)L.planarLattice, q);
+      // (... and whether each lane tested its own four disks; scene: the host rule alone, lattice_lanes_rule)
+      std::fprintf(stderr, "[vr] planar disks: lanes: scene %d, VR_LATTICE_LANE_TESTS %d, launch %d, particle %zu\n",
+                   (int)L.latticeLanesScene, (int)c->knobs.latticeLaneTests, (int)L.latticeLanes, q);
     }
   const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
   if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)

@@ -120,6 +120,7 @@ struct Knobs {
   bool planarDisks = true;             // VR_PLANAR_DISKS (0: off): ... the planar one of them (off: planar disks run the uniform-disk kernel)
   bool planarRound = true;             // VR_PLANAR_ROUND (0: off): ... in its one-point-per-round form (off: the planar kernel as it was)
   bool planarLattice = true;           // VR_PLANAR_LATTICE (0: off): ... with its candidates from the lattice table where the cloud is a lattice cloud (off: the one-point-per-round kernel as it was)
+  bool latticeLaneTests = true;        // VR_LATTICE_LANE_TESTS (0: off): ... each lane testing the four disks at the corners of its point's cell where the disks are small against the pitch (off: trace_kernel_lattice as it was)
   std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
   std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
   // kernel parameters (TraceParams)
@@ -210,6 +211,11 @@ struct ParticleLaunch {
   // from the lattice table, the table's words in the frame as well (VR_F_PL_*).  Only ever set with planarRound.  Not a mode:
   // the launch takes launch_trace_lattice in place of launch_trace(kernel_mode())
   bool planarLattice = false;
+  // ... whose disks are small enough against the pitch (lattice_lanes_rule, vr_planar_lattice.hpp) with VR_LATTICE_LANE_TESTS
+  // on: that kernel with four disk tests per lane in place of the candidate loop (launch_trace_lattice_lanes).  Only ever
+  // set with planarLattice
+  bool latticeLanes = false;
+  bool latticeLanesScene = false; // (the rule's verdict on the scene alone, for the VR_PRINT_LAUNCHES line)
   int kernel_mode() const { // the mode launch_trace takes
     if (planarRound)
       return (int)MODE_ABSORB_FLAT_PLANAR_ROUND;

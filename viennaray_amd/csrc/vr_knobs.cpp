@@ -62,6 +62,8 @@ Knobs read_knobs() {
     k.planarRound = std::atoi(e) != 0;
   if (const char *e = std::getenv("VR_PLANAR_LATTICE"))
     k.planarLattice = std::atoi(e) != 0;
+  if (const char *e = std::getenv("VR_LATTICE_LANE_TESTS"))
+    k.latticeLaneTests = std::atoi(e) != 0;
   if (const char *e = std::getenv("VR_SPAN_BINS"))
     k.spanBins = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
   if (const char *e = std::getenv("VR_QUEUES"))

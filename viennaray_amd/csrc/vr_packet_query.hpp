@@ -120,6 +120,7 @@ struct PqCands {
   bool box;       // KEEPQ: records VR_PQ_BOX, + 1 hold the query's box (false: no ray reached the scene, nothing stored)
   unsigned mine;  // per lane: the candidate that is this lane's closest hit so far (valid where the hit came from the query)
   PlanarRound round; // ROUND: the round's point and thresholds, the caller's (trace_kernel computes them before the walls)
+  unsigned slots;    // pq_hit_lattice_lanes alone, per lane: the window slots of the lane's four corners, a byte each (VR_PQ_NO_SLOT: none)
 };
 constexpr unsigned VR_PQ_CANDS = 52; // >= 2 * pqMaxCand + 1 (pqMaxCand <= 24, vr_knobs.cpp) + the two records below
 // KEEPQ: records 50 / 51 keep the query's (padded) box {lo.xyz, -}{hi.xyz, -} for the round's follow-up segments
@@ -665,6 +666,170 @@ __device__ __forceinline__ bool pq_hit_lattice(const TraceParams &p, HitRec &h, 
     }
     ++tests;
   }
+#ifdef VR_DIAG
+  {
+    const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+    if (lane == 0u)
+      phaseT[15] += now_ - pqT0; // (diag: the exact tests)
+  }
+#endif
+  return true;
+}
+
+// ---------------------------------------------------------------------------
+// The packet query of a lattice cloud whose disks are small against the pitch (trace_kernel_lattice_lanes, vr_trace.hip;
+// vr_planar_lattice.hpp "four corners per lane" has the rule and the argument): pq_hit_lattice's box and window, then NO
+// candidate loop and no give-up (a window of more than 64 cells: the direct form, in the function).  Lane l files the disk of window cell l — {leaf position, centre} in record l of
+// the wave's LDS records, its original id in word l behind them, VR_LATTICE_EMPTY where the cell has none — and every lane
+// tests the four disks at the corners of ITS point's cell: planar_round_cand on the record's bits, hit_update_lds with the
+// record's id and leaf position, as the candidate loop does.  A disk that accepts a lane's point is one of its four corners
+// (the rule), and for a lane whose point is in the round's box it lies inside the window (the window's argument: it passes
+// the parent's ball-box filter); the other lanes accept nothing that counts (a wall comes first, or the point lies outside
+// the scene).  So each lane sees every disk that pq_hit_lattice's loop would have let it accept, and the closest-hit rule
+// does not depend on the others.  No ball-box filter, no ballot, no give-up on the candidate count: always true.
+// Behind it: h; cd.mine = which of the four corners is the lane's closest hit; cd.local = bit k: the lane's ray passes the
+// neighbour test on corner k; cd.slots = the four window slots, a byte each (VR_PQ_NO_SLOT: a corner outside the window);
+// cd.count = 0.  The wave's records: VR_PQ_LANE_IDS .. hold the 64 id words, VR_PQ_LANE_CNT .. the 64 counters of the
+// crediting (trace_kernel), all inside the VR_PQ_RECORDS records the wave has anyway.
+// Every LDS index is a window slot (lattice_window_slot: below w * rows <= 64) or 0, every table index is formed as in
+// pq_hit_lattice, and the cell's indices pass through lattice_lane_corner's clamp in float.
+// ---------------------------------------------------------------------------
+constexpr unsigned VR_PQ_NO_SLOT = 0xFFu;
+constexpr unsigned VR_PQ_LANE_IDS = 64, VR_PQ_LANE_CNT = 80; // (records: 16 of them hold 64 words)
+static_assert(VR_PQ_LANE_CNT + 16u <= VR_PQ_RECORDS && VR_LATTICE_WINDOW == 64, "the wave's records hold the lanes' tables");
+template <bool CREDIT>
+__device__ __forceinline__ bool pq_hit_lattice_lanes(const TraceParams &p, HitRec &h, PqCands &cd, const float *__restrict__ wallS,
+                                                     float tWall VR_DIAG_ARGS) {
+  const unsigned lane = threadIdx.x & 63u;
+  cd.count = 0;
+  cd.local = 0ull;
+  cd.box = false;
+  const float big = 3.0e38f;
+  const int pa = __float_as_int(wallS[VR_F_PD_AXIS]);
+  int b1, b2;
+  planar_in_plane_axes(pa, b1, b2);
+  const V3 q = mk(cd.round.qx, cd.round.qy, cd.round.qz);
+  const float u = getc(q, b1), v = getc(q, b2);
+  const bool in = planar_round_valid(cd.round, u, v, tWall, wallS[VR_F_PR_SB], wallS[VR_F_PR_SB + 1], wallS[VR_F_PR_SB + 2], wallS[VR_F_PR_SB + 3]);
+  if (!ballot64(in))
+    return true; // nobody's point lies in the scene: every ray misses the geometry
+  float ulo = in ? u : big, vlo = in ? v : big, uhi = in ? u : -big, vhi = in ? v : -big;
+  wave_minmax4(ulo, vlo, uhi, vhi);
+  const float pad = wallS[VR_F_PQ_PAD];
+  ulo -= pad;
+  vlo -= pad;
+  uhi += pad;
+  vhi += pad;
+#ifdef VR_DIAG
+  unsigned long long pqT0 = __builtin_amdgcn_s_memtime();
+#endif
+  // the window of lattice points around the box (wave-uniform: every operand is)
+  const int n1 = __float_as_int(wallS[VR_F_PL_N1]), n2 = __float_as_int(wallS[VR_F_PL_N2]);
+  const float invD = wallS[VR_F_PL_INVD], reach = wallS[VR_F_PL_REACH];
+  const float phase1 = wallS[VR_F_PL_PHASE1], phase2 = wallS[VR_F_PL_PHASE2];
+  int i0, i1, j0, j1;
+  lattice_axis_window(ulo, uhi, phase1, invD, reach, n1, i0, i1);
+  lattice_axis_window(vlo, vhi, phase2, invD, reach, n2, j0, j1);
+  i0 = __builtin_amdgcn_readfirstlane(i0);
+  i1 = __builtin_amdgcn_readfirstlane(i1);
+  j0 = __builtin_amdgcn_readfirstlane(j0);
+  j1 = __builtin_amdgcn_readfirstlane(j1);
+  const int w = i1 - i0 + 1, rows = j1 - j0 + 1;
+  if (w <= 0 || rows <= 0)
+    return true; // no lattice point near the box: every ray misses the geometry
+  typedef const __attribute__((address_space(1))) unsigned *GlobalU32;
+  const GlobalU32 table = reinterpret_cast<GlobalU32>(frame_addr(wallS, VR_F_PL_PTR_LO));
+  const float4 *__restrict__ prims = reinterpret_cast<const float4 *>(p.prims);
+  if (w > VR_LATTICE_WINDOW || rows > VR_LATTICE_WINDOW || w * rows > VR_LATTICE_WINDOW) {
+    // The window does not fit the wave (a round that holds a ray folded in from the far side of the domain): the DIRECT
+    // form.  The rule needs no window — a disk that accepts a lane's point is a corner of its cell, wherever the other
+    // lanes' points lie — so each lane reads its four table words and records from global memory: a corner outside the
+    // table is no candidate, the table index of one inside is below n1 n2, and an absent corner reads word 0 / record 0,
+    // which exist.  The same tests on the same record bits as the tree packet and the walk make, the same tie rule: the
+    // hits are theirs.  Behind it: cd.count = 1 (wave-uniform: the decision is), record l of the wave = lane l's four
+    // leaf positions (VR_LATTICE_EMPTY: none) for the crediting, cd.local as below.
+    DIAG(14); // (diag: the window did not fit)
+    const int di = lattice_lane_corner(u, phase1, invD, n1), dj = lattice_lane_corner(v, phase2, invD, n2);
+    unsigned ps[4], loc = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      DIAG(4);
+      const int i = di + (k & 1), j = dj + (k >> 1);
+      const bool inT = (i >= 0) & (i < n1) & (j >= 0) & (j < n2);
+      const unsigned pos = table[inT ? (unsigned)j * (unsigned)n1 + (unsigned)i : 0u];
+      const bool present = inT & (pos != VR_LATTICE_EMPTY);
+      const size_t rp = present ? (size_t)pos : (size_t)0;
+      const float4 r0 = prims[2 * rp];
+      const unsigned orig = __float_as_uint(prims[2 * rp + 1].w);
+      bool ok, okLocal;
+      planar_round_cand(cd.round, r0.x, r0.y, r0.z, ok, okLocal);
+      hit_update_lds(h, ok & present, cd.round.t, orig, pos);
+      loc |= (unsigned)(okLocal & present) << k;
+      ps[k] = present ? pos : VR_LATTICE_EMPTY;
+    }
+    if (CREDIT) {
+      cd.rec[lane] = mk_u4(ps[0], ps[1], ps[2], ps[3]);
+      cd.local = (unsigned long long)loc;
+      cd.count = 1u;
+      cd.slots = 0u;
+    }
+    return true;
+  }
+  VR_LDS unsigned *const ids = (VR_LDS unsigned *)(cd.rec + VR_PQ_LANE_IDS);
+  { // lane l files the disk of window cell l
+    unsigned pos = VR_LATTICE_EMPTY;
+    float4 r0 = make_float4(0, 0, 0, 0);
+    unsigned orig = 0u;
+    if ((int)lane < w * rows) {
+      int col, row;
+      lattice_lane_cell((int)lane, w, __builtin_amdgcn_rcpf((float)w), col, row);
+      // (inside the window for every rounding of the reciprocal: the clamp costs two instructions, a load outside the table a fault)
+      col = col < 0 ? 0 : (col >= w ? w - 1 : col);
+      row = row < 0 ? 0 : (row >= rows ? rows - 1 : row);
+      pos = table[(unsigned)(j0 + row) * (unsigned)n1 + (unsigned)(i0 + col)];
+      if (pos != VR_LATTICE_EMPTY) {
+        DIAG(3);
+        r0 = prims[2 * (size_t)pos];
+        orig = __float_as_uint(prims[2 * (size_t)pos + 1].w);
+      }
+    }
+    // (the lane made an opaque value here, so that the record's address and the lane's float are recomputed per round and
+    //  not hoisted and spilled — no scratch left in the kernel — was built and measured: trace 2.44 ms against 2.38 ms)
+    cd.rec[lane] = mk_u4(pos, __float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r0.z));
+    ids[lane] = orig;
+  }
+  __builtin_amdgcn_wave_barrier();
+#ifdef VR_DIAG
+  {
+    const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+    if (lane == 0u)
+      phaseT[9] += now_ - pqT0; // (diag: the window, the cells' record loads, their filing)
+    pqT0 = now_;
+  }
+#endif
+  // the four corners of this lane's cell.  (Every lane: one whose thresholds are both 0 accepts nothing, and a branch
+  // around it would be exec bookkeeping for the lanes of a wave that nearly all take part.)
+  const int ci = lattice_lane_corner(u, phase1, invD, n1), cj = lattice_lane_corner(v, phase2, invD, n2);
+  unsigned slots = 0u, local = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    DIAG(4);
+    const int s = lattice_window_slot(ci + (k & 1), cj + (k >> 1), i0, i1, j0, j1);
+    const unsigned sl = s < 0 ? 0u : (unsigned)s; // (slot 0 is a cell of every window: its record is this round's)
+    const U4 cr = cd.rec[sl];
+    const unsigned orig = ids[sl];
+    const bool present = (s >= 0) & (cr.x != VR_LATTICE_EMPTY);
+    bool ok, okLocal;
+    planar_round_cand(cd.round, __uint_as_float(cr.y), __uint_as_float(cr.z), __uint_as_float(cr.w), ok, okLocal);
+    const bool took = hit_update_lds(h, ok & present, cd.round.t, orig, cr.x);
+    if (CREDIT) {
+      cd.mine = took ? (unsigned)k : cd.mine;
+      local |= (unsigned)(okLocal & present) << k;
+      slots |= (s < 0 ? VR_PQ_NO_SLOT : (unsigned)s) << (8 * k);
+    }
+  }
+  cd.local = (unsigned long long)local;
+  cd.slots = slots;
 #ifdef VR_DIAG
   {
     const unsigned long long now_ = __builtin_amdgcn_s_memtime();

@@ -94,4 +94,56 @@ VR_HD void lattice_lane_cell(int l, int w, float invW, int &col, int &row) {
   col = l - row * w;
 }
 
+// ==== four corners per lane (trace_kernel_lattice_lanes, vr_trace.hip; pq_hit_lattice_lanes, vr_packet_query.hpp) ==========
+// A round's point q (vr_planar_disks.hpp (1)) lies in one lattice cell; where the disks are small enough against the pitch,
+// only the lattice points at that cell's four corners can carry a disk that accepts q.  Each lane then tests its own four
+// disks instead of every candidate of the wave's window.
+//
+// The rule, per in-plane axis, with u the point's coordinate, x = phase + k delta a lattice point (real numbers: phase and
+// delta are floats), c the centre of the disk filed at x, r the radius, C a bound on |u| and |phase| and ulp the
+// spacing of the floats at C:
+//   acceptance: planar_round_cand accepts (either test: both thresholds are at most r^2 rounded, uniform_disk_threshold)
+//     only where fl(u - c)^2 < r^2 in float, so |u - c| < r (1 + 2^-22) in real numbers (vr_planar_disks.hpp (2)).
+//   the centre: lattice_cell_of filed c at x because |f - rint(f)| <= 1/8 for f = fl(fl(c - phase) invD), invD = fl(1 / delta).
+//     f - rint(f) is exact; f itself differs from (c - phase) / delta by e / delta with
+//       e <= |fl(c - phase) - (c - phase)| + |fl(c - phase)| (2^-24 + 2^-24 + 2^-48)   (the product's rounding, invD's)
+//         <= ulp + 2 C 2.0001 2^-24 < ulp + 4.001 ulp                                     (|c - phase| <= 2 C; C 2^-24 < ulp)
+//     so |c - x| <= delta / 8 + 5.001 ulp.
+//   the cell: lattice_lane_corner takes i = floor(g), g = fl(fl(u - phase) invD): the same two roundings, |g delta -
+//     (u - phase)| < 5.001 ulp.
+// An accepting disk's lattice point has |u - x| < R = r (1 + 2^-22) + delta / 8 + 5.001 ulp, i.e. |(u - phase) / delta - k|
+// < R / delta, and |g - k| < (R + 5.001 ulp) / delta.  Where
+//       r (1 + 2^-22) + delta / 8 + 12 ulp <= delta                                        (lattice_lanes_rule)
+// (12 ulp: the two 5.001 with room to spare) that is |g - k| < 1: k = floor(g) or floor(g) + 1, a corner of the cell.
+// A point with |u| > C: C is the scene's largest coordinate plus two pitches (lattice_lanes_coord), every centre lies in the
+// scene box and every lattice point within delta / 8 + 5.001 ulp of one, so such a point is farther than delta >= R from
+// every lattice point and no disk accepts it, whichever cell the arithmetic names.  Testing a corner that does not accept is
+// harmless: the test is planar_round_cand on the disk's own record.  Both ends of the index pass through a clamp in float
+// before the conversion (as in lattice_axis_window): an infinite or NaN point names a cell outside the table, never an
+// index a conversion made up.
+constexpr float VR_LATTICE_LANES_ULPS = 12.f;
+// the bound C on an in-plane coordinate that matters: the scene's largest (scene_scale, vr_prepare.cpp) and two pitches
+inline float lattice_lanes_coord(float sceneScale, float delta) { return sceneScale + 2.f * delta; }
+// the rule above, in double on the host (the three terms and delta are floats: their sum is exact enough by 2^-29)
+inline bool lattice_lanes_rule(float radius, float delta, float C) {
+  if (!(radius > 0.f) || !(delta > 0.f) || !(C >= 0.f) || !(C < 1e30f))
+    return false;
+  const double ulp = (double)__builtin_nextafterf(C, __builtin_inff()) - (double)C;
+  return (double)radius * (1.0 + 2.384185791015625e-07) + 0.125 * (double)delta + (double)VR_LATTICE_LANES_ULPS * ulp <= (double)delta;
+}
+// The lower corner's lattice index along one axis, -1 .. n (n the axis's points): floor((u - phase) / delta), clamped in
+// float first.  The cell's two corners along the axis are k and k + 1; each is a lattice point only where 0 <= . < n.
+VR_HD int lattice_lane_corner(float u, float phase, float invDelta, int n) {
+  const float g = (u - phase) * invDelta;
+  const float gc = __builtin_fminf(__builtin_fmaxf(g, -1.f), (float)n); // (fmaxf / fminf of a NaN: the other operand)
+  return (int)__builtin_floorf(gc);
+}
+// The window slot (the lane that owns the cell, lattice_lane_cell) of lattice point (i, j) in the window i0 .. i1 x
+// j0 .. j1, or -1 where the point lies outside it.  The window lies inside the table and has at most VR_LATTICE_WINDOW
+// cells, so a slot that is not -1 is below VR_LATTICE_WINDOW and names a cell of the table.
+VR_HD int lattice_window_slot(int i, int j, int i0, int i1, int j0, int j1) {
+  const bool in = (i >= i0) & (i <= i1) & (j >= j0) & (j <= j1);
+  return in ? (j - j0) * (i1 - i0 + 1) + (i - i0) : -1;
+}
+
 } // namespace vr

@@ -628,6 +628,10 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   // windows fit a wave (vr_planar_lattice.hpp)
   L.planarLattice = L.planarRound && K.planarLattice && c->planarLattice &&
                     lattice_window_pays(lattice_reach(c->geo.diskRadius, c->geo.gridDelta, 1e-5f * scene_scale(c)), 1.f / c->geo.gridDelta);
+  // ... each lane testing the four disks at the corners of its point's cell, where no other disk can accept the point
+  // (vr_planar_lattice.hpp, "four corners per lane")
+  L.latticeLanesScene = c->planarLattice && lattice_lanes_rule(c->geo.diskRadius, c->geo.gridDelta, lattice_lanes_coord(scene_scale(c), c->geo.gridDelta));
+  L.latticeLanes = L.planarLattice && K.latticeLaneTests && L.latticeLanesScene;
   int blocks = 1;
   L.userKernel = nullptr;
   L.userGen = nullptr;
@@ -650,8 +654,9 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
     for (int m : {L.kernel_mode(), L.relief ? L.looseMode : L.kernel_mode()}) // (launch_trace would refuse it: said here, by name)
       if (!trace_kernel_exists(set, D, c->geo.geo, trace_kernel_particle(L.kernelParticle, m), m))
         return fail(c, VR_E_STATE, ("no trace kernel for this geometry / particle in MODE " + std::to_string(m)).c_str());
-    blocks = std::max(1, L.planarLattice ? trace_lattice_blocks_per_cu()
-                                         : trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.kernel_mode(), L.params.smallBytes));
+    blocks = std::max(1, L.latticeLanes    ? trace_lattice_lanes_blocks_per_cu()
+                         : L.planarLattice ? trace_lattice_blocks_per_cu()
+                                           : trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.kernel_mode(), L.params.smallBytes));
   }
   // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
   // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of

@@ -122,5 +122,28 @@ int trace_lattice_blocks_per_cu() {
   return nb;
 }
 
+// ... and that kernel with four disk tests per lane in place of the candidate loop (ParticleLaunch::latticeLanes;
+// trace_kernel's LATTICE_LANES, pq_hit_lattice_lanes): the text a third time, under its own name, with both flags on.
+} // namespace vr
+#define VR_TRACE_KERNEL_TWIN trace_kernel_lattice_lanes
+#define VR_TRACE_KERNEL_LANES
+#include "vr_trace_kernel.hpp"
+#undef VR_TRACE_KERNEL_LANES
+#undef VR_TRACE_KERNEL_TWIN
+namespace vr {
+static constexpr StreamKernel VR_LATTICE_LANES_KERNEL = trace_kernel_lattice_lanes<3, 0, 0, MODE_ABSORB_FLAT_PLANAR_ROUND>;
+
+hipError_t launch_trace_lattice_lanes(const TraceParams &p, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL(VR_LATTICE_LANES_KERNEL, dim3(grid), dim3(VR_BLOCK), 0, s, p);
+  return hipGetLastError();
+}
+
+int trace_lattice_lanes_blocks_per_cu() {
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, VR_LATTICE_LANES_KERNEL, VR_BLOCK, 0) != hipSuccess)
+    return 2;
+  return nb;
+}
+
 } // namespace vr
 #endif // VR_USER_MODULE

@@ -9,7 +9,8 @@
 // The kernel's text compiles under a second name as well: a translation unit that includes this file AGAIN with
 // VR_TRACE_KERNEL_TWIN defined as a name gets that text alone — none of the helpers — as a kernel template of that name
 // with PLANAR_LATTICE on, the one variant that is not a mode of the catalogue (vr_trace.hip: trace_kernel_lattice).  Same
-// text, another symbol: trace_kernel itself compiles exactly as if the twin did not exist.
+// text, another symbol: trace_kernel itself compiles exactly as if the twin did not exist.  With VR_TRACE_KERNEL_LANES
+// defined beside it the twin also has LATTICE_LANES on (vr_trace.hip: trace_kernel_lattice_lanes).
 #if !defined(VR_TRACE_KERNEL_HPP) || defined(VR_TRACE_KERNEL_TWIN)
 #ifndef VR_TRACE_KERNEL_TWIN
 #define VR_TRACE_KERNEL_HPP
@@ -202,6 +203,11 @@ VR_TRACE_KERNEL_NAME(const TraceParams p) {
   static_assert(T.planarRound, "the lattice table serves the one-point-per-round kernel");
 #else
   constexpr bool PLANAR_LATTICE = false;
+#endif
+#if defined(VR_TRACE_KERNEL_TWIN) && defined(VR_TRACE_KERNEL_LANES) // (... each lane testing the four disks at the corners of its point's cell: pq_hit_lattice_lanes)
+  constexpr bool LATTICE_LANES = true;
+#else
+  constexpr bool LATTICE_LANES = false;
 #endif
   constexpr bool PLANAR_ROUND = T.planarRound; // (... with the plane hit as the round's one point: pq_hit_packet ROUND, wall-free rounds)
   constexpr bool PLANAR = T.planar; // (... with its PLANAR candidate tests, which are UNIFORM ones)
@@ -630,7 +636,9 @@ VR_TRACE_KERNEL_NAME(const TraceParams p) {
           }
         }
         // ---- packet query: the call and its back-off ----
-        if constexpr (PLANAR_LATTICE) // (the lattice table's window in place of the search: no frontier lists, no leaf-node boxes)
+        if constexpr (LATTICE_LANES) // (... and four disk tests per lane in place of the candidate loop)
+          packetDone = pq_hit_lattice_lanes<PQ_CREDIT>(p, h, cands, wallS, tWall VR_DIAG_PASS);
+        else if constexpr (PLANAR_LATTICE) // (the lattice table's window in place of the search: no frontier lists, no leaf-node boxes)
           packetDone = pq_hit_lattice<PQ_CREDIT>(p, h, cands, wallS, tWall VR_DIAG_PASS);
         else
           packetDone = pq_hit_packet<GEO, PQ_CREDIT, FRAME_LDS, FOLLOW, RELIEF, PQ_CACHE, LEAN, UNIFORM, PLANAR, PLANAR_ROUND>(p, active, org, dir, tnear, h, (volatile VR_LDS unsigned *)(pqS + waveInBlock * 128u), cands, wallS, (volatile VR_LDS float *)(pqBoxS + (PQ_CACHE ? waveInBlock * (6u * VR_PQ_KEEP) : 0u)), tWall VR_DIAG_PASS);
@@ -761,7 +769,11 @@ VR_TRACE_KERNEL_NAME(const TraceParams p) {
           // geometry hit
           V3 geomNormal;
           if (GEO == 0) {
-            if (PQ_CREDIT && pqCredit) { // (found by the packet query: the candidate's record in LDS, not a dependent global load)
+            if (LATTICE_LANES && pqCredit) {
+              // (uniform disks: every record's normal is record 0's word for word — uniform_disks_kernel compares the
+              //  words — and the frame's VR_F_UD_N are those words: the bits the record would give)
+              geomNormal = mk(wallS[VR_F_UD_N], wallS[VR_F_UD_N + 1], wallS[VR_F_UD_N + 2]);
+            } else if (PQ_CREDIT && pqCredit) { // (found by the packet query: the candidate's record in LDS, not a dependent global load)
               const U4 nr = cands.rec[VR_PQ_NRM + cands.mine];
               geomNormal = mk(__uint_as_float(nr.x), __uint_as_float(nr.y), __uint_as_float(nr.z));
             } else {
@@ -1015,8 +1027,8 @@ VR_TRACE_KERNEL_NAME(const TraceParams p) {
       // evaluated on the same floats) and its ray passes the neighbour test on q.  All lanes
       // crediting q add to ONE address: a single atomic (absorbing: count x unit weight).
       if (ballot64(creditLane)) {
-        // centre of this lane's closest disk
-        const U4 own = cands.rec[creditLane ? cands.mine : 0u];
+        // centre of this lane's closest disk (LATTICE_LANES: cands.mine is one of the lane's four corners, its record in that corner's slot)
+        const U4 own = cands.rec[!creditLane ? 0u : LATTICE_LANES ? (cands.slots >> (8u * cands.mine)) & 0xFFu : cands.mine];
         const float px = __uint_as_float(own.y), py = __uint_as_float(own.z), pz = __uint_as_float(own.w);
         const float dist = p.nbDist, dist2 = dist * dist;
         // General kernels: the lanes crediting candidate c add their fixed-point weights to the wave's LDS sum of c
@@ -1030,7 +1042,57 @@ VR_TRACE_KERNEL_NAME(const TraceParams p) {
             candAcc[k] = 0ull;
           __builtin_amdgcn_wave_barrier();
         }
-        if constexpr (LEAN) {
+        if constexpr (LATTICE_LANES) {
+          // Four corners per lane (pq_hit_lattice_lanes): the `sel` rule of the loop below on each of the lane's own four
+          // disks — the same expression on the same centre bits — and every selected disk's count goes up by one in the
+          // wave's LDS counters, slot by slot (ds_add_u32 without return; integer adds, any order).  Then, as below, lane l
+          // sends slot l's count in ONE wave instruction of atomics on distinct addresses: a slot is a lattice cell, its
+          // disk no other slot's.
+          if (cands.count != 0u) {
+            // A round of the DIRECT form (the window did not fit the wave; wave-uniform): record l holds lane l's four leaf
+            // positions, not a window.  The kernel's per-lane path for unpacketed hits, on the four corners: the closest
+            // disk, and every corner that is its neighbour (the `near` relation of the CSR, on the same centre bits, read
+            // from the records) and passes the neighbour test, each through credit_aggregated.  Integer sums: the fall-back's.
+            const U4 pp = cands.rec[lane];
+            const unsigned ps[4] = {pp.x, pp.y, pp.z, pp.w};
+            const float4 oc = prims[2 * (size_t)(creditLane ? h.pos : 0u)];
+#pragma unroll
+            for (unsigned k = 0; k < 4u; ++k) {
+              DIAG(6);
+              const bool there = ps[k] != VR_LATTICE_EMPTY;
+              const float4 c4 = prims[2 * (size_t)(there ? ps[k] : 0u)];
+              const float dx = oc.x - c4.x, dy = oc.y - c4.y, dz = oc.z - c4.z;
+              const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
+              const bool near = (ax <= dist) & (ay <= dist) & ((p.geoD == 2) | (az <= dist)) & (((dx * dx + dy * dy) + dz * dz) <= dist2);
+              const bool sel = creditLane & there & ((h.pos == ps[k]) | (near & (((cands.local >> k) & 1ull) != 0ull)));
+              credit_aggregated(fluxAcc, sel, ps[k], 1099511627776ull);
+            }
+          } else {
+          VR_LDS unsigned *const cntL = (VR_LDS unsigned *)(cands.rec + VR_PQ_LANE_CNT);
+          cntL[lane] = 0u;
+          __builtin_amdgcn_wave_barrier();
+          // (corner by corner, read, test, add.  The four records read together first and the adds behind them — one trip
+          //  to LDS in place of four — was built and measured: trace 2.43 ms against 2.38 ms this way, twice.)
+#pragma unroll
+          for (unsigned k = 0; k < 4u; ++k) {
+            DIAG(6);
+            const unsigned s = (cands.slots >> (8u * k)) & 0xFFu;
+            const bool there = s != VR_PQ_NO_SLOT;
+            const unsigned sl = there ? s : 0u;
+            const U4 cr = cands.rec[sl];
+            const float dx = px - __uint_as_float(cr.y), dy = py - __uint_as_float(cr.z), dz = pz - __uint_as_float(cr.w);
+            const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
+            const bool near = (ax <= dist) & (ay <= dist) & ((p.geoD == 2) | (az <= dist)) & (((dx * dx + dy * dy) + dz * dz) <= dist2);
+            const bool sel = creditLane & there & ((h.pos == cr.x) | (near & (((cands.local >> k) & 1ull) != 0ull)));
+            if (sel)
+              __hip_atomic_fetch_add(cntL + sl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+          }
+          __builtin_amdgcn_wave_barrier();
+          const unsigned mine = cntL[lane];
+          if (mine)
+            atomicAdd(&fluxAcc[cands.rec[lane].x], (u64)mine * 1099511627776ull); // unit weights: count x 2^40
+          }
+        } else if constexpr (LEAN) {
           // The absorbing flat-scene kernel: unit weights, so candidate c receives (lanes crediting it) x 2^40.  The vote
           // per candidate leaves its count with LANE c, and the lanes then send all the counts in ONE wave instruction of
           // atomics on distinct addresses.  (One single-lane atomic per candidate — behind a branch on the vote, a
