@@ -386,6 +386,58 @@ int vr_map_to_points(vr_context *ctx, const float *values, uint32_t n, const flo
 /* vr_get_flux_device(dataIdx, normType, numNeighbors) into a work buffer, then the map: the flux never leaves the device */
 int vr_get_flux_at_points_device(vr_context *ctx, uint32_t dataIdx, int normType, int numNeighbors, const float *points,
                                  const float *normals, uint32_t m, uint32_t ld, float radius, float *out, void *stream);
+/* ---- closest-hit queries for the caller's rays (not in the reference) ---------------------------------------------------
+ * "Where does this ray hit?" for m rays of the caller against the resident scene: the BVH, the packed primitives and
+ * the side walls with their REFLECTIVE / PERIODIC / IGNORE rules, exactly as an apply() traces them.  The definition:
+ *   A ray is an origin and a direction.  The direction is used as the tracer uses a host ray's (vr_set_host_rays): as it
+ *     stands, NOT normalised — except on a 2-D scene, where a direction with z != 0 has its z dropped and is then
+ *     normalised (rows of 2 floats have z = 0).  So t, and with it dist and tmax, runs in units of the direction's
+ *     length wherever the direction is used as it stands.
+ *   A segment: the closest hit of the ray from its origin among the primitives and the eight wall triangles, from
+ *     parameter tnear on; ties go to the smaller t, then to a wall, then to the lower original primitive id (the
+ *     tracer's rule).  The first segment uses the caller's tnear (pass 1e-4f for the tracer's), every later one 1e-4f.
+ *   A geometry hit ends the ray.  A miss ends the ray.  A wall hit ends the ray unless VR_CAST_FOLLOW_BOUNDARIES is
+ *     set; with it the ray goes on from the wall as the tracer's would — reflected, wrapped to the opposite wall, or
+ *     passed through from its back side — unless the wall is IGNORE (the ray leaves: a miss) or this wall is one more
+ *     than vr_set_max_boundary_hits allows (the ray stops on it).
+ *   dist  the float32 sum of the segments' t, added in segment order.
+ *   tmax >= 0 (INFINITY: none): the result is that of the unbounded cast with every outcome whose dist > tmax turned
+ *     into a miss.  A hit at exactly tmax counts.
+ * Outputs, one row per ray, in the caller's order:
+ *   prim[i]   >= 0: the original id of the primitive hit (what vr_debug_intersect calls primID);
+ *             VR_CAST_MISS: nothing — the ray left the scene, passed an IGNORE wall, or dist exceeds tmax;
+ *             VR_CAST_WALL: the ray stopped on a wall (following is off, or the boundary-hit budget ran out).
+ *   dist[i]   as above; +INFINITY for VR_CAST_MISS.
+ *   hitPoints[3 i ..]  (optional) origin + direction * t of the LAST segment, the tracer's own expression, where the ray
+ *             ended on a primitive or a wall; NaN for VR_CAST_MISS.
+ *   boundaryHits[i]  (optional) the walls the ray was continued at.  With a finite tmax a VR_CAST_MISS reports 0 (such a
+ *             ray may have been stopped before its end); without one it reports the walls passed before the ray left.
+ * Same bits whatever the order the rays are walked in (VR_CAST_SORT_MIN: from that many rays on they are walked in
+ * the Morton order of their origins), and however a set of rays is split over calls.
+ * Refused, the outputs untouched and the context usable, message in vr_last_error:
+ *   VR_E_INVALID  a null origins / directions / prim / dist with m > 0; ld outside {2, 3}, ld == 2 with D == 3; tnear or
+ *                 tmax negative or NaN; a flag bit other than VR_CAST_FOLLOW_BOUNDARIES; (device form) a pointer that is
+ *                 not device memory of ctx's device;
+ *   VR_E_STATE    nothing to cast against: no vr_apply / vr_apply_prepare yet, or the geometry, the boundary conditions,
+ *                 the source direction (the walls and the BVH's child order follow them) or another setting that makes
+ *                 the next prepare redo the scene's configuration changed since; or the scene was built by the host
+ *                 builder (VR_HOST_BUILD).
+ * The call reads what the last prepare left and changes nothing of it: it prepares nothing, a finished apply's result
+ * stays, and a later apply gives the bits it would have given without the cast.  m == 0 is VR_OK after the argument
+ * checks.  Streams: as vr_map_to_points_device — on the context's stream, so ordered with applies; `stream` waits for
+ * the result by an event; no host synchronisation unless a work buffer has to grow.
+ *
+ * origins / directions: DEVICE, m rows of ld (2 or 3; 2 only with D == 2) floats; prim / dist: DEVICE, m words each;
+ * hitPoints: NULL or DEVICE m x 3 floats; boundaryHits: NULL or DEVICE m words */
+#define VR_CAST_FOLLOW_BOUNDARIES 1u
+#define VR_CAST_MISS (-1)
+#define VR_CAST_WALL (-2)
+int vr_cast_rays_device(vr_context *ctx, const float *origins, const float *directions, uint32_t m, uint32_t ld,
+                        float tnear, float tmax, uint32_t flags, int32_t *prim, float *dist, float *hitPoints,
+                        uint32_t *boundaryHits, void *stream);
+/* the same from and to host arrays (m x 3): upload, kernel, download */
+int vr_cast_rays(vr_context *ctx, const float *origins3, const float *directions3, uint32_t m, float tnear, float tmax,
+                 uint32_t flags, int32_t *prim, float *dist, float *hitPoints, uint32_t *boundaryHits);
 /* ---- flux statistics (not in the reference): per-primitive hit counts and the Monte-Carlo error of the flux ----------
  * vr_set_flux_statistics(on != 0): every later apply() keeps, for each particle and alongside its data label 0 (the flux
  * label of every built-in model), two more int64 sums per primitive:

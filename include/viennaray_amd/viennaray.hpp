@@ -886,6 +886,16 @@ public:
   }
 };
 
+/// what Trace::castRays returns, one entry per ray (not in the reference; vr_cast_rays, whose header comment has the
+/// definition): primIDs >= 0 the primitive hit, VR_CAST_MISS (-1) or VR_CAST_WALL (-2); distances +inf and hitPoints NaN
+/// for a miss; boundaryHits the walls the ray was continued at
+template <class NumericType> struct CastResult {
+  std::vector<int> primIDs;
+  std::vector<NumericType> distances;
+  std::vector<Vec3D<NumericType>> hitPoints;
+  std::vector<unsigned> boundaryHits;
+};
+
 // ---- Trace<T,D> ----------------------------------------------------------------------
 template <class NumericType, int D> class Trace {
 public:
@@ -1251,6 +1261,49 @@ public:
                                    (uint32_t)points.size(), radius, raw.data())))
       raw.clear();
     return std::vector<NumericType>(raw.begin(), raw.end());
+  }
+
+  // ---- closest-hit queries for the caller's rays (not in the reference; vr_cast_rays*, whose header comment has the
+  //      definition): each ray traced as apply() traces one — the closest primitive, the side walls followed by their
+  //      boundary conditions up to setMaxBoundaryHits — and reported as primitive id, path length, end point and walls
+  //      passed.  Directions are used as given, not normalised: distances and tmax are in units of the direction's length.
+  //      Needs what apply() leaves behind for the geometry, boundary conditions and source direction in force, and changes
+  //      none of it.
+  /// the host form: false (with the library's message on std::cerr, `out` emptied) if it was refused
+  bool castRays(const std::vector<Vec3D<NumericType>> &origins, const std::vector<Vec3D<NumericType>> &directions,
+                CastResult<NumericType> &out, NumericType tmax = std::numeric_limits<NumericType>::infinity(),
+                bool followBoundaries = true) {
+    const size_t m = origins.size();
+    std::vector<float> o(3 * m), d(3 * directions.size()), dist(m), hit(3 * m);
+    std::vector<int32_t> prim(m);
+    std::vector<uint32_t> bh(m);
+    for (size_t i = 0; i < m; ++i)
+      for (int k = 0; k < 3; ++k)
+        o[3 * i + k] = (float)origins[i][k];
+    for (size_t i = 0; i < directions.size(); ++i)
+      for (int k = 0; k < 3; ++k)
+        d[3 * i + k] = (float)directions[i][k];
+    out = CastResult<NumericType>{};
+    if (!ctx_ || directions.size() != m ||
+        !reported(vr_cast_rays(ctx_, o.data(), d.data(), (uint32_t)m, 1e-4f, (float)tmax,
+                               followBoundaries ? VR_CAST_FOLLOW_BOUNDARIES : 0u, prim.data(), dist.data(), hit.data(), bh.data())))
+      return false;
+    out.primIDs.assign(prim.begin(), prim.end());
+    out.distances.assign(dist.begin(), dist.end());
+    out.boundaryHits.assign(bh.begin(), bh.end());
+    out.hitPoints.resize(m);
+    for (size_t i = 0; i < m; ++i)
+      for (int k = 0; k < 3; ++k)
+        out.hitPoints[i][k] = (NumericType)hit[3 * i + k];
+    return true;
+  }
+  /// dOrg / dDir (m rows of ld = 2 or 3 floats, 2 only with D == 2), dPrim (m int32), dDist (m floats), dHit (nullptr or
+  /// m x 3 floats) and dBh (nullptr or m uint32) are DEVICE memory; flags: VR_CAST_FOLLOW_BOUNDARIES or 0; tnear as the
+  /// tracer's (1e-4); getFluxDevice's stream rules.  false if it was refused.
+  bool castRaysDevice(const float *dOrg, const float *dDir, size_t m, unsigned ld, float tmax, unsigned flags, int32_t *dPrim,
+                      float *dDist, float *dHit = nullptr, uint32_t *dBh = nullptr, void *stream = nullptr) {
+    return ctx_ && reported(vr_cast_rays_device(ctx_, dOrg, dDir, (uint32_t)m, ld, 1e-4f, tmax, flags, dPrim, dDist, dHit, dBh,
+                                                stream));
   }
 
   // ---- flux statistics (not in the reference; vr_set_flux_statistics): per-primitive hit counts and the Monte-Carlo

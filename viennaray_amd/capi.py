@@ -14,6 +14,8 @@ VR_OK, VR_E_INVALID, VR_E_HIP, VR_E_STATE = 0, -1, -2, -3
 VR_NORM_NONE = -1  # vr_get_flux_device: the raw flux
 VR_SOURCE_HAS_WEIGHT = 1  # vr_register_source_model: the model's kHasWeight is true
 VR_SOURCE_PARAMS = 16  # vr_set_source_model: parameters a source model reads
+VR_CAST_FOLLOW_BOUNDARIES = 1  # vr_cast_rays*: follow the side walls as the tracer does
+VR_CAST_MISS, VR_CAST_WALL = -1, -2  # ... its result codes in prim[]
 
 
 class VrError(RuntimeError):
@@ -112,6 +114,9 @@ SIGNATURES = {
     "vr_map_to_points": (C.c_int, [_vp, _fp, C.c_uint32, _fp, _fp, C.c_uint32, C.c_float, _fp]),
     "vr_get_flux_at_points_device": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, C.c_uint32, C.c_uint32,
                                                C.c_float, _vp, _vp]),
+    "vr_cast_rays_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    "vr_cast_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, _i32p, _fp, _fp, _u32p]),
     "vr_get_disk_areas": (C.c_int, [_vp, _fp, C.c_uint32]),
     "vr_get_bounding_box": (C.c_int, [_vp, _fp]),
     "vr_get_source_area": (C.c_float, [_vp]),

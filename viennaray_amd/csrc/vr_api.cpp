@@ -9,6 +9,7 @@
 //   vr_prepare.cpp  vr_apply_prepare and its stages
 //   vr_apply.cpp    vr_apply_launch / _finish, vr_apply, vr_apply_sharded
 //   vr_results.cpp  flux, TraceInfo and data-log getters, normalise, smooth, areas, values at the caller's points
+//   vr_cast_rays.cpp  closest-hit queries for the caller's rays (vr_cast_rays*)
 //   vr_debug.cpp    the vr_debug_* entry points
 #include <algorithm>
 #include <cstring>
@@ -54,6 +55,8 @@ int fail(vr_context *c, int code, const char *msg) {
 //                                 result is ready in stream order.
 //   vr_map_to_points_device,      caller_waits (vr_results.cpp).  The result is ready in stream order; the map's work buffers
 //   vr_get_flux_at_points_device  grow behind host_waits (the first call, a larger m), otherwise nothing waits on the host.
+//   vr_cast_rays_device           caller_waits (vr_cast_rays.cpp).  The results are ready in stream order; the ray sort's
+//                                 buffers (the map's) grow behind host_waits, otherwise nothing waits on the host.
 
 // `p` is device memory of `device` (hipMalloc / a torch tensor's storage; not host, pinned or managed memory)
 static bool is_device_memory_of(const void *p, int device) {

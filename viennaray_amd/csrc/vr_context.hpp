@@ -83,6 +83,10 @@ template <class T> struct DevBuf {
 
 // vr_map_to_points*: from this many query points on they are walked in Morton order (DESIGN.md 8n has the measurement)
 constexpr uint32_t VR_MAP_SORT_MIN = 1u << 19;
+// vr_cast_rays*: from this many rays on they are walked in the Morton order of their origins.  Never, by default: measured
+// (profiles/cast_rays_bench.json), the sort shortens the walk of scattered rays but costs more than it saves
+// at every ray count up to 10^7 on both scenes of the measurement
+constexpr uint32_t VR_CAST_SORT_MIN = 0xFFFFFFFFu;
 
 // Every tuning and experiment switch of the library, read from the environment in ONE place (read_knobs): an apply
 // reads them once, at vr_apply_prepare, into vr_context::knobs.  Unless its line says RESULTS, a switch only moves work
@@ -137,6 +141,7 @@ struct Knobs {
   float hfTile = 4.f;                  // VR_HF_TILE >= 0.25: height-field tile side in grid cells
   // results
   uint32_t mapSortMin = VR_MAP_SORT_MIN; // VR_MAP_SORT_MIN: vr_map_to_points* sorts its queries by Morton key from this many on (0: always, 4294967295: never; read at every call, like VR_HOST_SMOOTH); same bits either way
+  uint32_t castSortMin = VR_CAST_SORT_MIN; // VR_CAST_SORT_MIN: vr_cast_rays* sorts its rays by the Morton key of their origins from this many on (0: always, 4294967295: never, the default; read at every call); same bits either way
   // diagnostics
   bool printLaunches = false;          // VR_PRINT_LAUNCHES (set): trace-launch times and spilled rays on stderr
   bool hostSmooth = false;             // VR_HOST_SMOOTH (set): vr_smooth_flux on the host
@@ -381,6 +386,17 @@ struct vr_context {
   DevBuf<unsigned long long> dMapKeysA, dMapKeysB, dMapVisits;
   DevBuf<uint32_t> dMapValsA, dMapValsB, dMapSortTable, dMapScanTmp;
   DevBuf<float> dMapFlux, dMapValues, dMapPoints, dMapNormals, dMapOut;
+  // vr_cast_rays*: the launch parameters the last prepare_one left (pair nodes, records, wall table and boundary codes of
+  // its launch frame; the shared buffers' addresses are taken when a cast runs), good while castValid and castBuild is the
+  // build count; the walk's overflow word of a cast (its own: an apply's counters are not touched); the host form's staging.
+  // The ray sort shares the map's pairs and tables above: both run on the context's stream, one after the other
+  TraceParams castParams{};
+  bool castValid = false;
+  uint32_t castBuild = 0;
+  DevBuf<unsigned long long> dCastCounters;
+  DevBuf<float> dCastOrg, dCastDir, dCastDist, dCastHit;
+  DevBuf<int32_t> dCastPrim;
+  DevBuf<uint32_t> dCastBh;
   bool areasValid = false;
   DevBuf<uint32_t> dNbOff, dNbIds, dLeafOfOrig;
   DevBuf<uint32_t> dNbTmp; // the one-pass neighbourhood query's fixed-stride lists (build scratch)
@@ -511,6 +527,18 @@ void size_loose(int D, TraceParams &p);
 // vr_apply.cpp
 const ParticleLaunch &current_launch(const vr_context *c);
 TraceParams launch_params(const vr_context *c, const ParticleLaunch &L);
+
+// a work buffer of the map or of a cast grows behind host_waits only (vr_api.cpp: a buffer that moves)
+template <class T> int map_grow(vr_context *c, DevBuf<T> &b, size_t n, bool &waited) {
+  if (b.holds(n))
+    return VR_OK;
+  if (!waited) {
+    VR_TRY(host_waits(c));
+    waited = true;
+  }
+  VR_HIP(c, b.ensure_grow(n));
+  return VR_OK;
+}
 
 inline uint64_t rays_of_apply(const vr_context *c) {
   return c->src.rays_of_apply(c->geo.numPrims, c->numRaysPerPoint, c->numRaysFixed);

@@ -136,6 +136,22 @@ hipError_t launch_map_keys(const float *pts, unsigned m, unsigned ld, int D, con
 hipError_t launch_map_points(const SetupParams &s, const float *values, const float *pts, const float *normals, unsigned m,
                              unsigned ld, float radius, const unsigned *perm, float *out, unsigned long long *visits,
                              hipStream_t st);
+// closest-hit queries for the caller's rays (vr_cast.hip).  Every pointer is device memory.  Ray t of the walk is row
+// perm[t] (nullptr: row t) of org / dir, rows of ld floats (2: z = 0); the results go to that row of prim, dist, hit
+// (nullptr or 3 floats per row) and bh (nullptr or one word per row).  flags: VR_CAST_FOLLOW_BOUNDARIES
+struct CastArgs {
+  const float *org, *dir;
+  const unsigned *perm;
+  int32_t *prim;
+  float *dist, *hit;
+  uint32_t *bh;
+  uint32_t m, ld, groups; // groups = ceil(m / 64)
+  float tnear, tmax;
+  uint32_t flags, maxBoundaryHits;
+};
+// p: the launch parameters of the last prepare (pair nodes, records, wall table, boundary codes, walk stack); slabs: the
+// waves p.walkStack has a slab for.  One launch of at most min(slabs, groups) waves serves any m
+hipError_t launch_cast_rays(const TraceParams &p, int geo, int D, const CastArgs &a, unsigned slabs, hipStream_t st);
 // issue-ceiling microbenchmarks (vr_bench.hip); out: one {cycles, realtime, sink} triple of u64 per wave
 hipError_t launch_issue_kernel(int kind, unsigned blocks, unsigned iters, void *out, hipStream_t s);
 

@@ -91,6 +91,8 @@ Knobs read_knobs() {
     k.hfTile = std::max(0.25f, (float)std::atof(e));
   if (const char *e = std::getenv("VR_MAP_SORT_MIN"))
     k.mapSortMin = (uint32_t)std::min<unsigned long long>(0xFFFFFFFFull, std::strtoull(e, nullptr, 10));
+  if (const char *e = std::getenv("VR_CAST_SORT_MIN"))
+    k.castSortMin = (uint32_t)std::min<unsigned long long>(0xFFFFFFFFull, std::strtoull(e, nullptr, 10));
   k.printLaunches = std::getenv("VR_PRINT_LAUNCHES") != nullptr;
   k.hostSmooth = std::getenv("VR_HOST_SMOOTH") != nullptr;
   if (const char *e = std::getenv("VR_DEBUG_WALK"))

@@ -1039,6 +1039,7 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
 static int prepare_one(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L) {
   VR_HIP(c, hipSetDevice(c->device));
   const auto t0 = std::chrono::steady_clock::now();
+  c->castValid = false; // (a prepare that fails half way leaves nothing for vr_cast_rays* to read)
   const bool redoConfig = c->configDirty || c->geometryDirty;
   if (redoConfig)
     VR_TRY(setup_source_frame(c));
@@ -1073,6 +1074,9 @@ static int prepare_one(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L)
   VR_TRY(fill_trace_params(c, sp, L, S));
   VR_TRY(build_height_field(c, L, S));
   VR_TRY(write_launch_frame(c, L, S));
+  c->castParams = L.params; // what vr_cast_rays* reads of this prepare (vr_cast_rays.cpp)
+  c->castBuild = c->bvhBuilds;
+  c->castValid = true;
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (redoConfig)
     c->buildSeconds = secs; // a cheap re-prepare (new seed / ray range only) keeps the last build time

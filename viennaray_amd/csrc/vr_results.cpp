@@ -19,18 +19,6 @@ static float effective_source_area(const vr_context *c) {
   return c->sourceAreaOverride > 0.f ? c->sourceAreaOverride : c->sourceArea;
 }
 
-// a work buffer of the map grows behind host_waits only (vr_api.cpp: a buffer that moves)
-template <class T> static int map_grow(vr_context *c, DevBuf<T> &b, size_t n, bool &waited) {
-  if (b.holds(n))
-    return VR_OK;
-  if (!waited) {
-    VR_TRY(host_waits(c));
-    waited = true;
-  }
-  VR_HIP(c, b.ensure_grow(n));
-  return VR_OK;
-}
-
 extern "C" {
 
 // ---- results --------------------------------------------------------------------

@@ -38,6 +38,8 @@
 //   vr_post.hip          the results stage: smoothing, areas, flux gather, normalisation, statistics
 //   vr_map.hip           per-primitive values at the caller's points: a range / nearest walk of the resident BVH
 //   vr_setup_common.hpp  private to those six: the ordered-uint trick
+//   vr_cast.hip          closest-hit queries for the caller's rays: the pair walk and the walls, segment after segment
+//   vr_cast.hpp          ... the per-ray bookkeeping of that kernel, plain C++ (the host compiler takes it alone)
 // A run-time module is compiled from this file and what it includes: the Makefile's MODEL_SRCS names those files once.
 #include <hip/hip_runtime.h>
 

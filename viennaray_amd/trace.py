@@ -786,6 +786,82 @@ class Trace:
             C.c_void_p(out.data_ptr()), C.c_void_p(self._torch_stream())))
         return out if dev else out.cpu().numpy()
 
+    # --- closest-hit queries for the caller's rays (vr_cast_rays*, include/viennaray_amd.h has the definition) ---------
+    def castRays(self, origins, directions, tmax=float("inf"), followBoundaries=True, tnear=1e-4, returnPoints=False,
+                 returnBoundaryHits=False):
+        """Where does each ray hit?  m rays against the resident scene, traced as apply() traces a ray: the closest
+        primitive, and with followBoundaries the side walls reflect, wrap or let through as the boundary conditions say,
+        up to setMaxBoundaryHits walls.  Returns (prim, dist[, points][, boundaryHits]):
+          prim  int32: the primitive's index, capi.VR_CAST_MISS (-1: left the scene, passed an IGNORE wall, or further
+                than tmax) or capi.VR_CAST_WALL (-2: stopped on a wall — followBoundaries off, or the budget ran out);
+          dist  float32: the path length, the float32 sum of the segments' t; +inf for a miss;
+          points  [m, 3] float32 (returnPoints): where the ray ended; NaN for a miss;
+          boundaryHits  int32 (returnBoundaryHits): the walls the ray was continued at.
+        Directions are used as given, not normalised (on a 2-D tracer a z component is dropped first, and the direction
+        is then normalised): dist and tmax are in units of the direction's length.  tnear applies to the first segment.
+        float32 contiguous torch tensors on the tracer's device in ([m, 3]; [m, 2] on a 2-D tracer) give tensors out,
+        computed on the device and ordered on the current torch stream (vr_cast_rays_device; any other tensor raises
+        ValueError); host arrays in give numpy arrays out (vr_cast_rays).  Needs what apply() or applyPrepare() leaves
+        behind for the geometry, boundary conditions and source direction in force, and changes none of it."""
+        flags = capi.VR_CAST_FOLLOW_BOUNDARIES if followBoundaries else 0
+        if hasattr(origins, "data_ptr") or hasattr(directions, "data_ptr"):
+            import torch
+            cols = [(None, 2), (None, 3)] if self.D == 2 else [(None, 3)]
+            _check_device_tensor("castRays", "origins", origins, self._device, "torch.float32", cols)
+            _check_device_tensor("castRays", "directions", directions, self._device, "torch.float32",
+                                 [tuple(origins.shape)])
+            m, ld = int(origins.shape[0]), int(origins.shape[1])
+            dev = origins.device
+            prim = torch.empty(m, dtype=torch.int32, device=dev)
+            dist = torch.empty(m, dtype=torch.float32, device=dev)
+            pts = torch.empty((m, 3), dtype=torch.float32, device=dev) if returnPoints else None
+            bh = torch.empty(m, dtype=torch.int32, device=dev) if returnBoundaryHits else None
+            self._check(self._L.vr_cast_rays_device(
+                self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), m, ld, float(tnear),
+                float(tmax), flags, C.c_void_p(prim.data_ptr()), C.c_void_p(dist.data_ptr()),
+                C.c_void_p(pts.data_ptr()) if pts is not None else None,
+                C.c_void_p(bh.data_ptr()) if bh is not None else None, C.c_void_p(self._torch_stream())))
+        else:
+            o = np.asarray(origins, dtype=np.float32)
+            o = o.reshape(-1, o.shape[-1]) if o.ndim == 2 else o.reshape(-1, 3)
+            d = np.asarray(directions, dtype=np.float32).reshape(o.shape)
+            if o.shape[1] == 2:  # 2-D rows: z := 0, as setGeometry does
+                o = np.concatenate([o, np.zeros((o.shape[0], 1), np.float32)], axis=1)
+                d = np.concatenate([d, np.zeros((d.shape[0], 1), np.float32)], axis=1)
+            o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+            m = int(o.shape[0])
+            prim = np.empty(m, dtype=np.int32)
+            dist = np.empty(m, dtype=np.float32)
+            pts = np.empty((m, 3), dtype=np.float32) if returnPoints else None
+            bh = np.empty(m, dtype=np.uint32) if returnBoundaryHits else None
+            self._check(self._L.vr_cast_rays(
+                self._h, _fptr(o), _fptr(d), m, float(tnear), float(tmax), flags,
+                prim.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(dist), _fptr(pts) if pts is not None else None,
+                bh.ctypes.data_as(C.POINTER(C.c_uint32)) if bh is not None else None))
+            bh = bh.view(np.int32) if bh is not None else None
+        return tuple(x for x in (prim, dist, pts, bh) if x is not None)
+
+    def occluded(self, origins, targets):
+        """Is there a primitive on the straight segment from origins[i] to targets[i]?  One boolean per row.  A cast
+        along the unnormalised direction target - origin with tmax = 1 and the walls not followed: t runs in units of
+        that direction's length, so t <= 1 is the segment (a primitive exactly at the target counts).  On a 2-D tracer the
+        z components are left out.  Tensors in, a tensor out; host arrays in, a numpy array out."""
+        if hasattr(origins, "data_ptr") or hasattr(targets, "data_ptr"):
+            cols = [(None, 2), (None, 3)] if self.D == 2 else [(None, 3)]
+            _check_device_tensor("occluded", "origins", origins, self._device, "torch.float32", cols)
+            _check_device_tensor("occluded", "targets", targets, self._device, "torch.float32", [tuple(origins.shape)])
+            o, d = origins, targets - origins
+            if self.D == 2 and o.shape[1] == 3:
+                o, d = o[:, :2].contiguous(), d[:, :2].contiguous()
+        else:
+            o = np.asarray(origins, dtype=np.float32)
+            o = o.reshape(-1, o.shape[-1]) if o.ndim == 2 else o.reshape(-1, 3)
+            d = np.asarray(targets, dtype=np.float32).reshape(o.shape) - o
+            if self.D == 2:
+                o, d = o[:, :2], d[:, :2]
+        prim, _ = self.castRays(o, d, tmax=1.0, followBoundaries=False)
+        return prim >= 0
+
     # --- flux statistics: per-primitive hit counts and the Monte-Carlo error of the flux --------------------------
     def setCalculateFluxError(self, on=True):
         """Keep two more sums per primitive and particle alongside the flux label (vr_set_flux_statistics): the number of
