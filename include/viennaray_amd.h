@@ -438,6 +438,67 @@ int vr_cast_rays_device(vr_context *ctx, const float *origins, const float *dire
 /* the same from and to host arrays (m x 3): upload, kernel, download */
 int vr_cast_rays(vr_context *ctx, const float *origins3, const float *directions3, uint32_t m, float tnear, float tmax,
                  uint32_t flags, int32_t *prim, float *dist, float *hitPoints, uint32_t *boundaryHits);
+/* ---- gather flux (not in the reference): per-primitive direct flux by rays cast FROM the surface -----------------------
+ * From each primitive of a range, `samples` rays into its own hemisphere: what share of the source does it see?  Every
+ * primitive gets the same number of samples whatever its depth; an unoccluded flat surface under a power-1 source comes
+ * out as exactly 1.  With an emission table the same call is one radiosity (Neumann) iteration.  The definition:
+ * Scene   the resident scene of the last vr_apply / vr_apply_prepare (VR_E_STATE as vr_cast_rays_device).  a = the tracing
+ *         axis; u = the unit vector along a FROM the surface TO the source plane.  Primary direction, source kind and
+ *         the particle list play no part.
+ * Primitive i (original id)   origin o_i: the disk centre, or the triangle's centroid rebuilt from the tracer's packed
+ *         record ((v0 + v1 + v2) / 3 with v1 = v0 - e1, v2 = v0 + e2).  Normal m_i: the stored disk normal, or the
+ *         tracer's unit triangle normal, normalised once more.
+ * Sample k = 64 c + j of primitive i   chunk c owns one std::mt19937_64 seeded with tea<3>(i, S + c), S = the context's rng
+ *         seed (vr_set_rng_seed) XOR 0x47415448; sample j takes its outputs 2j and 2j + 1 as r1, r2 (libstdc++'s uniform
+ *         float).  vr_set_use_random_seeds does not apply: the call is a pure function of scene, seed and arguments.
+ *         Direction w, VR_GATHER_NORMAL: D = 3 the cosine law about m_i as the surface source builds it (cos = sqrtf(r2),
+ *           azimuth 2 pi r1, Frisvad basis, normalised); D = 2 the in-plane cosine law, sin(phi) = 2 r1 - 1 about m_i, z = 0
+ *           (r2 is drawn and unused).
+ *         Direction w, VR_GATHER_SOURCE: a sample of the SOURCE's law about u, the tracer's own (cos(theta) = powf(r2,
+ *           1 / (n + 1)), azimuth 2 pi r1, in the source frame; in 2-D z is dropped and the rest normalised).
+ * Walk    as vr_cast_rays with VR_CAST_FOLLOW_BOUNDARIES and tnear 1e-4f from o_i along w: closest hit with the tracer's
+ *         tie rule, walls followed up to vr_set_max_boundary_hits.  A geometry hit ENDS the sample: there is no
+ *         pass-through of a disk's back face as in a forward apply (hitFromBack); it matters only at the open rims of
+ *         disk clouds.
+ * Weight  n = cosinePower, c = u . w of the INITIAL direction (the side walls are parallel to a: following them never
+ *         changes c).  The walls span the box up to the source plane, so a sample that ends as a miss with c > 0 and
+ *         passed no IGNORE wall has crossed the source rectangle:
+ *           reached the source:  NORMAL  g_D(n) c^(n - 1), g_3 = (n + 1) / 2, g_2 = 2 / C_n, C_n = sqrt(pi) Gamma((n + 1) / 2)
+ *                                        / Gamma(n / 2 + 1); for n == 1 exactly g = 1 and no power is taken
+ *                                SOURCE  max(0, m_i . w) / c; a sample with m_i . w <= 0 weighs 0 and is not walked
+ *           hit primitive j on its front side (direction at the hit . m_j < 0), emission given:  emission[j]
+ *           everything else: 0 — a back-side hit, a miss with c <= 0, a sample that left through an IGNORE wall or was
+ *           stopped on a wall by the budget, a front-side hit without a table.
+ * Result  out[i - primFirst] = (float)((double)sum_k q(w_k) / 2^VR_FLUX_FRAC_BITS / samples), q(w) = (int64)(w * 2^
+ *         VR_FLUX_FRAC_BITS + 0.5), the flux accumulators' quantisation.  A weight that is not positive (NaN
+ *         included) counts 0; one above wmax = 2^22 / (samples rounded up to a power of two) counts wmax — 1024 at 4096
+ *         samples — so that no sum can leave an int64 whatever the emission table holds: an emission above wmax is cut
+ *         to it, and so is the rare SOURCE weight with c below m_i . w / wmax.  The sum is an exact int64 sum: the same bits for any launch shape, order, and any
+ *         split of the primitive range over calls.  Units are SOURCE-normalised: an unoccluded primitive facing the
+ *         source between walls that are not IGNORE is 1; emission is in the same units (incoming flux x reflectivity).
+ * Variance per sample: NORMAL w <= g c^(n-1) <= g, so Var <= F (g - F); SOURCE second moment <= (n + 1) / (2 (n - 1)), and
+ * <= 1 / (n - 1) for m_i normal to u — hence VR_GATHER_SOURCE needs n >= 2.
+ * Refused, out untouched and the context usable, message in vr_last_error:
+ *   VR_E_INVALID  samples == 0; primFirst + primCount > vr_num_primitives; cosinePower not finite or < 1; mode not 0 / 1;
+ *                 g_D(cosinePower) > wmax of `samples` (a NORMAL weight, at most g, would be cut: samples x g beyond 2^22);
+ *                 VR_GATHER_SOURCE with cosinePower < 2 or with an emission table; out null with primCount > 0; (device
+ *                 form) a pointer that is not device memory of ctx's device.  primCount == 0 is VR_OK after the checks.
+ *   VR_E_STATE    as vr_cast_rays_device.
+ * Streams, work buffers and "changes nothing of a finished apply; the next apply gives the bits it would have given": as
+ * vr_cast_rays_device.  The int64 sums live in a work buffer of the context that grows on demand.
+ *
+ * emission: NULL or DEVICE, vr_num_primitives floats by original id; out: DEVICE, primCount floats */
+#define VR_GATHER_NORMAL 0u
+#define VR_GATHER_SOURCE 1u
+int vr_gather_flux_device(vr_context *ctx, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                          uint32_t mode, const float *emission, float *out, void *stream);
+/* the same from and to host arrays: upload, kernels, download */
+int vr_gather_flux(vr_context *ctx, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                   uint32_t mode, const float *emission, float *out);
+/* o_i, m_i and the directions of samples first .. first + count - 1 of primitive `prim`, as the gather builds them (host
+ * arrays: 3, 3 and count x 3 floats) */
+int vr_debug_gather_samples(vr_context *ctx, uint32_t prim, uint32_t first, uint32_t count, uint32_t mode,
+                            float cosinePower, float *origin3, float *normal3, float *directions3);
 /* ---- flux statistics (not in the reference): per-primitive hit counts and the Monte-Carlo error of the flux ----------
  * vr_set_flux_statistics(on != 0): every later apply() keeps, for each particle and alongside its data label 0 (the flux
  * label of every built-in model), two more int64 sums per primitive:

@@ -896,6 +896,10 @@ template <class NumericType> struct CastResult {
   std::vector<unsigned> boundaryHits;
 };
 
+/// how Trace::gatherFlux samples (VR_GATHER_*): NORMAL the cosine law about the primitive's normal, SOURCE the source's
+/// power-cosine law about the direction to the source plane (cosinePower >= 2, no emission)
+enum class GatherMode : unsigned { NORMAL = VR_GATHER_NORMAL, SOURCE = VR_GATHER_SOURCE };
+
 // ---- Trace<T,D> ----------------------------------------------------------------------
 template <class NumericType, int D> class Trace {
 public:
@@ -1304,6 +1308,38 @@ public:
                       float *dDist, float *dHit = nullptr, uint32_t *dBh = nullptr, void *stream = nullptr) {
     return ctx_ && reported(vr_cast_rays_device(ctx_, dOrg, dDir, (uint32_t)m, ld, 1e-4f, tmax, flags, dPrim, dDist, dHit, dBh,
                                                 stream));
+  }
+
+  // ---- gather flux (not in the reference; vr_gather_flux*, whose header comment has the definition): the flux every
+  //      primitive receives straight from the source, estimated by `samples` rays cast FROM the primitive into its own
+  //      hemisphere — the same number for every primitive, whatever its depth.  SOURCE-normalised: an unoccluded primitive
+  //      facing the source is 1, exactly so for cosinePower 1.  With `emission` (one value per primitive: incoming flux x
+  //      reflectivity) a sample that lands on another primitive's front brings that value back: one radiosity iteration.
+  //      Needs what apply() leaves behind, like castRays, and changes none of it.
+  /// empty, with the library's message on std::cerr, if it was refused
+  [[nodiscard]] std::vector<NumericType> gatherFlux(unsigned samples, NumericType cosinePower = 1,
+                                                    GatherMode mode = GatherMode::NORMAL,
+                                                    const std::vector<NumericType> *emission = nullptr) {
+    if (!ctx_)
+      return {};
+    const uint32_t n = vr_num_primitives(ctx_);
+    std::vector<float> e, raw(n);
+    if (emission)
+      e.assign(emission->begin(), emission->end());
+    if (emission && e.size() != n) {
+      std::cerr << "viennaray_amd: gatherFlux: emission has " << e.size() << " entries, the scene " << n << " primitives\n";
+      return {};
+    }
+    if (!reported(vr_gather_flux(ctx_, 0u, n, samples, (float)cosinePower, (uint32_t)mode, emission ? e.data() : nullptr, raw.data())))
+      return {};
+    return std::vector<NumericType>(raw.begin(), raw.end());
+  }
+  /// dEmission (nullptr or numPrimitives floats) and dOut (primCount floats) are DEVICE memory; getFluxDevice's stream
+  /// rules.  false if it was refused.
+  bool gatherFluxDevice(unsigned primFirst, unsigned primCount, unsigned samples, float cosinePower, GatherMode mode,
+                        const float *dEmission, float *dOut, void *stream = nullptr) {
+    return ctx_ && reported(vr_gather_flux_device(ctx_, primFirst, primCount, samples, cosinePower, (uint32_t)mode, dEmission,
+                                                  dOut, stream));
   }
 
   // ---- flux statistics (not in the reference; vr_set_flux_statistics): per-primitive hit counts and the Monte-Carlo

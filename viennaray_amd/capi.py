@@ -16,6 +16,8 @@ VR_SOURCE_HAS_WEIGHT = 1  # vr_register_source_model: the model's kHasWeight is 
 VR_SOURCE_PARAMS = 16  # vr_set_source_model: parameters a source model reads
 VR_CAST_FOLLOW_BOUNDARIES = 1  # vr_cast_rays*: follow the side walls as the tracer does
 VR_CAST_MISS, VR_CAST_WALL = -1, -2  # ... its result codes in prim[]
+VR_GATHER_NORMAL, VR_GATHER_SOURCE = 0, 1  # vr_gather_flux*: the sampling mode
+VR_FLUX_FRAC_BITS = 40  # the flux accumulators' (and the gather's) fixed point
 
 
 class VrError(RuntimeError):
@@ -117,6 +119,9 @@ SIGNATURES = {
     "vr_cast_rays_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, _vp, _vp,
                                       _vp, _vp, _vp]),
     "vr_cast_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, _i32p, _fp, _fp, _u32p]),
+    "vr_gather_flux_device": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _vp, _vp, _vp]),
+    "vr_gather_flux": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _fp, _fp]),
+    "vr_debug_gather_samples": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _fp, _fp, _fp]),
     "vr_get_disk_areas": (C.c_int, [_vp, _fp, C.c_uint32]),
     "vr_get_bounding_box": (C.c_int, [_vp, _fp]),
     "vr_get_source_area": (C.c_float, [_vp]),

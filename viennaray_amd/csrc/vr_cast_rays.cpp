@@ -34,12 +34,28 @@ static int cast_refusal(vr_context *c, const char *api, const void *org, const v
 // the cast needs what a prepare leaves behind — the device build's pair nodes and packed records, the wall table and
 // boundary codes of its launch frame, the walk stack — for the geometry and configuration in force (the child order and
 // the walls follow the source direction and the boundary conditions: configDirty).  Modelled on map_state_refusal
-static int cast_state_refusal(vr_context *c, const char *api) {
+// Shared with vr_gather_flux.cpp (what: "cast against" / "gather from"): a gather walks what a cast walks, and a new
+// staleness condition belongs to both
+int resident_scene_refusal(vr_context *c, const char *api, const char *what) {
   if (!c->castValid || !c->haveSetup || c->geometryDirty || c->configDirty || c->castBuild != c->bvhBuilds || c->knobs.hostBuild ||
       c->geo.numPrims == 0 || c->walkStackWaves == 0)
-    return fail(c, VR_E_STATE, (std::string(api) + ": nothing to cast against for the geometry and configuration in force (call "
+    return fail(c, VR_E_STATE, (std::string(api) + ": nothing to " + what + " for the geometry and configuration in force (call "
                                                    "vr_apply or vr_apply_prepare after setting the geometry, the boundary "
                                                    "conditions or the source direction; not with VR_HOST_BUILD)").c_str());
+  return VR_OK;
+}
+static int cast_state_refusal(vr_context *c, const char *api) { return resident_scene_refusal(c, api, "cast against"); }
+
+// the launch parameters of a walk over the resident scene (shared likewise): what the last prepare kept, the walk stack,
+// and the casts' own counter block (the walk's overflow word: an apply's counters stay as they are)
+int resident_scene_params(vr_context *c, bool &waited, TraceParams &p) {
+  if (!c->dCastCounters.p) {
+    VR_TRY(map_grow(c, c->dCastCounters, C_BLOCK, waited));
+    VR_HIP(c, hipMemsetAsync(c->dCastCounters.p, 0, C_BLOCK * 8, c->stream));
+  }
+  p = c->castParams;
+  p.walkStack = c->dWalkStack.p;
+  p.counters = c->dCastCounters.p;
   return VR_OK;
 }
 
@@ -63,13 +79,8 @@ static int cast_on_device(vr_context *c, const float *org, const float *dir, uin
                                 c->dMapScanTmp.p, c->stream));
     perm = c->dMapValsA.p;
   }
-  if (!c->dCastCounters.p) { // (the walk's overflow word of a cast: its own block, so an apply's counters stay as they are)
-    VR_TRY(map_grow(c, c->dCastCounters, C_BLOCK, waited));
-    VR_HIP(c, hipMemsetAsync(c->dCastCounters.p, 0, C_BLOCK * 8, c->stream));
-  }
-  TraceParams p = c->castParams;
-  p.walkStack = c->dWalkStack.p;
-  p.counters = c->dCastCounters.p;
+  TraceParams p;
+  VR_TRY(resident_scene_params(c, waited, p));
   CastArgs a{};
   a.org = org;
   a.dir = dir;

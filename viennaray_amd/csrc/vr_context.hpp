@@ -397,6 +397,10 @@ struct vr_context {
   DevBuf<float> dCastOrg, dCastDir, dCastDist, dCastHit;
   DevBuf<int32_t> dCastPrim;
   DevBuf<uint32_t> dCastBh;
+  // vr_gather_flux*: the int64 sums of one call's range, and the host form's staging (out, emission; the debug entry
+  // point's rows too).  They read castParams like a cast and share its counter block.  Grown behind host_waits only
+  DevBuf<unsigned long long> dGatherAcc;
+  DevBuf<float> dGatherOut, dGatherEmission;
   bool areasValid = false;
   DevBuf<uint32_t> dNbOff, dNbIds, dLeafOfOrig;
   DevBuf<uint32_t> dNbTmp; // the one-pass neighbourhood query's fixed-stride lists (build scratch)
@@ -527,6 +531,10 @@ void size_loose(int D, TraceParams &p);
 // vr_apply.cpp
 const ParticleLaunch &current_launch(const vr_context *c);
 TraceParams launch_params(const vr_context *c, const ParticleLaunch &L);
+
+// vr_cast_rays.cpp: what every walk over the resident scene (a cast, a gather) refuses and starts from
+int resident_scene_refusal(vr_context *c, const char *api, const char *what);
+int resident_scene_params(vr_context *c, bool &waited, TraceParams &p);
 
 // a work buffer of the map or of a cast grows behind host_waits only (vr_api.cpp: a buffer that moves)
 template <class T> int map_grow(vr_context *c, DevBuf<T> &b, size_t n, bool &waited) {

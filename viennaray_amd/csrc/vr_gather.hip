@@ -1,0 +1,259 @@
+// vr_gather.hip — per-primitive direct flux by rays cast FROM the surface (vr_gather_flux_device; include/viennaray_amd.h
+// has the definition, vr_gather.hpp the arithmetic of a sample, vr_gather_flux.cpp the host side).  A translation unit of
+// its own, like vr_cast.hip: nothing an apply() runs is in it.
+//
+//   gather_samples_kernel<GEO, D>  a persistent grid, laid out as cast_rays_kernel: every wave owns one slab of the walk's
+//                                  global stack and its lanes' columns of the block's LDS stack for its whole life; the
+//                                  launcher never starts more waves than there are slabs or work items.
+//   gather_finish_kernel           int64 sums -> floats.
+//   debug_gather_samples_kernel    the origin, the normal and a run of sample directions of ONE primitive
+//                                  (vr_debug_gather_samples): the device functions the first kernel uses.
+//
+// A work item is (a group of 64 primitives) x (one chunk of 64 samples); lane = primitive.  Over the whole scene the
+// groups follow the PACKED (Morton) order, so a wave's origins are neighbours; over a sub-range they follow the caller's
+// ids through leafOfOrig.  The lane seeds its chunk's engine once — mt_first_outputs<2>, then the two streaming cursors of
+// vr_rng.hpp: 128 outputs, inside the streaming tier, no engine state anywhere — and loops over the chunk's samples; the
+// wave votes in pair_walk_lanes as in vr_cast.hip, a lane whose sample has ended (or is not walked at all) taking part
+// with part = false.  The lane's int64 sum of the chunk stays in registers and goes to the primitive's accumulator with
+// one 64-bit vector atomic.  Integer sums: the result has the same bits for any mapping, grid or split of the range.
+// Where (groups x chunks) would leave waves idle — a scene of a few ten thousand primitives at K = 64 — the host cuts
+// every chunk into a.subs runs of 64 / a.subs samples, work items of their own: such a lane seeds the chunk's engine,
+// steps over the draws of the samples before its run (two streaming steps per draw) and walks its run alone.
+#include <hip/hip_runtime.h>
+
+#include "vr_cast.hpp"
+#include "vr_gather.hpp"
+#include "vr_kernels.hpp"
+#include "vr_trace_kernel.hpp"
+
+namespace vr {
+
+constexpr float VR_GATHER_TNEAR = 1e-4f; // tnear of every segment: the tracer's
+
+__device__ __forceinline__ V3 v3(const GVec &v) { return V3{v.x, v.y, v.z}; }
+
+// origin o_i and normal m_i of the primitive at leaf position q, and its original id
+template <int GEO>
+__device__ __forceinline__ void gather_primitive(const float4 *__restrict__ prims, unsigned q, GVec &org, GVec &nrm, unsigned &orig) {
+  if (GEO == 0) {
+    const float4 c4 = prims[2 * (size_t)q], n4 = prims[2 * (size_t)q + 1];
+    org = GVec{c4.x, c4.y, c4.z};
+    nrm = GVec{n4.x, n4.y, n4.z};
+    orig = __float_as_uint(n4.w);
+  } else {
+    const float4 a = prims[4 * (size_t)q], b = prims[4 * (size_t)q + 1], c = prims[4 * (size_t)q + 2], e = prims[4 * (size_t)q + 3];
+    org = gather_tri_centroid(GVec{a.x, a.y, a.z}, GVec{b.x, b.y, b.z}, GVec{c.x, c.y, c.z});
+    nrm = GVec{b.w, c.w, e.w};
+    gather_normalize(nrm);
+    orig = __float_as_uint(a.w);
+  }
+}
+// the normal the tracer tests a hit's side against (trace_kernel: geomNormal)
+template <int GEO> __device__ __forceinline__ V3 gather_hit_normal(const float4 *__restrict__ prims, unsigned q) {
+  if (GEO == 0) {
+    const float4 n4 = prims[2 * (size_t)q + 1];
+    return mk(n4.x, n4.y, n4.z);
+  }
+  return mk(prims[4 * (size_t)q + 1].w, prims[4 * (size_t)q + 2].w, prims[4 * (size_t)q + 3].w);
+}
+
+// the next output of the streaming tier: k < 156 (vr_rng.hpp: rng_next's first branch)
+__device__ __forceinline__ u64 gather_draw(unsigned &k, u64 &lo, u64 &hi) {
+  const u64 lo1 = mt_step(lo, k + 1u);
+  const u64 v = mt_temper(mt_twist(lo, lo1, hi));
+  lo = lo1;
+  hi = mt_step(hi, k + 157u);
+  ++k;
+  return v;
+}
+
+template <int GEO, int D>
+__global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TraceParams p, const GatherArgs a) {
+  __shared__ float wallS[VR_WALL_TABLE];
+  __shared__ unsigned stackS[VR_STACK_LDS * VR_BLOCK]; // [entry][thread of the block]
+  for (unsigned k = threadIdx.x; k < VR_WALL_TABLE; k += blockDim.x)
+    wallS[k] = p.wallTable[k];
+  __syncthreads(); // (the only block-wide point: from here on the waves run on their own)
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned wavesPerBlock = blockDim.x >> 6;
+  const unsigned wave = blockIdx.x * wavesPerBlock + (threadIdx.x >> 6); // < waves <= the slabs of p.walkStack (launch_gather_samples)
+  const unsigned waves = gridDim.x * wavesPerBlock;
+  unsigned *const stackL = stackS + threadIdx.x;
+  unsigned *const stackG = p.walkStack + (size_t)wave * (VR_STACK_GLOBAL * 64u) + lane;
+  const uint4 *__restrict__ pnodes = reinterpret_cast<const uint4 *>(p.pnodes);
+  const float4 *__restrict__ prims = reinterpret_cast<const float4 *>(p.prims);
+  const GatherFrame frame{p.rayDir, p.firstDir, p.secondDir, -p.posNeg};
+  const bool haveEmission = a.emission != nullptr;
+#ifdef VR_DIAG
+  unsigned long long phaseDummy[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tLast = 0ull;
+  unsigned long long *const phaseT = phaseDummy;
+#endif
+  VR_DIAG_DECL
+  const unsigned run = GATHER_CHUNK / a.subs; // samples of a work item: a.subs runs per chunk
+  const u64 perGroup = (u64)a.chunks * a.subs, items = (u64)a.groups * perGroup;
+  for (u64 it = wave; it < items; it += waves) {
+    const unsigned sub = (unsigned)(it % a.subs), chunk = (unsigned)((it / a.subs) % a.chunks);
+    const u64 t = (it / perGroup) * 64u + lane; // index into the range, or (whole scene) the leaf position
+    const bool valid = t < (u64)a.primCount;
+    // ---- the lane's primitive ----
+    GVec o = GVec{0.f, 0.f, 0.f}, m = GVec{0.f, 0.f, 1.f};
+    unsigned orig = 0u;
+    if (valid) {
+      const unsigned q = a.leafOfOrig ? a.leafOfOrig[a.primFirst + (unsigned)t] : (unsigned)t;
+      gather_primitive<GEO>(prims, q, o, m, orig);
+      if (a.leafOfOrig)
+        orig = a.primFirst + (unsigned)t; // (what the record says; taken from the range so that the accumulator's index is in it)
+    }
+    const unsigned count = min(GATHER_CHUNK, a.samples - chunk * GATHER_CHUNK); // samples of this chunk: wave-uniform
+    // ---- the chunk's engine: outputs 0 and 1, then the streaming cursors ----
+    u64 out[2], lo, hi;
+    mt_first_outputs<2>(gather_chunk_seed(orig, a.seed, chunk), out, lo, hi);
+    unsigned k = 2u;
+    float r1 = gather_canon(out[0]), r2 = gather_canon(out[1]);
+    // ---- this item's run of the chunk: samples jFirst .. jEnd - 1 (the draws of those before it are stepped over) ----
+    const unsigned jFirst = sub * run, jEnd = min(count, jFirst + run);
+    for (unsigned j = 0; j < jFirst; ++j) {
+      r1 = gather_canon(gather_draw(k, lo, hi));
+      r2 = gather_canon(gather_draw(k, lo, hi));
+    }
+    long long sum = 0;
+    for (unsigned j = jFirst; j < jEnd; ++j) {
+      const GVec w0 = gather_direction(a.mode, D, r1, r2, m, a.cosinePower, frame);
+      const float c = gather_c(w0, frame), mDotW = gather_dot(m, w0);
+      V3 org = v3(o), rayDirection = v3(w0), dir = project_dir<D>(rayDirection);
+      // (a SOURCE sample facing away from the primitive weighs 0 whatever it meets: not walked)
+      bool active = valid && !(a.mode == GATHER_SOURCE && !(mDotW > 0.f));
+      const bool walked = active;
+      CastState s;
+      cast_begin(s);
+      bool ignored = false;
+      unsigned hitPos = 0u;
+      // ---- segments, until every sample of the wave has ended ----
+      while (ballot64(active)) {
+        HitRec h;
+        hit_clear(h);
+        unsigned node = 0u, sp = 0u;
+        pair_walk_lanes<GEO, VR_STACK_LDS>(p, pnodes, prims, stackL, stackG, active, org, dir, VR_GATHER_TNEAR, h, node, sp, 1u VR_DIAG_PASS);
+        if (active) {
+          hit_walls(p, wallS, org, dir, VR_GATHER_TNEAR, h);
+          const V3 hitPoint = mk(org.x + dir.x * h.t, org.y + dir.y * h.t, org.z + dir.z * h.t);
+          hitPos = h.pos;
+          if (cast_segment(s, h.geom, h.prim, h.t, true, a.maxBoundaryHits, __builtin_huge_valf()) == CAST_AT_WALL) {
+            process_boundary_hit<D>(p, wallS, h.prim, hitPoint, org, rayDirection, dir, active);
+            if (!active) {
+              cast_ignored(s);
+              ignored = true;
+            }
+          } else {
+            active = false;
+          }
+        }
+      }
+      if (walked) {
+        int end = s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL;
+        float emission = 0.f;
+        if (s.prim >= 0) {
+          end = vdot(dir, gather_hit_normal<GEO>(prims, hitPos)) < 0.f ? GATHER_END_FRONT : GATHER_END_BACK;
+          if (end == GATHER_END_FRONT && haveEmission)
+            emission = a.emission[(unsigned)s.prim]; // (the one load of the emission table: at a front-side hit)
+        }
+        sum += gather_q(gather_weight(end, a.mode, a.g, a.cosinePower, c, mDotW, haveEmission, emission), a.wmax);
+      }
+      if (j + 1u < jEnd) { // outputs 2 (j + 1) and 2 (j + 1) + 1
+        r1 = gather_canon(gather_draw(k, lo, hi));
+        r2 = gather_canon(gather_draw(k, lo, hi));
+      }
+    }
+    if (valid && sum != 0)
+      atomicAdd(a.acc + (orig - a.primFirst), (unsigned long long)sum);
+  }
+}
+
+__global__ void gather_finish_kernel(const unsigned long long *acc, unsigned n, unsigned samples, float *out) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+    out[i] = gather_result((long long)acc[i], samples);
+}
+
+// one thread per sample first + k of primitive a.primFirst; thread 0 also writes the origin and the normal
+template <int GEO, int D>
+__global__ void debug_gather_samples_kernel(const TraceParams p, const GatherArgs a, unsigned first, unsigned count, float *origin3,
+                                            float *normal3, float *directions3) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count && i != 0u)
+    return;
+  GVec o, m;
+  unsigned orig;
+  gather_primitive<GEO>(reinterpret_cast<const float4 *>(p.prims), a.leafOfOrig[a.primFirst], o, m, orig);
+  if (i == 0u) {
+    origin3[0] = o.x, origin3[1] = o.y, origin3[2] = o.z;
+    normal3[0] = m.x, normal3[1] = m.y, normal3[2] = m.z;
+  }
+  if (i >= count)
+    return;
+  const u64 sample = (u64)first + i;
+  const unsigned chunk = (unsigned)(sample / GATHER_CHUNK), j = (unsigned)(sample % GATHER_CHUNK);
+  u64 out[2], lo, hi;
+  mt_first_outputs<2>(gather_chunk_seed(orig, a.seed, chunk), out, lo, hi);
+  unsigned k = 2u;
+  float r1 = gather_canon(out[0]), r2 = gather_canon(out[1]);
+  for (unsigned s = 0; s < j; ++s) {
+    r1 = gather_canon(gather_draw(k, lo, hi));
+    r2 = gather_canon(gather_draw(k, lo, hi));
+  }
+  const GatherFrame frame{p.rayDir, p.firstDir, p.secondDir, -p.posNeg};
+  const GVec w = gather_direction(a.mode, D, r1, r2, m, a.cosinePower, frame);
+  directions3[3 * (size_t)i] = w.x, directions3[3 * (size_t)i + 1] = w.y, directions3[3 * (size_t)i + 2] = w.z;
+}
+
+hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned slabs, hipStream_t st) {
+  // no more waves than slabs, no more than work items; whole blocks of VR_BLOCK / 64 waves once there are that many
+  if (a.subs == 0 || a.subs > GATHER_MAX_SUBS || (a.subs & (a.subs - 1u)))
+    return hipErrorInvalidValue;
+  const unsigned long long items = (unsigned long long)a.groups * a.chunks * a.subs;
+  const unsigned perBlock = VR_BLOCK / 64;
+  unsigned waves = items < slabs ? (unsigned)items : slabs;
+  if (waves > perBlock)
+    waves -= waves % perBlock;
+  if (waves == 0)
+    return hipSuccess;
+  const dim3 g(waves > perBlock ? waves / perBlock : 1u), b(waves > perBlock ? (unsigned)VR_BLOCK : waves * 64u);
+  if (geo == 0) {
+    if (D == 2)
+      hipLaunchKernelGGL((gather_samples_kernel<0, 2>), g, b, 0, st, p, a);
+    else
+      hipLaunchKernelGGL((gather_samples_kernel<0, 3>), g, b, 0, st, p, a);
+  } else {
+    if (D == 2)
+      hipLaunchKernelGGL((gather_samples_kernel<1, 2>), g, b, 0, st, p, a);
+    else
+      hipLaunchKernelGGL((gather_samples_kernel<1, 3>), g, b, 0, st, p, a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_finish(const unsigned long long *acc, unsigned n, unsigned samples, float *out, hipStream_t st) {
+  if (n == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(gather_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, acc, n, samples, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_debug_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned first, unsigned count,
+                                       float *origin3, float *normal3, float *directions3, hipStream_t st) {
+  const dim3 g(count ? (count + 63u) / 64u : 1u), b(64); // (count == 0: the origin and the normal alone)
+  if (geo == 0) {
+    if (D == 2)
+      hipLaunchKernelGGL((debug_gather_samples_kernel<0, 2>), g, b, 0, st, p, a, first, count, origin3, normal3, directions3);
+    else
+      hipLaunchKernelGGL((debug_gather_samples_kernel<0, 3>), g, b, 0, st, p, a, first, count, origin3, normal3, directions3);
+  } else {
+    if (D == 2)
+      hipLaunchKernelGGL((debug_gather_samples_kernel<1, 2>), g, b, 0, st, p, a, first, count, origin3, normal3, directions3);
+    else
+      hipLaunchKernelGGL((debug_gather_samples_kernel<1, 3>), g, b, 0, st, p, a, first, count, origin3, normal3, directions3);
+  }
+  return hipGetLastError();
+}
+
+} // namespace vr

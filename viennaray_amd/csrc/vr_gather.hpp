@@ -1,0 +1,204 @@
+// vr_gather.hpp — the arithmetic of gatherFlux (vr_gather.hip: gather_samples_kernel) in plain C++: the host compiler takes
+// this file alone (tests/aux/gather.cpp), the kernel includes it.  What a sample IS lives here — the chunk's engine seed,
+// the direction from (r1, r2, normal, mode, D), the outcome -> weight rule, the constants g_D(n), the quantisation q() and
+// the final division — so that the host program and the device compute the same bits from the same text: sincosf / powf
+// are vr_libm.hpp's on both sides, every other operation is a single IEEE float or double operation in a fixed order
+// (-ffp-contract=off).  include/viennaray_amd.h has the definition this implements.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "vr_libm.hpp"
+
+#if defined(__HIPCC__)
+#define VR_GATHER_FN __host__ __device__ inline __attribute__((always_inline))
+#else
+#define VR_GATHER_FN inline
+#endif
+
+namespace vr {
+
+constexpr uint32_t GATHER_NORMAL = 0;         // VR_GATHER_NORMAL: the cosine law about the primitive's normal
+constexpr uint32_t GATHER_SOURCE = 1;         // VR_GATHER_SOURCE: the source's own power-cosine law about u
+constexpr uint32_t GATHER_SEED_XOR = 0x47415448u; // "GATH": S = rng seed ^ this
+constexpr uint32_t GATHER_CHUNK = 64;         // samples per engine
+constexpr int GATHER_FRAC_BITS = 40;          // VR_FLUX_FRAC_BITS
+constexpr uint32_t GATHER_MAX_SUBS = 16;      // a chunk is walked as at most this many work items (a power of two)
+
+struct GVec {
+  float x, y, z;
+};
+
+// tea<3> (vr_rng.hpp: tea3, the tracer's seed hash)
+VR_GATHER_FN uint32_t gather_tea3(uint32_t v0, uint32_t v1) {
+  uint32_t s0 = 0;
+  for (int n = 0; n < 3; ++n) {
+    s0 += 0x9e3779b9u;
+    v0 += ((v1 << 4) + 0xa341316cu) ^ (v1 + s0) ^ ((v1 >> 5) + 0xc8013ea4u);
+    v1 += ((v0 << 4) + 0xad90777du) ^ (v0 + s0) ^ ((v0 >> 5) + 0x7e95761eu);
+  }
+  return v0;
+}
+// the std::mt19937_64 seed of chunk `chunk` of ORIGINAL primitive `prim`; rngSeed: the context's (vr_set_rng_seed)
+VR_GATHER_FN uint32_t gather_chunk_seed(uint32_t prim, uint32_t rngSeed, uint32_t chunk) {
+  return gather_tea3(prim, (rngSeed ^ GATHER_SEED_XOR) + chunk);
+}
+// libstdc++'s uniform float from one 64-bit engine output (vr_rng.hpp: canon_f32)
+VR_GATHER_FN float gather_canon(uint64_t v) {
+  const float f = (float)v * 5.42101086242752217e-20f; // 2^-64
+  return f >= 1.0f ? 0.99999994f : f;
+}
+
+VR_GATHER_FN float gather_dot(const GVec &a, const GVec &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; } // (vdot)
+VR_GATHER_FN void gather_normalize(GVec &a) { // (vnormalize)
+  const float n = sqrtf(gather_dot(a, a));
+  if (n <= 0.f)
+    return;
+  a.x /= n;
+  a.y /= n;
+  a.z /= n;
+}
+VR_GATHER_FN float gather_axis(const GVec &v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
+VR_GATHER_FN void gather_set_axis(GVec &v, int a, float f) {
+  v.x = a == 0 ? f : v.x;
+  v.y = a == 1 ? f : v.y;
+  v.z = a == 2 ? f : v.z;
+}
+
+// the centroid of a packed triangle record {v0, e1 = v0 - v1, e2 = v2 - v0}: (v0 + v1 + v2) / 3, each vertex rebuilt from
+// the record
+VR_GATHER_FN GVec gather_tri_centroid(const GVec &v0, const GVec &e1, const GVec &e2) {
+  return GVec{((v0.x + (v0.x - e1.x)) + (v0.x + e2.x)) / 3.f, ((v0.y + (v0.y - e1.y)) + (v0.y + e2.y)) / 3.f,
+              ((v0.z + (v0.z - e1.z)) + (v0.z + e2.z)) / 3.f};
+}
+
+// the frame of the source: tracing axis, the two axes of the source plane, and uSign = -posNeg: the sign along the tracing
+// axis of u, the unit vector from the surface TO the source plane
+struct GatherFrame {
+  int rayDir, firstDir, secondDir;
+  float uSign;
+};
+
+// VR_GATHER_NORMAL, D = 3: the cosine law about m (surface_sample, vr_generate.hpp: cosT = sqrtf(r2), Frisvad basis)
+VR_GATHER_FN GVec gather_dir_normal3(float r1, float r2, const GVec &n) {
+  const float cosT = sqrtf(r2), sinT = sqrtf(fmaxf(0.f, 1.f - cosT * cosT));
+  float sinP, cosP;
+  glibc_sincosf((float)(3.14159265358979323846 * 2.f * (double)r1), sinP, cosP);
+  const float s = copysignf(1.f, n.z), a = -1.f / (s + n.z), b = n.x * n.y * a;
+  const GVec t{1.f + s * n.x * n.x * a, s * b, -s * n.x}, b2{b, s + n.y * n.y * a, -n.y};
+  const float ct = cosP * sinT, st = sinP * sinT;
+  GVec d{(n.x * cosT + t.x * ct) + b2.x * st, (n.y * cosT + t.y * ct) + b2.y * st, (n.z * cosT + t.z * ct) + b2.z * st};
+  gather_normalize(d);
+  return d;
+}
+// VR_GATHER_NORMAL, D = 2: the in-plane cosine law about m (pdf cos(phi) / 2 over the half circle): sin(phi) = 2 r1 - 1,
+// the tangent is m turned by +90 degrees in the plane; z = 0
+VR_GATHER_FN GVec gather_dir_normal2(float r1, const GVec &n) {
+  const float sinP = 2.f * r1 - 1.f, cosP = sqrtf(fmaxf(0.f, 1.f - sinP * sinP));
+  GVec d{n.x * cosP - n.y * sinP, n.y * cosP + n.x * sinP, 0.f};
+  gather_normalize(d);
+  return d;
+}
+// VR_GATHER_SOURCE: the source's law about u — cosine_sample (vr_rng.hpp) with the tracer's exponent 1 / (n + 1) in the
+// tracer's source frame (source_sample, vr_generate.hpp), the tracing-axis component towards the source; in 2-D followed
+// by project_dir<2>
+VR_GATHER_FN GVec gather_dir_source(float r1, float r2, float cosinePower, const GatherFrame &f, int D) {
+  const float ee = 1.f / (cosinePower + 1.f);
+  const float ang = (float)(3.14159265358979323846 * 2. * (double)r1);
+  float sinP, cosP;
+  glibc_sincosf(ang, sinP, cosP);
+  const float cosT = glibc_powf(r2, ee);
+  const float sinT = (float)sqrt(1. - (double)(cosT * cosT));
+  GVec d{0.f, 0.f, 0.f};
+  gather_set_axis(d, f.rayDir, f.uSign * cosT);
+  gather_set_axis(d, f.firstDir, cosP * sinT);
+  gather_set_axis(d, f.secondDir, sinP * sinT);
+  if (D == 2 && d.z != 0.f) {
+    d.z = 0.f;
+    gather_normalize(d);
+  }
+  return d;
+}
+VR_GATHER_FN GVec gather_direction(uint32_t mode, int D, float r1, float r2, const GVec &normal, float cosinePower,
+                                   const GatherFrame &f) {
+  if (mode == GATHER_SOURCE)
+    return gather_dir_source(r1, r2, cosinePower, f, D);
+  return D == 2 ? gather_dir_normal2(r1, normal) : gather_dir_normal3(r1, r2, normal);
+}
+// c = u . omega of the initial direction
+VR_GATHER_FN float gather_c(const GVec &dir, const GatherFrame &f) { return f.uSign * gather_axis(dir, f.rayDir); }
+
+// how a sample ended
+enum GatherEnd : int {
+  GATHER_END_MISS = 0,    // left the scene without passing an IGNORE wall
+  GATHER_END_IGNORED = 1, // left through an IGNORE wall
+  GATHER_END_WALL = 2,    // stopped on a wall: the boundary-hit budget ran out
+  GATHER_END_FRONT = 3,   // hit a primitive on its front side (direction . normal < 0)
+  GATHER_END_BACK = 4     // hit a primitive on its back side
+};
+
+// c^e for 0 < c, e > 0 by vr_libm.hpp's powf, which handles neither subnormal arguments nor results below the doubles'
+// range: a c below FLT_MIN counts as 0, and so does a power that is certainly below 2^-160 (an upper bound of log2(c) from
+// the exponent field, and from log2(c) <= (c - 1) / ln 2) — a float 0 either way
+VR_GATHER_FN float gather_pow(float c, float e) {
+  if (c >= 1.f)
+    return 1.f;
+  if (!(c >= 1.17549435e-38f))
+    return 0.f;
+  const float expo = (float)((int)((vr_asuint(c) >> 23) & 0xffu) - 126); // log2(c) < expo
+  if (e * expo < -160.f || e * (c - 1.f) * 1.44269502f < -160.f)
+    return 0.f;
+  return glibc_powf(c, e);
+}
+
+// The outcome -> weight rule.  g: g_D(n); n: cosinePower; c: u . omega of the INITIAL direction; mDotW: m_i . omega of
+// the initial direction; emission: emission[j] of the primitive hit (read only for GATHER_END_FRONT with a table)
+VR_GATHER_FN float gather_weight(int end, uint32_t mode, float g, float n, float c, float mDotW, bool haveEmission,
+                                 float emission) {
+  if (end == GATHER_END_MISS && c > 0.f) {
+    if (mode == GATHER_SOURCE)
+      return mDotW > 0.f ? mDotW / c : 0.f;
+    return n == 1.f ? g : g * gather_pow(c, n - 1.f);
+  }
+  if (end == GATHER_END_FRONT && haveEmission)
+    return emission;
+  return 0.f;
+}
+
+// The largest weight a sample of a call with `samples` samples may count: 2^22 / (samples rounded up to a power of two),
+// so that samples x wmax x 2^40 <= 2^62 — neither a chunk's sum in registers nor a primitive's int64 sum can overflow,
+// whatever the emission table holds.  4096 samples: 1024.  (The entry points refuse a call whose NORMAL weights, at most
+// g_D(n), would be cut: samples x g < 2^22.)
+VR_GATHER_FN float gather_wmax(uint32_t samples) {
+  float w = 4194304.f; // 2^22
+  for (uint64_t p = 1; p < (uint64_t)samples; p *= 2)
+    w *= 0.5f;
+  return w;
+}
+// q(w): the flux accumulators' quantisation (vr_trace_kernel.hpp: weight_fx).  A weight that is not positive (NaN
+// included) counts 0, one above wmax counts wmax
+VR_GATHER_FN int64_t gather_q(float w, float wmax) {
+  if (!(w > 0.f))
+    return 0;
+  const float wc = w > wmax ? wmax : w;
+  return (int64_t)((double)wc * 1099511627776.0 + 0.5);
+}
+// out[i] from the int64 sum of K samples
+VR_GATHER_FN float gather_result(int64_t sum, uint32_t samples) {
+  return (float)((double)sum / 1099511627776.0 / (double)samples);
+}
+
+// g_D(n) (a host function; the kernel takes the float): g_3 = (n + 1) / 2, g_2 = 2 / C_n with
+// C_n = sqrt(pi) Gamma((n + 1) / 2) / Gamma(n / 2 + 1) — the weight of a sample that reaches the source is the ratio of
+// the source's normalised law (n + 1) / (2 pi) c^n (3-D), c^n / C_n (2-D) and the receiver's cosine law c / pi, c / 2 for
+// a receiver facing the source; n == 1 gives exactly 1
+inline float gather_g(float n, int D) {
+  if (n == 1.f)
+    return 1.f;
+  if (D == 3)
+    return (n + 1.f) * 0.5f;
+  const double cn = std::sqrt(3.14159265358979323846) * std::exp(std::lgamma(((double)n + 1.) / 2.) - std::lgamma((double)n / 2. + 1.));
+  return (float)(2. / cn);
+}
+
+} // namespace vr

@@ -152,6 +152,28 @@ struct CastArgs {
 // p: the launch parameters of the last prepare (pair nodes, records, wall table, boundary codes, walk stack); slabs: the
 // waves p.walkStack has a slab for.  One launch of at most min(slabs, groups) waves serves any m
 hipError_t launch_cast_rays(const TraceParams &p, int geo, int D, const CastArgs &a, unsigned slabs, hipStream_t st);
+// per-primitive flux by rays cast from the surface (vr_gather.hip; vr_gather.hpp has the arithmetic).  Every pointer is
+// device memory.  The range is primCount ORIGINAL ids from primFirst; leafOfOrig: their leaf positions (nullptr: the range
+// is the whole scene, walked in leaf order); acc: primCount int64 sums, zeroed by the caller, acc[id - primFirst]
+struct GatherArgs {
+  const uint32_t *leafOfOrig;
+  const float *emission;        // nullptr or [numPrims], by original id
+  unsigned long long *acc;
+  uint32_t primFirst, primCount;
+  uint32_t samples, mode, seed; // seed: the context's rng seed (gather_chunk_seed adds the rest)
+  uint32_t groups, chunks;      // ceil(primCount / 64), ceil(samples / 64)
+  uint32_t maxBoundaryHits;
+  float cosinePower, g;         // g: gather_g(cosinePower, D)
+  float wmax;                   // gather_wmax(samples)
+  uint32_t subs;                // work items per (group, chunk): a power of two <= GATHER_MAX_SUBS, each a run of 64 / subs samples
+};
+// p, slabs: as launch_cast_rays.  One launch of at most min(slabs, groups x chunks x subs) waves
+hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned slabs, hipStream_t st);
+hipError_t launch_gather_finish(const unsigned long long *acc, unsigned n, unsigned samples, float *out, hipStream_t st);
+// origin and normal of original primitive a.primFirst (a.leafOfOrig set) and the directions of its samples first ..
+// first + count - 1
+hipError_t launch_debug_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned first, unsigned count,
+                                       float *origin3, float *normal3, float *directions3, hipStream_t st);
 // issue-ceiling microbenchmarks (vr_bench.hip); out: one {cycles, realtime, sink} triple of u64 per wave
 hipError_t launch_issue_kernel(int kind, unsigned blocks, unsigned iters, void *out, hipStream_t s);
 

@@ -39,6 +39,11 @@ class NormalizationType(enum.IntEnum):  # rayUtil.hpp:38
     MAX = 1
 
 
+class GatherMode(enum.IntEnum):  # Trace.gatherFlux (VR_GATHER_*, include/viennaray_amd.h)
+    NORMAL = 0  # samples follow the cosine law about the primitive's normal
+    SOURCE = 1  # samples follow the source's power-cosine law about the direction to the source plane
+
+
 class TracingDataMergeEnum(enum.IntEnum):  # rayTracingData.hpp:10-14
     SUM = 0
     APPEND = 1
@@ -861,6 +866,59 @@ class Trace:
                 o, d = o[:, :2], d[:, :2]
         prim, _ = self.castRays(o, d, tmax=1.0, followBoundaries=False)
         return prim >= 0
+
+    # --- gather flux: per-primitive direct flux by rays cast from the surface (vr_gather_flux*) -----------------------
+    def gatherFlux(self, samples, cosinePower=1.0, mode=GatherMode.NORMAL, emission=None, primFirst=0, primCount=None,
+                   numpy=False):
+        """The flux each primitive receives straight from the source, estimated by `samples` rays cast from the primitive
+        into its own hemisphere: one float32 per primitive of the range [primFirst, primFirst + primCount) (None: to the
+        last primitive), SOURCE-normalised — an unoccluded primitive facing the source is 1, exactly so for
+        cosinePower 1.  Every primitive gets the same number of samples whatever its depth.
+          mode      GatherMode.NORMAL: samples follow the cosine law about the primitive's normal (any cosinePower >= 1);
+                    GatherMode.SOURCE: they follow the source's power-cosine law (cosinePower >= 2, no emission).
+          emission  one float per primitive of the scene: what a sample that lands on the FRONT of primitive j brings back
+                    (incoming flux x reflectivity, in the same units) — one radiosity iteration.  None: such samples are 0.
+        A pure function of scene, setRngSeed and arguments, with the same bits for any split of the range over calls.
+        A float32 torch tensor on the tracer's device as emission gives a tensor out, on the current torch stream
+        (vr_gather_flux_device); a host array gives a numpy array (vr_gather_flux); with no emission a tensor on the
+        tracer's device comes back unless numpy=True.  Needs what apply() or applyPrepare() leaves behind for the
+        geometry, boundary conditions and source direction in force, and changes none of it
+        (include/viennaray_amd.h has the definition)."""
+        n = int(self._L.vr_num_primitives(self._h))
+        primFirst = int(primFirst)
+        primCount = max(0, n - primFirst) if primCount is None else int(primCount)
+        if primFirst < 0 or primCount < 0 or int(samples) < 0:
+            raise ValueError("gatherFlux: samples, primFirst and primCount must not be negative")
+        host = numpy if emission is None else not hasattr(emission, "data_ptr")
+        if host:
+            e = None
+            if emission is not None:
+                e = np.ascontiguousarray(emission, dtype=np.float32).reshape(-1)
+                if e.size != n:
+                    raise ValueError("gatherFlux: emission has %d entries, the scene %d primitives" % (e.size, n))
+            out = np.empty(primCount, dtype=np.float32)
+            self._check(self._L.vr_gather_flux(self._h, primFirst, primCount, int(samples), float(cosinePower), int(mode),
+                                               _fptr(e) if e is not None else None, _fptr(out)))
+            return out
+        import torch
+        dev = torch.device("cuda", self._device)
+        if emission is not None:
+            _check_device_tensor("gatherFlux", "emission", emission, self._device, "torch.float32", [(n,)])
+        out = torch.empty(primCount, dtype=torch.float32, device=dev)
+        self._check(self._L.vr_gather_flux_device(
+            self._h, primFirst, primCount, int(samples), float(cosinePower), int(mode),
+            C.c_void_p(emission.data_ptr()) if emission is not None else None, C.c_void_p(out.data_ptr()),
+            C.c_void_p(self._torch_stream())))
+        return out
+
+    def debugGatherSamples(self, prim, first, count, mode=GatherMode.NORMAL, cosinePower=1.0):
+        """(origin[3], normal[3], directions[count, 3]) of samples first .. first + count - 1 of primitive `prim`, as
+        gatherFlux builds them (vr_debug_gather_samples)"""
+        o, m = np.empty(3, np.float32), np.empty(3, np.float32)
+        d = np.empty((int(count), 3), np.float32)
+        self._check(self._L.vr_debug_gather_samples(self._h, int(prim), int(first), int(count), int(mode), float(cosinePower),
+                                                    _fptr(o), _fptr(m), _fptr(d)))
+        return o, m, d
 
     # --- flux statistics: per-primitive hit counts and the Monte-Carlo error of the flux --------------------------
     def setCalculateFluxError(self, on=True):
