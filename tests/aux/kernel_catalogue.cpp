@@ -22,7 +22,8 @@ static int failed = 0;
 static_assert(mode_traits(MODE_ABSORB_FLAT_PLANAR_ROUND).base == MODE_ABSORB_FLAT && mode_traits(MODE_SMALL).dynamicLds, "");
 static_assert(trace_kernel_exists(KERNELS_LIBRARY, 3, 0, 0, MODE_ABSORB_FLAT_UNIFORM) &&
                   !trace_kernel_exists(KERNELS_LIBRARY, 2, 0, 0, MODE_ABSORB_FLAT_UNIFORM), "");
-static_assert(VR_NUM_MODES == 11, "");
+static_assert(mode_traits(MODE_ABSORB_FLAT_LATTICE).base == MODE_ABSORB_FLAT && mode_traits(MODE_ABSORB_FLAT_LATTICE_LANES).base == MODE_ABSORB_FLAT, "");
+static_assert(VR_NUM_MODES == 13, "");
 
 // the kernels of `set` under particle ids lo .. hi, printed; returns their number
 static int print_set(const char *name, KernelSet set, int lo, int hi) {
@@ -43,12 +44,15 @@ static int print_set(const char *name, KernelSet set, int lo, int hi) {
 int main() {
   for (int mode = 0; mode < VR_NUM_MODES; ++mode) {
     const ModeTraits t = mode_traits(mode);
-    std::printf("mode %d base %d small %d relief %d resume %d uniform %d planar %d planarRound %d waves %d absorbing %d multiQueue %d "
-                "xcdQueues %d spanBins %d dynamicLds %d\n",
-                mode, t.base, (int)t.small, (int)t.relief, (int)t.resume, (int)t.uniform, (int)t.planar, (int)t.planarRound, t.waves,
+    std::printf("mode %d base %d small %d relief %d resume %d uniform %d planar %d planarRound %d lattice %d latticeLanes %d waves %d absorbing %d "
+                "multiQueue %d xcdQueues %d spanBins %d dynamicLds %d\n",
+                mode, t.base, (int)t.small, (int)t.relief, (int)t.resume, (int)t.uniform, (int)t.planar, (int)t.planarRound,
+                (int)t.lattice, (int)t.latticeLanes, t.waves,
                 (int)t.absorbing, (int)t.multiQueue, (int)t.xcdQueues, t.spanBins, (int)t.dynamicLds);
     CHECK(t.base >= MODE_GENERAL && t.base <= MODE_GENERAL_FLAT);
     CHECK(mode_traits(t.base).base == t.base); // (a base mode is its own)
+    CHECK(!t.latticeLanes || t.lattice);
+    CHECK(!t.lattice || t.planarRound);
     CHECK(!t.planarRound || t.planar);
     CHECK(!t.planar || t.uniform);
     CHECK(!t.uniform || t.base == MODE_ABSORB_FLAT);
@@ -75,7 +79,7 @@ int main() {
     CHECK(!trace_kernel_exists(KERNELS_LIBRARY, 3, 0, -1, mode) && !trace_kernel_exists(KERNELS_LIBRARY, 3, 0, P_EXT_FULL_STATS + 1, mode));
     CHECK(!trace_kernel_exists(KERNELS_MODULE, 3, 0, 0, mode) && !trace_kernel_exists(KERNELS_MODULE, 3, 0, 1, mode));
   }
-  CHECK(print_set("library", KERNELS_LIBRARY, 0, P_EXT_FULL) == 65);
+  CHECK(print_set("library", KERNELS_LIBRARY, 0, P_EXT_FULL) == 67);
   CHECK(print_set("statistics", KERNELS_LIBRARY, P_EXT_STATS, P_EXT_FULL_STATS) == 18);
   CHECK(print_set("module_lean", KERNELS_MODULE, P_EXT, P_EXT) == 10);
   CHECK(print_set("module_full", KERNELS_MODULE, P_EXT_FULL, P_EXT_FULL) == 8);

@@ -1,9 +1,10 @@
 """The catalogue of trace kernels (vr_types.hpp: mode_traits, trace_kernel_exists, trace_kernel_particle) on the host.  No
 GPU: tests/aux/kernel_catalogue.cpp includes vr_types.hpp alone, prints the catalogue and checks (a) the counts of its sets —
-65 kernels in the library's table, 18 in the statistics table, 10 / 8 in a lean / kNeedsFull module — and (c) the invariants
+67 kernels in the library's table, 18 in the statistics table, 10 / 8 in a lean / kNeedsFull module — and (c) the invariants
 of every mode's traits; the same program runs once more built with AddressSanitizer and UndefinedBehaviorSanitizer,
-stand-alone.  Here: (b) the catalogue's mangled names ARE the trace_kernel symbols of the device assembly of vr_trace.hip
-and vr_trace_stats.hip — the table and the code object cannot drift apart — and (d) every (particle, mode) that
+stand-alone.  Here: (b) the catalogue's mangled names ARE the symbols of the device assembly of vr_trace.hip and
+vr_trace_stats.hip whose name starts with trace_kernel, whatever follows — the table and the code object cannot drift apart,
+and no kernel can stand beside the table under a name of its own — and (d) every (particle, mode) that
 vr_prepare.cpp can ask for exists, for the geometry it asks it for, and the catalogue holds no kernel that nothing asks for."""
 import itertools
 import os
@@ -17,10 +18,11 @@ CSRC = os.path.join(ROOT, "viennaray_amd", "csrc")
 SRC = os.path.join(ROOT, "tests", "aux", "kernel_catalogue.cpp")
 FLAGS = ["-O2", "-std=c++17", "-Wall", "-I", CSRC]
 HIPCC = os.environ.get("VR_HIPCC", "/opt/rocm/bin/hipcc")
-COUNTS = {"library": 65, "statistics": 18, "module_lean": 10, "module_full": 8, "module_lean_statistics": 10,
+COUNTS = {"library": 67, "statistics": 18, "module_lean": 10, "module_full": 8, "module_lean_statistics": 10,
           "module_full_statistics": 8}
 # enum TraceMode and the particle ids of vr_types.hpp
-GENERAL, ABSORB_FLAT, ABSORB, GENERAL_FLAT, SMALL, ABSORB_RELIEF, GENERAL_RELIEF, RESUME, UNIFORM, PLANAR, PLANAR_ROUND = range(11)
+GENERAL, ABSORB_FLAT, ABSORB, GENERAL_FLAT, SMALL, ABSORB_RELIEF, GENERAL_RELIEF, RESUME, UNIFORM, PLANAR, PLANAR_ROUND, \
+    LATTICE, LATTICE_LANES = range(13)
 P_DIFFUSE, P_SPECULAR, P_EXT, P_EXT_FULL, P_EXT_STATS, P_EXT_FULL_STATS = range(6)
 
 
@@ -55,16 +57,16 @@ def catalogue(tmp_path_factory):
 def test_counts_and_traits(catalogue):
     sets, traits, served = catalogue
     assert {k: len(v) for k, v in sets.items()} == COUNTS  # (a)
-    assert sorted(traits) == list(range(11)) and len(served) == 11 * 6
+    assert sorted(traits) == list(range(13)) and len(served) == 13 * 6
     for mode, t in traits.items():  # (c), once more from the printed lines
         assert t["base"] in (GENERAL, ABSORB_FLAT, ABSORB, GENERAL_FLAT), (mode, t)
-        assert t["planarRound"] <= t["planar"] <= t["uniform"] <= (t["base"] == ABSORB_FLAT), (mode, t)
+        assert t["latticeLanes"] <= t["lattice"] <= t["planarRound"] <= t["planar"] <= t["uniform"] <= (t["base"] == ABSORB_FLAT), (mode, t)
         assert 1 <= t["waves"] <= 8, (mode, t)
         assert t["multiQueue"] == (t["base"] == GENERAL_FLAT) and t["xcdQueues"] == (mode == GENERAL_FLAT), (mode, t)
         assert t["spanBins"] == (16 if mode == GENERAL else 64 if mode in (GENERAL_FLAT, GENERAL_RELIEF) else 32), (mode, t)
         assert t["dynamicLds"] == (mode == SMALL), (mode, t)
     # the kernel's own defaults (vr_types.hpp: VR_*_WAVES) and the two fixed ones
-    assert [traits[m]["waves"] for m in range(11)] == [6, 8, 7, 6, 5, 8, 6, 6, 8, 8, 8]
+    assert [traits[m]["waves"] for m in range(13)] == [6, 8, 7, 6, 5, 8, 6, 6, 8, 8, 8, 8, 8]
 
 
 def test_catalogue_under_sanitizers(tmp_path):
@@ -86,7 +88,7 @@ def test_catalogue_is_the_code_objects_symbols(catalogue, tmp_path):
     for name, proc in procs.items():
         assert proc.wait() == 0, units[name]
         asm = open(tmp_path / (name + ".s")).read()
-        symbols = re.findall(r"^(_ZN2vr12trace_kernelI\w+):", asm, flags=re.M)
+        symbols = re.findall(r"^(_ZN2vr\d+trace_kernel\w*):", asm, flags=re.M)
         assert len(symbols) == len(set(symbols))
         assert set(symbols) == set(sets[name].values()), sorted(set(symbols) ^ set(sets[name].values()))
         assert len(symbols) == COUNTS[name]
@@ -119,9 +121,15 @@ REQUESTS = [
     # a scene that fits LDS: never absorbing (choose_particle_kernel: `if (S.smallScene) L.absorb = false`)
     ("L.traceMode = MODE_SMALL;", "library", (2, 3), ANY_GEO, range(6), (SMALL,)),
     ("L.traceMode = MODE_SMALL;", "module", (2, 3), ANY_GEO, range(P_EXT, 6), (SMALL,)),
-    # the uniform-disk variants of MODE_ABSORB_FLAT (ParticleLaunch::kernel_mode): 3-D disks, the library's
-    ("trace_kernel_exists(set, D, c->geo.geo, trace_kernel_particle(L.kernelParticle, MODE_ABSORB_FLAT_UNIFORM), MODE_ABSORB_FLAT_UNIFORM);",
-     "library", (3,), DISKS, BUILT_IN, (UNIFORM, PLANAR, PLANAR_ROUND)),
+    # the ladder of MODE_ABSORB_FLAT's variants (absorb_flat_kernel_mode, ParticleLaunch::kernelMode): 3-D disks, the library's.
+    # The first row asks for nothing, it holds what `exists` is: the catalogue's answer; then a rung a row
+    ("const auto exists = [&](int m) { return trace_kernel_exists(set, c->geo.D, c->geo.geo, trace_kernel_particle(L.kernelParticle, m), m); };",
+     "library", (3,), DISKS, BUILT_IN, ()),
+    ("!exists(MODE_ABSORB_FLAT_UNIFORM))", "library", (3,), DISKS, BUILT_IN, (UNIFORM,)),
+    ("!exists(MODE_ABSORB_FLAT_PLANAR))", "library", (3,), DISKS, BUILT_IN, (PLANAR,)),
+    ("!exists(MODE_ABSORB_FLAT_PLANAR_ROUND))", "library", (3,), DISKS, BUILT_IN, (PLANAR_ROUND,)),
+    ("!exists(MODE_ABSORB_FLAT_LATTICE))", "library", (3,), DISKS, BUILT_IN, (LATTICE,)),
+    ("!exists(MODE_ABSORB_FLAT_LATTICE_LANES))", "library", (3,), DISKS, BUILT_IN, (LATTICE_LANES,)),
 ]
 
 

@@ -6,7 +6,8 @@ source-normalised flux).
 
 The scene is that of tests/test_planar_round.py: disks on a 32 x 32 lattice of pitch 1, periodic walls, 200 000 rays, seed
 12345.  DiffuseParticle of sticking 1 runs MODE_ABSORB_FLAT (1) and, under VR_UNIFORM_DISKS / VR_PLANAR_DISKS /
-VR_PLANAR_ROUND, that mode's table entries 8, 9 and 10; VR_ABSORB_CARRY=1 gives MODE_ABSORB (2); sticking 0.5 runs
+VR_PLANAR_ROUND / VR_PLANAR_LATTICE / VR_LATTICE_LANE_TESTS, that mode's table entries 8 to 12 (with every knob at its
+default the scene climbs the whole ladder: tests/test_lattice_lanes.py, scene "a"); VR_ABSORB_CARRY=1 gives MODE_ABSORB (2); sticking 0.5 runs
 MODE_GENERAL_FLAT (3), with VR_GENERAL_FLAT=0 MODE_GENERAL (0), and with flux statistics the statistics table's
 MODE_GENERAL_FLAT.  MODE_SMALL (4) runs on the 2-D trench of tests/golden/data (a few hundred disks).
 
@@ -30,7 +31,8 @@ ORACLE_COUNTERS = ("totalRaysTraced", "nonGeometryHits", "geometryHits", "bounda
 FLUX_ORDER_TOL = 5e-6  # tests/test_planar_round.py
 FLUX_TOL = 1e-4        # ... and on the source-normalised flux
 SEED, RAYS = 12345, 200_000
-KNOBS = ("VR_UNIFORM_DISKS", "VR_PLANAR_DISKS", "VR_PLANAR_ROUND", "VR_ABSORB_CARRY", "VR_GENERAL_FLAT")
+KNOBS = ("VR_UNIFORM_DISKS", "VR_PLANAR_DISKS", "VR_PLANAR_ROUND", "VR_PLANAR_LATTICE", "VR_LATTICE_LANE_TESTS", "VR_ABSORB_CARRY",
+         "VR_GENERAL_FLAT")
 
 # name: (scene, sticking, flux statistics, environment, traceMode(), the mode of the kernel launched)
 CASES = {
@@ -41,7 +43,10 @@ CASES = {
     "small": ("trench2d", 0.5, False, {}, 4, 4),
     "uniform": ("lattice", 1.0, False, {"VR_UNIFORM_DISKS": "1", "VR_PLANAR_DISKS": "0"}, 1, 8),
     "planar": ("lattice", 1.0, False, {"VR_UNIFORM_DISKS": "1", "VR_PLANAR_DISKS": "1", "VR_PLANAR_ROUND": "0"}, 1, 9),
-    "planar_round": ("lattice", 1.0, False, {"VR_UNIFORM_DISKS": "1", "VR_PLANAR_DISKS": "1", "VR_PLANAR_ROUND": "1"}, 1, 10),
+    "planar_round": ("lattice", 1.0, False, {"VR_UNIFORM_DISKS": "1", "VR_PLANAR_DISKS": "1", "VR_PLANAR_ROUND": "1",
+                                             "VR_PLANAR_LATTICE": "0"}, 1, 10),
+    "lattice": ("lattice", 1.0, False, {"VR_PLANAR_LATTICE": "1", "VR_LATTICE_LANE_TESTS": "0"}, 1, 11),
+    "lattice_lanes": ("lattice", 1.0, False, {}, 1, 12),
     "statistics_general_flat": ("lattice", 0.5, True, {}, 3, 3),
     "statistics_small": ("trench2d", 0.5, True, {}, 4, 4),
 }
@@ -81,18 +86,26 @@ def oracle_run(name, sticking):
 
 
 def kernel_mode(trace_mode, err):
-    """the mode of the kernel the launch ran, from the VR_PRINT_LAUNCHES lines (ParticleLaunch::kernel_mode's rule)"""
+    """the mode of the kernel the launch ran (ParticleLaunch::kernelMode), from the VR_PRINT_LAUNCHES line that names it;
+    the five lines of the absorbing flat-scene ladder say the same, rung by rung"""
+    m = re.search(r"\[vr\] kernel: traceMode (\d+), kernel mode (\d+), particle 0", err)
+    assert m, "no kernel line on stderr"
+    assert int(m.group(1)) == trace_mode
+    kernel = int(m.group(2))
     launched = {}
     for key, pattern in (("uniform", r"\[vr\] uniform disks: scene \d, VR_UNIFORM_DISKS \d, launch (\d)"),
                          ("planar", r"\[vr\] planar disks: scene \d, VR_PLANAR_DISKS \d, launch (\d)"),
-                         ("round", r"\[vr\] planar disks: round: VR_PLANAR_ROUND \d, launch (\d)")):
+                         ("round", r"\[vr\] planar disks: round: VR_PLANAR_ROUND \d, launch (\d)"),
+                         ("lattice", r"\[vr\] planar disks: lattice: scene \d, VR_PLANAR_LATTICE \d, launch (\d)"),
+                         ("lanes", r"\[vr\] planar disks: lanes: scene \d, VR_LATTICE_LANE_TESTS \d, launch (\d)")):
         m = re.search(pattern, err)
         assert m, "no %s line on stderr" % key
         launched[key] = int(m.group(1))
-    assert launched["round"] <= launched["planar"] <= launched["uniform"], launched
+    assert launched["lanes"] <= launched["lattice"] <= launched["round"] <= launched["planar"] <= launched["uniform"], launched
     if launched["uniform"]:
         assert trace_mode == 1, (trace_mode, launched)
-    return 10 if launched["round"] else 9 if launched["planar"] else 8 if launched["uniform"] else trace_mode
+    assert kernel == (7 + sum(launched.values()) if launched["uniform"] else trace_mode), (kernel, trace_mode, launched)
+    return kernel
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -1,8 +1,8 @@
 """The lattice cloud's kernel with four disk tests per lane in place of the candidate loop (VR_LATTICE_LANE_TESTS;
-trace_kernel_lattice_lanes, pq_hit_lattice_lanes, vr_planar_lattice.hpp "four corners per lane"): where the disks are small
+MODE_ABSORB_FLAT_LATTICE_LANES, pq_hit_lattice_lanes, vr_planar_lattice.hpp "four corners per lane"): where the disks are small
 enough against the pitch, only the lattice points at the corners of a ray's own cell can accept its plane point, so each
 lane tests those four and credits them through the wave's LDS counters.  Same rays, same acceptance arithmetic, integer
-sums: every scene runs once with VR_LATTICE_LANE_TESTS=0 (trace_kernel_lattice as it was) and once with =1, both with
+sums: every scene runs once with VR_LATTICE_LANE_TESTS=0 (MODE_ABSORB_FLAT_LATTICE as it was) and once with =1, both with
 VR_SMALL_SCENE=0, and the raw float32 and float64 flux arrays are equal element for element, as is every TraceInfo counter;
 each run also goes against the CPU oracle with the bounds of tests/test_planar_lattice.py (counters equal, flux L2-relative
 error <= 5e-6, <= 1e-4 on the source-normalised flux).  The VR_PRINT_LAUNCHES lines say which kernel the launch ran.
@@ -12,7 +12,7 @@ and the tree packet and the walk with it off: the same comparison covers the dir
 
 The scenes: (a) (b) (c) (d) (f) (g) (r) (p) (s) (j) of tests/test_planar_lattice.py, and (k) every centre jittered by up to
 0.12 gridDelta per axis, seeded; (t) a 2 x 3 lattice under 50 000 rays with reflective walls: every corner lookup meets a
-table edge; (h) scene (d) with a 16 x 16 hole: whole windows are empty.  Two scenes keep trace_kernel_lattice and still
+table edge; (h) scene (d) with a 16 x 16 hole: whole windows are empty.  Two scenes keep MODE_ABSORB_FLAT_LATTICE and still
 match the oracle: (o) a 32 x 32 lattice moved so far from the origin that the host rule refuses it — the offset is what
 tests/aux/lattice_lanes.cpp computes from the rule, for this pitch and radius — and (m) that file's cloud with one centre
 0.3 gridDelta off, which is no lattice cloud at all."""
@@ -157,8 +157,8 @@ def test_four_lane_tests_change_no_result(name, monkeypatch, capfd):
     assert off["mode"] == 1 and on["mode"] == 1  # (the flat absorbing kernel; the reported mode stays 1)
     assert off["round"] == (1, 1) and on["round"] == (1, 1)
     assert off["lattice"] == (1, 1, 1) and on["lattice"] == (1, 1, 1)  # a lattice cloud's kernel ran both times ...
-    assert off["lanes"] == (1, 0, 0)  # ... the rule holds; the knob forces the launch's flag false: trace_kernel_lattice
-    assert on["lanes"] == (1, 1, 1)   # ... trace_kernel_lattice_lanes
+    assert off["lanes"] == (1, 0, 0)  # ... the rule holds; the knob forces the launch's flag false: MODE_ABSORB_FLAT_LATTICE
+    assert on["lanes"] == (1, 1, 1)   # ... MODE_ABSORB_FLAT_LATTICE_LANES
     assert on["info"] == off["info"], (off["info"], on["info"])
     i = on["info"]
     assert i["geometryHits"] > 0 and on["f64"].sum() > 0
@@ -178,7 +178,7 @@ def test_far_from_the_origin_the_rule_refuses(monkeypatch, capfd, tmp_path_facto
     print("o: offset", offset, "round", run["round"], "lattice", run["lattice"], "lanes", run["lanes"], run["info"])
     assert run["mode"] == 1
     assert run["lattice"][0] == 1  # still a lattice cloud
-    assert run["lanes"] == (0, 1, 0)  # the knob is on, the rule refuses the scene, the launch keeps trace_kernel_lattice
+    assert run["lanes"] == (0, 1, 0)  # the knob is on, the rule refuses the scene, the launch keeps MODE_ABSORB_FLAT_LATTICE
     assert run["info"]["geometryHits"] > 0
     against_oracle(run, oracle_run("o", offset))
 

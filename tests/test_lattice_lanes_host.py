@@ -1,4 +1,4 @@
-"""Four corners per lane (trace_kernel_lattice_lanes, pq_hit_lattice_lanes; vr_planar_lattice.hpp: lattice_lanes_rule,
+"""Four corners per lane (MODE_ABSORB_FLAT_LATTICE_LANES, pq_hit_lattice_lanes; vr_planar_lattice.hpp: lattice_lanes_rule,
 lattice_lane_corner, lattice_window_slot) on the host.  No GPU: tests/aux/lattice_lanes.cpp tests every disk of a lattice
 against points that are random, on lattice lines and within +-4 ulp of them, at the table's edges and non-finite — pitches 1,
 0.5 and 0.37, phases 0, 0.37 and -499.5, radii at the rule's limit and just below it, centres jittered by up to exactly

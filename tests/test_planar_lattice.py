@@ -1,4 +1,4 @@
-"""The one-point-per-round kernel with its candidates from the lattice table (VR_PLANAR_LATTICE; trace_kernel_lattice,
+"""The one-point-per-round kernel with its candidates from the lattice table (VR_PLANAR_LATTICE; MODE_ABSORB_FLAT_LATTICE,
 pq_hit_lattice, vr_planar_lattice.hpp): where the centres of a planar cloud sit on a square
 lattice of pitch gridDelta, the disks near a round's box are the lattice points of an index window, and the parent's
 ball-box filter on their records leaves the parent's candidates.  That only removes the search: every scene runs once with

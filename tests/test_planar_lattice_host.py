@@ -1,4 +1,4 @@
-"""The lattice table's arithmetic (vr_planar_lattice.hpp; trace_kernel_lattice, pq_hit_lattice) on
+"""The lattice table's arithmetic (vr_planar_lattice.hpp; MODE_ABSORB_FLAT_LATTICE, pq_hit_lattice) on
 the host.  No GPU: tests/aux/planar_lattice.cpp checks against a double-precision brute force that every lattice disk whose
 ball meets a round's padded box lies inside the index window — over random boxes, phases, pitches (also 0.5 and 0.37),
 radii and centres jittered by up to delta / 8 — that the window never leaves the table, that a lane's cell of the window

@@ -150,12 +150,7 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
       VR_HIP(c, hipModuleLaunchKernel(L.userKernel, gridBatch, 1, 1, VR_BLOCK, 1, 1, trace_dynamic_lds(L.traceMode, p.smallBytes), c->stream,
                                       args, nullptr));
     } else if (tight) {
-      if (L.latticeLanes) // (the lattice cloud's kernels: not modes of the table)
-        VR_HIP(c, launch_trace_lattice_lanes(p, gridBatch, c->stream));
-      else if (L.planarLattice)
-        VR_HIP(c, launch_trace_lattice(p, gridBatch, c->stream));
-      else
-        VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.kernel_mode(), gridBatch, c->stream));
+      VR_HIP(c, launch_trace(p, c->geo.D, c->geo.geo, L.kernelParticle, L.kernelMode, gridBatch, c->stream));
     }
     VR_HIP(c, hipEventRecord(k1, c->stream));
     ++traceNo;
@@ -374,23 +369,26 @@ int vr_apply_finish(vr_context *c) {
       const ParticleLaunch &L = c->launches[q];
       const BinGrid &g = L.binGrid;
       const double d = c->geo.gridDelta > 0.f ? (double)c->geo.gridDelta : 1.0;
+      const ModeTraits kernel = mode_traits(L.kernelMode);
       std::fprintf(stderr, "[vr] sort bins: %u (%d x %d cells), VR_BIN_ALIGN %d, aligned %d, cell %.4g x %.4g gridDelta, mean rays per bin %.1f, particle %zu\n",
                    L.params.numBins, g.T1, g.T2, (int)c->knobs.binAlign, g.aligned, g.cell1 / d, g.cell2 / d, g.meanRays, q);
       // (the scene's fact, and whether this launch ran the uniform-disk kernel on it)
       std::fprintf(stderr, "[vr] uniform disks: scene %d, VR_UNIFORM_DISKS %d, launch %d, particle %zu\n", (int)c->uniformDisks,
-                   (int)c->knobs.uniformDisks, (int)L.uniformDisks, q);
+                   (int)c->knobs.uniformDisks, (int)kernel.uniform, q);
       // (launch 1 above: a kernel of the uniform family ran; here: whether it was the planar one)
       std::fprintf(stderr, "[vr] planar disks: scene %d, VR_PLANAR_DISKS %d, launch %d, particle %zu\n", (int)c->planarDisks,
-                   (int)c->knobs.planarDisks, (int)L.planarDisks, q);
+                   (int)c->knobs.planarDisks, (int)kernel.planar, q);
       // (... and whether it was that kernel's one-point-per-round form)
       std::fprintf(stderr, "[vr] planar disks: round: VR_PLANAR_ROUND %d, launch %d, particle %zu\n", (int)c->knobs.planarRound,
-                   (int)L.planarRound, q);
+                   (int)kernel.planarRound, q);
       // (... and whether its candidates came from the lattice table)
       std::fprintf(stderr, "[vr] planar disks: lattice: scene %d, VR_PLANAR_LATTICE %d, launch %d, particle %zu\n", (int)c->planarLattice,
-                   (int)c->knobs.planarLattice, (int)L.planarLattice, q);
+                   (int)c->knobs.planarLattice, (int)kernel.lattice, q);
       // (... and whether each lane tested its own four disks; scene: the host rule alone, lattice_lanes_rule)
       std::fprintf(stderr, "[vr] planar disks: lanes: scene %d, VR_LATTICE_LANE_TESTS %d, launch %d, particle %zu\n",
-                   (int)L.latticeLanesScene, (int)c->knobs.latticeLaneTests, (int)L.latticeLanes, q);
+                   (int)L.latticeLanesScene, (int)c->knobs.latticeLaneTests, (int)kernel.latticeLanes, q);
+      // (... in one word: the mode the launch reports and the kernel of the table it ran)
+      std::fprintf(stderr, "[vr] kernel: traceMode %d, kernel mode %d, particle %zu\n", L.traceMode, L.kernelMode, q);
     }
   const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
   if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)

@@ -124,7 +124,7 @@ struct Knobs {
   bool planarDisks = true;             // VR_PLANAR_DISKS (0: off): ... the planar one of them (off: planar disks run the uniform-disk kernel)
   bool planarRound = true;             // VR_PLANAR_ROUND (0: off): ... in its one-point-per-round form (off: the planar kernel as it was)
   bool planarLattice = true;           // VR_PLANAR_LATTICE (0: off): ... with its candidates from the lattice table where the cloud is a lattice cloud (off: the one-point-per-round kernel as it was)
-  bool latticeLaneTests = true;        // VR_LATTICE_LANE_TESTS (0: off): ... each lane testing the four disks at the corners of its point's cell where the disks are small against the pitch (off: trace_kernel_lattice as it was)
+  bool latticeLaneTests = true;        // VR_LATTICE_LANE_TESTS (0: off): ... each lane testing the four disks at the corners of its point's cell where the disks are small against the pitch (off: MODE_ABSORB_FLAT_LATTICE as it was)
   std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
   std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
   // kernel parameters (TraceParams)
@@ -173,7 +173,7 @@ struct UserModel {
   bool needsFull = false;
   int numState = 0;                     // kStateWords of a stateful model (0: stateless)
   int logRows = 0;                      // kLogRows: rows of the data log its log_data hook writes (0: no hook)
-  std::map<int, hipFunction_t> kernels; // key: D * 100 + geo * 10 + mode
+  std::map<int, hipFunction_t> kernels; // key: module_kernel_key(D, geo, mode), vr_types.hpp
   hipFunction_t gen[2] = {nullptr, nullptr}; // a stateful model's generator (gen_state_kernel), 2-D / 3-D
   // flux statistics: the module's twin with the statistics compiled in (VR_USER_FLUX_STATS), built from the kept text
   // when a statistics-on apply first needs it, under a cache key of its own
@@ -202,30 +202,12 @@ struct ParticleLaunch {
   bool stats = false;    // flux statistics: two companion planes behind its data labels (planes numData, numData + 1)
   unsigned grid = 0;
   int traceMode = MODE_GENERAL, kernelParticle = 0;
-  // every disk of the scene has one normal and one radius (vr_context::uniformDisks), VR_UNIFORM_DISKS is on and the
-  // launch runs the library's 3-D MODE_ABSORB_FLAT kernel: it runs that kernel's uniform-disk variant, with the
-  // normal, the radius and the square-root threshold in its frame (VR_F_UD_*)
-  bool uniformDisks = false;
-  // ... and the scene's disks are planar (vr_context::planarDisks) with VR_PLANAR_DISKS on: the planar variant of that
-  // kernel, the plane's axis and coordinate in the frame as well (VR_F_PD_*).  Only ever set with uniformDisks
-  bool planarDisks = false;
-  // ... with VR_PLANAR_ROUND on: that kernel's one-point-per-round form, its words in the frame as well (VR_F_PR_*).  Only
-  // ever set with planarDisks
-  bool planarRound = false;
-  // ... on a lattice cloud (vr_context::planarLattice) with VR_PLANAR_LATTICE on: that kernel with the round's candidates
-  // from the lattice table, the table's words in the frame as well (VR_F_PL_*).  Only ever set with planarRound.  Not a mode:
-  // the launch takes launch_trace_lattice in place of launch_trace(kernel_mode())
-  bool planarLattice = false;
-  // ... whose disks are small enough against the pitch (lattice_lanes_rule, vr_planar_lattice.hpp) with VR_LATTICE_LANE_TESTS
-  // on: that kernel with four disk tests per lane in place of the candidate loop (launch_trace_lattice_lanes).  Only ever
-  // set with planarLattice
-  bool latticeLanes = false;
-  bool latticeLanesScene = false; // (the rule's verdict on the scene alone, for the VR_PRINT_LAUNCHES line)
-  int kernel_mode() const { // the mode launch_trace takes
-    if (planarRound)
-      return (int)MODE_ABSORB_FLAT_PLANAR_ROUND;
-    return planarDisks ? (int)MODE_ABSORB_FLAT_PLANAR : (uniformDisks ? (int)MODE_ABSORB_FLAT_UNIFORM : traceMode);
-  }
+  // the mode launch_trace takes: traceMode, except on the ladder of the absorbing flat-scene kernel's variants, where a
+  // MODE_ABSORB_FLAT launch runs the highest of modes 8 to 12 that the scene, the knobs and the catalogue allow
+  // (vr_prepare.cpp: absorb_flat_kernel_mode).  mode_traits(kernelMode) says which frame words the launch carries:
+  // uniform VR_F_UD_*, planar VR_F_PD_*, planarRound VR_F_PR_*, lattice VR_F_PL_*
+  int kernelMode = MODE_GENERAL;
+  bool latticeLanesScene = false; // (lattice_lanes_rule's verdict on the scene alone, for the VR_PRINT_LAUNCHES line)
   bool absorb = false;
   bool recExtra = false; // the records' side array (TraceParams::recExtra)
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)

@@ -15,17 +15,18 @@ enum { VR_F_SRC_PLANE = 96, VR_F_RAYDIR = 97, VR_F_FIRSTDIR = 98, VR_F_SECONDDIR
        // the height field over the source plane (HeightFieldParams; NX = 0: none)
        VR_F_HF_LO1 = 118, VR_F_HF_LO2 = 119, VR_F_HF_INVT = 120, VR_F_HF_TILE = 121, VR_F_HF_TOP = 122, VR_F_HF_SIGN = 123,
        VR_F_HF_NX = 124, VR_F_HF_NY = 125, VR_F_HF_PTR_LO = 126, VR_F_HF_PTR_HI = 127,
-       // a launch with uniform disks (ParticleLaunch::uniformDisks; read only by trace_kernel MODE_ABSORB_FLAT_UNIFORM): the
-       // one normal of every disk, their one radius, and the threshold T with radius > sqrtf(x) <=> x < T for every x
+       // a launch with uniform disks (mode_traits(ParticleLaunch::kernelMode).uniform; read only by trace_kernel
+       // MODE_ABSORB_FLAT_UNIFORM and up): the one normal of every disk, their one radius, and the threshold T with
+       // radius > sqrtf(x) <=> x < T for every x
        // (vr_uniform_disks.hpp).  They share the height field's first words: that field is built for launches that go on
        // after a hit, this kernel is an absorbing one (write_launch_frame fills one or the other)
        VR_F_UD_N = VR_F_HF_LO1 /* n.x, n.y, n.z */, VR_F_UD_RADIUS = VR_F_HF_TILE, VR_F_UD_T = VR_F_HF_TOP,
-       // ... whose disks are planar as well (ParticleLaunch::planarDisks; read only by trace_kernel MODE_ABSORB_FLAT_PLANAR):
+       // ... whose disks are planar as well (.planar; read only by trace_kernel MODE_ABSORB_FLAT_PLANAR and up):
        // the axis a of the normal's +-1 (an int) and the one coordinate a of every centre (vr_planar_disks.hpp), in the
        // next words of the same block
        VR_F_PD_AXIS = VR_F_HF_SIGN, VR_F_PD_COORD = VR_F_HF_NX,
-       // ... and that runs the one-point-per-round kernel (ParticleLaunch::planarRound; read only by trace_kernel
-       // MODE_ABSORB_FLAT_PLANAR_ROUND; vr_planar_disks.hpp (2), (3)).  Such a launch has neither a height field nor a
+       // ... and that runs the one-point-per-round kernel (.planarRound; read only by trace_kernel
+       // MODE_ABSORB_FLAT_PLANAR_ROUND and up; vr_planar_disks.hpp (2), (3)).  Such a launch has neither a height field nor a
        // relief field: these are words of theirs.  QLO / QHI: the query box along the plane's axis, coordinate -+ pad;
        // IN: the wall rectangle shrunk by the wall-free margin {lo1, hi1, lo2, hi2} (empty where the rule does not hold);
        // SB: the scene box along the two in-plane axes, widened by the pad {lo1, hi1, lo2, hi2}
@@ -38,8 +39,8 @@ enum { VR_F_SRC_PLANE = 96, VR_F_RAYDIR = 97, VR_F_FIRSTDIR = 98, VR_F_SECONDDIR
        // per-ray state of the batch (float4 per ray, indexed like TraceParams::recExtra) and the material id per ORIGINAL
        // primitive (0: none set).  (Here, not in TraceParams: the library's own kernels stay exactly as they are.)
        VR_F_STATE_LO = 136, VR_F_STATE_HI = 137, VR_F_MAT_LO = 138, VR_F_MAT_HI = 139,
-       // ... a planar-round launch on a lattice cloud (ParticleLaunch::planarLattice; read only by
-       // trace_kernel_lattice; vr_planar_lattice.hpp): the lattice table's address, its n1 x n2 points (ints),
+       // ... a planar-round launch on a lattice cloud (.lattice; read only by trace_kernel MODE_ABSORB_FLAT_LATTICE /
+       // _LATTICE_LANES; vr_planar_lattice.hpp): the lattice table's address, its n1 x n2 points (ints),
        // the lattice's phase along the two in-plane axes, 1 / delta and the window's reach.  Such a launch runs a kernel
        // of the library on a built-in particle: it has neither a stateful model nor a data log, these are words of theirs
        VR_F_PL_PTR_LO = VR_F_STATE_LO, VR_F_PL_PTR_HI = VR_F_STATE_HI, VR_F_PL_N1 = VR_F_MAT_LO, VR_F_PL_N2 = VR_F_MAT_HI,

@@ -13,12 +13,6 @@ hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int 
                         hipStream_t s);
 // resident 256-thread blocks per CU of the trace kernel instantiation (occupancy API)
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes);
-// ... and the one-point-per-round kernel of a lattice cloud (trace_kernel_lattice, vr_trace.hip): 3-D disks, particle id 0
-hipError_t launch_trace_lattice(const TraceParams &p, unsigned grid, hipStream_t s);
-int trace_lattice_blocks_per_cu();
-// ... and its form with four disk tests per lane (trace_kernel_lattice_lanes; ParticleLaunch::latticeLanes)
-hipError_t launch_trace_lattice_lanes(const TraceParams &p, unsigned grid, hipStream_t s);
-int trace_lattice_lanes_blocks_per_cu();
 // ... the kernels with flux statistics (vr_trace_stats.hip; particle: P_EXT_STATS / P_EXT_FULL_STATS); launch_trace and
 // trace_blocks_per_cu forward to them
 hipError_t launch_trace_stats(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid, hipStream_t s);

@@ -233,7 +233,7 @@ static int build_particle_module(vr_context *c, const char *source, int numData,
 }
 
 // the trace kernels of a loaded particle module — the catalogue's KERNELS_MODULE set (vr_types.hpp) under the module's
-// particle id — by their mangled names (key: D * 100 + geo * 10 + mode)
+// particle id — by their mangled names (key: module_kernel_key, vr_types.hpp)
 static int find_trace_kernels(vr_context *c, hipModule_t module, bool full, bool stats, std::map<int, hipFunction_t> &kernels) {
   const int P = stats ? (full ? (int)P_EXT_FULL_STATS : (int)P_EXT_STATS) : (full ? (int)P_EXT_FULL : (int)P_EXT);
   for (int D = 2; D <= 3; ++D)
@@ -246,7 +246,7 @@ static int find_trace_kernels(vr_context *c, hipModule_t module, bool full, bool
         hipFunction_t f = nullptr;
         if (hipModuleGetFunction(&f, module, sym) != hipSuccess || !f)
           return fail(c, VR_E_STATE, (std::string("vr_register_particle_model: kernel missing from the code object: ") + sym).c_str());
-        kernels[D * 100 + geo * 10 + mode] = f;
+        kernels[module_kernel_key(D, geo, mode)] = f;
       }
   return VR_OK;
 }

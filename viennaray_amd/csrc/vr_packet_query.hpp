@@ -551,7 +551,7 @@ __device__ __forceinline__ bool pq_hit_packet(const TraceParams &p, bool part, c
 }
 
 // ---------------------------------------------------------------------------
-// The packet query of a LATTICE cloud (trace_kernel_lattice, vr_trace.hip; vr_planar_lattice.hpp has the table and
+// The packet query of a LATTICE cloud (trace_kernel MODE_ABSORB_FLAT_LATTICE; vr_planar_lattice.hpp has the table and
 // the argument): the contract of pq_hit_packet<... ROUND> — the same inputs, the same h, cd.rec, cd.local, cd.count and
 // cd.mine behind it, false with nothing touched — without the search.  The round's box is the parent's (planar_round_valid,
 // wave_minmax4 of the plane hits, the pad); the disks that can meet it are the lattice points of an index window that
@@ -677,7 +677,7 @@ __device__ __forceinline__ bool pq_hit_lattice(const TraceParams &p, HitRec &h, 
 }
 
 // ---------------------------------------------------------------------------
-// The packet query of a lattice cloud whose disks are small against the pitch (trace_kernel_lattice_lanes, vr_trace.hip;
+// The packet query of a lattice cloud whose disks are small against the pitch (trace_kernel MODE_ABSORB_FLAT_LATTICE_LANES;
 // vr_planar_lattice.hpp "four corners per lane" has the rule and the argument): pq_hit_lattice's box and window, then NO
 // candidate loop and no give-up (a window of more than 64 cells: the direct form, in the function).  Lane l files the disk of window cell l — {leaf position, centre} in record l of
 // the wave's LDS records, its original id in word l behind them, VR_LATTICE_EMPTY where the cell has none — and every lane

@@ -1,5 +1,5 @@
 // vr_planar_lattice.hpp — the lattice table of a planar cloud whose centres sit on a square lattice, and the index window
-// of a packet round in it (trace_kernel_lattice, vr_trace.hip; pq_hit_lattice, vr_packet_query.hpp): the
+// of a packet round in it (trace_kernel MODE_ABSORB_FLAT_LATTICE; pq_hit_lattice, vr_packet_query.hpp): the
 // arithmetic, the host's rule for the table and the per-disk rule of the kernel that fills it.  Plain floats, no HIP type
 // in here: tests/aux/planar_lattice.cpp compiles this file with the host compiler alone.
 //
@@ -94,7 +94,7 @@ VR_HD void lattice_lane_cell(int l, int w, float invW, int &col, int &row) {
   col = l - row * w;
 }
 
-// ==== four corners per lane (trace_kernel_lattice_lanes, vr_trace.hip; pq_hit_lattice_lanes, vr_packet_query.hpp) ==========
+// ==== four corners per lane (trace_kernel MODE_ABSORB_FLAT_LATTICE_LANES; pq_hit_lattice_lanes, vr_packet_query.hpp) ==========
 // A round's point q (vr_planar_disks.hpp (1)) lies in one lattice cell; where the disks are small enough against the pitch,
 // only the lattice points at that cell's four corners can carry a disk that accepts q.  Each lane then tests its own four
 // disks instead of every candidate of the wave's window.

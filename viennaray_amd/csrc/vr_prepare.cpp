@@ -580,6 +580,33 @@ static int size_ray_stream(vr_context *c, ParticleLaunch &L, const PrepareState 
   return VR_OK;
 }
 
+// The kernel of a launch whose traceMode is MODE_ABSORB_FLAT: the ladder of that kernel's variants (vr_types.hpp, modes 8 to
+// 12), climbed as far as it goes.  A rung needs the rung below, its knob, the scene's fact and its kernel in the catalogue
+// (a run-time model's code object has none of them).  Every other launch: its traceMode
+static int absorb_flat_kernel_mode(const vr_context *c, KernelSet set, const ParticleLaunch &L) {
+  const Knobs &K = c->knobs;
+  const auto exists = [&](int m) { return trace_kernel_exists(set, c->geo.D, c->geo.geo, trace_kernel_particle(L.kernelParticle, m), m); };
+  // one normal and one radius for the whole cloud (build_scene: vr_context::uniformDisks)
+  if (L.traceMode != MODE_ABSORB_FLAT || !K.uniformDisks || !c->uniformDisks || !exists(MODE_ABSORB_FLAT_UNIFORM))
+    return L.traceMode;
+  // ... the disks also share a plane normal to a coordinate axis (vr_context::planarDisks)
+  if (!K.planarDisks || !c->planarDisks || !exists(MODE_ABSORB_FLAT_PLANAR))
+    return MODE_ABSORB_FLAT_UNIFORM;
+  // ... that kernel in its one-point-per-round form (vr_planar_disks.hpp (1) - (3))
+  if (!K.planarRound || !exists(MODE_ABSORB_FLAT_PLANAR_ROUND))
+    return MODE_ABSORB_FLAT_PLANAR;
+  // ... with its candidates from the lattice table where the cloud is a lattice cloud (vr_context::planarLattice) whose
+  // windows fit a wave (vr_planar_lattice.hpp)
+  if (!K.planarLattice || !c->planarLattice ||
+      !lattice_window_pays(lattice_reach(c->geo.diskRadius, c->geo.gridDelta, 1e-5f * scene_scale(c)), 1.f / c->geo.gridDelta) ||
+      !exists(MODE_ABSORB_FLAT_LATTICE))
+    return MODE_ABSORB_FLAT_PLANAR_ROUND;
+  // ... each lane testing the four disks at the corners of its point's cell, where no other disk can accept the point
+  if (!K.latticeLaneTests || !L.latticeLanesScene || !exists(MODE_ABSORB_FLAT_LATTICE_LANES))
+    return MODE_ABSORB_FLAT_LATTICE;
+  return MODE_ABSORB_FLAT_LATTICE_LANES;
+}
+
 // launch geometry of the persistent kernels: trace mode, the loose launch of a relief scene, blocks per CU
 static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L, const PrepareState &S) {
   const Knobs &K = c->knobs;
@@ -616,22 +643,9 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
     L.relief = false;
     L.params.reliefCoarse = nullptr;
   }
-  // one normal and one radius for the whole cloud (build_scene: vr_context::uniformDisks): the library's 3-D absorbing
-  // flat-scene kernel in its uniform-disk variant (a run-time model's code object has no such kernel)
-  L.uniformDisks = K.uniformDisks && c->uniformDisks && L.traceMode == MODE_ABSORB_FLAT &&
-                   trace_kernel_exists(set, D, c->geo.geo, trace_kernel_particle(L.kernelParticle, MODE_ABSORB_FLAT_UNIFORM), MODE_ABSORB_FLAT_UNIFORM);
-  // ... in its planar variant where the disks also share a plane normal to a coordinate axis (vr_context::planarDisks)
-  L.planarDisks = L.uniformDisks && K.planarDisks && c->planarDisks;
-  // ... and that one in its one-point-per-round form (vr_planar_disks.hpp (1) - (3))
-  L.planarRound = L.planarDisks && K.planarRound;
-  // ... with its candidates from the lattice table where the cloud is a lattice cloud (vr_context::planarLattice) whose
-  // windows fit a wave (vr_planar_lattice.hpp)
-  L.planarLattice = L.planarRound && K.planarLattice && c->planarLattice &&
-                    lattice_window_pays(lattice_reach(c->geo.diskRadius, c->geo.gridDelta, 1e-5f * scene_scale(c)), 1.f / c->geo.gridDelta);
-  // ... each lane testing the four disks at the corners of its point's cell, where no other disk can accept the point
-  // (vr_planar_lattice.hpp, "four corners per lane")
+  // (the rule's verdict on the scene alone: vr_planar_lattice.hpp, "four corners per lane")
   L.latticeLanesScene = c->planarLattice && lattice_lanes_rule(c->geo.diskRadius, c->geo.gridDelta, lattice_lanes_coord(scene_scale(c), c->geo.gridDelta));
-  L.latticeLanes = L.planarLattice && K.latticeLaneTests && L.latticeLanesScene;
+  L.kernelMode = absorb_flat_kernel_mode(c, set, L);
   int blocks = 1;
   L.userKernel = nullptr;
   L.userGen = nullptr;
@@ -640,7 +654,7 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
     if (L.stats) // (the module's twin with the statistics compiled in: built on first use)
       VR_TRY(ensure_stats_module(c, um));
     const std::map<int, hipFunction_t> &kernels = L.stats ? um.statsKernels : um.kernels; // (find_trace_kernels: the same predicate)
-    auto it = kernels.find(D * 100 + c->geo.geo * 10 + L.traceMode);
+    auto it = kernels.find(module_kernel_key(D, c->geo.geo, L.traceMode));
     if (!trace_kernel_exists(set, D, c->geo.geo, L.kernelParticle, L.traceMode) || it == kernels.end())
       return fail(c, VR_E_STATE, S.stateful ? "stateful particle model: only the general kernels (MODE 0 / 4) carry the state"
                                             : "run-time particle model: no kernel for this geometry / mode in its code object");
@@ -651,12 +665,10 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
       nb = 2;
     blocks = std::max(1, nb);
   } else {
-    for (int m : {L.kernel_mode(), L.relief ? L.looseMode : L.kernel_mode()}) // (launch_trace would refuse it: said here, by name)
+    for (int m : {L.kernelMode, L.relief ? L.looseMode : L.kernelMode}) // (launch_trace would refuse it: said here, by name)
       if (!trace_kernel_exists(set, D, c->geo.geo, trace_kernel_particle(L.kernelParticle, m), m))
         return fail(c, VR_E_STATE, ("no trace kernel for this geometry / particle in MODE " + std::to_string(m)).c_str());
-    blocks = std::max(1, L.latticeLanes    ? trace_lattice_lanes_blocks_per_cu()
-                         : L.planarLattice ? trace_lattice_blocks_per_cu()
-                                           : trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.kernel_mode(), L.params.smallBytes));
+    blocks = std::max(1, trace_blocks_per_cu(D, c->geo.geo, L.kernelParticle, L.kernelMode, L.params.smallBytes));
   }
   // a small launch does better on fewer persistent waves: every wave pays its start-up and its tail.  Best grid on
   // P(100), blocks per CU (tools/small_launch.py): 3 10^5 rays 1, 6 10^5 2, 10^6 3, 2 - 3 10^6 4, 10^7 and more all of
@@ -971,7 +983,8 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
     f[VR_F_HF_NY] = bits(q.ny);
     addr(VR_F_HF_PTR_LO, q.field);
   }
-  if (L.uniformDisks) { // (an absorbing launch: no height field, whose first words these are — vr_frame.hpp, VR_F_UD_*)
+  const ModeTraits kernel = mode_traits(L.kernelMode); // (the launch's kernel: which blocks of the frame it reads)
+  if (kernel.uniform) { // (an absorbing launch: no height field, whose first words these are — vr_frame.hpp, VR_F_UD_*)
     if (S.heightField)
       return fail(c, VR_E_STATE, "a launch with uniform disks has no height field: their frame words are the same");
     float w[4];
@@ -980,11 +993,11 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
       f[VR_F_UD_N + k] = w[k];
     f[VR_F_UD_RADIUS] = w[3];
     f[VR_F_UD_T] = uniform_disk_threshold(w[3]);
-    if (L.planarDisks) { // (VR_F_PD_*: the next words of the same block)
+    if (kernel.planar) { // (VR_F_PD_*: the next words of the same block)
       f[VR_F_PD_AXIS] = bits(c->planarAxis);
       f[VR_F_PD_COORD] = bits((int32_t)c->planarWord);
     }
-    if (L.planarRound) { // (VR_F_PR_*: words of the height field and of the relief field, which such a launch has not)
+    if (kernel.planarRound) { // (VR_F_PR_*: words of the height field and of the relief field, which such a launch has not)
       if (L.relief)
         return fail(c, VR_E_STATE, "a planar-round launch has no relief field: their frame words are the same");
       float ca;
@@ -1000,7 +1013,7 @@ static int write_launch_frame(vr_context *c, const ParticleLaunch &L, const Prep
       f[VR_F_PR_SB + 2] = p.sceneLo[b2] - p.pqPad;
       f[VR_F_PR_SB + 3] = p.sceneHi[b2] + p.pqPad;
     }
-    if (L.planarLattice) { // (VR_F_PL_*: words of a stateful model and of the data log, which such a launch has not)
+    if (kernel.lattice) { // (VR_F_PL_*: words of a stateful model and of the data log, which such a launch has not)
       if (S.stateful || S.logs)
         return fail(c, VR_E_STATE, "a planar-lattice launch has no stateful model: their frame words are the same");
       addr(VR_F_PL_PTR_LO, c->dLattice.p);

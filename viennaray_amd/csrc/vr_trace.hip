@@ -100,52 +100,5 @@ int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBy
   return LibraryKernels::blocks_per_cu(D, geo, particle, mode, smallBytes);
 }
 
-// The one-point-per-round kernel of a LATTICE cloud (ParticleLaunch::planarLattice): trace_kernel<3, 0, 0,
-// MODE_ABSORB_FLAT_PLANAR_ROUND> with the round's candidates from the lattice table (trace_kernel's PLANAR_LATTICE).  Not a mode
-// of the catalogue — a launch of it is a MODE_ABSORB_FLAT_PLANAR_ROUND launch in every other respect — and a kernel of the
-// library alone: it has its own name, launcher and occupancy query here.  Its text is trace_kernel's, compiled a second time
-// under that name with PLANAR_LATTICE on.
-} // namespace vr
-#define VR_TRACE_KERNEL_TWIN trace_kernel_lattice // (the kernel's text once more, under this name: vr_trace_kernel.hpp)
-#include "vr_trace_kernel.hpp"
-#undef VR_TRACE_KERNEL_TWIN
-namespace vr {
-static constexpr StreamKernel VR_LATTICE_KERNEL = trace_kernel_lattice<3, 0, 0, MODE_ABSORB_FLAT_PLANAR_ROUND>;
-
-hipError_t launch_trace_lattice(const TraceParams &p, unsigned grid, hipStream_t s) {
-  hipLaunchKernelGGL(VR_LATTICE_KERNEL, dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  return hipGetLastError();
-}
-
-int trace_lattice_blocks_per_cu() {
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, VR_LATTICE_KERNEL, VR_BLOCK, 0) != hipSuccess)
-    return 2;
-  return nb;
-}
-
-// ... and that kernel with four disk tests per lane in place of the candidate loop (ParticleLaunch::latticeLanes;
-// trace_kernel's LATTICE_LANES, pq_hit_lattice_lanes): the text a third time, under its own name, with both flags on.
-} // namespace vr
-#define VR_TRACE_KERNEL_TWIN trace_kernel_lattice_lanes
-#define VR_TRACE_KERNEL_LANES
-#include "vr_trace_kernel.hpp"
-#undef VR_TRACE_KERNEL_LANES
-#undef VR_TRACE_KERNEL_TWIN
-namespace vr {
-static constexpr StreamKernel VR_LATTICE_LANES_KERNEL = trace_kernel_lattice_lanes<3, 0, 0, MODE_ABSORB_FLAT_PLANAR_ROUND>;
-
-hipError_t launch_trace_lattice_lanes(const TraceParams &p, unsigned grid, hipStream_t s) {
-  hipLaunchKernelGGL(VR_LATTICE_LANES_KERNEL, dim3(grid), dim3(VR_BLOCK), 0, s, p);
-  return hipGetLastError();
-}
-
-int trace_lattice_lanes_blocks_per_cu() {
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, VR_LATTICE_LANES_KERNEL, VR_BLOCK, 0) != hipSuccess)
-    return 2;
-  return nb;
-}
-
 } // namespace vr
 #endif // VR_USER_MODULE

@@ -5,15 +5,7 @@
 //
 // tools/salu_inventory.py finds the phases of a round by the `// ---- ` marker comments of the kernel body: their texts
 // are listed there, and each must stay unique and in order.
-//
-// The kernel's text compiles under a second name as well: a translation unit that includes this file AGAIN with
-// VR_TRACE_KERNEL_TWIN defined as a name gets that text alone — none of the helpers — as a kernel template of that name
-// with PLANAR_LATTICE on, the one variant that is not a mode of the catalogue (vr_trace.hip: trace_kernel_lattice).  Same
-// text, another symbol: trace_kernel itself compiles exactly as if the twin did not exist.  With VR_TRACE_KERNEL_LANES
-// defined beside it the twin also has LATTICE_LANES on (vr_trace.hip: trace_kernel_lattice_lanes).
-#if !defined(VR_TRACE_KERNEL_HPP) || defined(VR_TRACE_KERNEL_TWIN)
-#ifndef VR_TRACE_KERNEL_TWIN
-#define VR_TRACE_KERNEL_HPP
+#pragma once
 #include "vr_device.hpp"
 #include "vr_particles.hpp"
 
@@ -185,30 +177,17 @@ constexpr KernelSet VR_KERNEL_SET = KERNELS_MODULE;
 #else
 constexpr KernelSet VR_KERNEL_SET = KERNELS_LIBRARY;
 #endif
-#define VR_TRACE_KERNEL_NAME trace_kernel
-#else // VR_TRACE_KERNEL_TWIN: the kernel's text alone, under that name
-namespace vr {
-#define VR_TRACE_KERNEL_NAME VR_TRACE_KERNEL_TWIN
-#endif
 template <int D, int GEO, int PARTICLE, int MODE_>
 __global__ __launch_bounds__(VR_BLOCK) __attribute__((amdgpu_num_sgpr(80)))
 __attribute__((amdgpu_waves_per_eu(mode_traits(MODE_).waves, mode_traits(MODE_).waves))) void
-VR_TRACE_KERNEL_NAME(const TraceParams p) {
+trace_kernel(const TraceParams p) {
   constexpr ModeTraits T = mode_traits(MODE_); // (what the mode is: vr_types.hpp)
   constexpr bool SMALL = T.small;
   constexpr bool RELIEF = T.relief;
   constexpr bool RESUME = T.resume;
-#ifdef VR_TRACE_KERNEL_TWIN // (... with the round's candidates from the lattice table: pq_hit_lattice, vr_planar_lattice.hpp)
-  constexpr bool PLANAR_LATTICE = true;
-  static_assert(T.planarRound, "the lattice table serves the one-point-per-round kernel");
-#else
-  constexpr bool PLANAR_LATTICE = false;
-#endif
-#if defined(VR_TRACE_KERNEL_TWIN) && defined(VR_TRACE_KERNEL_LANES) // (... each lane testing the four disks at the corners of its point's cell: pq_hit_lattice_lanes)
-  constexpr bool LATTICE_LANES = true;
-#else
-  constexpr bool LATTICE_LANES = false;
-#endif
+  constexpr bool LATTICE_LANES = T.latticeLanes; // (... each lane testing the four disks at the corners of its point's cell: pq_hit_lattice_lanes)
+  constexpr bool PLANAR_LATTICE = T.lattice; // (... with the round's candidates from the lattice table: pq_hit_lattice, vr_planar_lattice.hpp)
+  static_assert(!T.lattice || T.planarRound, "the lattice table serves the one-point-per-round kernel");
   constexpr bool PLANAR_ROUND = T.planarRound; // (... with the plane hit as the round's one point: pq_hit_packet ROUND, wall-free rounds)
   constexpr bool PLANAR = T.planar; // (... with its PLANAR candidate tests, which are UNIFORM ones)
   constexpr bool UNIFORM = T.uniform; // (MODE_ABSORB_FLAT with pq_hit_packet's UNIFORM candidate tests)
@@ -1389,7 +1368,5 @@ VR_TRACE_KERNEL_NAME(const TraceParams p) {
       atomicAdd(&p.counters[i], s);
   }
 }
-#undef VR_TRACE_KERNEL_NAME
 
 } // namespace vr
-#endif // !VR_TRACE_KERNEL_HPP || VR_TRACE_KERNEL_TWIN

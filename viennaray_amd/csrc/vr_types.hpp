@@ -309,18 +309,23 @@ enum TraceMode : int {
   MODE_RESUME = 7,         // MODE_GENERAL over those loose bins that also resumes the rays of MODE_GENERAL_RELIEF's spill
                            // queue (TraceParams::spillRec)
   MODE_ABSORB_FLAT_UNIFORM = 8, // MODE_ABSORB_FLAT's kernel for a launch whose disks all have one normal and one radius
-                           // (ParticleLaunch::uniformDisks; 3-D disks only): the per-ray terms of the candidate tests once
+                           // (vr_context::uniformDisks; 3-D disks only): the per-ray terms of the candidate tests once
                            // per round (pq_hit_packet UNIFORM).  A kernel of the library's table, never a launch's
-                           // traceMode: that stays MODE_ABSORB_FLAT (ParticleLaunch::kernel_mode)
-  MODE_ABSORB_FLAT_PLANAR = 9, // ... whose disks also share a plane normal to a coordinate axis (ParticleLaunch::planarDisks):
+                           // traceMode: that stays MODE_ABSORB_FLAT (ParticleLaunch::kernelMode)
+  MODE_ABSORB_FLAT_PLANAR = 9, // ... whose disks also share a plane normal to a coordinate axis (vr_context::planarDisks):
                            // one plane hit per ray and round, a distance per candidate (pq_hit_packet PLANAR).  Like
                            // MODE_ABSORB_FLAT_UNIFORM a kernel of the table, never a launch's traceMode
-  MODE_ABSORB_FLAT_PLANAR_ROUND = 10 // ... with that plane hit as the round's one point (ParticleLaunch::planarRound): both
-                           // candidate tests from it, the query's box around it, no wall test in a round whose rays
-                           // start and land well inside the walls (pq_hit_packet ROUND, vr_planar_disks.hpp).  Likewise
-                           // a kernel of the table alone
+  MODE_ABSORB_FLAT_PLANAR_ROUND = 10, // ... with that plane hit as the round's one point: both candidate tests from it, the
+                           // query's box around it, no wall test in a round whose rays start and land well inside the
+                           // walls (pq_hit_packet ROUND, vr_planar_disks.hpp).  Likewise a kernel of the table alone
+  MODE_ABSORB_FLAT_LATTICE = 11, // ... on a lattice cloud (vr_context::planarLattice): the round's candidates from the lattice
+                           // table, not the tree (pq_hit_lattice, vr_planar_lattice.hpp).  A kernel of the table, never a
+                           // launch's traceMode
+  MODE_ABSORB_FLAT_LATTICE_LANES = 12 // ... whose disks are small against the pitch (lattice_lanes_rule): four disk tests per
+                           // lane in place of the candidate loop (pq_hit_lattice_lanes).  A kernel of the table, never a
+                           // launch's traceMode
 };
-constexpr int VR_NUM_MODES = MODE_ABSORB_FLAT_PLANAR_ROUND + 1;
+constexpr int VR_NUM_MODES = MODE_ABSORB_FLAT_LATTICE_LANES + 1;
 
 // Waves per SIMD of the trace kernels (tuning knobs: a -DVR_..._WAVES=n build overrides one)
 #ifndef VR_GENERAL_WAVES
@@ -342,6 +347,7 @@ struct ModeTraits {
   int base = -1; // (-1: not a TraceMode)
   bool small = false, relief = false, resume = false;
   bool uniform = false, planar = false, planarRound = false; // pq_hit_packet UNIFORM / PLANAR / ROUND: each implies the one before
+  bool lattice = false, latticeLanes = false; // ... pq_hit_lattice, pq_hit_lattice_lanes in its place: each implies the one before too
   int waves = 0; // waves per SIMD (amdgpu_waves_per_eu)
   // the host's view
   bool absorbing = false;  // nothing after the first hit is observable: one instantiation, particle id 0, serves every particle
@@ -357,6 +363,7 @@ constexpr ModeTraits make_mode_traits(int mode, int base, int waves, int spanBin
   t.relief = relief;
   t.resume = mode == MODE_RESUME;
   t.uniform = variant >= 1, t.planar = variant >= 2, t.planarRound = variant >= 3;
+  t.lattice = variant >= 4, t.latticeLanes = variant >= 5;
   t.waves = waves;
   t.absorbing = base == MODE_ABSORB_FLAT || base == MODE_ABSORB;
   t.multiQueue = base == MODE_GENERAL_FLAT;
@@ -378,6 +385,8 @@ constexpr ModeTraits mode_traits(int mode) {
   case MODE_ABSORB_FLAT_UNIFORM:      return make_mode_traits(mode, MODE_ABSORB_FLAT,  8,                32, 1);
   case MODE_ABSORB_FLAT_PLANAR:       return make_mode_traits(mode, MODE_ABSORB_FLAT,  8,                32, 2);
   case MODE_ABSORB_FLAT_PLANAR_ROUND: return make_mode_traits(mode, MODE_ABSORB_FLAT,  8,                32, 3);
+  case MODE_ABSORB_FLAT_LATTICE:      return make_mode_traits(mode, MODE_ABSORB_FLAT,  8,                32, 4);
+  case MODE_ABSORB_FLAT_LATTICE_LANES: return make_mode_traits(mode, MODE_ABSORB_FLAT, 8,                32, 5);
   }
   return ModeTraits{};
 }
@@ -411,6 +420,8 @@ constexpr bool trace_kernel_exists(KernelSet set, int D, int geo, int particle, 
     return true;
   return set == KERNELS_LIBRARY && particle < P_EXT_STATS; // MODE_GENERAL_RELIEF, MODE_RESUME
 }
+// the key a loaded module's kernels are kept under (UserModel::kernels): one number per (D, geo, mode)
+constexpr int module_kernel_key(int D, int geo, int mode) { return ((D - 2) * 2 + geo) * VR_NUM_MODES + mode; }
 
 // The generator of a launch.  vr_prepare.cpp records one per launch from the source in force (RaySource::generator,
 // vr_source.hpp); 0 - 4 are the library's own, in the order of vr_trace.hip's table (launch_gen takes one of these).
