@@ -499,6 +499,62 @@ int vr_gather_flux(vr_context *ctx, uint32_t primFirst, uint32_t primCount, uint
  * arrays: 3, 3 and count x 3 floats) */
 int vr_debug_gather_samples(vr_context *ctx, uint32_t prim, uint32_t first, uint32_t count, uint32_t mode,
                             float cosinePower, float *origin3, float *normal3, float *directions3);
+/* ---- radiosity solve (not in the reference): the steady-state flux of a diffusely re-emitting species ------------------
+ * vr_gather_flux with an emission table is one radiosity iteration, and its walks are a constant of the scene.  These
+ * calls record them once — a link table — and iterate over the table on the device without walking again.
+ * Scene, seed, sample k of primitive i, its direction, its walk and "front side" are exactly those of vr_gather_flux in
+ * VR_GATHER_NORMAL mode over the whole scene (primFirst = 0, primCount = vr_num_primitives).
+ * Link table for (samples = K, cosinePower = n), per primitive i:
+ *   direct[i]   = sum_k q(w_k) over the samples that reached the source: the int64 sum of a vr_gather_flux call without
+ *                 emission.
+ *   link[i][k]  = the original id j of the primitive sample k hit on its front side; -1 for everything else — a
+ *                 back-side hit, a miss with c <= 0, a sample that left through an IGNORE wall or was stopped by the wall
+ *                 budget, and a sample that reached the source.
+ * One iteration with emission table e (float32 per primitive):
+ *   G(e)[i] = result(direct[i] + sum_{k: link >= 0} q(e[link[i][k]]), K), q and result those of vr_gather_flux with
+ *   wmax(K).  Exact int64 sums: G(e) has the bits of vr_gather_flux(0, N, K, n, VR_GATHER_NORMAL, e).
+ * Solve with reflectivity rho (one float32 per primitive or a scalar, 0 <= rho <= 1; for sticking s, rho = 1 - s):
+ *   F_0 = G(nothing), the direct flux;  e_t[j] = rho[j] * F_{t-1}[j] (one float32 multiply);  F_t = G(e_t);
+ *   r_t = max_i |F_t[i] - F_{t-1}[i]| (a float32 subtraction; the maximum is taken over the bit patterns, so order cannot
+ *   show).  The solve stops at the first t >= 1 with r_t <= tolerance, or at t = maxIterations; maxIterations = 0 returns
+ *   F_0.  It returns F_t, t and r_t (0 for t = 0).  A pure function of scene, vr_set_rng_seed, vr_set_max_boundary_hits, K,
+ *   n, rho, tolerance and maxIterations: grid shape and the way the host batches iterations cannot show.
+ * Units are the gather's: the SOURCE-normalised INCOMING flux (what a diffuse particle credits), not that flux times the
+ * sticking.
+ * Memory: the table takes 4 x (N rounded up to 64) x K bytes plus 8 N for the sums, in buffers the context keeps until
+ *   vr_radiosity_free_links or vr_destroy; vr_radiosity_link_bytes says how much before it is built.  Its layout is
+ *   private.  A table that cannot be allocated is refused with VR_E_HIP; the context stays usable and NO table is resident
+ *   afterwards (building replaces: the previous table is gone as soon as the arguments have been accepted).
+ * vr_radiosity_links_device builds or replaces the table.  Refused as vr_gather_flux_device in VR_GATHER_NORMAL mode
+ *   (VR_E_INVALID: samples == 0, cosinePower not finite or < 1, samples x g beyond 2^22; VR_E_STATE: as
+ *   vr_cast_rays_device).  Changes nothing of a finished apply; the next apply gives the bits it would have given.
+ * A table remembers the scene build, the boundary conditions, the source direction, vr_set_max_boundary_hits, the rng
+ *   seed, K and n it was built from.  Every call that reads it is VR_E_STATE, with a message that says which of them has
+ *   changed, once they no longer match the settings in force — and VR_E_STATE when there is no table.
+ *   vr_radiosity_resident: 1 if a table for (samples, cosinePower) is resident and matches, else 0.
+ * vr_radiosity_solve_device: reflectivity NULL (reflectivityScalar counts) or DEVICE, N floats by original id; out:
+ *   DEVICE, N floats; iterations / residual: NULL or host words.  The host waits for the residuals.  Refused, out
+ *   untouched and the context usable: VR_E_INVALID for a reflectivity that is NaN, negative or above 1 (checked on the
+ *   device, ONE word back; the message names the lowest such index), a tolerance that is negative or NaN (0 is allowed:
+ *   the solve then runs until the flux stops changing bit for bit, or maxIterations), out null, a pointer that is not
+ *   device memory of ctx's device; VR_E_STATE as above.
+ * vr_radiosity_solve: the same from and to host arrays.  vr_radiosity_direct_device: F_0 from the table.
+ * vr_debug_radiosity_links: links first .. first + count - 1 of primitive prim as ORIGINAL ids, into host memory.
+ * vr_debug_radiosity_time_iterations: a measurement — `count` iteration kernels with a scalar reflectivity launched back
+ *   to back between two events, converged or not, with (nontemporal != 0) or without non-temporal loads for the link
+ *   stream; *msPerIteration is the elapsed time over count.  It returns no flux. */
+uint64_t vr_radiosity_link_bytes(const vr_context *ctx, uint32_t samples);
+int vr_radiosity_links_device(vr_context *ctx, uint32_t samples, float cosinePower, void *stream);
+int vr_radiosity_resident(const vr_context *ctx, uint32_t samples, float cosinePower);
+int vr_radiosity_solve_device(vr_context *ctx, const float *reflectivity, float reflectivityScalar, float tolerance,
+                              uint32_t maxIterations, float *out, uint32_t *iterations, float *residual, void *stream);
+int vr_radiosity_solve(vr_context *ctx, const float *reflectivity, float reflectivityScalar, float tolerance,
+                       uint32_t maxIterations, float *out, uint32_t *iterations, float *residual);
+int vr_radiosity_direct_device(vr_context *ctx, float *out, void *stream);
+int vr_debug_radiosity_links(vr_context *ctx, uint32_t prim, uint32_t first, uint32_t count, int32_t *links);
+int vr_debug_radiosity_time_iterations(vr_context *ctx, float reflectivityScalar, uint32_t count, int nontemporal,
+                                       float *msPerIteration);
+int vr_radiosity_free_links(vr_context *ctx);
 /* ---- flux statistics (not in the reference): per-primitive hit counts and the Monte-Carlo error of the flux ----------
  * vr_set_flux_statistics(on != 0): every later apply() keeps, for each particle and alongside its data label 0 (the flux
  * label of every built-in model), two more int64 sums per primitive:

@@ -1342,6 +1342,59 @@ public:
                                                   dOut, stream));
   }
 
+  // ---- radiosity solve (not in the reference; vr_radiosity_*, whose header comment has the definition): the
+  //      steady-state incoming flux of a species re-emitted diffusely with probability 1 - sticking — the fixed point of
+  //      gatherFlux(samples, emission = (1 - sticking) x flux).  The samples are walked once into a link table that stays
+  //      resident and is reused while samples, cosinePower and the scene's settings stay as they are; every iteration is
+  //      a pass over that table.  SOURCE-normalised like gatherFlux.
+  /// what the solve did beyond the flux
+  struct RadiosityInfo {
+    unsigned iterations = 0;
+    float residual = 0.f;
+  };
+  /// empty, with the library's message on std::cerr, if it was refused; the table is built when none matches
+  [[nodiscard]] std::vector<NumericType> solveRadiosity(unsigned samples, NumericType sticking, NumericType cosinePower = 1,
+                                                        NumericType tolerance = NumericType(1e-4), unsigned maxIterations = 1000,
+                                                        RadiosityInfo *info = nullptr) {
+    return solveRadiosityImpl(samples, nullptr, 1.f - (float)sticking, cosinePower, tolerance, maxIterations, info);
+  }
+  /// ... with one sticking value per primitive
+  [[nodiscard]] std::vector<NumericType> solveRadiosity(unsigned samples, const std::vector<NumericType> &sticking,
+                                                        NumericType cosinePower = 1, NumericType tolerance = NumericType(1e-4),
+                                                        unsigned maxIterations = 1000, RadiosityInfo *info = nullptr) {
+    std::vector<float> rho(sticking.size());
+    for (size_t i = 0; i < rho.size(); ++i)
+      rho[i] = 1.f - (float)sticking[i];
+    if (!ctx_ || rho.size() != vr_num_primitives(ctx_)) {
+      std::cerr << "viennaray_amd: solveRadiosity: sticking has " << rho.size() << " entries, the scene "
+                << (ctx_ ? vr_num_primitives(ctx_) : 0u) << " primitives\n";
+      return {};
+    }
+    return solveRadiosityImpl(samples, rho.data(), 0.f, cosinePower, tolerance, maxIterations, info);
+  }
+  /// build or replace the link table (solveRadiosity does it when none matches); false if it was refused
+  bool radiosityLinks(unsigned samples, float cosinePower = 1.f, void *stream = nullptr) {
+    return ctx_ && reported(vr_radiosity_links_device(ctx_, samples, cosinePower, stream));
+  }
+  [[nodiscard]] uint64_t radiosityLinkBytes(unsigned samples) const { return ctx_ ? vr_radiosity_link_bytes(ctx_, samples) : 0; }
+  void freeRadiosityLinks() {
+    if (ctx_)
+      check(vr_radiosity_free_links(ctx_));
+  }
+  /// dReflectivity (nullptr: reflectivityScalar counts; else numPrimitives floats) and dOut (numPrimitives floats) are
+  /// DEVICE memory; needs a table (radiosityLinks); getFluxDevice's stream rules.  false if it was refused.
+  bool solveRadiosityDevice(const float *dReflectivity, float reflectivityScalar, float tolerance, unsigned maxIterations,
+                            float *dOut, RadiosityInfo *info = nullptr, void *stream = nullptr) {
+    uint32_t its = 0;
+    float res = 0.f;
+    if (!ctx_ || !reported(vr_radiosity_solve_device(ctx_, dReflectivity, reflectivityScalar, tolerance, maxIterations, dOut, &its,
+                                                     &res, stream)))
+      return false;
+    if (info)
+      *info = RadiosityInfo{its, res};
+    return true;
+  }
+
   // ---- flux statistics (not in the reference; vr_set_flux_statistics): per-primitive hit counts and the Monte-Carlo
   //      error of the flux label.  A per-credit estimator: it ignores the correlation between several credits of one ray
   //      to the same primitive.  Off by default; an absorbing particle keeps its kernels, every other launch runs the
@@ -1434,6 +1487,23 @@ protected:
     if (rc != VR_OK)
       std::cerr << "viennaray_amd: " << vr_last_error(ctx_) << "\n";
     return rc == VR_OK;
+  }
+  // rho: nullptr (the scalar counts) or numPrimitives reflectivities
+  std::vector<NumericType> solveRadiosityImpl(unsigned samples, const float *rho, float rhoScalar, NumericType cosinePower,
+                                              NumericType tolerance, unsigned maxIterations, RadiosityInfo *info) {
+    if (!ctx_)
+      return {};
+    if (!vr_radiosity_resident(ctx_, samples, (float)cosinePower) &&
+        !reported(vr_radiosity_links_device(ctx_, samples, (float)cosinePower, nullptr)))
+      return {};
+    std::vector<float> raw(vr_num_primitives(ctx_));
+    uint32_t its = 0;
+    float res = 0.f;
+    if (!reported(vr_radiosity_solve(ctx_, rho, rhoScalar, (float)tolerance, maxIterations, raw.data(), &its, &res)))
+      return {};
+    if (info)
+      *info = RadiosityInfo{its, res};
+    return std::vector<NumericType>(raw.begin(), raw.end());
   }
   std::vector<NumericType> fluxError(unsigned particleIdx, int kind) {
     std::vector<float> raw(ctx_ ? vr_num_primitives(ctx_) : 0);

@@ -122,6 +122,15 @@ SIGNATURES = {
     "vr_gather_flux_device": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _vp, _vp, _vp]),
     "vr_gather_flux": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _fp, _fp]),
     "vr_debug_gather_samples": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _fp, _fp, _fp]),
+    "vr_radiosity_link_bytes": (C.c_uint64, [_vp, C.c_uint32]),
+    "vr_radiosity_links_device": (C.c_int, [_vp, C.c_uint32, C.c_float, _vp]),
+    "vr_radiosity_resident": (C.c_int, [_vp, C.c_uint32, C.c_float]),
+    "vr_radiosity_solve_device": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.c_uint32, _vp, _u32p, _fp, _vp]),
+    "vr_radiosity_solve": (C.c_int, [_vp, _fp, C.c_float, C.c_float, C.c_uint32, _fp, _u32p, _fp]),
+    "vr_radiosity_direct_device": (C.c_int, [_vp, _vp, _vp]),
+    "vr_debug_radiosity_links": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _i32p]),
+    "vr_debug_radiosity_time_iterations": (C.c_int, [_vp, C.c_float, C.c_uint32, C.c_int, _fp]),
+    "vr_radiosity_free_links": (C.c_int, [_vp]),
     "vr_get_disk_areas": (C.c_int, [_vp, _fp, C.c_uint32]),
     "vr_get_bounding_box": (C.c_int, [_vp, _fp]),
     "vr_get_source_area": (C.c_float, [_vp]),

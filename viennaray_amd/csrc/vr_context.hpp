@@ -383,6 +383,22 @@ struct vr_context {
   // point's rows too).  They read castParams like a cast and share its counter block.  Grown behind host_waits only
   DevBuf<unsigned long long> dGatherAcc;
   DevBuf<float> dGatherOut, dGatherEmission;
+  // vr_radiosity_*: the link table of the last vr_radiosity_links_device (slots x samples int32 in leaf order,
+  // vr_radiosity.hpp), its direct sums and leaf -> original id table, what it was built from, and a solve's work buffers
+  // (leaf order: reflectivity, F, the two emission tables; the words that come back; the host forms' staging).  A table
+  // is good while radValid and radStamp describes the settings in force (vr_radiosity_solve.cpp: radiosity_stale)
+  struct RadiosityStamp {
+    uint32_t build = 0, numPrims = 0;
+    int bcs[3] = {0, 0, 0}, sourceDirection = -1;
+    uint32_t maxBoundaryHits = 0, seed = 0, samples = 0;
+    float cosinePower = 0.f;
+  };
+  bool radValid = false;
+  RadiosityStamp radStamp;
+  DevBuf<int32_t> dRadLinks, dRadDebug;
+  DevBuf<unsigned long long> dRadDirect;
+  DevBuf<uint32_t> dRadOrigOfLeaf, dRadWords;
+  DevBuf<float> dRadRho, dRadF, dRadE0, dRadE1, dRadIn, dRadOut;
   bool areasValid = false;
   DevBuf<uint32_t> dNbOff, dNbIds, dLeafOfOrig;
   DevBuf<uint32_t> dNbTmp; // the one-pass neighbourhood query's fixed-stride lists (build scratch)
@@ -517,6 +533,13 @@ TraceParams launch_params(const vr_context *c, const ParticleLaunch &L);
 // vr_cast_rays.cpp: what every walk over the resident scene (a cast, a gather) refuses and starts from
 int resident_scene_refusal(vr_context *c, const char *api, const char *what);
 int resident_scene_params(vr_context *c, bool &waited, TraceParams &p);
+
+// vr_gather_flux.cpp: what a gather refuses and launches with, shared with the link recording (vr_radiosity_solve.cpp)
+int gather_refusal(vr_context *c, const char *api, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                   uint32_t mode, const void *emission, const void *out);
+int gather_params(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a, uint32_t primFirst, uint32_t primCount,
+                  uint32_t samples, float cosinePower, uint32_t mode);
+void gather_cut_chunks(GatherArgs &a, unsigned slabs);
 
 // a work buffer of the map or of a cast grows behind host_waits only (vr_api.cpp: a buffer that moves)
 template <class T> int map_grow(vr_context *c, DevBuf<T> &b, size_t n, bool &waited) {

@@ -5,6 +5,8 @@
 //   gather_samples_kernel<GEO, D>  a persistent grid, laid out as cast_rays_kernel: every wave owns one slab of the walk's
 //                                  global stack and its lanes' columns of the block's LDS stack for its whole life; the
 //                                  launcher never starts more waves than there are slabs or work items.
+//                                  With REC it records the link table of vr_radiosity_links_device instead of
+//                                  reading an emission table: one text for what a sample is.
 //   gather_finish_kernel           int64 sums -> floats.
 //   debug_gather_samples_kernel    the origin, the normal and a run of sample directions of ONE primitive
 //                                  (vr_debug_gather_samples): the device functions the first kernel uses.
@@ -24,6 +26,7 @@
 #include "vr_cast.hpp"
 #include "vr_gather.hpp"
 #include "vr_kernels.hpp"
+#include "vr_radiosity.hpp"
 #include "vr_trace_kernel.hpp"
 
 namespace vr {
@@ -67,7 +70,10 @@ __device__ __forceinline__ u64 gather_draw(unsigned &k, u64 &lo, u64 &hi) {
   return v;
 }
 
-template <int GEO, int D>
+// REC: the link recording of vr_radiosity_links_device (vr_radiosity.hpp has the table's index).  The same samples and
+// walks; every walked sample stores one int32 — the leaf position of a front-side hit, RADIOSITY_NO_LINK for anything
+// else — and only the direct weights are summed, into acc[leaf position].  Whole scene, NORMAL mode, no emission table
+template <int GEO, int D, bool REC>
 __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TraceParams p, const GatherArgs a) {
   __shared__ float wallS[VR_WALL_TABLE];
   __shared__ unsigned stackS[VR_STACK_LDS * VR_BLOCK]; // [entry][thread of the block]
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
   const uint4 *__restrict__ pnodes = reinterpret_cast<const uint4 *>(p.pnodes);
   const float4 *__restrict__ prims = reinterpret_cast<const float4 *>(p.prims);
   const GatherFrame frame{p.rayDir, p.firstDir, p.secondDir, -p.posNeg};
-  const bool haveEmission = a.emission != nullptr;
+  const bool haveEmission = !REC && a.emission != nullptr;
 #ifdef VR_DIAG
   unsigned long long phaseDummy[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tLast = 0ull;
   unsigned long long *const phaseT = phaseDummy;
@@ -158,6 +164,9 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
             emission = a.emission[(unsigned)s.prim]; // (the one load of the emission table: at a front-side hit)
         }
         sum += gather_q(gather_weight(end, a.mode, a.g, a.cosinePower, c, mDotW, haveEmission, emission), a.wmax);
+        if (REC) // (t < a.primCount <= a.linkSlots, the sample < a.samples: inside the table's linkSlots x samples entries)
+          a.links[radiosity_link_index(a.linkSlots, (unsigned)t, chunk * GATHER_CHUNK + j)] =
+              end == GATHER_END_FRONT ? (int)hitPos : RADIOSITY_NO_LINK;
       }
       if (j + 1u < jEnd) { // outputs 2 (j + 1) and 2 (j + 1) + 1
         r1 = gather_canon(gather_draw(k, lo, hi));
@@ -165,7 +174,7 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
       }
     }
     if (valid && sum != 0)
-      atomicAdd(a.acc + (orig - a.primFirst), (unsigned long long)sum);
+      atomicAdd(a.acc + (REC ? (unsigned)t : orig - a.primFirst), (unsigned long long)sum);
   }
 }
 
@@ -218,16 +227,32 @@ hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const Gat
   if (waves == 0)
     return hipSuccess;
   const dim3 g(waves > perBlock ? waves / perBlock : 1u), b(waves > perBlock ? (unsigned)VR_BLOCK : waves * 64u);
+  if (a.links) { // the recording: the whole scene in leaf order, NORMAL samples, a table of linkSlots x samples entries
+    if (a.leafOfOrig || a.emission || a.mode != GATHER_NORMAL || a.primFirst != 0u || a.linkSlots < a.primCount)
+      return hipErrorInvalidValue;
+    if (geo == 0) {
+      if (D == 2)
+        hipLaunchKernelGGL((gather_samples_kernel<0, 2, true>), g, b, 0, st, p, a);
+      else
+        hipLaunchKernelGGL((gather_samples_kernel<0, 3, true>), g, b, 0, st, p, a);
+    } else {
+      if (D == 2)
+        hipLaunchKernelGGL((gather_samples_kernel<1, 2, true>), g, b, 0, st, p, a);
+      else
+        hipLaunchKernelGGL((gather_samples_kernel<1, 3, true>), g, b, 0, st, p, a);
+    }
+    return hipGetLastError();
+  }
   if (geo == 0) {
     if (D == 2)
-      hipLaunchKernelGGL((gather_samples_kernel<0, 2>), g, b, 0, st, p, a);
+      hipLaunchKernelGGL((gather_samples_kernel<0, 2, false>), g, b, 0, st, p, a);
     else
-      hipLaunchKernelGGL((gather_samples_kernel<0, 3>), g, b, 0, st, p, a);
+      hipLaunchKernelGGL((gather_samples_kernel<0, 3, false>), g, b, 0, st, p, a);
   } else {
     if (D == 2)
-      hipLaunchKernelGGL((gather_samples_kernel<1, 2>), g, b, 0, st, p, a);
+      hipLaunchKernelGGL((gather_samples_kernel<1, 2, false>), g, b, 0, st, p, a);
     else
-      hipLaunchKernelGGL((gather_samples_kernel<1, 3>), g, b, 0, st, p, a);
+      hipLaunchKernelGGL((gather_samples_kernel<1, 3, false>), g, b, 0, st, p, a);
   }
   return hipGetLastError();
 }

@@ -16,8 +16,8 @@ static_assert(VR_GATHER_NORMAL == vr::GATHER_NORMAL && VR_GATHER_SOURCE == vr::G
 namespace vr {
 
 // what every form refuses before it touches anything; `api`: the entry point's name
-static int gather_refusal(vr_context *c, const char *api, uint32_t primFirst, uint32_t primCount, uint32_t samples,
-                          float cosinePower, uint32_t mode, const void *emission, const void *out) {
+int gather_refusal(vr_context *c, const char *api, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                   uint32_t mode, const void *emission, const void *out) {
   const std::string name = api;
   if (samples == 0)
     return fail(c, VR_E_INVALID, (name + ": samples must not be 0").c_str());
@@ -43,8 +43,8 @@ static int gather_refusal(vr_context *c, const char *api, uint32_t primFirst, ui
 static int gather_state_refusal(vr_context *c, const char *api) { return resident_scene_refusal(c, api, "gather from"); }
 
 // launch parameters and the arguments every kernel of this file shares
-static int gather_params(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a, uint32_t primFirst, uint32_t primCount,
-                         uint32_t samples, float cosinePower, uint32_t mode) {
+int gather_params(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a, uint32_t primFirst, uint32_t primCount,
+                  uint32_t samples, float cosinePower, uint32_t mode) {
   VR_TRY(resident_scene_params(c, waited, p));
   a = GatherArgs{};
   a.leafOfOrig = c->dLeafOfOrig.p;
@@ -63,6 +63,13 @@ static int gather_params(vr_context *c, bool &waited, TraceParams &p, GatherArgs
   return VR_OK;
 }
 
+// a chunk is cut into `subs` runs of samples, work items of their own, until there is an item for every wave the
+// walk stack allows (a scene of a few ten thousand primitives at K = 64 is a few hundred (group, chunk) pairs)
+void gather_cut_chunks(GatherArgs &a, unsigned slabs) {
+  while (a.subs < GATHER_MAX_SUBS && (uint64_t)a.groups * a.chunks * a.subs < slabs)
+    a.subs *= 2;
+}
+
 // the kernels, on the context's stream: every pointer is device memory, the arguments have been accepted
 static int gather_on_device(vr_context *c, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
                             uint32_t mode, const float *emission, float *out) {
@@ -77,10 +84,7 @@ static int gather_on_device(vr_context *c, uint32_t primFirst, uint32_t primCoun
   a.acc = c->dGatherAcc.p;
   VR_HIP(c, hipMemsetAsync(c->dGatherAcc.p, 0, (size_t)primCount * 8, c->stream));
   const unsigned slabs = (unsigned)std::min<size_t>(c->walkStackWaves, 0xFFFFFFFFu);
-  // a chunk is cut into `subs` runs of samples, work items of their own, until there is an item for every wave the
-  // walk stack allows (a scene of a few ten thousand primitives at K = 64 is a few hundred (group, chunk) pairs)
-  while (a.subs < GATHER_MAX_SUBS && (uint64_t)a.groups * a.chunks * a.subs < slabs)
-    a.subs *= 2;
+  gather_cut_chunks(a, slabs);
   VR_HIP(c, launch_gather_samples(p, c->geo.geo, c->geo.D, a, slabs, c->stream));
   VR_HIP(c, launch_gather_finish(c->dGatherAcc.p, primCount, samples, out, c->stream));
   return VR_OK;

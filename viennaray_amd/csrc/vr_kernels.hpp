@@ -160,6 +160,10 @@ struct GatherArgs {
   float cosinePower, g;         // g: gather_g(cosinePower, D)
   float wmax;                   // gather_wmax(samples)
   uint32_t subs;                // work items per (group, chunk): a power of two <= GATHER_MAX_SUBS, each a run of 64 / subs samples
+  // the link recording of vr_radiosity_links_device (nullptr: an ordinary gather): linkSlots x samples int32,
+  // vr_radiosity.hpp's radiosity_link_index; acc is then indexed by LEAF position and holds the direct sums alone
+  int32_t *links;
+  unsigned long long linkSlots;
 };
 // p, slabs: as launch_cast_rays.  One launch of at most min(slabs, groups x chunks x subs) waves
 hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned slabs, hipStream_t st);
@@ -168,6 +172,34 @@ hipError_t launch_gather_finish(const unsigned long long *acc, unsigned n, unsig
 // first + count - 1
 hipError_t launch_debug_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned first, unsigned count,
                                        float *origin3, float *normal3, float *directions3, hipStream_t st);
+// the radiosity solve over a recorded link table (vr_radiosity.hip; vr_radiosity.hpp has the arithmetic and the table's
+// index).  Every pointer is device memory; everything but rho / out of the rho and unpermute launches is in LEAF order
+struct RadiosityArgs {
+  const int32_t *links;             // slots x samples entries: -1 or a leaf position < n
+  const unsigned long long *direct; // n int64 sums of the direct weights
+  const float *rho;                 // n reflectivities
+  const float *eIn;                 // e_t
+  float *eOut;                      // e_{t+1} = rho F_t
+  float *F;                         // F_{t-1} in, F_t out
+  uint32_t *residual;               // this iteration's word, zeroed by the caller: max |F_t - F_{t-1}| as bits
+  const uint32_t *prevResidual;     // nullptr, or the word of iteration t - 1: the kernel does nothing if that one stopped the solve
+  float tolerance;
+  uint32_t n, samples;
+  unsigned long long slots;         // radiosity_slots(n)
+  float wmax;                       // gather_wmax(samples)
+};
+// rho: n floats by original id, or nullptr for `scalar`; *bad (preset to all ones): the lowest index that is refused
+hipError_t launch_radiosity_rho(const float *rho, float scalar, const unsigned *leafOfOrig, unsigned n, float *rhoLeaf,
+                                unsigned *bad, hipStream_t st);
+hipError_t launch_radiosity_init(const unsigned long long *direct, const float *rhoLeaf, unsigned n, unsigned samples, float *F,
+                                 float *e, hipStream_t st);
+// nontemporal: the link stream by non-temporal loads (the emission table keeps the caches)
+hipError_t launch_radiosity_iterate(const RadiosityArgs &a, bool nontemporal, hipStream_t st);
+hipError_t launch_radiosity_unpermute(const float *F, const unsigned *leafOfOrig, unsigned n, float *out, hipStream_t st);
+hipError_t launch_radiosity_orig_of_leaf(const unsigned *leafOfOrig, unsigned n, unsigned *origOfLeaf, hipStream_t st);
+// the caller keeps prim < n and first + count <= samples
+hipError_t launch_radiosity_debug_links(const int *links, unsigned long long slots, const unsigned *leafOfOrig, unsigned prim,
+                                        unsigned first, unsigned count, const unsigned *origOfLeaf, int *out, hipStream_t st);
 // issue-ceiling microbenchmarks (vr_bench.hip); out: one {cycles, realtime, sink} triple of u64 per wave
 hipError_t launch_issue_kernel(int kind, unsigned blocks, unsigned iters, void *out, hipStream_t s);
 

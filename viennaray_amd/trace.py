@@ -920,6 +920,78 @@ class Trace:
                                                     _fptr(o), _fptr(m), _fptr(d)))
         return o, m, d
 
+    # --- radiosity solve: the steady-state flux of a diffusely re-emitting species (vr_radiosity_*) ------------------
+    def radiosityLinkBytes(self, samples):
+        """bytes of device memory the link table for `samples` samples per primitive takes (vr_radiosity_link_bytes)"""
+        return int(self._L.vr_radiosity_link_bytes(self._h, int(samples)))
+
+    def radiosityLinks(self, samples, cosinePower=1.0):
+        """Build (or replace) the link table solveRadiosity iterates over: gatherFlux's samples walked once, the primitive
+        each lands on recorded (vr_radiosity_links_device).  Needs what apply() or applyPrepare() leaves behind, like
+        gatherFlux, and changes none of it.  On torch's current stream."""
+        self._check(self._L.vr_radiosity_links_device(self._h, int(samples), float(cosinePower),
+                                                      C.c_void_p(self._torch_stream())))
+
+    def freeRadiosityLinks(self):
+        """give the link table's memory back (vr_radiosity_free_links)"""
+        self._check(self._L.vr_radiosity_free_links(self._h))
+
+    def debugRadiosityLinks(self, prim, first, count):
+        """links first .. first + count - 1 of primitive `prim` in the resident table, as original ids; -1: the sample
+        brings nothing back from the surface (vr_debug_radiosity_links)"""
+        out = np.empty(int(count), dtype=np.int32)
+        self._check(self._L.vr_debug_radiosity_links(self._h, int(prim), int(first), int(count),
+                                                     out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def solveRadiosity(self, samples, sticking=None, reflectivity=None, cosinePower=1.0, tolerance=1e-4, maxIterations=1000,
+                       returnInfo=False):
+        """The steady-state incoming flux of a species that is re-emitted diffusely with probability 1 - sticking: the
+        fixed point of gatherFlux(samples, emission=reflectivity * flux), one float32 per primitive, SOURCE-normalised.
+          sticking | reflectivity  exactly one of them: a scalar, a numpy array or a float32 tensor on the tracer's device,
+                                   one value per primitive, in [0, 1]; reflectivity = 1 - sticking.
+          tolerance                the solve stops at the first iteration whose largest change of a flux value is at most
+                                   this, or after maxIterations; maxIterations=0 gives gatherFlux(samples).
+        The samples are walked once, into a link table that stays resident (radiosityLinkBytes(samples) bytes) and is
+        reused while samples, cosinePower and the scene's settings stay as they are: several species share one table.
+        A tensor in gives a tensor out on torch's current stream, anything else a numpy array.  returnInfo=True:
+        (flux, iterations, residual).  A pure function of scene, setRngSeed and arguments (include/viennaray_amd.h has
+        the definition)."""
+        if (sticking is None) == (reflectivity is None):
+            raise ValueError("solveRadiosity: give exactly one of sticking and reflectivity")
+        n = int(self._L.vr_num_primitives(self._h))
+        given = sticking if reflectivity is None else reflectivity
+        device = hasattr(given, "data_ptr")
+        scalar, table = 0.0, None
+        if device:
+            _check_device_tensor("solveRadiosity", "sticking" if reflectivity is None else "reflectivity", given,
+                                 self._device, "torch.float32", [(n,)])
+            table = (1.0 - given) if reflectivity is None else given
+            table = table.contiguous()
+        elif np.ndim(given) == 0:
+            scalar = float(np.float32(1.0) - np.float32(given)) if reflectivity is None else float(given)
+        else:
+            table = np.ascontiguousarray(given, dtype=np.float32).reshape(-1)
+            if table.size != n:
+                raise ValueError("solveRadiosity: the table has %d entries, the scene %d primitives" % (table.size, n))
+            if reflectivity is None:
+                table = (np.float32(1.0) - table).astype(np.float32)
+        if not self._L.vr_radiosity_resident(self._h, int(samples), float(cosinePower)):
+            self.radiosityLinks(samples, cosinePower)
+        its, res = C.c_uint32(0), C.c_float(0.0)
+        if device:
+            import torch
+            out = torch.empty(n, dtype=torch.float32, device=torch.device("cuda", self._device))
+            self._check(self._L.vr_radiosity_solve_device(
+                self._h, C.c_void_p(table.data_ptr()), 0.0, float(tolerance), int(maxIterations),
+                C.c_void_p(out.data_ptr()), C.byref(its), C.byref(res), C.c_void_p(self._torch_stream())))
+        else:
+            out = np.empty(n, dtype=np.float32)
+            self._check(self._L.vr_radiosity_solve(self._h, _fptr(table) if table is not None else None, scalar,
+                                                   float(tolerance), int(maxIterations), _fptr(out), C.byref(its),
+                                                   C.byref(res)))
+        return (out, int(its.value), float(res.value)) if returnInfo else out
+
     # --- flux statistics: per-primitive hit counts and the Monte-Carlo error of the flux --------------------------
     def setCalculateFluxError(self, on=True):
         """Keep two more sums per primitive and particle alongside the flux label (vr_set_flux_statistics): the number of
