@@ -499,6 +499,82 @@ int vr_gather_flux(vr_context *ctx, uint32_t primFirst, uint32_t primCount, uint
  * arrays: 3, 3 and count x 3 floats) */
 int vr_debug_gather_samples(vr_context *ctx, uint32_t prim, uint32_t first, uint32_t count, uint32_t mode,
                             float cosinePower, float *origin3, float *normal3, float *directions3);
+/* ---- path gather (not in the reference): multi-bounce flux by paths traced BACK from the surface ------------------------
+ * A mirror reflection is its own reverse and keeps etendue: a sample cast from primitive i can be followed through its
+ * reflections until it reaches the source plane, and then brings back the source's radiance in its FINAL direction times
+ * the product of the reflectivities on the way — the multi-bounce incoming flux of a specularly reflected species with
+ * sticking below 1, with the same number of samples at every depth.  With a cosine re-emission at each vertex the same
+ * loop is the unbiased estimate of the diffuse steady state (vr_radiosity_solve's fixed point) without a link table.
+ * Scene, range, o_i, m_i, sample numbering, chunk engines and the INITIAL direction are exactly those of vr_gather_flux
+ * in VR_GATHER_NORMAL mode: sample k of primitive i starts along the same bits.  What differs:
+ * Segment  as vr_gather_flux: a followed cast, tnear 1e-4f, walls by their boundary conditions.  The
+ *          vr_set_max_boundary_hits budget is counted over the WHOLE path, as the tracer counts it over a ray's life; a
+ *          reflection does not reset it.
+ * Vertex   a front-side hit of primitive j (direction at the hit . n_j < 0, n_j the normal the tracer tests sides
+ *          against: the stored disk normal, the tracer's unit triangle normal) with fewer than maxBounces bounces made:
+ *          T <- T * rho[j] (one float32 multiply, from T = 1; rho by original id, or the scalar).  T == 0: the path ends
+ *          with weight 0.  Otherwise it goes on from the hit point (origin + direction * t, the tracer's restart) along
+ *            VR_GATHER_REFLECT_SPECULAR  the tracer's mirror direction 2 (n_j . -d) n_j + d of the unprojected direction d
+ *                                        (operation order: f = 2 * ((n.x * -d.x + n.y * -d.y) + n.z * -d.z); f * n.x - -d.x,
+ *                                        ...), in 2-D followed by the tracer's projection (z dropped, then normalised);
+ *            VR_GATHER_REFLECT_DIFFUSE   the cosine law about n_j as vr_gather_flux builds it about m_i (D = 3: cos =
+ *                                        sqrtf(r2), azimuth 2 pi r1, Frisvad basis, normalised; D = 2: sin(phi) = 2 r1 - 1),
+ *                                        from two uniforms of a COUNTER draw: with tea<8> the eight-round form of the
+ *                                        tracer's seed hash, key = tea<8>(i, (S ^ 0x50415448) + k) for the path's starting
+ *                                        primitive i (original id), sample index k and the context's rng seed S;
+ *                                        r1, r2 = (float)(tea<8>(key, 2 b + {0, 1}) >> 8) * 2^-24 at bounce b = 0, 1, ...
+ *                                        A pure function of (seed, i, k, b): nothing of chunks, ranges or earlier samples.
+ * Ends     the source plane reached — a miss that passed no IGNORE wall, with c_end = u . w_end > 0 of the FINAL
+ *          direction: weight T g_D(n) c_end^(n - 1), vr_gather_flux's NORMAL rule on c_end, then one multiply by T.
+ *          Everything else weighs 0: a back-side hit, an IGNORE wall, the boundary-hit budget spent, a front-side hit
+ *          with maxBounces bounces made (VR_GATHER_END_BOUNCES), T == 0 (VR_GATHER_END_ABSORBED).
+ * Result   q(), wmax(samples), the exact int64 sum and the final division of vr_gather_flux; weights are at most g, so the
+ *          same samples x g <= 2^22 refusal applies.  The same bits for any split of the range over calls and any launch
+ *          shape; a pure function of scene, vr_set_rng_seed, vr_set_max_boundary_hits and arguments.  With maxBounces == 0,
+ *          or reflectivity 0 everywhere, the result has the bits of vr_gather_flux(primFirst, primCount, samples,
+ *          cosinePower, VR_GATHER_NORMAL, NULL).  Units: the SOURCE-normalised INCOMING flux.
+ * Variance per sample: w <= g, so Var <= F (g - F) as for the gather.  The estimate is truncated at maxBounces bounces: it
+ *          lacks at most rho_max^(maxBounces + 1) g.
+ * Refused, out untouched and the context usable, message in vr_last_error:
+ *   VR_E_INVALID  what vr_gather_flux_device refuses in VR_GATHER_NORMAL mode; reflection not 0 / 1; maxBounces above
+ *                 VR_GATHER_MAX_BOUNCES; a reflectivity that is NaN, negative or above 1 (a table is checked on the device,
+ *                 ONE word back; the message names the lowest such index); (device form) a pointer that is not device
+ *                 memory of ctx's device.  primCount == 0 is VR_OK after the checks.
+ *   VR_E_STATE    as vr_gather_flux_device.
+ * Streams, work buffers and "changes nothing of a finished apply": as vr_gather_flux_device; the host waits once for the
+ * verdict on a reflectivity table.
+ *
+ * reflectivity: NULL (reflectivityScalar counts) or DEVICE, vr_num_primitives floats by original id; out: DEVICE,
+ * primCount floats */
+#define VR_GATHER_REFLECT_SPECULAR 0u
+#define VR_GATHER_REFLECT_DIFFUSE 1u
+#define VR_GATHER_MAX_BOUNCES 65535u
+int vr_gather_paths_device(vr_context *ctx, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                           uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float reflectivityScalar,
+                           float *out, void *stream);
+/* the same from and to host arrays: upload, kernels, download */
+int vr_gather_paths(vr_context *ctx, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                    uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float reflectivityScalar, float *out);
+/* ONE path — sample `sample` of primitive `prim` — as the call above walks it, through the same device functions (host
+ * arrays; reflectivity: NULL or vr_num_primitives HOST floats).  Vertex 0 is the starting primitive, every later vertex a
+ * geometry hit.  vertexIds[v]: the original id; vertexData[12 v ..]: the point (o_i, then hit points), the arriving
+ * direction (NaN for vertex 0), the normal used (m_i, then n_j) and the leaving direction (NaN where the path ends on the
+ * vertex), three floats each, unprojected.  Up to maxVertices vertices are stored; *numVertices counts all of them.
+ * *end: how the path ended (VR_GATHER_END_*); finalDirection3: the direction it went along last; *throughput: T;
+ * *weight: the unquantised weight.  Any of the five outputs behind vertexData may be NULL.  Refused as vr_gather_paths
+ * for (prim, 1 primitive, 1 sample); also sample >= 2^22 (no call has that many) and maxVertices above
+ * VR_GATHER_MAX_BOUNCES + 2 */
+#define VR_GATHER_PATH_VERTEX_FLOATS 12u
+#define VR_GATHER_END_MISS 0     /* reached the source plane (weight 0 still if c_end <= 0) */
+#define VR_GATHER_END_IGNORED 1  /* left through an IGNORE wall */
+#define VR_GATHER_END_WALL 2     /* stopped on a wall: the boundary-hit budget is spent */
+#define VR_GATHER_END_BACK 4     /* hit a primitive on its back side */
+#define VR_GATHER_END_BOUNCES 5  /* a front-side hit with maxBounces bounces made */
+#define VR_GATHER_END_ABSORBED 6 /* a front-side hit that took the throughput to 0 */
+int vr_debug_gather_path(vr_context *ctx, uint32_t prim, uint32_t sample, float cosinePower, uint32_t reflection,
+                         uint32_t maxBounces, const float *reflectivity, float reflectivityScalar, uint32_t maxVertices,
+                         uint32_t *vertexIds, float *vertexData, uint32_t *numVertices, uint32_t *end,
+                         float *finalDirection3, float *throughput, float *weight);
 /* ---- radiosity solve (not in the reference): the steady-state flux of a diffusely re-emitting species ------------------
  * vr_gather_flux with an emission table is one radiosity iteration, and its walks are a constant of the scene.  These
  * calls record them once — a link table — and iterate over the table on the device without walking again.

@@ -899,6 +899,9 @@ template <class NumericType> struct CastResult {
 /// how Trace::gatherFlux samples (VR_GATHER_*): NORMAL the cosine law about the primitive's normal, SOURCE the source's
 /// power-cosine law about the direction to the source plane (cosinePower >= 2, no emission)
 enum class GatherMode : unsigned { NORMAL = VR_GATHER_NORMAL, SOURCE = VR_GATHER_SOURCE };
+/// what a vertex of Trace::gatherPaths does (VR_GATHER_REFLECT_*): SPECULAR the mirror direction, DIFFUSE the cosine law
+/// about the normal hit
+enum class GatherReflection : unsigned { SPECULAR = VR_GATHER_REFLECT_SPECULAR, DIFFUSE = VR_GATHER_REFLECT_DIFFUSE };
 
 // ---- Trace<T,D> ----------------------------------------------------------------------
 template <class NumericType, int D> class Trace {
@@ -1342,6 +1345,39 @@ public:
                                                   dOut, stream));
   }
 
+  // ---- path gather (not in the reference; vr_gather_paths*, whose header comment has the definition): gatherFlux's
+  //      samples followed through their reflections until they reach the source plane — the multi-bounce incoming flux of
+  //      a species that reflects specularly (or is re-emitted diffusely) with probability 1 - sticking, with the same
+  //      number of samples for every primitive.  SOURCE-normalised like gatherFlux; maxBounces = 0 is gatherFlux(samples).
+  /// empty, with the library's message on std::cerr, if it was refused
+  [[nodiscard]] std::vector<NumericType> gatherPaths(unsigned samples, NumericType sticking,
+                                                     GatherReflection reflection = GatherReflection::SPECULAR,
+                                                     unsigned maxBounces = 64, NumericType cosinePower = 1) {
+    return gatherPathsImpl(samples, nullptr, 1.f - (float)sticking, reflection, maxBounces, cosinePower);
+  }
+  /// ... with one sticking value per primitive
+  [[nodiscard]] std::vector<NumericType> gatherPaths(unsigned samples, const std::vector<NumericType> &sticking,
+                                                     GatherReflection reflection = GatherReflection::SPECULAR,
+                                                     unsigned maxBounces = 64, NumericType cosinePower = 1) {
+    std::vector<float> rho(sticking.size());
+    for (size_t i = 0; i < rho.size(); ++i)
+      rho[i] = 1.f - (float)sticking[i];
+    if (!ctx_ || rho.size() != vr_num_primitives(ctx_)) {
+      std::cerr << "viennaray_amd: gatherPaths: sticking has " << rho.size() << " entries, the scene "
+                << (ctx_ ? vr_num_primitives(ctx_) : 0u) << " primitives\n";
+      return {};
+    }
+    return gatherPathsImpl(samples, rho.data(), 0.f, reflection, maxBounces, cosinePower);
+  }
+  /// dReflectivity (nullptr: reflectivityScalar counts; else numPrimitives floats) and dOut (primCount floats) are DEVICE
+  /// memory; getFluxDevice's stream rules.  false if it was refused.
+  bool gatherPathsDevice(unsigned primFirst, unsigned primCount, unsigned samples, float cosinePower, GatherReflection reflection,
+                         unsigned maxBounces, const float *dReflectivity, float reflectivityScalar, float *dOut,
+                         void *stream = nullptr) {
+    return ctx_ && reported(vr_gather_paths_device(ctx_, primFirst, primCount, samples, cosinePower, (uint32_t)reflection,
+                                                   maxBounces, dReflectivity, reflectivityScalar, dOut, stream));
+  }
+
   // ---- radiosity solve (not in the reference; vr_radiosity_*, whose header comment has the definition): the
   //      steady-state incoming flux of a species re-emitted diffusely with probability 1 - sticking — the fixed point of
   //      gatherFlux(samples, emission = (1 - sticking) x flux).  The samples are walked once into a link table that stays
@@ -1503,6 +1539,17 @@ protected:
       return {};
     if (info)
       *info = RadiosityInfo{its, res};
+    return std::vector<NumericType>(raw.begin(), raw.end());
+  }
+  // rho: nullptr (the scalar counts) or numPrimitives reflectivities
+  std::vector<NumericType> gatherPathsImpl(unsigned samples, const float *rho, float rhoScalar, GatherReflection reflection,
+                                           unsigned maxBounces, NumericType cosinePower) {
+    if (!ctx_)
+      return {};
+    std::vector<float> raw(vr_num_primitives(ctx_));
+    if (!reported(vr_gather_paths(ctx_, 0u, (uint32_t)raw.size(), samples, (float)cosinePower, (uint32_t)reflection, maxBounces, rho,
+                                  rhoScalar, raw.data())))
+      return {};
     return std::vector<NumericType>(raw.begin(), raw.end());
   }
   std::vector<NumericType> fluxError(unsigned particleIdx, int kind) {

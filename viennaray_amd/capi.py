@@ -17,6 +17,12 @@ VR_SOURCE_PARAMS = 16  # vr_set_source_model: parameters a source model reads
 VR_CAST_FOLLOW_BOUNDARIES = 1  # vr_cast_rays*: follow the side walls as the tracer does
 VR_CAST_MISS, VR_CAST_WALL = -1, -2  # ... its result codes in prim[]
 VR_GATHER_NORMAL, VR_GATHER_SOURCE = 0, 1  # vr_gather_flux*: the sampling mode
+VR_GATHER_REFLECT_SPECULAR, VR_GATHER_REFLECT_DIFFUSE = 0, 1  # vr_gather_paths*: what a vertex does
+VR_GATHER_MAX_BOUNCES = 65535  # ... the largest maxBounces
+VR_GATHER_PATH_VERTEX_FLOATS = 12  # vr_debug_gather_path: point, arriving direction, normal, leaving direction
+# ... how a path ended
+(VR_GATHER_END_MISS, VR_GATHER_END_IGNORED, VR_GATHER_END_WALL, VR_GATHER_END_BACK, VR_GATHER_END_BOUNCES,
+ VR_GATHER_END_ABSORBED) = 0, 1, 2, 4, 5, 6
 VR_FLUX_FRAC_BITS = 40  # the flux accumulators' (and the gather's) fixed point
 
 
@@ -122,6 +128,12 @@ SIGNATURES = {
     "vr_gather_flux_device": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _vp, _vp, _vp]),
     "vr_gather_flux": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _fp, _fp]),
     "vr_debug_gather_samples": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _fp, _fp, _fp]),
+    "vr_gather_paths_device": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _vp,
+                                         C.c_float, _vp, _vp]),
+    "vr_gather_paths": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _fp, C.c_float,
+                                  _fp]),
+    "vr_debug_gather_path": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _fp, C.c_float,
+                                       C.c_uint32, _u32p, _fp, _u32p, _u32p, _fp, _fp, _fp]),
     "vr_radiosity_link_bytes": (C.c_uint64, [_vp, C.c_uint32]),
     "vr_radiosity_links_device": (C.c_int, [_vp, C.c_uint32, C.c_float, _vp]),
     "vr_radiosity_resident": (C.c_int, [_vp, C.c_uint32, C.c_float]),

@@ -383,6 +383,10 @@ struct vr_context {
   // point's rows too).  They read castParams like a cast and share its counter block.  Grown behind host_waits only
   DevBuf<unsigned long long> dGatherAcc;
   DevBuf<float> dGatherOut, dGatherEmission;
+  // vr_gather_paths*: the reflectivity table in leaf order, its verdict word, and the host form's staging of the table;
+  // the sums and the output staging are the gather's.  Grown behind host_waits only
+  DevBuf<float> dPathRho, dPathIn;
+  DevBuf<uint32_t> dPathWord;
   // vr_radiosity_*: the link table of the last vr_radiosity_links_device (slots x samples int32 in leaf order,
   // vr_radiosity.hpp), its direct sums and leaf -> original id table, what it was built from, and a solve's work buffers
   // (leaf order: reflectivity, F, the two emission tables; the words that come back; the host forms' staging).  A table

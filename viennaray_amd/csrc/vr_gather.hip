@@ -7,6 +7,9 @@
 //                                  launcher never starts more waves than there are slabs or work items.
 //                                  With REC it records the link table of vr_radiosity_links_device instead of
 //                                  reading an emission table: one text for what a sample is.
+//                                  With PATH it follows a sample through its reflections (vr_gather_paths_device,
+//                                  vr_gather_paths.cpp): a front-side hit keeps the lane in the segment loop.
+//                                  With PATH == 2 it writes ONE path vertex by vertex (vr_debug_gather_path).
 //   gather_finish_kernel           int64 sums -> floats.
 //   debug_gather_samples_kernel    the origin, the normal and a run of sample directions of ONE primitive
 //                                  (vr_debug_gather_samples): the device functions the first kernel uses.
@@ -70,10 +73,65 @@ __device__ __forceinline__ u64 gather_draw(unsigned &k, u64 &lo, u64 &hi) {
   return v;
 }
 
+// The step of a path (vr_gather_paths) at a geometry hit: true when the path goes on — from the hit point along the new
+// direction, T, c = u . rayDirection and the bounce count updated — false when it ends there, `end` saying how.  hitPos:
+// the leaf position of the primitive hit, nj: the normal the tracer tests its side against; startPrim, sample: what the
+// counter draw of a DIFFUSE vertex is keyed by.  The kernel and vr_debug_gather_path both step through here
+template <int GEO, int D>
+__device__ __forceinline__ bool gather_bounce(const float4 *__restrict__ prims, const GatherArgs &a, const GatherFrame &frame,
+                                              unsigned hitPos, unsigned startPrim, unsigned sample, const V3 &hitPoint, V3 &org,
+                                              V3 &rayDirection, V3 &dir, float &T, float &c, unsigned &bounces, int &end, V3 &nj) {
+  nj = gather_hit_normal<GEO>(prims, hitPos);
+  if (!(vdot(dir, nj) < 0.f)) {
+    end = GATHER_END_BACK;
+    return false;
+  }
+  if (bounces >= a.maxBounces) {
+    end = GATHER_END_BOUNCES;
+    return false;
+  }
+  float rho = a.rho;
+  if (a.rhoLeaf)
+    rho = a.rhoLeaf[hitPos]; // (hitPos < numPrims: a leaf position the walk returned)
+  T = gather_path_throughput(T, rho);
+  if (T == 0.f) {
+    end = GATHER_END_ABSORBED;
+    return false;
+  }
+  if (a.reflection == GATHER_REFLECT_SPECULAR) // (wave-uniform)
+    rayDirection = reflect_specular(rayDirection, nj);
+  else
+    rayDirection = v3(gather_path_diffuse(D, a.seed, startPrim, sample, bounces, GVec{nj.x, nj.y, nj.z}));
+  dir = project_dir<D>(rayDirection);
+  org = hitPoint; // (org + dir * t: the tracer's restart)
+  c = gather_c(GVec{rayDirection.x, rayDirection.y, rayDirection.z}, frame);
+  ++bounces;
+  end = GATHER_END_FRONT;
+  return true;
+}
+
+// vertex v of the path vr_debug_gather_path records: a row of GATHER_PATH_ROW floats, if the caller's table has room for it
+__device__ __forceinline__ void gather_path_put(const GatherArgs &a, unsigned v, unsigned id, const V3 &pt, const V3 &in, const V3 &n,
+                                                const V3 &outDir) {
+  if (v >= a.pathMaxVertices)
+    return;
+  float *row = a.pathVertices + (size_t)v * GATHER_PATH_ROW;
+  row[0] = __uint_as_float(id);
+  row[1] = pt.x, row[2] = pt.y, row[3] = pt.z;
+  row[4] = in.x, row[5] = in.y, row[6] = in.z;
+  row[7] = n.x, row[8] = n.y, row[9] = n.z;
+  row[10] = outDir.x, row[11] = outDir.y, row[12] = outDir.z;
+}
+
 // REC: the link recording of vr_radiosity_links_device (vr_radiosity.hpp has the table's index).  The same samples and
 // walks; every walked sample stores one int32 — the leaf position of a front-side hit, RADIOSITY_NO_LINK for anything
 // else — and only the direct weights are summed, into acc[leaf position].  Whole scene, NORMAL mode, no emission table
-template <int GEO, int D, bool REC>
+// PATH: the paths of vr_gather_paths_device.  The same samples and walks; a front-side hit does not end the sample but
+// reflects it on (gather_bounce), the lane staying active with its new origin, rayDirection, dir, T and c, until the path
+// reaches the source plane or one of its other ends.  The cast state is the path's: the walls passed count over all of it.
+// PATH == 2 is vr_debug_gather_path: a range of ONE primitive, of whose samples lane 0 walks a.pathSample alone and
+// writes its vertices (gather_path_put) and the path's tail — the same loop, not a second one
+template <int GEO, int D, bool REC, int PATH = 0>
 __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TraceParams p, const GatherArgs a) {
   __shared__ float wallS[VR_WALL_TABLE];
   __shared__ unsigned stackS[VR_STACK_LDS * VR_BLOCK]; // [entry][thread of the block]
@@ -99,6 +157,10 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
   const u64 perGroup = (u64)a.chunks * a.subs, items = (u64)a.groups * perGroup;
   for (u64 it = wave; it < items; it += waves) {
     const unsigned sub = (unsigned)(it % a.subs), chunk = (unsigned)((it / a.subs) % a.chunks);
+    if constexpr (PATH == 2) {
+      if (chunk != a.pathSample / GATHER_CHUNK) // (wave-uniform) only the chunk that holds the one sample is looked at
+        continue;
+    }
     const u64 t = (it / perGroup) * 64u + lane; // index into the range, or (whole scene) the leaf position
     const bool valid = t < (u64)a.primCount;
     // ---- the lane's primitive ----
@@ -129,11 +191,22 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
       V3 org = v3(o), rayDirection = v3(w0), dir = project_dir<D>(rayDirection);
       // (a SOURCE sample facing away from the primitive weighs 0 whatever it meets: not walked)
       bool active = valid && !(a.mode == GATHER_SOURCE && !(mDotW > 0.f));
+      if constexpr (PATH == 2)
+        active = active && lane == 0u && chunk * GATHER_CHUNK + j == a.pathSample;
       const bool walked = active;
       CastState s;
       cast_begin(s);
       bool ignored = false;
       unsigned hitPos = 0u;
+      [[maybe_unused]] float T = 1.f, cEnd = c; // (PATH) the throughput, and u . omega of the direction the path goes along
+      [[maybe_unused]] unsigned bounces = 0u;
+      [[maybe_unused]] unsigned pathCount = 1u; // (PATH == 2) vertices so far: vertex 0 is the primitive itself
+      [[maybe_unused]] int pathEnd = GATHER_END_MISS;
+      if constexpr (PATH == 2) {
+        if (walked)
+          gather_path_put(a, 0u, orig, org, mk(__int_as_float(0x7FC00000), __int_as_float(0x7FC00000), __int_as_float(0x7FC00000)),
+                          v3(m), rayDirection);
+      }
       // ---- segments, until every sample of the wave has ended ----
       while (ballot64(active)) {
         HitRec h;
@@ -141,6 +214,10 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
         unsigned node = 0u, sp = 0u;
         pair_walk_lanes<GEO, VR_STACK_LDS>(p, pnodes, prims, stackL, stackG, active, org, dir, VR_GATHER_TNEAR, h, node, sp, 1u VR_DIAG_PASS);
         if (active) {
+#ifdef VR_DIAG
+          if constexpr (PATH) // (one wave-iteration per round of segments, one lane-iteration per segment walked in it)
+            DIAG(0);
+#endif
           hit_walls(p, wallS, org, dir, VR_GATHER_TNEAR, h);
           const V3 hitPoint = mk(org.x + dir.x * h.t, org.y + dir.y * h.t, org.z + dir.z * h.t);
           hitPos = h.pos;
@@ -152,10 +229,41 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
             }
           } else {
             active = false;
+            if constexpr (PATH) {
+              if (s.prim >= 0) {
+                int end;
+                V3 nj;
+                [[maybe_unused]] const V3 arriving = rayDirection;
+                active = gather_bounce<GEO, D>(prims, a, frame, hitPos, orig, chunk * GATHER_CHUNK + j, hitPoint, org, rayDirection, dir,
+                                               T, cEnd, bounces, end, nj);
+                if constexpr (PATH == 2) {
+                  const float QNAN = __int_as_float(0x7FC00000);
+                  gather_path_put(a, pathCount, (unsigned)s.prim, hitPoint, arriving, nj, active ? rayDirection : mk(QNAN, QNAN, QNAN));
+                  ++pathCount;
+                  pathEnd = end;
+                }
+              }
+            }
           }
         }
       }
-      if (walked) {
+      if constexpr (PATH) {
+        // (a path that ended on a primitive weighs 0 like one stopped on a wall; vr_debug_gather_path tells the ends apart)
+        if (walked)
+          sum += gather_q(gather_path_weight(s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL,
+                                             a.g, a.cosinePower, cEnd, T),
+                          a.wmax);
+        if constexpr (PATH == 2) {
+          if (walked) { // (lane 0, the one sample)
+            const int end = s.prim >= 0 ? pathEnd : s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL;
+            a.pathTail[0] = __uint_as_float(pathCount);
+            a.pathTail[1] = __uint_as_float((unsigned)end);
+            a.pathTail[2] = rayDirection.x, a.pathTail[3] = rayDirection.y, a.pathTail[4] = rayDirection.z;
+            a.pathTail[5] = T;
+            a.pathTail[6] = gather_path_weight(end, a.g, a.cosinePower, cEnd, T);
+          }
+        }
+      } else if (walked) {
         int end = s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL;
         float emission = 0.f;
         if (s.prim >= 0) {
@@ -176,6 +284,15 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
     if (valid && sum != 0)
       atomicAdd(a.acc + (REC ? (unsigned)t : orig - a.primFirst), (unsigned long long)sum);
   }
+#ifdef VR_DIAG
+  if constexpr (PATH) { // the rounds of segments and the segments walked in them: vr_gather_paths.cpp prints the two sums
+    const unsigned long long sw = wave_sum(diagW[0]), sl = wave_sum(diagL[0]);
+    if (lane == 0u && sl) {
+      atomicAdd(&p.counters[C_DIAG], sw);
+      atomicAdd(&p.counters[C_DIAG + 1], sl);
+    }
+  }
+#endif
 }
 
 __global__ void gather_finish_kernel(const unsigned long long *acc, unsigned n, unsigned samples, float *out) {
@@ -228,7 +345,7 @@ hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const Gat
     return hipSuccess;
   const dim3 g(waves > perBlock ? waves / perBlock : 1u), b(waves > perBlock ? (unsigned)VR_BLOCK : waves * 64u);
   if (a.links) { // the recording: the whole scene in leaf order, NORMAL samples, a table of linkSlots x samples entries
-    if (a.leafOfOrig || a.emission || a.mode != GATHER_NORMAL || a.primFirst != 0u || a.linkSlots < a.primCount)
+    if (a.paths || a.leafOfOrig || a.emission || a.mode != GATHER_NORMAL || a.primFirst != 0u || a.linkSlots < a.primCount)
       return hipErrorInvalidValue;
     if (geo == 0) {
       if (D == 2)
@@ -240,6 +357,22 @@ hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const Gat
         hipLaunchKernelGGL((gather_samples_kernel<1, 2, true>), g, b, 0, st, p, a);
       else
         hipLaunchKernelGGL((gather_samples_kernel<1, 3, true>), g, b, 0, st, p, a);
+    }
+    return hipGetLastError();
+  }
+  if (a.paths) { // the paths: NORMAL samples, no emission table
+    if (a.emission || a.mode != GATHER_NORMAL || a.reflection > GATHER_REFLECT_DIFFUSE || a.maxBounces > GATHER_MAX_BOUNCES)
+      return hipErrorInvalidValue;
+    if (geo == 0) {
+      if (D == 2)
+        hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 1>), g, b, 0, st, p, a);
+      else
+        hipLaunchKernelGGL((gather_samples_kernel<0, 3, false, 1>), g, b, 0, st, p, a);
+    } else {
+      if (D == 2)
+        hipLaunchKernelGGL((gather_samples_kernel<1, 2, false, 1>), g, b, 0, st, p, a);
+      else
+        hipLaunchKernelGGL((gather_samples_kernel<1, 3, false, 1>), g, b, 0, st, p, a);
     }
     return hipGetLastError();
   }
@@ -277,6 +410,37 @@ hipError_t launch_debug_gather_samples(const TraceParams &p, int geo, int D, con
       hipLaunchKernelGGL((debug_gather_samples_kernel<1, 2>), g, b, 0, st, p, a, first, count, origin3, normal3, directions3);
     else
       hipLaunchKernelGGL((debug_gather_samples_kernel<1, 3>), g, b, 0, st, p, a, first, count, origin3, normal3, directions3);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_debug_gather_path(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned sample, unsigned maxVertices,
+                                    float *vertices, float *tail, hipStream_t st) {
+  if (!a.paths || !a.leafOfOrig || a.emission || a.links || a.mode != GATHER_NORMAL || a.reflection > GATHER_REFLECT_DIFFUSE ||
+      a.maxBounces > GATHER_MAX_BOUNCES || !a.acc || !tail || (maxVertices && !vertices))
+    return hipErrorInvalidValue;
+  // one wave over the one chunk that holds the sample: a range of one primitive, samples 0 .. sample, whole chunks
+  GatherArgs b2 = a;
+  b2.primCount = 1u;
+  b2.groups = 1u;
+  b2.samples = sample + 1u; // (sample < 2^22: vr_gather_paths.cpp)
+  b2.chunks = sample / GATHER_CHUNK + 1u;
+  b2.subs = 1u;
+  b2.pathSample = sample;
+  b2.pathMaxVertices = maxVertices;
+  b2.pathVertices = vertices;
+  b2.pathTail = tail;
+  const dim3 g(1), b(64);
+  if (geo == 0) {
+    if (D == 2)
+      hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 2>), g, b, 0, st, p, b2);
+    else
+      hipLaunchKernelGGL((gather_samples_kernel<0, 3, false, 2>), g, b, 0, st, p, b2);
+  } else {
+    if (D == 2)
+      hipLaunchKernelGGL((gather_samples_kernel<1, 2, false, 2>), g, b, 0, st, p, b2);
+    else
+      hipLaunchKernelGGL((gather_samples_kernel<1, 3, false, 2>), g, b, 0, st, p, b2);
   }
   return hipGetLastError();
 }

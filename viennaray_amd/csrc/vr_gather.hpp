@@ -188,6 +188,57 @@ VR_GATHER_FN float gather_result(int64_t sum, uint32_t samples) {
   return (float)((double)sum / 1099511627776.0 / (double)samples);
 }
 
+// ---- gatherPaths (vr_gather_paths*): a sample followed through its reflections ---------------------------------------
+constexpr uint32_t GATHER_REFLECT_SPECULAR = 0;        // VR_GATHER_REFLECT_SPECULAR: the mirror direction at every vertex
+constexpr uint32_t GATHER_REFLECT_DIFFUSE = 1;         // VR_GATHER_REFLECT_DIFFUSE: the cosine law about the normal hit
+constexpr uint32_t GATHER_PATH_SEED_XOR = 0x50415448u; // "PATH": the counter draws' key starts from rng seed ^ this
+constexpr uint32_t GATHER_MAX_BOUNCES = 65535;         // VR_GATHER_MAX_BOUNCES
+// the two ends a path adds to a sample's (both weigh 0)
+constexpr int GATHER_END_BOUNCES = 5;  // a front-side hit with maxBounces bounces made
+constexpr int GATHER_END_ABSORBED = 6; // a front-side hit that took the throughput to 0
+
+// tea<8>: gather_tea3's rounds, eight of them — every output bit depends on every input bit, which a counter needs
+VR_GATHER_FN uint32_t gather_tea8(uint32_t v0, uint32_t v1) {
+  uint32_t s0 = 0;
+  for (int n = 0; n < 8; ++n) {
+    s0 += 0x9e3779b9u;
+    v0 += ((v1 << 4) + 0xa341316cu) ^ (v1 + s0) ^ ((v1 >> 5) + 0xc8013ea4u);
+    v1 += ((v0 << 4) + 0xad90777du) ^ (v0 + s0) ^ ((v0 >> 5) + 0x7e95761eu);
+  }
+  return v0;
+}
+// The counter draw of a DIFFUSE vertex: a pure function of (rng seed, ORIGINAL id of the primitive the path starts from,
+// sample index, bounce index) — no engine, nothing of chunks, ranges or earlier samples.  key: one hash per path
+VR_GATHER_FN uint32_t gather_path_key(uint32_t rngSeed, uint32_t prim, uint32_t sample) {
+  return gather_tea8(prim, (rngSeed ^ GATHER_PATH_SEED_XOR) + sample);
+}
+// uniform `which` (0: r1, 1: r2) of bounce `bounce`: the top 24 bits of a hash, in [0, 1) (both operations are exact)
+VR_GATHER_FN float gather_path_uniform(uint32_t key, uint32_t bounce, uint32_t which) {
+  return (float)(gather_tea8(key, 2u * bounce + which) >> 8) * 5.9604644775390625e-08f; // 2^-24
+}
+VR_GATHER_FN void gather_path_draw(uint32_t rngSeed, uint32_t prim, uint32_t sample, uint32_t bounce, float &r1, float &r2) {
+  const uint32_t key = gather_path_key(rngSeed, prim, sample);
+  r1 = gather_path_uniform(key, bounce, 0u);
+  r2 = gather_path_uniform(key, bounce, 1u);
+}
+// the direction a DIFFUSE vertex leaves along: the cosine law about the normal hit, from the counter draw
+VR_GATHER_FN GVec gather_path_diffuse(int D, uint32_t rngSeed, uint32_t prim, uint32_t sample, uint32_t bounce, const GVec &n) {
+  float r1, r2;
+  gather_path_draw(rngSeed, prim, sample, bounce, r1, r2);
+  return D == 2 ? gather_dir_normal2(r1, n) : gather_dir_normal3(r1, r2, n);
+}
+// T after a front-side hit of a primitive of reflectivity rho: one float32 multiply
+VR_GATHER_FN float gather_path_throughput(float T, float rho) { return T * rho; }
+// The end -> weight rule of a path.  cEnd: u . omega of the FINAL direction; T: the product of the reflectivities on the
+// way.  gather_weight's NORMAL rule on cEnd, then one multiply by T; every end but the source weighs 0
+VR_GATHER_FN float gather_path_weight(int end, float g, float n, float cEnd, float T) {
+  if (end != GATHER_END_MISS)
+    return 0.f;
+  return gather_weight(end, GATHER_NORMAL, g, n, cEnd, 0.f, false, 0.f) * T;
+}
+// a reflectivity the entry points accept (vr_radiosity.hpp: radiosity_rho_ok has the same rule)
+VR_GATHER_FN bool gather_path_rho_ok(float rho) { return rho >= 0.f && rho <= 1.f; }
+
 // g_D(n) (a host function; the kernel takes the float): g_3 = (n + 1) / 2, g_2 = 2 / C_n with
 // C_n = sqrt(pi) Gamma((n + 1) / 2) / Gamma(n / 2 + 1) — the weight of a sample that reaches the source is the ratio of
 // the source's normalised law (n + 1) / (2 pi) c^n (3-D), c^n / C_n (2-D) and the receiver's cosine law c / pi, c / 2 for

@@ -164,10 +164,25 @@ struct GatherArgs {
   // vr_radiosity.hpp's radiosity_link_index; acc is then indexed by LEAF position and holds the direct sums alone
   int32_t *links;
   unsigned long long linkSlots;
+  // the paths of vr_gather_paths_device (paths == 0: an ordinary gather): a front-side hit reflects the sample on,
+  // NORMAL mode, no emission table, no recording
+  uint32_t paths;
+  uint32_t reflection, maxBounces; // GATHER_REFLECT_*; bounces a path may make
+  float rho;                       // the reflectivity of every primitive where rhoLeaf is nullptr
+  const float *rhoLeaf;            // nullptr or [numPrims] reflectivities in LEAF order (launch_radiosity_rho)
+  // vr_debug_gather_path (launch_debug_gather_path fills these): the one sample whose path is written
+  uint32_t pathSample, pathMaxVertices;
+  float *pathVertices, *pathTail;
 };
 // p, slabs: as launch_cast_rays.  One launch of at most min(slabs, groups x chunks x subs) waves
 hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned slabs, hipStream_t st);
 hipError_t launch_gather_finish(const unsigned long long *acc, unsigned n, unsigned samples, float *out, hipStream_t st);
+// ONE path of vr_gather_paths (vr_debug_gather_path): sample `sample` of original primitive a.primFirst (a.leafOfOrig
+// set, a.paths set).  vertices: up to maxVertices rows of GATHER_PATH_ROW floats {id bits, point, arriving direction,
+// normal, leaving direction}; tail: GATHER_PATH_TAIL floats {vertex count bits, end code bits, final direction, T, weight}
+constexpr unsigned GATHER_PATH_ROW = 13, GATHER_PATH_TAIL = 7;
+hipError_t launch_debug_gather_path(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned sample, unsigned maxVertices,
+                                    float *vertices, float *tail, hipStream_t st);
 // origin and normal of original primitive a.primFirst (a.leafOfOrig set) and the directions of its samples first ..
 // first + count - 1
 hipError_t launch_debug_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned first, unsigned count,

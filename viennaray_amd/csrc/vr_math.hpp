@@ -1,6 +1,14 @@
 // vr_math.hpp — the vector type, wave votes and reductions, LDS pointer types, reflection (gfx950).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#else
+// the host compiler takes the plain vector arithmetic alone — V3, vdot, vnormalize, reflect_specular, project_dir
+// (tests/aux/gather_paths.cpp) — and none of the wave-level parts
+#include <cmath>
+#define __device__
+#define __forceinline__ inline
+#endif
 namespace vr {
 
 struct V3 {
@@ -41,6 +49,7 @@ __device__ __forceinline__ void vnormalize(V3 &a) {
 
 typedef unsigned long long u64;
 
+#if defined(__HIPCC__)
 // a device address kept as two words of the frame (lo, hi)
 __device__ __forceinline__ unsigned long long frame_addr(const float *f, int lo) {
   return ((unsigned long long)__float_as_uint(f[lo + 1]) << 32) | __float_as_uint(f[lo]);
@@ -110,6 +119,7 @@ __device__ __forceinline__ U4 mk_u4(unsigned x, unsigned y, unsigned z, unsigned
   v.x = x, v.y = y, v.z = z, v.w = w;
   return v;
 }
+#endif // __HIPCC__
 
 // rayReflection.hpp:13-29
 __device__ __forceinline__ V3 reflect_specular(const V3 &dir, const V3 &n) {

@@ -44,6 +44,11 @@ class GatherMode(enum.IntEnum):  # Trace.gatherFlux (VR_GATHER_*, include/vienna
     SOURCE = 1  # samples follow the source's power-cosine law about the direction to the source plane
 
 
+class GatherReflection(enum.IntEnum):  # Trace.gatherPaths (VR_GATHER_REFLECT_*, include/viennaray_amd.h)
+    SPECULAR = 0  # a vertex reflects the path into the mirror direction
+    DIFFUSE = 1   # a vertex re-emits it by the cosine law about the normal hit
+
+
 class TracingDataMergeEnum(enum.IntEnum):  # rayTracingData.hpp:10-14
     SUM = 0
     APPEND = 1
@@ -919,6 +924,87 @@ class Trace:
         self._check(self._L.vr_debug_gather_samples(self._h, int(prim), int(first), int(count), int(mode), float(cosinePower),
                                                     _fptr(o), _fptr(m), _fptr(d)))
         return o, m, d
+
+    # --- path gather: multi-bounce flux by paths traced back from the surface (vr_gather_paths*) ---------------------
+    def _pathReflectivity(self, name, sticking, reflectivity, host_only=False):
+        """(device?, scalar, table) of exactly one of sticking / reflectivity: a scalar, a numpy array or a float32 tensor
+        on the tracer's device, one value per primitive; reflectivity = 1 - sticking in float32"""
+        if (sticking is None) == (reflectivity is None):
+            raise ValueError("%s: give exactly one of sticking and reflectivity" % name)
+        n = int(self._L.vr_num_primitives(self._h))
+        given = sticking if reflectivity is None else reflectivity
+        if hasattr(given, "data_ptr"):
+            _check_device_tensor(name, "sticking" if reflectivity is None else "reflectivity", given, self._device,
+                                 "torch.float32", [(n,)])
+            table = ((1.0 - given) if reflectivity is None else given).contiguous()
+            return (True, 0.0, table) if not host_only else (False, 0.0, table.cpu().numpy())
+        if np.ndim(given) == 0:
+            return False, (float(np.float32(1.0) - np.float32(given)) if reflectivity is None else float(given)), None
+        table = np.ascontiguousarray(given, dtype=np.float32).reshape(-1)
+        if table.size != n:
+            raise ValueError("%s: the table has %d entries, the scene %d primitives" % (name, table.size, n))
+        if reflectivity is None:
+            table = (np.float32(1.0) - table).astype(np.float32)
+        return False, 0.0, table
+
+    def gatherPaths(self, samples, sticking=None, reflectivity=None, reflection=GatherReflection.SPECULAR, maxBounces=64,
+                    cosinePower=1.0, primFirst=0, primCount=None, numpy=False):
+        """The multi-bounce incoming flux of a species that is reflected with probability 1 - sticking, by gatherFlux's
+        samples followed BACK through their reflections until they reach the source plane: one float32 per primitive of
+        the range, SOURCE-normalised, the same number of samples at every depth.
+          sticking | reflectivity  exactly one of them: a scalar, a numpy array or a float32 tensor on the tracer's device,
+                                   one value per primitive, in [0, 1]; reflectivity = 1 - sticking.
+          reflection               GatherReflection.SPECULAR: the mirror direction at every vertex (what a
+                                   SpecularParticle does); GatherReflection.DIFFUSE: the cosine law about the normal hit
+                                   (the steady state solveRadiosity iterates to, without a link table).
+          maxBounces               reflections a path may make; the estimate lacks at most reflectivity^(maxBounces + 1).
+                                   0 gives gatherFlux(samples) bit for bit.
+        A pure function of scene, setRngSeed and arguments, with the same bits for any split of the range over calls.
+        A tensor in gives a tensor out on torch's current stream (vr_gather_paths_device), a numpy array in a numpy array
+        (vr_gather_paths); with a scalar a tensor comes back unless numpy=True.  Needs what apply() or applyPrepare()
+        leaves behind, like gatherFlux, and changes none of it (include/viennaray_amd.h has the definition)."""
+        n = int(self._L.vr_num_primitives(self._h))
+        primFirst = int(primFirst)
+        primCount = max(0, n - primFirst) if primCount is None else int(primCount)
+        if primFirst < 0 or primCount < 0 or int(samples) < 0 or int(maxBounces) < 0:
+            raise ValueError("gatherPaths: samples, maxBounces, primFirst and primCount must not be negative")
+        device, scalar, table = self._pathReflectivity("gatherPaths", sticking, reflectivity)
+        if not device and (table is not None or numpy):
+            out = np.empty(primCount, dtype=np.float32)
+            self._check(self._L.vr_gather_paths(self._h, primFirst, primCount, int(samples), float(cosinePower),
+                                                int(reflection), int(maxBounces), _fptr(table) if table is not None else None,
+                                                scalar, _fptr(out)))
+            return out
+        import torch
+        out = torch.empty(primCount, dtype=torch.float32, device=torch.device("cuda", self._device))
+        self._check(self._L.vr_gather_paths_device(
+            self._h, primFirst, primCount, int(samples), float(cosinePower), int(reflection), int(maxBounces),
+            C.c_void_p(table.data_ptr()) if device else None, scalar, C.c_void_p(out.data_ptr()),
+            C.c_void_p(self._torch_stream())))
+        return out
+
+    def debugGatherPath(self, prim, sample, sticking=None, reflectivity=None, reflection=GatherReflection.SPECULAR,
+                        maxBounces=64, cosinePower=1.0, maxVertices=None):
+        """ONE path of gatherPaths — sample `sample` of primitive `prim` — as a dict (vr_debug_gather_path):
+          ids [v] int64, points / arriving / normals / leaving [v, 3] float32: the stored vertices, vertex 0 the starting
+                 primitive (arriving NaN), every later one a geometry hit (leaving NaN where the path ends on it);
+          numVertices: all vertices of the path (maxVertices, default maxBounces + 2, caps the stored ones);
+          end: capi.VR_GATHER_END_*; direction [3]: the final direction; throughput; weight (unquantised)."""
+        _, scalar, table = self._pathReflectivity("debugGatherPath", sticking, reflectivity, host_only=True)
+        cap = int(maxBounces) + 2 if maxVertices is None else int(maxVertices)
+        ids = np.zeros(cap, dtype=np.uint32)
+        data = np.full((cap, 4, 3), np.nan, dtype=np.float32)
+        count, end = C.c_uint32(0), C.c_uint32(0)
+        final = np.empty(3, np.float32)
+        T, w = C.c_float(0.0), C.c_float(0.0)
+        self._check(self._L.vr_debug_gather_path(
+            self._h, int(prim), int(sample), float(cosinePower), int(reflection), int(maxBounces),
+            _fptr(table) if table is not None else None, scalar, cap, ids.ctypes.data_as(C.POINTER(C.c_uint32)), _fptr(data),
+            C.byref(count), C.byref(end), _fptr(final), C.byref(T), C.byref(w)))
+        v = min(cap, int(count.value))
+        return {"ids": ids[:v].astype(np.int64), "points": data[:v, 0], "arriving": data[:v, 1], "normals": data[:v, 2],
+                "leaving": data[:v, 3], "numVertices": int(count.value), "end": int(end.value), "direction": final,
+                "throughput": np.float32(T.value), "weight": np.float32(w.value)}
 
     # --- radiosity solve: the steady-state flux of a diffusely re-emitting species (vr_radiosity_*) ------------------
     def radiosityLinkBytes(self, samples):
