@@ -575,6 +575,77 @@ int vr_debug_gather_path(vr_context *ctx, uint32_t prim, uint32_t sample, float 
                          uint32_t maxBounces, const float *reflectivity, float reflectivityScalar, uint32_t maxVertices,
                          uint32_t *vertexIds, float *vertexData, uint32_t *numVertices, uint32_t *end,
                          float *finalDirection3, float *throughput, float *weight);
+/* ---- gather to a target error (not in the reference): per-primitive sums, standard error, adaptive sample counts --------
+ * vr_gather_flux and vr_gather_paths give every primitive the same K and say nothing of the error.  Sample k of primitive
+ * i is a pure function of (seed, i, k) and lives in chunks of 64 with their own engines, so "64 more samples for these
+ * primitives only" is exact: nothing already summed is redone.  Two layers.
+ * Spec     vr_gather_spec says what a sample is.  paths == 0: vr_gather_flux's sample (cosinePower, mode, emission; the
+ *          other fields are not read).  paths == 1: vr_gather_paths's (cosinePower, reflection, maxBounces, reflectivity or
+ *          reflectivityScalar); mode must be VR_GATHER_NORMAL and emission NULL.  Pointers are DEVICE memory in the _device
+ *          forms and HOST memory in the others.
+ * Sums     vr_gather_sums*: for the primitive range and chunks [chunkFirst, chunkFirst + chunks), that is samples
+ *          [64 chunkFirst, 64 (chunkFirst + chunks)), of a call of `budget` samples:
+ *            sum[i - primFirst]   = sum_k q(w_k)    the exact int64 sum vr_gather_flux / vr_gather_paths divide, q with
+ *                                                   wmax(budget);
+ *            sumSq[i - primFirst] = sum_k q2(w_k)   q2(w) = 0 for a weight that is not positive, otherwise
+ *                                                   (int64)(wc * wc * 2^28 + 0.5) in double, wc = min(w, wmax(budget), 2048).
+ *          Outputs are overwritten.  Over chunks [0, K / 64) with budget K, (float)((double)sum / 2^40 / K) has the bits of
+ *          the fixed-K call; sums over adjacent chunk ranges add.  budget sums of q2 stay within 2^61.
+ * Error    from S1 = sum, S2 = sumSq over K samples, in double, one IEEE operation each in this order, no contraction:
+ *            m1 = (double)S1 * 2^-40 / K;  m2 = (double)S2 * 2^-28 / K;  v = m2 - m1 * m1, 0 unless v > 0;
+ *            se2 = v / (K - 1);  stdErr = (float)sqrt(se2): the standard error of the mean m1.
+ *          converged(rel, abs): se2 <= tol * tol with tol = max((double)rel * m1, (double)abs); rel == abs == 0 means
+ *          never.  A primitive whose samples so far all weigh 0 is converged at minSamples under any positive target: the
+ *          call cannot know better.  The relative target is on the primitive's own mean.
+ * Adaptive vr_gather_adaptive*: minSamples = 64 c0, maxSamples = minSamples 2^R.  wmax = wmax(maxSamples) in every round.
+ *          Round 0: every primitive of the range runs chunks [0, c0), K = minSamples.  After a round every primitive still
+ *          listed is tested at its K; a converged one gets flux = (float)((double)S1 / 2^40 / K), stdErr, samplesUsed = K
+ *          and leaves the list.  Round r >= 1: the listed primitives run chunks [c0 2^(r-1), c0 2^r), K doubles, the sums
+ *          are accumulated.  It stops when the list is empty or K == maxSamples; primitives still listed then get their
+ *          outputs at maxSamples, and info->unconverged counts those that fail the test there.  info->rounds: rounds run;
+ *          info->totalSamples: the sum of samplesUsed over the range.  Weights at most wmax(maxSamples) — every NORMAL
+ *          weight — give flux[i] the bits of the fixed-K call at K = samplesUsed[i].
+ *          A pure function of scene, vr_set_rng_seed, vr_set_max_boundary_hits and arguments: exact sums and per-primitive
+ *          decisions, the same bits for any split of the primitive range over calls and any launch shape.
+ * Refused, outputs untouched and the context usable, message in vr_last_error:
+ *   VR_E_INVALID  what the fixed-K call of the spec refuses at samples = budget / maxSamples (the samples x g <= 2^22
+ *                 rule included); paths not 0 / 1; paths == 1 with a mode other than VR_GATHER_NORMAL or with an emission
+ *                 table; 64 (chunkFirst + chunks) > budget; minSamples not a positive multiple of 64; maxSamples not
+ *                 minSamples times a power of two; a target that is negative or NaN; a null spec, sum, sumSq, flux or info.
+ *                 stdErr and samplesUsed may be NULL.  primCount == 0 is VR_OK after the checks.
+ *   VR_E_STATE    as vr_gather_flux_device.
+ * Streams, work buffers and "changes nothing of a finished apply": as vr_gather_flux_device.  The adaptive call reads ONE
+ * word per round, the next list's length; the work buffers (two int64 arrays, two lists, a few words) grow on demand.
+ *
+ * sum, sumSq: DEVICE, primCount int64; flux, stdErr: DEVICE, primCount floats; samplesUsed: DEVICE, primCount uint32;
+ * info: HOST */
+typedef struct vr_gather_spec {
+  float cosinePower;
+  uint32_t mode;             /* VR_GATHER_NORMAL / VR_GATHER_SOURCE */
+  const float *emission;     /* NULL or vr_num_primitives floats by original id (paths == 0) */
+  uint32_t paths;            /* 0: vr_gather_flux's sample; 1: vr_gather_paths's */
+  uint32_t reflection;       /* VR_GATHER_REFLECT_* (paths == 1) */
+  uint32_t maxBounces;
+  const float *reflectivity; /* NULL (reflectivityScalar counts) or vr_num_primitives floats by original id */
+  float reflectivityScalar;
+} vr_gather_spec;
+typedef struct vr_gather_adaptive_info {
+  uint32_t rounds;
+  uint32_t unconverged;
+  uint64_t totalSamples;
+} vr_gather_adaptive_info;
+int vr_gather_sums_device(vr_context *ctx, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount,
+                          uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq, void *stream);
+/* the same from and to host arrays */
+int vr_gather_sums(vr_context *ctx, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst,
+                   uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq);
+int vr_gather_adaptive_device(vr_context *ctx, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount,
+                              uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux,
+                              float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream);
+/* the same from and to host arrays */
+int vr_gather_adaptive(vr_context *ctx, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount,
+                       uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux, float *stdErr,
+                       uint32_t *samplesUsed, vr_gather_adaptive_info *info);
 /* ---- radiosity solve (not in the reference): the steady-state flux of a diffusely re-emitting species ------------------
  * vr_gather_flux with an emission table is one radiosity iteration, and its walks are a constant of the scene.  These
  * calls record them once — a link table — and iterate over the table on the device without walking again.

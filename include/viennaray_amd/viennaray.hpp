@@ -1378,6 +1378,76 @@ public:
                                                    maxBounces, dReflectivity, reflectivityScalar, dOut, stream));
   }
 
+  // ---- gather to a target error (not in the reference; vr_gather_sums* / vr_gather_adaptive*, whose header comment has
+  //      the definition): every primitive starts with minSamples samples and doubles its own count until the standard
+  //      error of its mean is at most max(relTarget x mean, absTarget), or maxSamples is reached.  flux[i] has the bits of
+  //      the fixed-K call at K = samplesUsed[i].
+  /// what an adaptive gather returns: one entry per primitive, and the call's info; empty vectors if it was refused
+  struct GatherAdaptiveResult {
+    std::vector<NumericType> flux, stdErr;
+    std::vector<unsigned> samplesUsed;
+    vr_gather_adaptive_info info{};
+  };
+  [[nodiscard]] GatherAdaptiveResult gatherFluxAdaptive(NumericType relTarget, unsigned minSamples = 64, unsigned maxSamples = 4096,
+                                                        NumericType absTarget = 0, NumericType cosinePower = 1,
+                                                        GatherMode mode = GatherMode::NORMAL,
+                                                        const std::vector<NumericType> *emission = nullptr) {
+    std::vector<float> e;
+    if (emission)
+      e.assign(emission->begin(), emission->end());
+    if (ctx_ && emission && e.size() != vr_num_primitives(ctx_)) {
+      std::cerr << "viennaray_amd: gatherFluxAdaptive: emission has " << e.size() << " entries, the scene "
+                << vr_num_primitives(ctx_) << " primitives\n";
+      return {};
+    }
+    vr_gather_spec spec{};
+    spec.cosinePower = (float)cosinePower;
+    spec.mode = (uint32_t)mode;
+    spec.emission = emission ? e.data() : nullptr;
+    return gatherAdaptiveImpl(spec, relTarget, absTarget, minSamples, maxSamples);
+  }
+  [[nodiscard]] GatherAdaptiveResult gatherPathsAdaptive(NumericType relTarget, NumericType sticking,
+                                                         GatherReflection reflection = GatherReflection::SPECULAR,
+                                                         unsigned maxBounces = 64, unsigned minSamples = 64,
+                                                         unsigned maxSamples = 4096, NumericType absTarget = 0,
+                                                         NumericType cosinePower = 1) {
+    return gatherAdaptiveImpl(pathsSpec(nullptr, 1.f - (float)sticking, reflection, maxBounces, cosinePower), relTarget, absTarget,
+                              minSamples, maxSamples);
+  }
+  /// the spec's tables and the outputs (dFlux: primCount floats; dStdErr, dSamplesUsed: nullptr or primCount entries) are
+  /// DEVICE memory, info is the host's; getFluxDevice's stream rules, the host waits for one word per round.  false if it
+  /// was refused.
+  bool gatherAdaptiveDevice(const vr_gather_spec &spec, unsigned primFirst, unsigned primCount, unsigned minSamples,
+                            unsigned maxSamples, float relTarget, float absTarget, float *dFlux, float *dStdErr,
+                            uint32_t *dSamplesUsed, vr_gather_adaptive_info &info, void *stream = nullptr) {
+    return ctx_ && reported(vr_gather_adaptive_device(ctx_, &spec, primFirst, primCount, minSamples, maxSamples, relTarget,
+                                                      absTarget, dFlux, dStdErr, dSamplesUsed, &info, stream));
+  }
+  /// the exact int64 sums of the quantised weights (2^-40) and of their squares (2^-28) over chunks [chunkFirst,
+  /// chunkFirst + chunks) of a call of `budget` samples, per primitive (host tables in the spec).  false if it was refused.
+  bool gatherSums(const vr_gather_spec &spec, unsigned chunkFirst, unsigned chunks, unsigned budget, std::vector<int64_t> &sum,
+                  std::vector<int64_t> &sumSq) {
+    if (!ctx_)
+      return false;
+    const uint32_t n = vr_num_primitives(ctx_);
+    sum.assign(n, 0);
+    sumSq.assign(n, 0);
+    return reported(vr_gather_sums(ctx_, &spec, 0u, n, chunkFirst, chunks, budget, sum.data(), sumSq.data()));
+  }
+  /// the spec of a gatherPaths sample (reflectivity: nullptr or numPrimitives values the caller keeps alive)
+  static vr_gather_spec pathsSpec(const float *reflectivity, float reflectivityScalar, GatherReflection reflection,
+                                  unsigned maxBounces, NumericType cosinePower = 1) {
+    vr_gather_spec spec{};
+    spec.cosinePower = (float)cosinePower;
+    spec.mode = VR_GATHER_NORMAL;
+    spec.paths = 1u;
+    spec.reflection = (uint32_t)reflection;
+    spec.maxBounces = maxBounces;
+    spec.reflectivity = reflectivity;
+    spec.reflectivityScalar = reflectivityScalar;
+    return spec;
+  }
+
   // ---- radiosity solve (not in the reference; vr_radiosity_*, whose header comment has the definition): the
   //      steady-state incoming flux of a species re-emitted diffusely with probability 1 - sticking — the fixed point of
   //      gatherFlux(samples, emission = (1 - sticking) x flux).  The samples are walked once into a link table that stays
@@ -1551,6 +1621,22 @@ protected:
                                   rhoScalar, raw.data())))
       return {};
     return std::vector<NumericType>(raw.begin(), raw.end());
+  }
+  GatherAdaptiveResult gatherAdaptiveImpl(const vr_gather_spec &spec, NumericType relTarget, NumericType absTarget,
+                                          unsigned minSamples, unsigned maxSamples) {
+    if (!ctx_)
+      return {};
+    const uint32_t n = vr_num_primitives(ctx_);
+    std::vector<float> flux(n), err(n);
+    GatherAdaptiveResult r;
+    r.samplesUsed.resize(n);
+    static_assert(sizeof(unsigned) == sizeof(uint32_t), "samplesUsed is filled as uint32_t");
+    if (!reported(vr_gather_adaptive(ctx_, &spec, 0u, n, minSamples, maxSamples, (float)relTarget, (float)absTarget, flux.data(),
+                                     err.data(), reinterpret_cast<uint32_t *>(r.samplesUsed.data()), &r.info)))
+      return {};
+    r.flux.assign(flux.begin(), flux.end());
+    r.stdErr.assign(err.begin(), err.end());
+    return r;
   }
   std::vector<NumericType> fluxError(unsigned particleIdx, int kind) {
     std::vector<float> raw(ctx_ ? vr_num_primitives(ctx_) : 0);

@@ -52,6 +52,21 @@ class ParticlePOD(C.Structure):
                 ("params", C.c_float * 8)]
 
 
+class GatherSpecPOD(C.Structure):
+    """vr_gather_spec (include/viennaray_amd.h): what a sample of vr_gather_sums* / vr_gather_adaptive* is"""
+    _fields_ = [("cosinePower", C.c_float), ("mode", C.c_uint32), ("emission", C.c_void_p), ("paths", C.c_uint32),
+                ("reflection", C.c_uint32), ("maxBounces", C.c_uint32), ("reflectivity", C.c_void_p),
+                ("reflectivityScalar", C.c_float)]
+
+
+class GatherAdaptiveInfoPOD(C.Structure):
+    """vr_gather_adaptive_info (include/viennaray_amd.h)"""
+    _fields_ = [("rounds", C.c_uint32), ("unconverged", C.c_uint32), ("totalSamples", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # every symbol include/viennaray_amd.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -134,6 +149,14 @@ SIGNATURES = {
                                   _fp]),
     "vr_debug_gather_path": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _fp, C.c_float,
                                        C.c_uint32, _u32p, _fp, _u32p, _u32p, _fp, _fp, _fp]),
+    "vr_gather_sums_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, _vp, _vp, _vp]),
+    "vr_gather_sums": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vr_gather_adaptive_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_float, C.c_float, _vp, _vp, _vp, C.POINTER(GatherAdaptiveInfoPOD), _vp]),
+    "vr_gather_adaptive": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_float, C.c_float, _fp, _fp, _u32p, C.POINTER(GatherAdaptiveInfoPOD)]),
     "vr_radiosity_link_bytes": (C.c_uint64, [_vp, C.c_uint32]),
     "vr_radiosity_links_device": (C.c_int, [_vp, C.c_uint32, C.c_float, _vp]),
     "vr_radiosity_resident": (C.c_int, [_vp, C.c_uint32, C.c_float]),

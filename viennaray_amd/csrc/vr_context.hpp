@@ -387,6 +387,12 @@ struct vr_context {
   // the sums and the output staging are the gather's.  Grown behind host_waits only
   DevBuf<float> dPathRho, dPathIn;
   DevBuf<uint32_t> dPathWord;
+  // vr_gather_sums* / vr_gather_adaptive*: the int64 sums of the squared weights beside dGatherAcc, the two primitive
+  // lists a round reads and writes, the decide kernel's block counts with the word that comes back behind them, and the
+  // host forms' staging of stdErr and samplesUsed.  Grown behind host_waits only
+  DevBuf<unsigned long long> dGatherAccSq;
+  DevBuf<uint32_t> dGatherListA, dGatherListB, dGatherWords, dGatherUsed;
+  DevBuf<float> dGatherErr;
   // vr_radiosity_*: the link table of the last vr_radiosity_links_device (slots x samples int32 in leaf order,
   // vr_radiosity.hpp), its direct sums and leaf -> original id table, what it was built from, and a solve's work buffers
   // (leaf order: reflectivity, F, the two emission tables; the words that come back; the host forms' staging).  A table
@@ -544,6 +550,11 @@ int gather_refusal(vr_context *c, const char *api, uint32_t primFirst, uint32_t 
 int gather_params(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a, uint32_t primFirst, uint32_t primCount,
                   uint32_t samples, float cosinePower, uint32_t mode);
 void gather_cut_chunks(GatherArgs &a, unsigned slabs);
+// vr_gather_paths.cpp: what a path gather refuses beyond that, and its reflectivity table into leaf order (c->dPathRho),
+// shared with the sums and the adaptive gather (vr_gather_adaptive.cpp)
+int paths_refusal(vr_context *c, const char *api, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                  uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float scalar, const void *out);
+int paths_table(vr_context *c, const char *api, const float *rho);
 
 // a work buffer of the map or of a cast grows behind host_waits only (vr_api.cpp: a buffer that moves)
 template <class T> int map_grow(vr_context *c, DevBuf<T> &b, size_t n, bool &waited) {

@@ -10,7 +10,12 @@
 //                                  With PATH it follows a sample through its reflections (vr_gather_paths_device,
 //                                  vr_gather_paths.cpp): a front-side hit keeps the lane in the segment loop.
 //                                  With PATH == 2 it writes ONE path vertex by vertex (vr_debug_gather_path).
+//                                  With STAT it sums a range of chunks for a list of primitives and carries the sum of
+//                                  the squared weights beside the sum (vr_gather_sums_device, vr_gather_adaptive_device;
+//                                  vr_gather_adaptive.cpp).
 //   gather_finish_kernel           int64 sums -> floats.
+//   gather_decide_kernel           one round's verdict of the adaptive gather: outputs of the converged primitives, the
+//                                  others compacted in order into the next list.
 //   debug_gather_samples_kernel    the origin, the normal and a run of sample directions of ONE primitive
 //                                  (vr_debug_gather_samples): the device functions the first kernel uses.
 //
@@ -131,7 +136,10 @@ __device__ __forceinline__ void gather_path_put(const GatherArgs &a, unsigned v,
 // reaches the source plane or one of its other ends.  The cast state is the path's: the walls passed count over all of it.
 // PATH == 2 is vr_debug_gather_path: a range of ONE primitive, of whose samples lane 0 walks a.pathSample alone and
 // writes its vertices (gather_path_put) and the path's tail — the same loop, not a second one
-template <int GEO, int D, bool REC, int PATH = 0>
+// STAT: the sums of vr_gather_sums_device / vr_gather_adaptive_device (REC false, PATH 0 or 1).  The same samples and
+// walks; the item's chunk is a.chunkFirst + chunk, the lane's primitive comes from a.list where there is one, and the
+// lane carries a second int64, the sum of gather_q2, to a.accSq
+template <int GEO, int D, bool REC, int PATH = 0, int STAT = 0>
 __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TraceParams p, const GatherArgs a) {
   __shared__ float wallS[VR_WALL_TABLE];
   __shared__ unsigned stackS[VR_STACK_LDS * VR_BLOCK]; // [entry][thread of the block]
@@ -156,13 +164,19 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
   const unsigned run = GATHER_CHUNK / a.subs; // samples of a work item: a.subs runs per chunk
   const u64 perGroup = (u64)a.chunks * a.subs, items = (u64)a.groups * perGroup;
   for (u64 it = wave; it < items; it += waves) {
-    const unsigned sub = (unsigned)(it % a.subs), chunk = (unsigned)((it / a.subs) % a.chunks);
+    const unsigned sub = (unsigned)(it % a.subs), chunk = (STAT ? a.chunkFirst : 0u) + (unsigned)((it / a.subs) % a.chunks);
     if constexpr (PATH == 2) {
       if (chunk != a.pathSample / GATHER_CHUNK) // (wave-uniform) only the chunk that holds the one sample is looked at
         continue;
     }
-    const u64 t = (it / perGroup) * 64u + lane; // index into the range, or (whole scene) the leaf position
-    const bool valid = t < (u64)a.primCount;
+    u64 t = (it / perGroup) * 64u + lane; // index into the range, or (whole scene) the leaf position
+    bool valid = t < (u64)a.primCount;
+    if constexpr (STAT) {
+      if (a.list) { // (wave-uniform) the lane's primitive is the list's: entries < a.primCount (gather_decide_kernel)
+        valid = t < (u64)a.listCount;
+        t = valid ? a.list[t] : 0u;
+      }
+    }
     // ---- the lane's primitive ----
     GVec o = GVec{0.f, 0.f, 0.f}, m = GVec{0.f, 0.f, 1.f};
     unsigned orig = 0u;
@@ -185,6 +199,7 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
       r2 = gather_canon(gather_draw(k, lo, hi));
     }
     long long sum = 0;
+    [[maybe_unused]] long long sumSq = 0; // (STAT)
     for (unsigned j = jFirst; j < jEnd; ++j) {
       const GVec w0 = gather_direction(a.mode, D, r1, r2, m, a.cosinePower, frame);
       const float c = gather_c(w0, frame), mDotW = gather_dot(m, w0);
@@ -249,10 +264,13 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
       }
       if constexpr (PATH) {
         // (a path that ended on a primitive weighs 0 like one stopped on a wall; vr_debug_gather_path tells the ends apart)
-        if (walked)
-          sum += gather_q(gather_path_weight(s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL,
-                                             a.g, a.cosinePower, cEnd, T),
-                          a.wmax);
+        if (walked) {
+          const float w = gather_path_weight(s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL,
+                                             a.g, a.cosinePower, cEnd, T);
+          sum += gather_q(w, a.wmax);
+          if constexpr (STAT)
+            sumSq += gather_q2(w, a.wmax);
+        }
         if constexpr (PATH == 2) {
           if (walked) { // (lane 0, the one sample)
             const int end = s.prim >= 0 ? pathEnd : s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL;
@@ -271,7 +289,10 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
           if (end == GATHER_END_FRONT && haveEmission)
             emission = a.emission[(unsigned)s.prim]; // (the one load of the emission table: at a front-side hit)
         }
-        sum += gather_q(gather_weight(end, a.mode, a.g, a.cosinePower, c, mDotW, haveEmission, emission), a.wmax);
+        const float w = gather_weight(end, a.mode, a.g, a.cosinePower, c, mDotW, haveEmission, emission);
+        sum += gather_q(w, a.wmax);
+        if constexpr (STAT)
+          sumSq += gather_q2(w, a.wmax);
         if (REC) // (t < a.primCount <= a.linkSlots, the sample < a.samples: inside the table's linkSlots x samples entries)
           a.links[radiosity_link_index(a.linkSlots, (unsigned)t, chunk * GATHER_CHUNK + j)] =
               end == GATHER_END_FRONT ? (int)hitPos : RADIOSITY_NO_LINK;
@@ -283,6 +304,10 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
     }
     if (valid && sum != 0)
       atomicAdd(a.acc + (REC ? (unsigned)t : orig - a.primFirst), (unsigned long long)sum);
+    if constexpr (STAT) {
+      if (valid && sumSq != 0)
+        atomicAdd(a.accSq + (orig - a.primFirst), (unsigned long long)sumSq);
+    }
   }
 #ifdef VR_DIAG
   if constexpr (PATH) { // the rounds of segments and the segments walked in them: vr_gather_paths.cpp prints the two sums
@@ -299,6 +324,69 @@ __global__ void gather_finish_kernel(const unsigned long long *acc, unsigned n, 
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n)
     out[i] = gather_result((long long)acc[i], samples);
+}
+
+// One round's verdict of vr_gather_adaptive_device: one thread per entry of the current list, a block per
+// GATHER_DECIDE_BLOCK entries.  The next list keeps the order of the current one, so a wave's origins stay neighbours:
+// a lane's place is (kept entries of the blocks before) + (of the block's waves before) + (of the wave's lanes before) —
+// wave ballots and a block prefix, no atomic append.  WRITE false: the block's count alone, for a list of more than one
+// block; WRITE true: the outputs and the next list, the block's base summed from those counts (none for block 0)
+template <bool WRITE> __global__ __launch_bounds__(GATHER_DECIDE_BLOCK) void gather_decide_kernel(const GatherDecideArgs d) {
+  __shared__ unsigned waveCount[GATHER_DECIDE_BLOCK / 64];
+  __shared__ unsigned red[GATHER_DECIDE_BLOCK];
+  const unsigned e = blockIdx.x * GATHER_DECIDE_BLOCK + threadIdx.x; // (count <= 2^32 - 1: a primitive range)
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const bool have = e < d.count;
+  unsigned entry = 0u, idx = 0u;
+  long long S1 = 0, S2 = 0;
+  bool keep = false;
+  if (have) {
+    entry = d.list ? d.list[e] : e;
+    idx = d.origWords ? d.origWords[(size_t)entry * d.origStride + d.origOffset] : entry; // < the range's primCount
+    S1 = (long long)d.acc[idx];
+    S2 = (long long)d.accSq[idx];
+    keep = !gather_converged(S1, S2, d.samples, d.rel, d.abs);
+  }
+  const unsigned long long mask = ballot64(keep);
+  if (lane == 0u)
+    waveCount[wave] = (unsigned)__popcll(mask);
+  if constexpr (WRITE) { // the kept entries of the blocks before this one
+    unsigned part = 0u;
+    for (unsigned b = threadIdx.x; b < blockIdx.x; b += GATHER_DECIDE_BLOCK)
+      part += d.blockCounts[b];
+    red[threadIdx.x] = part;
+  }
+  __syncthreads();
+  unsigned before = 0u, total = 0u;
+  for (unsigned w = 0; w < GATHER_DECIDE_BLOCK / 64; ++w) {
+    const unsigned n = waveCount[w];
+    before += w < wave ? n : 0u;
+    total += n;
+  }
+  if constexpr (!WRITE) {
+    if (threadIdx.x == 0u)
+      d.blockCounts[blockIdx.x] = total;
+  } else {
+    for (unsigned s = GATHER_DECIDE_BLOCK / 2; s > 0u; s >>= 1) {
+      if (threadIdx.x < s)
+        red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    const unsigned base = red[0];
+    if (have) {
+      if (!keep || d.last) {
+        d.flux[idx] = gather_result(S1, d.samples);
+        if (d.stdErr)
+          d.stdErr[idx] = (float)sqrt(gather_stderr2(S1, S2, d.samples));
+        if (d.samplesUsed)
+          d.samplesUsed[idx] = d.samples;
+      }
+      if (keep) // (base + before + the lanes before < the kept entries of the whole list <= count: inside `next`)
+        d.next[base + before + (unsigned)__popcll(mask & ((1ull << lane) - 1ull))] = entry;
+    }
+    if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 0u)
+      *d.word = base + total;
+  }
 }
 
 // one thread per sample first + k of primitive a.primFirst; thread 0 also writes the origin and the normal
@@ -344,6 +432,39 @@ hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const Gat
   if (waves == 0)
     return hipSuccess;
   const dim3 g(waves > perBlock ? waves / perBlock : 1u), b(waves > perBlock ? (unsigned)VR_BLOCK : waves * 64u);
+  if (a.stat) { // the sums: chunks from a.chunkFirst on, a list of primitives or all of the range, no recording
+    if (a.links || !a.accSq || a.paths > 1u || (a.list ? a.listCount > a.primCount : false) ||
+        (unsigned long long)(a.chunkFirst + (unsigned long long)a.chunks) * GATHER_CHUNK > a.samples)
+      return hipErrorInvalidValue;
+    if (a.paths && (a.emission || a.mode != GATHER_NORMAL || a.reflection > GATHER_REFLECT_DIFFUSE || a.maxBounces > GATHER_MAX_BOUNCES))
+      return hipErrorInvalidValue;
+    if (geo == 0) {
+      if (D == 2) {
+        if (a.paths)
+          hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 1, 1>), g, b, 0, st, p, a);
+        else
+          hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 0, 1>), g, b, 0, st, p, a);
+      } else {
+        if (a.paths)
+          hipLaunchKernelGGL((gather_samples_kernel<0, 3, false, 1, 1>), g, b, 0, st, p, a);
+        else
+          hipLaunchKernelGGL((gather_samples_kernel<0, 3, false, 0, 1>), g, b, 0, st, p, a);
+      }
+    } else {
+      if (D == 2) {
+        if (a.paths)
+          hipLaunchKernelGGL((gather_samples_kernel<1, 2, false, 1, 1>), g, b, 0, st, p, a);
+        else
+          hipLaunchKernelGGL((gather_samples_kernel<1, 2, false, 0, 1>), g, b, 0, st, p, a);
+      } else {
+        if (a.paths)
+          hipLaunchKernelGGL((gather_samples_kernel<1, 3, false, 1, 1>), g, b, 0, st, p, a);
+        else
+          hipLaunchKernelGGL((gather_samples_kernel<1, 3, false, 0, 1>), g, b, 0, st, p, a);
+      }
+    }
+    return hipGetLastError();
+  }
   if (a.links) { // the recording: the whole scene in leaf order, NORMAL samples, a table of linkSlots x samples entries
     if (a.paths || a.leafOfOrig || a.emission || a.mode != GATHER_NORMAL || a.primFirst != 0u || a.linkSlots < a.primCount)
       return hipErrorInvalidValue;
@@ -394,6 +515,17 @@ hipError_t launch_gather_finish(const unsigned long long *acc, unsigned n, unsig
   if (n == 0)
     return hipSuccess;
   hipLaunchKernelGGL(gather_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, acc, n, samples, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_decide(const GatherDecideArgs &d, hipStream_t st) {
+  if (d.count == 0 || !d.acc || !d.accSq || !d.next || !d.blockCounts || !d.word || !d.flux || d.samples < 2u)
+    return hipErrorInvalidValue;
+  // one launch where the list fits a block, otherwise the blocks' counts first
+  const unsigned blocks = (unsigned)(((unsigned long long)d.count + GATHER_DECIDE_BLOCK - 1u) / GATHER_DECIDE_BLOCK);
+  if (blocks > 1u)
+    hipLaunchKernelGGL((gather_decide_kernel<false>), dim3(blocks), dim3(GATHER_DECIDE_BLOCK), 0, st, d);
+  hipLaunchKernelGGL((gather_decide_kernel<true>), dim3(blocks), dim3(GATHER_DECIDE_BLOCK), 0, st, d);
   return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // vr_gather.hpp — the arithmetic of gatherFlux (vr_gather.hip: gather_samples_kernel) in plain C++: the host compiler takes
 // this file alone (tests/aux/gather.cpp), the kernel includes it.  What a sample IS lives here — the chunk's engine seed,
 // the direction from (r1, r2, normal, mode, D), the outcome -> weight rule, the constants g_D(n), the quantisation q() and
-// the final division — so that the host program and the device compute the same bits from the same text: sincosf / powf
+// the final division, the quantised square q2() and the standard error of the adaptive gather (tests/aux/
+// gather_adaptive.cpp) — so that the host program and the device compute the same bits from the same text: sincosf / powf
 // are vr_libm.hpp's on both sides, every other operation is a single IEEE float or double operation in a fixed order
 // (-ffp-contract=off).  include/viennaray_amd.h has the definition this implements.
 #pragma once
@@ -186,6 +187,71 @@ VR_GATHER_FN int64_t gather_q(float w, float wmax) {
 // out[i] from the int64 sum of K samples
 VR_GATHER_FN float gather_result(int64_t sum, uint32_t samples) {
   return (float)((double)sum / 1099511627776.0 / (double)samples);
+}
+
+// ---- the second sum and the standard error (vr_gather_sums*, vr_gather_adaptive*) ------------------------------------
+constexpr int GATHER_SQ_FRAC_BITS = 28;   // the fixed point of a squared weight
+constexpr int GATHER_SQ_CUT_LOG2 = 11;    // a squared weight is that of min(w, wmax, 2^11)
+// q2(w): the quantised SQUARE of the weight q() counts.  0 for a weight that is not positive (NaN included); otherwise
+// wc = min(w, wmax, 2048) and (int64)(wc * wc * 2^28 + 0.5) — the product of two floats is exact in double.
+// The sum of `budget` such terms stays within 2^61 for every budget the gather accepts (samples x g <= 2^22, g >= 1):
+//   budget <= 2^11:  wc <= 2^11, a term <= 2^(22 + 28) = 2^50, the sum <= 2^11 x 2^50 = 2^61;
+//   budget  = 2^b > 2^11:  wc <= wmax = 2^(22 - b), a term <= 2^(72 - 2b), the sum <= 2^(72 - b) < 2^61.
+// (tests/aux/gather_adaptive.cpp walks every power-of-two budget.)
+static_assert(GATHER_SQ_CUT_LOG2 + 2 * GATHER_SQ_CUT_LOG2 + GATHER_SQ_FRAC_BITS == 61 &&
+                  2 * 22 + GATHER_SQ_FRAC_BITS - (GATHER_SQ_CUT_LOG2 + 1) < 61,
+              "a primitive's int64 sum of squares cannot overflow");
+VR_GATHER_FN int64_t gather_q2(float w, float wmax) {
+  if (!(w > 0.f))
+    return 0;
+  float wc = w > wmax ? wmax : w;
+  wc = wc > 2048.f ? 2048.f : wc;
+  return (int64_t)((double)wc * (double)wc * 268435456.0 + 0.5);
+}
+// The mean m1 and the squared standard error se2 of the mean of K samples (K >= 2; the gather's K is >= 64) from the two
+// exact sums S1 = sum q(w), S2 = sum q2(w):
+//   m1 = (double)S1 * 2^-40 / K;  m2 = (double)S2 * 2^-28 / K;  v = m2 - m1 * m1, 0 unless v > 0;  se2 = v / (K - 1).
+// Every operation is one IEEE double operation in this order, contraction off, so that the host, the device and numpy
+// float64 agree bit for bit
+#if defined(__clang__)
+#define VR_GATHER_NO_CONTRACT _Pragma("clang fp contract(off)")
+#define VR_GATHER_NO_CONTRACT_ATTR
+#elif defined(__GNUC__)
+#define VR_GATHER_NO_CONTRACT
+#define VR_GATHER_NO_CONTRACT_ATTR __attribute__((optimize("fp-contract=off")))
+#else
+#define VR_GATHER_NO_CONTRACT
+#define VR_GATHER_NO_CONTRACT_ATTR
+#endif
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN void gather_moments(int64_t S1, int64_t S2, uint32_t K, double &m1, double &se2) {
+  VR_GATHER_NO_CONTRACT
+  const double k = (double)K;
+  m1 = (double)S1 * 9.094947017729282379150390625e-13 / k; // 2^-40
+  const double m2 = (double)S2 * 3.7252902984619140625e-09 / k; // 2^-28
+  const double sq = m1 * m1;
+  double v = m2 - sq;
+  if (!(v > 0.))
+    v = 0.;
+  se2 = v / (k - 1.);
+}
+VR_GATHER_FN double gather_stderr2(int64_t S1, int64_t S2, uint32_t K) {
+  double m1, se2;
+  gather_moments(S1, S2, K, m1, se2);
+  return se2;
+}
+// The stopping rule of a primitive after K samples: tol = max(rel * m1, abs), converged if and only if se2 <= tol * tol.
+// rel == abs == 0 means "never": every primitive runs to maxSamples, one of zero variance included.  A primitive whose
+// samples so far all weigh 0 has m1 = se2 = 0 and is converged at minSamples under any positive target: the call cannot
+// know better — nothing it has seen tells a primitive in full shadow from one whose first bright sample is still to come
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN bool gather_converged(int64_t S1, int64_t S2, uint32_t K, float rel, float abs) {
+  VR_GATHER_NO_CONTRACT
+  if (!(rel > 0.f) && !(abs > 0.f))
+    return false;
+  double m1, se2;
+  gather_moments(S1, S2, K, m1, se2);
+  const double r = (double)rel * m1, a = (double)abs;
+  const double tol = r > a ? r : a;
+  return se2 <= tol * tol;
 }
 
 // ---- gatherPaths (vr_gather_paths*): a sample followed through its reflections ---------------------------------------

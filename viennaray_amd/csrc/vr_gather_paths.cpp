@@ -22,8 +22,8 @@ static_assert(VR_GATHER_REFLECT_SPECULAR == vr::GATHER_REFLECT_SPECULAR && VR_GA
 namespace vr {
 
 // what every form refuses before it touches anything, beyond the gather's own checks
-static int paths_refusal(vr_context *c, const char *api, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
-                         uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float scalar, const void *out) {
+int paths_refusal(vr_context *c, const char *api, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                  uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float scalar, const void *out) {
   const std::string name = api;
   VR_TRY(gather_refusal(c, api, primFirst, primCount, samples, cosinePower, VR_GATHER_NORMAL, nullptr, out));
   if (reflection != VR_GATHER_REFLECT_SPECULAR && reflection != VR_GATHER_REFLECT_DIFFUSE)
@@ -36,7 +36,7 @@ static int paths_refusal(vr_context *c, const char *api, uint32_t primFirst, uin
 }
 
 // the table (device memory, by original id) into leaf order and its verdict: ONE word back, the lowest refused index
-static int paths_table(vr_context *c, const char *api, const float *rho) {
+int paths_table(vr_context *c, const char *api, const float *rho) {
   const uint32_t n = c->geo.numPrims;
   bool waited = false;
   VR_TRY(map_grow(c, c->dPathRho, n, waited));

@@ -173,7 +173,33 @@ struct GatherArgs {
   // vr_debug_gather_path (launch_debug_gather_path fills these): the one sample whose path is written
   uint32_t pathSample, pathMaxVertices;
   float *pathVertices, *pathTail;
+  // the sums of vr_gather_sums_device / vr_gather_adaptive_device (stat == 0: none of this is read; no recording, paths
+  // 0 or 1): the launch covers chunks chunkFirst .. chunkFirst + chunks - 1 of a call of samples = 64 (chunkFirst + chunks)
+  // samples or more, wmax that of the call's budget; accSq: the int64 sums of the squared weights (gather_q2), indexed as
+  // acc; list (nullptr: every primitive of the range): listCount entries, each an index into the range — a LEAF
+  // position where leafOfOrig is nullptr — of which lane l of group g takes list[64 g + l]; groups = ceil(listCount / 64)
+  uint32_t stat, chunkFirst;
+  unsigned long long *accSq;
+  const uint32_t *list;
+  uint32_t listCount;
 };
+// one round's verdict of vr_gather_adaptive_device (vr_gather.hip: gather_decide_kernel).  Entry e of the current list
+// (list == nullptr: e itself) is a primitive of the range as GatherArgs::list names it; origWords != nullptr (the whole
+// scene): its index into acc / accSq and the outputs is origWords[entry * origStride + origOffset], the original id in
+// the packed record, otherwise the entry itself.  A converged primitive — every primitive when `last` — gets flux,
+// stdErr and samplesUsed (either may be nullptr) written; the others go to `next` in the order of the current list.
+// *word: how many those are.  blockCounts: ceil(count / GATHER_DECIDE_BLOCK) words of scratch
+struct GatherDecideArgs {
+  const unsigned long long *acc, *accSq;
+  const uint32_t *list, *origWords;
+  uint32_t *next, *blockCounts, *word;
+  float *flux, *stdErr;
+  uint32_t *samplesUsed;
+  uint32_t count, samples, origStride, origOffset, last;
+  float rel, abs;
+};
+constexpr unsigned GATHER_DECIDE_BLOCK = 1024;
+hipError_t launch_gather_decide(const GatherDecideArgs &d, hipStream_t st);
 // p, slabs: as launch_cast_rays.  One launch of at most min(slabs, groups x chunks x subs) waves
 hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned slabs, hipStream_t st);
 hipError_t launch_gather_finish(const unsigned long long *acc, unsigned n, unsigned samples, float *out, hipStream_t st);

@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from . import capi
-from .capi import VrError, TraceInfoPOD, ParticlePOD
+from .capi import VrError, TraceInfoPOD, ParticlePOD, GatherSpecPOD, GatherAdaptiveInfoPOD
 
 
 class BoundaryCondition(enum.IntEnum):  # rayBoundary.hpp:10-14
@@ -1005,6 +1005,115 @@ class Trace:
         return {"ids": ids[:v].astype(np.int64), "points": data[:v, 0], "arriving": data[:v, 1], "normals": data[:v, 2],
                 "leaving": data[:v, 3], "numVertices": int(count.value), "end": int(end.value), "direction": final,
                 "throughput": np.float32(T.value), "weight": np.float32(w.value)}
+
+    # --- gather to a target error: sums, standard error, adaptive sample counts (vr_gather_sums*, vr_gather_adaptive*) --
+    def _gatherRange(self, name, primFirst, primCount, *counts):
+        n = int(self._L.vr_num_primitives(self._h))
+        primFirst = int(primFirst)
+        primCount = max(0, n - primFirst) if primCount is None else int(primCount)
+        if primFirst < 0 or primCount < 0 or any(int(v) < 0 for v in counts):
+            raise ValueError("%s: counts, primFirst and primCount must not be negative" % name)
+        return n, primFirst, primCount
+
+    def _fluxSpec(self, name, n, cosinePower, mode, emission, numpy):
+        """(spec, host?, what the spec points to) of a gatherFlux sample"""
+        spec = GatherSpecPOD(cosinePower=float(cosinePower), mode=int(mode), paths=0)
+        host = numpy if emission is None else not hasattr(emission, "data_ptr")
+        keep = None
+        if emission is not None and host:
+            keep = np.ascontiguousarray(emission, dtype=np.float32).reshape(-1)
+            if keep.size != n:
+                raise ValueError("%s: emission has %d entries, the scene %d primitives" % (name, keep.size, n))
+            spec.emission = keep.ctypes.data
+        elif emission is not None:
+            _check_device_tensor(name, "emission", emission, self._device, "torch.float32", [(n,)])
+            keep = emission
+            spec.emission = emission.data_ptr()
+        return spec, host, keep
+
+    def _pathsSpec(self, name, sticking, reflectivity, reflection, maxBounces, cosinePower, numpy):
+        """(spec, host?, what the spec points to) of a gatherPaths sample"""
+        device, scalar, table = self._pathReflectivity(name, sticking, reflectivity)
+        spec = GatherSpecPOD(cosinePower=float(cosinePower), mode=int(GatherMode.NORMAL), paths=1, reflection=int(reflection),
+                             maxBounces=int(maxBounces), reflectivityScalar=scalar)
+        if table is not None:
+            spec.reflectivity = table.data_ptr() if device else table.ctypes.data
+        return spec, (not device and (table is not None or numpy)), table
+
+    def _gatherSums(self, spec, host, primFirst, primCount, chunkFirst, chunks, budget):
+        if host:
+            s1, s2 = np.empty(primCount, dtype=np.int64), np.empty(primCount, dtype=np.int64)
+            i64 = C.POINTER(C.c_int64)
+            self._check(self._L.vr_gather_sums(self._h, C.byref(spec), primFirst, primCount, int(chunkFirst), int(chunks),
+                                               int(budget), s1.ctypes.data_as(i64), s2.ctypes.data_as(i64)))
+            return s1, s2
+        import torch
+        dev = torch.device("cuda", self._device)
+        s1, s2 = torch.empty(primCount, dtype=torch.int64, device=dev), torch.empty(primCount, dtype=torch.int64, device=dev)
+        self._check(self._L.vr_gather_sums_device(self._h, C.byref(spec), primFirst, primCount, int(chunkFirst), int(chunks),
+                                                  int(budget), C.c_void_p(s1.data_ptr()), C.c_void_p(s2.data_ptr()),
+                                                  C.c_void_p(self._torch_stream())))
+        return s1, s2
+
+    def _gatherAdaptive(self, spec, host, primFirst, primCount, target, absTarget, minSamples, maxSamples, returnInfo):
+        info = GatherAdaptiveInfoPOD()
+        if host:
+            flux, err = np.empty(primCount, dtype=np.float32), np.empty(primCount, dtype=np.float32)
+            used = np.empty(primCount, dtype=np.uint32)
+            self._check(self._L.vr_gather_adaptive(self._h, C.byref(spec), primFirst, primCount, int(minSamples),
+                                                   int(maxSamples), float(target), float(absTarget), _fptr(flux), _fptr(err),
+                                                   used.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info)))
+        else:
+            import torch
+            dev = torch.device("cuda", self._device)
+            flux, err = torch.empty(primCount, dtype=torch.float32, device=dev), torch.empty(primCount, dtype=torch.float32, device=dev)
+            store = torch.empty(primCount, dtype=torch.int32, device=dev)  # (the uint32 counts, at most 2^22)
+            self._check(self._L.vr_gather_adaptive_device(
+                self._h, C.byref(spec), primFirst, primCount, int(minSamples), int(maxSamples), float(target), float(absTarget),
+                C.c_void_p(flux.data_ptr()), C.c_void_p(err.data_ptr()), C.c_void_p(store.data_ptr()), C.byref(info),
+                C.c_void_p(self._torch_stream())))
+            used = store
+        return (flux, err, used, info.as_dict()) if returnInfo else (flux, err, used)
+
+    def gatherFluxAdaptive(self, target, minSamples=64, maxSamples=4096, absTarget=0.0, cosinePower=1.0, mode=GatherMode.NORMAL,
+                           emission=None, primFirst=0, primCount=None, returnInfo=False, numpy=False):
+        """gatherFlux to a target error: every primitive starts with minSamples samples (a multiple of 64) and doubles its
+        own count until the standard error of its mean is at most max(target x mean, absTarget) or maxSamples
+        (minSamples times a power of two) is reached.  Returns (flux, stdErr, samples): float32, float32 and the sample
+        count used, one per primitive of the range; with returnInfo a dict {rounds, unconverged, totalSamples} as well.
+        flux[i] has the bits of gatherFlux(samples[i]) wherever no weight exceeds 2^22 / maxSamples (every NORMAL
+        weight).  target = absTarget = 0 runs every primitive to maxSamples.  A primitive whose first minSamples samples
+        all weigh 0 stops there with flux 0 and stdErr 0: the call cannot know better.  A pure function of scene,
+        setRngSeed and arguments; tensors and numpy arrays as gatherFlux (vr_gather_adaptive*)."""
+        n, primFirst, primCount = self._gatherRange("gatherFluxAdaptive", primFirst, primCount, minSamples, maxSamples)
+        spec, host, keep = self._fluxSpec("gatherFluxAdaptive", n, cosinePower, mode, emission, numpy)
+        return self._gatherAdaptive(spec, host, primFirst, primCount, target, absTarget, minSamples, maxSamples, returnInfo)
+
+    def gatherPathsAdaptive(self, target, sticking=None, reflectivity=None, reflection=GatherReflection.SPECULAR, maxBounces=64,
+                            minSamples=64, maxSamples=4096, absTarget=0.0, cosinePower=1.0, primFirst=0, primCount=None,
+                            returnInfo=False, numpy=False):
+        """gatherPaths to a target error, as gatherFluxAdaptive: (flux, stdErr, samples), plus the info dict when asked;
+        sticking | reflectivity, reflection and maxBounces as gatherPaths, tensors and numpy arrays likewise."""
+        _, primFirst, primCount = self._gatherRange("gatherPathsAdaptive", primFirst, primCount, minSamples, maxSamples, maxBounces)
+        spec, host, keep = self._pathsSpec("gatherPathsAdaptive", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
+        return self._gatherAdaptive(spec, host, primFirst, primCount, target, absTarget, minSamples, maxSamples, returnInfo)
+
+    def gatherFluxSums(self, chunkFirst, chunks, budget, cosinePower=1.0, mode=GatherMode.NORMAL, emission=None, primFirst=0,
+                       primCount=None, numpy=False):
+        """(sum, sumSq): per primitive of the range the exact int64 sums of gatherFlux's quantised weights (2^-40) and of
+        their squares (2^-28) over samples [64 chunkFirst, 64 (chunkFirst + chunks)) of a call of `budget` samples.
+        float32(sum / 2^40 / K) over chunks [0, K / 64) with budget K has the bits of gatherFlux(K); sums over adjacent
+        chunk ranges add (vr_gather_sums*)."""
+        n, primFirst, primCount = self._gatherRange("gatherFluxSums", primFirst, primCount, chunkFirst, chunks, budget)
+        spec, host, keep = self._fluxSpec("gatherFluxSums", n, cosinePower, mode, emission, numpy)
+        return self._gatherSums(spec, host, primFirst, primCount, chunkFirst, chunks, budget)
+
+    def gatherPathsSums(self, chunkFirst, chunks, budget, sticking=None, reflectivity=None, reflection=GatherReflection.SPECULAR,
+                        maxBounces=64, cosinePower=1.0, primFirst=0, primCount=None, numpy=False):
+        """(sum, sumSq) as gatherFluxSums, of gatherPaths's samples"""
+        _, primFirst, primCount = self._gatherRange("gatherPathsSums", primFirst, primCount, chunkFirst, chunks, budget, maxBounces)
+        spec, host, keep = self._pathsSpec("gatherPathsSums", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
+        return self._gatherSums(spec, host, primFirst, primCount, chunkFirst, chunks, budget)
 
     # --- radiosity solve: the steady-state flux of a diffusely re-emitting species (vr_radiosity_*) ------------------
     def radiosityLinkBytes(self, samples):
