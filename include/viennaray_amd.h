@@ -646,6 +646,82 @@ int vr_gather_adaptive_device(vr_context *ctx, const vr_gather_spec *spec, uint3
 int vr_gather_adaptive(vr_context *ctx, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount,
                        uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux, float *stdErr,
                        uint32_t *samplesUsed, vr_gather_adaptive_info *info);
+/* ---- angular gather (not in the reference): a path weighed by tabulated source radiance, sticking and yield -------------
+ * vr_gather_paths knows one physics: a power-cosine source, a constant reflectivity, a sample that counts 1 whatever its
+ * angle of incidence.  These calls take up to three tabulated ANGULAR LAWS and are otherwise vr_gather_paths bit for bit:
+ * scene, range, o_i, m_i, sample numbering, chunk engines, initial direction, segments, wall budget, ends, q(), q2(), wmax,
+ * the sums and the final division.
+ * Law      M float32 values, 2 <= M <= 256, read as the piecewise-linear function of a cosine x in [0, 1] with nodes at
+ *          x_k = k / (M - 1).  The look-up law(t, M, x), float32, one IEEE operation per step, no contraction:
+ *            xs = min(max(x, 0), 1) * (float)(M - 1);  k = min((int)xs, M - 2);  f = xs - (float)k;
+ *            value = t[k] + f * (t[k + 1] - t[k]).
+ *          A NaN x reads as 0.  Host, device and numpy float32 agree bit for bit.  A law whose table is NULL is absent.
+ * sourceLaw        L(c): the source's radiance as a function of c = u . w, relative to a Lambertian source: the forward
+ *                  source has the direction density L(c) c / Z per solid angle; L = c^(n - 1) is the power cosine.  The
+ *                  library normalises on the host, in double, by exact integration of the interpolant: 3-D
+ *                  Z = 2 pi int_0^1 L(c) c dc; 2-D Z = 2 int_0^1 L(c) c / sqrt(1 - c^2) dc (per segment, L = a + b c: the
+ *                  antiderivative -a sqrt(1 - c^2) + b (asin c - c sqrt(1 - c^2)) / 2).  g_L = (float)(pi / Z) in 3-D,
+ *                  (float)(2 / Z) in 2-D.  A path that reaches the source plane with c_end > 0 weighs
+ *                  (g_L * law(L, c_end)) * T in place of g c_end^(n - 1) * T.  Entries finite and >= 0, not all 0;
+ *                  spec->cosinePower must be 1.
+ * reflectivityLaw  R(mu): the share that is NOT absorbed, as a function of mu = n_j . (the direction the path LEAVES the
+ *                  vertex along) — unprojected, after the reflection, (n.x d.x + n.y d.y) + n.z d.z — the forward particle's
+ *                  cosine of incidence.  For a mirror that is the arriving ray's cosine; for a DIFFUSE vertex the cosine of
+ *                  the direction just drawn, the adjoint of "sticks by its incidence, re-emits by the cosine law".
+ *                  T <- (T * rho[j]) * R(mu): two multiplies in this order; T == 0 after either ends the path
+ *                  (VR_GATHER_END_ABSORBED).  Entries in [0, 1].
+ * yieldLaw         Y(mu0), mu0 = m_i . w_0 of the sample's INITIAL direction against the starting primitive's own normal.
+ *                  One more multiply, last: w = ((g_L L(c_end) or g c_end^(n - 1)) * T) * Y(mu0).  Entries finite and >= 0;
+ *                  they may exceed 1.
+ * Bounds   wbound = (g_L max L or g) max Y.  A call with samples x wbound > 2^22 is refused as samples x g is; the
+ *          per-sample variance is at most F (wbound - F).  The source law WEIGHS the samples, it does not place them: a
+ *          narrow L has the variance g_L max L says it has (vr_gather_angular_adaptive's stdErr shows it).
+ * Identities  laws == NULL or all three tables NULL: the bits of vr_gather_paths / vr_gather_sums / vr_gather_adaptive /
+ *          vr_debug_gather_path.  All-ones tables of any M: those bits too (g_L is exactly 1.0f).  R = 0.5 everywhere with
+ *          reflectivity rho: the bits of vr_gather_paths at rho / 2.
+ * Coned-cosine reflection is not offered: its kernel p(w_out | w_in) is not symmetric (the cone's opening depends on the
+ * incidence), so a backward path cannot reverse it step by step as it reverses a mirror or a Lambertian re-emission.
+ * spec: a vr_gather_spec with paths == 1, mode VR_GATHER_NORMAL and emission NULL (anything else is refused);
+ * spec->reflectivity is DEVICE memory in the _device forms and HOST memory in the others.  The tables of vr_gather_laws are
+ * always HOST pointers: they are tiny, validated and normalised on the host, and copied at the call.
+ * Refused, outputs untouched and the context usable, message in vr_last_error:
+ *   VR_E_INVALID  what the matching entry point without laws refuses; a count outside 2 .. 256; an entry outside its
+ *                 law's range (the message names the law and the lowest such index); a source law that is all 0, or with
+ *                 cosinePower != 1; samples (budget, maxSamples) x wbound > 2^22.
+ *   VR_E_STATE    as vr_gather_flux_device.
+ * Streams, work buffers and "changes nothing of a finished apply": as the matching entry point without laws.
+ * Outputs as those of vr_gather_paths*, vr_gather_sums*, vr_gather_adaptive* and vr_debug_gather_path */
+typedef struct vr_gather_laws {
+  const float *sourceLaw;       /* NULL or sourceCount HOST floats */
+  uint32_t sourceCount;
+  const float *reflectivityLaw; /* NULL or reflectivityCount HOST floats */
+  uint32_t reflectivityCount;
+  const float *yieldLaw;        /* NULL or yieldCount HOST floats */
+  uint32_t yieldCount;
+} vr_gather_laws;
+int vr_gather_angular_device(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                             uint32_t primCount, uint32_t samples, float *out, void *stream);
+int vr_gather_angular(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                      uint32_t primCount, uint32_t samples, float *out);
+int vr_gather_angular_sums_device(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                                  uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum,
+                                  int64_t *sumSq, void *stream);
+int vr_gather_angular_sums(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                           uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum,
+                           int64_t *sumSq);
+int vr_gather_angular_adaptive_device(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws,
+                                      uint32_t primFirst, uint32_t primCount, uint32_t minSamples, uint32_t maxSamples,
+                                      float relTarget, float absTarget, float *flux, float *stdErr, uint32_t *samplesUsed,
+                                      vr_gather_adaptive_info *info, void *stream);
+int vr_gather_angular_adaptive(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                               uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget,
+                               float *flux, float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info);
+/* ONE path as vr_debug_gather_path records it (spec->reflectivity: NULL or HOST floats), weighed by the laws: the leaving
+ * direction and the normal of every vertex give its mu, *throughput and *weight are the path's */
+int vr_debug_gather_angular_path(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t prim,
+                                 uint32_t sample, uint32_t maxVertices, uint32_t *vertexIds, float *vertexData,
+                                 uint32_t *numVertices, uint32_t *end, float *finalDirection3, float *throughput,
+                                 float *weight);
 /* ---- radiosity solve (not in the reference): the steady-state flux of a diffusely re-emitting species ------------------
  * vr_gather_flux with an emission table is one radiosity iteration, and its walks are a constant of the scene.  These
  * calls record them once — a link table — and iterate over the table on the device without walking again.

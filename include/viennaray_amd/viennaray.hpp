@@ -1448,6 +1448,101 @@ public:
     return spec;
   }
 
+  // ---- angular gather (not in the reference; vr_gather_angular*, whose header comment has the definition): gatherPaths
+  //      with up to three tabulated laws of a cosine in [0, 1] — the source's radiance L(c), the reflectivity R(mu) by the
+  //      cosine of incidence, the yield Y(mu0) by the sample's own starting angle.  With no law, or all-ones laws, the
+  //      results are gatherPaths's word for word.
+  /// the laws of an angular gather: each empty (absent) or 2 .. 256 values, nodes at k / (M - 1); the object must outlive
+  /// the vr_gather_laws taken from it
+  struct GatherLaws {
+    std::vector<float> source, reflectivity, yield;
+    [[nodiscard]] vr_gather_laws pod() const {
+      vr_gather_laws l{};
+      l.sourceLaw = source.empty() ? nullptr : source.data();
+      l.sourceCount = (uint32_t)source.size();
+      l.reflectivityLaw = reflectivity.empty() ? nullptr : reflectivity.data();
+      l.reflectivityCount = (uint32_t)reflectivity.size();
+      l.yieldLaw = yield.empty() ? nullptr : yield.data();
+      l.yieldCount = (uint32_t)yield.size();
+      return l;
+    }
+  };
+  /// one value per primitive (empty if it was refused); sticking: the scalar of gatherPaths
+  [[nodiscard]] std::vector<NumericType> gatherAngular(unsigned samples, const GatherLaws &laws, NumericType sticking,
+                                                       GatherReflection reflection = GatherReflection::SPECULAR,
+                                                       unsigned maxBounces = 64, NumericType cosinePower = 1) {
+    if (!ctx_)
+      return {};
+    const vr_gather_spec spec = pathsSpec(nullptr, 1.f - (float)sticking, reflection, maxBounces, cosinePower);
+    const vr_gather_laws l = laws.pod();
+    std::vector<float> raw(vr_num_primitives(ctx_));
+    if (!reported(vr_gather_angular(ctx_, &spec, &l, 0u, (uint32_t)raw.size(), samples, raw.data())))
+      return {};
+    return std::vector<NumericType>(raw.begin(), raw.end());
+  }
+  /// spec.reflectivity and dOut (primCount floats) are DEVICE memory, the laws the host's; gatherPathsDevice's stream rules
+  bool gatherAngularDevice(const vr_gather_spec &spec, const GatherLaws &laws, unsigned primFirst, unsigned primCount,
+                           unsigned samples, float *dOut, void *stream = nullptr) {
+    const vr_gather_laws l = laws.pod();
+    return ctx_ && reported(vr_gather_angular_device(ctx_, &spec, &l, primFirst, primCount, samples, dOut, stream));
+  }
+  [[nodiscard]] GatherAdaptiveResult gatherAngularAdaptive(NumericType relTarget, const GatherLaws &laws, NumericType sticking,
+                                                           GatherReflection reflection = GatherReflection::SPECULAR,
+                                                           unsigned maxBounces = 64, unsigned minSamples = 64,
+                                                           unsigned maxSamples = 4096, NumericType absTarget = 0,
+                                                           NumericType cosinePower = 1) {
+    if (!ctx_)
+      return {};
+    const vr_gather_spec spec = pathsSpec(nullptr, 1.f - (float)sticking, reflection, maxBounces, cosinePower);
+    const vr_gather_laws l = laws.pod();
+    const uint32_t n = vr_num_primitives(ctx_);
+    std::vector<float> flux(n), err(n);
+    GatherAdaptiveResult r;
+    r.samplesUsed.resize(n);
+    if (!reported(vr_gather_angular_adaptive(ctx_, &spec, &l, 0u, n, minSamples, maxSamples, (float)relTarget, (float)absTarget,
+                                             flux.data(), err.data(), reinterpret_cast<uint32_t *>(r.samplesUsed.data()), &r.info)))
+      return {};
+    r.flux.assign(flux.begin(), flux.end());
+    r.stdErr.assign(err.begin(), err.end());
+    return r;
+  }
+  bool gatherAngularAdaptiveDevice(const vr_gather_spec &spec, const GatherLaws &laws, unsigned primFirst, unsigned primCount,
+                                   unsigned minSamples, unsigned maxSamples, float relTarget, float absTarget, float *dFlux,
+                                   float *dStdErr, uint32_t *dSamplesUsed, vr_gather_adaptive_info &info, void *stream = nullptr) {
+    const vr_gather_laws l = laws.pod();
+    return ctx_ && reported(vr_gather_angular_adaptive_device(ctx_, &spec, &l, primFirst, primCount, minSamples, maxSamples,
+                                                              relTarget, absTarget, dFlux, dStdErr, dSamplesUsed, &info, stream));
+  }
+  /// gatherSums of an angular gather's samples (host tables in the spec).  false if it was refused.
+  bool gatherAngularSums(const vr_gather_spec &spec, const GatherLaws &laws, unsigned chunkFirst, unsigned chunks, unsigned budget,
+                         std::vector<int64_t> &sum, std::vector<int64_t> &sumSq) {
+    if (!ctx_)
+      return false;
+    const vr_gather_laws l = laws.pod();
+    const uint32_t n = vr_num_primitives(ctx_);
+    sum.assign(n, 0);
+    sumSq.assign(n, 0);
+    return reported(vr_gather_angular_sums(ctx_, &spec, &l, 0u, n, chunkFirst, chunks, budget, sum.data(), sumSq.data()));
+  }
+  /// ONE path of gatherAngular (vr_debug_gather_angular_path): up to maxVertices vertices in ids / data (12 floats each),
+  /// how it ended, its throughput and weight.  false if it was refused.
+  struct GatherPathRecord {
+    std::vector<uint32_t> ids;
+    std::vector<float> data;
+    uint32_t numVertices = 0, end = 0;
+    float direction[3] = {0.f, 0.f, 0.f}, throughput = 0.f, weight = 0.f;
+  };
+  bool debugGatherAngularPath(const vr_gather_spec &spec, const GatherLaws &laws, unsigned prim, unsigned sample,
+                              unsigned maxVertices, GatherPathRecord &rec) {
+    if (!ctx_)
+      return false;
+    const vr_gather_laws l = laws.pod();
+    rec.ids.assign(maxVertices, 0u);
+    rec.data.assign((size_t)maxVertices * VR_GATHER_PATH_VERTEX_FLOATS, 0.f);
+    return reported(vr_debug_gather_angular_path(ctx_, &spec, &l, prim, sample, maxVertices, rec.ids.data(), rec.data.data(),
+                                                 &rec.numVertices, &rec.end, rec.direction, &rec.throughput, &rec.weight));
+  }
+
   // ---- radiosity solve (not in the reference; vr_radiosity_*, whose header comment has the definition): the
   //      steady-state incoming flux of a species re-emitted diffusely with probability 1 - sticking — the fixed point of
   //      gatherFlux(samples, emission = (1 - sticking) x flux).  The samples are walked once into a link table that stays

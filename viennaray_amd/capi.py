@@ -59,6 +59,12 @@ class GatherSpecPOD(C.Structure):
                 ("reflectivityScalar", C.c_float)]
 
 
+class GatherLawsPOD(C.Structure):
+    """vr_gather_laws (include/viennaray_amd.h): the angular laws of vr_gather_angular*, HOST tables"""
+    _fields_ = [("sourceLaw", C.c_void_p), ("sourceCount", C.c_uint32), ("reflectivityLaw", C.c_void_p),
+                ("reflectivityCount", C.c_uint32), ("yieldLaw", C.c_void_p), ("yieldCount", C.c_uint32)]
+
+
 class GatherAdaptiveInfoPOD(C.Structure):
     """vr_gather_adaptive_info (include/viennaray_amd.h)"""
     _fields_ = [("rounds", C.c_uint32), ("unconverged", C.c_uint32), ("totalSamples", C.c_uint64)]
@@ -157,6 +163,22 @@ SIGNATURES = {
                                             C.c_float, C.c_float, _vp, _vp, _vp, C.POINTER(GatherAdaptiveInfoPOD), _vp]),
     "vr_gather_adaptive": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_float, C.c_float, _fp, _fp, _u32p, C.POINTER(GatherAdaptiveInfoPOD)]),
+    "vr_gather_angular_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                           C.c_uint32, _vp, _vp]),
+    "vr_gather_angular": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32, C.c_uint32,
+                                    _fp]),
+    "vr_gather_angular_sums_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vr_gather_angular_sums": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vr_gather_angular_adaptive_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32,
+                                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, _vp, _vp, _vp,
+                                                    C.POINTER(GatherAdaptiveInfoPOD), _vp]),
+    "vr_gather_angular_adaptive": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_float, C.c_float, _fp, _fp, _u32p,
+                                             C.POINTER(GatherAdaptiveInfoPOD)]),
+    "vr_debug_gather_angular_path": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                               C.c_uint32, _u32p, _fp, _u32p, _u32p, _fp, _fp, _fp]),
     "vr_radiosity_link_bytes": (C.c_uint64, [_vp, C.c_uint32]),
     "vr_radiosity_links_device": (C.c_int, [_vp, C.c_uint32, C.c_float, _vp]),
     "vr_radiosity_resident": (C.c_int, [_vp, C.c_uint32, C.c_float]),

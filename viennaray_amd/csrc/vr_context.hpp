@@ -393,6 +393,9 @@ struct vr_context {
   DevBuf<unsigned long long> dGatherAccSq;
   DevBuf<uint32_t> dGatherListA, dGatherListB, dGatherWords, dGatherUsed;
   DevBuf<float> dGatherErr;
+  // vr_gather_angular*: the three angular laws of the call in flight, 3 x GATHER_LAW_MAX floats (written by a kernel from
+  // its own arguments on c->stream, so behind an earlier call that still reads them).  Grown behind host_waits only
+  DevBuf<float> dGatherLaws;
   // vr_radiosity_*: the link table of the last vr_radiosity_links_device (slots x samples int32 in leaf order,
   // vr_radiosity.hpp), its direct sums and leaf -> original id table, what it was built from, and a solve's work buffers
   // (leaf order: reflectivity, F, the two emission tables; the words that come back; the host forms' staging).  A table
@@ -555,6 +558,41 @@ void gather_cut_chunks(GatherArgs &a, unsigned slabs);
 int paths_refusal(vr_context *c, const char *api, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
                   uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float scalar, const void *out);
 int paths_table(vr_context *c, const char *api, const float *rho);
+// vr_gather_angular.cpp: the angular laws of a call (laws == nullptr, or all three tables NULL: none).  gather_laws_refusal
+// checks them on the host — before anything is touched — against the call's cosinePower, sample budget and dimension and
+// leaves them normalised in `set`; gather_laws_args puts them on the device and into the launch arguments
+struct GatherLawSet {
+  bool any = false;
+  uint32_t count[3] = {0, 0, 0};
+  float gL = 1.f;
+  float table[3 * 256] = {}; // (GATHER_LAW_MAX each)
+};
+int gather_laws_refusal(vr_context *c, const char *api, const vr_gather_laws *laws, float cosinePower, uint32_t samples,
+                        GatherLawSet &set);
+int gather_laws_args(vr_context *c, bool &waited, const GatherLawSet &set, GatherArgs &a);
+// the entry points of vr_gather_paths.cpp, vr_gather_adaptive.cpp and vr_gather_angular.cpp share one implementation each
+// (laws == nullptr: the former); `api` names the entry point in the messages
+int paths_call_device(vr_context *c, const char *api, const vr_gather_laws *laws, uint32_t primFirst, uint32_t primCount,
+                      uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, const float *reflectivity,
+                      float reflectivityScalar, float *out, void *stream);
+int paths_call_host(vr_context *c, const char *api, const vr_gather_laws *laws, uint32_t primFirst, uint32_t primCount,
+                    uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, const float *reflectivity,
+                    float reflectivityScalar, float *out);
+int paths_call_debug(vr_context *c, const char *api, const vr_gather_laws *laws, uint32_t prim, uint32_t sample, float cosinePower,
+                     uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float reflectivityScalar,
+                     uint32_t maxVertices, uint32_t *vertexIds, float *vertexData, uint32_t *numVertices, uint32_t *end,
+                     float *finalDirection3, float *throughput, float *weight);
+int sums_call_device(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                     uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq,
+                     void *stream);
+int sums_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                   uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq);
+int adaptive_call_device(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                         uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget,
+                         float *flux, float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream);
+int adaptive_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
+                       uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux,
+                       float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info);
 
 // a work buffer of the map or of a cast grows behind host_waits only (vr_api.cpp: a buffer that moves)
 template <class T> int map_grow(vr_context *c, DevBuf<T> &b, size_t n, bool &waited) {

@@ -10,10 +10,13 @@
 //                                  With PATH it follows a sample through its reflections (vr_gather_paths_device,
 //                                  vr_gather_paths.cpp): a front-side hit keeps the lane in the segment loop.
 //                                  With PATH == 2 it writes ONE path vertex by vertex (vr_debug_gather_path).
+//                                  With PATH == 3 the path is weighed by up to three angular laws staged in LDS
+//                                  (vr_gather_angular*, vr_gather_angular.cpp); PATH == 2 takes them at run time.
 //                                  With STAT it sums a range of chunks for a list of primitives and carries the sum of
 //                                  the squared weights beside the sum (vr_gather_sums_device, vr_gather_adaptive_device;
 //                                  vr_gather_adaptive.cpp).
 //   gather_finish_kernel           int64 sums -> floats.
+//   gather_laws_put_kernel         the angular laws of a call, from the launch arguments into device memory.
 //   gather_decide_kernel           one round's verdict of the adaptive gather: outputs of the converged primitives, the
 //                                  others compacted in order into the next list.
 //   debug_gather_samples_kernel    the origin, the normal and a run of sample directions of ONE primitive
@@ -81,11 +84,14 @@ __device__ __forceinline__ u64 gather_draw(unsigned &k, u64 &lo, u64 &hi) {
 // The step of a path (vr_gather_paths) at a geometry hit: true when the path goes on — from the hit point along the new
 // direction, T, c = u . rayDirection and the bounce count updated — false when it ends there, `end` saying how.  hitPos:
 // the leaf position of the primitive hit, nj: the normal the tracer tests its side against; startPrim, sample: what the
-// counter draw of a DIFFUSE vertex is keyed by.  The kernel and vr_debug_gather_path both step through here
-template <int GEO, int D>
+// counter draw of a DIFFUSE vertex is keyed by.  The kernel and vr_debug_gather_path both step through here.
+// PATH >= 2 with a reflectivity law (lawS: the block's staged laws; a.lawCount: wave-uniform): T takes a second multiply,
+// by R at mu = n_j . (the direction the path leaves along), and a T of 0 ends the path there as one of rho 0 does
+template <int GEO, int D, int PATH = 1>
 __device__ __forceinline__ bool gather_bounce(const float4 *__restrict__ prims, const GatherArgs &a, const GatherFrame &frame,
                                               unsigned hitPos, unsigned startPrim, unsigned sample, const V3 &hitPoint, V3 &org,
-                                              V3 &rayDirection, V3 &dir, float &T, float &c, unsigned &bounces, int &end, V3 &nj) {
+                                              V3 &rayDirection, V3 &dir, float &T, float &c, unsigned &bounces, int &end, V3 &nj,
+                                              [[maybe_unused]] const float *lawS = nullptr) {
   nj = gather_hit_normal<GEO>(prims, hitPos);
   if (!(vdot(dir, nj) < 0.f)) {
     end = GATHER_END_BACK;
@@ -103,10 +109,22 @@ __device__ __forceinline__ bool gather_bounce(const float4 *__restrict__ prims, 
     end = GATHER_END_ABSORBED;
     return false;
   }
+  V3 leaving;
   if (a.reflection == GATHER_REFLECT_SPECULAR) // (wave-uniform)
-    rayDirection = reflect_specular(rayDirection, nj);
+    leaving = reflect_specular(rayDirection, nj);
   else
-    rayDirection = v3(gather_path_diffuse(D, a.seed, startPrim, sample, bounces, GVec{nj.x, nj.y, nj.z}));
+    leaving = v3(gather_path_diffuse(D, a.seed, startPrim, sample, bounces, GVec{nj.x, nj.y, nj.z}));
+  if constexpr (PATH >= 2) {
+    if (a.lawCount[GATHER_LAW_REFLECTIVITY]) { // (wave-uniform)
+      T = gather_path_throughput_law(T, lawS + GATHER_LAW_REFLECTIVITY * GATHER_LAW_MAX, a.lawCount[GATHER_LAW_REFLECTIVITY],
+                                     vdot(nj, leaving));
+      if (T == 0.f) {
+        end = GATHER_END_ABSORBED;
+        return false;
+      }
+    }
+  }
+  rayDirection = leaving;
   dir = project_dir<D>(rayDirection);
   org = hitPoint; // (org + dir * t: the tracer's restart)
   c = gather_c(GVec{rayDirection.x, rayDirection.y, rayDirection.z}, frame);
@@ -145,6 +163,14 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
   __shared__ unsigned stackS[VR_STACK_LDS * VR_BLOCK]; // [entry][thread of the block]
   for (unsigned k = threadIdx.x; k < VR_WALL_TABLE; k += blockDim.x)
     wallS[k] = p.wallTable[k];
+  [[maybe_unused]] const float *lawS = nullptr; // (PATH >= 2) the three laws, staged beside the wall table
+  if constexpr (PATH >= 2) {
+    __shared__ float lawBuf[3 * GATHER_LAW_MAX];
+    if (a.laws) // (block-uniform; absent laws are never read: a.lawCount says which are there)
+      for (unsigned k = threadIdx.x; k < 3 * GATHER_LAW_MAX; k += blockDim.x)
+        lawBuf[k] = a.laws[k];
+    lawS = lawBuf;
+  }
   __syncthreads(); // (the only block-wide point: from here on the waves run on their own)
   const unsigned lane = threadIdx.x & 63u;
   const unsigned wavesPerBlock = blockDim.x >> 6;
@@ -217,6 +243,7 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
       [[maybe_unused]] unsigned bounces = 0u;
       [[maybe_unused]] unsigned pathCount = 1u; // (PATH == 2) vertices so far: vertex 0 is the primitive itself
       [[maybe_unused]] int pathEnd = GATHER_END_MISS;
+      [[maybe_unused]] float pathWeight = 0.f; // (PATH == 2) the one sample's unquantised weight
       if constexpr (PATH == 2) {
         if (walked)
           gather_path_put(a, 0u, orig, org, mk(__int_as_float(0x7FC00000), __int_as_float(0x7FC00000), __int_as_float(0x7FC00000)),
@@ -249,8 +276,8 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
                 int end;
                 V3 nj;
                 [[maybe_unused]] const V3 arriving = rayDirection;
-                active = gather_bounce<GEO, D>(prims, a, frame, hitPos, orig, chunk * GATHER_CHUNK + j, hitPoint, org, rayDirection, dir,
-                                               T, cEnd, bounces, end, nj);
+                active = gather_bounce<GEO, D, PATH>(prims, a, frame, hitPos, orig, chunk * GATHER_CHUNK + j, hitPoint, org,
+                                                     rayDirection, dir, T, cEnd, bounces, end, nj, lawS);
                 if constexpr (PATH == 2) {
                   const float QNAN = __int_as_float(0x7FC00000);
                   gather_path_put(a, pathCount, (unsigned)s.prim, hitPoint, arriving, nj, active ? rayDirection : mk(QNAN, QNAN, QNAN));
@@ -265,8 +292,18 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
       if constexpr (PATH) {
         // (a path that ended on a primitive weighs 0 like one stopped on a wall; vr_debug_gather_path tells the ends apart)
         if (walked) {
-          const float w = gather_path_weight(s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL,
-                                             a.g, a.cosinePower, cEnd, T);
+          const int tailEnd = s.prim == CAST_MISS ? (ignored ? GATHER_END_IGNORED : GATHER_END_MISS) : GATHER_END_WALL;
+          float w;
+          if constexpr (PATH >= 2) // (a.lawCount: wave-uniform; with none of the three this is gather_path_weight)
+            w = gather_path_weight_laws(tailEnd, a.g, a.cosinePower, cEnd, T,
+                                        a.lawCount[GATHER_LAW_SOURCE] ? lawS + GATHER_LAW_SOURCE * GATHER_LAW_MAX : nullptr,
+                                        a.lawCount[GATHER_LAW_SOURCE], a.gL,
+                                        a.lawCount[GATHER_LAW_YIELD] ? lawS + GATHER_LAW_YIELD * GATHER_LAW_MAX : nullptr,
+                                        a.lawCount[GATHER_LAW_YIELD], mDotW);
+          else
+            w = gather_path_weight(tailEnd, a.g, a.cosinePower, cEnd, T);
+          if constexpr (PATH == 2)
+            pathWeight = w;
           sum += gather_q(w, a.wmax);
           if constexpr (STAT)
             sumSq += gather_q2(w, a.wmax);
@@ -278,7 +315,7 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_samples_kernel(const TracePar
             a.pathTail[1] = __uint_as_float((unsigned)end);
             a.pathTail[2] = rayDirection.x, a.pathTail[3] = rayDirection.y, a.pathTail[4] = rayDirection.z;
             a.pathTail[5] = T;
-            a.pathTail[6] = gather_path_weight(end, a.g, a.cosinePower, cEnd, T);
+            a.pathTail[6] = pathWeight; // (0 for a path that ended on a primitive: the tail's rule)
           }
         }
       } else if (walked) {
@@ -324,6 +361,17 @@ __global__ void gather_finish_kernel(const unsigned long long *acc, unsigned n, 
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n)
     out[i] = gather_result((long long)acc[i], samples);
+}
+
+// the three angular laws of a call from the launch's own arguments (3 KiB of them) into the table the PATH >= 2 kernels
+// stage: no host buffer has to outlive the call, and the write is ordered on the stream like any kernel
+struct GatherLawTable {
+  float v[3 * GATHER_LAW_MAX];
+};
+__global__ void gather_laws_put_kernel(const GatherLawTable t, float *dst) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 3 * GATHER_LAW_MAX)
+    dst[i] = t.v[i];
 }
 
 // One round's verdict of vr_gather_adaptive_device: one thread per entry of the current list, a block per
@@ -420,6 +468,17 @@ __global__ void debug_gather_samples_kernel(const TraceParams p, const GatherArg
   directions3[3 * (size_t)i] = w.x, directions3[3 * (size_t)i + 1] = w.y, directions3[3 * (size_t)i + 2] = w.z;
 }
 
+// laws go with paths alone, no law has more entries than its place in the table holds, and there is at least one
+static bool gather_laws_ok(const GatherArgs &a) {
+  const uint32_t *n = a.lawCount;
+  if (!a.laws)
+    return n[0] == 0 && n[1] == 0 && n[2] == 0;
+  for (int w = 0; w < 3; ++w)
+    if (n[w] && !gather_law_count_ok(n[w]))
+      return false;
+  return a.paths == 1u && !a.links && (n[0] || n[1] || n[2]);
+}
+
 hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned slabs, hipStream_t st) {
   // no more waves than slabs, no more than work items; whole blocks of VR_BLOCK / 64 waves once there are that many
   if (a.subs == 0 || a.subs > GATHER_MAX_SUBS || (a.subs & (a.subs - 1u)))
@@ -431,6 +490,8 @@ hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const Gat
     waves -= waves % perBlock;
   if (waves == 0)
     return hipSuccess;
+  if (!gather_laws_ok(a))
+    return hipErrorInvalidValue;
   const dim3 g(waves > perBlock ? waves / perBlock : 1u), b(waves > perBlock ? (unsigned)VR_BLOCK : waves * 64u);
   if (a.stat) { // the sums: chunks from a.chunkFirst on, a list of primitives or all of the range, no recording
     if (a.links || !a.accSq || a.paths > 1u || (a.list ? a.listCount > a.primCount : false) ||
@@ -440,24 +501,32 @@ hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const Gat
       return hipErrorInvalidValue;
     if (geo == 0) {
       if (D == 2) {
-        if (a.paths)
+        if (a.laws)
+          hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 3, 1>), g, b, 0, st, p, a);
+        else if (a.paths)
           hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 1, 1>), g, b, 0, st, p, a);
         else
           hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 0, 1>), g, b, 0, st, p, a);
       } else {
-        if (a.paths)
+        if (a.laws)
+          hipLaunchKernelGGL((gather_samples_kernel<0, 3, false, 3, 1>), g, b, 0, st, p, a);
+        else if (a.paths)
           hipLaunchKernelGGL((gather_samples_kernel<0, 3, false, 1, 1>), g, b, 0, st, p, a);
         else
           hipLaunchKernelGGL((gather_samples_kernel<0, 3, false, 0, 1>), g, b, 0, st, p, a);
       }
     } else {
       if (D == 2) {
-        if (a.paths)
+        if (a.laws)
+          hipLaunchKernelGGL((gather_samples_kernel<1, 2, false, 3, 1>), g, b, 0, st, p, a);
+        else if (a.paths)
           hipLaunchKernelGGL((gather_samples_kernel<1, 2, false, 1, 1>), g, b, 0, st, p, a);
         else
           hipLaunchKernelGGL((gather_samples_kernel<1, 2, false, 0, 1>), g, b, 0, st, p, a);
       } else {
-        if (a.paths)
+        if (a.laws)
+          hipLaunchKernelGGL((gather_samples_kernel<1, 3, false, 3, 1>), g, b, 0, st, p, a);
+        else if (a.paths)
           hipLaunchKernelGGL((gather_samples_kernel<1, 3, false, 1, 1>), g, b, 0, st, p, a);
         else
           hipLaunchKernelGGL((gather_samples_kernel<1, 3, false, 0, 1>), g, b, 0, st, p, a);
@@ -484,6 +553,20 @@ hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const Gat
   if (a.paths) { // the paths: NORMAL samples, no emission table
     if (a.emission || a.mode != GATHER_NORMAL || a.reflection > GATHER_REFLECT_DIFFUSE || a.maxBounces > GATHER_MAX_BOUNCES)
       return hipErrorInvalidValue;
+    if (a.laws) { // the paths with angular laws
+      if (geo == 0) {
+        if (D == 2)
+          hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 3>), g, b, 0, st, p, a);
+        else
+          hipLaunchKernelGGL((gather_samples_kernel<0, 3, false, 3>), g, b, 0, st, p, a);
+      } else {
+        if (D == 2)
+          hipLaunchKernelGGL((gather_samples_kernel<1, 2, false, 3>), g, b, 0, st, p, a);
+        else
+          hipLaunchKernelGGL((gather_samples_kernel<1, 3, false, 3>), g, b, 0, st, p, a);
+      }
+      return hipGetLastError();
+    }
     if (geo == 0) {
       if (D == 2)
         hipLaunchKernelGGL((gather_samples_kernel<0, 2, false, 1>), g, b, 0, st, p, a);
@@ -518,6 +601,16 @@ hipError_t launch_gather_finish(const unsigned long long *acc, unsigned n, unsig
   return hipGetLastError();
 }
 
+hipError_t launch_gather_laws(const float *hostTable, float *dst, hipStream_t st) {
+  if (!hostTable || !dst)
+    return hipErrorInvalidValue;
+  GatherLawTable t;
+  for (unsigned k = 0; k < 3 * GATHER_LAW_MAX; ++k)
+    t.v[k] = hostTable[k];
+  hipLaunchKernelGGL(gather_laws_put_kernel, dim3(3), dim3(GATHER_LAW_MAX), 0, st, t, dst);
+  return hipGetLastError();
+}
+
 hipError_t launch_gather_decide(const GatherDecideArgs &d, hipStream_t st) {
   if (d.count == 0 || !d.acc || !d.accSq || !d.next || !d.blockCounts || !d.word || !d.flux || d.samples < 2u)
     return hipErrorInvalidValue;
@@ -549,7 +642,7 @@ hipError_t launch_debug_gather_samples(const TraceParams &p, int geo, int D, con
 hipError_t launch_debug_gather_path(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned sample, unsigned maxVertices,
                                     float *vertices, float *tail, hipStream_t st) {
   if (!a.paths || !a.leafOfOrig || a.emission || a.links || a.mode != GATHER_NORMAL || a.reflection > GATHER_REFLECT_DIFFUSE ||
-      a.maxBounces > GATHER_MAX_BOUNCES || !a.acc || !tail || (maxVertices && !vertices))
+      a.maxBounces > GATHER_MAX_BOUNCES || !a.acc || !tail || (maxVertices && !vertices) || !gather_laws_ok(a))
     return hipErrorInvalidValue;
   // one wave over the one chunk that holds the sample: a range of one primitive, samples 0 .. sample, whole chunks
   GatherArgs b2 = a;

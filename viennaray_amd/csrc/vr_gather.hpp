@@ -305,6 +305,96 @@ VR_GATHER_FN float gather_path_weight(int end, float g, float n, float cEnd, flo
 // a reflectivity the entry points accept (vr_radiosity.hpp: radiosity_rho_ok has the same rule)
 VR_GATHER_FN bool gather_path_rho_ok(float rho) { return rho >= 0.f && rho <= 1.f; }
 
+// ---- gatherAngular (vr_gather_angular*): a path weighed by tabulated angular laws -------------------------------------
+constexpr uint32_t GATHER_LAW_MIN = 2, GATHER_LAW_MAX = 256; // entries of a law
+// the three laws' places in the device table (GATHER_LAW_MAX floats each) and in GatherArgs::lawCount
+constexpr int GATHER_LAW_SOURCE = 0, GATHER_LAW_REFLECTIVITY = 1, GATHER_LAW_YIELD = 2;
+// An angular law: M float32 values read as the piecewise-linear function of a cosine x in [0, 1] with nodes at
+// x_k = k / (M - 1).  float32, one IEEE operation per step in this order, contraction off, so that the host, the device and
+// numpy float32 agree bit for bit.  A NaN x reads as 0 (fmaxf returns its other argument)
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN float gather_law(const float *t, uint32_t M, float x) {
+  VR_GATHER_NO_CONTRACT
+  const float xc = fminf(fmaxf(x, 0.f), 1.f);
+  const float xs = xc * (float)(M - 1u);
+  int k = (int)xs;
+  k = k < (int)M - 2 ? k : (int)M - 2;
+  const float f = xs - (float)k;
+  const float d = t[k + 1] - t[k];
+  const float fd = f * d;
+  return t[k] + fd;
+}
+// what an entry of each law may be: finite and >= 0 (source, yield), in [0, 1] (reflectivity)
+VR_GATHER_FN bool gather_law_entry_ok(int which, float v) {
+  if (which == GATHER_LAW_REFLECTIVITY)
+    return v >= 0.f && v <= 1.f;
+  return v >= 0.f && v <= 3.40282347e+38f;
+}
+VR_GATHER_FN bool gather_law_count_ok(uint32_t M) { return M >= GATHER_LAW_MIN && M <= GATHER_LAW_MAX; }
+// the lowest index whose entry is refused, M where there is none
+inline uint32_t gather_law_first_bad(int which, const float *t, uint32_t M) {
+  for (uint32_t k = 0; k < M; ++k)
+    if (!gather_law_entry_ok(which, t[k]))
+      return k;
+  return M;
+}
+inline float gather_law_max(const float *t, uint32_t M) {
+  float m = t[0];
+  for (uint32_t k = 1; k < M; ++k)
+    m = t[k] > m ? t[k] : m;
+  return m;
+}
+// Z of a source law L (a host function, double): the forward source has the direction density L(c) c / Z per solid angle.
+// The interpolant integrated exactly, segment by segment, L = a + b c on [c0, c1]:
+//   D = 3: Z = 2 pi int_0^1 L(c) c dc,                  antiderivative a c^2 / 2 + b c^3 / 3;
+//   D = 2: Z = 2 int_0^1 L(c) c / sqrt(1 - c^2) dc,     antiderivative -a s + b (asin(c) - c s) / 2, s = sqrt(1 - c^2).
+inline double gather_law_norm(const float *t, uint32_t M, int D) {
+  const double h = 1. / (double)(M - 1u);
+  double sum = 0.;
+  for (uint32_t k = 0; k + 1u < M; ++k) {
+    const double c0 = (double)k * h, c1 = k + 2u == M ? 1. : (double)(k + 1u) * h;
+    const double b = ((double)t[k + 1] - (double)t[k]) / (c1 - c0), a = (double)t[k] - b * c0;
+    if (D == 3) {
+      sum += a * (c1 - c0) * (c1 + c0) / 2. + b * (c1 - c0) * (c1 * c1 + c1 * c0 + c0 * c0) / 3.;
+    } else {
+      const double s0 = std::sqrt((1. - c0) * (1. + c0)), s1 = std::sqrt((1. - c1) * (1. + c1));
+      sum += a * (s0 - s1) + b * ((std::asin(c1) - c1 * s1) - (std::asin(c0) - c0 * s0)) / 2.;
+    }
+  }
+  return D == 3 ? 2. * 3.14159265358979323846 * sum : 2. * sum;
+}
+// g_L: the weight of a path that reaches the source is g_L L(c_end) T — the ratio of the source's law L(c) c / Z and the
+// receiver's cosine law c / pi (3-D), c / 2 (2-D).  L = 1 gives exactly 1: Z is pi (2) to a few ulps of a double
+inline float gather_law_g(const float *t, uint32_t M, int D) {
+  return (float)((D == 3 ? 3.14159265358979323846 : 2.) / gather_law_norm(t, M, D));
+}
+// The end -> weight rule of a path with laws (a law that is nullptr is absent): gather_path_weight's, with
+// g_L L(c_end) in place of g c_end^(n - 1) where there is a source law, and one more multiply, last, by the yield at
+// mu0 = m_i . omega_0 of the INITIAL direction:  w = ((g_L L(c_end) or g c_end^(n - 1)) * T) * Y(mu0)
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN float gather_path_weight_laws(int end, float g, float n, float cEnd, float T, const float *L,
+                                                                      uint32_t ML, float gL, const float *Y, uint32_t MY,
+                                                                      float mu0) {
+  VR_GATHER_NO_CONTRACT
+  if (end != GATHER_END_MISS)
+    return 0.f;
+  float w;
+  if (L) {
+    if (!(cEnd > 0.f))
+      return 0.f;
+    const float s = gL * gather_law(L, ML, cEnd);
+    w = s * T;
+  } else {
+    w = gather_weight(end, GATHER_NORMAL, g, n, cEnd, 0.f, false, 0.f) * T;
+  }
+  if (Y)
+    w = w * gather_law(Y, MY, mu0);
+  return w;
+}
+// T after a front-side hit with a reflectivity law R at mu = n_j . (the direction the path leaves along): two multiplies
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN float gather_path_throughput_law(float Trho, const float *R, uint32_t MR, float mu) {
+  VR_GATHER_NO_CONTRACT
+  return Trho * gather_law(R, MR, mu);
+}
+
 // g_D(n) (a host function; the kernel takes the float): g_3 = (n + 1) / 2, g_2 = 2 / C_n with
 // C_n = sqrt(pi) Gamma((n + 1) / 2) / Gamma(n / 2 + 1) — the weight of a sample that reaches the source is the ratio of
 // the source's normalised law (n + 1) / (2 pi) c^n (3-D), c^n / C_n (2-D) and the receiver's cosine law c / pi, c / 2 for

@@ -13,11 +13,18 @@
 namespace vr {
 
 // what every form refuses before it touches anything; samples: the budget or maxSamples; out: a non-null output
-static int spec_refusal(vr_context *c, const char *api, const vr_gather_spec *s, uint32_t primFirst, uint32_t primCount,
-                        uint32_t samples, const void *out) {
+static int spec_refusal(vr_context *c, const char *api, const vr_gather_spec *s, const vr_gather_laws *lawsIn, GatherLawSet &laws,
+                        uint32_t primFirst, uint32_t primCount, uint32_t samples, const void *out) {
   const std::string name = api;
   if (!s)
     return fail(c, VR_E_INVALID, (name + ": spec must not be null").c_str());
+  if (lawsIn) { // (an angular entry point: the laws weigh a path)
+    if (s->paths != 1u || s->mode != VR_GATHER_NORMAL || s->emission)
+      return fail(c, VR_E_INVALID, (name + ": angular laws need spec.paths == 1, VR_GATHER_NORMAL and no emission table").c_str());
+    VR_TRY(paths_refusal(c, api, primFirst, primCount, samples, s->cosinePower, s->reflection, s->maxBounces, s->reflectivity,
+                         s->reflectivityScalar, out));
+    return gather_laws_refusal(c, api, lawsIn, s->cosinePower, samples, laws);
+  }
   if (s->paths > 1u)
     return fail(c, VR_E_INVALID, (name + ": spec.paths is 0 (vr_gather_flux's sample) or 1 (vr_gather_paths's)").c_str());
   if (s->paths == 0u)
@@ -30,9 +37,10 @@ static int spec_refusal(vr_context *c, const char *api, const vr_gather_spec *s,
 
 // the arguments every launch of a call shares; emission: device memory or nullptr; table: c->dPathRho holds the
 // reflectivities (paths_table).  budget: what wmax follows
-static int stat_args(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a, const vr_gather_spec &s, const float *emission,
-                     bool table, uint32_t primFirst, uint32_t primCount, uint32_t budget) {
+static int stat_args(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a, const vr_gather_spec &s, const GatherLawSet &laws,
+                     const float *emission, bool table, uint32_t primFirst, uint32_t primCount, uint32_t budget) {
   VR_TRY(gather_params(c, waited, p, a, primFirst, primCount, budget, s.cosinePower, s.paths ? VR_GATHER_NORMAL : s.mode));
+  VR_TRY(gather_laws_args(c, waited, laws, a));
   if (primCount == c->geo.numPrims)
     a.leafOfOrig = nullptr; // the whole scene: in leaf order
   if (s.paths) {
@@ -64,22 +72,23 @@ static int stat_launch(vr_context *c, const TraceParams &p, GatherArgs a, uint32
   return VR_OK;
 }
 
-static int sums_refusal(vr_context *c, const char *api, const vr_gather_spec *s, uint32_t primFirst, uint32_t primCount,
-                        uint32_t chunkFirst, uint32_t chunks, uint32_t budget, const void *sum, const void *sumSq) {
-  VR_TRY(spec_refusal(c, api, s, primFirst, primCount, budget, sum && sumSq ? sum : nullptr));
+static int sums_refusal(vr_context *c, const char *api, const vr_gather_spec *s, const vr_gather_laws *lawsIn, GatherLawSet &laws,
+                        uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget,
+                        const void *sum, const void *sumSq) {
+  VR_TRY(spec_refusal(c, api, s, lawsIn, laws, primFirst, primCount, budget, sum && sumSq ? sum : nullptr));
   if (((uint64_t)chunkFirst + chunks) * GATHER_CHUNK > budget)
     return fail(c, VR_E_INVALID, (std::string(api) + ": the chunks end beyond the budget: 64 (chunkFirst + chunks) > budget").c_str());
   return VR_OK;
 }
 
 // every pointer is device memory, the arguments have been accepted
-static int sums_on_device(vr_context *c, const vr_gather_spec &s, const float *emission, bool table, uint32_t primFirst,
+static int sums_on_device(vr_context *c, const vr_gather_spec &s, const GatherLawSet &laws, const float *emission, bool table, uint32_t primFirst,
                           uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, unsigned long long *sum,
                           unsigned long long *sumSq) {
   bool waited = false;
   TraceParams p;
   GatherArgs a;
-  VR_TRY(stat_args(c, waited, p, a, s, emission, table, primFirst, primCount, budget));
+  VR_TRY(stat_args(c, waited, p, a, s, laws, emission, table, primFirst, primCount, budget));
   VR_HIP(c, hipMemsetAsync(sum, 0, (size_t)primCount * 8, c->stream));
   VR_HIP(c, hipMemsetAsync(sumSq, 0, (size_t)primCount * 8, c->stream));
   if (chunks == 0)
@@ -89,8 +98,9 @@ static int sums_on_device(vr_context *c, const vr_gather_spec &s, const float *e
   return stat_launch(c, p, a, chunkFirst, chunks, nullptr, 0u);
 }
 
-static int adaptive_refusal(vr_context *c, const char *api, const vr_gather_spec *s, uint32_t primFirst, uint32_t primCount,
-                            uint32_t minSamples, uint32_t maxSamples, float rel, float abs, const void *flux, const void *info) {
+static int adaptive_refusal(vr_context *c, const char *api, const vr_gather_spec *s, const vr_gather_laws *lawsIn,
+                            GatherLawSet &laws, uint32_t primFirst, uint32_t primCount, uint32_t minSamples, uint32_t maxSamples,
+                            float rel, float abs, const void *flux, const void *info) {
   const std::string name = api;
   if (minSamples == 0 || minSamples % GATHER_CHUNK)
     return fail(c, VR_E_INVALID, (name + ": minSamples must be a positive multiple of 64").c_str());
@@ -101,12 +111,12 @@ static int adaptive_refusal(vr_context *c, const char *api, const vr_gather_spec
     return fail(c, VR_E_INVALID, (name + ": the targets must not be negative or NaN").c_str());
   if (!info)
     return fail(c, VR_E_INVALID, (name + ": info must not be null").c_str());
-  return spec_refusal(c, api, s, primFirst, primCount, maxSamples, flux);
+  return spec_refusal(c, api, s, lawsIn, laws, primFirst, primCount, maxSamples, flux);
 }
 
 // The rounds.  Every pointer is device memory (stdErr, samplesUsed: or nullptr), the arguments have been accepted.  The
 // host waits once per round for one word, the next list's length
-static int adaptive_on_device(vr_context *c, const vr_gather_spec &s, const float *emission, bool table, uint32_t primFirst,
+static int adaptive_on_device(vr_context *c, const vr_gather_spec &s, const GatherLawSet &laws, const float *emission, bool table, uint32_t primFirst,
                               uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float rel, float abs, float *flux,
                               float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info &info) {
   bool waited = false;
@@ -118,7 +128,7 @@ static int adaptive_on_device(vr_context *c, const vr_gather_spec &s, const floa
   VR_TRY(map_grow(c, c->dGatherWords, (size_t)blocks + 1u, waited));
   TraceParams p;
   GatherArgs a;
-  VR_TRY(stat_args(c, waited, p, a, s, emission, table, primFirst, primCount, maxSamples));
+  VR_TRY(stat_args(c, waited, p, a, s, laws, emission, table, primFirst, primCount, maxSamples));
   a.acc = c->dGatherAcc.p;
   a.accSq = c->dGatherAccSq.p;
   VR_HIP(c, hipMemsetAsync(a.acc, 0, (size_t)primCount * 8, c->stream));
@@ -188,37 +198,30 @@ static int spec_upload(vr_context *c, const char *api, const vr_gather_spec &s, 
   return VR_OK;
 }
 
-} // namespace vr
 
-using namespace vr;
-
-extern "C" {
-
-int vr_gather_sums_device(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst,
-                          uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq, void *stream) {
-  if (!c)
-    return VR_E_INVALID;
-  const char *api = "vr_gather_sums_device";
-  VR_TRY(sums_refusal(c, api, spec, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq));
+int sums_call_device(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *lawsIn, uint32_t primFirst,
+                     uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq,
+                     void *stream) {
+  GatherLawSet laws;
+  VR_TRY(sums_refusal(c, api, spec, lawsIn, laws, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_TRY(hand_over(c, {spec->emission, spec->reflectivity, sum, sumSq},
-                   "vr_gather_sums_device: the spec's tables, sum and sumSq must be device memory of the context's device", stream));
+                   (std::string(api) + ": the spec's tables, sum and sumSq must be device memory of the context's device").c_str(),
+                   stream));
   const bool table = spec->paths && spec->reflectivity;
   if (table)
     VR_TRY(paths_table(c, api, spec->reflectivity));
   if (primCount == 0)
     return caller_waits(c, stream);
-  VR_TRY(sums_on_device(c, *spec, spec->paths ? nullptr : spec->emission, table, primFirst, primCount, chunkFirst, chunks, budget,
+  VR_TRY(sums_on_device(c, *spec, laws, spec->paths ? nullptr : spec->emission, table, primFirst, primCount, chunkFirst, chunks, budget,
                         reinterpret_cast<unsigned long long *>(sum), reinterpret_cast<unsigned long long *>(sumSq)));
   return caller_waits(c, stream);
 }
 
-int vr_gather_sums(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst,
-                   uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq) {
-  if (!c)
-    return VR_E_INVALID;
-  const char *api = "vr_gather_sums";
-  VR_TRY(sums_refusal(c, api, spec, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq));
+int sums_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *lawsIn, uint32_t primFirst,
+                   uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq) {
+  GatherLawSet laws;
+  VR_TRY(sums_refusal(c, api, spec, lawsIn, laws, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_HIP(c, hipSetDevice(c->device));
   bool waited = false;
@@ -229,7 +232,7 @@ int vr_gather_sums(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst
     return VR_OK;
   VR_TRY(map_grow(c, c->dGatherAcc, primCount, waited));
   VR_TRY(map_grow(c, c->dGatherAccSq, primCount, waited));
-  VR_TRY(sums_on_device(c, *spec, emission, table, primFirst, primCount, chunkFirst, chunks, budget, c->dGatherAcc.p,
+  VR_TRY(sums_on_device(c, *spec, laws, emission, table, primFirst, primCount, chunkFirst, chunks, budget, c->dGatherAcc.p,
                         c->dGatherAccSq.p));
   VR_HIP(c, hipMemcpyAsync(sum, c->dGatherAcc.p, (size_t)primCount * 8, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipMemcpyAsync(sumSq, c->dGatherAccSq.p, (size_t)primCount * 8, hipMemcpyDeviceToHost, c->stream));
@@ -237,17 +240,15 @@ int vr_gather_sums(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst
   return VR_OK;
 }
 
-int vr_gather_adaptive_device(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount,
-                              uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux, float *stdErr,
-                              uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream) {
-  if (!c)
-    return VR_E_INVALID;
-  const char *api = "vr_gather_adaptive_device";
-  VR_TRY(adaptive_refusal(c, api, spec, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget, flux, info));
+int adaptive_call_device(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *lawsIn, uint32_t primFirst,
+                         uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget,
+                         float *flux, float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream) {
+  GatherLawSet laws;
+  VR_TRY(adaptive_refusal(c, api, spec, lawsIn, laws, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget, flux, info));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_TRY(hand_over(c, {spec->emission, spec->reflectivity, flux, stdErr, samplesUsed},
-                   "vr_gather_adaptive_device: the spec's tables, flux, stdErr and samplesUsed must be device memory of the "
-                   "context's device",
+                   (std::string(api) + ": the spec's tables, flux, stdErr and samplesUsed must be device memory of the context's device")
+                       .c_str(),
                    stream));
   const bool table = spec->paths && spec->reflectivity;
   if (table)
@@ -255,18 +256,16 @@ int vr_gather_adaptive_device(vr_context *c, const vr_gather_spec *spec, uint32_
   *info = vr_gather_adaptive_info{};
   if (primCount == 0)
     return caller_waits(c, stream);
-  VR_TRY(adaptive_on_device(c, *spec, spec->paths ? nullptr : spec->emission, table, primFirst, primCount, minSamples, maxSamples,
+  VR_TRY(adaptive_on_device(c, *spec, laws, spec->paths ? nullptr : spec->emission, table, primFirst, primCount, minSamples, maxSamples,
                             relTarget, absTarget, flux, stdErr, samplesUsed, *info));
   return caller_waits(c, stream);
 }
 
-int vr_gather_adaptive(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount, uint32_t minSamples,
-                       uint32_t maxSamples, float relTarget, float absTarget, float *flux, float *stdErr, uint32_t *samplesUsed,
-                       vr_gather_adaptive_info *info) {
-  if (!c)
-    return VR_E_INVALID;
-  const char *api = "vr_gather_adaptive";
-  VR_TRY(adaptive_refusal(c, api, spec, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget, flux, info));
+int adaptive_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *lawsIn, uint32_t primFirst,
+                       uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux,
+                       float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info) {
+  GatherLawSet laws;
+  VR_TRY(adaptive_refusal(c, api, spec, lawsIn, laws, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget, flux, info));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_HIP(c, hipSetDevice(c->device));
   bool waited = false;
@@ -279,7 +278,7 @@ int vr_gather_adaptive(vr_context *c, const vr_gather_spec *spec, uint32_t primF
   VR_TRY(map_grow(c, c->dGatherOut, primCount, waited));
   VR_TRY(map_grow(c, c->dGatherErr, primCount, waited));
   VR_TRY(map_grow(c, c->dGatherUsed, primCount, waited));
-  VR_TRY(adaptive_on_device(c, *spec, emission, table, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget,
+  VR_TRY(adaptive_on_device(c, *spec, laws, emission, table, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget,
                             c->dGatherOut.p, c->dGatherErr.p, c->dGatherUsed.p, *info));
   VR_HIP(c, hipMemcpyAsync(flux, c->dGatherOut.p, (size_t)primCount * 4, hipMemcpyDeviceToHost, c->stream));
   if (stdErr)
@@ -288,6 +287,45 @@ int vr_gather_adaptive(vr_context *c, const vr_gather_spec *spec, uint32_t primF
     VR_HIP(c, hipMemcpyAsync(samplesUsed, c->dGatherUsed.p, (size_t)primCount * 4, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   return VR_OK;
+}
+
+} // namespace vr
+
+using namespace vr;
+
+extern "C" {
+
+int vr_gather_sums_device(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst,
+                          uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq, void *stream) {
+  if (!c)
+    return VR_E_INVALID;
+  return sums_call_device(c, "vr_gather_sums_device", spec, nullptr, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq,
+                          stream);
+}
+
+int vr_gather_sums(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst,
+                   uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq) {
+  if (!c)
+    return VR_E_INVALID;
+  return sums_call_host(c, "vr_gather_sums", spec, nullptr, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq);
+}
+
+int vr_gather_adaptive_device(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount,
+                              uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux, float *stdErr,
+                              uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream) {
+  if (!c)
+    return VR_E_INVALID;
+  return adaptive_call_device(c, "vr_gather_adaptive_device", spec, nullptr, primFirst, primCount, minSamples, maxSamples, relTarget,
+                              absTarget, flux, stdErr, samplesUsed, info, stream);
+}
+
+int vr_gather_adaptive(vr_context *c, const vr_gather_spec *spec, uint32_t primFirst, uint32_t primCount, uint32_t minSamples,
+                       uint32_t maxSamples, float relTarget, float absTarget, float *flux, float *stdErr, uint32_t *samplesUsed,
+                       vr_gather_adaptive_info *info) {
+  if (!c)
+    return VR_E_INVALID;
+  return adaptive_call_host(c, "vr_gather_adaptive", spec, nullptr, primFirst, primCount, minSamples, maxSamples, relTarget,
+                            absTarget, flux, stdErr, samplesUsed, info);
 }
 
 } // extern "C"

@@ -53,9 +53,11 @@ int paths_table(vr_context *c, const char *api, const float *rho) {
   return VR_OK;
 }
 
-static int paths_args(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a, uint32_t primFirst, uint32_t primCount,
-                      uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, bool table, float scalar) {
+static int paths_args(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a, const GatherLawSet &laws, uint32_t primFirst,
+                      uint32_t primCount, uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, bool table,
+                      float scalar) {
   VR_TRY(gather_params(c, waited, p, a, primFirst, primCount, samples, cosinePower, VR_GATHER_NORMAL));
+  VR_TRY(gather_laws_args(c, waited, laws, a));
   a.paths = 1u;
   a.reflection = reflection;
   a.maxBounces = maxBounces;
@@ -66,13 +68,13 @@ static int paths_args(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a
 
 // the kernels, on the context's stream: every pointer is device memory, the arguments have been accepted, a table
 // (table: c->dPathRho holds it) has passed paths_table
-static int paths_on_device(vr_context *c, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
-                           uint32_t reflection, uint32_t maxBounces, bool table, float scalar, float *out) {
+static int paths_on_device(vr_context *c, const GatherLawSet &laws, uint32_t primFirst, uint32_t primCount, uint32_t samples,
+                           float cosinePower, uint32_t reflection, uint32_t maxBounces, bool table, float scalar, float *out) {
   bool waited = false;
   VR_TRY(map_grow(c, c->dGatherAcc, primCount, waited));
   TraceParams p;
   GatherArgs a;
-  VR_TRY(paths_args(c, waited, p, a, primFirst, primCount, samples, cosinePower, reflection, maxBounces, table, scalar));
+  VR_TRY(paths_args(c, waited, p, a, laws, primFirst, primCount, samples, cosinePower, reflection, maxBounces, table, scalar));
   if (primCount == c->geo.numPrims)
     a.leafOfOrig = nullptr; // the whole scene: in leaf order
   a.acc = c->dGatherAcc.p;
@@ -97,35 +99,31 @@ static int paths_on_device(vr_context *c, uint32_t primFirst, uint32_t primCount
   return VR_OK;
 }
 
-} // namespace vr
 
-extern "C" {
-
-int vr_gather_paths_device(vr_context *c, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
-                           uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float reflectivityScalar, float *out,
-                           void *stream) {
-  if (!c)
-    return VR_E_INVALID;
-  const char *api = "vr_gather_paths_device";
+int paths_call_device(vr_context *c, const char *api, const vr_gather_laws *lawsIn, uint32_t primFirst, uint32_t primCount,
+                      uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, const float *reflectivity,
+                      float reflectivityScalar, float *out, void *stream) {
   VR_TRY(paths_refusal(c, api, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity, reflectivityScalar, out));
+  GatherLawSet laws;
+  VR_TRY(gather_laws_refusal(c, api, lawsIn, cosinePower, samples, laws));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
-  VR_TRY(hand_over(c, {reflectivity, out}, "vr_gather_paths_device: reflectivity and out must be device memory of the context's device",
-                   stream));
+  VR_TRY(hand_over(c, {reflectivity, out},
+                   (std::string(api) + ": reflectivity and out must be device memory of the context's device").c_str(), stream));
   if (reflectivity)
     VR_TRY(paths_table(c, api, reflectivity));
   if (primCount == 0)
     return caller_waits(c, stream);
-  VR_TRY(paths_on_device(c, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity != nullptr,
+  VR_TRY(paths_on_device(c, laws, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity != nullptr,
                          reflectivityScalar, out));
   return caller_waits(c, stream);
 }
 
-int vr_gather_paths(vr_context *c, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower, uint32_t reflection,
-                    uint32_t maxBounces, const float *reflectivity, float reflectivityScalar, float *out) {
-  if (!c)
-    return VR_E_INVALID;
-  const char *api = "vr_gather_paths";
+int paths_call_host(vr_context *c, const char *api, const vr_gather_laws *lawsIn, uint32_t primFirst, uint32_t primCount,
+                    uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, const float *reflectivity,
+                    float reflectivityScalar, float *out) {
   VR_TRY(paths_refusal(c, api, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity, reflectivityScalar, out));
+  GatherLawSet laws;
+  VR_TRY(gather_laws_refusal(c, api, lawsIn, cosinePower, samples, laws));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_HIP(c, hipSetDevice(c->device));
   bool waited = false;
@@ -138,28 +136,28 @@ int vr_gather_paths(vr_context *c, uint32_t primFirst, uint32_t primCount, uint3
   if (primCount == 0)
     return VR_OK;
   VR_TRY(map_grow(c, c->dGatherOut, primCount, waited));
-  VR_TRY(paths_on_device(c, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity != nullptr,
+  VR_TRY(paths_on_device(c, laws, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity != nullptr,
                          reflectivityScalar, c->dGatherOut.p));
   VR_HIP(c, hipMemcpyAsync(out, c->dGatherOut.p, (size_t)primCount * 4, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   return VR_OK;
 }
 
-int vr_debug_gather_path(vr_context *c, uint32_t prim, uint32_t sample, float cosinePower, uint32_t reflection, uint32_t maxBounces,
-                         const float *reflectivity, float reflectivityScalar, uint32_t maxVertices, uint32_t *vertexIds,
-                         float *vertexData, uint32_t *numVertices, uint32_t *end, float *finalDirection3, float *throughput,
-                         float *weight) {
-  if (!c)
-    return VR_E_INVALID;
-  const char *api = "vr_debug_gather_path";
+int paths_call_debug(vr_context *c, const char *api, const vr_gather_laws *lawsIn, uint32_t prim, uint32_t sample, float cosinePower,
+                     uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float reflectivityScalar,
+                     uint32_t maxVertices, uint32_t *vertexIds, float *vertexData, uint32_t *numVertices, uint32_t *end,
+                     float *finalDirection3, float *throughput, float *weight) {
+  const std::string name = api;
   // (the checks of the call itself for a range of one primitive and one sample; c: a non-null `out`)
   VR_TRY(paths_refusal(c, api, prim, 1, 1, cosinePower, reflection, maxBounces, reflectivity, reflectivityScalar, c));
+  GatherLawSet laws;
+  VR_TRY(gather_laws_refusal(c, api, lawsIn, cosinePower, 1, laws));
   if (maxVertices && (!vertexIds || !vertexData))
-    return fail(c, VR_E_INVALID, "vr_debug_gather_path: vertexIds and vertexData must not be null with maxVertices > 0");
+    return fail(c, VR_E_INVALID, (name + ": vertexIds and vertexData must not be null with maxVertices > 0").c_str());
   if (maxVertices > VR_GATHER_MAX_BOUNCES + 2u)
-    return fail(c, VR_E_INVALID, "vr_debug_gather_path: maxVertices must not exceed VR_GATHER_MAX_BOUNCES + 2");
+    return fail(c, VR_E_INVALID, (name + ": maxVertices must not exceed VR_GATHER_MAX_BOUNCES + 2").c_str());
   if (sample >= (1u << 22)) // (samples x g <= 2^22: no call has a sample beyond)
-    return fail(c, VR_E_INVALID, "vr_debug_gather_path: sample must be below 2^22, the most samples a call can have");
+    return fail(c, VR_E_INVALID, (name + ": sample must be below 2^22, the most samples a call can have").c_str());
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_HIP(c, hipSetDevice(c->device));
   bool waited = false;
@@ -174,9 +172,10 @@ int vr_debug_gather_path(vr_context *c, uint32_t prim, uint32_t sample, float co
   VR_TRY(map_grow(c, c->dGatherAcc, 1, waited));
   TraceParams p;
   GatherArgs a;
-  VR_TRY(paths_args(c, waited, p, a, prim, 1, 1, cosinePower, reflection, maxBounces, reflectivity != nullptr, reflectivityScalar));
+  VR_TRY(paths_args(c, waited, p, a, laws, prim, 1, 1, cosinePower, reflection, maxBounces, reflectivity != nullptr,
+                    reflectivityScalar));
   if (c->walkStackWaves == 0)
-    return fail(c, VR_E_STATE, "vr_debug_gather_path: the walk stack has no slab");
+    return fail(c, VR_E_STATE, (name + ": the walk stack has no slab").c_str());
   a.acc = c->dGatherAcc.p; // (the kernel is the gather's: the one sample's sum goes where a gather's would)
   VR_HIP(c, hipMemsetAsync(c->dGatherAcc.p, 0, 8, c->stream));
   float *d = c->dGatherOut.p;
@@ -207,6 +206,40 @@ int vr_debug_gather_path(vr_context *c, uint32_t prim, uint32_t sample, float co
   if (weight)
     *weight = tail[6];
   return VR_OK;
+}
+
+} // namespace vr
+
+using namespace vr;
+
+extern "C" {
+
+int vr_gather_paths_device(vr_context *c, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower,
+                           uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float reflectivityScalar, float *out,
+                           void *stream) {
+  if (!c)
+    return VR_E_INVALID;
+  return paths_call_device(c, "vr_gather_paths_device", nullptr, primFirst, primCount, samples, cosinePower, reflection, maxBounces,
+                           reflectivity, reflectivityScalar, out, stream);
+}
+
+int vr_gather_paths(vr_context *c, uint32_t primFirst, uint32_t primCount, uint32_t samples, float cosinePower, uint32_t reflection,
+                    uint32_t maxBounces, const float *reflectivity, float reflectivityScalar, float *out) {
+  if (!c)
+    return VR_E_INVALID;
+  return paths_call_host(c, "vr_gather_paths", nullptr, primFirst, primCount, samples, cosinePower, reflection, maxBounces,
+                         reflectivity, reflectivityScalar, out);
+}
+
+int vr_debug_gather_path(vr_context *c, uint32_t prim, uint32_t sample, float cosinePower, uint32_t reflection, uint32_t maxBounces,
+                         const float *reflectivity, float reflectivityScalar, uint32_t maxVertices, uint32_t *vertexIds,
+                         float *vertexData, uint32_t *numVertices, uint32_t *end, float *finalDirection3, float *throughput,
+                         float *weight) {
+  if (!c)
+    return VR_E_INVALID;
+  return paths_call_debug(c, "vr_debug_gather_path", nullptr, prim, sample, cosinePower, reflection, maxBounces, reflectivity,
+                          reflectivityScalar, maxVertices, vertexIds, vertexData, numVertices, end, finalDirection3, throughput,
+                          weight);
 }
 
 } // extern "C"

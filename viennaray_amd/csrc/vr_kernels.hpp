@@ -182,6 +182,12 @@ struct GatherArgs {
   unsigned long long *accSq;
   const uint32_t *list;
   uint32_t listCount;
+  // the angular laws of vr_gather_angular* (laws == nullptr: none; read by the PATH 3 kernels and by the one-path walk
+  // alone): 3 x GATHER_LAW_MAX floats — source, reflectivity, yield (vr_gather.hpp: GATHER_LAW_*) — of which law w has
+  // lawCount[w] entries, 0: absent; gL: gather_law_g of the source law
+  const float *laws;
+  uint32_t lawCount[3];
+  float gL;
 };
 // one round's verdict of vr_gather_adaptive_device (vr_gather.hip: gather_decide_kernel).  Entry e of the current list
 // (list == nullptr: e itself) is a primitive of the range as GatherArgs::list names it; origWords != nullptr (the whole
@@ -203,6 +209,8 @@ hipError_t launch_gather_decide(const GatherDecideArgs &d, hipStream_t st);
 // p, slabs: as launch_cast_rays.  One launch of at most min(slabs, groups x chunks x subs) waves
 hipError_t launch_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned slabs, hipStream_t st);
 hipError_t launch_gather_finish(const unsigned long long *acc, unsigned n, unsigned samples, float *out, hipStream_t st);
+// hostTable: 3 x 256 HOST floats (GatherArgs::laws' layout), copied at the call; dst: that many floats of device memory
+hipError_t launch_gather_laws(const float *hostTable, float *dst, hipStream_t st);
 // ONE path of vr_gather_paths (vr_debug_gather_path): sample `sample` of original primitive a.primFirst (a.leafOfOrig
 // set, a.paths set).  vertices: up to maxVertices rows of GATHER_PATH_ROW floats {id bits, point, arriving direction,
 // normal, leaving direction}; tail: GATHER_PATH_TAIL floats {vertex count bits, end code bits, final direction, T, weight}

@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from . import capi
-from .capi import VrError, TraceInfoPOD, ParticlePOD, GatherSpecPOD, GatherAdaptiveInfoPOD
+from .capi import VrError, TraceInfoPOD, ParticlePOD, GatherSpecPOD, GatherAdaptiveInfoPOD, GatherLawsPOD
 
 
 class BoundaryCondition(enum.IntEnum):  # rayBoundary.hpp:10-14
@@ -1040,38 +1040,44 @@ class Trace:
             spec.reflectivity = table.data_ptr() if device else table.ctypes.data
         return spec, (not device and (table is not None or numpy)), table
 
-    def _gatherSums(self, spec, host, primFirst, primCount, chunkFirst, chunks, budget):
+    def _gatherSums(self, spec, host, primFirst, primCount, chunkFirst, chunks, budget, laws=None):
+        """laws: None (vr_gather_sums*) or a GatherLawsPOD (vr_gather_angular_sums*)"""
+        head = (self._h, C.byref(spec)) + ((C.byref(laws),) if laws is not None else ())
         if host:
             s1, s2 = np.empty(primCount, dtype=np.int64), np.empty(primCount, dtype=np.int64)
             i64 = C.POINTER(C.c_int64)
-            self._check(self._L.vr_gather_sums(self._h, C.byref(spec), primFirst, primCount, int(chunkFirst), int(chunks),
-                                               int(budget), s1.ctypes.data_as(i64), s2.ctypes.data_as(i64)))
+            call = self._L.vr_gather_sums if laws is None else self._L.vr_gather_angular_sums
+            self._check(call(*head, primFirst, primCount, int(chunkFirst), int(chunks), int(budget), s1.ctypes.data_as(i64),
+                             s2.ctypes.data_as(i64)))
             return s1, s2
         import torch
         dev = torch.device("cuda", self._device)
         s1, s2 = torch.empty(primCount, dtype=torch.int64, device=dev), torch.empty(primCount, dtype=torch.int64, device=dev)
-        self._check(self._L.vr_gather_sums_device(self._h, C.byref(spec), primFirst, primCount, int(chunkFirst), int(chunks),
-                                                  int(budget), C.c_void_p(s1.data_ptr()), C.c_void_p(s2.data_ptr()),
-                                                  C.c_void_p(self._torch_stream())))
+        call = self._L.vr_gather_sums_device if laws is None else self._L.vr_gather_angular_sums_device
+        self._check(call(*head, primFirst, primCount, int(chunkFirst), int(chunks), int(budget), C.c_void_p(s1.data_ptr()),
+                         C.c_void_p(s2.data_ptr()), C.c_void_p(self._torch_stream())))
         return s1, s2
 
-    def _gatherAdaptive(self, spec, host, primFirst, primCount, target, absTarget, minSamples, maxSamples, returnInfo):
+    def _gatherAdaptive(self, spec, host, primFirst, primCount, target, absTarget, minSamples, maxSamples, returnInfo,
+                        laws=None):
+        """laws: None (vr_gather_adaptive*) or a GatherLawsPOD (vr_gather_angular_adaptive*)"""
         info = GatherAdaptiveInfoPOD()
+        head = (self._h, C.byref(spec)) + ((C.byref(laws),) if laws is not None else ())
         if host:
             flux, err = np.empty(primCount, dtype=np.float32), np.empty(primCount, dtype=np.float32)
             used = np.empty(primCount, dtype=np.uint32)
-            self._check(self._L.vr_gather_adaptive(self._h, C.byref(spec), primFirst, primCount, int(minSamples),
-                                                   int(maxSamples), float(target), float(absTarget), _fptr(flux), _fptr(err),
-                                                   used.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info)))
+            call = self._L.vr_gather_adaptive if laws is None else self._L.vr_gather_angular_adaptive
+            self._check(call(*head, primFirst, primCount, int(minSamples), int(maxSamples), float(target), float(absTarget),
+                             _fptr(flux), _fptr(err), used.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info)))
         else:
             import torch
             dev = torch.device("cuda", self._device)
             flux, err = torch.empty(primCount, dtype=torch.float32, device=dev), torch.empty(primCount, dtype=torch.float32, device=dev)
             store = torch.empty(primCount, dtype=torch.int32, device=dev)  # (the uint32 counts, at most 2^22)
-            self._check(self._L.vr_gather_adaptive_device(
-                self._h, C.byref(spec), primFirst, primCount, int(minSamples), int(maxSamples), float(target), float(absTarget),
-                C.c_void_p(flux.data_ptr()), C.c_void_p(err.data_ptr()), C.c_void_p(store.data_ptr()), C.byref(info),
-                C.c_void_p(self._torch_stream())))
+            call = self._L.vr_gather_adaptive_device if laws is None else self._L.vr_gather_angular_adaptive_device
+            self._check(call(*head, primFirst, primCount, int(minSamples), int(maxSamples), float(target), float(absTarget),
+                             C.c_void_p(flux.data_ptr()), C.c_void_p(err.data_ptr()), C.c_void_p(store.data_ptr()), C.byref(info),
+                             C.c_void_p(self._torch_stream())))
             used = store
         return (flux, err, used, info.as_dict()) if returnInfo else (flux, err, used)
 
@@ -1114,6 +1120,108 @@ class Trace:
         _, primFirst, primCount = self._gatherRange("gatherPathsSums", primFirst, primCount, chunkFirst, chunks, budget, maxBounces)
         spec, host, keep = self._pathsSpec("gatherPathsSums", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
         return self._gatherSums(spec, host, primFirst, primCount, chunkFirst, chunks, budget)
+
+    # --- angular gather: a path weighed by tabulated source radiance, sticking and yield (vr_gather_angular*) --------
+    def _angularLaws(self, name, sourceLaw, reflectivityLaw, yieldLaw, stickingLaw=None):
+        """(GatherLawsPOD, the host arrays it points to): each law None or 2 .. 256 values over a cosine in [0, 1], a
+        sequence, a numpy array or a tensor (the tables are always handed over as HOST arrays); stickingLaw is accepted
+        in place of reflectivityLaw as 1 - R in float32"""
+        if stickingLaw is not None:
+            if reflectivityLaw is not None:
+                raise ValueError("%s: give at most one of stickingLaw and reflectivityLaw" % name)
+            t = stickingLaw.detach().cpu().numpy() if hasattr(stickingLaw, "data_ptr") else stickingLaw
+            reflectivityLaw = (np.float32(1.0) - np.asarray(t, dtype=np.float32)).astype(np.float32)
+        pod, keep = GatherLawsPOD(), []
+        for field, count, law in (("sourceLaw", "sourceCount", sourceLaw), ("reflectivityLaw", "reflectivityCount", reflectivityLaw),
+                                  ("yieldLaw", "yieldCount", yieldLaw)):
+            if law is None:
+                continue
+            if hasattr(law, "data_ptr"):
+                law = law.detach().cpu().numpy()
+            t = np.ascontiguousarray(law, dtype=np.float32).reshape(-1)
+            keep.append(t)
+            setattr(pod, field, t.ctypes.data)
+            setattr(pod, count, t.size)
+        return pod, keep
+
+    def gatherAngular(self, samples, sourceLaw=None, reflectivityLaw=None, yieldLaw=None, sticking=None, reflectivity=None,
+                      reflection=GatherReflection.SPECULAR, maxBounces=64, primFirst=0, primCount=None, numpy=False,
+                      cosinePower=1.0, stickingLaw=None):
+        """gatherPaths with up to three tabulated ANGULAR LAWS: each 2 .. 256 float32 values read as the piecewise-linear
+        function of a cosine in [0, 1], nodes at k / (M - 1).
+          sourceLaw        L(c), the source's radiance by c = u . direction relative to a Lambertian source (a measured
+                           sputter-target distribution; c^(n - 1) is the power cosine).  Normalised by the library; needs
+                           cosinePower == 1.  The law weighs the samples, it does not place them.
+          reflectivityLaw  R(mu), the share NOT absorbed at a vertex by mu = normal . leaving direction, the forward
+                           particle's cosine of incidence; the throughput takes (T * reflectivity) * R(mu).  stickingLaw=
+                           is accepted as 1 - R.
+          yieldLaw         Y(mu0) by the sample's initial direction against the starting primitive's normal: the etch or
+                           resputter yield of what arrives; it may exceed 1.
+        sticking | reflectivity, reflection, maxBounces, the range, tensors and numpy arrays as gatherPaths (the laws
+        themselves are always read on the host).  With no law, or with all-ones laws, the result has gatherPaths's bits
+        (vr_gather_angular*; include/viennaray_amd.h has the definition)."""
+        _, primFirst, primCount = self._gatherRange("gatherAngular", primFirst, primCount, samples, maxBounces)
+        spec, host, keep = self._pathsSpec("gatherAngular", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
+        laws, keepLaws = self._angularLaws("gatherAngular", sourceLaw, reflectivityLaw, yieldLaw, stickingLaw)
+        if host:
+            out = np.empty(primCount, dtype=np.float32)
+            self._check(self._L.vr_gather_angular(self._h, C.byref(spec), C.byref(laws), primFirst, primCount, int(samples),
+                                                  _fptr(out)))
+            return out
+        import torch
+        out = torch.empty(primCount, dtype=torch.float32, device=torch.device("cuda", self._device))
+        self._check(self._L.vr_gather_angular_device(self._h, C.byref(spec), C.byref(laws), primFirst, primCount, int(samples),
+                                                     C.c_void_p(out.data_ptr()), C.c_void_p(self._torch_stream())))
+        return out
+
+    def gatherAngularAdaptive(self, target, sourceLaw=None, reflectivityLaw=None, yieldLaw=None, sticking=None, reflectivity=None,
+                              reflection=GatherReflection.SPECULAR, maxBounces=64, minSamples=64, maxSamples=4096, absTarget=0.0,
+                              primFirst=0, primCount=None, returnInfo=False, numpy=False, cosinePower=1.0, stickingLaw=None):
+        """gatherAngular to a target error, as gatherPathsAdaptive: (flux, stdErr, samples), plus the info dict when asked;
+        flux[i] has the bits of gatherAngular(samples[i]) (vr_gather_angular_adaptive*)."""
+        _, primFirst, primCount = self._gatherRange("gatherAngularAdaptive", primFirst, primCount, minSamples, maxSamples, maxBounces)
+        spec, host, keep = self._pathsSpec("gatherAngularAdaptive", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
+        laws, keepLaws = self._angularLaws("gatherAngularAdaptive", sourceLaw, reflectivityLaw, yieldLaw, stickingLaw)
+        return self._gatherAdaptive(spec, host, primFirst, primCount, target, absTarget, minSamples, maxSamples, returnInfo, laws)
+
+    def gatherAngularSums(self, chunkFirst, chunks, budget, sourceLaw=None, reflectivityLaw=None, yieldLaw=None, sticking=None,
+                          reflectivity=None, reflection=GatherReflection.SPECULAR, maxBounces=64, primFirst=0, primCount=None,
+                          numpy=False, cosinePower=1.0, stickingLaw=None):
+        """(sum, sumSq) as gatherPathsSums, of gatherAngular's samples (vr_gather_angular_sums*)"""
+        _, primFirst, primCount = self._gatherRange("gatherAngularSums", primFirst, primCount, chunkFirst, chunks, budget, maxBounces)
+        spec, host, keep = self._pathsSpec("gatherAngularSums", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
+        laws, keepLaws = self._angularLaws("gatherAngularSums", sourceLaw, reflectivityLaw, yieldLaw, stickingLaw)
+        return self._gatherSums(spec, host, primFirst, primCount, chunkFirst, chunks, budget, laws)
+
+    def debugGatherAngularPath(self, prim, sample, laws=None, sticking=None, reflectivity=None, reflection=GatherReflection.SPECULAR,
+                               maxBounces=64, cosinePower=1.0, maxVertices=None):
+        """ONE path of gatherAngular, as debugGatherPath's dict.  laws: None or a dict with any of the keys sourceLaw,
+        reflectivityLaw, stickingLaw, yieldLaw.  Every vertex's mu is normals[v] . leaving[v]; throughput and weight are
+        the path's under the laws (vr_debug_gather_angular_path)."""
+        _, scalar, table = self._pathReflectivity("debugGatherAngularPath", sticking, reflectivity, host_only=True)
+        spec = GatherSpecPOD(cosinePower=float(cosinePower), mode=int(GatherMode.NORMAL), paths=1, reflection=int(reflection),
+                             maxBounces=int(maxBounces), reflectivityScalar=scalar)
+        if table is not None:
+            spec.reflectivity = table.ctypes.data
+        laws = dict(laws or {})
+        unknown = set(laws) - {"sourceLaw", "reflectivityLaw", "stickingLaw", "yieldLaw"}
+        if unknown:
+            raise ValueError("debugGatherAngularPath: unknown laws %s" % sorted(unknown))
+        pod, keepLaws = self._angularLaws("debugGatherAngularPath", laws.get("sourceLaw"), laws.get("reflectivityLaw"),
+                                          laws.get("yieldLaw"), laws.get("stickingLaw"))
+        cap = int(maxBounces) + 2 if maxVertices is None else int(maxVertices)
+        ids = np.zeros(cap, dtype=np.uint32)
+        data = np.full((cap, 4, 3), np.nan, dtype=np.float32)
+        count, end = C.c_uint32(0), C.c_uint32(0)
+        final = np.empty(3, np.float32)
+        T, w = C.c_float(0.0), C.c_float(0.0)
+        self._check(self._L.vr_debug_gather_angular_path(
+            self._h, C.byref(spec), C.byref(pod), int(prim), int(sample), cap, ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+            _fptr(data), C.byref(count), C.byref(end), _fptr(final), C.byref(T), C.byref(w)))
+        v = min(cap, int(count.value))
+        return {"ids": ids[:v].astype(np.int64), "points": data[:v, 0], "arriving": data[:v, 1], "normals": data[:v, 2],
+                "leaving": data[:v, 3], "numVertices": int(count.value), "end": int(end.value), "direction": final,
+                "throughput": np.float32(T.value), "weight": np.float32(w.value)}
 
     # --- radiosity solve: the steady-state flux of a diffusely re-emitting species (vr_radiosity_*) ------------------
     def radiosityLinkBytes(self, samples):
