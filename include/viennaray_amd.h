@@ -722,6 +722,62 @@ int vr_debug_gather_angular_path(vr_context *ctx, const vr_gather_spec *spec, co
                                  uint32_t sample, uint32_t maxVertices, uint32_t *vertexIds, float *vertexData,
                                  uint32_t *numVertices, uint32_t *end, float *finalDirection3, float *throughput,
                                  float *weight);
+/* ---- species gather (not in the reference): several species weighed along one set of traced paths ----------------------
+ * A process step has two or three ion species, or one whose arrivals feed several yields.  Each is a vr_gather_angular
+ * call, and every call walks the same paths again: the samples are a pure function of (seed, primitive, sample), the
+ * mirror direction follows from the normal, the DIFFUSE draw from (seed, primitive, sample, bounce).  What differs per
+ * species is a handful of multiplies along the path.  These calls walk once for up to VR_GATHER_MAX_SPECIES species.
+ * Species  A call has S species, 1 <= S <= VR_GATHER_MAX_SPECIES.  Species s is specs[s] plus, where laws is not NULL,
+ *          laws[s], and means exactly what vr_gather_angular means by that pair (vr_gather_paths where it has no law).
+ *          Shared by all species: paths == 1, mode == VR_GATHER_NORMAL, emission == NULL, reflection, maxBounces.
+ *          Per species: cosinePower (1 where it has a source law), reflectivity or reflectivityScalar, the three laws.
+ * Path     The shared path is sample k of primitive i exactly as vr_gather_paths starts and walks it.  Every species
+ *          starts alive with T_s = 1.  At a geometry hit of primitive j, in vr_gather_paths's order:
+ *            1. a back side ends the path for every species;
+ *            2. bounces >= maxBounces ends the path for every species;
+ *            3. for each species still alive T_s <- T_s * rho_s[j]; T_s == 0 makes that species dead;
+ *            4. if no species is alive the path ends;
+ *            5. otherwise the leaving direction is formed ONCE (the mirror direction, or the counter draw of this bounce);
+ *            6. for each living species with a reflectivity law T_s <- T_s * R_s(mu); T_s == 0 makes it dead;
+ *            7. if none is alive the path ends; otherwise it restarts from the hit point and the bounce is counted.
+ *          A dead species weighs exactly 0 for this sample: it is not weighed from a T of 0.  The path's geometry is that
+ *          of the species that lives longest; up to its own death every species sees its own single-species path.
+ * Weight   At the path's tail every living species is weighed by vr_gather_angular's rule with its own g, cosinePower,
+ *          g_L, laws and T_s and the shared c_end and mu0, then q() with wmax(samples) into its own exact int64 sum.
+ * Result   out[s * primCount + (i - primFirst)].  Row s has the BITS of the single-species call of species s —
+ *          vr_gather_angular(specs[s], laws[s]), vr_gather_paths without laws — for every s, S, order of the species,
+ *          split of the primitive range over calls and launch shape.  That identity is the specification.
+ * Sums     vr_gather_species_sums*: sum and sumSq as vr_gather_angular_sums gives them, numSpecies x primCount each, row s
+ *          that call's for species s bit for bit.  (An adaptive species call is not offered: the sums are its layer.)
+ * Bounds   samples (budget) x wbound_s <= 2^22 for every species, wbound as vr_gather_angular's.
+ * Refused, outputs untouched and the context usable, message in vr_last_error — every message about one species names it
+ * ("... species 2: ..."):
+ *   VR_E_INVALID  specs NULL; numSpecies 0 or above VR_GATHER_MAX_SPECIES; a species whose paths is not 1, whose mode is
+ *                 not VR_GATHER_NORMAL or that has an emission table; a species whose reflection or maxBounces differs from
+ *                 species 0's (the first such species); what vr_gather_angular refuses of a species' spec and laws — the
+ *                 samples x wbound rule, a law's count or entries, a reflectivity outside [0, 1] (a table is checked on
+ *                 the device, one word per species back: the first species with a bad entry and its lowest such index);
+ *                 out, sum or sumSq null with primCount > 0; 64 (chunkFirst + chunks) > budget.
+ *                 primCount == 0 is VR_OK after the checks.
+ *   VR_E_STATE    as vr_gather_flux_device.
+ * Streams, work buffers (numSpecies of each of the gather's) and "changes nothing of a finished apply": as
+ * vr_gather_angular_device.  vr_debug_gather_angular_path with species s's spec and laws returns that species' prefix of
+ * the shared path.
+ * specs: numSpecies structs; laws: NULL or numSpecies structs (HOST tables, as vr_gather_angular); specs[s].reflectivity:
+ * DEVICE memory in the _device forms, HOST memory in the others; out: numSpecies x primCount floats; sum, sumSq:
+ * numSpecies x primCount int64 */
+#define VR_GATHER_MAX_SPECIES 4u
+int vr_gather_species_device(vr_context *ctx, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t numSpecies,
+                             uint32_t primFirst, uint32_t primCount, uint32_t samples, float *out, void *stream);
+/* the same from and to host arrays */
+int vr_gather_species(vr_context *ctx, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t numSpecies,
+                      uint32_t primFirst, uint32_t primCount, uint32_t samples, float *out);
+int vr_gather_species_sums_device(vr_context *ctx, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t numSpecies,
+                                  uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget,
+                                  int64_t *sum, int64_t *sumSq, void *stream);
+int vr_gather_species_sums(vr_context *ctx, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t numSpecies,
+                           uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget,
+                           int64_t *sum, int64_t *sumSq);
 /* ---- radiosity solve (not in the reference): the steady-state flux of a diffusely re-emitting species ------------------
  * vr_gather_flux with an emission table is one radiosity iteration, and its walks are a constant of the scene.  These
  * calls record them once — a link table — and iterate over the table on the device without walking again.

@@ -1543,6 +1543,67 @@ public:
                                                  &rec.numVertices, &rec.end, rec.direction, &rec.throughput, &rec.weight));
   }
 
+  // ---- species gather (not in the reference; vr_gather_species*, whose header comment has the definition): up to
+  //      VR_GATHER_MAX_SPECIES species weighed along ONE set of traced paths.  Row s of the result is gatherAngular of
+  //      species s word for word; reflection and maxBounces make the path and are shared.
+  /// one species: gatherAngular's per-species arguments.  reflectivity: empty (the scalar 1 - sticking counts) or one value
+  /// per primitive; the object must outlive the call
+  struct GatherSpecies {
+    NumericType sticking = 1;
+    std::vector<float> reflectivity;
+    NumericType cosinePower = 1;
+    GatherLaws laws;
+  };
+  /// row-major [species][primitive] (empty if it was refused)
+  [[nodiscard]] std::vector<NumericType> gatherSpecies(unsigned samples, const std::vector<GatherSpecies> &species,
+                                                       GatherReflection reflection = GatherReflection::SPECULAR,
+                                                       unsigned maxBounces = 64) {
+    if (!ctx_)
+      return {};
+    std::vector<vr_gather_spec> specs;
+    std::vector<vr_gather_laws> laws;
+    speciesPods(species, reflection, maxBounces, specs, laws);
+    std::vector<float> raw(species.size() * (size_t)vr_num_primitives(ctx_));
+    if (!reported(vr_gather_species(ctx_, specs.data(), laws.data(), (uint32_t)species.size(), 0u, vr_num_primitives(ctx_), samples,
+                                    raw.data())))
+      return {};
+    return std::vector<NumericType>(raw.begin(), raw.end());
+  }
+  /// specs[s].reflectivity and dOut (numSpecies x primCount floats) are DEVICE memory, the laws the host's (nullptr: none);
+  /// gatherPathsDevice's stream rules
+  bool gatherSpeciesDevice(const std::vector<vr_gather_spec> &specs, const vr_gather_laws *laws, unsigned primFirst,
+                           unsigned primCount, unsigned samples, float *dOut, void *stream = nullptr) {
+    return ctx_ && reported(vr_gather_species_device(ctx_, specs.data(), laws, (uint32_t)specs.size(), primFirst, primCount, samples,
+                                                     dOut, stream));
+  }
+  /// gatherAngularSums for every species along one set of paths: sum, sumSq row-major [species][primitive].  false if it
+  /// was refused.
+  bool gatherSpeciesSums(const std::vector<GatherSpecies> &species, GatherReflection reflection, unsigned maxBounces,
+                         unsigned chunkFirst, unsigned chunks, unsigned budget, std::vector<int64_t> &sum,
+                         std::vector<int64_t> &sumSq) {
+    if (!ctx_)
+      return false;
+    std::vector<vr_gather_spec> specs;
+    std::vector<vr_gather_laws> laws;
+    speciesPods(species, reflection, maxBounces, specs, laws);
+    const uint32_t n = vr_num_primitives(ctx_);
+    sum.assign(species.size() * (size_t)n, 0);
+    sumSq.assign(species.size() * (size_t)n, 0);
+    return reported(vr_gather_species_sums(ctx_, specs.data(), laws.data(), (uint32_t)species.size(), 0u, n, chunkFirst, chunks, budget,
+                                           sum.data(), sumSq.data()));
+  }
+  /// the specs and laws of a list of species (host tables; the species must outlive them)
+  static void speciesPods(const std::vector<GatherSpecies> &species, GatherReflection reflection, unsigned maxBounces,
+                          std::vector<vr_gather_spec> &specs, std::vector<vr_gather_laws> &laws) {
+    specs.clear();
+    laws.clear();
+    for (const GatherSpecies &s : species) {
+      specs.push_back(pathsSpec(s.reflectivity.empty() ? nullptr : s.reflectivity.data(), 1.f - (float)s.sticking, reflection,
+                                maxBounces, s.cosinePower));
+      laws.push_back(s.laws.pod());
+    }
+  }
+
   // ---- radiosity solve (not in the reference; vr_radiosity_*, whose header comment has the definition): the
   //      steady-state incoming flux of a species re-emitted diffusely with probability 1 - sticking — the fixed point of
   //      gatherFlux(samples, emission = (1 - sticking) x flux).  The samples are walked once into a link table that stays

@@ -20,6 +20,8 @@ for b in blocks:
     n = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip().replace('vr::', '').split('(')[0]
     if len(sys.argv) > 2 and not any(k in n for k in sys.argv[2:]):
         continue
-    print("%-40s sgpr %4s vgpr %4s scratch %4s occ %2s sspill %3s vspill %3s lds %6s" % (
+    # (AGPRs count against the same 512 registers per SIMD lane as the VGPRs: shown where a kernel uses any)
+    agprs = g(' AGPRs')
+    print("%-40s sgpr %4s vgpr %4s scratch %4s occ %2s sspill %3s vspill %3s lds %6s%s" % (
         n[-40:], g('SGPRs'), g('VGPRs'), g(r'ScratchSize \[bytes/lane\]'), g(r'Occupancy \[waves/SIMD\]'),
-        g('SGPRs Spill'), g('VGPRs Spill'), g(r'LDS Size \[bytes/block\]')))
+        g('SGPRs Spill'), g('VGPRs Spill'), g(r'LDS Size \[bytes/block\]'), "" if agprs in ("0", "?") else " agpr %3s" % agprs))

@@ -19,6 +19,7 @@ VR_CAST_MISS, VR_CAST_WALL = -1, -2  # ... its result codes in prim[]
 VR_GATHER_NORMAL, VR_GATHER_SOURCE = 0, 1  # vr_gather_flux*: the sampling mode
 VR_GATHER_REFLECT_SPECULAR, VR_GATHER_REFLECT_DIFFUSE = 0, 1  # vr_gather_paths*: what a vertex does
 VR_GATHER_MAX_BOUNCES = 65535  # ... the largest maxBounces
+VR_GATHER_MAX_SPECIES = 4  # vr_gather_species*: the most species of a call
 VR_GATHER_PATH_VERTEX_FLOATS = 12  # vr_debug_gather_path: point, arriving direction, normal, leaving direction
 # ... how a path ended
 (VR_GATHER_END_MISS, VR_GATHER_END_IGNORED, VR_GATHER_END_WALL, VR_GATHER_END_BACK, VR_GATHER_END_BOUNCES,
@@ -179,6 +180,15 @@ SIGNATURES = {
                                              C.POINTER(GatherAdaptiveInfoPOD)]),
     "vr_debug_gather_angular_path": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
                                                C.c_uint32, _u32p, _fp, _u32p, _u32p, _fp, _fp, _fp]),
+    "vr_gather_species_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vr_gather_species": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32, C.c_uint32,
+                                    C.c_uint32, _fp]),
+    "vr_gather_species_sums_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vr_gather_species_sums": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64)]),
     "vr_radiosity_link_bytes": (C.c_uint64, [_vp, C.c_uint32]),
     "vr_radiosity_links_device": (C.c_int, [_vp, C.c_uint32, C.c_float, _vp]),
     "vr_radiosity_resident": (C.c_int, [_vp, C.c_uint32, C.c_float]),

@@ -395,6 +395,7 @@ struct vr_context {
   DevBuf<float> dGatherErr;
   // vr_gather_angular*: the three angular laws of the call in flight, 3 x GATHER_LAW_MAX floats (written by a kernel from
   // its own arguments on c->stream, so behind an earlier call that still reads them).  Grown behind host_waits only
+  // vr_gather_species* keeps numSpecies of each in the gather's own buffers: sums, laws, reflectivities, verdict words
   DevBuf<float> dGatherLaws;
   // vr_radiosity_*: the link table of the last vr_radiosity_links_device (slots x samples int32 in leaf order,
   // vr_radiosity.hpp), its direct sums and leaf -> original id table, what it was built from, and a solve's work buffers

@@ -395,6 +395,53 @@ VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN float gather_path_throughput_law(float T
   return Trho * gather_law(R, MR, mu);
 }
 
+// ---- gatherSpecies (vr_gather_species*): several species weighed along one traced path -------------------------------
+constexpr uint32_t GATHER_MAX_SPECIES = 4; // VR_GATHER_MAX_SPECIES
+#if defined(__clang__)
+#define VR_GATHER_UNROLL _Pragma("unroll")
+#else
+#define VR_GATHER_UNROLL
+#endif
+// The step of NS species at a front-side hit of the path they share, in two halves: the leaving direction — and with it
+// mu — is formed between them, once, and only if a species is left to follow it.  alive: bit s set while species s still
+// follows the path; a species whose T reaches 0 leaves the mask and its T is not touched again (it weighs 0, it is not
+// weighed).  Each species' multiplies are gather_path_throughput and gather_path_throughput_law, in that order: the T and
+// the vertex of death of species s are those of the single-species path with its rho and R.
+// First half: T_s <- T_s * rho_s of the primitive hit.  Returns the species still alive; 0: the path ends there
+template <int NS> VR_GATHER_FN unsigned gather_species_absorb(float (&T)[NS], unsigned alive, const float (&rho)[NS]) {
+  VR_GATHER_UNROLL
+  for (int s = 0; s < NS; ++s)
+    if ((alive >> s) & 1u) {
+      T[s] = gather_path_throughput(T[s], rho[s]);
+      if (T[s] == 0.f)
+        alive &= ~(1u << s);
+    }
+  return alive;
+}
+// Second half: T_s <- T_s * R_s(mu) for the living species that have a reflectivity law (MR[s] != 0: R[s] holds it), mu =
+// n_j . (the direction the path leaves along)
+template <int NS>
+VR_GATHER_FN unsigned gather_species_reflect(float (&T)[NS], unsigned alive, const float *const (&R)[NS], const uint32_t (&MR)[NS],
+                                             float mu) {
+  VR_GATHER_UNROLL
+  for (int s = 0; s < NS; ++s)
+    if (((alive >> s) & 1u) && MR[s]) {
+      T[s] = gather_path_throughput_law(T[s], R[s], MR[s], mu);
+      if (T[s] == 0.f)
+        alive &= ~(1u << s);
+    }
+  return alive;
+}
+// both halves for a mu that is known beforehand (a host program's view of the step; the kernel calls the halves)
+template <int NS>
+VR_GATHER_FN unsigned gather_species_step(float (&T)[NS], unsigned alive, const float (&rho)[NS], const float *const (&R)[NS],
+                                          const uint32_t (&MR)[NS], float mu) {
+  alive = gather_species_absorb<NS>(T, alive, rho);
+  if (!alive)
+    return 0u;
+  return gather_species_reflect<NS>(T, alive, R, MR, mu);
+}
+
 // g_D(n) (a host function; the kernel takes the float): g_3 = (n + 1) / 2, g_2 = 2 / C_n with
 // C_n = sqrt(pi) Gamma((n + 1) / 2) / Gamma(n / 2 + 1) — the weight of a sample that reaches the source is the ratio of
 // the source's normalised law (n + 1) / (2 pi) c^n (3-D), c^n / C_n (2-D) and the receiver's cosine law c / pi, c / 2 for

@@ -221,6 +221,24 @@ hipError_t launch_debug_gather_path(const TraceParams &p, int geo, int D, const 
 // first + count - 1
 hipError_t launch_debug_gather_samples(const TraceParams &p, int geo, int D, const GatherArgs &a, unsigned first, unsigned count,
                                        float *origin3, float *normal3, float *directions3, hipStream_t st);
+// several species along one set of traced paths (vr_gather_species.hip: gather_species_kernel; vr_gather_species.cpp).
+// a: what the species share — the range, samples, seed, groups / chunks / subs, maxBoundaryHits, wmax, reflection,
+// maxBounces, stat and chunkFirst of a path gather (no list, no laws, no rho: those fields are not read); a.acc (and
+// a.accSq with a.stat): num x primCount int64 sums, species-major, zeroed by the caller.  Per species s < num: rho[s] or
+// rhoLeaf[s] (LEAF order), cosinePower[s], g[s], gL[s], lawCount[s][w] (0: absent) of the three laws at
+// laws + (3 s + w) x GATHER_LAW_MAX (laws == nullptr: no species has a law)
+constexpr unsigned GATHER_SPECIES_MAX = 4;
+struct GatherSpeciesArgs {
+  GatherArgs a;
+  uint32_t num; // 2 .. GATHER_SPECIES_MAX (one species is a path gather)
+  float rho[GATHER_SPECIES_MAX];
+  const float *rhoLeaf[GATHER_SPECIES_MAX];
+  float cosinePower[GATHER_SPECIES_MAX], g[GATHER_SPECIES_MAX], gL[GATHER_SPECIES_MAX];
+  uint32_t lawCount[GATHER_SPECIES_MAX][3];
+  const float *laws;
+};
+// p, slabs: as launch_gather_samples, and its shape: one launch of at most min(slabs, groups x chunks x subs) waves
+hipError_t launch_gather_species(const TraceParams &p, int geo, int D, const GatherSpeciesArgs &sa, unsigned slabs, hipStream_t st);
 // the radiosity solve over a recorded link table (vr_radiosity.hip; vr_radiosity.hpp has the arithmetic and the table's
 // index).  Every pointer is device memory; everything but rho / out of the rho and unpermute launches is in LEAF order
 struct RadiosityArgs {

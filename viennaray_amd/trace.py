@@ -1223,6 +1223,79 @@ class Trace:
                 "leaving": data[:v, 3], "numVertices": int(count.value), "end": int(end.value), "direction": final,
                 "throughput": np.float32(T.value), "weight": np.float32(w.value)}
 
+    # --- species gather: several species weighed along one set of traced paths (vr_gather_species*) ------------------
+    _SPECIES_KEYS = {"sticking", "reflectivity", "cosinePower", "sourceLaw", "reflectivityLaw", "stickingLaw", "yieldLaw"}
+
+    def _speciesSpecs(self, name, species, reflection, maxBounces, numpy):
+        """(specs array, laws array, host?, what they point to) of a list of species dicts"""
+        species = list(species)
+        specs, laws, keep = (GatherSpecPOD * max(1, len(species)))(), (GatherLawsPOD * max(1, len(species)))(), []
+        forms = set()
+        for s, sp in enumerate(species):
+            sp = dict(sp)
+            unknown = set(sp) - self._SPECIES_KEYS
+            if unknown:
+                raise ValueError("%s: species %d: unknown keys %s" % (name, s, sorted(unknown)))
+            who = "%s: species %d" % (name, s)
+            device, scalar, table = self._pathReflectivity(who, sp.get("sticking"), sp.get("reflectivity"))
+            specs[s] = GatherSpecPOD(cosinePower=float(sp.get("cosinePower", 1.0)), mode=int(GatherMode.NORMAL), paths=1,
+                                     reflection=int(reflection), maxBounces=int(maxBounces), reflectivityScalar=scalar)
+            if table is not None:
+                specs[s].reflectivity = table.data_ptr() if device else table.ctypes.data
+                forms.add("device" if device else "host")
+            laws[s], keepLaws = self._angularLaws(who, sp.get("sourceLaw"), sp.get("reflectivityLaw"), sp.get("yieldLaw"),
+                                                  sp.get("stickingLaw"))
+            keep += [table, keepLaws]
+        if len(forms) > 1:
+            raise ValueError("%s: the species' tables are tensors (the device form) or numpy arrays (the host form), not both" % name)
+        host = "host" in forms or (not forms and numpy)
+        return specs, laws, len(species), host, keep
+
+    def gatherSpecies(self, samples, species, reflection=GatherReflection.SPECULAR, maxBounces=64, primFirst=0, primCount=None,
+                      numpy=False):
+        """gatherAngular for up to capi.VR_GATHER_MAX_SPECIES species along ONE set of traced paths: [S, primCount] float32,
+        row s with the bits of gatherAngular called with species s's arguments.  A path's geometry does not depend on the
+        species; what differs is each one's multiplies along it, so S species cost about the walk of the one that lives
+        longest.
+          species  a list of dicts with keys from sticking | reflectivity (exactly one: a scalar, a numpy array or a
+                   float32 tensor on the tracer's device, per primitive), cosinePower, sourceLaw, reflectivityLaw |
+                   stickingLaw, yieldLaw — gatherAngular's arguments of those names.  Unknown keys raise ValueError.
+          reflection, maxBounces  shared by all species: they make the path.
+        Tensor tables select the device form (a tensor out, on torch's current stream), numpy tables the host form;
+        mixing the two raises ValueError; with scalars alone a tensor comes back unless numpy=True
+        (vr_gather_species*; include/viennaray_amd.h has the definition)."""
+        _, primFirst, primCount = self._gatherRange("gatherSpecies", primFirst, primCount, samples, maxBounces)
+        specs, laws, S, host, keep = self._speciesSpecs("gatherSpecies", species, reflection, maxBounces, numpy)
+        if host:
+            out = np.empty((S, primCount), dtype=np.float32)
+            self._check(self._L.vr_gather_species(self._h, specs, laws, S, primFirst, primCount, int(samples), _fptr(out)))
+            return out
+        import torch
+        out = torch.empty((S, primCount), dtype=torch.float32, device=torch.device("cuda", self._device))
+        self._check(self._L.vr_gather_species_device(self._h, specs, laws, S, primFirst, primCount, int(samples),
+                                                     C.c_void_p(out.data_ptr()), C.c_void_p(self._torch_stream())))
+        return out
+
+    def gatherSpeciesSums(self, chunkFirst, chunks, budget, species, reflection=GatherReflection.SPECULAR, maxBounces=64,
+                          primFirst=0, primCount=None, numpy=False):
+        """(sum, sumSq), two int64 [S, primCount]: row s as gatherAngularSums gives them for species s, along one set of
+        traced paths; species, reflection, maxBounces, tensors and numpy arrays as gatherSpecies (vr_gather_species_sums*)"""
+        _, primFirst, primCount = self._gatherRange("gatherSpeciesSums", primFirst, primCount, chunkFirst, chunks, budget, maxBounces)
+        specs, laws, S, host, keep = self._speciesSpecs("gatherSpeciesSums", species, reflection, maxBounces, numpy)
+        if host:
+            s1, s2 = np.empty((S, primCount), dtype=np.int64), np.empty((S, primCount), dtype=np.int64)
+            i64 = C.POINTER(C.c_int64)
+            self._check(self._L.vr_gather_species_sums(self._h, specs, laws, S, primFirst, primCount, int(chunkFirst), int(chunks),
+                                                       int(budget), s1.ctypes.data_as(i64), s2.ctypes.data_as(i64)))
+            return s1, s2
+        import torch
+        dev = torch.device("cuda", self._device)
+        s1, s2 = torch.empty((S, primCount), dtype=torch.int64, device=dev), torch.empty((S, primCount), dtype=torch.int64, device=dev)
+        self._check(self._L.vr_gather_species_sums_device(self._h, specs, laws, S, primFirst, primCount, int(chunkFirst), int(chunks),
+                                                          int(budget), C.c_void_p(s1.data_ptr()), C.c_void_p(s2.data_ptr()),
+                                                          C.c_void_p(self._torch_stream())))
+        return s1, s2
+
     # --- radiosity solve: the steady-state flux of a diffusely re-emitting species (vr_radiosity_*) ------------------
     def radiosityLinkBytes(self, samples):
         """bytes of device memory the link table for `samples` samples per primitive takes (vr_radiosity_link_bytes)"""
