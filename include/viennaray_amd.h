@@ -748,7 +748,7 @@ int vr_debug_gather_angular_path(vr_context *ctx, const vr_gather_spec *spec, co
  *          vr_gather_angular(specs[s], laws[s]), vr_gather_paths without laws — for every s, S, order of the species,
  *          split of the primitive range over calls and launch shape.  That identity is the specification.
  * Sums     vr_gather_species_sums*: sum and sumSq as vr_gather_angular_sums gives them, numSpecies x primCount each, row s
- *          that call's for species s bit for bit.  (An adaptive species call is not offered: the sums are its layer.)
+ *          that call's for species s bit for bit.  They are the layer under the adaptive call below.
  * Bounds   samples (budget) x wbound_s <= 2^22 for every species, wbound as vr_gather_angular's.
  * Refused, outputs untouched and the context usable, message in vr_last_error — every message about one species names it
  * ("... species 2: ..."):
@@ -778,6 +778,60 @@ int vr_gather_species_sums_device(vr_context *ctx, const vr_gather_spec *specs, 
 int vr_gather_species_sums(vr_context *ctx, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t numSpecies,
                            uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget,
                            int64_t *sum, int64_t *sumSq);
+/* ---- species gather to a target error (not in the reference): per-species adaptive sampling along one walk ----------------
+ * A process step wants each of its species to a target error, not to a fixed K.  vr_gather_species at the worst
+ * primitive's K wastes samples; numSpecies vr_gather_angular_adaptive calls walk the same paths again.  These calls run the
+ * rounds of vr_gather_adaptive once, for all species, and let every species of every primitive stop on its own.
+ * Species  specs[s] plus laws[s], exactly as vr_gather_species takes them, 1 <= numSpecies <= VR_GATHER_MAX_SPECIES.
+ * Targets  relTargets[s], absTargets[s]: HOST arrays of numSpecies floats, the targets of species s.
+ * Rounds   minSamples, maxSamples, the chunk ranges of the rounds and wmax = wmax(maxSamples) in every round are those of
+ *          vr_gather_adaptive.  Every listed primitive carries a MASK of the species still sampling there; in round 0 every
+ *          primitive of the range is listed with all species.  After a round, at its K, every species in a listed
+ *          primitive's mask is tested by converged(relTargets[s], absTargets[s]) on its own two sums:
+ *            - one that converges gets flux, stdErr and samplesUsed at that K and leaves the mask; its sums are never
+ *              touched again;
+ *            - a primitive leaves the list when its mask is empty;
+ *            - at K == maxSamples every species still in a mask gets its outputs, and info->unconverged[s] counts those of
+ *              species s that fail the test there.
+ *          In a later round a primitive's paths start with alive = its mask.  A species outside the mask is dead from the
+ *          start: it is weighed nowhere, and it does not keep the shared path going.
+ * Result   flux, stdErr, samplesUsed: [s * primCount + (i - primFirst)].  Row s of each has the BITS of
+ *          vr_gather_angular_adaptive (vr_gather_adaptive where the species has no law) called with specs[s], laws[s],
+ *          relTargets[s], absTargets[s] and the same minSamples / maxSamples — for every s and numSpecies, every order of
+ *          the species, every choice of the OTHER species and their targets, every split of the primitive range over calls
+ *          and every launch shape.  That identity is the specification.  It holds because up to the vertex where species s
+ *          dies the shared path is its own path (vr_gather_species), and its sums take exactly the chunks its own call
+ *          would have run: it is in the mask in exactly the rounds its own call lists the primitive.
+ * info     rounds: the rounds run, the maximum of the species' own calls' rounds.  unconverged[s], totalSamples[s]: what
+ *          the call of species s alone reports.  walkedSamples: the sum over the primitives of the largest samplesUsed
+ *          among their species — the samples actually walked; at most the sum of totalSamples, and below it wherever two
+ *          species of a primitive share a round.
+ * numSpecies == 1 is vr_gather_angular_adaptive itself.
+ * Refused, outputs untouched and the context usable, message in vr_last_error — every message about one species names it:
+ *   VR_E_INVALID  what vr_gather_species refuses at samples = maxSamples; what vr_gather_adaptive refuses of minSamples and
+ *                 maxSamples; relTargets or absTargets NULL; a target of a species that is negative or NaN ("... species 2:
+ *                 ..."); flux or info NULL.  stdErr and samplesUsed may be NULL.  primCount == 0 is VR_OK after the checks.
+ *   VR_E_STATE    as vr_gather_flux_device.
+ * Streams and "changes nothing of a finished apply": as vr_gather_adaptive_device.  The host waits once per round, for five
+ * words: the next list's length and, per species, the primitives it still samples in.  Work buffers: numSpecies x primCount
+ * of each sum, two lists with their masks, a few words per round; they grow on demand.
+ * flux, stdErr: numSpecies x primCount floats, samplesUsed: numSpecies x primCount uint32 — DEVICE memory in the _device
+ * form (as specs[s].reflectivity), HOST memory in the other; relTargets, absTargets, info: HOST */
+typedef struct vr_gather_species_adaptive_info {
+  uint32_t rounds;
+  uint32_t unconverged[VR_GATHER_MAX_SPECIES];
+  uint64_t totalSamples[VR_GATHER_MAX_SPECIES];
+  uint64_t walkedSamples;
+} vr_gather_species_adaptive_info;
+int vr_gather_species_adaptive_device(vr_context *ctx, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t numSpecies,
+                                      uint32_t primFirst, uint32_t primCount, uint32_t minSamples, uint32_t maxSamples,
+                                      const float *relTargets, const float *absTargets, float *flux, float *stdErr,
+                                      uint32_t *samplesUsed, vr_gather_species_adaptive_info *info, void *stream);
+/* the same from and to host arrays */
+int vr_gather_species_adaptive(vr_context *ctx, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t numSpecies,
+                               uint32_t primFirst, uint32_t primCount, uint32_t minSamples, uint32_t maxSamples,
+                               const float *relTargets, const float *absTargets, float *flux, float *stdErr, uint32_t *samplesUsed,
+                               vr_gather_species_adaptive_info *info);
 /* ---- radiosity solve (not in the reference): the steady-state flux of a diffusely re-emitting species ------------------
  * vr_gather_flux with an emission table is one radiosity iteration, and its walks are a constant of the scene.  These
  * calls record them once — a link table — and iterate over the table on the device without walking again.

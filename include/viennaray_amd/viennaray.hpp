@@ -1592,6 +1592,56 @@ public:
     return reported(vr_gather_species_sums(ctx_, specs.data(), laws.data(), (uint32_t)species.size(), 0u, n, chunkFirst, chunks, budget,
                                            sum.data(), sumSq.data()));
   }
+  /// what an adaptive species gather returns: flux, stdErr and samplesUsed row-major [species][primitive], and the call's
+  /// info; empty vectors if it was refused
+  struct GatherSpeciesAdaptiveResult {
+    std::vector<NumericType> flux, stdErr;
+    std::vector<unsigned> samplesUsed;
+    vr_gather_species_adaptive_info info{};
+  };
+  /// gatherSpecies to a target error per species (vr_gather_species_adaptive, whose header comment has the definition):
+  /// row s is gatherAngularAdaptive of species s under relTargets[s] / absTargets[s] word for word, along one set of
+  /// traced paths.  relTargets: one value per species; absTargets: one per species, or empty (all 0)
+  [[nodiscard]] GatherSpeciesAdaptiveResult gatherSpeciesAdaptive(const std::vector<float> &relTargets,
+                                                                  const std::vector<GatherSpecies> &species,
+                                                                  GatherReflection reflection = GatherReflection::SPECULAR,
+                                                                  unsigned maxBounces = 64, unsigned minSamples = 64,
+                                                                  unsigned maxSamples = 4096, std::vector<float> absTargets = {}) {
+    if (!ctx_)
+      return {};
+    if (absTargets.empty())
+      absTargets.assign(species.size(), 0.f);
+    if (relTargets.size() != species.size() || absTargets.size() != species.size()) {
+      std::cerr << "viennaray_amd: gatherSpeciesAdaptive: " << species.size() << " species, " << relTargets.size()
+                << " relative and " << absTargets.size() << " absolute targets\n";
+      return {};
+    }
+    std::vector<vr_gather_spec> specs;
+    std::vector<vr_gather_laws> laws;
+    speciesPods(species, reflection, maxBounces, specs, laws);
+    const size_t n = species.size() * (size_t)vr_num_primitives(ctx_);
+    std::vector<float> flux(n), err(n);
+    GatherSpeciesAdaptiveResult r;
+    r.samplesUsed.resize(n);
+    if (!reported(vr_gather_species_adaptive(ctx_, specs.data(), laws.data(), (uint32_t)species.size(), 0u, vr_num_primitives(ctx_),
+                                             minSamples, maxSamples, relTargets.data(), absTargets.data(), flux.data(), err.data(),
+                                             reinterpret_cast<uint32_t *>(r.samplesUsed.data()), &r.info)))
+      return {};
+    r.flux.assign(flux.begin(), flux.end());
+    r.stdErr.assign(err.begin(), err.end());
+    return r;
+  }
+  /// specs[s].reflectivity and the outputs (dFlux: numSpecies x primCount floats; dStdErr, dSamplesUsed: nullptr or as many
+  /// entries) are DEVICE memory; the laws (nullptr: none), the targets (numSpecies floats each) and info are the host's;
+  /// gatherAdaptiveDevice's stream rules.  false if it was refused.
+  bool gatherSpeciesAdaptiveDevice(const std::vector<vr_gather_spec> &specs, const vr_gather_laws *laws, unsigned primFirst,
+                                   unsigned primCount, unsigned minSamples, unsigned maxSamples, const float *relTargets,
+                                   const float *absTargets, float *dFlux, float *dStdErr, uint32_t *dSamplesUsed,
+                                   vr_gather_species_adaptive_info &info, void *stream = nullptr) {
+    return ctx_ && reported(vr_gather_species_adaptive_device(ctx_, specs.data(), laws, (uint32_t)specs.size(), primFirst, primCount,
+                                                              minSamples, maxSamples, relTargets, absTargets, dFlux, dStdErr,
+                                                              dSamplesUsed, &info, stream));
+  }
   /// the specs and laws of a list of species (host tables; the species must outlive them)
   static void speciesPods(const std::vector<GatherSpecies> &species, GatherReflection reflection, unsigned maxBounces,
                           std::vector<vr_gather_spec> &specs, std::vector<vr_gather_laws> &laws) {

@@ -74,6 +74,16 @@ class GatherAdaptiveInfoPOD(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class GatherSpeciesAdaptiveInfoPOD(C.Structure):
+    """vr_gather_species_adaptive_info (include/viennaray_amd.h)"""
+    _fields_ = [("rounds", C.c_uint32), ("unconverged", C.c_uint32 * VR_GATHER_MAX_SPECIES),
+                ("totalSamples", C.c_uint64 * VR_GATHER_MAX_SPECIES), ("walkedSamples", C.c_uint64)]
+
+    def as_dict(self, numSpecies=VR_GATHER_MAX_SPECIES):
+        return {"rounds": int(self.rounds), "unconverged": [int(v) for v in self.unconverged[:numSpecies]],
+                "totalSamples": [int(v) for v in self.totalSamples[:numSpecies]], "walkedSamples": int(self.walkedSamples)}
+
+
 # every symbol include/viennaray_amd.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -189,6 +199,12 @@ SIGNATURES = {
     "vr_gather_species_sums": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64)]),
+    "vr_gather_species_adaptive_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32,
+                                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, _vp, _vp, _vp,
+                                                    C.POINTER(GatherSpeciesAdaptiveInfoPOD), _vp]),
+    "vr_gather_species_adaptive": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, _fp, _fp, _u32p,
+                                             C.POINTER(GatherSpeciesAdaptiveInfoPOD)]),
     "vr_radiosity_link_bytes": (C.c_uint64, [_vp, C.c_uint32]),
     "vr_radiosity_links_device": (C.c_int, [_vp, C.c_uint32, C.c_float, _vp]),
     "vr_radiosity_resident": (C.c_int, [_vp, C.c_uint32, C.c_float]),

@@ -389,7 +389,8 @@ struct vr_context {
   DevBuf<uint32_t> dPathWord;
   // vr_gather_sums* / vr_gather_adaptive*: the int64 sums of the squared weights beside dGatherAcc, the two primitive
   // lists a round reads and writes, the decide kernel's block counts with the word that comes back behind them, and the
-  // host forms' staging of stdErr and samplesUsed.  Grown behind host_waits only
+  // host forms' staging of stdErr and samplesUsed.  Grown behind host_waits only.  vr_gather_species_adaptive* keeps
+  // numSpecies of each sum and output, a list's masks behind the list (2 primCount words) and five words per round
   DevBuf<unsigned long long> dGatherAccSq;
   DevBuf<uint32_t> dGatherListA, dGatherListB, dGatherWords, dGatherUsed;
   DevBuf<float> dGatherErr;

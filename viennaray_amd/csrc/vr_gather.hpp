@@ -442,6 +442,24 @@ VR_GATHER_FN unsigned gather_species_step(float (&T)[NS], unsigned alive, const 
   return gather_species_reflect<NS>(T, alive, R, MR, mu);
 }
 
+// ---- gatherSpeciesAdaptive (vr_gather_species_adaptive*): every species of a primitive to its own target --------------
+// One round's verdict of one primitive (gather_species_decide_kernel; tests/aux/gather_species_adaptive.cpp).  mask: the
+// species still sampling there; S1[s], S2[s]: the two sums of species s after K samples — read for the species in the mask
+// alone: one outside it stopped at an older K, its sums are not sums over K.  Each species in the mask is tested by
+// gather_converged on its own sums under its own targets, which is the test its own adaptive call makes at this K.
+// Returns the species that failed: the next round's mask, or with `last` (K == maxSamples) the unconverged.  writes: the
+// species whose outputs are written at this K — those that converged, with `last` all of the mask
+VR_GATHER_FN unsigned gather_species_decide(const int64_t *S1, const int64_t *S2, uint32_t numSpecies, uint32_t K, const float *rel,
+                                            const float *abs, unsigned mask, bool last, unsigned &writes) {
+  unsigned failed = 0u;
+  VR_GATHER_UNROLL
+  for (uint32_t s = 0; s < GATHER_MAX_SPECIES; ++s)
+    if (s < numSpecies && ((mask >> s) & 1u) && !gather_converged(S1[s], S2[s], K, rel[s], abs[s]))
+      failed |= 1u << s;
+  writes = last ? mask : mask & ~failed;
+  return failed;
+}
+
 // g_D(n) (a host function; the kernel takes the float): g_3 = (n + 1) / 2, g_2 = 2 / C_n with
 // C_n = sqrt(pi) Gamma((n + 1) / 2) / Gamma(n / 2 + 1) — the weight of a sample that reaches the source is the ratio of
 // the source's normalised law (n + 1) / (2 pi) c^n (3-D), c^n / C_n (2-D) and the receiver's cosine law c / pi, c / 2 for

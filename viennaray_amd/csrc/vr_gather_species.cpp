@@ -5,6 +5,8 @@
 // name that carries the species.  One species IS the angular call and goes to its implementation.  Like the other gather
 // calls these prepare nothing and touch none of prepared / launched / haveResult; the work buffers are the gather's
 // (sums, laws, reflectivities in leaf order, staging), grown to numSpecies of each.
+// vr_gather_species_adaptive* are the rounds of vr_gather_adaptive.cpp over those sums, with a mask of species per listed
+// primitive: a species that has met its own target stops there and no longer keeps the shared path alive.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -21,15 +23,21 @@ constexpr size_t LAW_WORDS = 3 * GATHER_LAW_MAX; // a species' three laws on the
 
 static std::string species_name(const char *api, uint32_t s) { return std::string(api) + ": species " + std::to_string(s); }
 
-// what every form refuses before it touches anything; samples: the call's, or the budget; out: a non-null output.
-// sets[s]: the laws of species s, normalised
-static int species_refusal(vr_context *c, const char *api, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t S,
-                           uint32_t primFirst, uint32_t primCount, uint32_t samples, const void *out, GatherLawSet *sets) {
+// there are specs to read, and as many as a call takes
+static int species_count_refusal(vr_context *c, const char *api, const vr_gather_spec *specs, uint32_t S) {
   const std::string name = api;
   if (!specs)
     return fail(c, VR_E_INVALID, (name + ": specs must not be null").c_str());
   if (S == 0 || S > VR_GATHER_MAX_SPECIES)
     return fail(c, VR_E_INVALID, (name + ": numSpecies must be 1 .. VR_GATHER_MAX_SPECIES (4)").c_str());
+  return VR_OK;
+}
+
+// what every form refuses before it touches anything; samples: the call's, or the budget; out: a non-null output.
+// sets[s]: the laws of species s, normalised
+static int species_refusal(vr_context *c, const char *api, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t S,
+                           uint32_t primFirst, uint32_t primCount, uint32_t samples, const void *out, GatherLawSet *sets) {
+  VR_TRY(species_count_refusal(c, api, specs, S));
   for (uint32_t s = 0; s < S; ++s) {
     const vr_gather_spec &sp = specs[s];
     const std::string who = species_name(api, s);
@@ -174,6 +182,139 @@ static int species_sums_refusal(vr_context *c, const char *api, const vr_gather_
   return VR_OK;
 }
 
+// ---- vr_gather_species_adaptive*: every species of a primitive to its own target, along one set of paths ---------------
+// what both forms refuse before they touch anything: vr_gather_adaptive's checks, the targets per species, then what
+// vr_gather_species refuses at samples = maxSamples
+static int species_adaptive_refusal(vr_context *c, const char *api, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t S,
+                                    uint32_t primFirst, uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, const float *rel,
+                                    const float *abs, const void *flux, const void *info, GatherLawSet *sets) {
+  const std::string name = api;
+  if (minSamples == 0 || minSamples % GATHER_CHUNK)
+    return fail(c, VR_E_INVALID, (name + ": minSamples must be a positive multiple of 64").c_str());
+  const uint32_t ratio = maxSamples / minSamples;
+  if (maxSamples % minSamples || ratio == 0 || (ratio & (ratio - 1u)))
+    return fail(c, VR_E_INVALID, (name + ": maxSamples must be minSamples times a power of two").c_str());
+  VR_TRY(species_count_refusal(c, api, specs, S)); // (the targets are numSpecies floats each)
+  if (!rel || !abs)
+    return fail(c, VR_E_INVALID, (name + ": relTargets and absTargets must not be null (numSpecies floats each)").c_str());
+  for (uint32_t s = 0; s < S; ++s)
+    if (!(rel[s] >= 0.f) || !(abs[s] >= 0.f))
+      return fail(c, VR_E_INVALID, (species_name(api, s) + ": the targets must not be negative or NaN").c_str());
+  if (!info)
+    return fail(c, VR_E_INVALID, (name + ": info must not be null").c_str());
+  return species_refusal(c, api, specs, laws, S, primFirst, primCount, maxSamples, flux, sets);
+}
+
+// one species: the angular adaptive call itself, its info in the species call's form
+static void species_info_of_one(const vr_gather_adaptive_info &one, vr_gather_species_adaptive_info &info) {
+  info = vr_gather_species_adaptive_info{};
+  info.rounds = one.rounds;
+  info.unconverged[0] = one.unconverged;
+  info.totalSamples[0] = one.totalSamples;
+  info.walkedSamples = one.totalSamples;
+}
+
+// The rounds (vr_gather_adaptive.cpp: adaptive_on_device, for S >= 2 species).  Every pointer is device memory (stdErr,
+// samplesUsed: or nullptr), S x primCount each, the arguments have been accepted.  Work buffers: the S x primCount sums and
+// sums of squares, two lists with their masks behind them (2 primCount words each), the decide kernel's block counts and
+// five words per round.  The host waits once per round, for those five words: the next list's length and, per species,
+// the entries it is still sampling in — from which totalSamples and rounds of every species follow without a pass over
+// the outputs
+static int species_adaptive_on_device(vr_context *c, const vr_gather_spec *specs, const GatherLawSet *sets, uint32_t S, uint32_t primFirst,
+                                      uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, const float *rel, const float *abs,
+                                      float *flux, float *stdErr, uint32_t *samplesUsed, vr_gather_species_adaptive_info &info) {
+  constexpr uint32_t ROUND_WORDS = 1u + VR_GATHER_MAX_SPECIES;
+  bool waited = false;
+  const uint32_t blocks = (uint32_t)(((uint64_t)primCount + GATHER_DECIDE_BLOCK - 1u) / GATHER_DECIDE_BLOCK);
+  uint32_t rounds = 1u;
+  for (uint32_t k = minSamples; k < maxSamples; k *= 2u)
+    ++rounds;
+  VR_TRY(map_grow(c, c->dGatherAcc, (size_t)S * primCount, waited));
+  VR_TRY(map_grow(c, c->dGatherAccSq, (size_t)S * primCount, waited));
+  VR_TRY(map_grow(c, c->dGatherListA, (size_t)2 * primCount, waited));
+  VR_TRY(map_grow(c, c->dGatherListB, (size_t)2 * primCount, waited));
+  VR_TRY(map_grow(c, c->dGatherWords, (size_t)blocks + (size_t)rounds * ROUND_WORDS, waited));
+  TraceParams p;
+  GatherSpeciesArgs sa;
+  VR_TRY(species_args(c, waited, p, sa, specs, sets, S, primFirst, primCount, maxSamples));
+  GatherArgs &a = sa.a;
+  a.stat = 1u;
+  a.acc = c->dGatherAcc.p;
+  a.accSq = c->dGatherAccSq.p;
+  VR_HIP(c, hipMemsetAsync(a.acc, 0, (size_t)S * primCount * 8, c->stream));
+  VR_HIP(c, hipMemsetAsync(a.accSq, 0, (size_t)S * primCount * 8, c->stream));
+  VR_HIP(c, hipMemsetAsync(c->dGatherWords.p + blocks, 0, (size_t)rounds * ROUND_WORDS * 4, c->stream));
+  GatherSpeciesDecideArgs d{};
+  d.acc = a.acc;
+  d.accSq = a.accSq;
+  if (!a.leafOfOrig) { // the whole scene: a list entry is a leaf position, the sums' index the record's original id
+    d.origWords = reinterpret_cast<const uint32_t *>(p.prims);
+    d.origStride = c->geo.geo == 0 ? 8u : 16u;
+    d.origOffset = c->geo.geo == 0 ? 7u : 3u;
+  }
+  d.blockCounts = c->dGatherWords.p;
+  d.flux = flux;
+  d.stdErr = stdErr;
+  d.samplesUsed = samplesUsed;
+  d.primCount = primCount;
+  d.num = S;
+  for (uint32_t s = 0; s < S; ++s)
+    d.rel[s] = rel[s], d.abs[s] = abs[s];
+  const unsigned slabs = (unsigned)std::min<size_t>(c->walkStackWaves, 0xFFFFFFFFu);
+  const uint32_t c0 = minSamples / GATHER_CHUNK;
+  const uint32_t *list = nullptr, *masks = nullptr;
+  uint32_t listCount = primCount;
+  uint32_t sampling[VR_GATHER_MAX_SPECIES] = {0u, 0u, 0u, 0u}; // entries species s samples in this round
+  for (uint32_t s = 0; s < S; ++s)
+    sampling[s] = primCount;
+  info = vr_gather_species_adaptive_info{};
+  for (uint32_t r = 0;; ++r) {
+    const uint32_t chunkFirst = r == 0 ? 0u : c0 << (r - 1u), chunks = r == 0 ? c0 : c0 << (r - 1u);
+    const uint32_t K = (chunkFirst + chunks) * GATHER_CHUNK; // (<= maxSamples <= 2^22: the entry points' checks)
+    a.chunkFirst = chunkFirst;
+    a.chunks = chunks;
+    a.samples = K;
+    a.list = list;
+    a.listCount = list ? listCount : 0u;
+    sa.listMask = masks;
+    a.groups = (uint32_t)(((uint64_t)listCount + 63) / 64);
+    a.subs = 1u;
+    gather_cut_chunks(a, slabs); // per launch: the late rounds have few primitives
+    VR_HIP(c, launch_gather_species(p, c->geo.geo, c->geo.D, sa, slabs, c->stream));
+    const uint64_t roundSamples = (uint64_t)chunks * GATHER_CHUNK;
+    info.walkedSamples += (uint64_t)listCount * roundSamples;
+    for (uint32_t s = 0; s < S; ++s)
+      info.totalSamples[s] += (uint64_t)sampling[s] * roundSamples;
+    ++info.rounds; // (the list is not empty: one species at least samples in this round)
+    uint32_t *const next = (r & 1u) ? c->dGatherListB.p : c->dGatherListA.p;
+    d.list = list;
+    d.masks = masks;
+    d.count = listCount;
+    d.samples = K;
+    d.last = K == maxSamples ? 1u : 0u;
+    d.next = next;
+    d.nextMasks = next + primCount;
+    d.words = c->dGatherWords.p + blocks + (size_t)r * ROUND_WORDS;
+    VR_HIP(c, launch_gather_species_decide(d, c->stream));
+    uint32_t words[ROUND_WORDS];
+    VR_HIP(c, hipMemcpyAsync(words, d.words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
+    VR_TRY(host_waits(c));
+    if (d.last) {
+      for (uint32_t s = 0; s < S; ++s)
+        info.unconverged[s] = words[1u + s];
+      break;
+    }
+    if (words[0] == 0u)
+      break;
+    list = next;
+    masks = next + primCount;
+    listCount = words[0];
+    for (uint32_t s = 0; s < S; ++s)
+      sampling[s] = words[1u + s];
+  }
+  return VR_OK;
+}
+
 } // namespace vr
 
 using namespace vr;
@@ -275,6 +416,81 @@ int vr_gather_species_sums(vr_context *c, const vr_gather_spec *specs, const vr_
   VR_TRY(species_sums_on_device(c, specs, sets, S, primFirst, primCount, chunkFirst, chunks, budget, c->dGatherAcc.p, c->dGatherAccSq.p));
   VR_HIP(c, hipMemcpyAsync(sum, c->dGatherAcc.p, (size_t)S * primCount * 8, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipMemcpyAsync(sumSq, c->dGatherAccSq.p, (size_t)S * primCount * 8, hipMemcpyDeviceToHost, c->stream));
+  VR_HIP(c, hipStreamSynchronize(c->stream));
+  return VR_OK;
+}
+
+int vr_gather_species_adaptive_device(vr_context *c, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t S,
+                                      uint32_t primFirst, uint32_t primCount, uint32_t minSamples, uint32_t maxSamples,
+                                      const float *relTargets, const float *absTargets, float *flux, float *stdErr,
+                                      uint32_t *samplesUsed, vr_gather_species_adaptive_info *info, void *stream) {
+  if (!c)
+    return VR_E_INVALID;
+  const char *api = "vr_gather_species_adaptive_device";
+  GatherLawSet sets[VR_GATHER_MAX_SPECIES];
+  VR_TRY(species_adaptive_refusal(c, api, specs, laws, S, primFirst, primCount, minSamples, maxSamples, relTargets, absTargets, flux, info,
+                                  sets));
+  if (S == 1u) { // (one species: the angular adaptive call itself)
+    vr_gather_adaptive_info one{};
+    VR_TRY(adaptive_call_device(c, api, specs, laws, primFirst, primCount, minSamples, maxSamples, relTargets[0], absTargets[0], flux,
+                                stdErr, samplesUsed, &one, stream));
+    species_info_of_one(one, *info);
+    return VR_OK;
+  }
+  VR_TRY(resident_scene_refusal(c, api, "gather from"));
+  const float *rho[VR_GATHER_MAX_SPECIES] = {nullptr, nullptr, nullptr, nullptr};
+  for (uint32_t s = 0; s < S; ++s)
+    rho[s] = specs[s].reflectivity;
+  VR_TRY(hand_over(c, {rho[0], rho[1], rho[2], rho[3], flux, stdErr, samplesUsed},
+                   (std::string(api) +
+                    ": the species' reflectivity tables, flux, stdErr and samplesUsed must be device memory of the context's device")
+                       .c_str(),
+                   stream));
+  bool waited = false;
+  VR_TRY(species_tables(c, api, rho, S, waited));
+  *info = vr_gather_species_adaptive_info{};
+  if (primCount == 0)
+    return caller_waits(c, stream);
+  VR_TRY(species_adaptive_on_device(c, specs, sets, S, primFirst, primCount, minSamples, maxSamples, relTargets, absTargets, flux, stdErr,
+                                    samplesUsed, *info));
+  return caller_waits(c, stream);
+}
+
+int vr_gather_species_adaptive(vr_context *c, const vr_gather_spec *specs, const vr_gather_laws *laws, uint32_t S, uint32_t primFirst,
+                               uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, const float *relTargets,
+                               const float *absTargets, float *flux, float *stdErr, uint32_t *samplesUsed,
+                               vr_gather_species_adaptive_info *info) {
+  if (!c)
+    return VR_E_INVALID;
+  const char *api = "vr_gather_species_adaptive";
+  GatherLawSet sets[VR_GATHER_MAX_SPECIES];
+  VR_TRY(species_adaptive_refusal(c, api, specs, laws, S, primFirst, primCount, minSamples, maxSamples, relTargets, absTargets, flux, info,
+                                  sets));
+  if (S == 1u) {
+    vr_gather_adaptive_info one{};
+    VR_TRY(adaptive_call_host(c, api, specs, laws, primFirst, primCount, minSamples, maxSamples, relTargets[0], absTargets[0], flux, stdErr,
+                              samplesUsed, &one));
+    species_info_of_one(one, *info);
+    return VR_OK;
+  }
+  VR_TRY(resident_scene_refusal(c, api, "gather from"));
+  VR_HIP(c, hipSetDevice(c->device));
+  bool waited = false;
+  VR_TRY(species_upload(c, api, specs, S, waited));
+  *info = vr_gather_species_adaptive_info{};
+  if (primCount == 0)
+    return VR_OK;
+  const size_t n = (size_t)S * primCount;
+  VR_TRY(map_grow(c, c->dGatherOut, n, waited));
+  VR_TRY(map_grow(c, c->dGatherErr, n, waited));
+  VR_TRY(map_grow(c, c->dGatherUsed, n, waited));
+  VR_TRY(species_adaptive_on_device(c, specs, sets, S, primFirst, primCount, minSamples, maxSamples, relTargets, absTargets,
+                                    c->dGatherOut.p, c->dGatherErr.p, c->dGatherUsed.p, *info));
+  VR_HIP(c, hipMemcpyAsync(flux, c->dGatherOut.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (stdErr)
+    VR_HIP(c, hipMemcpyAsync(stdErr, c->dGatherErr.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (samplesUsed)
+    VR_HIP(c, hipMemcpyAsync(samplesUsed, c->dGatherUsed.p, n * 4, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   return VR_OK;
 }

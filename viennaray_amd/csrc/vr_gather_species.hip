@@ -12,6 +12,13 @@
 //                                  (gather_species_absorb, gather_species_reflect); the path goes on while one is alive.
 //                                  At the tail every living species is weighed by its own laws (gather_path_weight_laws)
 //                                  and summed into its own exact int64 sum: row s has the bits of the single-species call.
+//                                  With STAT and a list (a later round of vr_gather_species_adaptive_device) the lane's
+//                                  primitive is a list entry and its paths start with the species of the entry's mask
+//                                  alive: one that has met its target is dead from the start — it adds nothing to its
+//                                  sums and does not keep the shared path going.
+//   gather_species_decide_kernel   one round's verdict of that call: per entry the species of its mask tested each under
+//                                  its own targets (vr_gather.hpp: gather_species_decide), the outputs of those that
+//                                  leave, the entries with a species left compacted in order with their new masks.
 //
 // Registers.  The triangle instantiations of the parent sit at 255 VGPRs, the 2-D disks at 166 of 168: NS throughputs and
 // NS (2 NS with STAT) int64 sums per lane do not fit beside the walk.  They live in lane-private LDS slots instead —
@@ -103,8 +110,17 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_species_kernel(const TracePar
   const u64 perGroup = (u64)a.chunks * a.subs, items = (u64)a.groups * perGroup;
   for (u64 it = wave; it < items; it += waves) {
     const unsigned sub = (unsigned)(it % a.subs), chunk = (STAT ? a.chunkFirst : 0u) + (unsigned)((it / a.subs) % a.chunks);
-    const u64 t = (it / perGroup) * 64u + lane; // index into the range, or (whole scene) the leaf position
-    const bool valid = t < (u64)a.primCount;
+    u64 t = (it / perGroup) * 64u + lane; // index into the range, or (whole scene) the leaf position
+    bool valid = t < (u64)a.primCount;
+    unsigned startAlive = allAlive; // the species the lane's paths start with
+    if constexpr (STAT) {
+      if (a.list) { // (wave-uniform; a later round of the adaptive call) the lane's primitive is the list's — entries <
+                    // a.primCount — and its paths start with the species still sampling there (gather_species_decide_kernel)
+        valid = t < (u64)a.listCount;
+        startAlive = valid ? sa.listMask[t] & allAlive : 0u;
+        t = valid ? a.list[t] : 0u;
+      }
+    }
     // ---- the lane's primitive ----
     GVec o = GVec{0.f, 0.f, 0.f}, m = GVec{0.f, 0.f, 1.f};
     unsigned orig = 0u;
@@ -141,7 +157,7 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_species_kernel(const TracePar
       unsigned hitPos = 0u;
       float cEnd = c;           // u . omega of the direction the path goes along
       unsigned bounces = 0u;
-      unsigned alive = allAlive; // the species that still follow the path
+      unsigned alive = startAlive; // the species that still follow the path
 #pragma unroll
       for (int s = 0; s < NS; ++s)
         tL[s * VR_BLOCK] = 1.f;
@@ -255,6 +271,87 @@ __global__ __launch_bounds__(VR_BLOCK) void gather_species_kernel(const TracePar
   }
 }
 
+// One round's verdict of vr_gather_species_adaptive_device: gather_decide_kernel's shape — one thread per entry of the
+// current list, a block per GATHER_DECIDE_BLOCK entries, the next list in the order of the current one by wave ballots and
+// a block prefix, no atomic append — with a mask of species per entry.  Only the species of the entry's mask are loaded
+// and tested: one outside it stopped at an older K.  WRITE false: the block's count alone, for a list of more than one
+// block; WRITE true: the outputs, the next list and its masks, the list's length, and per species the entries it is left
+// in (one atomic per wave and species: a count, not a place)
+template <bool WRITE> __global__ __launch_bounds__(GATHER_DECIDE_BLOCK) void gather_species_decide_kernel(const GatherSpeciesDecideArgs d) {
+  __shared__ unsigned waveCount[GATHER_DECIDE_BLOCK / 64];
+  __shared__ unsigned red[GATHER_DECIDE_BLOCK];
+  const unsigned e = blockIdx.x * GATHER_DECIDE_BLOCK + threadIdx.x; // (count <= 2^32 - 1: a primitive range)
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const bool have = e < d.count;
+  unsigned entry = 0u, idx = 0u, mask = 0u, failed = 0u, writes = 0u;
+  int64_t S1[GATHER_SPECIES_MAX] = {0, 0, 0, 0}, S2[GATHER_SPECIES_MAX] = {0, 0, 0, 0};
+  if (have) {
+    entry = d.list ? d.list[e] : e;
+    idx = d.origWords ? d.origWords[(size_t)entry * d.origStride + d.origOffset] : entry; // < primCount
+    mask = (d.masks ? d.masks[e] : ~0u) & ((1u << d.num) - 1u);
+#pragma unroll
+    for (unsigned s = 0; s < GATHER_SPECIES_MAX; ++s)
+      if (s < d.num && ((mask >> s) & 1u)) { // (s < num, idx < primCount: inside the num x primCount sums)
+        S1[s] = (int64_t)d.acc[(size_t)s * d.primCount + idx];
+        S2[s] = (int64_t)d.accSq[(size_t)s * d.primCount + idx];
+      }
+    failed = gather_species_decide(S1, S2, d.num, d.samples, d.rel, d.abs, mask, d.last != 0u, writes);
+  }
+  const bool keep = failed != 0u;
+  const unsigned long long kept = ballot64(keep);
+  if (lane == 0u)
+    waveCount[wave] = (unsigned)__popcll(kept);
+  if constexpr (WRITE) { // the kept entries of the blocks before this one
+    unsigned part = 0u;
+    for (unsigned b = threadIdx.x; b < blockIdx.x; b += GATHER_DECIDE_BLOCK)
+      part += d.blockCounts[b];
+    red[threadIdx.x] = part;
+  }
+  __syncthreads();
+  unsigned before = 0u, total = 0u;
+  for (unsigned w = 0; w < GATHER_DECIDE_BLOCK / 64; ++w) {
+    const unsigned n = waveCount[w];
+    before += w < wave ? n : 0u;
+    total += n;
+  }
+  if constexpr (!WRITE) {
+    if (threadIdx.x == 0u)
+      d.blockCounts[blockIdx.x] = total;
+  } else {
+    for (unsigned s = GATHER_DECIDE_BLOCK / 2; s > 0u; s >>= 1) {
+      if (threadIdx.x < s)
+        red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    const unsigned base = red[0];
+#pragma unroll
+    for (unsigned s = 0; s < GATHER_SPECIES_MAX; ++s) {
+      const unsigned long long left = ballot64(((failed >> s) & 1u) != 0u); // (every lane of the wave is here)
+      if (lane == 0u && left)
+        atomicAdd(d.words + 1u + s, (unsigned)__popcll(left));
+    }
+    if (have) {
+#pragma unroll
+      for (unsigned s = 0; s < GATHER_SPECIES_MAX; ++s)
+        if ((writes >> s) & 1u) { // (writes is a subset of the mask: s < num)
+          const size_t o = (size_t)s * d.primCount + idx;
+          d.flux[o] = gather_result(S1[s], d.samples);
+          if (d.stdErr)
+            d.stdErr[o] = (float)sqrt(gather_stderr2(S1[s], S2[s], d.samples));
+          if (d.samplesUsed)
+            d.samplesUsed[o] = d.samples;
+        }
+      if (keep) { // (base + before + the lanes before < the kept entries of the whole list <= count: inside next / nextMasks)
+        const unsigned at = base + before + (unsigned)__popcll(kept & ((1ull << lane) - 1ull));
+        d.next[at] = entry;
+        d.nextMasks[at] = failed;
+      }
+    }
+    if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 0u)
+      d.words[0] = base + total;
+  }
+}
+
 template <int NS, int STAT>
 static void species_launch(int geo, int D, dim3 g, dim3 b, hipStream_t st, const TraceParams &p, const GatherSpeciesArgs &sa) {
   if (geo == 0) {
@@ -276,8 +373,12 @@ hipError_t launch_gather_species(const TraceParams &p, int geo, int D, const Gat
   // reflectivities, counts and tables the look-ups may index
   if (a.subs == 0 || a.subs > GATHER_MAX_SUBS || (a.subs & (a.subs - 1u)))
     return hipErrorInvalidValue;
-  if (sa.num < 2u || sa.num > GATHER_SPECIES_MAX || !a.acc || a.paths != 1u || a.links || a.emission || a.list || a.laws ||
+  if (sa.num < 2u || sa.num > GATHER_SPECIES_MAX || !a.acc || a.paths != 1u || a.links || a.emission || a.laws ||
       a.mode != GATHER_NORMAL || a.reflection > GATHER_REFLECT_DIFFUSE || a.maxBounces > GATHER_MAX_BOUNCES)
+    return hipErrorInvalidValue;
+  // a list goes with the sums alone, has its masks beside it and is no longer than the range (its entries index the range)
+  if (a.list ? !a.stat || !sa.listMask || a.listCount > a.primCount || a.groups != (uint32_t)(((unsigned long long)a.listCount + 63u) / 64u)
+             : sa.listMask != nullptr)
     return hipErrorInvalidValue;
   if (a.stat && (!a.accSq || (unsigned long long)(a.chunkFirst + (unsigned long long)a.chunks) * GATHER_CHUNK > a.samples))
     return hipErrorInvalidValue;
@@ -304,6 +405,18 @@ hipError_t launch_gather_species(const TraceParams &p, int geo, int D, const Gat
     else
       species_launch<4, 0>(geo, D, g, b, st, p, sa);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_species_decide(const GatherSpeciesDecideArgs &d, hipStream_t st) {
+  if (d.count == 0 || d.count > d.primCount || d.num < 2u || d.num > GATHER_SPECIES_MAX || !d.acc || !d.accSq || !d.next ||
+      !d.nextMasks || !d.blockCounts || !d.words || !d.flux || d.samples < 2u || (d.masks && !d.list))
+    return hipErrorInvalidValue;
+  // one launch where the list fits a block, otherwise the blocks' counts first
+  const unsigned blocks = (unsigned)(((unsigned long long)d.count + GATHER_DECIDE_BLOCK - 1u) / GATHER_DECIDE_BLOCK);
+  if (blocks > 1u)
+    hipLaunchKernelGGL((gather_species_decide_kernel<false>), dim3(blocks), dim3(GATHER_DECIDE_BLOCK), 0, st, d);
+  hipLaunchKernelGGL((gather_species_decide_kernel<true>), dim3(blocks), dim3(GATHER_DECIDE_BLOCK), 0, st, d);
   return hipGetLastError();
 }
 

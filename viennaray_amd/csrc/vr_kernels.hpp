@@ -223,10 +223,12 @@ hipError_t launch_debug_gather_samples(const TraceParams &p, int geo, int D, con
                                        float *origin3, float *normal3, float *directions3, hipStream_t st);
 // several species along one set of traced paths (vr_gather_species.hip: gather_species_kernel; vr_gather_species.cpp).
 // a: what the species share — the range, samples, seed, groups / chunks / subs, maxBoundaryHits, wmax, reflection,
-// maxBounces, stat and chunkFirst of a path gather (no list, no laws, no rho: those fields are not read); a.acc (and
+// maxBounces, stat and chunkFirst of a path gather (no laws, no rho: those fields are not read); a.acc (and
 // a.accSq with a.stat): num x primCount int64 sums, species-major, zeroed by the caller.  Per species s < num: rho[s] or
 // rhoLeaf[s] (LEAF order), cosinePower[s], g[s], gL[s], lawCount[s][w] (0: absent) of the three laws at
-// laws + (3 s + w) x GATHER_LAW_MAX (laws == nullptr: no species has a law)
+// laws + (3 s + w) x GATHER_LAW_MAX (laws == nullptr: no species has a law).
+// With a.stat, a.list / a.listCount as GatherArgs has them (a later round of vr_gather_species_adaptive_device) and beside
+// the list listMask: entry e's species still sampling, bit s for species s — a lane starts its paths with that mask alive
 constexpr unsigned GATHER_SPECIES_MAX = 4;
 struct GatherSpeciesArgs {
   GatherArgs a;
@@ -236,9 +238,27 @@ struct GatherSpeciesArgs {
   float cosinePower[GATHER_SPECIES_MAX], g[GATHER_SPECIES_MAX], gL[GATHER_SPECIES_MAX];
   uint32_t lawCount[GATHER_SPECIES_MAX][3];
   const float *laws;
+  const uint32_t *listMask; // a.listCount words where a.list is set, each a non-empty subset of the num species
 };
 // p, slabs: as launch_gather_samples, and its shape: one launch of at most min(slabs, groups x chunks x subs) waves
 hipError_t launch_gather_species(const TraceParams &p, int geo, int D, const GatherSpeciesArgs &sa, unsigned slabs, hipStream_t st);
+// one round's verdict of vr_gather_species_adaptive_device (vr_gather_species.hip: gather_species_decide_kernel): what
+// GatherDecideArgs is to vr_gather_adaptive_device, for num species.  acc / accSq and the outputs are num x primCount,
+// species-major; masks: the species still sampling per entry of the current list (nullptr: all of them, round 0).  Every
+// species of an entry's mask is tested under rel[s] / abs[s] (vr_gather.hpp: gather_species_decide); one that converges —
+// every one when `last` — gets its outputs.  Entries with a species left go to next / nextMasks in the current order.
+// words[0]: how many those are; words[1 + s]: in how many of them species s is left (with `last`: the unconverged of
+// species s).  words[1 ..] are added to: the caller zeroes them.  blockCounts: ceil(count / GATHER_DECIDE_BLOCK) words
+struct GatherSpeciesDecideArgs {
+  const unsigned long long *acc, *accSq;
+  const uint32_t *list, *masks, *origWords;
+  uint32_t *next, *nextMasks, *blockCounts, *words;
+  float *flux, *stdErr;
+  uint32_t *samplesUsed;
+  uint32_t count, samples, origStride, origOffset, last, primCount, num;
+  float rel[GATHER_SPECIES_MAX], abs[GATHER_SPECIES_MAX];
+};
+hipError_t launch_gather_species_decide(const GatherSpeciesDecideArgs &d, hipStream_t st);
 // the radiosity solve over a recorded link table (vr_radiosity.hip; vr_radiosity.hpp has the arithmetic and the table's
 // index).  Every pointer is device memory; everything but rho / out of the rho and unpermute launches is in LEAF order
 struct RadiosityArgs {

@@ -1296,6 +1296,49 @@ class Trace:
                                                           C.c_void_p(self._torch_stream())))
         return s1, s2
 
+    def gatherSpeciesAdaptive(self, target, species, reflection=GatherReflection.SPECULAR, maxBounces=64, minSamples=64,
+                              maxSamples=4096, absTarget=0.0, primFirst=0, primCount=None, returnInfo=False, numpy=False):
+        """gatherSpecies to a target error per species: (flux, stdErr, samples), each [S, primCount], row s with the bits
+        of gatherAngularAdaptive called with species s's arguments and targets.  The rounds are gatherPathsAdaptive's,
+        run once for all species along one set of traced paths; on every primitive each species stops at its own K, and
+        one that has stopped no longer keeps the shared path going.
+          target, absTarget  a scalar, which applies to all species, or a sequence of S values
+          species, reflection, maxBounces, tensors and numpy arrays  as gatherSpecies
+          minSamples, maxSamples  as gatherPathsAdaptive
+        With returnInfo a dict as well: rounds, unconverged (a list of S), totalSamples (a list of S: what each species'
+        own call reports) and walkedSamples, the samples actually walked — per primitive the largest count among its
+        species (vr_gather_species_adaptive*; include/viennaray_amd.h has the definition)."""
+        _, primFirst, primCount = self._gatherRange("gatherSpeciesAdaptive", primFirst, primCount, minSamples, maxSamples, maxBounces)
+        specs, laws, S, host, keep = self._speciesSpecs("gatherSpeciesAdaptive", species, reflection, maxBounces, numpy)
+
+        def targets(what, value):
+            t = np.asarray(value, dtype=np.float32).reshape(-1)
+            if t.size == 1:
+                t = np.repeat(t, max(1, S))
+            if t.size != max(1, S):
+                raise ValueError("gatherSpeciesAdaptive: %s takes a scalar or one value per species (%d), not %d" % (what, S, t.size))
+            return np.ascontiguousarray(t)
+
+        rel, absT = targets("target", target), targets("absTarget", absTarget)
+        info = capi.GatherSpeciesAdaptiveInfoPOD()
+        if host:
+            flux, err = np.empty((S, primCount), dtype=np.float32), np.empty((S, primCount), dtype=np.float32)
+            used = np.empty((S, primCount), dtype=np.uint32)
+            self._check(self._L.vr_gather_species_adaptive(self._h, specs, laws, S, primFirst, primCount, int(minSamples), int(maxSamples),
+                                                           _fptr(rel), _fptr(absT), _fptr(flux), _fptr(err),
+                                                           used.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info)))
+        else:
+            import torch
+            dev = torch.device("cuda", self._device)
+            flux = torch.empty((S, primCount), dtype=torch.float32, device=dev)
+            err = torch.empty((S, primCount), dtype=torch.float32, device=dev)
+            used = torch.empty((S, primCount), dtype=torch.int32, device=dev)  # (the uint32 counts, at most 2^22)
+            self._check(self._L.vr_gather_species_adaptive_device(
+                self._h, specs, laws, S, primFirst, primCount, int(minSamples), int(maxSamples), _fptr(rel), _fptr(absT),
+                C.c_void_p(flux.data_ptr()), C.c_void_p(err.data_ptr()), C.c_void_p(used.data_ptr()), C.byref(info),
+                C.c_void_p(self._torch_stream())))
+        return (flux, err, used, info.as_dict(S)) if returnInfo else (flux, err, used)
+
     # --- radiosity solve: the steady-state flux of a diffusely re-emitting species (vr_radiosity_*) ------------------
     def radiosityLinkBytes(self, samples):
         """bytes of device memory the link table for `samples` samples per primitive takes (vr_radiosity_link_bytes)"""
