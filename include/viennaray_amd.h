@@ -722,6 +722,88 @@ int vr_debug_gather_angular_path(vr_context *ctx, const vr_gather_spec *spec, co
                                  uint32_t sample, uint32_t maxVertices, uint32_t *vertexIds, float *vertexData,
                                  uint32_t *numVertices, uint32_t *end, float *finalDirection3, float *throughput,
                                  float *weight);
+/* ---- energy gather (not in the reference): an ion's energy lost along a path, a yield by the arrival energy -------------
+ * vr_gather_angular weighs a path by angles.  An ion-enhanced etch or sputter yield also depends on the ENERGY the ion
+ * arrives with: it leaves the source with E0 and keeps a share eps(mu) of its energy at every reflection.  A backward path
+ * can carry that exactly because the loss is multiplicative: the ion arrives with E0 prod_j eps(mu_j), a product that does
+ * not depend on the order the vertices are visited in.  These calls are vr_gather_angular with one more multiply at the
+ * tail and are otherwise that call bit for bit: samples, chunk engines, segments, walls, ends, q(), q2(), wmax, the sums
+ * and the final division.
+ * Tables   vr_gather_energy holds HOST tables, read by vr_gather_angular's look-up law(t, M, x):
+ *   energyYield      Y_E(e), REQUIRED, 2 .. 256 entries finite and >= 0, read at e in [0, 1].
+ *   energyMax        the energy that e = 1 stands for; finite, > 0.
+ *   sourceQuantiles  NULL, or 2 .. 256 entries finite and >= 0: the source's inverse CDF Q(u), read at u.
+ *   sourceEnergy     used where sourceQuantiles is NULL: a monoenergetic source.  Finite, >= 0.
+ *   retentionLaw     NULL (no loss), or 2 .. 256 entries in [0, 1]: eps(mu) at the mu of reflectivityLaw,
+ *                    mu = n_j . (the direction the path LEAVES the vertex along).
+ *   energyCut        1 or 0 (below).
+ * Sample   Per sample k of primitive i, float32, one IEEE operation per step in this order, no contraction:
+ *            key = tea8(i, (seed ^ "PATH") + k), the key of the DIFFUSE draws;
+ *            u = (tea8(key, 0x454E5247) >> 8) * 2^-24   (the counter is "ENRG"; the bounce counters stop at 131071);
+ *            E0 = sourceQuantiles ? law(Q, MQ, u) : sourceEnergy;  P = 1;
+ *            at every front-side hit after which the path goes on (both of T's multiplies passed):
+ *              P = P * law(eps, Meps, mu);
+ *            e = (E0 * P) / energyMax   — the arrival energy in table units, the product first;
+ *            w = w_angular * law(Y_E, MY, e)   — the last multiply.
+ * Bounds   wbound = wbound_angular max Y_E; samples (budget, maxSamples) x wbound > 2^22 is refused.
+ * Cut      Z0: the number of leading entries of energyYield equal to 0.  With energyCut and Z0 >= 2, and
+ *          xs = min(max(e, 0), 1) * (float)(MY - 1) — the look-up's own xs — a path ends with VR_GATHER_END_ENERGY, weight
+ *          0, as soon as xs < (float)(Z0 - 1).  The test is made once before the walk (P = 1: such a sample is not walked
+ *          at all) and after every update of P.  eps <= 1 and rounding is monotone, so e never rises, and every e with
+ *          xs < Z0 - 1 reads exactly 0: flux, sums and sums of squares have the same bits with the cut on and off.
+ * Identities  energy == NULL: the bits of the vr_gather_angular* call.  An all-ones energyYield of any M, with anything in
+ *          the other fields: those bits too.  With reflectivityScalar 1, no yieldLaw, sourceEnergy = energyMax = 1,
+ *          energyYield = {0, 1} and retentionLaw = R: the bits of vr_gather_angular with reflectivityLaw = R (P is then that
+ *          call's T multiply for multiply, and {0, 1} read at e returns e).
+ * Refused, outputs untouched and the context usable, message in vr_last_error:
+ *   VR_E_INVALID  what the matching vr_gather_angular* call refuses; a NULL energyYield; a count outside 2 .. 256; an
+ *                 entry outside its table's range (the message names the table and the lowest such index); energyMax not
+ *                 finite or not > 0; a negative or non-finite sourceEnergy; energyCut other than 0 or 1;
+ *                 samples x wbound > 2^22.
+ *   VR_E_STATE    as vr_gather_flux_device.
+ * Streams, work buffers and "changes nothing of a finished apply": as the matching vr_gather_angular* call.
+ * Outputs as those of vr_gather_angular*.  Energy in vr_gather_species*, a stochastic spread of the retained energy and
+ * yields of two variables Y(theta, E) are not offered */
+#define VR_GATHER_END_ENERGY 7 /* the arrival energy entered the zero region of energyYield (the cut) */
+/* (a struct tag alone, no typedef: vr_gather_energy is also the name of the host entry point) */
+struct vr_gather_energy {
+  const float *energyYield; /* energyYieldCount HOST floats */
+  uint32_t energyYieldCount;
+  float energyMax;
+  const float *sourceQuantiles; /* NULL or sourceQuantilesCount HOST floats */
+  uint32_t sourceQuantilesCount;
+  float sourceEnergy;
+  const float *retentionLaw; /* NULL or retentionCount HOST floats */
+  uint32_t retentionCount;
+  uint32_t energyCut;
+};
+int vr_gather_energy_device(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws,
+                            const struct vr_gather_energy *energy, uint32_t primFirst, uint32_t primCount, uint32_t samples,
+                            float *out, void *stream);
+int vr_gather_energy(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws, const struct vr_gather_energy *energy,
+                     uint32_t primFirst, uint32_t primCount, uint32_t samples, float *out);
+int vr_gather_energy_sums_device(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws,
+                                 const struct vr_gather_energy *energy, uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst,
+                                 uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq, void *stream);
+int vr_gather_energy_sums(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws,
+                          const struct vr_gather_energy *energy, uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst,
+                          uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq);
+int vr_gather_energy_adaptive_device(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws,
+                                     const struct vr_gather_energy *energy, uint32_t primFirst, uint32_t primCount,
+                                     uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux,
+                                     float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream);
+int vr_gather_energy_adaptive(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws,
+                              const struct vr_gather_energy *energy, uint32_t primFirst, uint32_t primCount, uint32_t minSamples,
+                              uint32_t maxSamples, float relTarget, float absTarget, float *flux, float *stdErr,
+                              uint32_t *samplesUsed, vr_gather_adaptive_info *info);
+/* ONE path as vr_debug_gather_angular_path records it, with its energy: energyOut4 (NULL, or 4 floats) = {u, E0, P, e}; with
+ * energy == NULL it is that call and energyOut4 is left alone.  A sample the cut ended before its walk has one vertex; a
+ * vertex the cut ended the path on keeps its leaving direction — the one its retention was read at — where every other
+ * last vertex has NaN */
+int vr_debug_gather_energy_path(vr_context *ctx, const vr_gather_spec *spec, const vr_gather_laws *laws,
+                                const struct vr_gather_energy *energy, uint32_t prim, uint32_t sample, uint32_t maxVertices,
+                                uint32_t *vertexIds, float *vertexData, uint32_t *numVertices, uint32_t *end,
+                                float *finalDirection3, float *throughput, float *weight, float *energyOut4);
 /* ---- species gather (not in the reference): several species weighed along one set of traced paths ----------------------
  * A process step has two or three ion species, or one whose arrivals feed several yields.  Each is a vr_gather_angular
  * call, and every call walks the same paths again: the samples are a pure function of (seed, primitive, sample), the

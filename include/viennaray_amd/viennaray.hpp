@@ -1543,6 +1543,86 @@ public:
                                                  &rec.numVertices, &rec.end, rec.direction, &rec.throughput, &rec.weight));
   }
 
+  // ---- energy gather (not in the reference; vr_gather_energy*, whose header comment has the definition): gatherAngular
+  //      with the ion's energy carried along every path — E0 at the source, a share retention(mu) kept at every
+  //      reflection, one more multiply by yield(E / energyMax) at the tail.  With an all-ones yield the results are
+  //      gatherAngular's word for word.
+  /// the energy tables of an energy gather: yield required, quantiles and retention empty (absent) or 2 .. 256 values;
+  /// the object must outlive the vr_gather_energy taken from it
+  struct GatherEnergy {
+    std::vector<float> yield, sourceQuantiles, retention;
+    float energyMax = 1.f, sourceEnergy = 0.f; // sourceEnergy counts where sourceQuantiles is empty
+    bool energyCut = true;
+    [[nodiscard]] struct vr_gather_energy pod() const {
+      struct vr_gather_energy e {};
+      e.energyYield = yield.empty() ? nullptr : yield.data();
+      e.energyYieldCount = (uint32_t)yield.size();
+      e.energyMax = energyMax;
+      e.sourceQuantiles = sourceQuantiles.empty() ? nullptr : sourceQuantiles.data();
+      e.sourceQuantilesCount = (uint32_t)sourceQuantiles.size();
+      e.sourceEnergy = sourceEnergy;
+      e.retentionLaw = retention.empty() ? nullptr : retention.data();
+      e.retentionCount = (uint32_t)retention.size();
+      e.energyCut = energyCut ? 1u : 0u;
+      return e;
+    }
+  };
+  /// one value per primitive (empty if it was refused); sticking: the scalar of gatherPaths
+  [[nodiscard]] std::vector<NumericType> gatherEnergy(unsigned samples, const GatherEnergy &energy, const GatherLaws &laws,
+                                                      NumericType sticking, GatherReflection reflection = GatherReflection::SPECULAR,
+                                                      unsigned maxBounces = 64, NumericType cosinePower = 1) {
+    if (!ctx_)
+      return {};
+    const vr_gather_spec spec = pathsSpec(nullptr, 1.f - (float)sticking, reflection, maxBounces, cosinePower);
+    const vr_gather_laws l = laws.pod();
+    const struct vr_gather_energy e = energy.pod();
+    std::vector<float> raw(vr_num_primitives(ctx_));
+    if (!reported(::vr_gather_energy(ctx_, &spec, &l, &e, 0u, (uint32_t)raw.size(), samples, raw.data())))
+      return {};
+    return std::vector<NumericType>(raw.begin(), raw.end());
+  }
+  /// spec.reflectivity and dOut (primCount floats) are DEVICE memory, the tables the host's; gatherPathsDevice's stream rules
+  bool gatherEnergyDevice(const vr_gather_spec &spec, const GatherLaws &laws, const GatherEnergy &energy, unsigned primFirst,
+                          unsigned primCount, unsigned samples, float *dOut, void *stream = nullptr) {
+    const vr_gather_laws l = laws.pod();
+    const struct vr_gather_energy e = energy.pod();
+    return ctx_ && reported(vr_gather_energy_device(ctx_, &spec, &l, &e, primFirst, primCount, samples, dOut, stream));
+  }
+  /// gatherSums of an energy gather's samples (host tables in the spec).  false if it was refused.
+  bool gatherEnergySums(const vr_gather_spec &spec, const GatherLaws &laws, const GatherEnergy &energy, unsigned chunkFirst,
+                        unsigned chunks, unsigned budget, std::vector<int64_t> &sum, std::vector<int64_t> &sumSq) {
+    if (!ctx_)
+      return false;
+    const vr_gather_laws l = laws.pod();
+    const struct vr_gather_energy e = energy.pod();
+    const uint32_t n = vr_num_primitives(ctx_);
+    sum.assign(n, 0);
+    sumSq.assign(n, 0);
+    return reported(vr_gather_energy_sums(ctx_, &spec, &l, &e, 0u, n, chunkFirst, chunks, budget, sum.data(), sumSq.data()));
+  }
+  [[nodiscard]] GatherAdaptiveResult gatherEnergyAdaptive(NumericType relTarget, const GatherEnergy &energy, const GatherLaws &laws,
+                                                          NumericType sticking,
+                                                          GatherReflection reflection = GatherReflection::SPECULAR,
+                                                          unsigned maxBounces = 64, unsigned minSamples = 64,
+                                                          unsigned maxSamples = 4096, NumericType absTarget = 0,
+                                                          NumericType cosinePower = 1) {
+    if (!ctx_)
+      return {};
+    const vr_gather_spec spec = pathsSpec(nullptr, 1.f - (float)sticking, reflection, maxBounces, cosinePower);
+    const vr_gather_laws l = laws.pod();
+    const struct vr_gather_energy e = energy.pod();
+    const uint32_t n = vr_num_primitives(ctx_);
+    std::vector<float> flux(n), err(n);
+    GatherAdaptiveResult r;
+    r.samplesUsed.resize(n);
+    if (!reported(vr_gather_energy_adaptive(ctx_, &spec, &l, &e, 0u, n, minSamples, maxSamples, (float)relTarget, (float)absTarget,
+                                            flux.data(), err.data(), reinterpret_cast<uint32_t *>(r.samplesUsed.data()), &r.info)))
+      return {};
+    r.flux.assign(flux.begin(), flux.end());
+    r.stdErr.assign(err.begin(), err.end());
+    return r;
+  }
+
   // ---- species gather (not in the reference; vr_gather_species*, whose header comment has the definition): up to
   //      VR_GATHER_MAX_SPECIES species weighed along ONE set of traced paths.  Row s of the result is gatherAngular of
   //      species s word for word; reflection and maxBounces make the path and are shared.

@@ -5,7 +5,7 @@ its Python host mirror (used by bench.py and the parity tests).
 """
 from .capi import VrError, load, device_available, LIB_PATH  # noqa: F401
 from .trace import (BoundaryCondition, TraceDirection, NormalizationType,  # noqa: F401
-                    TracingDataMergeEnum, GatherMode, GatherReflection, DiffuseParticle, SpecularParticle,
+                    TracingDataMergeEnum, GatherMode, GatherReflection, GatherEnd, DiffuseParticle, SpecularParticle,
                     ConedCosineParticle, DiffuseCosineParticle, CoverageStickingParticle, UserModelParticle, SourceGrid, SourceModel,
                     TracingData, Trace, TraceDisk, TraceTriangle)
 from . import io  # noqa: F401

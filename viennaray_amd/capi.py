@@ -66,6 +66,13 @@ class GatherLawsPOD(C.Structure):
                 ("reflectivityCount", C.c_uint32), ("yieldLaw", C.c_void_p), ("yieldCount", C.c_uint32)]
 
 
+class GatherEnergyPOD(C.Structure):
+    """struct vr_gather_energy (include/viennaray_amd.h): the energy tables of vr_gather_energy*, HOST tables"""
+    _fields_ = [("energyYield", C.c_void_p), ("energyYieldCount", C.c_uint32), ("energyMax", C.c_float),
+                ("sourceQuantiles", C.c_void_p), ("sourceQuantilesCount", C.c_uint32), ("sourceEnergy", C.c_float),
+                ("retentionLaw", C.c_void_p), ("retentionCount", C.c_uint32), ("energyCut", C.c_uint32)]
+
+
 class GatherAdaptiveInfoPOD(C.Structure):
     """vr_gather_adaptive_info (include/viennaray_amd.h)"""
     _fields_ = [("rounds", C.c_uint32), ("unconverged", C.c_uint32), ("totalSamples", C.c_uint64)]
@@ -190,6 +197,23 @@ SIGNATURES = {
                                              C.POINTER(GatherAdaptiveInfoPOD)]),
     "vr_debug_gather_angular_path": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
                                                C.c_uint32, _u32p, _fp, _u32p, _u32p, _fp, _fp, _fp]),
+    "vr_gather_energy_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.POINTER(GatherEnergyPOD),
+                                          C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vr_gather_energy": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.POINTER(GatherEnergyPOD), C.c_uint32,
+                                   C.c_uint32, C.c_uint32, _fp]),
+    "vr_gather_energy_sums_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.POINTER(GatherEnergyPOD),
+                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vr_gather_energy_sums": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.POINTER(GatherEnergyPOD),
+                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64)]),
+    "vr_gather_energy_adaptive_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD),
+                                                   C.POINTER(GatherEnergyPOD), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                   C.c_float, C.c_float, _vp, _vp, _vp, C.POINTER(GatherAdaptiveInfoPOD), _vp]),
+    "vr_gather_energy_adaptive": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.POINTER(GatherEnergyPOD),
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, _fp, _fp, _u32p,
+                                            C.POINTER(GatherAdaptiveInfoPOD)]),
+    "vr_debug_gather_energy_path": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.POINTER(GatherEnergyPOD),
+                                              C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _fp, _u32p, _u32p, _fp, _fp, _fp, _fp]),
     "vr_gather_species_device": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32,
                                            C.c_uint32, C.c_uint32, _vp, _vp]),
     "vr_gather_species": (C.c_int, [_vp, C.POINTER(GatherSpecPOD), C.POINTER(GatherLawsPOD), C.c_uint32, C.c_uint32, C.c_uint32,

@@ -398,6 +398,9 @@ struct vr_context {
   // its own arguments on c->stream, so behind an earlier call that still reads them).  Grown behind host_waits only
   // vr_gather_species* keeps numSpecies of each in the gather's own buffers: sums, laws, reflectivities, verdict words
   DevBuf<float> dGatherLaws;
+  // vr_gather_energy*: the three energy tables of the call in flight beside them, 3 x GATHER_LAW_MAX floats, written and
+  // grown the same way
+  DevBuf<float> dGatherEnergy;
   // vr_radiosity_*: the link table of the last vr_radiosity_links_device (slots x samples int32 in leaf order,
   // vr_radiosity.hpp), its direct sums and leaf -> original id table, what it was built from, and a solve's work buffers
   // (leaf order: reflectivity, F, the two emission tables; the words that come back; the host forms' staging).  A table
@@ -567,34 +570,56 @@ struct GatherLawSet {
   bool any = false;
   uint32_t count[3] = {0, 0, 0};
   float gL = 1.f;
+  double wbound = 1.; // (g_L max L or g) max Y: the largest weight a path of the call can have
   float table[3 * 256] = {}; // (GATHER_LAW_MAX each)
 };
 int gather_laws_refusal(vr_context *c, const char *api, const vr_gather_laws *laws, float cosinePower, uint32_t samples,
                         GatherLawSet &set);
 int gather_laws_args(vr_context *c, bool &waited, const GatherLawSet &set, GatherArgs &a);
-// the entry points of vr_gather_paths.cpp, vr_gather_adaptive.cpp and vr_gather_angular.cpp share one implementation each
-// (laws == nullptr: the former); `api` names the entry point in the messages
+// vr_gather_energy.cpp: the energy tables of a call (energy == nullptr: none — the call is the angular one).
+// gather_energy_refusal checks them on the host, before anything is touched, against the angular call's wbound and the
+// sample budget and leaves them in `set`; gather_energy_args puts them on the device and into `ea` (all but ea.a);
+// gather_launch is the one place a path gather's samples are launched from: the energy kernel with ea (its .a taken from
+// a), the gather's own without
+struct GatherEnergySet {
+  bool any = false;
+  uint32_t count[3] = {0, 0, 0}; // yield, quantiles, retention (vr_gather.hpp: GATHER_ENERGY_*)
+  float energyMax = 1.f, sourceEnergy = 0.f;
+  uint32_t zeros = 0; // the cut's Z0; 0: no cut
+  float table[3 * 256] = {}; // (GATHER_LAW_MAX each)
+};
+int gather_energy_refusal(vr_context *c, const char *api, const struct vr_gather_energy *energy, double wboundAngular, uint32_t samples,
+                          GatherEnergySet &set);
+int gather_energy_args(vr_context *c, bool &waited, const GatherEnergySet &set, GatherEnergyArgs &ea);
+int gather_launch(vr_context *c, const TraceParams &p, const GatherArgs &a, const GatherEnergyArgs *ea, unsigned slabs);
+// the entry points of vr_gather_paths.cpp, vr_gather_adaptive.cpp, vr_gather_angular.cpp and vr_gather_energy.cpp share one
+// implementation each (laws == nullptr: the former; energy != nullptr: the latter, whose one-path walk also fills
+// energyOut4); `api` names the entry point in the messages
 int paths_call_device(vr_context *c, const char *api, const vr_gather_laws *laws, uint32_t primFirst, uint32_t primCount,
                       uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, const float *reflectivity,
-                      float reflectivityScalar, float *out, void *stream);
+                      float reflectivityScalar, float *out, void *stream, const struct vr_gather_energy *energy = nullptr);
 int paths_call_host(vr_context *c, const char *api, const vr_gather_laws *laws, uint32_t primFirst, uint32_t primCount,
                     uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, const float *reflectivity,
-                    float reflectivityScalar, float *out);
+                    float reflectivityScalar, float *out, const struct vr_gather_energy *energy = nullptr);
 int paths_call_debug(vr_context *c, const char *api, const vr_gather_laws *laws, uint32_t prim, uint32_t sample, float cosinePower,
                      uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float reflectivityScalar,
                      uint32_t maxVertices, uint32_t *vertexIds, float *vertexData, uint32_t *numVertices, uint32_t *end,
-                     float *finalDirection3, float *throughput, float *weight);
+                     float *finalDirection3, float *throughput, float *weight, const struct vr_gather_energy *energy = nullptr,
+                     float *energyOut4 = nullptr);
 int sums_call_device(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
                      uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq,
-                     void *stream);
+                     void *stream, const struct vr_gather_energy *energy = nullptr);
 int sums_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
-                   uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq);
+                   uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq,
+                   const struct vr_gather_energy *energy = nullptr);
 int adaptive_call_device(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
                          uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget,
-                         float *flux, float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream);
+                         float *flux, float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream,
+                         const struct vr_gather_energy *energy = nullptr);
 int adaptive_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *laws, uint32_t primFirst,
                        uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux,
-                       float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info);
+                       float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info,
+                       const struct vr_gather_energy *energy = nullptr);
 
 // a work buffer of the map or of a cast grows behind host_waits only (vr_api.cpp: a buffer that moves)
 template <class T> int map_grow(vr_context *c, DevBuf<T> &b, size_t n, bool &waited) {

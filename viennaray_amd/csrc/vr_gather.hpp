@@ -460,6 +460,56 @@ VR_GATHER_FN unsigned gather_species_decide(const int64_t *S1, const int64_t *S2
   return failed;
 }
 
+// ---- gatherEnergy (vr_gather_energy*): an ion's energy carried along a path ------------------------------------------
+constexpr uint32_t GATHER_ENERGY_COUNTER = 0x454E5247u; // "ENRG": the counter of the energy draw (the bounce draws' stop at 131071)
+constexpr int GATHER_END_ENERGY = 7;                    // VR_GATHER_END_ENERGY: the arrival energy has entered the yield's zero region
+// the three energy tables' places in the device table (GATHER_LAW_MAX floats each) and in GatherEnergyArgs::count
+constexpr int GATHER_ENERGY_YIELD = 0, GATHER_ENERGY_QUANTILES = 1, GATHER_ENERGY_RETENTION = 2;
+// u of a path: the top 24 bits of one hash of the path's key (gather_path_key), in [0, 1); both operations are exact
+VR_GATHER_FN float gather_energy_u(uint32_t key) {
+  return (float)(gather_tea8(key, GATHER_ENERGY_COUNTER) >> 8) * 5.9604644775390625e-08f; // 2^-24
+}
+// E0: the source's inverse CDF Q read at u, or (Q == nullptr) the one energy of a monoenergetic source
+VR_GATHER_FN float gather_energy_source(const float *Q, uint32_t MQ, float u, float sourceEnergy) {
+  return Q ? gather_law(Q, MQ, u) : sourceEnergy;
+}
+// P after a front-side hit the path goes on from: one multiply by the retention law at mu, the reflectivity law's mu
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN float gather_energy_retain(float P, const float *eps, uint32_t Meps, float mu) {
+  VR_GATHER_NO_CONTRACT
+  return P * gather_law(eps, Meps, mu);
+}
+// e: the arrival energy in the yield table's units — the product first, then the division
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN float gather_energy_arrival(float E0, float P, float energyMax) {
+  VR_GATHER_NO_CONTRACT
+  const float EP = E0 * P;
+  return EP / energyMax;
+}
+// the last multiply of a path's weight: by the energy yield at e
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN float gather_energy_weight(float wAngular, const float *YE, uint32_t MY, float e) {
+  VR_GATHER_NO_CONTRACT
+  return wAngular * gather_law(YE, MY, e);
+}
+// Z0: the leading entries of an energy yield that are 0
+inline uint32_t gather_energy_zeros(const float *YE, uint32_t MY) {
+  uint32_t z = 0;
+  while (z < MY && YE[z] == 0.f)
+    ++z;
+  return z;
+}
+// The cut (Z0 >= 2): true when e lies where the yield reads exactly 0 — xs, gather_law's own, is below node Z0 - 1, so the
+// look-up interpolates between two entries that are both 0.  e = (E0 P) / energyMax never rises along a path: P only takes
+// multiplies by values in [0, 1] and every rounding is monotone, so a path for which this holds weighs 0 whatever follows
+VR_GATHER_NO_CONTRACT_ATTR VR_GATHER_FN bool gather_energy_cut(float e, uint32_t MY, uint32_t Z0) {
+  VR_GATHER_NO_CONTRACT
+  const float xc = fminf(fmaxf(e, 0.f), 1.f);
+  const float xs = xc * (float)(MY - 1u);
+  return xs < (float)(Z0 - 1u);
+}
+// what an entry of each energy table may be: finite and >= 0 (yield, quantiles), in [0, 1] (retention)
+VR_GATHER_FN bool gather_energy_entry_ok(int which, float v) {
+  return gather_law_entry_ok(which == GATHER_ENERGY_RETENTION ? GATHER_LAW_REFLECTIVITY : GATHER_LAW_YIELD, v);
+}
+
 // g_D(n) (a host function; the kernel takes the float): g_3 = (n + 1) / 2, g_2 = 2 / C_n with
 // C_n = sqrt(pi) Gamma((n + 1) / 2) / Gamma(n / 2 + 1) — the weight of a sample that reaches the source is the ratio of
 // the source's normalised law (n + 1) / (2 pi) c^n (3-D), c^n / C_n (2-D) and the receiver's cosine law c / pi, c / 2 for

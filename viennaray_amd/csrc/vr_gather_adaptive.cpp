@@ -14,7 +14,8 @@ namespace vr {
 
 // what every form refuses before it touches anything; samples: the budget or maxSamples; out: a non-null output
 static int spec_refusal(vr_context *c, const char *api, const vr_gather_spec *s, const vr_gather_laws *lawsIn, GatherLawSet &laws,
-                        uint32_t primFirst, uint32_t primCount, uint32_t samples, const void *out) {
+                        const struct vr_gather_energy *energyIn, GatherEnergySet &energy, uint32_t primFirst, uint32_t primCount,
+                        uint32_t samples, const void *out) {
   const std::string name = api;
   if (!s)
     return fail(c, VR_E_INVALID, (name + ": spec must not be null").c_str());
@@ -23,7 +24,8 @@ static int spec_refusal(vr_context *c, const char *api, const vr_gather_spec *s,
       return fail(c, VR_E_INVALID, (name + ": angular laws need spec.paths == 1, VR_GATHER_NORMAL and no emission table").c_str());
     VR_TRY(paths_refusal(c, api, primFirst, primCount, samples, s->cosinePower, s->reflection, s->maxBounces, s->reflectivity,
                          s->reflectivityScalar, out));
-    return gather_laws_refusal(c, api, lawsIn, s->cosinePower, samples, laws);
+    VR_TRY(gather_laws_refusal(c, api, lawsIn, s->cosinePower, samples, laws));
+    return gather_energy_refusal(c, api, energyIn, laws.wbound, samples, energy); // (an energy entry point has laws, if empty ones)
   }
   if (s->paths > 1u)
     return fail(c, VR_E_INVALID, (name + ": spec.paths is 0 (vr_gather_flux's sample) or 1 (vr_gather_paths's)").c_str());
@@ -57,8 +59,8 @@ static int stat_args(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a,
 }
 
 // chunks [chunkFirst, chunkFirst + chunks) of the listed primitives (list == nullptr: of the whole range) into a.acc / a.accSq
-static int stat_launch(vr_context *c, const TraceParams &p, GatherArgs a, uint32_t chunkFirst, uint32_t chunks, const uint32_t *list,
-                       uint32_t listCount) {
+static int stat_launch(vr_context *c, const TraceParams &p, GatherArgs a, const GatherEnergyArgs *ea, uint32_t chunkFirst,
+                       uint32_t chunks, const uint32_t *list, uint32_t listCount) {
   a.chunkFirst = chunkFirst;
   a.chunks = chunks;
   a.samples = (chunkFirst + chunks) * GATHER_CHUNK; // (<= the budget <= 2^22: the entry points' checks)
@@ -68,39 +70,42 @@ static int stat_launch(vr_context *c, const TraceParams &p, GatherArgs a, uint32
   a.subs = 1u;
   const unsigned slabs = (unsigned)std::min<size_t>(c->walkStackWaves, 0xFFFFFFFFu);
   gather_cut_chunks(a, slabs); // per launch: the late rounds of an adaptive call have few primitives
-  VR_HIP(c, launch_gather_samples(p, c->geo.geo, c->geo.D, a, slabs, c->stream));
-  return VR_OK;
+  return gather_launch(c, p, a, ea, slabs);
 }
 
 static int sums_refusal(vr_context *c, const char *api, const vr_gather_spec *s, const vr_gather_laws *lawsIn, GatherLawSet &laws,
-                        uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget,
+                        const struct vr_gather_energy *energyIn, GatherEnergySet &energy, uint32_t primFirst, uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget,
                         const void *sum, const void *sumSq) {
-  VR_TRY(spec_refusal(c, api, s, lawsIn, laws, primFirst, primCount, budget, sum && sumSq ? sum : nullptr));
+  VR_TRY(spec_refusal(c, api, s, lawsIn, laws, energyIn, energy, primFirst, primCount, budget, sum && sumSq ? sum : nullptr));
   if (((uint64_t)chunkFirst + chunks) * GATHER_CHUNK > budget)
     return fail(c, VR_E_INVALID, (std::string(api) + ": the chunks end beyond the budget: 64 (chunkFirst + chunks) > budget").c_str());
   return VR_OK;
 }
 
 // every pointer is device memory, the arguments have been accepted
-static int sums_on_device(vr_context *c, const vr_gather_spec &s, const GatherLawSet &laws, const float *emission, bool table, uint32_t primFirst,
+static int sums_on_device(vr_context *c, const vr_gather_spec &s, const GatherLawSet &laws, const GatherEnergySet &energy,
+                          const float *emission, bool table, uint32_t primFirst,
                           uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, unsigned long long *sum,
                           unsigned long long *sumSq) {
   bool waited = false;
   TraceParams p;
   GatherArgs a;
   VR_TRY(stat_args(c, waited, p, a, s, laws, emission, table, primFirst, primCount, budget));
+  GatherEnergyArgs ea;
+  VR_TRY(gather_energy_args(c, waited, energy, ea));
   VR_HIP(c, hipMemsetAsync(sum, 0, (size_t)primCount * 8, c->stream));
   VR_HIP(c, hipMemsetAsync(sumSq, 0, (size_t)primCount * 8, c->stream));
   if (chunks == 0)
     return VR_OK;
   a.acc = sum;
   a.accSq = sumSq;
-  return stat_launch(c, p, a, chunkFirst, chunks, nullptr, 0u);
+  return stat_launch(c, p, a, energy.any ? &ea : nullptr, chunkFirst, chunks, nullptr, 0u);
 }
 
 static int adaptive_refusal(vr_context *c, const char *api, const vr_gather_spec *s, const vr_gather_laws *lawsIn,
-                            GatherLawSet &laws, uint32_t primFirst, uint32_t primCount, uint32_t minSamples, uint32_t maxSamples,
-                            float rel, float abs, const void *flux, const void *info) {
+                            GatherLawSet &laws, const struct vr_gather_energy *energyIn, GatherEnergySet &energy, uint32_t primFirst,
+                            uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float rel, float abs, const void *flux,
+                            const void *info) {
   const std::string name = api;
   if (minSamples == 0 || minSamples % GATHER_CHUNK)
     return fail(c, VR_E_INVALID, (name + ": minSamples must be a positive multiple of 64").c_str());
@@ -111,12 +116,13 @@ static int adaptive_refusal(vr_context *c, const char *api, const vr_gather_spec
     return fail(c, VR_E_INVALID, (name + ": the targets must not be negative or NaN").c_str());
   if (!info)
     return fail(c, VR_E_INVALID, (name + ": info must not be null").c_str());
-  return spec_refusal(c, api, s, lawsIn, laws, primFirst, primCount, maxSamples, flux);
+  return spec_refusal(c, api, s, lawsIn, laws, energyIn, energy, primFirst, primCount, maxSamples, flux);
 }
 
 // The rounds.  Every pointer is device memory (stdErr, samplesUsed: or nullptr), the arguments have been accepted.  The
 // host waits once per round for one word, the next list's length
-static int adaptive_on_device(vr_context *c, const vr_gather_spec &s, const GatherLawSet &laws, const float *emission, bool table, uint32_t primFirst,
+static int adaptive_on_device(vr_context *c, const vr_gather_spec &s, const GatherLawSet &laws, const GatherEnergySet &energy,
+                              const float *emission, bool table, uint32_t primFirst,
                               uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float rel, float abs, float *flux,
                               float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info &info) {
   bool waited = false;
@@ -129,6 +135,8 @@ static int adaptive_on_device(vr_context *c, const vr_gather_spec &s, const Gath
   TraceParams p;
   GatherArgs a;
   VR_TRY(stat_args(c, waited, p, a, s, laws, emission, table, primFirst, primCount, maxSamples));
+  GatherEnergyArgs ea;
+  VR_TRY(gather_energy_args(c, waited, energy, ea));
   a.acc = c->dGatherAcc.p;
   a.accSq = c->dGatherAccSq.p;
   VR_HIP(c, hipMemsetAsync(a.acc, 0, (size_t)primCount * 8, c->stream));
@@ -155,7 +163,7 @@ static int adaptive_on_device(vr_context *c, const vr_gather_spec &s, const Gath
   for (uint32_t r = 0;; ++r) {
     const uint32_t chunkFirst = r == 0 ? 0u : c0 << (r - 1u), chunks = r == 0 ? c0 : c0 << (r - 1u);
     const uint32_t K = (chunkFirst + chunks) * GATHER_CHUNK;
-    VR_TRY(stat_launch(c, p, a, chunkFirst, chunks, list, listCount));
+    VR_TRY(stat_launch(c, p, a, energy.any ? &ea : nullptr, chunkFirst, chunks, list, listCount));
     info.totalSamples += (uint64_t)listCount * chunks * GATHER_CHUNK;
     ++info.rounds;
     d.list = list;
@@ -201,9 +209,10 @@ static int spec_upload(vr_context *c, const char *api, const vr_gather_spec &s, 
 
 int sums_call_device(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *lawsIn, uint32_t primFirst,
                      uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq,
-                     void *stream) {
+                     void *stream, const struct vr_gather_energy *energyIn) {
   GatherLawSet laws;
-  VR_TRY(sums_refusal(c, api, spec, lawsIn, laws, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq));
+  GatherEnergySet energy;
+  VR_TRY(sums_refusal(c, api, spec, lawsIn, laws, energyIn, energy, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_TRY(hand_over(c, {spec->emission, spec->reflectivity, sum, sumSq},
                    (std::string(api) + ": the spec's tables, sum and sumSq must be device memory of the context's device").c_str(),
@@ -213,15 +222,17 @@ int sums_call_device(vr_context *c, const char *api, const vr_gather_spec *spec,
     VR_TRY(paths_table(c, api, spec->reflectivity));
   if (primCount == 0)
     return caller_waits(c, stream);
-  VR_TRY(sums_on_device(c, *spec, laws, spec->paths ? nullptr : spec->emission, table, primFirst, primCount, chunkFirst, chunks, budget,
+  VR_TRY(sums_on_device(c, *spec, laws, energy, spec->paths ? nullptr : spec->emission, table, primFirst, primCount, chunkFirst, chunks, budget,
                         reinterpret_cast<unsigned long long *>(sum), reinterpret_cast<unsigned long long *>(sumSq)));
   return caller_waits(c, stream);
 }
 
 int sums_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *lawsIn, uint32_t primFirst,
-                   uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq) {
+                   uint32_t primCount, uint32_t chunkFirst, uint32_t chunks, uint32_t budget, int64_t *sum, int64_t *sumSq,
+                   const struct vr_gather_energy *energyIn) {
   GatherLawSet laws;
-  VR_TRY(sums_refusal(c, api, spec, lawsIn, laws, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq));
+  GatherEnergySet energy;
+  VR_TRY(sums_refusal(c, api, spec, lawsIn, laws, energyIn, energy, primFirst, primCount, chunkFirst, chunks, budget, sum, sumSq));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_HIP(c, hipSetDevice(c->device));
   bool waited = false;
@@ -232,7 +243,7 @@ int sums_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, c
     return VR_OK;
   VR_TRY(map_grow(c, c->dGatherAcc, primCount, waited));
   VR_TRY(map_grow(c, c->dGatherAccSq, primCount, waited));
-  VR_TRY(sums_on_device(c, *spec, laws, emission, table, primFirst, primCount, chunkFirst, chunks, budget, c->dGatherAcc.p,
+  VR_TRY(sums_on_device(c, *spec, laws, energy, emission, table, primFirst, primCount, chunkFirst, chunks, budget, c->dGatherAcc.p,
                         c->dGatherAccSq.p));
   VR_HIP(c, hipMemcpyAsync(sum, c->dGatherAcc.p, (size_t)primCount * 8, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipMemcpyAsync(sumSq, c->dGatherAccSq.p, (size_t)primCount * 8, hipMemcpyDeviceToHost, c->stream));
@@ -242,9 +253,11 @@ int sums_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, c
 
 int adaptive_call_device(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *lawsIn, uint32_t primFirst,
                          uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget,
-                         float *flux, float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream) {
+                         float *flux, float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, void *stream,
+                         const struct vr_gather_energy *energyIn) {
   GatherLawSet laws;
-  VR_TRY(adaptive_refusal(c, api, spec, lawsIn, laws, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget, flux, info));
+  GatherEnergySet energy;
+  VR_TRY(adaptive_refusal(c, api, spec, lawsIn, laws, energyIn, energy, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget, flux, info));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_TRY(hand_over(c, {spec->emission, spec->reflectivity, flux, stdErr, samplesUsed},
                    (std::string(api) + ": the spec's tables, flux, stdErr and samplesUsed must be device memory of the context's device")
@@ -256,16 +269,17 @@ int adaptive_call_device(vr_context *c, const char *api, const vr_gather_spec *s
   *info = vr_gather_adaptive_info{};
   if (primCount == 0)
     return caller_waits(c, stream);
-  VR_TRY(adaptive_on_device(c, *spec, laws, spec->paths ? nullptr : spec->emission, table, primFirst, primCount, minSamples, maxSamples,
+  VR_TRY(adaptive_on_device(c, *spec, laws, energy, spec->paths ? nullptr : spec->emission, table, primFirst, primCount, minSamples, maxSamples,
                             relTarget, absTarget, flux, stdErr, samplesUsed, *info));
   return caller_waits(c, stream);
 }
 
 int adaptive_call_host(vr_context *c, const char *api, const vr_gather_spec *spec, const vr_gather_laws *lawsIn, uint32_t primFirst,
                        uint32_t primCount, uint32_t minSamples, uint32_t maxSamples, float relTarget, float absTarget, float *flux,
-                       float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info) {
+                       float *stdErr, uint32_t *samplesUsed, vr_gather_adaptive_info *info, const struct vr_gather_energy *energyIn) {
   GatherLawSet laws;
-  VR_TRY(adaptive_refusal(c, api, spec, lawsIn, laws, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget, flux, info));
+  GatherEnergySet energy;
+  VR_TRY(adaptive_refusal(c, api, spec, lawsIn, laws, energyIn, energy, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget, flux, info));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_HIP(c, hipSetDevice(c->device));
   bool waited = false;
@@ -278,7 +292,7 @@ int adaptive_call_host(vr_context *c, const char *api, const vr_gather_spec *spe
   VR_TRY(map_grow(c, c->dGatherOut, primCount, waited));
   VR_TRY(map_grow(c, c->dGatherErr, primCount, waited));
   VR_TRY(map_grow(c, c->dGatherUsed, primCount, waited));
-  VR_TRY(adaptive_on_device(c, *spec, laws, emission, table, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget,
+  VR_TRY(adaptive_on_device(c, *spec, laws, energy, emission, table, primFirst, primCount, minSamples, maxSamples, relTarget, absTarget,
                             c->dGatherOut.p, c->dGatherErr.p, c->dGatherUsed.p, *info));
   VR_HIP(c, hipMemcpyAsync(flux, c->dGatherOut.p, (size_t)primCount * 4, hipMemcpyDeviceToHost, c->stream));
   if (stdErr)

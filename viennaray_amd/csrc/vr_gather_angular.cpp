@@ -18,6 +18,7 @@ static_assert(sizeof(GatherLawSet::table) == 3 * GATHER_LAW_MAX * sizeof(float),
 int gather_laws_refusal(vr_context *c, const char *api, const vr_gather_laws *laws, float cosinePower, uint32_t samples,
                         GatherLawSet &set) {
   set = GatherLawSet{};
+  set.wbound = (double)gather_g(cosinePower, c->geo.D);
   if (!laws)
     return VR_OK;
   const std::string name = api;
@@ -56,6 +57,7 @@ int gather_laws_refusal(vr_context *c, const char *api, const vr_gather_laws *la
   if (!(wbound <= (double)gather_wmax(samples)))
     return fail(c, VR_E_INVALID,
                 (name + ": samples x wbound must stay below 2^22, wbound = (g_L max L or g) max Y (the int64 sums' range)").c_str());
+  set.wbound = wbound;
   return VR_OK;
 }
 

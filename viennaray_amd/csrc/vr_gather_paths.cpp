@@ -68,13 +68,16 @@ static int paths_args(vr_context *c, bool &waited, TraceParams &p, GatherArgs &a
 
 // the kernels, on the context's stream: every pointer is device memory, the arguments have been accepted, a table
 // (table: c->dPathRho holds it) has passed paths_table
-static int paths_on_device(vr_context *c, const GatherLawSet &laws, uint32_t primFirst, uint32_t primCount, uint32_t samples,
-                           float cosinePower, uint32_t reflection, uint32_t maxBounces, bool table, float scalar, float *out) {
+static int paths_on_device(vr_context *c, const GatherLawSet &laws, const GatherEnergySet &energy, uint32_t primFirst,
+                           uint32_t primCount, uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces,
+                           bool table, float scalar, float *out) {
   bool waited = false;
   VR_TRY(map_grow(c, c->dGatherAcc, primCount, waited));
   TraceParams p;
   GatherArgs a;
   VR_TRY(paths_args(c, waited, p, a, laws, primFirst, primCount, samples, cosinePower, reflection, maxBounces, table, scalar));
+  GatherEnergyArgs ea;
+  VR_TRY(gather_energy_args(c, waited, energy, ea));
   if (primCount == c->geo.numPrims)
     a.leafOfOrig = nullptr; // the whole scene: in leaf order
   a.acc = c->dGatherAcc.p;
@@ -84,7 +87,7 @@ static int paths_on_device(vr_context *c, const GatherLawSet &laws, uint32_t pri
 #ifdef VR_DIAG
   VR_HIP(c, hipMemsetAsync(p.counters + C_DIAG, 0, 16, c->stream));
 #endif
-  VR_HIP(c, launch_gather_samples(p, c->geo.geo, c->geo.D, a, slabs, c->stream));
+  VR_TRY(gather_launch(c, p, a, energy.any ? &ea : nullptr, slabs));
   VR_HIP(c, launch_gather_finish(c->dGatherAcc.p, primCount, samples, out, c->stream));
 #ifdef VR_DIAG
   { // the segment loop's lane occupancy (tools/gather_paths_bench.py reads the line): a round of segments occupies the
@@ -102,10 +105,12 @@ static int paths_on_device(vr_context *c, const GatherLawSet &laws, uint32_t pri
 
 int paths_call_device(vr_context *c, const char *api, const vr_gather_laws *lawsIn, uint32_t primFirst, uint32_t primCount,
                       uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, const float *reflectivity,
-                      float reflectivityScalar, float *out, void *stream) {
+                      float reflectivityScalar, float *out, void *stream, const struct vr_gather_energy *energyIn) {
   VR_TRY(paths_refusal(c, api, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity, reflectivityScalar, out));
   GatherLawSet laws;
   VR_TRY(gather_laws_refusal(c, api, lawsIn, cosinePower, samples, laws));
+  GatherEnergySet energy;
+  VR_TRY(gather_energy_refusal(c, api, energyIn, laws.wbound, samples, energy));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_TRY(hand_over(c, {reflectivity, out},
                    (std::string(api) + ": reflectivity and out must be device memory of the context's device").c_str(), stream));
@@ -113,17 +118,19 @@ int paths_call_device(vr_context *c, const char *api, const vr_gather_laws *laws
     VR_TRY(paths_table(c, api, reflectivity));
   if (primCount == 0)
     return caller_waits(c, stream);
-  VR_TRY(paths_on_device(c, laws, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity != nullptr,
+  VR_TRY(paths_on_device(c, laws, energy, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity != nullptr,
                          reflectivityScalar, out));
   return caller_waits(c, stream);
 }
 
 int paths_call_host(vr_context *c, const char *api, const vr_gather_laws *lawsIn, uint32_t primFirst, uint32_t primCount,
                     uint32_t samples, float cosinePower, uint32_t reflection, uint32_t maxBounces, const float *reflectivity,
-                    float reflectivityScalar, float *out) {
+                    float reflectivityScalar, float *out, const struct vr_gather_energy *energyIn) {
   VR_TRY(paths_refusal(c, api, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity, reflectivityScalar, out));
   GatherLawSet laws;
   VR_TRY(gather_laws_refusal(c, api, lawsIn, cosinePower, samples, laws));
+  GatherEnergySet energy;
+  VR_TRY(gather_energy_refusal(c, api, energyIn, laws.wbound, samples, energy));
   VR_TRY(resident_scene_refusal(c, api, "gather from"));
   VR_HIP(c, hipSetDevice(c->device));
   bool waited = false;
@@ -136,7 +143,7 @@ int paths_call_host(vr_context *c, const char *api, const vr_gather_laws *lawsIn
   if (primCount == 0)
     return VR_OK;
   VR_TRY(map_grow(c, c->dGatherOut, primCount, waited));
-  VR_TRY(paths_on_device(c, laws, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity != nullptr,
+  VR_TRY(paths_on_device(c, laws, energy, primFirst, primCount, samples, cosinePower, reflection, maxBounces, reflectivity != nullptr,
                          reflectivityScalar, c->dGatherOut.p));
   VR_HIP(c, hipMemcpyAsync(out, c->dGatherOut.p, (size_t)primCount * 4, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
@@ -146,12 +153,14 @@ int paths_call_host(vr_context *c, const char *api, const vr_gather_laws *lawsIn
 int paths_call_debug(vr_context *c, const char *api, const vr_gather_laws *lawsIn, uint32_t prim, uint32_t sample, float cosinePower,
                      uint32_t reflection, uint32_t maxBounces, const float *reflectivity, float reflectivityScalar,
                      uint32_t maxVertices, uint32_t *vertexIds, float *vertexData, uint32_t *numVertices, uint32_t *end,
-                     float *finalDirection3, float *throughput, float *weight) {
+                     float *finalDirection3, float *throughput, float *weight, const struct vr_gather_energy *energyIn, float *energyOut4) {
   const std::string name = api;
   // (the checks of the call itself for a range of one primitive and one sample; c: a non-null `out`)
   VR_TRY(paths_refusal(c, api, prim, 1, 1, cosinePower, reflection, maxBounces, reflectivity, reflectivityScalar, c));
   GatherLawSet laws;
   VR_TRY(gather_laws_refusal(c, api, lawsIn, cosinePower, 1, laws));
+  GatherEnergySet energy;
+  VR_TRY(gather_energy_refusal(c, api, energyIn, laws.wbound, 1, energy));
   if (maxVertices && (!vertexIds || !vertexData))
     return fail(c, VR_E_INVALID, (name + ": vertexIds and vertexData must not be null with maxVertices > 0").c_str());
   if (maxVertices > VR_GATHER_MAX_BOUNCES + 2u)
@@ -168,19 +177,27 @@ int paths_call_debug(vr_context *c, const char *api, const vr_gather_laws *lawsI
     VR_TRY(paths_table(c, api, c->dPathIn.p));
   }
   const size_t rows = (size_t)maxVertices * GATHER_PATH_ROW;
-  VR_TRY(map_grow(c, c->dGatherOut, rows + GATHER_PATH_TAIL, waited));
+  VR_TRY(map_grow(c, c->dGatherOut, rows + GATHER_PATH_TAIL + 4u, waited)); // (4: the energy path's {u, E0, P, e})
   VR_TRY(map_grow(c, c->dGatherAcc, 1, waited));
   TraceParams p;
   GatherArgs a;
   VR_TRY(paths_args(c, waited, p, a, laws, prim, 1, 1, cosinePower, reflection, maxBounces, reflectivity != nullptr,
                     reflectivityScalar));
+  GatherEnergyArgs ea;
+  VR_TRY(gather_energy_args(c, waited, energy, ea));
   if (c->walkStackWaves == 0)
     return fail(c, VR_E_STATE, (name + ": the walk stack has no slab").c_str());
   a.acc = c->dGatherAcc.p; // (the kernel is the gather's: the one sample's sum goes where a gather's would)
   VR_HIP(c, hipMemsetAsync(c->dGatherAcc.p, 0, 8, c->stream));
   float *d = c->dGatherOut.p;
-  VR_HIP(c, launch_debug_gather_path(p, c->geo.geo, c->geo.D, a, sample, maxVertices, d, d + rows, c->stream));
-  std::vector<float> host(rows + GATHER_PATH_TAIL);
+  if (energy.any) {
+    ea.a = a;
+    VR_HIP(c, launch_debug_gather_energy_path(p, c->geo.geo, c->geo.D, ea, sample, maxVertices, d, d + rows, d + rows + GATHER_PATH_TAIL,
+                                              c->stream));
+  } else {
+    VR_HIP(c, launch_debug_gather_path(p, c->geo.geo, c->geo.D, a, sample, maxVertices, d, d + rows, c->stream));
+  }
+  std::vector<float> host(rows + GATHER_PATH_TAIL + 4u);
   VR_HIP(c, hipMemcpyAsync(host.data(), d, host.size() * 4, hipMemcpyDeviceToHost, c->stream));
   VR_HIP(c, hipStreamSynchronize(c->stream));
   auto word = [](float f) {
@@ -205,6 +222,8 @@ int paths_call_debug(vr_context *c, const char *api, const vr_gather_laws *lawsI
     *throughput = tail[5];
   if (weight)
     *weight = tail[6];
+  if (energy.any && energyOut4)
+    std::memcpy(energyOut4, tail + GATHER_PATH_TAIL, 16);
   return VR_OK;
 }
 

@@ -259,6 +259,28 @@ struct GatherSpeciesDecideArgs {
   float rel[GATHER_SPECIES_MAX], abs[GATHER_SPECIES_MAX];
 };
 hipError_t launch_gather_species_decide(const GatherSpeciesDecideArgs &d, hipStream_t st);
+// an ion's energy carried along the paths of an angular gather (vr_gather_energy.hip: gather_energy_kernel;
+// vr_gather_energy.cpp).  a: the arguments of the angular call — a path gather's, with a.laws / a.lawCount / a.gL where it
+// has angular laws (a.laws == nullptr: none).  tables: 3 x GATHER_LAW_MAX floats of device memory — the energy yield, the
+// source's quantiles, the retention law (vr_gather.hpp: GATHER_ENERGY_*) — of which table w has count[w] entries; the
+// yield is always there, 0 for either of the others: a monoenergetic source of sourceEnergy, no loss.  zeros: the cut's
+// Z0, the yield's leading zeros, or 0 where the cut is off or has nothing to cut (Z0 < 2)
+struct GatherEnergyArgs {
+  GatherArgs a;
+  const float *tables;
+  uint32_t count[3];
+  float energyMax, sourceEnergy;
+  uint32_t zeros;
+  float *pathEnergy; // (the one-path walk) 4 floats: u, E0, P, e
+};
+// as launch_gather_samples for a path gather (a.paths == 1, no recording, no emission table), fixed K or a.stat
+hipError_t launch_gather_energy(const TraceParams &p, int geo, int D, const GatherEnergyArgs &ea, unsigned slabs, hipStream_t st);
+// hostTable: 3 x 256 HOST floats (GatherEnergyArgs::tables' layout), copied at the call; dst: that many floats of device memory
+hipError_t launch_gather_energy_tables(const float *hostTable, float *dst, hipStream_t st);
+// ONE path of vr_gather_energy (vr_debug_gather_energy_path): launch_debug_gather_path's arguments and outputs, and
+// energy4: {u, E0, P, e} of the path
+hipError_t launch_debug_gather_energy_path(const TraceParams &p, int geo, int D, const GatherEnergyArgs &ea, unsigned sample,
+                                           unsigned maxVertices, float *vertices, float *tail, float *energy4, hipStream_t st);
 // the radiosity solve over a recorded link table (vr_radiosity.hip; vr_radiosity.hpp has the arithmetic and the table's
 // index).  Every pointer is device memory; everything but rho / out of the rho and unpermute launches is in LEAF order
 struct RadiosityArgs {

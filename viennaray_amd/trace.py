@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from . import capi
-from .capi import VrError, TraceInfoPOD, ParticlePOD, GatherSpecPOD, GatherAdaptiveInfoPOD, GatherLawsPOD
+from .capi import VrError, TraceInfoPOD, ParticlePOD, GatherSpecPOD, GatherAdaptiveInfoPOD, GatherLawsPOD, GatherEnergyPOD
 
 
 class BoundaryCondition(enum.IntEnum):  # rayBoundary.hpp:10-14
@@ -47,6 +47,16 @@ class GatherMode(enum.IntEnum):  # Trace.gatherFlux (VR_GATHER_*, include/vienna
 class GatherReflection(enum.IntEnum):  # Trace.gatherPaths (VR_GATHER_REFLECT_*, include/viennaray_amd.h)
     SPECULAR = 0  # a vertex reflects the path into the mirror direction
     DIFFUSE = 1   # a vertex re-emits it by the cosine law about the normal hit
+
+
+class GatherEnd(enum.IntEnum):  # how a gathered path ended (VR_GATHER_END_*, include/viennaray_amd.h): debugGather*Path's "end"
+    MISS = 0      # reached the source plane
+    IGNORED = 1   # left through an IGNORE wall
+    WALL = 2      # stopped on a wall: the boundary-hit budget is spent
+    BACK = 4      # hit a primitive on its back side
+    BOUNCES = 5   # a front-side hit with maxBounces bounces made
+    ABSORBED = 6  # a front-side hit that took the throughput to 0
+    ENERGY = 7    # gatherEnergy's cut: the arrival energy entered the zero region of energyYield
 
 
 class TracingDataMergeEnum(enum.IntEnum):  # rayTracingData.hpp:10-14
@@ -1040,13 +1050,16 @@ class Trace:
             spec.reflectivity = table.data_ptr() if device else table.ctypes.data
         return spec, (not device and (table is not None or numpy)), table
 
-    def _gatherSums(self, spec, host, primFirst, primCount, chunkFirst, chunks, budget, laws=None):
-        """laws: None (vr_gather_sums*) or a GatherLawsPOD (vr_gather_angular_sums*)"""
+    def _gatherSums(self, spec, host, primFirst, primCount, chunkFirst, chunks, budget, laws=None, energy=None):
+        """laws: None (vr_gather_sums*) or a GatherLawsPOD (vr_gather_angular_sums*); with it energy: None or a
+        GatherEnergyPOD (vr_gather_energy_sums*)"""
         head = (self._h, C.byref(spec)) + ((C.byref(laws),) if laws is not None else ())
+        head += (C.byref(energy),) if energy is not None else ()
         if host:
             s1, s2 = np.empty(primCount, dtype=np.int64), np.empty(primCount, dtype=np.int64)
             i64 = C.POINTER(C.c_int64)
             call = self._L.vr_gather_sums if laws is None else self._L.vr_gather_angular_sums
+            call = call if energy is None else self._L.vr_gather_energy_sums
             self._check(call(*head, primFirst, primCount, int(chunkFirst), int(chunks), int(budget), s1.ctypes.data_as(i64),
                              s2.ctypes.data_as(i64)))
             return s1, s2
@@ -1054,19 +1067,23 @@ class Trace:
         dev = torch.device("cuda", self._device)
         s1, s2 = torch.empty(primCount, dtype=torch.int64, device=dev), torch.empty(primCount, dtype=torch.int64, device=dev)
         call = self._L.vr_gather_sums_device if laws is None else self._L.vr_gather_angular_sums_device
+        call = call if energy is None else self._L.vr_gather_energy_sums_device
         self._check(call(*head, primFirst, primCount, int(chunkFirst), int(chunks), int(budget), C.c_void_p(s1.data_ptr()),
                          C.c_void_p(s2.data_ptr()), C.c_void_p(self._torch_stream())))
         return s1, s2
 
     def _gatherAdaptive(self, spec, host, primFirst, primCount, target, absTarget, minSamples, maxSamples, returnInfo,
-                        laws=None):
-        """laws: None (vr_gather_adaptive*) or a GatherLawsPOD (vr_gather_angular_adaptive*)"""
+                        laws=None, energy=None):
+        """laws: None (vr_gather_adaptive*) or a GatherLawsPOD (vr_gather_angular_adaptive*); with it energy: None or a
+        GatherEnergyPOD (vr_gather_energy_adaptive*)"""
         info = GatherAdaptiveInfoPOD()
         head = (self._h, C.byref(spec)) + ((C.byref(laws),) if laws is not None else ())
+        head += (C.byref(energy),) if energy is not None else ()
         if host:
             flux, err = np.empty(primCount, dtype=np.float32), np.empty(primCount, dtype=np.float32)
             used = np.empty(primCount, dtype=np.uint32)
             call = self._L.vr_gather_adaptive if laws is None else self._L.vr_gather_angular_adaptive
+            call = call if energy is None else self._L.vr_gather_energy_adaptive
             self._check(call(*head, primFirst, primCount, int(minSamples), int(maxSamples), float(target), float(absTarget),
                              _fptr(flux), _fptr(err), used.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info)))
         else:
@@ -1075,6 +1092,7 @@ class Trace:
             flux, err = torch.empty(primCount, dtype=torch.float32, device=dev), torch.empty(primCount, dtype=torch.float32, device=dev)
             store = torch.empty(primCount, dtype=torch.int32, device=dev)  # (the uint32 counts, at most 2^22)
             call = self._L.vr_gather_adaptive_device if laws is None else self._L.vr_gather_angular_adaptive_device
+            call = call if energy is None else self._L.vr_gather_energy_adaptive_device
             self._check(call(*head, primFirst, primCount, int(minSamples), int(maxSamples), float(target), float(absTarget),
                              C.c_void_p(flux.data_ptr()), C.c_void_p(err.data_ptr()), C.c_void_p(store.data_ptr()), C.byref(info),
                              C.c_void_p(self._torch_stream())))
@@ -1222,6 +1240,136 @@ class Trace:
         return {"ids": ids[:v].astype(np.int64), "points": data[:v, 0], "arriving": data[:v, 1], "normals": data[:v, 2],
                 "leaving": data[:v, 3], "numVertices": int(count.value), "end": int(end.value), "direction": final,
                 "throughput": np.float32(T.value), "weight": np.float32(w.value)}
+
+    # --- energy gather: an ion's energy lost along a path, a yield by the arrival energy (vr_gather_energy*) ----------
+    def _energyTables(self, name, energyYield, energyMax, sourceEnergy, sourceQuantiles, retentionLaw, energyCut):
+        """(GatherEnergyPOD, the host arrays it points to): energyYield 2 .. 256 values over e = E / energyMax in [0, 1];
+        sourceQuantiles None or 2 .. 256 values of the source's inverse CDF over u in [0, 1]; retentionLaw None or 2 .. 256
+        values over a cosine in [0, 1].  Sequences, numpy arrays or tensors, always handed over as HOST arrays"""
+        if energyYield is None or energyMax is None:
+            raise ValueError("%s: energyYield and energyMax are required" % name)
+        if sourceEnergy is not None and sourceQuantiles is not None:
+            raise ValueError("%s: give at most one of sourceEnergy and sourceQuantiles" % name)
+        if sourceEnergy is None and sourceQuantiles is None:
+            raise ValueError("%s: give sourceEnergy (a monoenergetic source) or sourceQuantiles" % name)
+        pod, keep = GatherEnergyPOD(), []
+        for field, count, law in (("energyYield", "energyYieldCount", energyYield),
+                                  ("sourceQuantiles", "sourceQuantilesCount", sourceQuantiles),
+                                  ("retentionLaw", "retentionCount", retentionLaw)):
+            if law is None:
+                continue
+            if hasattr(law, "data_ptr"):
+                law = law.detach().cpu().numpy()
+            t = np.ascontiguousarray(law, dtype=np.float32).reshape(-1)
+            keep.append(t)
+            setattr(pod, field, t.ctypes.data)
+            setattr(pod, count, t.size)
+        pod.energyMax = float(energyMax)
+        pod.sourceEnergy = float(sourceEnergy) if sourceEnergy is not None else 0.0
+        pod.energyCut = int(energyCut)
+        return pod, keep
+
+    def gatherEnergy(self, samples, energyYield=None, energyMax=None, sourceEnergy=None, sourceQuantiles=None, retentionLaw=None,
+                     energyCut=True, sourceLaw=None, reflectivityLaw=None, yieldLaw=None, sticking=None, reflectivity=None,
+                     reflection=GatherReflection.SPECULAR, maxBounces=64, primFirst=0, primCount=None, numpy=False,
+                     cosinePower=1.0, stickingLaw=None):
+        """gatherAngular with the ion's ENERGY carried along every path: the ion leaves the source with E0, keeps the share
+        retentionLaw(mu) of its energy at every reflection, and the path's weight takes one more multiply, by
+        energyYield(E / energyMax) of the energy it arrives with.
+          energyYield      Y_E(e), 2 .. 256 values over e = E / energyMax in [0, 1] (sqrt(E) - sqrt(E_th), 0 below the
+                           threshold, tabulated); required, as energyMax.
+          sourceEnergy     the one energy of a monoenergetic source, or
+          sourceQuantiles  the source's inverse CDF Q(u), 2 .. 256 values over u in [0, 1]: E0 = Q(u), u a counter draw
+                           of (seed, primitive, sample).
+          retentionLaw     eps(mu) in [0, 1] by mu = normal . leaving direction, reflectivityLaw's mu; None: no loss.
+          energyCut        end a path (GatherEnd.ENERGY) as soon as its energy has entered the leading zeros of
+                           energyYield: it can only weigh 0.  No bit of the result depends on it.
+        Everything else as gatherAngular.  With an all-ones energyYield the result has gatherAngular's bits
+        (vr_gather_energy*; include/viennaray_amd.h has the definition)."""
+        _, primFirst, primCount = self._gatherRange("gatherEnergy", primFirst, primCount, samples, maxBounces)
+        spec, host, keep = self._pathsSpec("gatherEnergy", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
+        laws, keepLaws = self._angularLaws("gatherEnergy", sourceLaw, reflectivityLaw, yieldLaw, stickingLaw)
+        energy, keepEnergy = self._energyTables("gatherEnergy", energyYield, energyMax, sourceEnergy, sourceQuantiles, retentionLaw,
+                                                energyCut)
+        if host:
+            out = np.empty(primCount, dtype=np.float32)
+            self._check(self._L.vr_gather_energy(self._h, C.byref(spec), C.byref(laws), C.byref(energy), primFirst, primCount,
+                                                 int(samples), _fptr(out)))
+            return out
+        import torch
+        out = torch.empty(primCount, dtype=torch.float32, device=torch.device("cuda", self._device))
+        self._check(self._L.vr_gather_energy_device(self._h, C.byref(spec), C.byref(laws), C.byref(energy), primFirst, primCount,
+                                                    int(samples), C.c_void_p(out.data_ptr()), C.c_void_p(self._torch_stream())))
+        return out
+
+    def gatherEnergyAdaptive(self, target, energyYield=None, energyMax=None, sourceEnergy=None, sourceQuantiles=None,
+                             retentionLaw=None, energyCut=True, sourceLaw=None, reflectivityLaw=None, yieldLaw=None, sticking=None,
+                             reflectivity=None, reflection=GatherReflection.SPECULAR, maxBounces=64, minSamples=64,
+                             maxSamples=4096, absTarget=0.0, primFirst=0, primCount=None, returnInfo=False, numpy=False,
+                             cosinePower=1.0, stickingLaw=None):
+        """gatherEnergy to a target error, as gatherAngularAdaptive: (flux, stdErr, samples), plus the info dict when
+        asked; flux[i] has the bits of gatherEnergy(samples[i]) (vr_gather_energy_adaptive*)."""
+        _, primFirst, primCount = self._gatherRange("gatherEnergyAdaptive", primFirst, primCount, minSamples, maxSamples, maxBounces)
+        spec, host, keep = self._pathsSpec("gatherEnergyAdaptive", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
+        laws, keepLaws = self._angularLaws("gatherEnergyAdaptive", sourceLaw, reflectivityLaw, yieldLaw, stickingLaw)
+        energy, keepEnergy = self._energyTables("gatherEnergyAdaptive", energyYield, energyMax, sourceEnergy, sourceQuantiles,
+                                                retentionLaw, energyCut)
+        return self._gatherAdaptive(spec, host, primFirst, primCount, target, absTarget, minSamples, maxSamples, returnInfo, laws,
+                                    energy)
+
+    def gatherEnergySums(self, chunkFirst, chunks, budget, energyYield=None, energyMax=None, sourceEnergy=None,
+                         sourceQuantiles=None, retentionLaw=None, energyCut=True, sourceLaw=None, reflectivityLaw=None,
+                         yieldLaw=None, sticking=None, reflectivity=None, reflection=GatherReflection.SPECULAR, maxBounces=64,
+                         primFirst=0, primCount=None, numpy=False, cosinePower=1.0, stickingLaw=None):
+        """(sum, sumSq) as gatherAngularSums, of gatherEnergy's samples (vr_gather_energy_sums*)"""
+        _, primFirst, primCount = self._gatherRange("gatherEnergySums", primFirst, primCount, chunkFirst, chunks, budget, maxBounces)
+        spec, host, keep = self._pathsSpec("gatherEnergySums", sticking, reflectivity, reflection, maxBounces, cosinePower, numpy)
+        laws, keepLaws = self._angularLaws("gatherEnergySums", sourceLaw, reflectivityLaw, yieldLaw, stickingLaw)
+        energy, keepEnergy = self._energyTables("gatherEnergySums", energyYield, energyMax, sourceEnergy, sourceQuantiles,
+                                                retentionLaw, energyCut)
+        return self._gatherSums(spec, host, primFirst, primCount, chunkFirst, chunks, budget, laws, energy)
+
+    _ENERGY_KEYS = {"energyYield", "energyMax", "sourceEnergy", "sourceQuantiles", "retentionLaw", "energyCut"}
+
+    def debugGatherEnergyPath(self, prim, sample, energy, laws=None, sticking=None, reflectivity=None,
+                              reflection=GatherReflection.SPECULAR, maxBounces=64, cosinePower=1.0, maxVertices=None):
+        """ONE path of gatherEnergy, as debugGatherAngularPath's dict plus "u", "E0", "P" and "e": the energy draw, the
+        energy at the source, the product of the retentions and the arrival energy in table units.  energy: a dict with
+        gatherEnergy's keywords energyYield, energyMax, sourceEnergy | sourceQuantiles, retentionLaw, energyCut; laws as
+        debugGatherAngularPath.  "end" is a GatherEnd; a sample the cut ended before its walk has numVertices == 1
+        (vr_debug_gather_energy_path)."""
+        _, scalar, table = self._pathReflectivity("debugGatherEnergyPath", sticking, reflectivity, host_only=True)
+        spec = GatherSpecPOD(cosinePower=float(cosinePower), mode=int(GatherMode.NORMAL), paths=1, reflection=int(reflection),
+                             maxBounces=int(maxBounces), reflectivityScalar=scalar)
+        if table is not None:
+            spec.reflectivity = table.ctypes.data
+        laws, energy = dict(laws or {}), dict(energy or {})
+        unknown = set(laws) - {"sourceLaw", "reflectivityLaw", "stickingLaw", "yieldLaw"}
+        if unknown:
+            raise ValueError("debugGatherEnergyPath: unknown laws %s" % sorted(unknown))
+        unknown = set(energy) - self._ENERGY_KEYS
+        if unknown:
+            raise ValueError("debugGatherEnergyPath: unknown energy keys %s" % sorted(unknown))
+        pod, keepLaws = self._angularLaws("debugGatherEnergyPath", laws.get("sourceLaw"), laws.get("reflectivityLaw"),
+                                          laws.get("yieldLaw"), laws.get("stickingLaw"))
+        epod, keepEnergy = self._energyTables("debugGatherEnergyPath", energy.get("energyYield"), energy.get("energyMax"),
+                                              energy.get("sourceEnergy"), energy.get("sourceQuantiles"), energy.get("retentionLaw"),
+                                              energy.get("energyCut", True))
+        cap = int(maxBounces) + 2 if maxVertices is None else int(maxVertices)
+        ids = np.zeros(cap, dtype=np.uint32)
+        data = np.full((cap, 4, 3), np.nan, dtype=np.float32)
+        count, end = C.c_uint32(0), C.c_uint32(0)
+        final, e4 = np.empty(3, np.float32), np.zeros(4, np.float32)
+        T, w = C.c_float(0.0), C.c_float(0.0)
+        self._check(self._L.vr_debug_gather_energy_path(
+            self._h, C.byref(spec), C.byref(pod), C.byref(epod), int(prim), int(sample), cap,
+            ids.ctypes.data_as(C.POINTER(C.c_uint32)), _fptr(data), C.byref(count), C.byref(end), _fptr(final), C.byref(T),
+            C.byref(w), _fptr(e4)))
+        v = min(cap, int(count.value))
+        return {"ids": ids[:v].astype(np.int64), "points": data[:v, 0], "arriving": data[:v, 1], "normals": data[:v, 2],
+                "leaving": data[:v, 3], "numVertices": int(count.value), "end": int(end.value), "direction": final,
+                "throughput": np.float32(T.value), "weight": np.float32(w.value), "u": e4[0], "E0": e4[1], "P": e4[2],
+                "e": e4[3]}
 
     # --- species gather: several species weighed along one set of traced paths (vr_gather_species*) ------------------
     _SPECIES_KEYS = {"sticking", "reflectivity", "cosinePower", "sourceLaw", "reflectivityLaw", "stickingLaw", "yieldLaw"}
