@@ -37,6 +37,14 @@ import sys
 from collections import defaultdict
 
 KERNELS = ("trace_kernel", "gen_kernel")
+# the kernels of a phase by name: the tile-bucket pipeline's generator and its tile kernel (vr_tile_buckets.hpp) belong to
+# the generator and the trace phase ("tile_trace_kernel" holds "trace_kernel")
+ALSO = {"gen_kernel": ("gen_tile_kernel",)}
+
+
+def is_kind(kind, kernel_name):
+    return kind in kernel_name or any(a in kernel_name for a in ALSO.get(kind, ()))
+
 PASSES = [
     ("fetch", ["FETCH_SIZE"]),
     ("write", ["WRITE_SIZE"]),
@@ -147,7 +155,7 @@ def main():
         per = {kk: defaultdict(dict) for kk in KERNELS}
         for r in csv.DictReader(open(f)):
             for kk in KERNELS:
-                if kk in r.get("Kernel_Name", ""):
+                if is_kind(kk, r.get("Kernel_Name", "")):
                     per[kk][short(r["Kernel_Name"])][r["Dispatch_Id"]] = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
         for kk in KERNELS:
             for nm, disp in per[kk].items():
@@ -159,7 +167,7 @@ def main():
         per = {kk: defaultdict(lambda: defaultdict(lambda: defaultdict(float))) for kk in KERNELS}
         for r in csv.DictReader(open(f)):
             for kk in KERNELS:
-                if kk in r.get("Kernel_Name", ""):
+                if is_kind(kk, r.get("Kernel_Name", "")):
                     per[kk][short(r["Kernel_Name"])][r["Counter_Name"]][r["Dispatch_Id"]] += float(r.get("Counter_Value", 0))
         for kk in KERNELS:
             for nm, ctrs in per[kk].items():

@@ -9,6 +9,7 @@
 
 #include "vr_context.hpp"
 #include "vr_frame.hpp"
+#include "vr_lattice_tiles.hpp"
 
 namespace vr {
 
@@ -47,8 +48,16 @@ TraceParams launch_params(const vr_context *c, const ParticleLaunch &L) {
   return p;
 }
 
+// Tile buckets: the rays of a batch that the lattice-lanes kernel is expected to trace at most — those that cross a wall or
+// fall through a hole, an eighth of the batch — for the sizes of its grid and of its queue's spans (more of them are traced
+// all the same: the grid is persistent, the spans only deal the work out)
+static uint32_t tile_bin_rays(uint32_t count) { return (uint32_t)std::min<uint64_t>(count, std::max<uint64_t>(4096, count / 8)); }
+
 // the batch's own fields of a particle's launch parameters: sort bins, spans per queue grab, queues
-static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t first, uint32_t count) {
+// tiles: a tile-bucket launch (vr_tile_buckets.hpp) — no sort bins, the rays its tile kernel does not finish lie in the
+// overflow region; binRays: how many of them the queue's spans and the grid are sized for
+static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t first, uint32_t count, bool tiles = false) {
+  const uint32_t binRays = tiles ? tile_bin_rays(count) : count;
   const Knobs &K = c->knobs;
   TraceParams p = launch_params(c, L);
   p.batchFirst = first;
@@ -67,7 +76,7 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   p.numBins = nbBatch;
   // a surface source has no sort bins: its records lie in index order in the overflow region (gen_surface_kernel),
   // which the trace kernel reads as virtual bins of binCap rays
-  const bool unbinned = L.gen == GEN_SURFACE;
+  const bool unbinned = L.gen == GEN_SURFACE || tiles;
   if (L.genWeights) // the batch's start weights, addressed by GLOBAL ray index like a host source's (gen_surface_kernel / a source model's generator writes them)
     p.hostWeights = c->dSurfRayWeights.p - first;
   if (unbinned)
@@ -79,7 +88,7 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   {
     // bins per queue grab: ~1024 rays for big batches, but never so many that a small
     // batch (a short last one, a small launch) is handed to a few waves only
-    const uint64_t waves = std::min<uint64_t>(L.grid, ((uint64_t)count + 255) / 256) * (VR_BLOCK / 64);
+    const uint64_t waves = std::min<uint64_t>(L.grid, ((uint64_t)binRays + 255) / 256) * (VR_BLOCK / 64);
     // (a grab of the queue costs two dependent trips to memory: the packet kernels want long spans; the
     //  general kernel's rounds are long and its bounce chains uneven: shorter spans balance its tail)
     // (a round that straddles two spans mixes rays of two places: its packet query gives up — every failed query of a flat
@@ -88,7 +97,7 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
     uint64_t spanBins = (uint64_t)mode_traits(L.traceMode).spanBins; // (16 general, 64 general flat-scene kernels, 32 the others)
     if (K.spanBins)
       spanBins = *K.spanBins;
-    const uint64_t binsToDeal = unbinned ? ((uint64_t)count + p.binCap - 1) / p.binCap : nbBatch;
+    const uint64_t binsToDeal = unbinned ? ((uint64_t)binRays + p.binCap - 1) / p.binCap : nbBatch;
     p.chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spanBins, binsToDeal / std::max<uint64_t>(waves * 2, 1)));
   }
   // One queue per XCD pays where neighbouring rounds share primitive records that do not fit an XCD's 4 MiB L2 and the
@@ -103,6 +112,20 @@ static TraceParams batch_params(vr_context *c, const ParticleLaunch &L, uint64_t
   return p;
 }
 
+// Can two launches share a generator pass?  (A stateful model's generator runs its own init: a pass of its own.  relief,
+// binAlign: the generator's bins are laid out differently.)
+static bool same_gen_group(const ParticleLaunch &a, const ParticleLaunch &b) {
+  return !a.userGen && !b.userGen && a.absorb == b.absorb && a.params.ee == b.params.ee && a.params.eeGrid == b.params.eeGrid &&
+         a.relief == b.relief && a.binAlign == b.binAlign;
+}
+// ... and is this launch alone in its group?  (The tile buckets serve one particle's kernel: run_batch.)
+static bool tile_group_alone(const vr_context *c, const ParticleLaunch &L) {
+  for (const ParticleLaunch &o : c->launches)
+    if (&o != &L && same_gen_group(o, L))
+      return false;
+  return true;
+}
+
 // One batch of the ray stream: ONE generator pass straight into the sort bins, then the trace kernel of every
 // particle of `group` over the same records (particles of a group share source distribution and record format).
 static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &group, uint64_t first, uint32_t count,
@@ -110,7 +133,19 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
   int rc = VR_OK;
   const ParticleLaunch &G = *group[0];
   const bool keepRng = !G.absorb; // records carry the RNG cursors
-  const TraceParams pg = batch_params(c, G, first, count);
+  // Tile buckets (vr_tile_buckets.hpp): a launch that is alone in its group.  It has no sort bins: the rays that are not
+  // simple lie in the overflow region, the buckets behind it.  memsets, tile generator, tile kernel, then the
+  // lattice-lanes kernel over the overflow region.
+  const bool tiles = G.tileBuckets && group.size() == 1;
+  const uint32_t binRays = tiles ? tile_bin_rays(count) : count;
+  const TraceParams pg = batch_params(c, G, first, count, tiles);
+  TileParams tp = G.tile;
+  if (tiles) {
+    tp.tileCount = c->dTileCount.p;
+    tp.slotBase = pg.numBins * pg.binCap + pg.ovCap;
+    tp.tileCap = c->knobs.tileCap.value_or(lattice_tile_capacity(count, G.tileSide, G.tileSrcArea));
+    VR_HIP(c, hipMemsetAsync(tp.tileCount, 0, (size_t)tp.numTiles * 4, c->stream));
+  }
   VR_HIP(c, hipMemsetAsync(pg.binCount, 0, (pg.reliefCoarse ? (size_t)pg.looseCntBase + pg.looseNumBins + 1 : (size_t)pg.numBins + 1) * 4, c->stream));
   hipEvent_t g0 = event_at(c->evG, 2 * genNo, c, rc), g1 = event_at(c->evG, 2 * genNo + 1, c, rc);
   if (rc != VR_OK)
@@ -122,6 +157,8 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
     void *args[] = {&pk, &sc}; // (gen_state_kernel takes the first alone)
     const unsigned grid = std::min<unsigned>((count + VR_BLOCK - 1) / VR_BLOCK, (unsigned)c->numCUs * 8u);
     VR_HIP(c, hipModuleLaunchKernel(G.userGen, grid, 1, 1, VR_BLOCK, 1, 1, 0, c->stream, args, nullptr));
+  } else if (tiles) {
+    VR_HIP(c, launch_gen_tiles(pg, tp, (unsigned)c->numCUs * (unsigned)std::max(1, c->tileGenBlocks), c->stream));
   } else {
     VR_HIP(c, launch_gen(pg, G.gen, c->geo.D, keepRng, (unsigned)c->numCUs * 8u, c->stream));
   }
@@ -143,7 +180,9 @@ static int run_batch(vr_context *c, const std::vector<const ParticleLaunch *> &g
       return rc;
     VR_HIP(c, hipEventRecord(k0, c->stream));
     // a small batch does not need the whole persistent grid: one wave per 64 rays is plenty
-    const unsigned gridBatch = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(L.grid, ((uint64_t)count + 255) / 256));
+    const unsigned gridBatch = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(L.grid, ((uint64_t)binRays + 255) / 256));
+    if (tiles) // (the buckets first: the rays it hands on join the overflow region the kernel below reads)
+      VR_HIP(c, launch_tile_trace(p, tp, c->stream));
     if (tight && L.userKernel) {
       TraceParams pk = p;
       void *args[] = {&pk};
@@ -203,9 +242,8 @@ int vr_apply_launch(vr_context *c) {
   std::vector<std::vector<const ParticleLaunch *>> groups;
   for (const ParticleLaunch &L : c->launches) {
     bool placed = false;
-    for (auto &g : groups) // (a stateful model's generator runs its own init: a generator pass of its own)
-      if (!g[0]->userGen && !L.userGen && g[0]->absorb == L.absorb && g[0]->params.ee == L.params.ee &&
-          g[0]->params.eeGrid == L.params.eeGrid && g[0]->relief == L.relief && g[0]->binAlign == L.binAlign) { // (relief, binAlign: the generator's bins are laid out differently)
+    for (auto &g : groups)
+      if (same_gen_group(*g[0], L)) {
         g.push_back(&L);
         placed = true;
         break;
@@ -389,7 +427,17 @@ int vr_apply_finish(vr_context *c) {
                    (int)L.latticeLanesScene, (int)c->knobs.latticeLaneTests, (int)kernel.latticeLanes, q);
       // (... in one word: the mode the launch reports and the kernel of the table it ran)
       std::fprintf(stderr, "[vr] kernel: traceMode %d, kernel mode %d, particle %zu\n", L.traceMode, L.kernelMode, q);
+      // (the tile buckets: whether this launch ran them — it also has to be alone in its generator group — and the share
+      //  of its rays that the lattice-lanes kernel traced instead: those the generator found not simple or found no room
+      //  for, and those the tile kernel handed on)
+      const bool ran = L.tileBuckets && tile_group_alone(c, L);
+      const double rays = (double)std::max<uint64_t>(1, c->rayEndLaunch - c->rayFirstLaunch);
+      std::fprintf(stderr, "[vr] tile buckets: VR_TILE_BUCKETS %d, launch %d, tiles %u (%d x %d of %d cells a side), slices %u, "
+                           "other rays %.6f, handed on %.6f, particle %zu\n",
+                   (int)c->knobs.tileBuckets, (int)ran, ran ? L.tile.numTiles : 0u, L.tile.tiles1, L.tile.tiles2, ran ? 1 << L.tile.shift : 0,
+                   L.tile.slices, ran ? (double)all[C_BLOCK * q + C_TILE_FALLBACK] / rays : 0., ran ? (double)all[C_BLOCK * q + C_TILE_HANDED] / rays : 0., q);
     }
+
   const uint32_t *spillCount = launch_params(c, current_launch(c)).spillCount;
   if (c->knobs.printLaunches && spillCount) { // (diagnostics: rays the tight general relief kernel handed over)
     uint32_t sp = 0;

@@ -125,6 +125,9 @@ struct Knobs {
   bool planarRound = true;             // VR_PLANAR_ROUND (0: off): ... in its one-point-per-round form (off: the planar kernel as it was)
   bool planarLattice = true;           // VR_PLANAR_LATTICE (0: off): ... with its candidates from the lattice table where the cloud is a lattice cloud (off: the one-point-per-round kernel as it was)
   bool latticeLaneTests = true;        // VR_LATTICE_LANE_TESTS (0: off): ... each lane testing the four disks at the corners of its point's cell where the disks are small against the pitch (off: MODE_ABSORB_FLAT_LATTICE as it was)
+  bool tileBuckets = true;             // VR_TILE_BUCKETS (0: off): a lattice-lanes launch files its simple rays by lattice tile and finishes them against the tile in LDS (vr_tile_buckets.hpp; off: generator and kernel as they were)
+  int tileShift = 6;                   // VR_TILE_SHIFT [1, 6]: ... a tile is 2^shift x 2^shift lattice cells
+  std::optional<uint32_t> tileCap;     // VR_TILE_CAP >= 1: ... record slots per bucket (unset: lattice_tile_capacity)
   std::optional<uint32_t> spanBins;    // VR_SPAN_BINS [1, 64]: sort bins per work-queue grab (unset: by trace mode)
   std::optional<uint32_t> numQueues;   // VR_QUEUES (set): >= VR_QUEUES one queue per XCD, else one (unset: by scene)
   // kernel parameters (TraceParams)
@@ -208,6 +211,12 @@ struct ParticleLaunch {
   // uniform VR_F_UD_*, planar VR_F_PD_*, planarRound VR_F_PR_*, lattice VR_F_PL_*
   int kernelMode = MODE_GENERAL;
   bool latticeLanesScene = false; // (lattice_lanes_rule's verdict on the scene alone, for the VR_PRINT_LAUNCHES line)
+  // The tile buckets of a lattice-lanes launch (vr_prepare.cpp: plan_tile_buckets; vr_tile_buckets.hpp): the launch's
+  // simple rays go through gen_tile_kernel and tile_trace_kernel, the others through the record stream's overflow region and kernelMode's kernel
+  // as before.  tile: everything but the batch's own fields (tileCount, slotBase, tileCap: run_batch)
+  bool tileBuckets = false;
+  TileParams tile{};
+  double tileSide = 0., tileSrcArea = 0.; // a tile's side and the source rectangle's area: lattice_tile_capacity's operands
   bool absorb = false;
   bool recExtra = false; // the records' side array (TraceParams::recExtra)
   hipFunction_t userKernel = nullptr; // the trace kernel of a run-time model (nullptr: a kernel of the library)
@@ -475,6 +484,9 @@ struct vr_context {
   // ray stream (one batch)
   DevBuf<float> dSlotRec, dWalls;
   DevBuf<uint32_t> dBinCount;
+  DevBuf<uint32_t> dTileCount; // tile buckets: VR_TILE_MAX_TILES cursors (TileParams::tileCount)
+  int tileGenBlocks = 0;       // ... resident blocks per CU of the tile generator on this context's device (0: not asked yet)
+  int tileLdsShift = 0;        // ... the largest tile size the tile kernel's dynamic LDS was allowed for on it (0: the default limit)
   size_t slotStride = 0; // record slots of the ray-stream buffer (bins + overflow region)
   uint32_t raysPerBin = 40;
   DevBuf<uint32_t> dScanTmp;

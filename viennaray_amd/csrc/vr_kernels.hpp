@@ -11,6 +11,12 @@ namespace vr {
 hipError_t launch_gen(const TraceParams &p, Generator gen, int D, bool keepRng, unsigned maxBlocks, hipStream_t s);
 hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int mode, unsigned grid,
                         hipStream_t s);
+// the tile-bucket pipeline of a lattice-lanes launch (vr_tile_buckets.hpp): p as launch_gen / launch_trace take it
+// (tile_gen_blocks_per_cu, tile_trace_allow_lds: facts and settings of the CURRENT device, asked for at prepare)
+int tile_gen_blocks_per_cu();
+hipError_t launch_gen_tiles(const TraceParams &p, const TileParams &tp, unsigned maxBlocks, hipStream_t s);
+hipError_t tile_trace_allow_lds(int shift);
+hipError_t launch_tile_trace(const TraceParams &p, const TileParams &tp, hipStream_t s);
 // resident 256-thread blocks per CU of the trace kernel instantiation (occupancy API)
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes);
 // ... the kernels with flux statistics (vr_trace_stats.hip; particle: P_EXT_STATS / P_EXT_FULL_STATS); launch_trace and

@@ -64,6 +64,12 @@ Knobs read_knobs() {
     k.planarLattice = std::atoi(e) != 0;
   if (const char *e = std::getenv("VR_LATTICE_LANE_TESTS"))
     k.latticeLaneTests = std::atoi(e) != 0;
+  if (const char *e = std::getenv("VR_TILE_BUCKETS"))
+    k.tileBuckets = std::atoi(e) != 0;
+  if (const char *e = std::getenv("VR_TILE_SHIFT"))
+    k.tileShift = std::min(6, std::max(1, std::atoi(e)));
+  if (const char *e = std::getenv("VR_TILE_CAP"))
+    k.tileCap = (uint32_t)std::max(1, std::atoi(e));
   if (const char *e = std::getenv("VR_SPAN_BINS"))
     k.spanBins = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
   if (const char *e = std::getenv("VR_QUEUES"))

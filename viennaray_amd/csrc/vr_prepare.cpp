@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "vr_context.hpp"
+#include "vr_lattice_tiles.hpp"
 #include "vr_particles.hpp"
 #include "vr_planar_disks.hpp"
 #include "vr_planar_lattice.hpp"
@@ -685,6 +686,60 @@ static int choose_trace_mode(vr_context *c, const ParticleSpec &sp, ParticleLaun
   return VR_OK;
 }
 
+// The tile buckets of a lattice-lanes launch (vr_tile_buckets.hpp).  Eligible: the launch runs MODE_ABSORB_FLAT_LATTICE_LANES
+// in three dimensions with the plain generator of the library (no tilted direction, no side array, no weights, no relief,
+// no kernel experiment), the lattice fits VR_TILE_MAX_TILES tiles of the knob's size, and the buckets' record slots —
+// behind the overflow region in the same buffer — keep the 32-bit slot index.  Anything else: the
+// launch as it was.  (That the launch is alone in its generator group is seen where the groups are made: run_batch.)
+static int plan_tile_buckets(vr_context *c, ParticleLaunch &L) {
+  const Knobs &K = c->knobs;
+  const TraceParams &p = L.params;
+  L.tileBuckets = false;
+  L.tile = TileParams{};
+  if (!K.tileBuckets || L.kernelMode != MODE_ABSORB_FLAT_LATTICE_LANES || c->geo.D != 3 || L.gen != GEN_RANDOM || L.userGen ||
+      L.userKernel || L.relief || L.recExtra || L.genWeights || p.useBasis || K.debugFlags != 0u || !c->planarLattice)
+    return VR_OK;
+  // The source has to look at the FRONT of the disks: the plane normal to the source axis and its normal against the
+  // rays.  From behind every hit is a back-face hit, which the tile kernel cannot end — it would hand every ray on, a
+  // bucket write, a read and a copy for nothing.  (A ray's component along the source axis is posNeg times a cosine.)
+  {
+    float n[3];
+    std::memcpy(n, c->uniformWords, sizeof(n));
+    if (c->planarAxis != p.rayDir || !(p.posNeg * n[c->planarAxis] < 0.f))
+      return VR_OK;
+  }
+  const int shift = std::min(VR_TILE_SHIFT_MAX, std::max(VR_TILE_SHIFT_MIN, K.tileShift));
+  const int t1 = lattice_tiles_axis(c->latticeN[0], shift), t2 = lattice_tiles_axis(c->latticeN[1], shift);
+  if ((uint64_t)t1 * (uint64_t)t2 > VR_TILE_MAX_TILES)
+    return VR_OK;
+  L.tile.shift = shift;
+  L.tile.tiles1 = t1;
+  L.tile.tiles2 = t2;
+  L.tile.numTiles = (uint32_t)(t1 * t2);
+  L.tileSide = (double)(1 << shift) * (double)c->geo.gridDelta;
+  L.tileSrcArea = ((double)p.hi1 - (double)p.lo1) * ((double)p.hi2 - (double)p.lo2);
+  // workgroups per bucket: about four blocks per CU in all, so that a launch of few tiles still fills the chip
+  // (C2, 256 tiles, trace phase in one call: 2 / 4 / 8 workgroups per bucket 1.58 / 1.63 / 1.99 ms)
+  L.tile.slices = std::min<uint32_t>(64u, std::max<uint32_t>(1u, (4u * (uint32_t)c->numCUs + L.tile.numTiles - 1u) / L.tile.numTiles));
+  const uint64_t rays = std::max<uint64_t>(c->batchCap, std::min<uint64_t>(c->reserveRays, 1ull << 27));
+  const uint64_t cap = K.tileCap.value_or(lattice_tile_capacity(rays, L.tileSide, L.tileSrcArea));
+  const uint64_t slots = (uint64_t)c->slotStride + (uint64_t)L.tile.numTiles * cap;
+  if (slots >= (1ull << 32))
+    return VR_OK;
+  VR_HIP(c, c->dSlotRec.ensure_grow((size_t)slots * 8));
+  VR_HIP(c, c->dTileCount.ensure_grow(VR_TILE_MAX_TILES));
+  // (this context's device: the generator's resident blocks, the tile kernel's dynamic LDS where a tile needs more than
+  //  the default limit — asked once per context and tile size)
+  if (c->tileGenBlocks == 0)
+    c->tileGenBlocks = tile_gen_blocks_per_cu();
+  if (lattice_tile_lds_bytes(shift) > 48u * 1024u && shift > c->tileLdsShift) {
+    VR_HIP(c, tile_trace_allow_lds(shift));
+    c->tileLdsShift = shift;
+  }
+  L.tileBuckets = true;
+  return VR_OK;
+}
+
 // the launch's scratch: walk stacks, RNG slabs, the spill queue (buffers every particle of the apply shares)
 static int size_scratch(vr_context *c, const ParticleLaunch &L, const PrepareState &S) {
   // deep part of the per-lane walk's stack (entries beyond the LDS-resident ones), one slab per resident wave
@@ -1085,6 +1140,7 @@ static int prepare_one(vr_context *c, const ParticleSpec &sp, ParticleLaunch &L)
   VR_TRY(choose_trace_mode(c, sp, L, S)); // (after the ray stream: blocks follow the batch size; the buffers keep the relief layout)
   VR_TRY(size_scratch(c, L, S));
   VR_TRY(fill_trace_params(c, sp, L, S));
+  VR_TRY(plan_tile_buckets(c, L));
   VR_TRY(build_height_field(c, L, S));
   VR_TRY(write_launch_frame(c, L, S));
   c->castParams = L.params; // what vr_cast_rays* reads of this prepare (vr_cast_rays.cpp)

@@ -48,6 +48,7 @@
 #else
 #include "vr_generate.hpp"
 #include "vr_kernel_table.hpp"
+#include "vr_tile_buckets.hpp"
 
 namespace vr {
 
@@ -92,6 +93,50 @@ hipError_t launch_trace(const TraceParams &p, int D, int geo, int particle, int 
   if (particle >= P_EXT_STATS)
     return launch_trace_stats(p, D, geo, particle, mode, grid, s);
   return LibraryKernels::launch(p, D, geo, particle, mode, grid, s);
+}
+
+// The tile-bucket pipeline of a lattice-lanes launch (vr_tile_buckets.hpp): the generator that files the simple rays by
+// lattice tile, and the kernel that finishes them against a tile held in LDS.
+// Block of 256 threads, chunk of 1 024 rays: 29 KB of LDS, five blocks per CU.  (Measured in one call on C2, generator:
+// 256 / 1024 4.16 ms, 512 / 2048 4.31, 256 / 2048 4.73, 1024 / 4096 4.78; with 32-cell tiles 4.49 against 5.32 for 512 /
+// 2048: profiles/tile_buckets_ab.txt.)
+using TileGen = void (*)(const TraceParams, const TileParams);
+constexpr unsigned VR_TILE_GEN_BLOCK = 256, VR_TILE_GEN_CHUNK = 1024;
+static const TileGen tileGen = gen_tile_kernel<VR_TILE_GEN_BLOCK, VR_TILE_GEN_CHUNK>;
+
+// resident blocks per CU of the tile generator on the current device (the caller keeps the answer with its context)
+int tile_gen_blocks_per_cu() {
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, tileGen, VR_TILE_GEN_BLOCK, 0) != hipSuccess || nb < 1)
+    nb = 1;
+  return nb;
+}
+// (the grid is what the chip holds at once: a block more per CU would run as a second wave of blocks behind the first)
+hipError_t launch_gen_tiles(const TraceParams &p, const TileParams &tp, unsigned maxBlocks, hipStream_t s) {
+  if (tp.numTiles == 0u || tp.numTiles > VR_TILE_MAX_TILES || tp.shift < VR_TILE_SHIFT_MIN || tp.shift > VR_TILE_SHIFT_MAX || maxBlocks == 0u)
+    return hipErrorInvalidValue;
+  unsigned grid = (p.batchCount + VR_TILE_GEN_CHUNK - 1) / VR_TILE_GEN_CHUNK;
+  if (grid == 0)
+    return hipSuccess;
+  if (grid > maxBlocks)
+    grid = maxBlocks;
+  hipLaunchKernelGGL(tileGen, dim3(grid), dim3(VR_TILE_GEN_BLOCK), 0, s, p, tp);
+  return hipGetLastError();
+}
+
+// the tile kernel's dynamic LDS for tiles of 2^shift cells a side allowed on the current device (above the default limit
+// it has to be asked for, per device: the caller does so when it prepares a launch)
+hipError_t tile_trace_allow_lds(int shift) {
+  if (shift < VR_TILE_SHIFT_MIN || shift > VR_TILE_SHIFT_MAX)
+    return hipErrorInvalidValue;
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(tile_trace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)lattice_tile_lds_bytes(shift));
+}
+hipError_t launch_tile_trace(const TraceParams &p, const TileParams &tp, hipStream_t s) {
+  if (tp.numTiles == 0u || tp.numTiles > VR_TILE_MAX_TILES || tp.slices == 0u || tp.shift < VR_TILE_SHIFT_MIN || tp.shift > VR_TILE_SHIFT_MAX)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tile_trace_kernel, dim3(tp.numTiles * tp.slices), dim3(VR_TILE_TRACE_BLOCK), lattice_tile_lds_bytes(tp.shift), s, p, tp);
+  return hipGetLastError();
 }
 
 int trace_blocks_per_cu(int D, int geo, int particle, int mode, unsigned smallBytes) {

@@ -435,6 +435,20 @@ enum Generator : int {
                        // launch's SourceCtx as its second argument (ParticleLaunch::userGen, ::source)
 };
 
+// The tile buckets of a lattice-lanes launch (vr_tile_buckets.hpp; vr_lattice_tiles.hpp has the tiles' arithmetic): the
+// second argument of gen_tile_kernel and tile_trace_kernel, by value.  No other kernel takes it: TraceParams stays as it is.
+// Bucket t holds the records of the simple rays whose point lies in tile t: 32-byte records like a sort bin's, in
+// TraceParams::slotRec from slot slotBase + t * tileCap on.
+struct TileParams {
+  uint32_t *tileCount; // [numTiles] rays that asked for a slot of the bucket (above tileCap: the excess went to the overflow region)
+  uint32_t slotBase;   // first record slot of bucket 0: behind the record stream's overflow region
+  uint32_t tileCap;    // record slots per bucket
+  int32_t shift;       // a tile is 2^shift x 2^shift lattice cells
+  int32_t tiles1, tiles2; // tiles per in-plane axis
+  uint32_t numTiles;   // tiles1 * tiles2 <= VR_TILE_MAX_TILES
+  uint32_t slices;     // workgroups of tile_trace_kernel per bucket
+};
+
 // counters[] slots: every particle of an apply has one block of C_BLOCK words (TraceParams::counters points at it)
 enum {
   C_TRACES = 0,
@@ -446,7 +460,9 @@ enum {
   C_TERMINATED,
   C_TIER2,      // diagnostic: rays that needed the full-state RNG
   C_COUNT,
-  C_DIAG = 16,          // -DVR_DIAG: DIAG(k)'s wave-iterations at C_DIAG + 2k, its lane-iterations behind them, k < 16
+  C_TILE_FALLBACK = 9,  // tile buckets: rays the tile generator filed in the overflow region (not simple, or their bucket was full)
+  C_TILE_HANDED = 10,   // ... and rays the tile kernel handed on to the overflow region (no front-side hit)
+  C_DIAG = 16,         // -DVR_DIAG: DIAG(k)'s wave-iterations at C_DIAG + 2k, its lane-iterations behind them, k < 16
   C_CHECK = 48,         // -DVR_SELFCHECK: segments that disagree with the escape-link walk
   C_CHECK_RAY = 50,     // ... the first of them: origin, direction, t of the kernel's hit and of the walk's (8 float words)
   C_CHECK_POS = 58,     // ... its wall positions (kernel's << 32 | walk's)
